@@ -8,13 +8,18 @@ scaling, no collective inside the step; the frozen weights are broadcast once ov
 The timed region OPENS on a sample boundary, so the per-sample precomputation (txt_in, vec path, all 29x1.06M
 modulation rows, RoPE table; reported separately as `precompute_ms`) is inside it; inputs are resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the bf16
-MFMA GEMM with the gate/residual epilogue, timed live with HIP events on its launch stream) and
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs:
+set up, W warm-up steps, K timed steps, the line.  `--full` adds everything else: the board's power / clock during the
+timed steps, `precompute_ms`, `roofline` (dominant kernel = the bf16 MFMA GEMM with the gate/residual epilogue, timed
+live with HIP events on its launch stream), `launch_classes`, `attention_kernel`, the rocprofv3 counter passes and
 `cpu_baseline` (the CPU oracle — a "port" — timed on a bounded sample on the host cores).
+`--dump-outputs DIR`: after the timed steps, the latent they left (what the sampling path hands its caller) goes to
+DIR/latent.npy in float32 (DIR/latent_rank<r>.npy per rank in a world of several); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -635,8 +640,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=29)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="384-grid-2x3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = committed file)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: board power / clock, precompute_ms, the handle's launch "
+                         "profile (roofline, launch_classes, attention_kernel), the rocprofv3 counter passes, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latent the timed steps left as DIR/latent.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 --pmc child passes (roofline.traffic = committed file)")
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub-engine", action="store_true", help=argparse.SUPPRESS)   # tests: the driver over gloo without a GPU
     # tests (tests/test_parallel_gpu.py): the REAL engine in a world of two on ONE GPU - RCCL refuses two ranks on one device,
@@ -716,6 +726,24 @@ def rank_record(rank, local, a, own_elapsed, board=None, numa=None, device=None)
             "steps_per_s": round(a.steps * a.per_gpu_batch / own_elapsed, 4), "elapsed_s": round(own_elapsed, 4),
             "power_w_avg": b.get("power_w_avg"), "power_cap_w": b.get("power_cap_w"), "sclk_mhz_avg": b.get("sclk_mhz_avg"),
             "board_source": b.get("source")}
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: bytes in all, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32.  Past `budget` bytes in all,
+    each keeps a fixed, seeded sample of its rows (flattened to [rows, last dim]), in row order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > budget:
+            a = a.reshape(-1, a.shape[-1])
+            keep = a.shape[0] * budget // total
+            a = a[torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
 
 
 def self_launch(a, argv):
@@ -810,15 +838,17 @@ def main(argv=None):
     job = Job(model, x, kw, wl["steps"], t0=wl.get("t0", 0.0), do_shift=wl.get("do_shift", True))
 
     from visualcloze_amd.board import BoardSampler, pci_bus_id_of
-    # every rank samples ITS GPU (socket power, power cap, shader clock; sysfs hwmon) at 10 Hz - one small file read per
-    # 100 ms beside a loop that issues one graph launch per ~50 ms; the rate is in the record (`board.hz`)
-    board = BoardSampler(pci_bus_id_of(local), index=local, hz=10.0)
+    # --full: every rank samples ITS GPU (socket power, power cap, shader clock; sysfs hwmon) at 10 Hz - one small file read
+    # per 100 ms beside a loop that issues one graph launch per ~50 ms; the rate is in the record (`board.hz`)
+    board = BoardSampler(pci_bus_id_of(local), index=local, hz=10.0) if a.full else None
     with torch.cuda.stream(eng.stream):
         elapsed = timed_region(job, a.steps, a.warmup, max_over_ranks=lambda s: par.max_over_ranks(s, dev), board=board)
     with torch.cuda.stream(eng.stream):
         final = job.state().float()
     torch.cuda.synchronize()
     assert torch.isfinite(final).all(), "non-finite latent"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"latent" if world == 1 else f"latent_rank{rank}": final}, budget=DUMP_BYTES // world)
 
     T, N = 512, x.shape[1]
     rec = result_record(a, wl, world, elapsed, T, N, bcast_s, weight_bytes, rccl_ranks=par.rccl_rank_count(dev))
@@ -831,6 +861,8 @@ def main(argv=None):
                    final_latent_sum=float(final.double().sum()))
         if rank == 0:
             print(json.dumps(rec), flush=True)
+    elif rank == 0 and not a.full:
+        print(json.dumps(rec), flush=True)
     elif rank == 0:
         rec["board"] = board.summary()              # sampled DURING the timed steps: did this box sit at its power cap?
         rec["precompute_ms"] = round(job.precompute_ms(), 3)

@@ -444,3 +444,25 @@ def test_bench_roofline_legs_from_a_handle_profile():
     assert g["launches_per_eval"] == 76 and g["flops_per_launch"] == pytest.approx(fl / 76)
     assert g["avg_launch_us"] == pytest.approx(us / 76, abs=0.01) and g["frac"] == pytest.approx(fl / (us * 1e-6) / 2.5e15, abs=1e-4)
     assert g["bound"] == "mfma" and g["unit"] == "TFLOP/s" and "vc_flux_profile" in g["timed"]
+
+
+def test_bench_dump_outputs_and_full_flag(tmp_path):
+    """bench.py: a plain run leaves the extra legs to `--full` (off by default); `--dump-outputs DIR` writes the latent as float32
+    .npy, exactly while it fits the byte budget and past it as the same seeded sample of rows every time."""
+    import numpy as np
+    import bench
+    a = bench.parse_args(["--steps", "4", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 4
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    x = torch.randn(2, 300, 64, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "whole"), {"latent": x})
+    got = np.load(tmp_path / "whole" / "latent.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    budget = 100 * 64 * 4
+    bench.dump_outputs(str(tmp_path / "s1"), {"latent": x}, budget=budget)
+    bench.dump_outputs(str(tmp_path / "s2"), {"latent": x}, budget=budget)
+    s1, s2 = np.load(tmp_path / "s1" / "latent.npy"), np.load(tmp_path / "s2" / "latent.npy")
+    assert s1.nbytes <= budget and s1.shape == (100, 64) and np.array_equal(s1, s2)
+    rows = x.float().reshape(-1, 64).numpy()
+    assert all(any(np.array_equal(r, q) for q in rows) for r in s1[:5])

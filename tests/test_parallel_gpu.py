@@ -99,15 +99,17 @@ def test_real_engine_world2_on_one_gpu_over_gloo(tmp_path):
         assert f"rank {r} ok" in o
 
 
-def test_bench_gpus2_self_launch_with_the_real_engine():
+def test_bench_gpus2_self_launch_with_the_real_engine(tmp_path):
     """`python bench.py --gpus 2` started bare: re-launches itself as two ranks (torch.distributed.run --standalone), each
     builds the model (meta construction, rank 0 initialises, broadcast into rank 1), prepares a sampling-only engine, runs the
     timed region through the C handle, max over ranks, rank 0 prints ONE line with n_gpus = 2.  (gloo + one shared device +
-    the tiny model: the record says so and is marked as a driver test.)"""
+    the tiny model: the record says so and is marked as a driver test.)  `--dump-outputs`: every rank writes the latent it left,
+    rank 0's the one its record sums."""
+    import numpy as np
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "4"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device-index", "0",
-                        "--test-tiny", "--workload", "384-grid-1x2", "--steps", "6", "--warmup", "2"],
+                        "--test-tiny", "--workload", "384-grid-1x2", "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -118,3 +120,6 @@ def test_bench_gpus2_self_launch_with_the_real_engine():
     assert [q["rank"] for q in rec["per_rank"]] == [0, 1] and all(q["steps_per_s"] > 0 for q in rec["per_rank"])
     assert rec["stub"] is True and rec["metric"] == "stub-driver-test"
     assert rec["value"] > 0 and rec["weight_broadcast_s"] > 0 and abs(rec["final_latent_sum"]) < float("inf")
+    lat = [np.load(tmp_path / f"latent_rank{k}.npy") for k in (0, 1)]
+    assert all(x.dtype == np.float32 and x.shape == lat[0].shape and np.isfinite(x).all() for x in lat)
+    assert float(lat[0].astype(np.float64).sum()) == pytest.approx(rec["final_latent_sum"], rel=1e-9, abs=1e-9)

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 for WL in $WLS; do
   for PB in 1 2 4; do
-    python bench.py --workload $WL --per-gpu-batch $PB --no-cpu-baseline --no-traffic $BENCH_EXTRA > $OUT/${TAG}_${WL}_pb${PB}.json 2> $OUT/${TAG}_${WL}_pb${PB}.err
+    python bench.py --full --workload $WL --per-gpu-batch $PB --no-cpu-baseline --no-traffic $BENCH_EXTRA > $OUT/${TAG}_${WL}_pb${PB}.json 2> $OUT/${TAG}_${WL}_pb${PB}.err
     python - <<PY
 import json
 try:
