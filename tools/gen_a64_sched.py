@@ -1,4 +1,4 @@
-"""Generates visualcloze_amd/csrc/attention64_sched.h: which filler instructions sit in which MFMA gap of the bounded-softmax
+"""Generates visualcloze_amd/csrc/attention64_sched8.h: which filler instructions sit in which MFMA gap of the bounded-softmax
 tile of attention64.hip (`attn64_kernel<true>`).
 
 The tile is two phases of 32 MFMAs (one wave per SIMD, 32 cycles per MFMA = 7 issue slots of ~4.6 cycles: the MFMA itself and
@@ -15,19 +15,17 @@ six others).  Everything else the tile needs is a TOKEN with a measured issue pr
 
 This script deals the tokens out so that every gap carries about the same price, under the data dependences of the tile:
 
-  phase A(t):  S(t+1) = K(t+1) . Q^T (32 MFMAs: 4 chains of 8)  ||  20 pairs of P(t) (8..15, 20..31), the four V^T(t)
-               fragments of the first 16-key step, the 4 V^T(t+2) LDS-DMA pieces and one K(t+4) piece
+  phase A(t):  S(t+1) = K(t+1) . Q^T (32 MFMAs: 4 chains of 8)  ||  20 pairs of P(t) (8..15, 20..31), the eight V^T(t)
+               fragments of the first two 16-key steps and the 4 V^T(t+2) LDS-DMA pieces
   phase B(t):  O += V^T(t) . P(t)^T, 16-key step s major (MFMA j: s = j >> 3, dt = (j >> 1) & 3, qb = j & 1)  ||  12 pairs
                of P(t+1) written straight into the P registers that the s-major order has retired (pairs 0..3 -> P[0][0] after
-               MFMA 6, 16..19 -> P[1][0] after MFMA 7, 4..7 -> P[0][1] after MFMA 14), V^T(t) fragment (dt, s + 1) into the
-               register of (dt, s) as it retires (a ring of FOUR fragments: 16 registers), the 16 K(t+2) fragments, 3 K(t+4) pieces
+               MFMA 6, 16..19 -> P[1][0] after MFMA 7, 4..7 -> P[0][1] after MFMA 14), V^T(t) fragment (dt, s + 2) into the
+               register of (dt, s) as it retires (a ring of EIGHT fragments: 32 registers), the 16 K(t+2) fragments, 4 K(t+4) pieces
   waits:       lgkmcnt is in order for LDS reads, so each first use of a fragment waits with the COUNT of reads issued after it.
 
-    python tools/gen_a64_sched.py            # rewrites attention64_sched.h (ring of 4 fragment registers), prints the per-gap prices
-    python tools/gen_a64_sched.py --ring8    # attention64_sched8.h: ring of 8 (two 16-key steps; -DVC_A64_RING8 builds use it)
+    python tools/gen_a64_sched.py            # rewrites attention64_sched8.h, prints the per-gap prices
 """
 import os
-import sys
 
 E0, E1, A0, A1, CV, RV, RV2, RK, DMA, WAIT = range(10)
 NAMES = ["e", "E", "a", "A", "C", "RV", "RV2_", "RK", "DMA", "WAIT"]
@@ -101,29 +99,21 @@ def pair_chain(pairs, pos0, pos1):
     return out
 
 
-RING = 4            # V^T fragment registers: 4 (one 16-key step; set by main()) or 8 (two)
+RING = 8            # V^T fragment registers: two 16-key steps
 
 
 def vreg(dt, s):
     """register of V^T fragment (dt, s)"""
-    return dt if RING == 4 else (s & 1) * 4 + dt
+    return (s & 1) * 4 + dt
 
 
 def phase_a():
     toks = [dict(kind=kind, a=k, b=0, earliest=0, order=pos) for kind, k, pos in pair_chain(LATE_PAIRS, 0.0, 32.0)]
-    if RING == 8:
-        # V^T(t) fragments of the first two 16-key steps, in the order the P.V MFMAs use them; all issued by gap ~27
-        for f in range(8):
-            toks.append(dict(kind=RV, a=(f & 3) + 4 * (f >> 2), b=vreg(f & 3, f >> 2), earliest=0, order=1.0 + f * 3.6))
-        for i in range(4):                                # V^T(t+2) pieces
-            toks.append(dict(kind=DMA, a=i, b=0, earliest=0, order=3.0 + i * 8.0))
-        return deal(toks)
-    # V^T(t) fragments of the first 16-key step (s = 0): register dt; the ring is FOUR fragments deep - fragment (dt, s + 1)
-    # is read into register dt as soon as MFMA (s, dt, qb = 1) has issued, eight MFMAs before its first use
-    for f in range(4):
-        toks.append(dict(kind=RV, a=f, b=vreg(f, 0), earliest=0, order=14.0 + f * 4.0))
-    for i in range(5):                                # the 4 V^T(t+2) pieces and the first K(t+4) piece
-        toks.append(dict(kind=DMA, a=i, b=0, earliest=0, order=2.0 + i * 6.4))
+    # V^T(t) fragments of the first two 16-key steps, in the order the P.V MFMAs use them; all issued by gap ~27
+    for f in range(8):
+        toks.append(dict(kind=RV, a=(f & 3) + 4 * (f >> 2), b=vreg(f & 3, f >> 2), earliest=0, order=1.0 + f * 3.6))
+    for i in range(4):                                # V^T(t+2) pieces
+        toks.append(dict(kind=DMA, a=i, b=0, earliest=0, order=3.0 + i * 8.0))
     return deal(toks)
 
 
@@ -140,27 +130,16 @@ def phase_b():
     for kind, k, pos in pair_chain(EARLY_PAIRS, 7.0, 32.0):
         e = p_free_gap(k) + 1 if kind == CV else 0
         toks.append(dict(kind=kind, a=k, b=0, earliest=e, order=max(pos, e + 0.01 * (kind == CV))))
-    if RING == 8:
-        # fragment (dt, s + 2) into the register of (dt, s) behind MFMA (s, dt, qb = 1) = 8 s + 2 dt + 1
-        for s in range(2):
-            for dt in range(4):
-                j = 8 * s + 2 * dt + 1
-                toks.append(dict(kind=RV2, a=dt + 4 * (s + 2), b=vreg(dt, s + 2), earliest=j, order=j + 0.05))
-        for i, pos in enumerate([0.0, 2.0, 4.0, 6.0]):
-            toks.append(dict(kind=DMA, a=4 + i, b=0, earliest=0, order=pos))
-        for ut in range(16):
-            toks.append(dict(kind=RK, a=ut, b=0, earliest=0, order=(0.6 + ut * 2.0) if ut < 2 else 7.5 + (ut - 2) * 1.72))
-        return deal(toks)
-    # V^T(t) fragment (dt, s) for s = 1..3 into register dt behind MFMA (s - 1, dt, qb = 1) = 8 (s - 1) + 2 dt + 1
-    for s in range(1, 4):
+    # fragment (dt, s + 2) into the register of (dt, s) behind MFMA (s, dt, qb = 1) = 8 s + 2 dt + 1
+    for s in range(2):
         for dt in range(4):
-            j = 8 * (s - 1) + 2 * dt + 1
-            toks.append(dict(kind=RV2, a=dt + 4 * s, b=vreg(dt, s), earliest=j, order=j + 0.05))
-    # the other 3 K(t+4) pieces open the phase (its first gaps have no pair work), the 16 K(t+2) fragments are spread over the rest
-    for i, pos in enumerate([0.0, 2.5, 5.0]):
-        toks.append(dict(kind=DMA, a=5 + i, b=0, earliest=0, order=pos))
+            j = 8 * s + 2 * dt + 1
+            toks.append(dict(kind=RV2, a=dt + 4 * (s + 2), b=vreg(dt, s + 2), earliest=j, order=j + 0.05))
+    # the 4 K(t+4) pieces open the phase (its first gaps have no pair work), the 16 K(t+2) fragments are spread over the rest
+    for i, pos in enumerate([0.0, 2.0, 4.0, 6.0]):
+        toks.append(dict(kind=DMA, a=4 + i, b=0, earliest=0, order=pos))
     for ut in range(16):
-        toks.append(dict(kind=RK, a=ut, b=0, earliest=0, order=(0.6 + ut * 2.0) if ut < 3 else 8.5 + (ut - 3) * 1.78))
+        toks.append(dict(kind=RK, a=ut, b=0, earliest=0, order=(0.6 + ut * 2.0) if ut < 2 else 7.5 + (ut - 2) * 1.72))
     return deal(toks)
 
 
@@ -181,8 +160,8 @@ def add_waits(ga, gb):
         tok = next(t for g in ga + gb for t in g if t["kind"] in (RV, RV2) and t["a"] == code)
         where = (0, 31) if j == 0 else (1, j - 1)
         idx = next(i for i, r in enumerate(reads) if r[2] is tok)
-        if RING == 8 and p["dt"] == 0:
-            # ring of eight: all four fragments of a 16-key step are issued a whole step before its first MFMA - ONE wait per
+        if p["dt"] == 0:
+            # all four fragments of a 16-key step are issued a whole step before its first MFMA - ONE wait per
             # step, for the last of them (free by then), instead of one per fragment
             grp = [next(i for i, r in enumerate(reads) if r[2] is t) for g in ga + gb for t in g
                    if t["kind"] in (RV, RV2) and t["a"] // 4 == p["s"]]
@@ -243,8 +222,6 @@ constexpr int EARLY_FIRST[2] = {{{next(k for k in EARLY_PAIRS if k < 16)}, {next
 
 
 def main():
-    global RING
-    RING = 8 if "--ring8" in sys.argv else 4
     ga, gb = phase_a(), phase_b()
     ga, gb = add_waits(ga, gb)
     for name, gaps in (("A", ga), ("B", gb)):
@@ -253,7 +230,7 @@ def main():
         for g, toks in enumerate(gaps):
             print(f"  {g:2d} {price(toks):5.1f}  " + " ".join(f"{NAMES[t['kind']]}{t['a']}" + (f">{t['b']}" if t['kind'] in (RV, RV2) else "") for t in toks))
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    emit(ga, gb, os.path.join(here, "visualcloze_amd", "csrc", "attention64_sched.h" if RING == 4 else "attention64_sched8.h"))
+    emit(ga, gb, os.path.join(here, "visualcloze_amd", "csrc", "attention64_sched8.h"))
 
 
 if __name__ == "__main__":

@@ -44,11 +44,7 @@
 #include <type_traits>
 #include "common.h"
 #include "vcloze_internal.h"
-#ifdef VC_A64_RING4
-#include "attention64_sched.h"       // A/B builds: a ring of four V^T fragment registers (16 VGPRs less, -0.2 % per step: r06e)
-#else
-#include "attention64_sched8.h"      // a ring of eight (two 16-key steps)
-#endif
+#include "attention64_sched8.h"      // a ring of eight V^T fragment registers (two 16-key steps)
 
 namespace {
 
@@ -193,10 +189,13 @@ VC_DEV uint32_t v_cvt_pk(float lo, float hi) {
   return r;
 }
 // one LDS-DMA piece, `global_load_lds_dwordx4 v_off, s[base]`, with M0 = lds_wave + imm written in the same statement (one wait
-// state before the DMA reads it)
+// state before the DMA reads it; the "m0" clobber and its warning: see glds16_saddr in common.h)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 VC_DEV void glds16_m0(const char* sbase, uint32_t voff, uint32_t lds_wave, int imm) {
   asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_wave), "i"(imm) : "memory", "m0", "scc");
 }
+#pragma clang diagnostic pop
 template <int A> VC_DEV float agpr_read() {
   float r;
   asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(r) : "n"(A));
@@ -265,6 +264,7 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(const Attn64Args a) {
   const uint64_t ts0 = __builtin_amdgcn_s_memtime();
   int ts_tiles = 0, ts_seg = 0;
   // per work item of the workgroup (up to 3): start, prologue done, first tile done, loop done, epilogue done, tiles
+  // (attn64s_kernel stamps with the same macro)
 #define TS_SEG(k) do { if (a.debug_ts && tid == 0 && ts_seg < 3) a.debug_ts[blockIdx.x * 32 + 8 + ts_seg * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define TS_SEG(k) do { } while (0)
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(const Attn64Args a) {
     };
 
     // (b) bounded-logit form: no row max, so the fillers of a tile are exp / add / pack, the 32 fragment reads and the 8
-    // LDS-DMA pieces - dealt out over the 64 MFMA gaps by tools/gen_a64_sched.py (attention64_sched.h) so that every gap
+    // LDS-DMA pieces - dealt out over the 64 MFMA gaps by tools/gen_a64_sched.py (attention64_sched8.h) so that every gap
     // carries about the same issue price.  12 pairs of P(kt+1) are exponentiated in the P.V phase of tile kt, straight into
     // the P registers that the s-major order of that phase has already retired (and into l: nothing rescales it here).
     float pe0[32], pe1[32];              // probabilities between their v_exp and their row-sum add / pack (2-3 pairs live)
@@ -981,12 +981,8 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
   // the counted waits, every barrier, the K'(0) fragment reads that belong to the NEXT item - and skips the item's MFMAs,
   // exponentials and fragment reads: 3 % of the launch's arithmetic at cfg 2, on a board that runs at its power cap.
   bool dead = false;
-#ifdef VC_A64_NO_DEAD_WAVES      // A/B builds: every wave computes its padded rows (rounds 2-6)
-#define VC_DEAD_OF(id) false
-#else
 #define VC_DEAD_OF(id) (BOUNDED && __builtin_amdgcn_readfirstlane((int)(((id) % a.qblocks) * QB + wave * QW >= L)) != 0)   /* (the running-max
      template has no registers left for the second item skeleton: 44 accumulator spills) */
-#endif
 
   auto read_k = [&](auto SLOT, auto UT) __attribute__((always_inline)) {
     constexpr int ut = decltype(UT)::value, u = ut >> 3, t = ut & 7;
@@ -1133,7 +1129,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
     __builtin_amdgcn_s_barrier();
     SB();
   };
-  // ---- one filler token of the generated schedule (attention64_sched.h); LAST: the item's last tile, which has no S(t+1) -
+  // ---- one filler token of the generated schedule (attention64_sched8.h); LAST: the item's last tile, which has no S(t+1) -
   // no exponentials of it, no K fragments of the tile after it (the K registers keep K'(0) of the next item), and its counted
   // waits, sized for the full read stream, become lgkmcnt(0) ----
   auto run_tok = [&](auto PH, auto TI, auto LASTc, auto RKc, auto SBASE, auto SLOT_V, auto SLOT_K2, auto SLOT_K4, uint32_t v_sc, uint32_t k_sc, uint32_t k_bd) __attribute__((always_inline)) {
@@ -1226,7 +1222,6 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
   // fragments where a live step reads them (stream tile kt + 2 = the next item's first tile), the step's waits and its barrier
   auto dead_tile = [&](auto Jc, auto LASTc, int kt) __attribute__((always_inline)) {
     constexpr int J = decltype(Jc)::value;
-    constexpr bool LAST = decltype(LASTc)::value;
     using SLOT_K2 = std::integral_constant<int, (J + 2) % 3>;
     using SLOT_K4 = std::integral_constant<int, (J + 1) % 3>;
     uint32_t k_bd;
@@ -1374,11 +1369,6 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
     }
   };
   // =================================================== the item loop ===================================================
-#ifdef VC_ATTN_TIMESTAMPS
-#define TS_S(k) do { if (a.debug_ts && tid == 0 && ts_seg < 3) a.debug_ts[blockIdx.x * 32 + 8 + ts_seg * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TS_S(k) do { } while (0)
-#endif
   bool hard = true;
   for (;;) {
     pad1 = c_kt0 + (c_kt1 - c_kt0 + 2) / 3 * 3;
@@ -1387,7 +1377,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
     ts_tiles += c_kt1 - c_kt0;
     if (a.debug_ts && tid == 0 && ts_seg < 3) a.debug_ts[blockIdx.x * 32 + 8 + ts_seg * 8 + 5] = c_kt1 - c_kt0;
 #endif
-    TS_S(0);
+    TS_SEG(0);
     if (hard) {
       // ---- HARD start: every wait stands in front of its first consumer.  Issue order K(0), Q, K(1), V^T(0), K(2), V^T(1)
       // [then K(3)]: S(kt0) needs K(0) and Q only; the rest lands under it (first_s waits for K(1) before it reads its fragments,
@@ -1414,7 +1404,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
       for (int i = 0; i < 4; ++i) dma_k(I0{}, kt0 + 3, i);
       SB();
     }
-    TS_S(1);
+    TS_SEG(1);
     const bool soft = have_next && (c_kt1 - c_kt0) >= 4;     // the look-ahead of a shorter item was issued before its successor was known
     const int kt_last = c_kt1 - 1;
     int kt = c_kt0, exit_j;
@@ -1429,7 +1419,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
       wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();
       SB();
-      TS_S(2);
+      TS_SEG(2);
       for (;;) {
         if (kt >= kt_last) { exit_j = 0; break; }
         dead_tile(I0{}, std::false_type{}, kt); ++kt;
@@ -1448,12 +1438,12 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
       } else {
         dead_tile(I2{}, std::true_type{}, kt);
       }
-      TS_S(3);
+      TS_SEG(3);
       if (pub >= 0) { publish(pub); pub = -1; }
       if (c_piece >= 0) pub = c_piece;           // (no row of this wave exists; `pub` stays uniform across the workgroup)
     } else {
     first_s(hard);
-    TS_S(2);
+    TS_SEG(2);
     // ---- the item's tiles but the last: a single-entry loop over the three rotations ----
     for (;;) {
       if (kt >= kt_last) { exit_j = 0; break; }
@@ -1474,11 +1464,11 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
     } else {
       tile_any(I2{}, std::true_type{}, kt);
     }
-    TS_S(3);
+    TS_SEG(3);
     if (pub >= 0) { publish(pub); pub = -1; }
     store_out();
     }
-    TS_S(4);
+    TS_SEG(4);
 #ifdef VC_ATTN_TIMESTAMPS
     ++ts_seg;
 #endif

@@ -24,12 +24,8 @@ namespace {
 
 constexpr int BK = 64;
 // raster: ids walk GROUP_M m-tiles, then the n-tiles (an XCD's 32 resident workgroups = GROUP_M x 32/GROUP_M tiles)
-#ifndef VC_GEMM_GROUP_M
-#define VC_GEMM_GROUP_M 8
-#endif
-#ifndef VC_GEMM_STREAMK_MIN_K
-#define VC_GEMM_STREAMK_MIN_K 6144      /* the stream remainder is not offered below this K (the partial traffic outweighs the short tiles) */
-#endif
+constexpr int GROUP_M = 8;
+constexpr int STREAMK_MIN_K = 6144;     // the stream remainder is not offered below this K (the partial traffic outweighs the short tiles)
 
 // CONV (loader-wave schedule only): the A operand is the im2col matrix of a 3x3 convolution over an NHWC map, gathered
 // on the fly by the loader waves - K-tile kt lies inside tap kt*64 / C, row m is output pixel (m / W, m % W), out-of-
@@ -121,7 +117,6 @@ __global__ __launch_bounds__((WM * WN + (PP == 2 ? 4 : 0)) * 64) void gemm_bf16_
     Tile t;
     t.P = pi == 3 ? args.p[3] : pi == 2 ? args.p[2] : pi == 1 ? args.p[1] : args.p[0];
     id -= t.P.tile_start;
-    constexpr int GROUP_M = VC_GEMM_GROUP_M;
     const int in_group = GROUP_M * t.P.tiles_n;
     const int group = id / in_group;
     const int first_m = group * GROUP_M;
@@ -147,11 +142,7 @@ __global__ __launch_bounds__((WM * WN + (PP == 2 ? 4 : 0)) * 64) void gemm_bf16_
   // `global_load_lds v_off, s[base]` with the K position folded into the scalar base: no vector instruction per piece in the
   // loader waves, which issue on the SIMDs the compute waves feed the matrix pipe from (element offsets against a bf16 pointer
   // made hipcc form a 64-bit address per piece: one v_lshl_add_u64 for each of the 14 pieces of a K-tile).
-#ifndef VC_GEMM_NO_SADDR      // (A/B builds: round 3's per-piece 64-bit vector addresses)
   constexpr bool BYTE_OFF = PP == 2 && !CONV;
-#else
-  constexpr bool BYTE_OFF = false;
-#endif
   auto staging_offsets_a = [&](uint32_t (&ao)[A_IT], const VcGemmProblem& Q, int m0q, int st) {
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
@@ -286,11 +277,7 @@ __global__ __launch_bounds__((WM * WN + (PP == 2 ? 4 : 0)) * 64) void gemm_bf16_
   // rows): written the second way the K-slice-1 fragments of an operand share ONE base register and take their row offsets as
   // ds_read immediates; the first way hipcc kept one pre-XORed register per fragment and a v_add per fragment and K-tile - vector
   // instructions in the MEMORY segment, i.e. beside the partner wave's MFMAs on the same SIMD
-#ifdef VC_GEMM_FRAG_XOR_PER_FRAGMENT      // (A/B builds: round 3's form)
-#define FRAG_AT(x, off, kk) (((x) + (off)) ^ ((kk) * 64))
-#else
 #define FRAG_AT(x, off, kk) ((((x) ^ ((kk) * 64))) + (off))
-#endif
   const int fr = lane & 15, fq = lane >> 4;
   const int sw0 = ((fq ^ (lane & 7)) << 4);  // kk=0 slot; kk=1 is sw0 ^ 64
   const int a_rd = (wm * TM + fr) * 128 + sw0;
@@ -423,15 +410,11 @@ __global__ __launch_bounds__((WM * WN + (PP == 2 ? 4 : 0)) * 64) void gemm_bf16_
       // nothing to accumulate: it keeps the K loop's barriers - four per K-tile - and skips its fragment reads and MFMAs.  Its
       // SIMD's other waves run on; what comes back is power (the board runs at its cap), not time.  The epilogue is the same
       // for every wave (rows >= M are never stored).
-#ifdef VC_GEMM_NO_DEAD_WAVES      // A/B builds
-      constexpr bool wdead = false;
-#else
       const bool wdead = __builtin_amdgcn_readfirstlane((int)(m0 + wm * TM >= M)) != 0;
-#endif
       if (wdead) {
         for (int kt = 0; kt < nk; ++kt) { bar(); bar(); bar(); bar(); }
       } else
-#if !defined(VC_GEMM_NO_LDSREAD) && !defined(VC_GEMM_NO_MFMA) && !defined(VC_GEMM_NO_SLOT_UNROLL)
+#if !defined(VC_GEMM_NO_LDSREAD) && !defined(VC_GEMM_NO_MFMA)
       // The K loop unrolled over the ring period (A: 2 slots, W: 3 slots -> 6 K-tiles), so that every fragment address is ONE of
       // six lane-constant base registers + an immediate: no vector instruction at all in the MEMORY segment, which runs beside
       // the partner wave's MFMAs (with the slot offsets in scalar registers it was 5 v_add per K-tile, 11 before round 4).
@@ -1030,7 +1013,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const VcGemmArgs arg
     if (q < args.nprob && id >= args.p[q].tile_start) pi = q;
   const VcGemmProblem P = pi == 3 ? args.p[3] : pi == 2 ? args.p[2] : pi == 1 ? args.p[1] : args.p[0];   // scalar selects, as decode()
   id -= P.tile_start;
-  constexpr int GROUP_M = VC_GEMM_GROUP_M;        // the raster of gemm_bf16_kernel's decode
   const int in_group = GROUP_M * P.tiles_n, group = id / in_group, first_m = group * GROUP_M;
   const int gsz = min(P.tiles_m - first_m, GROUP_M);
   const int m = P.m_begin + (first_m + (id % in_group) % gsz) * BM + row, n = ((id % in_group) / gsz) * BN + ch * 8;
@@ -1467,13 +1449,13 @@ static GemmPlan plan_gemm(const VcGemmArgs& a, int tile_cfg) {
   // fill): interleaved whole steps, profiles/r05d_ab_*.log - cfg 3's N = 3072 launches (416 tiles = 256 + 160, f = 0.625: instead
   // of the row cut into 256 + 240 narrower tiles) +1.7 % per step, all of it from K >= 12288 (K = 3072 included: +0.0 %);
   // cfg 5's (464 = 256 + 208, f = 0.81: instead of a second round at 81 % fill) -1.2 %, with K = 3072 -2.1 %.  Taken for
-  // 0.5 < f <= 0.7 and K >= VC_GEMM_STREAMK_MIN_K.
+  // 0.5 < f <= 0.7 and K >= STREAMK_MIN_K.
   if (!no_splitk && sk.sk_S == 0 && a.splitk_ws && a.epi != VC_EPI_QKV) {
     const long total = tiles_of(a, 4), R = total / n_cus, rem = total % n_cus;
     bool same_k = true;
     for (int i = 1; i < a.nprob; ++i) same_k = same_k && a.p[i].K == a.p[0].K;
     const bool prefer = (tile_cfg_flags & VC_GEMM_PREFER_STREAMK) != 0, any_k = (tile_cfg_flags & VC_GEMM_STREAMK_ANY_K) != 0;
-    if (R >= 1 && 2 * rem > n_cus && same_k && (a.p[0].K >= VC_GEMM_STREAMK_MIN_K || any_k) && (double)n_cus * 2 * cfg_bm[4] * cfg_bn[4] * 4 <= (double)a.splitk_ws_bytes) {
+    if (R >= 1 && 2 * rem > n_cus && same_k && (a.p[0].K >= STREAMK_MIN_K || any_k) && (double)n_cus * 2 * cfg_bm[4] * cfg_bn[4] * 4 <= (double)a.splitk_ws_bytes) {
       // (advisor r05: only where the one-launch plan would have chosen the 256x192 tile itself - at N = 256 or 4096 a 192-wide
       // tile wastes columns and another tile may cost far less than any remainder scheme on this one)
       if (prefer || any_k || (10 * rem <= 7 * n_cus && whole.tile_cfg == 4)) return stream_plan();

@@ -96,7 +96,6 @@ __global__ __launch_bounds__(256) void qknorm_rope_vt_kernel(bf16_t* __restrict_
   const int sub = tid & 15;  // 16 lanes x 8 elements = one head row
 
   // ---- phase 1: q and k rows ----
-#pragma unroll 2
   for (int p = (parts & 1) ? 0 : 4; p < ((parts & 2) ? 8 : 4); ++p) {
     const int rowid = p * 16 + (tid >> 4);
     const int which = rowid >> 6;  // 0 = q, 1 = k
@@ -236,12 +235,9 @@ int vc_qknorm_rope_vt_launch(void* qkv, int64_t ld, int64_t bstride, const void*
   if (!q_scale2 || !k_scale2) { q_scale2 = q_scale; k_scale2 = k_scale; split = L; }
   if (B <= 0 || L <= 0 || H <= 0) { snprintf(err, errlen, "qknorm_rope_vt: empty problem"); return VC_ERR_ARG; }
   if (Lpad < L || Lpad % 64 || ld % 8 || bstride % 8) { snprintf(err, errlen, "qknorm_rope_vt: Lpad=%d must be a multiple of 64 >= L=%d; ld, bstride multiples of 8", Lpad, L); return VC_ERR_ARG; }
-#ifndef VC_QKN_HG
-#define VC_QKN_HG 2
-#endif
 #ifndef VC_QKN_TILE_ONLY          // analysis builds (tools/qkn_ab.py): the 64-token tile kernel for every `parts`
-  if (!(parts & VC_QKN_VT)) {     // rows only: one (cos, sin) read per token for VC_QKN_HG heads
-    constexpr int HG = VC_QKN_HG;
+  if (!(parts & VC_QKN_VT)) {     // rows only: one (cos, sin) read per token for HG heads
+    constexpr int HG = 2;
     hipLaunchKernelGGL(qknorm_rope_rows_kernel<HG>, dim3((L + 15) / 16, (H + HG - 1) / HG, B), dim3(256), 0, s, (bf16_t*)qkv, (long)ld,
                        (long)bstride, (const bf16_t*)q_scale, (const bf16_t*)k_scale, (const bf16_t*)q_scale2, (const bf16_t*)k_scale2,
                        split, rope, (long)rope_bstride, L, H, parts);
