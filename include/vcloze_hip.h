@@ -21,7 +21,7 @@ extern "C" {
 #define VC_ERR_HIP (-2)
 #define VC_ERR_STATE (-3)
 
-#define VC_ABI_VERSION 10
+#define VC_ABI_VERSION 11
 int vc_abi_version(void);
 const char* vc_last_error(void);
 /* sizeof(VcGemmProblem), sizeof(VcGemmArgs), sizeof(VcLnStream), sizeof(VcAttention), sizeof(VcFluxConfig),
@@ -318,6 +318,25 @@ int vc_mul(const void* a, const void* b, void* y, int64_t n, void* stream);
 int vc_add(const void* a, const void* b, void* y, int64_t n, void* stream);
 int vc_quick_gelu(const void* x, void* y, int64_t n, void* stream);
 
+/* ---- LoRA merge (ABI 11): LinearLora (models/modules/lora.py:66-67 the factor pair, :92-98 its forward) folded into ONE weight ----
+ *   out[o, i]   = bf16( f32(W[o, i]) + scale * acc[o, i] ),   acc[o, i] = sum_k f32(B[o, k]) * f32(A[k, i])
+ *   bias_out[o] = bf16( f32(b[o])    + scale * f32(bB[o]) )
+ * W = the Linear's weight [out_features, in_features], bf16 or F32 (w_is_f32), row stride ldw; A = lora_A.weight [rank, in_features]
+ * and B = lora_B.weight [out_features, rank], bf16, each in nn.Linear's OWN layout (row strides lda, ldb: no transposed copy is
+ * asked for); out [out_features, in_features] bf16, row stride ldo.  The products are bf16 x bf16 on the matrix cores, exact in
+ * f32, and accumulate in f32 - only the order of those sums differs from an f32 matmul.  TWO more roundings follow, as in
+ * `W32 += scale * (B32 @ A32)`: scale * acc is rounded to f32, then the sum with W is, then the result goes to bf16 (nearest even);
+ * no fused multiply-add.  0 <= rank <= 512; any out_features, in_features.  16-byte accesses need 16-byte aligned bases and
+ * in_features and every row stride a multiple of 8; anything else runs element-wise, slower, with the same results.
+ * out may BE w (bf16 weight, ldo == ldw: merged in place, no second matrix exists); it must not overlap w in any other way, nor
+ * the factors.  bias: b [out_features] bf16 or F32 (bias_is_f32) or NULL (= 0), bB = lora_B.bias bf16 or NULL (bias_out = bf16(b));
+ * bias_out NULL with both NULL, and may be b itself when b is bf16.  rank == 0 with NULL factors: a conversion / copy of W
+ * (and b), so that every Linear of a checkpoint can go through this one entry point.  Arguments are checked before the device
+ * is touched (VC_ERR_ARG + message).  Replaces: the torch f32 matmul a host would otherwise need to fold a LoRA checkpoint. */
+int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                  float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias, void* bias_out,
+                  int32_t out_features, int32_t in_features, int32_t rank, void* stream);
+
 /* ---- handle API: the whole of Flux.forward, and the whole fixed-grid Euler loop, behind one call each ----
  * vc_flux_forward       replaces Flux.forward                      (models/model.py:85-124)
  * vc_flux_sample_euler  replaces odeint(method="euler") over it    (transport/integrators.py:106-120, transport.py:361-410:
@@ -325,7 +344,9 @@ int vc_quick_gelu(const void* x, void* y, int64_t n, void* stream);
  * The handle holds no tensor: weights are zero-copy views bound by name, every activation lives in a caller-provided
  * workspace.  It does own small host-side state (a pinned staging buffer, the captured hipGraph of one solver step, events).
  * One handle per device per process; not thread-safe per handle.  bf16 everywhere, LoRA pairs already folded into the
- * bound weights (W + s*B@A, lora.py:92-98; the un-merged parity mode stays on the op-level API). */
+ * bound weights (W + s*B@A, lora.py:92-98; the un-merged parity mode stays on the op-level API).  A C caller gets there from a
+ * LoRA checkpoint with one vc_lora_merge call per Linear - in place on its own copy of the base weight, or with `out` pointing at
+ * the Linear's rows of the stacked "modulation" matrix - and binds the results. */
 typedef struct VcFluxConfig {   /* FluxParams, models/model.py:18-32 */
   int32_t in_channels, out_channels, vec_in_dim, context_in_dim, hidden_size, num_heads, depth, depth_single_blocks;
   int32_t mlp_hidden;           /* hidden_size * mlp_ratio */

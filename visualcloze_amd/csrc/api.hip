@@ -148,6 +148,12 @@ int vc_pack_mask(const void* mask, void* tokens, int32_t H, int32_t W, int64_t l
 int vc_unpack_latent(const void* tokens, int64_t ld, int32_t col0, void* latent, int32_t C, int32_t h, int32_t w, void* stream) {
   return vc_unpack_latent_launch(tokens, ld, col0, latent, C, h, w, S(stream), ERRBUF);
 }
+int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                  float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias, void* bias_out,
+                  int32_t out_features, int32_t in_features, int32_t rank, void* stream) {
+  return vc_lora_merge_launch(w, w_is_f32, ldw, lora_a, lda, lora_b, ldb, scale, out, ldo, bias, bias_is_f32, lora_b_bias, bias_out,
+                              out_features, in_features, rank, S(stream), ERRBUF);
+}
 
 /* ---- handle API (flux_engine.hip) ---- */
 int vc_flux_create(const VcFluxConfig* cfg, void** handle) { return vc_flux_create_impl(cfg, handle, ERRBUF); }

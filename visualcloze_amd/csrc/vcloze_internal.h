@@ -74,6 +74,9 @@ int vc_rownorm_launch(const void* x, const void* w, const void* b, void* y, int 
 int vc_ewise_launch(const void* a, const void* b, void* y, int64_t n, int op, hipStream_t s, char* err, int errlen);
 int vc_conv3x3_launch(const void* x, const void* w, const void* bias, void* out, int64_t ldc, const void* res, int64_t ldres,
                       const void* gate, int H, int W, int C, int O, int mode, hipStream_t s, char* err, int errlen);
+int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                         float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
+                         void* bias_out, int32_t out_features, int32_t in_features, int32_t rank, hipStream_t s, char* err, int errlen);
 
 // flux_engine.hip: the handle API
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen);

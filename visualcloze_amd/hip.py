@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VC_HIP_LIB") or os.path.join(_HERE, "lib", "libvcloze_hip.so")   # VC_HIP_LIB: profiling build
 CSRC = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 10               # VC_ABI_VERSION of include/vcloze_hip.h
+ABI_VERSION = 11               # VC_ABI_VERSION of include/vcloze_hip.h
 GEMM_MAX_PROBLEMS = 4          # VC_GEMM_MAX_PROBLEMS: grouped problems per vc_gemm launch
 EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_SILU, EPI_QKV = 0, 1, 2, 3, 4
 GEMM_NO_SPLIT = 64             # VC_GEMM_NO_SPLIT: tile_cfg value that keeps an auto-tiled vc_gemm one launch
@@ -146,6 +146,7 @@ SYMBOLS = {
     "vc_nchw_to_nhwc": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, C.c_float, C.c_float, _vp]),
     "vc_nhwc_to_nchw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp]),
     "vc_gaussian_sample": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp]),
+    "vc_lora_merge": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vc_flux_create": (C.c_int, [C.POINTER(FluxConfig), C.POINTER(_vp)]),
     "vc_flux_destroy": (C.c_int, [_vp]),
     "vc_flux_bind_weight": (C.c_int, [_vp, C.c_char_p, _vp, _vp, _i32, _i32, _i64]),
@@ -339,6 +340,55 @@ def linear(a, w, bias=None, out=None, epi=EPI_BIAS, res=None, gate=None, tile_cf
         out = torch.empty(a.shape[0], w.shape[0], dtype=torch.bfloat16, device=a.device)
     gemm(make_problem(a, w, bias, out, res=res, gate=gate), epi=epi, tile_cfg=tile_cfg, stream=stream)
     return out
+
+
+def lora_merge(weight, lora_a, lora_b, scale, out=None, bias=None, lora_b_bias=None, stream=None):
+    """(W', b') = (bf16(W + scale * B @ A), bf16(b + scale * b_B)): LinearLora (models/modules/lora.py:92-98) folded into one
+    weight by vc_lora_merge.  `weight` [out, in] and `bias` [out]: bf16 or f32; `lora_a` [r, in], `lora_b` [out, r],
+    `lora_b_bias` [out]: bf16 (f32 factors are not bf16 values - the matrix cores would round them - and are refused); both
+    factors None = rank 0, a conversion of `weight` / `bias`.  `out`: a [out, in] bf16 view with any row stride (rows of a
+    stacked matrix), `weight` itself (bf16: merged in place) or None (a new tensor).  Returns (out, bias_out or None)."""
+    if weight.dim() != 2 or not weight.is_cuda or weight.dtype not in (torch.bfloat16, torch.float32) or weight.stride(1) != 1:
+        raise VclozeHipError(f"lora_merge weight: need a 2-D CUDA bf16 / f32 tensor with contiguous last dim, got {weight.dtype} "
+                             f"{tuple(weight.shape)} on {weight.device}")
+    O, I = weight.shape
+    for n, t in (("lora_a", lora_a), ("lora_b", lora_b), ("out", out), ("bias", bias), ("lora_b_bias", lora_b_bias)):
+        if t is not None and t.device != weight.device:
+            raise VclozeHipError(f"lora_merge {n}: on device {t.device}, the weight is on {weight.device}")
+    if stream is None and weight.device.index != torch.cuda.current_device():
+        raise VclozeHipError(f"lora_merge: the tensors are on device {weight.device}, the current stream on cuda:{torch.cuda.current_device()}")
+    if (lora_a is None) != (lora_b is None):
+        raise VclozeHipError("lora_merge: lora_a and lora_b come together")
+    R = 0
+    if lora_a is not None:
+        for n, t in (("lora_a", lora_a), ("lora_b", lora_b)):
+            if t.dtype == torch.float32:
+                raise VclozeHipError(f"lora_merge {n}: f32 LoRA factors are not merged on the bf16 matrix cores (they would be "
+                                     "rounded); use the torch merge (lora_merge=\"torch\") or cast the factors to bf16")
+            _bf16(t, "lora_merge " + n)
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise VclozeHipError(f"lora_merge {n}: need a 2-D tensor with contiguous last dim")
+        R = lora_a.shape[0]
+        if lora_a.shape[1] != I or tuple(lora_b.shape) != (O, R):
+            raise VclozeHipError(f"lora_merge shape mismatch W{tuple(weight.shape)} A{tuple(lora_a.shape)} B{tuple(lora_b.shape)}")
+    if out is None:
+        out = torch.empty(O, I, dtype=torch.bfloat16, device=weight.device)
+    _bf16(out, "lora_merge out")
+    if tuple(out.shape) != (O, I) or out.stride(1) != 1:
+        raise VclozeHipError(f"lora_merge out: need a [{O}, {I}] view with contiguous last dim, got {tuple(out.shape)}")
+    bias_out = None
+    for n, t in (("bias", bias), ("lora_b_bias", lora_b_bias)):
+        if t is None:
+            continue
+        ok = (torch.bfloat16, torch.float32) if n == "bias" else (torch.bfloat16,)
+        if not t.is_cuda or t.dtype not in ok or tuple(t.shape) != (O,) or not t.is_contiguous():
+            raise VclozeHipError(f"lora_merge {n}: need a contiguous CUDA [{O}] tensor of {ok}, got {t.dtype} {tuple(t.shape)}")
+        bias_out = torch.empty(O, dtype=torch.bfloat16, device=weight.device) if bias_out is None else bias_out
+    _check(lib().vc_lora_merge(weight.data_ptr(), int(weight.dtype == torch.float32), weight.stride(0),
+                               _p(lora_a), lora_a.stride(0) if R else 0, _p(lora_b), lora_b.stride(0) if R else 0, float(scale),
+                               out.data_ptr(), out.stride(0), _p(bias), int(bias is not None and bias.dtype == torch.float32),
+                               _p(lora_b_bias), _p(bias_out), O, I, R, stream if stream is not None else cur_stream()), "vc_lora_merge")
+    return out, bias_out
 
 
 def ln_modulate(x, shift, scale, out=None, step_ptr=None, mod_step_stride=0, stream=None, rows_per_batch=None,

@@ -266,6 +266,10 @@ class Flux(nn.Module):
         # the prepared qkv weights (merged mode) are stored HEAD-PERMUTED - every key head inside one 192-column GEMM tile -
         # so that QKNorm + RoPE of k can ride the projection's epilogue (hip.qkv_head_permutation, VcGemmProblem.kn_heads)
         self.qkv_permute = True
+        # who forms W + s*B@A in prepare(): "torch" (an f32 matmul of the vendor BLAS plus f32 temporaries, the path every parity
+        # number of DESIGN.md was taken on) or "hip" (vc_lora_merge, csrc/lora_merge.hip: one launch per Linear, no f32 copy, no
+        # vendor GEMM; the same arithmetic up to the order of the f32 sums)
+        self.lora_merge = "torch"
 
     # ------------------------------------------------------------------ weights -> engine
     def _linears(self):
@@ -275,17 +279,41 @@ class Flux(nn.Module):
 
     def _weights_fingerprint(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple(
-            m.scale for _, m in self._linears()) + (self.lora_mode, self.qkv_permute)
+            m.scale for _, m in self._linears()) + (self.lora_mode, self.qkv_permute, self.lora_merge)
 
     @staticmethod
     @torch.no_grad()
-    def merged_linear(m: "Linear", consume: bool = False, out: Optional[Tensor] = None):
+    def merged_linear(m: "Linear", consume: bool = False, out: Optional[Tensor] = None, backend: str = "torch"):
         """(W', b') of one Linear as the engine executes it: bf16(W + s*B@A), bf16(b + s*b_B) - LinearLora
         (models/modules/lora.py:92-98) with its LoRA pair folded in, exact in f32 and rounded to bf16 once.
         `out`: write W' into this [out, in] bf16 view instead of a new tensor (the stacked modulation matrix).
         `consume`: the module gives its storage away - W' overwrites m.weight's own memory (when that is a contiguous bf16
         tensor) and every parameter of the Linear is left EMPTY, so that preparing a sampling-only rank never holds the
-        un-merged and the merged set at once (26.3 GB peak instead of 56.7)."""
+        un-merged and the merged set at once (26.3 GB peak instead of 56.7).
+        `backend`: "torch" forms the merge with torch ops (f32 temporaries, the vendor BLAS); "hip" with vc_lora_merge - bf16 or
+        f32 weight / bias read as they are, bf16 factors only, no temporary of the size of W."""
+        if backend == "hip":
+            W = m.weight.detach()
+            A = Bm = bB = None
+            if m.rank:
+                A, Bm = m.lora_A.weight.detach(), m.lora_B.weight.detach()
+                bB = None if m.lora_B.bias is None else m.lora_B.bias.detach()
+                if bB is not None and bB.dtype != torch.bfloat16:
+                    raise hip.VclozeHipError(f"lora_merge='hip': lora_B.bias is {bB.dtype}, not bf16; use lora_merge=\"torch\"")
+            if out is None and consume and W.dtype == torch.bfloat16 and W.is_contiguous():
+                out = W                      # in place: each tile of W is read before it is written (csrc/lora_merge.hip)
+            if out is W and not m.rank and (m.bias is None or (m.bias.dtype == torch.bfloat16 and m.bias.is_contiguous())):
+                bias = None if m.bias is None else m.bias.detach()       # nothing to merge: the storage changes hands untouched
+                for p in m.parameters():
+                    p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+                return out, bias
+            out, bias = hip.lora_merge(W, A, Bm, m.scale, out=out, bias=None if m.bias is None else m.bias.detach(), lora_b_bias=bB)
+            if consume:
+                for p in m.parameters():
+                    p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+            return out, bias
+        if backend != "torch":
+            raise ValueError(f"merged_linear backend must be 'torch' or 'hip', got {backend!r}")
         W = m.weight.detach()
         W32 = W.float()                   # NOT a copy when the parameter is f32 already: never update it in place
         B32 = None if m.bias is None else m.bias.detach().float()
@@ -326,6 +354,8 @@ class Flux(nn.Module):
             raise hip.VclozeHipError("parameters were released by prepare(free_parameters=True); load weights again first")
         if self.lora_mode not in ("merged", "ref"):
             raise ValueError(f"lora_mode must be 'merged' or 'ref', got {self.lora_mode!r}")
+        if self.lora_merge not in ("torch", "hip"):
+            raise ValueError(f"lora_merge must be 'torch' or 'hip', got {self.lora_merge!r}")
         w, b, ref = {}, {}, ({} if self.lora_mode == "ref" else None)
         bf = lambda t: None if t is None else t.detach().to(torch.bfloat16).contiguous()  # noqa: E731
         # all modulation projections are stacked: one GEMM yields every shift/scale/gate of a step.  Their merged rows
@@ -346,11 +376,11 @@ class Flux(nn.Module):
         for name, m in lin.items():
             if ref is None:
                 if name in off:
-                    _, bb = self.merged_linear(m, consume, out=mod_w[off[name]:off[name] + m.out_features])
+                    _, bb = self.merged_linear(m, consume, out=mod_w[off[name]:off[name] + m.out_features], backend=self.lora_merge)
                     if bb is not None:
                         mod_b[off[name]:off[name] + m.out_features] = bb
                 else:
-                    w[name], b[name] = self.merged_linear(m, consume)
+                    w[name], b[name] = self.merged_linear(m, consume, backend=self.lora_merge)
                 continue
             w[name], b[name] = bf(m.weight), bf(m.bias)
             A = B = bB = sc = None
