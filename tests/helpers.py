@@ -63,3 +63,37 @@ def parity_log(line: str) -> None:
     if path:
         with open(path, "a") as f:
             f.write(line + "\n")
+
+
+def gemm_plan_case(group: dict, case: list):
+    """One case of tests/golden/gemm_plans.json.gz -> (GemmArgs, tile_cfg, expected).  group = {"p": [[M, N, K, {field: value}?] ...],
+    "epi", "args": {GemmArgs field: value}?}; case = [tile_cfg, scratch state (index into the header's "ws"), batch, expected].
+    Fields a problem does not name: A = W = C = res = gate = 0x1000 (the planner never dereferences them), lda = ldw = K,
+    ldc = ldres = N, rows_per_batch = M, everything else 0."""
+    from visualcloze_amd import hip
+    tile_cfg, ws, batch, expected = case
+    a = hip.GemmArgs()
+    a.nprob, a.epi, a.batch = len(group["p"]), group["epi"], batch
+    a.splitk_ws, a.splitk_ws_bytes = GEMM_PLAN_WS[ws]
+    for i, (M, N, K, *extra) in enumerate(group["p"]):
+        p = a.p[i]
+        p.A = p.W = p.C = p.res = p.gate = 0x1000
+        p.lda, p.ldw, p.ldc, p.ldres = K, K, N, N
+        p.M, p.N, p.K, p.rows_per_batch = M, N, K, M
+        for k, v in (extra[0] if extra else {}).items():
+            setattr(p, k, v)
+    for k, v in group.get("args", {}).items():
+        setattr(a, k, v)
+    return a, tile_cfg, expected
+
+
+# the split-K scratch on offer: none / the size the product allocates / too small for most remainders (4 MiB)
+GEMM_PLAN_WS = [(0, 0), (0x1000, 2 * 256 * 256 * 192 * 4), (0x1000, 4 << 20)]
+
+
+def gemm_plan_answer(lib, a, tile_cfg):
+    """what vc_gemm_plan answers: the eight integers, or [return code, error text]"""
+    import ctypes as C
+    out = (C.c_int32 * 8)()
+    rc = lib.vc_gemm_plan(C.byref(a), tile_cfg, out)
+    return list(out) if rc == 0 else [rc, lib.vc_last_error().decode()]

@@ -253,6 +253,29 @@ def test_gemm_launch_plans_for_the_flux_shapes():
     assert L.vc_gemm_plan(C.byref(a), 0, (C.c_int32 * 8)()) == -1 and b"multiple of 64" in L.vc_last_error()
 
 
+def test_gemm_plans_match_the_recorded_table():
+    """tests/golden/gemm_plans.json.gz holds what vc_gemm_plan answered at the commit its header names, over a sweep of shapes,
+    epilogues, scratch states and tile_cfg words (tests/golden/make_gemm_plans.py): the library reproduces every record -
+    the eight integers, or the return code and the whole error text - exactly.  Rearranging the planner must not move a plan."""
+    import gzip
+    import json
+    from tests.helpers import gemm_plan_answer, gemm_plan_case
+    from visualcloze_amd import hip
+    L = hip.lib()
+    with gzip.open(os.path.join(REPO, "tests", "golden", "gemm_plans.json.gz"), "rt") as f:
+        table = json.load(f)
+    n, wrong = 0, []
+    for g in table["groups"]:
+        for case in g["cases"]:
+            a, tile_cfg, expected = gemm_plan_case(g, case)
+            got = gemm_plan_answer(L, a, tile_cfg)
+            n += 1
+            if got != expected:
+                wrong.append((g["p"], g["epi"], g.get("args"), case, got))
+    assert n == table["header"]["cases"] and n >= 10000
+    assert not wrong, f"{len(wrong)} of {n} plans differ from the table; the first: {wrong[:5]}"
+
+
 def test_procedural_torch_equals_numpy():
     """tests/procedural.py: the torch evaluation of the closed-form weights (what the GPU tests use at full width) is
     bit-identical to the numpy one (what the golden generators use), chunk boundary included."""

@@ -19,13 +19,13 @@
 #include <type_traits>
 #include "common.h"
 #include "vcloze_internal.h"
+#include "gemm_plan.h"
 
 namespace {
 
 constexpr int BK = 64;
 // raster: ids walk GROUP_M m-tiles, then the n-tiles (an XCD's 32 resident workgroups = GROUP_M x 32/GROUP_M tiles)
 constexpr int GROUP_M = 8;
-constexpr int STREAMK_MIN_K = 6144;     // the stream remainder is not offered below this K (the partial traffic outweighs the short tiles)
 
 // CONV (loader-wave schedule only): the A operand is the im2col matrix of a 3x3 convolution over an NHWC map, gathered
 // on the fly by the loader waves - K-tile kt lies inside tap kt*64 / C, row m is output pixel (m / W, m % W), out-of-
@@ -1095,19 +1095,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const VcGemmArgs arg
   *(u32x4*)((bf16_t*)P.C + crow + n) = o;
 }
 
+// Launch fn with `lds` bytes of dynamic LDS; the first launch of a kernel on a device raises its dynamic-LDS limit first
+// (`attr_done` is the caller's flag for exactly this kernel instantiation).
+hipError_t launch_with_lds(VcOncePerDevice& attr_done, void (*fn)(const VcGemmArgs), int lds, dim3 grid, int threads, hipStream_t s, const VcGemmArgs& a) {
+  if (attr_done.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    attr_done.mark();
+  }
+  hipLaunchKernelGGL(fn, grid, dim3(threads), lds, s, a);
+  return hipGetLastError();
+}
+
 // VcGemmArgs.batch = Z > 1: Z instances of every problem, grid (tiles, Z), the 128x128 tile with the plain bias epilogue
 hipError_t launch_zbatch(const VcGemmArgs& a, int total_tiles, hipStream_t s) {
   constexpr int BM = 128, BN = 128, NT = 4 * 64, LDS_STAGES = 2 * (BM + BN) * BK * 2, LDS_EPI = BM * (BN * 2 + 16);
   constexpr int LDS = LDS_STAGES > LDS_EPI ? LDS_STAGES : LDS_EPI;
   void (*fn)(const VcGemmArgs) = gemm_bf16_kernel<BM, BN, 2, 2, VC_EPI_BIAS, 0, false, false, false, true>;
   static VcOncePerDevice attr_done;
-  if (attr_done.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_done.mark();
-  }
-  hipLaunchKernelGGL(fn, dim3(total_tiles, a.batch), dim3(NT), LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds(attr_done, fn, LDS, dim3(total_tiles, a.batch), NT, s, a);
 }
 
 // First launch of the remainder: sk_rem * sk_S work items of the 256x192 loader-wave kernel, each over K / sk_S, no epilogue
@@ -1115,13 +1121,7 @@ hipError_t launch_splitk_slices(const VcGemmArgs& a, hipStream_t s) {
   constexpr int BM = 256, BN = 192, NT = 12 * 64, LDS = (2 * BM + 3 * BN) * BK * 2;
   void (*fn)(const VcGemmArgs) = gemm_bf16_kernel<BM, BN, 4, 2, VC_EPI_BIAS, 2, false, false, true>;
   static VcOncePerDevice attr_done;
-  if (attr_done.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_done.mark();
-  }
-  hipLaunchKernelGGL(fn, dim3(a.sk_stream > 0 ? a.sk_stream : a.sk_rem * a.sk_S), dim3(NT), LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds(attr_done, fn, LDS, dim3(a.sk_stream > 0 ? a.sk_stream : a.sk_rem * a.sk_S), NT, s, a);
 }
 
 hipError_t launch_splitk_reduce(const VcGemmArgs& a, hipStream_t s) {
@@ -1162,13 +1162,7 @@ hipError_t launch_cfg(const VcGemmArgs& a, int total_tiles, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
   static VcOncePerDevice attr_done[5];
-  if (attr_done[a.epi].need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_done[a.epi].mark();
-  }
-  hipLaunchKernelGGL(fn, dim3(PERSIST ? std::min(total_tiles, vc_cu_count() / 8 * 8) : total_tiles), dim3(NT), LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds(attr_done[a.epi], fn, LDS, dim3(PERSIST ? std::min(total_tiles, vc_cu_count() / 8 * 8) : total_tiles), NT, s, a);
 }
 
 // 3x3 convolution over an NHWC map as ONE GEMM launch: the loader waves gather the im2col rows on the fly.
@@ -1181,14 +1175,7 @@ hipError_t launch_conv(const VcGemmArgs& a, int total_tiles, hipStream_t s) {
   void (*fn)(const VcGemmArgs) = a.epi == VC_EPI_GATE_RES ? gemm_bf16_kernel<BM, BN, 4, 2, VC_EPI_GATE_RES, 2, true>
                                                           : gemm_bf16_kernel<BM, BN, 4, 2, VC_EPI_BIAS, 2, true>;
   static VcOncePerDevice attr_done[2];
-  const int k = a.epi == VC_EPI_GATE_RES ? 1 : 0;
-  if (attr_done[k].need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_done[k].mark();
-  }
-  hipLaunchKernelGGL(fn, dim3(total_tiles), dim3(NT), LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds(attr_done[a.epi == VC_EPI_GATE_RES ? 1 : 0], fn, LDS, dim3(total_tiles), NT, s, a);
 }
 
 }  // namespace
@@ -1222,44 +1209,14 @@ int vc_conv3x3_launch(const void* x, const void* w, const void* bias, void* out,
 
 namespace {
 
-constexpr int cfg_bm[6] = {0, 128, 256, 256, 256, 256}, cfg_bn[6] = {0, 128, 128, 256, 192, 288};
+using vcplan::Launch;
+static_assert(BK == vcplan::BK, "the planner counts K-iterations of the kernels' K-tile");
 
-// Cost model fitted on MI355X (M=3968 FLUX shapes): time = block-rounds on 256 CUs x (tile area x (K + fixed
-// prologue/epilogue charge) / streaming efficiency of that tile).  Candidates: 128x128 simple loop (2 blocks per
-// CU; small or skinny problems), 256x192 with loader waves (1 block per CU), which beat the 256x256 / 256x192
-// ping-pong and the 256x288 tiles on every FLUX shape in an interleaved A/B (tools/gemm_ab.py; those stay
-// selectable by number), and its 256x128 sibling.  For M <= 4096, 256x192 gives N=3072 / 9216 / 12288 exactly
-// 1 / 3 / 4 rounds.
-struct TilePlan { int tile_cfg, pp; double cost; };
-constexpr int N_CAND = 3;
-constexpr int cand[N_CAND] = {1, 4, 2};
-constexpr int cand_pp[N_CAND] = {0, 2, 2};        // 256x128 with loaders: more blocks when M is short (L = 1664: 168 vs 112)
-constexpr double cand_eff[N_CAND] = {0.55, 0.94, 0.84}, cand_ovh[N_CAND] = {500.0, 350.0, 350.0};
-
-inline long tiles_of(const VcGemmArgs& a, int c) {
-  long tiles = 0;
-  for (int i = 0; i < a.nprob; ++i) {
-    const int rows = a.p[i].M - a.p[i].m_begin;
-    if (rows > 0) tiles += (long)((rows + cfg_bm[c] - 1) / cfg_bm[c]) * ((a.p[i].N + cfg_bn[c] - 1) / cfg_bn[c]);
-  }
-  return tiles;
-}
-TilePlan best_tile(const VcGemmArgs& a) {
-  TilePlan best{0, 0, 1e300};
-  for (int ci = 0; ci < N_CAND; ++ci) {
-    const int c = cand[ci];
-    const int per_cu = (c == 1) ? 2 : 1;
-    const long n_cu = vc_cu_count();
-    const long rounds = (tiles_of(a, c) + n_cu * per_cu - 1) / (n_cu * per_cu);
-    const double t = rounds * (per_cu * (double)cfg_bm[c] * cfg_bn[c] * ((double)a.p[0].K + cand_ovh[ci]) / cand_eff[ci]);
-    if (t < best.cost) best = TilePlan{c, cand_pp[ci], t};
-  }
-  return best;
-}
-
-int launch_tiles(VcGemmArgs a, int tile_cfg, int pp, bool want_persist, hipStream_t s, char* err, int errlen, int splitk_S = 0, int stream_items = 0) {
-  if (tile_cfg < 1 || tile_cfg > 5 || pp > 2 || (pp == 1 && tile_cfg < 3) || (pp == 2 && tile_cfg != 4 && tile_cfg != 2)) { snprintf(err, errlen, "gemm: bad tile_cfg %d", tile_cfg); return VC_ERR_ARG; }
-  const int bm = cfg_bm[tile_cfg], bn = cfg_bn[tile_cfg];
+int launch_tiles(const Launch& l, bool want_persist, hipStream_t s, char* err, int errlen) {
+  const int tile = l.tile, pp = l.pp;
+  if (!vcplan::tile_form_exists(tile, pp)) { snprintf(err, errlen, "gemm: bad tile_cfg %d", tile); return VC_ERR_ARG; }
+  const int bm = vcplan::TILES[tile].bm, bn = vcplan::TILES[tile].bn;
+  VcGemmArgs a = l.args;
   int total = 0, np = 0;
   for (int i = 0; i < a.nprob; ++i) {       // problems left without rows by a split are dropped from the grid
     if (a.p[i].M - a.p[i].m_begin <= 0) continue;
@@ -1274,37 +1231,35 @@ int launch_tiles(VcGemmArgs a, int tile_cfg, int pp, bool want_persist, hipStrea
   a.nprob = np;
   a.sk_full = total; a.sk_rem = 0; a.sk_S = 1; a.sk_stream = 0;
   if (a.batch > 1) {
-    if (tile_cfg != 1 || pp != 0 || a.epi != VC_EPI_BIAS) { snprintf(err, errlen, "gemm: batch > 1 runs on the 128x128 tile with VC_EPI_BIAS"); return VC_ERR_ARG; }
+    if (tile != 1 || pp != 0 || a.epi != VC_EPI_BIAS) { snprintf(err, errlen, "gemm: batch > 1 runs on the 128x128 tile with VC_EPI_BIAS"); return VC_ERR_ARG; }
     const hipError_t ez = launch_zbatch(a, total, s);
     if (ez != hipSuccess) { snprintf(err, errlen, "gemm batch launch: %s", hipGetErrorString(ez)); return VC_ERR_HIP; }
     return VC_OK;
   }
-  if (splitk_S > 1) {      // the tiles beyond the last whole round of the CUs run as splitk_S K-slices each (plan_gemm decided)
+  // the tiles beyond the last whole round of the CUs run as splitk_S K-slices each, or as stream_items work items over their
+  // flattened K-iterations (stream form) - plan_gemm decided; both on the 256x192 loader-wave tile
+  if (l.splitk_S > 1 || l.stream_items > 0) {
     const int n_cu = vc_cu_count();
     const int full = total / n_cu * n_cu, rem = total - full;
-    if (tile_cfg != 4 || pp != 2 || a.epi == VC_EPI_QKV) { snprintf(err, errlen, "gemm: split-K runs on the 256x192 loader-wave tile, not with VC_EPI_QKV"); return VC_ERR_ARG; }
-    if (rem > 0) {
-      if (!a.splitk_ws || a.splitk_ws_bytes < (int64_t)rem * splitk_S * bm * bn * 4) {
-        snprintf(err, errlen, "gemm: split-K of %d tiles x %d slices needs %lld bytes of splitk_ws (have %lld)", rem, splitk_S,
-                 (long long)rem * splitk_S * bm * bn * 4, (long long)(a.splitk_ws ? a.splitk_ws_bytes : 0)); return VC_ERR_ARG; }
+    if (tile != vcplan::LW192.tile || pp != vcplan::LW192.pp || a.epi == VC_EPI_QKV) { snprintf(err, errlen, "gemm: split-K runs on the 256x192 loader-wave tile, not with VC_EPI_QKV"); return VC_ERR_ARG; }
+    if (rem > 0 && l.splitk_S > 1) {
+      if (!a.splitk_ws || a.splitk_ws_bytes < (int64_t)rem * l.splitk_S * bm * bn * 4) {
+        snprintf(err, errlen, "gemm: split-K of %d tiles x %d slices needs %lld bytes of splitk_ws (have %lld)", rem, l.splitk_S,
+                 (long long)rem * l.splitk_S * bm * bn * 4, (long long)(a.splitk_ws ? a.splitk_ws_bytes : 0)); return VC_ERR_ARG; }
       for (int i = 0; i < np; ++i)
-        if (a.p[i].K / BK < splitk_S) { snprintf(err, errlen, "gemm: K=%d is too short for %d slices", a.p[i].K, splitk_S); return VC_ERR_ARG; }
-      a.sk_full = full; a.sk_rem = rem; a.sk_S = splitk_S;
-    }
-  } else if (stream_items > 0) {      // ... or as stream_items work items over their flattened K-iterations (stream form)
-    const int n_cu = vc_cu_count();
-    const int full = total / n_cu * n_cu, rem = total - full;
-    if (tile_cfg != 4 || pp != 2 || a.epi == VC_EPI_QKV) { snprintf(err, errlen, "gemm: split-K runs on the 256x192 loader-wave tile, not with VC_EPI_QKV"); return VC_ERR_ARG; }
-    if (rem > 0) {
-      if (stream_items < rem || stream_items > 4096) { snprintf(err, errlen, "gemm: %d stream items for %d remainder tiles", stream_items, rem); return VC_ERR_ARG; }
-      if (!a.splitk_ws || a.splitk_ws_bytes < (int64_t)stream_items * 2 * bm * bn * 4) {
-        snprintf(err, errlen, "gemm: stream split-K with %d work items needs %lld bytes of splitk_ws (have %lld)", stream_items,
-                 (long long)stream_items * 2 * bm * bn * 4, (long long)(a.splitk_ws ? a.splitk_ws_bytes : 0)); return VC_ERR_ARG; }
+        if (a.p[i].K / BK < l.splitk_S) { snprintf(err, errlen, "gemm: K=%d is too short for %d slices", a.p[i].K, l.splitk_S); return VC_ERR_ARG; }
+      a.sk_S = l.splitk_S;
+    } else if (rem > 0) {
+      if (l.stream_items < rem || l.stream_items > 4096) { snprintf(err, errlen, "gemm: %d stream items for %d remainder tiles", l.stream_items, rem); return VC_ERR_ARG; }
+      if (!a.splitk_ws || a.splitk_ws_bytes < (int64_t)l.stream_items * 2 * bm * bn * 4) {
+        snprintf(err, errlen, "gemm: stream split-K with %d work items needs %lld bytes of splitk_ws (have %lld)", l.stream_items,
+                 (long long)l.stream_items * 2 * bm * bn * 4, (long long)(a.splitk_ws ? a.splitk_ws_bytes : 0)); return VC_ERR_ARG; }
       for (int i = 1; i < np; ++i)
         if (a.p[i].K != a.p[0].K) { snprintf(err, errlen, "gemm: stream split-K needs one K for all problems"); return VC_ERR_ARG; }
-      a.sk_full = full; a.sk_rem = rem; a.sk_stream = stream_items;
+      a.sk_stream = l.stream_items;
       a.sk_S = 2;                     // (marks "remainder split" for the code below; the stream form reads sk_stream, not sk_S)
     }
+    if (rem > 0) { a.sk_full = full; a.sk_rem = rem; }
   }
   // VC_GEMM_PERSIST + more tiles than CUs on the loader-wave schedule: one persistent workgroup per CU walks them
   // (gemm_bf16_kernel PERSIST).  OPT-IN: bit-identical, and worth +0.05 % steps/s at cfg 2 (-0.4 ... -0.7 % per qkv / MLP-up
@@ -1317,7 +1272,7 @@ int launch_tiles(VcGemmArgs a, int tile_cfg, int pp, bool want_persist, hipStrea
   hipError_t e = hipSuccess;
   if (a.sk_S > 1) total = a.sk_full;        // the whole rounds run as ever (ids [0, sk_full)); the remainder follows below
   if (total > 0)
-  switch (tile_cfg) {
+  switch (tile) {
     case 1: e = launch_cfg<128, 128, 2, 2, 0>(a, total, s); break;
     case 2: e = pp == 2 ? (persist ? launch_cfg<256, 128, 4, 2, 2, true>(a, total, s) : launch_cfg<256, 128, 4, 2, 2>(a, total, s))
                         : launch_cfg<256, 128, 4, 2, 0>(a, total, s); break;
@@ -1337,195 +1292,28 @@ int launch_tiles(VcGemmArgs a, int tile_cfg, int pp, bool want_persist, hipStrea
 
 }  // namespace
 
-static int validate_gemm(VcGemmArgs& a, char* err, int errlen) {
-  if (a.nprob < 1 || a.nprob > VC_GEMM_MAX_PROBLEMS) { snprintf(err, errlen, "gemm: nprob must be 1..%d", VC_GEMM_MAX_PROBLEMS); return VC_ERR_ARG; }
-  for (int i = 0; i < a.nprob; ++i) {
-    VcGemmProblem& p = a.p[i];
-    p.m_begin = 0;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0) { snprintf(err, errlen, "gemm: empty problem %d (M=%d N=%d K=%d)", i, p.M, p.N, p.K); return VC_ERR_ARG; }
-    if (p.K % BK) { snprintf(err, errlen, "gemm: K=%d must be a multiple of %d", p.K, BK); return VC_ERR_ARG; }
-    if (p.N % 8 || p.ldc % 8 || p.lda % 8) { snprintf(err, errlen, "gemm: need N, ldc, lda multiples of 8 (N=%d ldc=%ld lda=%ld)", p.N, (long)p.ldc, (long)p.lda); return VC_ERR_ARG; }
-    if (!p.A || !p.W || !p.C) { snprintf(err, errlen, "gemm: null operand"); return VC_ERR_ARG; }
-    if (p.a_rpb < 0 || p.c_rpb < 0 || p.a_bstride % 8 || p.c_bstride % 8 || (p.c_rpb > 0 && p.res && p.ldres != p.ldc)) {
-      snprintf(err, errlen, "gemm: bad batch-strided row description"); return VC_ERR_ARG; }
-    if ((p.a_rpb > 0 ? (uint64_t)((p.M + p.a_rpb - 1) / p.a_rpb) * (uint64_t)p.a_bstride : 0) >= (1ull << 32) ||
-        (uint64_t)(p.a_rpb > 0 ? p.a_rpb : p.M) * (uint64_t)p.lda >= (1ull << 32) || (uint64_t)p.N * (uint64_t)p.ldw >= (1ull << 32) || (p.ldw != 0 && p.ldw < p.K) || p.ldw % 8) {
-      snprintf(err, errlen, "gemm: operand exceeds 32-bit element offsets"); return VC_ERR_ARG; }
-    // the loader-wave kernels address A with 32-bit BYTE offsets against the operand, W with byte offsets against its n-tile
-    // (the largest element offset of A the kernel forms, + one K-tile: batch-strided rows may overlap or leave gaps, so both
-    // terms count - advisor r04)
-    const uint64_t a_last = p.a_rpb > 0 ? (uint64_t)((p.M - 1) / p.a_rpb) * (uint64_t)p.a_bstride + (uint64_t)(p.a_rpb - 1) * (uint64_t)p.lda
-                                        : (uint64_t)(p.M - 1) * (uint64_t)p.lda;
-    if (a_last + (uint64_t)p.K + 64 >= (1ull << 31) || (uint64_t)288 * (uint64_t)p.ldw >= (1ull << 31)) {
-      snprintf(err, errlen, "gemm: A operand spanning 4 GB or more (2^31 bf16 elements; or a W row stride beyond 7 M elements) is not supported"); return VC_ERR_ARG; }
-    if (a.epi == VC_EPI_GATE_RES && (!p.res || !p.gate || p.rows_per_batch <= 0 || p.ldres % 8 || p.gate_bstride % 8 || a.gate_step_stride % 8)) {
-      snprintf(err, errlen, "gemm: gate/residual epilogue needs res, gate, rows_per_batch"); return VC_ERR_ARG; }
-    if (a.epi == VC_EPI_QKV && p.kn_heads != 0 && (p.kn_heads < 0 || p.N != 384 * p.kn_heads || (p.vt && p.vt_col0 != 256 * p.kn_heads) || p.vt_rpb <= 0 ||
-                                                  ((p.kn_scale || p.qn_scale) && (!p.kn_rope || p.vt_row0 < 0 || p.kn_rope_bstride < 0)))) {
-      snprintf(err, errlen, "gemm: head-permuted qkv needs N = 3 * 128 * kn_heads (N=%d kn_heads=%d), vt_col0 = 2 * 128 * kn_heads, the row geometry "
-                            "vt_rpb / vt_row0, and with kn_scale / qn_scale a rope table", p.N, p.kn_heads); return VC_ERR_ARG; }
-    if ((a.epi != VC_EPI_QKV || p.kn_heads == 0) && (p.kn_heads != 0 || p.kn_scale || p.qn_scale || p.qn_prescale)) {
-      snprintf(err, errlen, "gemm: kn_heads / kn_scale / qn_scale belong to VC_EPI_QKV with head-permuted weights"); return VC_ERR_ARG; }
-    if (p.qn_prescale && !p.qn_scale) { snprintf(err, errlen, "gemm: qn_prescale without qn_scale"); return VC_ERR_ARG; }
-    if (a.epi == VC_EPI_QKV && p.vt && (p.vt_rpb <= 0 || p.vt_col0 < 0 || p.vt_col0 % 8 || p.vt_col0 >= p.N || p.vt_row0 < 0 ||
-                                        p.vt_lpad < p.vt_row0 + p.vt_rpb || p.vt_bstride < (int64_t)(p.N - p.vt_col0) * p.vt_lpad)) {
-      snprintf(err, errlen, "gemm: bad V^T description (vt_col0=%d vt_rpb=%d vt_row0=%d vt_lpad=%d vt_bstride=%ld)", p.vt_col0, p.vt_rpb,
-               p.vt_row0, p.vt_lpad, (long)p.vt_bstride); return VC_ERR_ARG; }
-  }
-  if (a.epi < 0 || a.epi > VC_EPI_QKV) { snprintf(err, errlen, "gemm: unknown epilogue %d", a.epi); return VC_ERR_ARG; }
-  if (a.batch < 0 || a.batch > 65535) { snprintf(err, errlen, "gemm: batch must be 0..65535"); return VC_ERR_ARG; }
-  if (a.batch > 1) {
-    if (a.epi != VC_EPI_BIAS) { snprintf(err, errlen, "gemm: batch > 1 supports VC_EPI_BIAS only"); return VC_ERR_ARG; }
-    for (int i = 0; i < a.nprob; ++i) {
-      const VcGemmProblem& p = a.p[i];
-      if (p.a_zstride % 8 || p.w_zstride % 8 || p.c_zstride % 8 || p.a_zstride < 0 || p.w_zstride < 0 || p.c_zstride < 0 || p.a_rpb || p.c_rpb ||
-          (uint64_t)a.batch * (uint64_t)p.a_zstride >= (1ull << 40) || (uint64_t)a.batch * (uint64_t)p.w_zstride >= (1ull << 40)) {
-        snprintf(err, errlen, "gemm: batch strides must be non-negative multiples of 8 elements (plain rows only)"); return VC_ERR_ARG; }
-    }
-  }
-  return VC_OK;
-}
-
-// The launch plan of one vc_gemm call: cut = first row of the second launch (0 = one launch); tile / pp of the two launches.
-struct GemmPlan { int cut, tile1, pp1, tile2, pp2, sk_S = 0, sk_tiles = 0, sk_stream = 0; };
-static GemmPlan plan_gemm(const VcGemmArgs& a, int tile_cfg) {
-  const int force_cut = (tile_cfg >> 8) & 255;         // tests: cut problem 0 at row force_cut * 256
-  const int force_sk = (tile_cfg >> 16) & 15;          // tests / A-B: VC_GEMM_SPLITK(S)
-  const bool no_split = (tile_cfg & VC_GEMM_NO_SPLIT) != 0, no_splitk = (tile_cfg & VC_GEMM_NO_SPLITK) != 0;
-  const int tile_cfg_flags = tile_cfg;
-  tile_cfg &= 63;
-  if (a.batch > 1) return GemmPlan{0, 1, 0, 0, 0};          // Z instances per problem: the 128x128 tile (grid (tiles, Z))
-  const long n_cus = vc_cu_count();
-  auto sk_plan = [&](int S) {
-    const long total = tiles_of(a, 4), rem = total % n_cus;
-    GemmPlan pl{0, 4, 2, 0, 0};
-    if (rem > 0) { pl.sk_S = S; pl.sk_tiles = (int)rem; }
-    return pl;
-  };
-  // stream form: n work items share the remainder's K-iterations evenly (each >= ~12 iterations, at most one per CU)
-  auto stream_plan = [&]() {
-    const long total = tiles_of(a, 4), rem = total % n_cus;
-    GemmPlan pl{0, 4, 2, 0, 0};
-    if (rem > 0) {
-      long n = rem * (a.p[0].K / BK) / 12;
-      n = n < rem ? rem : n > n_cus ? n_cus : n;
-      pl.sk_stream = (int)n; pl.sk_tiles = (int)rem;
-    }
-    return pl;
-  };
-  if (tile_cfg_flags & VC_GEMM_STREAMK) return stream_plan();
-  if (force_sk >= 2) return sk_plan(force_sk > 8 ? 8 : force_sk);
-  for (int i = 0; i < a.nprob; ++i)      // heads are normalised inside the epilogue: every head must lie in one 192-wide tile
-    if (a.epi == VC_EPI_QKV && (a.p[i].kn_scale || a.p[i].qn_scale)) return GemmPlan{0, 4, tile_cfg != 0 && ((tile_cfg >> 4) & 3) != 2 ? (tile_cfg >> 4) & 3 : 2, 0, 0};
-  if (tile_cfg != 0) return GemmPlan{0, tile_cfg & 15, (tile_cfg >> 4) & 3, 0, 0};
-  const TilePlan whole = best_tile(a);
-  // SPLIT-K REMAINDER: the 256x192 tiles are R whole rounds of the CUs plus r tiles - run those r as r * S slices of K / S
-  // (S <= 8, r * S <= CUs: ONE short round) that leave f32 partial tiles for a small second launch, instead of a second round
-  // at r / CUs fill or a narrower tile for everything.  Priced in the units of best_tile (one 256x192 tile of K = 15360 on its CU
-  // = 8.2e8 units = 255 us: 3.2e6 units per us): a slice pays its own prologue and the partial store instead of an epilogue
-  // (+150), the partials are written and read once at ~4 TB/s, the second launch costs a dependent kernel boundary (~3 us).
-  // Taken at >= 7 % under the best one-launch plan: SDEdit stage (L = 4608: 288 tiles = 256 + 32 x 8 slices, K = 12288 /
-  // 15360) and cfg 1 (L = 1664: 112 tiles x 2 slices); never at K = 3072 (the partial traffic outweighs 1 / S of a short tile).
-  GemmPlan sk{0, 0, 0, 0, 0};
-  double sk_cost = 1e300;
-  if (!no_splitk && a.splitk_ws && a.epi != VC_EPI_QKV) {
-    const long total = tiles_of(a, 4), R = total / n_cus, rem = total % n_cus;
-    const int nk = a.p[0].K / BK;
-    int S = rem > 0 ? (int)(n_cus / rem) : 0;
-    if (S > 8) S = 8;
-    if (S > nk / 8) S = nk / 8;
-    bool same_k = true;
-    for (int i = 1; i < a.nprob; ++i) same_k = same_k && a.p[i].K == a.p[0].K;
-    const double bytes = (double)rem * S * cfg_bm[4] * cfg_bn[4] * 4;
-    if (S >= 2 && same_k && bytes <= (double)a.splitk_ws_bytes) {
-      const double area = (double)cfg_bm[4] * cfg_bn[4] / cand_eff[1];
-      const double cost = R * area * (a.p[0].K + cand_ovh[1]) + area * ((double)a.p[0].K / S + cand_ovh[1] + 150.0) + (2.0 * bytes / 4e6 + 3.0) * 3.2e6;
-      if (cost < 0.93 * whole.cost) { sk = sk_plan(S); sk_cost = cost; }
-    }
-  }
-  // STREAM REMAINDER: more than half a round of tiles beyond the whole rounds (no uniform S >= 2 fits one round): every CU takes
-  // f = rem / CUs of a tile's K-iterations, at most two segments, <= 3 partial tiles per remainder tile.  Decided by measurement,
-  // not by the model (which prices a partly filled round at its full length; under the power cap it costs ~0.85 of one at 81 %
-  // fill): interleaved whole steps, profiles/r05d_ab_*.log - cfg 3's N = 3072 launches (416 tiles = 256 + 160, f = 0.625: instead
-  // of the row cut into 256 + 240 narrower tiles) +1.7 % per step, all of it from K >= 12288 (K = 3072 included: +0.0 %);
-  // cfg 5's (464 = 256 + 208, f = 0.81: instead of a second round at 81 % fill) -1.2 %, with K = 3072 -2.1 %.  Taken for
-  // 0.5 < f <= 0.7 and K >= STREAMK_MIN_K.
-  if (!no_splitk && sk.sk_S == 0 && a.splitk_ws && a.epi != VC_EPI_QKV) {
-    const long total = tiles_of(a, 4), R = total / n_cus, rem = total % n_cus;
-    bool same_k = true;
-    for (int i = 1; i < a.nprob; ++i) same_k = same_k && a.p[i].K == a.p[0].K;
-    const bool prefer = (tile_cfg_flags & VC_GEMM_PREFER_STREAMK) != 0, any_k = (tile_cfg_flags & VC_GEMM_STREAMK_ANY_K) != 0;
-    if (R >= 1 && 2 * rem > n_cus && same_k && (a.p[0].K >= STREAMK_MIN_K || any_k) && (double)n_cus * 2 * cfg_bm[4] * cfg_bn[4] * 4 <= (double)a.splitk_ws_bytes) {
-      // (advisor r05: only where the one-launch plan would have chosen the 256x192 tile itself - at N = 256 or 4096 a 192-wide
-      // tile wastes columns and another tile may cost far less than any remainder scheme on this one)
-      if (prefer || any_k || (10 * rem <= 7 * n_cus && whole.tile_cfg == 4)) return stream_plan();
-    }
-  }
-  // Block-round quantisation: cut problem 0's rows where the 256x192 tiles above the cut are (nearly) whole rounds of the 256
-  // CUs and price the remainder with the tile that suits it.  The two launches follow each other on the stream (the first
-  // has a flat tail by construction); a cut is taken when the model says it saves >= 10 % and both launches fill their rounds.
-  // The model over-credits by an order of magnitude: under the board's power limit a partly filled round runs at a higher
-  // clock, so quantisation costs far less than its fill factor.  Interleaved A/B, steps/s with / without cuts: L = 6656 (the
-  // N = 3072 launches: 416 tiles -> 256 + 240, model -12.7 % per launch) 9.846 / 9.804 = +0.4 %; L = 7424 (N = 12288 launches
-  // cut at 6144 rows, model -6.3 %) 8.683 / 8.693 = -0.1 % - hence the 10 % bar.
-  int cut = 0;
-  TilePlan rest_plan{0, 0, 0};
-  double best_cut = 1e300;
-  if (!no_split || force_cut > 0) {
-    double best = force_cut > 0 ? 1e300 : 0.90 * whole.cost;
-    const int tn = (a.p[0].N + cfg_bn[4] - 1) / cfg_bn[4];
-    const int mt_all = (a.p[0].M + 255) / 256;
-    for (int mt = 1; mt <= mt_all; ++mt) {
-      if (force_cut > 0 && mt != force_cut) continue;
-      const int rows = mt * 256 < a.p[0].M ? mt * 256 : a.p[0].M;
-      if (rows == a.p[0].M && a.nprob == 1) break;            // nothing left for the second launch
-      const long n_cu = vc_cu_count();
-      const long tiles1 = (long)mt * tn, rounds1 = (tiles1 + n_cu - 1) / n_cu;
-      if (force_cut == 0 && tiles1 < 0.97 * (double)n_cu * rounds1) continue;
-      const double t1 = rounds1 * ((double)cfg_bm[4] * cfg_bn[4] * ((double)a.p[0].K + cand_ovh[1]) / cand_eff[1]);
-      VcGemmArgs rest = a;
-      rest.p[0].m_begin = rows;
-      const TilePlan rp = best_tile(rest);
-      // the remainder must fill its own rounds too: a half-empty second launch loses more than the model credits it with
-      // (measured: L = 4608 cut into 4096 + 512 rows, 144 - 192 tiles in the second launch: -0.7 % steps/s)
-      const int per_cu = rp.tile_cfg == 1 ? 2 : 1;
-      const long tiles2 = tiles_of(rest, rp.tile_cfg), slots2 = (tiles2 + n_cu * per_cu - 1) / (n_cu * per_cu) * n_cu * per_cu;
-      if (force_cut == 0 && tiles2 < 0.9 * slots2) continue;
-      if (t1 + rp.cost < best) { best = t1 + rp.cost; cut = rows; rest_plan = rp; best_cut = best; }
-    }
-  }
-  if (sk.sk_S > 1 && (cut == 0 || sk_cost <= best_cut)) return sk;
-  if (cut == 0) return GemmPlan{0, whole.tile_cfg, whole.pp, 0, 0};
-  return GemmPlan{cut, 4, 2, rest_plan.tile_cfg, rest_plan.pp};
-}
-
-// tile_cfg: 0 = auto, 1 = 128x128 (4 waves), 2 = 256x128, 3 = 256x256, 4 = 256x192, 5 = 256x288 (8 waves each);
-// +16 = ping-pong main loop (3, 4, 5), +32 = ping-pong with loader waves (2, 4); VC_GEMM_NO_SPLIT / (k << 8): see the header
 int vc_gemm_launch(VcGemmArgs a, int tile_cfg, hipStream_t s, char* err, int errlen) {
-  int rc = validate_gemm(a, err, errlen);
+  int rc = vcplan::validate_gemm(a, err, errlen);
   if (rc != VC_OK) return rc;
-  const GemmPlan pl = plan_gemm(a, tile_cfg);
-  const bool want_persist = (tile_cfg & VC_GEMM_PERSIST) != 0;
-  if (pl.cut == 0) return launch_tiles(a, pl.tile1, pl.pp1, want_persist, s, err, errlen, pl.sk_S, pl.sk_stream);
-  VcGemmArgs first = a;
-  first.nprob = 1;
-  first.p[0].M = pl.cut;                                       // rows [0, cut) of problem 0 on the 256x192 loader-wave tile
-  rc = launch_tiles(first, pl.tile1, pl.pp1, want_persist, s, err, errlen);
-  if (rc != VC_OK) return rc;
-  a.p[0].m_begin = pl.cut;
-  return launch_tiles(a, pl.tile2, pl.pp2, want_persist, s, err, errlen);
+  const vcplan::TileRequest req = vcplan::decode_tile_cfg(tile_cfg);
+  Launch launches[2];
+  const int n = vcplan::plan_launches(a, vcplan::plan_gemm(a, req, vc_cu_count()), launches);
+  for (int i = 0; i < n && rc == VC_OK; ++i) rc = launch_tiles(launches[i], req.persist, s, err, errlen);
+  return rc;
 }
 
 // the plan without the launch: out = {cut row, tile / loader mode of the first (or only) launch, of the second, tiles of both}
 int vc_gemm_plan_impl(VcGemmArgs a, int tile_cfg, int32_t out[8], char* err, int errlen) {
-  const int rc = validate_gemm(a, err, errlen);
+  const int rc = vcplan::validate_gemm(a, err, errlen);
   if (rc != VC_OK) return rc;
-  const GemmPlan pl = plan_gemm(a, tile_cfg);
+  const vcplan::GemmPlan pl = vcplan::plan_gemm(a, vcplan::decode_tile_cfg(tile_cfg), vc_cu_count());
   if (pl.tile1 < 1 || pl.tile1 > 5) { snprintf(err, errlen, "gemm: bad tile_cfg %d", pl.tile1); return VC_ERR_ARG; }
+  Launch launches[2];
+  const int n = vcplan::plan_launches(a, pl, launches);
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) tiles += vcplan::tiles_of(launches[i].args, launches[i].tile);
   out[0] = pl.cut; out[1] = pl.tile1; out[2] = pl.pp1; out[3] = pl.tile2; out[4] = pl.pp2;
-  VcGemmArgs first = a, rest = a;
-  if (pl.cut) { first.nprob = 1; first.p[0].M = pl.cut; rest.p[0].m_begin = pl.cut; }
-  out[5] = (int32_t)(tiles_of(first, pl.tile1) + (pl.cut ? tiles_of(rest, pl.tile2) : 0));
+  out[5] = (int32_t)tiles;
   out[6] = pl.sk_stream > 0 ? -pl.sk_stream : pl.sk_S; out[7] = pl.sk_tiles;
   return VC_OK;
 }
