@@ -256,6 +256,32 @@ int vc_euler_step(void* x, const void* v, const float* dts, const int32_t* step_
  * reads under autocast.  v == NULL: refresh the shadow only. */
 int vc_euler_step_f32(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, void* stream);
 int vc_step_advance(int32_t* step_ptr, void* stream);
+/* ---- higher-order fixed-grid solvers: what odeint(method="midpoint" | "rk4") runs between model evaluations
+ * (transport/integrators.py:119).  Added WITHOUT a change of VC_ABI_VERSION: a binding detects these entry points (vc_solver_evals,
+ * vc_ode_stage, vc_flux_sample_ode, vc_flux_sample_begin_ode) by SYMBOL - look up vc_solver_evals - not by version.
+ * The step functions are torchdiffeq 0.2.x's fixed-grid solvers as recalled, unpinned against real torchdiffeq (the package was not
+ * available to check against; the same holds for the Euler rule).  With f(t, y) = -model(y || cond, 1 - t), dt = t1 - t0:
+ *   midpoint (2 evaluations)   y_mid = y0 + f0 * half_dt,  half_dt = 0.5 * dt;   y1 = y0 + dt * f(t0 + half_dt, y_mid)
+ *   rk4      (4, 3/8 rule)     k1 = f(t0, y0);  k2 = f(t0 + dt * (1/3), y0 + dt * k1 * (1/3));
+ *                              k3 = f(t0 + dt * (2/3), y0 + dt * (k2 - k1 * (1/3)));  k4 = f(t1, y0 + dt * (k1 - k2 + k3));
+ *                              y1 = y0 + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+ * evaluated left to right with torch's roundings: every intermediate of the bf16 velocities is a bf16 tensor, a bf16 tensor times
+ * the 0-dim f32 device tensor dt multiplies by bf16(dt), times a Python float by that float in f32, and the sum with y0 is bf16 for
+ * a bf16 state, f32 for an f32 state. */
+#define VC_SOLVER_EULER 0
+#define VC_SOLVER_MIDPOINT 1
+#define VC_SOLVER_RK4 2
+/* model evaluations per solver step: 1, 2, 4; VC_ERR_ARG for anything else.  Works without a GPU. */
+int vc_solver_evals(int method);
+/* One stage combination on n elements, method VC_SOLVER_MIDPOINT or VC_SOLVER_RK4.  v: the model's bf16 output of this stage's
+ * evaluation (the drift is -v).  stage >= 0: that stage; stage < 0: (*eval_ptr) % evals - the device-side evaluation counter, so
+ * one captured launch serves every stage.  dt = dts[(*eval_ptr) / evals] (eval_ptr NULL: dts[0]).  y: the state y0, bf16
+ * (state_is_bf16) or F32, read by every stage and replaced by y1 by the LAST one only.  k: bf16 [3][n], receives k1..k3 from rk4's
+ * stages 0..2 and is read by its later stages (midpoint: unused, may be NULL).  y_in: bf16 [n], the NEXT evaluation's input state
+ * - the stage state, or after the last stage bf16(y1), what img_in reads under autocast.  y, v, k, y_in must not overlap.
+ * 16-byte accesses need n % 8 == 0 and 16-byte aligned bases; anything else runs element-wise with the same results. */
+int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, const void* v, void* k, void* y_in,
+                 const float* dts, const int32_t* eval_ptr, int64_t n, void* stream);
 /* SDEdit start state x0 = noise*(1-s) + latent*s with the reference's bf16 roundings (visualcloze.py:221) */
 int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream);
 
@@ -390,7 +416,8 @@ int vc_flux_set_option(void* handle, const char* name, int32_t value);
 int64_t vc_flux_workspace_bytes(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps);
 
 typedef struct VcFluxInputs {   /* everything of model_kwargs that does not change along the trajectory */
-  int32_t B, T, N, max_steps;   /* samples stacked in one launch sequence; text / image tokens; solver steps the workspace holds */
+  int32_t B, T, N, max_steps;   /* samples stacked in one launch sequence; text / image tokens; model EVALUATIONS the workspace holds
+                                   (= solver steps for Euler; steps * vc_solver_evals(method) otherwise) */
   const void* txt;              /* [B, T, context_in_dim] bf16, device */
   const void* y;                /* [B, vec_in_dim] bf16, device */
   const float* guidance;        /* HOST [B], NULL without guidance_embed */
@@ -421,6 +448,18 @@ int vc_flux_sample_begin(void* handle, const void* x, const void* cond, const fl
                          int32_t state_is_bf16, void* stream);
 int vc_flux_sample_steps(void* handle, int32_t n_steps, void* trajectory, void* stream);
 int vc_flux_sample_end(void* handle, void* x_out, void* stream);
+/* The same loop for any VC_SOLVER_* method (sample_euler / sample_begin are the VC_SOLVER_EULER case; steps / end serve every
+ * method and count whole solver STEPS: trajectory receives the state after every step, never a stage state).  A step is
+ * vc_solver_evals(method) replays of ONE captured evaluation whose last node is vc_ode_stage switching on the device-side
+ * evaluation counter; the time embeddings and modulation rows of all (n_points - 1) * evals evaluations are built up front, in
+ * evaluation order: t0 | t0 + half_dt (midpoint), t0 | t0 + dt * (1/3) | t0 + dt * (2/3) | t1 (rk4), formed in f32 and then
+ * rounded to the state's dtype - rk4's last evaluation is at t_grid[n_points - 1], i.e. timesteps = 1 - t1.  An unknown method or
+ * (n_points - 1) * evals > max_steps is VC_ERR_ARG, checked before the device is touched.  The captured step is kept per
+ * (geometry, method). */
+int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                       int32_t state_is_bf16, void* trajectory, void* stream);
+int vc_flux_sample_begin_ode(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
+                             int32_t state_is_bf16, void* stream);
 
 /* ---- the plan's own stopwatch (ABI 10): HIP-event times of the launches of whole evaluations, class by class ----
  * What bench.py's `roofline` leg reports.  With a sample in flight (vc_flux_sample_begin), `evaluations` more evaluations of

@@ -95,6 +95,15 @@ int vc_euler_step(void* x, const void* v, const float* dts, const int32_t* step_
 int vc_euler_step_f32(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, void* stream) {
   return vc_euler_f32_launch(x32, shadow, v, dts, step_ptr, n, S(stream), ERRBUF);
 }
+int vc_solver_evals(int method) {
+  if (vc_evals_of(method)) return vc_evals_of(method);
+  snprintf(g_err, sizeof(g_err), "solver_evals: unknown method %d (VC_SOLVER_EULER, VC_SOLVER_MIDPOINT, VC_SOLVER_RK4)", method);
+  return VC_ERR_ARG;
+}
+int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, const void* v, void* k, void* y_in,
+                 const float* dts, const int32_t* eval_ptr, int64_t n, void* stream) {
+  return vc_ode_stage_launch(method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, S(stream), ERRBUF);
+}
 int vc_step_advance(int32_t* step_ptr, void* stream) { return vc_step_advance_launch(step_ptr, S(stream), ERRBUF); }
 
 int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream) {
@@ -174,7 +183,11 @@ int vc_flux_forward(void* handle, const void* img, const float* timesteps, int32
 }
 int vc_flux_sample_begin(void* handle, const void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                          void* stream) {
-  return vc_flux_sample_begin_impl(handle, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);
+  return vc_flux_sample_begin_impl(handle, VC_SOLVER_EULER, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);
+}
+int vc_flux_sample_begin_ode(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
+                             int32_t state_is_bf16, void* stream) {
+  return vc_flux_sample_begin_impl(handle, method, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);
 }
 int vc_flux_sample_steps(void* handle, int32_t n_steps, void* trajectory, void* stream) {
   return vc_flux_sample_steps_impl(handle, n_steps, trajectory, S(stream), ERRBUF);
@@ -183,12 +196,16 @@ int vc_flux_profile(void* handle, int32_t evaluations, VcFluxLaunchClass* out, i
   return vc_flux_profile_impl(handle, evaluations, out, capacity, count, S(stream), ERRBUF);
 }
 int vc_flux_sample_end(void* handle, void* x_out, void* stream) { return vc_flux_sample_end_impl(handle, x_out, S(stream), ERRBUF); }
-int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
-                         void* trajectory, void* stream) {
-  int rc = vc_flux_sample_begin_impl(handle, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);
+int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                       int32_t state_is_bf16, void* trajectory, void* stream) {
+  int rc = vc_flux_sample_begin_impl(handle, method, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);
   if (rc == VC_OK) rc = vc_flux_sample_steps_impl(handle, n_points - 1, trajectory, S(stream), ERRBUF);
   if (rc == VC_OK) rc = vc_flux_sample_end_impl(handle, x, S(stream), ERRBUF);
   return rc;
+}
+int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                         void* trajectory, void* stream) {
+  return vc_flux_sample_ode(handle, VC_SOLVER_EULER, x, cond, t_grid, n_points, state_is_bf16, trajectory, stream);
 }
 
 /* ---- streams / graphs / events ---- */

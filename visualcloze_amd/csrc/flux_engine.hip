@@ -1,16 +1,18 @@
-// Handle API of include/vcloze_hip.h: Flux.forward (models/model.py:85-124) and the fixed-grid Euler loop around it
-// (transport/integrators.py:106-120) as launch plans over the kernels of this library.  Host code only: it ORDERS launches
+// Handle API of include/vcloze_hip.h: Flux.forward (models/model.py:85-124) and the fixed-grid solver loop around it
+// (transport/integrators.py:106-120: Euler, and midpoint / rk4 as E evaluations per step) as launch plans over the kernels of this library.  Host code only: it ORDERS launches
 // (once per geometry, under stream capture, for the sampling loop); nothing here touches a tensor element except the RoPE
 // angle table, which math.py:102-109 computes in float64 on the host as well.
 //
-// Workspace (caller's device memory), bf16 unless noted; B samples, T text / N image tokens, L = T + N, D hidden, S = max_steps:
+// Workspace (caller's device memory), bf16 unless noted; B samples, T text / N image tokens, L = T + N, D hidden, S = max_steps
+// (model EVALUATIONS: solver steps * evaluations per step):
 //   XI [B*N, D] / XT [B*T, D]  residual streams of the DoubleStream blocks      X   [B*L, D]  joint stream of the SingleStream blocks
 //   XH [B*L, D]   LayerNorm+modulate output (GEMM A operand)                     QKV [B*L, 3D] "B L (K H D)" rows, joint order
 //   VT [B, H, 128, Lp]  V transposed per head (Lp = L rounded up to 64, padding zeroed once)
 //   CAT [B*L, D+mlp]    attn | gelu(mlp) = linear2's input; CAT[:, :D] is also the DoubleStream attention output
 //   HID [B*L, mlp]      MLP hidden of the DoubleStream blocks (image rows first)
-//   MOD [S*B, n_mod]    every modulation vector of every block for every solver step (row s*B + b)
+//   MOD [S*B, n_mod]    every modulation vector of every block for every evaluation (row s*B + b, evaluation order)
 //   XS / COND / XIN / V the ODE state, the conditioning columns, x || cond, the velocity
+//   KS [3][B*N*out] / YIN   k1..k3 of an rk4 step / the input state of the next evaluation (midpoint, rk4: vc_ode_stage)
 #include "common.h"
 #include "vcloze_internal.h"
 #include <math.h>
@@ -37,7 +39,7 @@ struct Err {
 };
 
 struct Buffers {   // the workspace carve-up
-  bf16_t *XI, *XT, *X, *XH, *QKV, *VT, *CAT, *HID, *TXT0, *XIN, *V, *XS, *COND, *MOD, *TEMB, *H1, *TVEC, *GVEC, *YVEC, *VEC, *GE, *GH, *YH;
+  bf16_t *XI, *XT, *X, *XH, *QKV, *VT, *CAT, *HID, *TXT0, *XIN, *V, *XS, *COND, *MOD, *TEMB, *H1, *TVEC, *GVEC, *YVEC, *VEC, *GE, *GH, *YH, *KS, *YIN;
   float *ROPE, *TS, *DTS, *G32, *FREQS, *XS32;
   int32_t *STEP, *KVLEN, *KVGAP;
   void* ATT_SCRATCH = nullptr;
@@ -69,17 +71,18 @@ struct Flux : Buffers {
   // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
   hipGraphExec_t graph = nullptr;      // = graphs.front().second while a sample is in flight
   struct Key {
-    char* base; int B, T, N, S, ragged, gapped, variant, tile, fuse, fuse_vt, state_f32, qkv_heads, fuse_knorm, bound, mlp_first, splitk; hipStream_t s;
+    char* base; int B, T, N, S, ragged, gapped, variant, tile, fuse, fuse_vt, state_f32, qkv_heads, fuse_knorm, bound, mlp_first, splitk, method; hipStream_t s;
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
              variant == o.variant && tile == o.tile && fuse == o.fuse && fuse_vt == o.fuse_vt && state_f32 == o.state_f32 &&
-             qkv_heads == o.qkv_heads && fuse_knorm == o.fuse_knorm && bound == o.bound && mlp_first == o.mlp_first && splitk == o.splitk && s == o.s;
+             qkv_heads == o.qkv_heads && fuse_knorm == o.fuse_knorm && bound == o.bound && mlp_first == o.mlp_first && splitk == o.splitk && method == o.method && s == o.s;
     }
   } key{};
   std::vector<std::pair<Key, hipGraphExec_t>> graphs;
   // sampling state
   int steps_total = 0, steps_done = 0;
   bool state_f32 = false;              // the sample in flight steps an f32 state (XS32; XS is its bf16 shadow)
+  int method = VC_SOLVER_EULER, evals = 1;   // ... with this solver: `evals` replays of the captured evaluation per step
   // host staging (pinned), reused once the copies that read it have completed
   char* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;
@@ -142,6 +145,7 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
   f.TS = c.take<float>((int64_t)S * B);      f.DTS = c.take<float>(S);
   f.G32 = c.take<float>(B);                  f.FREQS = c.take<float>(128);
   f.XS32 = c.take<float>(B * N * out_ch);    // f32 master copy of the ODE state (state_is_bf16 == 0)
+  f.KS = c.take<bf16_t>(3 * B * N * out_ch); f.YIN = c.take<bf16_t>(B * N * out_ch);   // midpoint / rk4 stages (vc_ode_stage)
   f.STEP = c.take<int32_t>(1);               f.KVLEN = c.take<int32_t>(B);  f.KVGAP = c.take<int32_t>(2 * B);
   f.att_scratch_bytes = vc_attention_scratch_bytes_impl();
   f.ATT_SCRATCH = c.take<char>(f.att_scratch_bytes);
@@ -448,12 +452,14 @@ int d2d(void* dst, const void* src, int64_t bytes, hipStream_t s, Err e) {
   return VC_OK;
 }
 
-// Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); the Euler update of XS when `euler`
+// Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it: the
+// Euler update of XS, or the midpoint / rk4 stage combination (state -> YIN, the input of the next evaluation).  step_ptr counts
+// EVALUATIONS (= steps for Euler).
 int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows, void* out, bool euler, hipStream_t s, Err e) {
   const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
   const int in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
   Ctx c{step_ptr, s, (int64_t)B * f.n_mod};
-  if (concat) TRY(vc_concat_cols_launch(f.XS, out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
+  if (concat) TRY(vc_concat_cols_launch(f.method == VC_SOLVER_EULER ? f.XS : f.YIN, out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
   TRY(d2d(f.XT, f.TXT0, (int64_t)B * T * D * 2, s, e));
   TRY(lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e));
   for (auto& w : f.dbl) TRY(double_block(f, c, w, e));
@@ -467,7 +473,11 @@ int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows
   VcGemmProblem p = prob(f.XH + (int64_t)T * D, D, f.final_lin, out ? out : f.V, out_ch, B * N);
   p.a_rpb = N; p.a_bstride = (int64_t)L * D;
   TRY(gemm(f, &p, 1, VC_EPI_BIAS, nullptr, 0, s, e));
-  if (euler) {
+  if (euler && f.method != VC_SOLVER_EULER) {
+    TRY(vc_ode_stage_launch(f.method, -1, f.state_f32 ? (void*)f.XS32 : (void*)f.XS, !f.state_f32, f.V, f.KS, f.YIN, f.DTS, step_ptr,
+                            (int64_t)B * N * out_ch, s, e.buf, e.len));
+    TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
+  } else if (euler) {
     if (f.state_f32) TRY(vc_euler_f32_launch(f.XS32, f.XS, f.V, f.DTS, step_ptr, (int64_t)B * N * out_ch, s, e.buf, e.len));
     else TRY(vc_euler_launch(f.XS, f.V, f.DTS, step_ptr, (int64_t)B * N * out_ch, s, e.buf, e.len));
     TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
@@ -537,10 +547,11 @@ void drop_graph(Flux& f) {
   f.graph = nullptr;
 }
 
-// the hipGraph of ONE solver step: everything step-dependent (modulation rows, dt) is indexed on the device by STEP
+// the hipGraph of ONE evaluation + the solver's update behind it (Euler: one solver step): everything that depends on the
+// evaluation (modulation rows, dt, the stage of a midpoint / rk4 step) is indexed on the device by STEP
 int step_graph(Flux& f, hipStream_t s, Err e) {
   Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.tile_cfg, f.fuse_qnorm, f.fuse_vt, f.state_f32,
-              f.qkv_heads, f.fuse_knorm, f.logit_bound_milli, f.mlp_first, f.splitk, s};
+              f.qkv_heads, f.fuse_knorm, f.logit_bound_milli, f.mlp_first, f.splitk, f.method, s};
   for (size_t i = 0; i < f.graphs.size(); ++i)
     if (f.graphs[i].first == k) {
       auto hit = f.graphs[i];
@@ -784,34 +795,58 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
   return evaluate(f, nullptr, false, img, out, false, s, e);
 }
 
-int vc_flux_sample_begin_impl(void* handle, const void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
-                              hipStream_t s, char* err, int errlen) {
+// the f32 times of the `evals` evaluations of the step t0 -> t1 (dt = t1 - t0), each formed in f32 operation by operation as
+// torch forms `t0 + half_dt`, `t0 + dt * (1/3)`, `t0 + dt * (2/3)` from 0-dim f32 tensors (no contraction into a fused multiply-add)
+void stage_times(int method, float t0, float t1, float dt, float* out) {
+#pragma clang fp contract(off)
+  out[0] = t0;
+  if (method == VC_SOLVER_MIDPOINT) {
+    volatile float half_dt = 0.5f * dt;
+    out[1] = t0 + half_dt;
+  } else if (method == VC_SOLVER_RK4) {
+    volatile float a = dt * (float)(1.0 / 3.0), b = dt * (float)(2.0 / 3.0);
+    out[1] = t0 + a; out[2] = t0 + b; out[3] = t1;
+  }
+}
+
+int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
+                              int32_t state_is_bf16, hipStream_t s, char* err, int errlen) {
   H(handle);
+  const int E = vc_evals_of(method);
+  if (!E) FAIL(VC_ERR_ARG, "flux_sample: unknown solver method %d (VC_SOLVER_EULER, VC_SOLVER_MIDPOINT, VC_SOLVER_RK4)", method);
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample: call vc_flux_prepare first");
   if (!x || !cond || !t_grid) FAIL(VC_ERR_ARG, "flux_sample: null argument");
   const int S = n_points - 1, B = f.B;
-  if (S < 1 || S > f.S) FAIL(VC_ERR_ARG, "flux_sample: %d steps, the prepared workspace holds 1..%d", S, f.S);
-  TRY(stage_begin(f, ((size_t)S * B + S) * sizeof(float) + 512, e));
-  float* ts = stage_take<float>(f, (size_t)S * B);
+  if (S < 1 || (int64_t)S * E > f.S)
+    FAIL(VC_ERR_ARG, "flux_sample: %d steps of %d evaluation(s), the prepared workspace holds 1..%d evaluations", S, E, f.S);
+  const int SE = S * E;
+  TRY(stage_begin(f, ((size_t)SE * B + S) * sizeof(float) + 512, e));
+  float* ts = stage_take<float>(f, (size_t)SE * B);
   float* dts = stage_take<float>(f, S);
   for (int i = 0; i < S; ++i) {
-    // the drift sees t_i in the state's dtype (torchdiffeq _PerturbFunc); the model sees 1 - t (transport.py:384)
-    const float tm = 1.0f - (state_is_bf16 ? bf16_round(t_grid[i]) : t_grid[i]);
-    for (int b = 0; b < B; ++b) ts[(size_t)i * B + b] = tm;
     dts[i] = t_grid[i + 1] - t_grid[i];   // fixed grid: dt = t1 - t0 in f32
+    float te[4];
+    stage_times(method, t_grid[i], t_grid[i + 1], dts[i], te);
+    for (int j = 0; j < E; ++j) {
+      // the drift sees t in the state's dtype (torchdiffeq _PerturbFunc); the model sees 1 - t (transport.py:384)
+      const float tm = 1.0f - (state_is_bf16 ? bf16_round(te[j]) : te[j]);
+      for (int b = 0; b < B; ++b) ts[((size_t)i * E + j) * B + b] = tm;
+    }
   }
-  TRY(stage_send(f, f.TS, ts, (size_t)S * B * sizeof(float), s, e));
+  TRY(stage_send(f, f.TS, ts, (size_t)SE * B * sizeof(float), s, e));
   TRY(stage_send(f, f.DTS, dts, S * sizeof(float), s, e));
   TRY(stage_end(f, s, e));
-  TRY(time_precompute(f, S, 0, s, e));
+  TRY(time_precompute(f, SE, 0, s, e));
   const int64_t n = (int64_t)B * f.N;
   f.state_f32 = !state_is_bf16;
+  f.method = method; f.evals = E;
   if (f.state_f32) {
     TRY(d2d(f.XS32, x, n * f.cfg.out_channels * 4, s, e));
     TRY(vc_euler_f32_launch(f.XS32, f.XS, nullptr, nullptr, nullptr, n * f.cfg.out_channels, s, e.buf, e.len));   // XS = bf16(XS32)
   } else {
     TRY(d2d(f.XS, x, n * f.cfg.out_channels * 2, s, e));
   }
+  if (E > 1) TRY(d2d(f.YIN, f.XS, n * f.cfg.out_channels * 2, s, e));      // the first evaluation reads bf16(y0)
   TRY(d2d(f.COND, cond, n * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
   HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
   if (s) TRY(step_graph(f, s, e));
@@ -828,8 +863,10 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
   const int64_t state_bytes = (int64_t)f.B * f.N * f.cfg.out_channels * (f.state_f32 ? 4 : 2);
   const void* state = f.state_f32 ? (const void*)f.XS32 : (const void*)f.XS;
   for (int i = 0; i < n_steps; ++i) {
-    if (s) HIP(hipGraphLaunch(f.graph, s), "hipGraphLaunch");
-    else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
+    for (int j = 0; j < f.evals; ++j) {      // a step = `evals` replays; the stage is the device-side counter modulo evals
+      if (s) HIP(hipGraphLaunch(f.graph, s), "hipGraphLaunch");
+      else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
+    }
     if (trajectory) TRY(d2d((char*)trajectory + (int64_t)i * state_bytes, state, state_bytes, s, e));
     ++f.steps_done;
   }

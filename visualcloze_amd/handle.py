@@ -1,5 +1,5 @@
 """`FluxHandle`: the handle API of include/vcloze_hip.h (vc_flux_*) behind torch tensors — Flux.forward and the whole
-fixed-grid Euler loop as ONE C call each.  The launch plan lives in csrc/flux_engine.hip; this class
+fixed-grid solver loop (Euler, midpoint, rk4) as ONE C call each.  The launch plan lives in csrc/flux_engine.hip; this class
 binds the prepared (bf16, LoRA-merged) weights by reference-module path, owns the workspace tensors and converts the
 host-side inputs (ids, timesteps, masks) to the plain arrays the ABI takes.  `engine.FluxEngine` is the same plan spelt
 in Python over the op-level ABI; it stays for the un-merged LoRA parity mode and for per-block taps."""
@@ -149,7 +149,7 @@ class FluxHandle:
     def prepare(self, txt, y, guidance, guidance_is_bf16: bool, img_ids, txt_ids, max_steps: int,
                 kv_len: Optional[Sequence[int]] = None, kv_gap: Optional[Sequence[Tuple[int, int]]] = None, stream=None) -> None:
         """txt [B,T,ctx] / y [B,vec] bf16 device tensors; guidance [B] (any device) or None; ids [B,N|T,3]; kv_len B ints;
-        kv_gap B (lo, hi) pairs (model.MaskLayout)."""
+        kv_gap B (lo, hi) pairs (model.MaskLayout).  max_steps bounds model EVALUATIONS: steps * hip.solver_evals(method)."""
         hip._bf16(txt, "txt"); hip._bf16(y, "y")
         B, T = txt.shape[0], txt.shape[1]
         N = img_ids.shape[-2]
@@ -192,13 +192,21 @@ class FluxHandle:
         if x.dtype != want:
             raise hip.VclozeHipError(f"{what}: state_is_bf16={bool(state_is_bf16)} needs a {want} state tensor, got {x.dtype}")
 
-    def sample_begin(self, x, cond, t_grid, state_is_bf16: bool, stream) -> None:
+    @staticmethod
+    def _method(method) -> int:
+        if isinstance(method, str):
+            if method not in hip.SOLVERS:
+                raise hip.VclozeHipError(f"unknown solver {method!r}: the fused loop implements {sorted(hip.SOLVERS)}")
+            return hip.SOLVERS[method]
+        return int(method)
+
+    def sample_begin(self, x, cond, t_grid, state_is_bf16: bool, stream, method="euler") -> None:
         self._state(x, state_is_bf16, "vc_flux_sample_begin"); hip._bf16(cond, "cond")
         if not (x.is_contiguous() and cond.is_contiguous()):
             raise hip.VclozeHipError("vc_flux_sample: contiguous x / cond expected")
         t = _f32(t_grid).reshape(-1)
-        hip._check(hip.lib().vc_flux_sample_begin(self.h, x.data_ptr(), cond.data_ptr(), _fp(t), t.size, int(bool(state_is_bf16)), stream),
-                   "vc_flux_sample_begin")
+        hip._check(hip.lib().vc_flux_sample_begin_ode(self.h, self._method(method), x.data_ptr(), cond.data_ptr(), _fp(t), t.size,
+                                                      int(bool(state_is_bf16)), stream), "vc_flux_sample_begin_ode")
 
     def sample_steps(self, n: int, stream, trajectory=None) -> None:
         hip._check(hip.lib().vc_flux_sample_steps(self.h, n, hip._p(trajectory), stream), "vc_flux_sample_steps")
@@ -215,6 +223,18 @@ class FluxHandle:
 
     def sample_end(self, x_out, stream) -> None:
         hip._check(hip.lib().vc_flux_sample_end(self.h, x_out.data_ptr(), stream), "vc_flux_sample_end")
+
+    def sample_ode(self, method, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
+        """vc_flux_sample_ode: as sample_euler with method "euler" | "midpoint" | "rk4" (or a VC_SOLVER_* code); the prepared
+        max_steps must hold (len(t_grid) - 1) * hip.solver_evals(method) evaluations; trajectory[i] = the state after STEP i"""
+        self._state(x, state_is_bf16, "vc_flux_sample_ode"); hip._bf16(cond, "cond")
+        if trajectory is not None:
+            self._state(trajectory, state_is_bf16, "vc_flux_sample_ode (trajectory)")
+        if not (x.is_contiguous() and cond.is_contiguous()) or (trajectory is not None and not trajectory.is_contiguous()):
+            raise hip.VclozeHipError("vc_flux_sample_ode: contiguous x / cond / trajectory expected")
+        t = _f32(t_grid).reshape(-1)
+        hip._check(hip.lib().vc_flux_sample_ode(self.h, self._method(method), x.data_ptr(), cond.data_ptr(), _fp(t), t.size,
+                                                int(bool(state_is_bf16)), hip._p(trajectory), stream), "vc_flux_sample_ode")
 
     def sample_euler(self, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
         """x [B,N,C] in place (bf16, or f32 with state_is_bf16 False): x(t_grid[0]) -> x(t_grid[-1]); trajectory: optional

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("VC_HIP_LIB") or os.path.join(_HERE, "lib", "libvcloze
 CSRC = os.path.join(_HERE, "csrc")
 
 ABI_VERSION = 11               # VC_ABI_VERSION of include/vcloze_hip.h
+SOLVER_EULER, SOLVER_MIDPOINT, SOLVER_RK4 = 0, 1, 2     # VC_SOLVER_*: the fixed-grid methods of the fused sampling loop
+SOLVERS = {"euler": SOLVER_EULER, "midpoint": SOLVER_MIDPOINT, "rk4": SOLVER_RK4}
 GEMM_MAX_PROBLEMS = 4          # VC_GEMM_MAX_PROBLEMS: grouped problems per vc_gemm launch
 EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_SILU, EPI_QKV = 0, 1, 2, 3, 4
 GEMM_NO_SPLIT = 64             # VC_GEMM_NO_SPLIT: tile_cfg value that keeps an auto-tiled vc_gemm one launch
@@ -128,6 +130,8 @@ SYMBOLS = {
     "vc_euler_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_euler_step_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_step_advance": (C.c_int, [_vp, _vp]),
+    "vc_solver_evals": (C.c_int, [C.c_int]),
+    "vc_ode_stage": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_float, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
@@ -159,6 +163,8 @@ SYMBOLS = {
     "vc_flux_sample_begin": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
     "vc_flux_sample_steps": (C.c_int, [_vp, _i32, _vp, _vp]),
     "vc_flux_sample_end": (C.c_int, [_vp, _vp, _vp]),
+    "vc_flux_sample_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
+    "vc_flux_sample_begin_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
     "vc_flux_profile": (C.c_int, [_vp, _i32, C.POINTER(FluxLaunchClass), _i32, C.POINTER(_i32), _vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
@@ -544,6 +550,34 @@ def euler_step_f32(x32, shadow, v, dts, step_ptr=None, stream=None):
 def euler_step(x, v, dts, step_ptr=None, stream=None):
     _check(lib().vc_euler_step(x.data_ptr(), v.data_ptr(), dts.data_ptr(), _p(step_ptr), x.numel(),
                                stream if stream is not None else cur_stream()), "vc_euler_step")
+
+
+def solver_evals(method) -> int:
+    """vc_solver_evals: model evaluations per solver step of a method name or VC_SOLVER_* code (no GPU needed)"""
+    code = SOLVERS.get(method, -1) if isinstance(method, str) else int(method)
+    n = lib().vc_solver_evals(code)
+    _check(0 if n > 0 else n, f"vc_solver_evals({method!r})")
+    return n
+
+
+def ode_stage(method, stage: int, y, v, k, y_in, dts, eval_ptr=None, stream=None):
+    """vc_ode_stage: one stage combination of a midpoint / rk4 step.  y: the bf16 or f32 state (replaced by y1 by the last stage),
+    v: this stage's bf16 model output, k: bf16 [3, n] (rk4; None for midpoint), y_in: bf16, the next evaluation's input;
+    stage < 0: the stage is eval_ptr[0] % evals on the device; dt = dts[eval_ptr[0] // evals]."""
+    code = SOLVERS[method] if isinstance(method, str) else int(method)
+    if y.dtype not in (torch.bfloat16, torch.float32) or dts.dtype != torch.float32:
+        raise VclozeHipError(f"vc_ode_stage: bf16 or f32 state and an f32 dt table expected, got {y.dtype} / {dts.dtype}")
+    _bf16(v, "v"); _bf16(y_in, "y_in")
+    if k is not None:
+        _bf16(k, "k")
+        if k.numel() < 3 * y.numel():
+            raise VclozeHipError("vc_ode_stage: k must hold 3 * n values")
+    if not (y.is_cuda and y.is_contiguous() and v.is_contiguous() and y_in.is_contiguous() and (k is None or k.is_contiguous())):
+        raise VclozeHipError("vc_ode_stage: contiguous device tensors expected")
+    if v.numel() != y.numel() or y_in.numel() != y.numel():
+        raise VclozeHipError("vc_ode_stage: y, v, y_in must hold the same number of elements")
+    _check(lib().vc_ode_stage(code, int(stage), y.data_ptr(), int(y.dtype == torch.bfloat16), v.data_ptr(), _p(k), y_in.data_ptr(),
+                              dts.data_ptr(), _p(eval_ptr), y.numel(), stream if stream is not None else cur_stream()), "vc_ode_stage")
 
 
 def step_advance(step_ptr, stream=None):

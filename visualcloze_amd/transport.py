@@ -5,10 +5,16 @@ transport/transport.py:236-410, transport/integrators.py:79-120, transport/utils
     sample_fn = sampler.sample_ode(sampling_method="euler", num_steps=30, ...)
     latents = sample_fn(x, model.forward, model_kwargs)[-1]
 
-Only the configuration the inference pipeline uses is implemented (Linear path, velocity prediction,
-fixed-grid Euler); anything else raises NotImplementedError.  When `model` is the bound `forward` of a
-`visualcloze_amd.Flux`, the whole loop runs as hipGraph replays of one captured evaluation + Euler update
-with zero host synchronisation inside the loop; a foreign callable is stepped eagerly with the same grid.
+Only the configuration the inference pipeline uses is implemented (Linear path, velocity prediction) with the
+fixed-grid solvers "euler", "midpoint" and "rk4"; anything else raises NotImplementedError.  When `model` is the
+bound `forward` of a `visualcloze_amd.Flux`, the whole loop runs as hipGraph replays of one captured evaluation +
+the solver's update (Euler step / midpoint or rk4 stage combination) with zero host synchronisation inside the
+loop; a foreign callable is stepped eagerly with the same grid.
+
+The step rules (`STEP_RULES`) are torchdiffeq 0.2.x's fixed-grid solvers as recalled - unpinned against real
+torchdiffeq, which was not available to check against (as the Euler rule, tests/golden/make_golden.py).  They
+are written ONCE, as the literal torch expressions: a correction is a one-line change here and in
+csrc/elementwise.hip (ode_update).
 """
 from __future__ import annotations
 
@@ -65,14 +71,38 @@ def create_transport(path_type="Linear", prediction="velocity", loss_weight=None
     return Transport(path_type, prediction, do_shift)
 
 
+def _step_euler(f, t0, t1, dt, y0):
+    return y0 + dt * f(t0, y0)
+
+
+def _step_midpoint(f, t0, t1, dt, y0):
+    half_dt = 0.5 * dt
+    f0 = f(t0, y0)
+    y_mid = y0 + f0 * half_dt
+    return y0 + dt * f(t0 + half_dt, y_mid)
+
+
+def _step_rk4(f, t0, t1, dt, y0):          # the 3/8 rule
+    k1 = f(t0, y0)
+    k2 = f(t0 + dt * (1 / 3), y0 + dt * k1 * (1 / 3))
+    k3 = f(t0 + dt * (2 / 3), y0 + dt * (k2 - k1 * (1 / 3)))
+    k4 = f(t1, y0 + dt * (k1 - k2 + k3))
+    return y0 + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+
+
+# y1 = rule(f, t0, t1, dt, y0) with 0-dim f32 tensors t0, t1, dt = t1 - t0 on the state's device and f(t, y) the drift
+STEP_RULES = {"euler": _step_euler, "midpoint": _step_midpoint, "rk4": _step_rk4}
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False,
                    do_shift=True, time_shifting_factor=None, strength=None, return_trajectory: bool = False):
-        if sampling_method != "euler":
-            raise NotImplementedError("only the fixed-grid 'euler' solver (the inference default) is implemented")
+        if sampling_method not in STEP_RULES:
+            raise NotImplementedError(f"solver {sampling_method!r}: only the fixed-grid solvers {sorted(STEP_RULES)} are implemented "
+                                      "(no adaptive or multistep methods)")
         t0, t1 = self.transport.check_interval(reverse=reverse)
         if strength is not None:
             t0 = (t1 - t0) * strength + t0
@@ -83,22 +113,26 @@ class Sampler:
             from .model import Flux
             owner = getattr(model, "__self__", None)
             if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward":
-                if _fusable(owner, x):
-                    return _sample_fused(owner, x, dict(model_kwargs), t, return_trajectory)
+                if _fusable(owner, x, sampling_method):
+                    return _sample_fused(owner, x, dict(model_kwargs), t, return_trajectory, sampling_method)
                 # stepped eagerly; the velocity of this model is a bf16 tensor as the reference's is under autocast
                 # (visualcloze.py:363) whatever dtype Flux.forward hands back to its caller: dt * f stays a bf16 product
                 fwd = model
                 model = lambda xin, **k: fwd(xin, **k).to(torch.bfloat16)  # noqa: E731
-            return _sample_foreign(model, x, dict(model_kwargs), t, return_trajectory)
+            return _sample_foreign(model, x, dict(model_kwargs), t, return_trajectory, sampling_method)
 
         return _sample
 
 
-def _fusable(flux, x: torch.Tensor) -> bool:
+def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
     """The fused loop steps a bf16 state (the pipeline's, visualcloze.py:399) or - through the C handle - an f32 one IN f32
     (integrators.py:119 keeps the caller's state dtype).  Anything else (f16 / f64 states, an f32 state in the un-merged LoRA
     parity mode whose plan is ordered from Python) is stepped eagerly through Flux.forward with torch's own promotion rules:
-    never a silent per-step rounding of the caller's state."""
+    never a silent per-step rounding of the caller's state.  The Python-ordered plan (engine.py: use_handle False, or the
+    un-merged LoRA parity mode lora_mode="ref") knows the Euler update only: "midpoint" / "rk4" without the C handle are
+    stepped eagerly too, one Flux.forward per stage through `_sample_foreign`."""
+    if method != "euler" and flux.handle() is None:
+        return False
     if x.dtype == torch.bfloat16:
         return True
     return x.dtype == torch.float32 and flux.handle() is not None
@@ -117,23 +151,29 @@ def model_times(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return torch.ones(len(t) - 1) * (1 - _solver_t_as_state(t32[:-1], x))
 
 
-def _sample_foreign(model, x, kw, t, return_trajectory):
-    """Any other callable: the same grid and update rule, one host-driven call per interval."""
+def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
+    """Any other callable: the same grid and step rule (STEP_RULES), one host-driven call per evaluation."""
     cond = kw.pop("cond", None)
+    rule = STEP_RULES[method]
+
+    def f(ti, y):            # the drift the reference builds (transport.py:193-198,384), ti a 0-dim f32 tensor
+        tt = torch.ones(y.size(0), device=y.device) * _solver_t_as_state(ti, y)
+        xin = torch.cat((y, cond), dim=-1) if cond is not None else y
+        v = model(xin, timesteps=torch.ones_like(tt) * (1 - tt), **kw)
+        assert v.shape == y.shape, "Output shape from ODE solver must match input shape"
+        return -v
+
+    t = t.to(x.device)       # as integrators.py:113: t0, t1 and dt are 0-dim tensors on the state's device
     states = [x]
     for i in range(len(t) - 1):
-        tt = torch.ones(x.size(0), device=x.device) * _solver_t_as_state(t[i], x).to(x.device)
-        xin = torch.cat((x, cond), dim=-1) if cond is not None else x
-        v = model(xin, timesteps=torch.ones_like(tt) * (1 - tt), **kw)
-        assert v.shape == x.shape, "Output shape from ODE solver must match input shape"
-        x = x + (t[i + 1] - t[i]).to(x.device) * (-v)
+        x = rule(f, t[i], t[i + 1], t[i + 1] - t[i], x)
         if return_trajectory:
             states.append(x)
     return torch.stack(states) if return_trajectory else x[None]
 
 
 @torch.no_grad()
-def _sample_fused(flux, x, kw, t, return_trajectory):
+def _sample_fused(flux, x, kw, t, return_trajectory, method="euler"):
     eng = flux.engine()
     dev = eng.dev
     B, N, C = x.shape
@@ -147,6 +187,7 @@ def _sample_fused(flux, x, kw, t, return_trajectory):
         raise ValueError("Didn't get guidance strength for guidance distilled model.")
     T = txt.shape[1]
     S = len(t) - 1
+    E = hip.solver_evals(method)                   # model evaluations per step: the workspace's tables hold S * E of them
     t32 = t.to(torch.float32)
     eval_t = model_times(t32, x)                   # Flux sees 1 - t (transport.py:384), t in the state's dtype
     dts = (t32[1:] - t32[:-1]).contiguous()        # torchdiffeq fixed grid: dt = t1 - t0
@@ -160,8 +201,8 @@ def _sample_fused(flux, x, kw, t, return_trajectory):
     lay = MaskLayout(kw.get("txt_mask"), kw.get("img_mask"), B, T, N)
     st = eng.stream
     st.wait_stream(torch.cuda.current_stream())
-    # the C handle runs the whole trajectory of a chunk in ONE call (vc_flux_sample_euler); the un-merged LoRA mode uses the
-    # Python-ordered plan (bf16 states only: _fusable)
+    # the C handle runs the whole trajectory of a chunk in ONE call (vc_flux_sample_ode); the un-merged LoRA mode uses the
+    # Python-ordered plan (bf16 states, Euler only: _fusable)
     h = flux.handle()
     with torch.cuda.stream(st):
         s = st.cuda_stream
@@ -170,10 +211,10 @@ def _sample_fused(flux, x, kw, t, return_trajectory):
             sl = slice(b0, b0 + bs)
             if h is not None:
                 h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                          lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), S, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
+                          lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), S * E, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
                 xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()   # updated in place: never the caller's
                 tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
-                h.sample_euler(xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+                h.sample_ode(method, xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
                 if return_trajectory:
                     traj.append(torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)]))
                 out[sl].copy_(lay.img_rows_back(xs, sl))
