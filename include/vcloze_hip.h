@@ -282,6 +282,24 @@ int vc_solver_evals(int method);
  * 16-byte accesses need n % 8 == 0 and 16-byte aligned bases; anything else runs element-wise with the same results. */
 int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, const void* v, void* k, void* y_in,
                  const float* dts, const int32_t* eval_ptr, int64_t n, void* stream);
+/* ---- the three elementwise passes of the first-block step cache (vc_flux_set_step_cache below; the rule is this library's own,
+ * DESIGN.md section 4).  Added without a change of VC_ABI_VERSION, like the solver entry points: detect by SYMBOL (look up
+ * vc_flux_set_step_cache).  bf16 storage, f32 math, 16-byte accesses: n, every sample stride a multiple of 8, bases 16-byte aligned
+ * (VC_ERR_ARG otherwise).
+ * residual_change: h0, h1, p [B][n] bf16 -> r [B][n] = bf16(f32(h1) - f32(h0)); sums [B][2] F32 = per sample
+ *                  (sum |f32(r) - f32(p)|, sum |f32(p)|), summed in f32 in a fixed order (two-pass block reduction, no atomics:
+ *                  repeated runs give the same bits); metric [1] F32 = max over the samples of sums[b][0] / sums[b][1], NaN as soon as
+ *                  one ratio is.  sums or metric may be NULL.  scratch: B * 2 * VC_RESIDUAL_CHANGE_MAX_BLOCKS F32 of device memory.
+ *                  r must not overlap h0, h1, p.
+ * residual_sub / residual_add: out[b][i] = bf16(f32(a[b][i]) -/+ f32(b[b][i])), i < n, sample b of each operand starting
+ *                  b * its stride (elements) after the base: rows of a strided stream (the image rows of the joint stream). */
+#define VC_RESIDUAL_CHANGE_MAX_BLOCKS 256
+int vc_residual_change(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch, int32_t B,
+                       int64_t n, void* stream);
+int vc_residual_sub(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
+                    int64_t n, void* stream);
+int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
+                    int64_t n, void* stream);
 /* SDEdit start state x0 = noise*(1-s) + latent*s with the reference's bf16 roundings (visualcloze.py:221) */
 int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream);
 
@@ -460,6 +478,25 @@ int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, 
                        int32_t state_is_bf16, void* trajectory, void* stream);
 int vc_flux_sample_begin_ode(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
                              int32_t state_is_bf16, void* stream);
+
+/* ---- first-block step cache of the Euler loop: OPT-IN, off by default.  IT CHANGES RESULTS: a reused evaluation is an
+ * approximation, not the model.  Its effect on image quality is unmeasured (only random-init weights were available) and no default
+ * threshold is recommended.  The rule is this library's own (the reference evaluates all blocks at every step), DESIGN.md section 4:
+ * with h0 = the image stream after img_in, h1 = after double block 0, hE = the image rows after the last single block,
+ * r = bf16(h1 - h0), P = the r of the last COMPUTED evaluation and R = bf16(hE - h1) of that evaluation, an evaluation is REUSED
+ * - the image rows become bf16(h1 + R), then the last layer and the Euler update run as usual, blocks 1..end are not launched -
+ * iff a P exists, m = max over the chunk's samples of sum|r - P| / sum|P| < threshold, and fewer than max_consecutive evaluations
+ * were reused in a row.  The first evaluation after vc_flux_sample_begin* always computes.
+ * threshold <= 0 or max_consecutive == 0: off (the default); max_consecutive < 0: no limit on consecutive reuses.  A changed setting
+ * takes effect at the next vc_flux_sample_begin* (which is where a non-Euler method with the cache on is refused: VC_ERR_ARG).
+ * While on: 3 * B * N * hidden_size bf16 (+ a few KB) more workspace - ask vc_flux_workspace_bytes AFTER setting it and prepare
+ * again; the step is three captured graphs (head / tail-compute / tail-reuse) and vc_flux_sample_steps synchronises `stream` once
+ * per step to read the 4-byte metric.  While off nothing changes: one graph, no host read, the same workspace size, the same bits.
+ * vc_flux_forward and vc_flux_profile ignore the cache.
+ * stats: of the trajectory in flight or just finished - *computed / *reused evaluation counts and, for the first `capacity`
+ * evaluations, metrics[i] = the m of evaluation i (NaN where none existed: the first evaluation, or the cache off). */
+int vc_flux_set_step_cache(void* handle, float threshold, int32_t max_consecutive);
+int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity);
 
 /* ---- the plan's own stopwatch (ABI 10): HIP-event times of the launches of whole evaluations, class by class ----
  * What bench.py's `roofline` leg reports.  With a sample in flight (vc_flux_sample_begin), `evaluations` more evaluations of

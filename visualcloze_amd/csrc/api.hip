@@ -105,6 +105,18 @@ int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, 
   return vc_ode_stage_launch(method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, S(stream), ERRBUF);
 }
 int vc_step_advance(int32_t* step_ptr, void* stream) { return vc_step_advance_launch(step_ptr, S(stream), ERRBUF); }
+int vc_residual_change(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch, int32_t B,
+                       int64_t n, void* stream) {
+  return vc_residual_change_launch(h0, h1, p, r, sums, metric, scratch, B, n, S(stream), ERRBUF);
+}
+int vc_residual_sub(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
+                    int64_t n, void* stream) {
+  return vc_residual_op_launch(0, a, a_bstride, b, b_bstride, out, out_bstride, B, n, S(stream), ERRBUF);
+}
+int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
+                    int64_t n, void* stream) {
+  return vc_residual_op_launch(1, a, a_bstride, b, b_bstride, out, out_bstride, B, n, S(stream), ERRBUF);
+}
 
 int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream) {
   return vc_sdedit_mix_launch(noise, latent, strength, out, n, S(stream), ERRBUF);
@@ -196,6 +208,12 @@ int vc_flux_profile(void* handle, int32_t evaluations, VcFluxLaunchClass* out, i
   return vc_flux_profile_impl(handle, evaluations, out, capacity, count, S(stream), ERRBUF);
 }
 int vc_flux_sample_end(void* handle, void* x_out, void* stream) { return vc_flux_sample_end_impl(handle, x_out, S(stream), ERRBUF); }
+int vc_flux_set_step_cache(void* handle, float threshold, int32_t max_consecutive) {
+  return vc_flux_set_step_cache_impl(handle, threshold, max_consecutive, ERRBUF);
+}
+int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity) {
+  return vc_flux_step_cache_stats_impl(handle, computed, reused, metrics, capacity, ERRBUF);
+}
 int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points,
                        int32_t state_is_bf16, void* trajectory, void* stream) {
   int rc = vc_flux_sample_begin_impl(handle, method, x, cond, t_grid, n_points, state_is_bf16, S(stream), ERRBUF);

@@ -13,6 +13,8 @@
 //   MOD [S*B, n_mod]    every modulation vector of every block for every evaluation (row s*B + b, evaluation order)
 //   XS / COND / XIN / V the ODE state, the conditioning columns, x || cond, the velocity
 //   KS [3][B*N*out] / YIN   k1..k3 of an rk4 step / the input state of the next evaluation (midpoint, rk4: vc_ode_stage)
+//   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
+//                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
 #include "common.h"
 #include "vcloze_internal.h"
 #include <math.h>
@@ -42,6 +44,8 @@ struct Buffers {   // the workspace carve-up
   bf16_t *XI, *XT, *X, *XH, *QKV, *VT, *CAT, *HID, *TXT0, *XIN, *V, *XS, *COND, *MOD, *TEMB, *H1, *TVEC, *GVEC, *YVEC, *VEC, *GE, *GH, *YH, *KS, *YIN;
   float *ROPE, *TS, *DTS, *G32, *FREQS, *XS32;
   int32_t *STEP, *KVLEN, *KVGAP;
+  bf16_t *SC_P = nullptr, *SC_R = nullptr, *SC_RS = nullptr;      // step cache (carved only while it is on)
+  float *SC_PART = nullptr, *SC_METRIC = nullptr;
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
   void* SK_WS = nullptr;               // f32 partial tiles of split-K GEMM remainders (VcGemmArgs.splitk_ws)
@@ -69,20 +73,33 @@ struct Flux : Buffers {
   bool ragged = false, gapped = false;
   char* base = nullptr;
   // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
-  hipGraphExec_t graph = nullptr;      // = graphs.front().second while a sample is in flight
+  hipGraphExec_t graph = nullptr;      // = graphs.front().second.g[0] while a sample is in flight
+  // a captured step: ONE graph (g[0]), or with the step cache on three - head, tail-compute, tail-reuse (an entry of `graphs` is a
+  // whole step, so a cached trajectory never evicts a graph of its own)
+  struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; } step;
   struct Key {
-    char* base; int B, T, N, S, ragged, gapped, variant, tile, fuse, fuse_vt, state_f32, qkv_heads, fuse_knorm, bound, mlp_first, splitk, method; hipStream_t s;
+    char* base; int B, T, N, S, ragged, gapped, variant, tile, fuse, fuse_vt, state_f32, qkv_heads, fuse_knorm, bound, mlp_first, splitk, method, cache; hipStream_t s;
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
              variant == o.variant && tile == o.tile && fuse == o.fuse && fuse_vt == o.fuse_vt && state_f32 == o.state_f32 &&
-             qkv_heads == o.qkv_heads && fuse_knorm == o.fuse_knorm && bound == o.bound && mlp_first == o.mlp_first && splitk == o.splitk && method == o.method && s == o.s;
+             qkv_heads == o.qkv_heads && fuse_knorm == o.fuse_knorm && bound == o.bound && mlp_first == o.mlp_first && splitk == o.splitk && method == o.method && cache == o.cache && s == o.s;
     }
   } key{};
-  std::vector<std::pair<Key, hipGraphExec_t>> graphs;
+  std::vector<std::pair<Key, Step>> graphs;
   // sampling state
   int steps_total = 0, steps_done = 0;
   bool state_f32 = false;              // the sample in flight steps an f32 state (XS32; XS is its bf16 shadow)
   int method = VC_SOLVER_EULER, evals = 1;   // ... with this solver: `evals` replays of the captured evaluation per step
+  // step cache.  sc_threshold / sc_max: the caller's setting (vc_flux_set_step_cache), which sizes the workspace
+  // at once and steers a trajectory from its sample_begin on (sc_active, sc_thr, sc_lim)
+  float sc_threshold = 0.0f; int sc_max = 0;
+  bool sc_on() const { return sc_threshold > 0.0f && sc_max != 0; }
+  bool ws_cache = false;               // the prepared workspace holds SC_P / SC_R / SC_RS
+  bool sc_active = false, sc_have = false;   // this trajectory runs cached; a P (and R) of this trajectory exists
+  float sc_thr = 0.0f; int sc_lim = 0, sc_run = 0;   // sc_run: evaluations reused in a row
+  int sc_computed = 0, sc_reused = 0;
+  std::vector<float> sc_metrics;       // m of every evaluation of the trajectory (NaN where no P existed)
+  float* sc_host = nullptr;            // pinned: the head graph's last node copies the metric here
   // host staging (pinned), reused once the copies that read it have completed
   char* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;
@@ -154,6 +171,10 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
   auto sk = g.bound.find("splitk_ws");
   if (sk != g.bound.end()) { f.SK_WS = const_cast<void*>(sk->second.w); f.sk_ws_bytes = (int64_t)sk->second.N * sk->second.K * 4; }
   else { f.SK_WS = c.take<char>(VC_GEMM_SPLITK_WS_BYTES); f.sk_ws_bytes = VC_GEMM_SPLITK_WS_BYTES; }
+  if (g.sc_on()) {    // behind everything else: with the cache off the carve-up and its size are what they always were
+    f.SC_P = c.take<bf16_t>(B * N * D); f.SC_R = c.take<bf16_t>(B * N * D); f.SC_RS = c.take<bf16_t>(B * N * D);
+    f.SC_PART = c.take<float>((int64_t)B * 2 * VC_RESIDUAL_CHANGE_MAX_BLOCKS); f.SC_METRIC = c.take<float>(1);
+  }
   return c.off;
 }
 
@@ -455,19 +476,31 @@ int d2d(void* dst, const void* src, int64_t bytes, hipStream_t s, Err e) {
 // Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it: the
 // Euler update of XS, or the midpoint / rk4 stage combination (state -> YIN, the input of the next evaluation).  step_ptr counts
 // EVALUATIONS (= steps for Euler).
-int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows, void* out, bool euler, hipStream_t s, Err e) {
-  const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
+// in three pieces, which `evaluate` issues back to back (the plan of every evaluation without the step cache) and the cached step
+// issues with its own launches in between: the inputs, the blocks from double block `first` on, the last layer + update.
+int eval_inputs(Flux& f, bool concat, const void* img_rows, hipStream_t s, Err e) {
+  const int B = f.B, T = f.T, N = f.N, D = f.D;
   const int in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
-  Ctx c{step_ptr, s, (int64_t)B * f.n_mod};
   if (concat) TRY(vc_concat_cols_launch(f.method == VC_SOLVER_EULER ? f.XS : f.YIN, out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
   TRY(d2d(f.XT, f.TXT0, (int64_t)B * T * D * 2, s, e));
-  TRY(lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e));
-  for (auto& w : f.dbl) TRY(double_block(f, c, w, e));
+  return lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e);
+}
+int eval_blocks(Flux& f, const Ctx& c, size_t first, Err e) {
+  const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
+  hipStream_t s = c.s;
+  for (size_t i = first; i < f.dbl.size(); ++i) TRY(double_block(f, c, f.dbl[i], e));
   for (int b = 0; b < B; ++b) {   // cat((txt, img), 1) per sample (model.py:116)
     TRY(d2d(f.X + (int64_t)b * L * D, f.XT + (int64_t)b * T * D, (int64_t)T * D * 2, s, e));
     TRY(d2d(f.X + ((int64_t)b * L + T) * D, f.XI + (int64_t)b * N * D, (int64_t)N * D * 2, s, e));
   }
   for (auto& w : f.sgl) TRY(single_block(f, c, w, e));
+  return VC_OK;
+}
+int eval_output(Flux& f, const Ctx& c, void* out, bool euler, Err e) {
+  const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
+  const int out_ch = f.cfg.out_channels;
+  const int32_t* step_ptr = c.step_ptr;
+  hipStream_t s = c.s;
   // LastLayer (layers.py:248-259) on the image rows
   TRY(ln1(f, c, f.final_mod, e));
   VcGemmProblem p = prob(f.XH + (int64_t)T * D, D, f.final_lin, out ? out : f.V, out_ch, B * N);
@@ -483,6 +516,43 @@ int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows
     TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
   }
   return VC_OK;
+}
+int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows, void* out, bool euler, hipStream_t s, Err e) {
+  Ctx c{step_ptr, s, (int64_t)f.B * f.n_mod};
+  TRY(eval_inputs(f, concat, img_rows, s, e));
+  TRY(eval_blocks(f, c, 0, e));
+  return eval_output(f, c, out, euler, e);
+}
+
+// ---- the step cache: one Euler evaluation as head + ONE of two tails, chosen by the host from the metric
+// head: the plan up to double block 0 (h0 is parked in X, which nothing uses before the streams are joined), then r, the metric and
+// its 4-byte copy to pinned host memory
+int cache_head(Flux& f, hipStream_t s, Err e) {
+  const int64_t nd = (int64_t)f.N * f.D;
+  Ctx c{f.STEP, s, (int64_t)f.B * f.n_mod};
+  TRY(eval_inputs(f, true, nullptr, s, e));
+  TRY(d2d(f.X, f.XI, f.B * nd * 2, s, e));                                   // h0
+  TRY(double_block(f, c, f.dbl[0], e));                                      // XI = h1
+  TRY(vc_residual_change_launch(f.X, f.XI, f.SC_P, f.SC_RS, nullptr, f.SC_METRIC, f.SC_PART, f.B, nd, s, e.buf, e.len));
+  HIP(hipMemcpyAsync(f.sc_host, f.SC_METRIC, sizeof(float), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
+  return VC_OK;
+}
+// tail-compute: P <- r, the scratch keeps h1, blocks 1..end, R <- hE - h1, then the last layer and the update as ever
+int cache_tail_compute(Flux& f, bool euler, hipStream_t s, Err e) {
+  const int64_t nd = (int64_t)f.N * f.D;
+  Ctx c{f.STEP, s, (int64_t)f.B * f.n_mod};
+  TRY(d2d(f.SC_P, f.SC_RS, f.B * nd * 2, s, e));
+  TRY(d2d(f.SC_RS, f.XI, f.B * nd * 2, s, e));
+  TRY(eval_blocks(f, c, 1, e));
+  TRY(vc_residual_op_launch(0, f.X + (int64_t)f.T * f.D, (int64_t)f.L * f.D, f.SC_RS, nd, f.SC_R, nd, f.B, nd, s, e.buf, e.len));
+  return eval_output(f, c, nullptr, euler, e);
+}
+// tail-reuse: the image rows of X <- h1 + R (its text rows keep the last computed evaluation's: the last layer reads image rows only)
+int cache_tail_reuse(Flux& f, bool euler, hipStream_t s, Err e) {
+  const int64_t nd = (int64_t)f.N * f.D;
+  Ctx c{f.STEP, s, (int64_t)f.B * f.n_mod};
+  TRY(vc_residual_op_launch(1, f.XI, nd, f.SC_R, nd, f.X + (int64_t)f.T * f.D, (int64_t)f.L * f.D, f.B, nd, s, e.buf, e.len));
+  return eval_output(f, c, nullptr, euler, e);
 }
 
 // ---------------------------------------------------------------- host staging
@@ -536,46 +606,73 @@ int time_precompute(Flux& f, int S, int timesteps_is_bf16, hipStream_t s, Err e)
   return lin(f, f.modulation, f.H1, D, f.MOD, f.n_mod, M, VC_EPI_BIAS, s, e);
 }
 
-constexpr size_t MAX_GRAPHS = 4;
+constexpr size_t MAX_GRAPHS = 4;      // captured STEPS (Flux::Step: one graph, or the three of a cached step)
 void drop_prof(Flux& f) {
   for (auto ev : f.prof_ev) (void)hipEventDestroy(ev);
   f.prof_ev.clear();
 }
 void drop_graph(Flux& f) {
-  for (auto& g : f.graphs) (void)hipGraphExecDestroy(g.second);
+  for (auto& g : f.graphs)
+    for (auto ge : g.second.g) if (ge) (void)hipGraphExecDestroy(ge);
   f.graphs.clear();
   f.graph = nullptr;
+  f.step = Flux::Step{};
 }
 
 // the hipGraph of ONE evaluation + the solver's update behind it (Euler: one solver step): everything that depends on the
 // evaluation (modulation rows, dt, the stage of a midpoint / rk4 step) is indexed on the device by STEP
+// capture what `issue` launches on `s` into an instantiated graph
+template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue) {
+  HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
+  const int rc = issue();
+  hipGraph_t g = nullptr;
+  hipError_t he = hipStreamEndCapture(s, &g);
+  if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
+  HIP(he, "hipStreamEndCapture");
+  he = hipGraphInstantiate(&out, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  HIP(he, "hipGraphInstantiate");
+  return VC_OK;
+}
 int step_graph(Flux& f, hipStream_t s, Err e) {
   Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.tile_cfg, f.fuse_qnorm, f.fuse_vt, f.state_f32,
-              f.qkv_heads, f.fuse_knorm, f.logit_bound_milli, f.mlp_first, f.splitk, f.method, s};
+              f.qkv_heads, f.fuse_knorm, f.logit_bound_milli, f.mlp_first, f.splitk, f.method, f.sc_active, s};
   for (size_t i = 0; i < f.graphs.size(); ++i)
     if (f.graphs[i].first == k) {
       auto hit = f.graphs[i];
       f.graphs.erase(f.graphs.begin() + i);
       f.graphs.insert(f.graphs.begin(), hit);
-      f.graph = hit.second; f.key = k;
+      f.step = hit.second; f.graph = f.step.g[0]; f.key = k;
       return VC_OK;
     }
   f.graph = nullptr;
-  // warm-up outside capture (kernel attributes are set on first launch): one evaluation into V, the state is untouched
-  TRY(evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e));
-  HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
-  const int rc = evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e);
-  hipGraph_t g = nullptr;
-  hipError_t he = hipStreamEndCapture(s, &g);
-  if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-  HIP(he, "hipStreamEndCapture");
-  hipGraphExec_t ge = nullptr;
-  he = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  HIP(he, "hipGraphInstantiate");
-  if (f.graphs.size() >= MAX_GRAPHS) { (void)hipGraphExecDestroy(f.graphs.back().second); f.graphs.pop_back(); }
-  f.graphs.insert(f.graphs.begin(), {k, ge});
-  f.graph = ge; f.key = k;
+  f.step = Flux::Step{};
+  Flux::Step st;
+  int rc = VC_OK;
+  if (!f.sc_active) {
+    // warm-up outside capture (kernel attributes are set on first launch): one evaluation into V, the state is untouched
+    TRY(evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e));
+    rc = capture(s, st.g[0], e, [&] { return evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e); });
+  } else {
+    // the same warm-up through the three pieces (P, R and the scratch it writes are rewritten by the trajectory's first evaluation,
+    // which always computes, before anything reads them)
+    TRY(cache_head(f, s, e));
+    TRY(cache_tail_compute(f, false, s, e));
+    TRY(cache_tail_reuse(f, false, s, e));
+    rc = capture(s, st.g[0], e, [&] { return cache_head(f, s, e); });
+    if (rc == VC_OK) rc = capture(s, st.g[1], e, [&] { return cache_tail_compute(f, true, s, e); });
+    if (rc == VC_OK) rc = capture(s, st.g[2], e, [&] { return cache_tail_reuse(f, true, s, e); });
+  }
+  if (rc != VC_OK) {
+    for (auto ge : st.g) if (ge) (void)hipGraphExecDestroy(ge);
+    return rc;
+  }
+  if (f.graphs.size() >= MAX_GRAPHS) {
+    for (auto ge : f.graphs.back().second.g) if (ge) (void)hipGraphExecDestroy(ge);
+    f.graphs.pop_back();
+  }
+  f.graphs.insert(f.graphs.begin(), {k, st});
+  f.step = st; f.graph = st.g[0]; f.key = k;
   return VC_OK;
 }
 
@@ -617,6 +714,7 @@ int vc_flux_destroy_impl(void* handle, char* err, int errlen) {
   drop_graph(f);
   drop_prof(f);
   if (f.pinned) (void)hipHostFree(f.pinned);
+  if (f.sc_host) (void)hipHostFree(f.sc_host);
   if (f.staged) (void)hipEventDestroy(f.staged);
   delete &f;
   return VC_OK;
@@ -688,6 +786,7 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
   const int64_t need = carve(f, f, (char*)workspace, B, T, N, S);
   if (workspace_bytes < need) FAIL(VC_ERR_ARG, "flux_prepare: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   f.base = (char*)workspace;
+  f.ws_cache = f.sc_on();
   f.B = B; f.T = T; f.N = N; f.L = T + N; f.Lp = (f.L + 63) / 64 * 64; f.S = S;
   const int L = f.L, D = f.D;
   // masks
@@ -819,6 +918,13 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   const int S = n_points - 1, B = f.B;
   if (S < 1 || (int64_t)S * E > f.S)
     FAIL(VC_ERR_ARG, "flux_sample: %d steps of %d evaluation(s), the prepared workspace holds 1..%d evaluations", S, E, f.S);
+  const bool cached = f.sc_on();
+  if (cached && method != VC_SOLVER_EULER)
+    FAIL(VC_ERR_ARG, "flux_sample: the step cache works with VC_SOLVER_EULER only (method %d): turn it off with vc_flux_set_step_cache(handle, 0, 0)", method);
+  if (cached && f.dbl.empty()) FAIL(VC_ERR_ARG, "flux_sample: the step cache needs at least one double block");
+  if (cached && !f.ws_cache)
+    FAIL(VC_ERR_STATE, "flux_sample: the step cache was turned on after vc_flux_prepare: ask vc_flux_workspace_bytes and prepare again");
+  if (cached && !f.sc_host) HIP(hipHostMalloc((void**)&f.sc_host, 256, hipHostMallocDefault), "hipHostMalloc");
   const int SE = S * E;
   TRY(stage_begin(f, ((size_t)SE * B + S) * sizeof(float) + 512, e));
   float* ts = stage_take<float>(f, (size_t)SE * B);
@@ -849,8 +955,29 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   if (E > 1) TRY(d2d(f.YIN, f.XS, n * f.cfg.out_channels * 2, s, e));      // the first evaluation reads bf16(y0)
   TRY(d2d(f.COND, cond, n * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
   HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
+  f.sc_active = cached; f.sc_thr = f.sc_threshold; f.sc_lim = f.sc_max;
+  f.sc_have = false; f.sc_run = f.sc_computed = f.sc_reused = 0;
+  f.sc_metrics.clear();
   if (s) TRY(step_graph(f, s, e));
+  // no P yet: the first metric is read against zeros (and reported as NaN), never against an earlier trajectory's residual
+  if (cached) HIP(hipMemsetAsync(f.SC_P, 0, (size_t)n * f.D * 2, s), "hipMemsetAsync");
   f.steps_total = S; f.steps_done = 0;
+  return VC_OK;
+}
+
+// one cached Euler step: head, ONE host read of the metric, the tail the rule picks
+static int cached_step(Flux& f, hipStream_t s, Err e) {
+  if (s) HIP(hipGraphLaunch(f.step.g[0], s), "hipGraphLaunch");
+  else TRY(cache_head(f, s, e));
+  HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
+  const float m = *(volatile float*)f.sc_host;
+  const bool reuse = f.sc_have && m < f.sc_thr && (f.sc_lim < 0 || f.sc_run < f.sc_lim);
+  f.sc_metrics.push_back(f.sc_have ? m : NAN);
+  if (s) HIP(hipGraphLaunch(f.step.g[reuse ? 2 : 1], s), "hipGraphLaunch");
+  else if (reuse) TRY(cache_tail_reuse(f, true, s, e));
+  else TRY(cache_tail_compute(f, true, s, e));
+  if (reuse) { ++f.sc_reused; ++f.sc_run; }
+  else { ++f.sc_computed; f.sc_run = 0; f.sc_have = true; }
   return VC_OK;
 }
 
@@ -864,8 +991,10 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
   const void* state = f.state_f32 ? (const void*)f.XS32 : (const void*)f.XS;
   for (int i = 0; i < n_steps; ++i) {
     for (int j = 0; j < f.evals; ++j) {      // a step = `evals` replays; the stage is the device-side counter modulo evals
+      if (f.sc_active) { TRY(cached_step(f, s, e)); continue; }
       if (s) HIP(hipGraphLaunch(f.graph, s), "hipGraphLaunch");
       else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
+      ++f.sc_computed;
     }
     if (trajectory) TRY(d2d((char*)trajectory + (int64_t)i * state_bytes, state, state_bytes, s, e));
     ++f.steps_done;
@@ -879,6 +1008,24 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
   if (!x_out) FAIL(VC_ERR_ARG, "flux_sample_end: null output");
   if (f.state_f32) return d2d(x_out, f.XS32, (int64_t)f.B * f.N * f.cfg.out_channels * 4, s, e);
   return d2d(x_out, f.XS, (int64_t)f.B * f.N * f.cfg.out_channels * 2, s, e);
+}
+
+int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {
+  H(handle);
+  if (threshold != threshold) FAIL(VC_ERR_ARG, "flux_set_step_cache: threshold is NaN");
+  f.sc_threshold = threshold > 0.0f ? threshold : 0.0f;
+  f.sc_max = max_consecutive;
+  return VC_OK;
+}
+
+int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity, char* err, int errlen) {
+  H(handle);
+  if (capacity < 0 || (capacity > 0 && !metrics)) FAIL(VC_ERR_ARG, "flux_step_cache_stats: bad arguments");
+  if (computed) *computed = f.sc_computed;
+  if (reused) *reused = f.sc_reused;
+  const int done = f.sc_computed + f.sc_reused;
+  for (int i = 0; i < capacity; ++i) metrics[i] = i < done && i < (int)f.sc_metrics.size() ? f.sc_metrics[i] : NAN;
+  return VC_OK;
 }
 
 // HIP-event times of the launches of the product's plan, class by class (vcloze_hip.h): `evaluations` evaluations of the sample in

@@ -93,6 +93,7 @@ class FluxHandle:
         hip._check(L.vc_flux_bind_weight(self.h, b"splitk_ws", self._sk_ws.data_ptr(), None, 1, nf, nf), "vc_flux_bind_weight(splitk_ws)")
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._opts: Dict[str, int] = {}
+        self._step_cache = (0.0, 0)       # vc_flux_set_step_cache: off
         self.geom: Optional[Tuple[int, int, int, int]] = None
         self._host = _HostCopies()
         # the storage order of the bound qkv rows (head-permuted or natural) and the logit bound are PROPERTIES OF THE
@@ -133,15 +134,32 @@ class FluxHandle:
                 hip._check(hip.lib().vc_flux_set_option(self.h, k.encode(), v), f"vc_flux_set_option({k})")
                 self._opts[k] = v
 
+    def set_step_cache(self, step_cache=None) -> None:
+        """vc_flux_set_step_cache: a `transport.StepCache` (or anything with .threshold / .max_consecutive), or None = off.
+        Takes effect at the next prepare + sample_begin (the workspace grows by 3 * B * N * hidden bf16 while it is on)."""
+        want = (0.0, 0) if step_cache is None else (float(step_cache.threshold), int(step_cache.max_consecutive))
+        if want != self._step_cache:
+            hip._check(hip.lib().vc_flux_set_step_cache(self.h, want[0], want[1]), "vc_flux_set_step_cache")
+            self._step_cache = want
+
+    def step_cache_stats(self, capacity: int = 256) -> dict:
+        """vc_flux_step_cache_stats of the trajectory in flight or just finished: {"computed", "reused", "metrics"}; metrics[i] is
+        the m of evaluation i, NaN where none existed (the first evaluation; every evaluation with the cache off)."""
+        c, r = C.c_int32(0), C.c_int32(0)
+        m = (C.c_float * max(int(capacity), 1))()
+        hip._check(hip.lib().vc_flux_step_cache_stats(self.h, C.byref(c), C.byref(r), m, int(capacity)), "vc_flux_step_cache_stats")
+        n = min(int(capacity), c.value + r.value)
+        return {"computed": c.value, "reused": r.value, "metrics": [float(m[i]) for i in range(n)]}
+
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
-        key = (B, T, N, S)
+        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0)
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:
                 self._ws.clear()
             n = hip.lib().vc_flux_workspace_bytes(self.h, B, T, N, S)
             if n <= 0:
-                raise hip.VclozeHipError(f"vc_flux_workspace_bytes({key}) = {n}")
+                raise hip.VclozeHipError(f"vc_flux_workspace_bytes({key[:4]}) = {n}")
             ws = torch.empty(n + 256, dtype=torch.uint8, device=self.dev)
             self._ws[key] = ws
         return ws

@@ -132,6 +132,9 @@ SYMBOLS = {
     "vc_step_advance": (C.c_int, [_vp, _vp]),
     "vc_solver_evals": (C.c_int, [C.c_int]),
     "vc_ode_stage": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "vc_residual_change": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
+    "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
+    "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_float, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
@@ -165,6 +168,8 @@ SYMBOLS = {
     "vc_flux_sample_end": (C.c_int, [_vp, _vp, _vp]),
     "vc_flux_sample_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
     "vc_flux_sample_begin_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
+    "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
+    "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
     "vc_flux_profile": (C.c_int, [_vp, _i32, C.POINTER(FluxLaunchClass), _i32, C.POINTER(_i32), _vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
@@ -582,6 +587,56 @@ def ode_stage(method, stage: int, y, v, k, y_in, dts, eval_ptr=None, stream=None
 
 def step_advance(step_ptr, stream=None):
     _check(lib().vc_step_advance(step_ptr.data_ptr(), stream if stream is not None else cur_stream()), "vc_step_advance")
+
+
+RESIDUAL_CHANGE_MAX_BLOCKS = 256     # VC_RESIDUAL_CHANGE_MAX_BLOCKS
+
+
+def residual_change(h0, h1, p, r=None, stream=None):
+    """vc_residual_change on [B, n] bf16 tensors (n = everything behind the first dimension): r = bf16(h1 - h0) and, per sample,
+    (sum |r - p|, sum |p|) in f32.  Returns (r, sums [B, 2] f32, metric [1] f32 = max_b sums[b, 0] / sums[b, 1])."""
+    for t, name in ((h0, "h0"), (h1, "h1"), (p, "p")):
+        _bf16(t, name)
+    if not (h0.shape == h1.shape == p.shape and h0.dim() >= 2 and h0.is_contiguous() and h1.is_contiguous() and p.is_contiguous()):
+        raise VclozeHipError("vc_residual_change: contiguous [B, ...] tensors of one shape expected")
+    r = torch.empty_like(h0) if r is None else r
+    _bf16(r, "r")
+    if r.shape != h0.shape or not r.is_contiguous():
+        raise VclozeHipError("vc_residual_change: r must be a contiguous tensor of the inputs' shape")
+    B = h0.shape[0]
+    sums = torch.empty(B, 2, dtype=torch.float32, device=h0.device)
+    metric = torch.empty(1, dtype=torch.float32, device=h0.device)
+    scratch = torch.empty(B * 2 * RESIDUAL_CHANGE_MAX_BLOCKS, dtype=torch.float32, device=h0.device)
+    _check(lib().vc_residual_change(h0.data_ptr(), h1.data_ptr(), p.data_ptr(), r.data_ptr(), sums.data_ptr(), metric.data_ptr(),
+                                    scratch.data_ptr(), B, h0.numel() // B, stream if stream is not None else cur_stream()),
+           "vc_residual_change")
+    return r, sums, metric
+
+
+def _residual_op(fn, what, a, b, out, stream):
+    """a, b, out: [B, n...] bf16, each sample's n elements contiguous, samples stride(0) apart (views of row ranges are fine)"""
+    _bf16(a, "a"); _bf16(b, "b")
+    out = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if out is None else out
+    _bf16(out, "out")
+    if not (a.shape == b.shape == out.shape and a.dim() >= 2):
+        raise VclozeHipError(f"{what}: [B, ...] tensors of one shape expected")
+    for t in (a, b, out):
+        if not t[0].is_contiguous():
+            raise VclozeHipError(f"{what}: every sample must be contiguous")
+    B = a.shape[0]
+    _check(fn(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), B, a[0].numel(),
+              stream if stream is not None else cur_stream()), what)
+    return out
+
+
+def residual_sub(a, b, out=None, stream=None):
+    """vc_residual_sub: bf16(f32(a) - f32(b))"""
+    return _residual_op(lib().vc_residual_sub, "vc_residual_sub", a, b, out, stream)
+
+
+def residual_add(a, b, out=None, stream=None):
+    """vc_residual_add: bf16(f32(a) + f32(b))"""
+    return _residual_op(lib().vc_residual_add, "vc_residual_add", a, b, out, stream)
 
 
 def sdedit_mix(noise, latent, strength, out=None, stream=None):

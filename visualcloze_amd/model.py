@@ -259,6 +259,7 @@ class Flux(nn.Module):
         # call per evaluation / per trajectory.  False (or lora_mode "ref"): the same launch plan ordered from Python
         # (engine.FluxEngine) over the op-level ABI - bit-identical results, kept for the parity mode and per-block taps.
         self.use_handle = True
+        self.last_step_cache_stats = None      # of the last trajectory sampled with a transport.StepCache: one dict per chunk
         # "merged": W + s*B@A folded once (the product mode).  "ref": LinearLora.forward executed as the
         # reference does - base GEMM, two skinny GEMMs, three bf16 roundings (models/modules/lora.py:92-98) - so that
         # the merge's one-rounding deviation is a choice, not a necessity; slower (+8 % FLOPs, unfused epilogues).

@@ -30,7 +30,7 @@ def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
 @torch.no_grad()
 def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[torch.Tensor],
                  mask_rows: List[torch.Tensor], txt: torch.Tensor, vec: torch.Tensor, cfg: float = 30.0,
-                 steps: int = 30, solver: str = "euler", time_shifting_factor=1) -> List[torch.Tensor]:
+                 steps: int = 30, solver: str = "euler", time_shifting_factor=1, step_cache=None) -> List[torch.Tensor]:
     """One grid: per-row noise [1,16,h,w], VAE latents of the grid rows (already shifted/scaled), per-row PIXEL
     fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w]."""
     dev = noise_rows[0].device
@@ -38,7 +38,7 @@ def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[t
     cond = packing.pack_cond(cond_latent_rows, mask_rows)                              # :381-389
     fn = Sampler(create_transport("Linear", "velocity", do_shift=True)).sample_ode(
         sampling_method=solver, num_steps=steps, atol=1e-6, rtol=1e-3, reverse=False, do_shift=True,
-        time_shifting_factor=time_shifting_factor)                                     # :284-292
+        time_shifting_factor=time_shifting_factor, step_cache=step_cache)              # :284-292
     samples = fn(img, model.forward, _kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]   # :415-420
     return packing.unpack_rows(samples, [tuple(r.shape[-2:]) for r in noise_rows])     # :425-429
 
@@ -46,7 +46,7 @@ def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[t
 @torch.no_grad()
 def sdedit_upsample(model, noise: torch.Tensor, latent: torch.Tensor, blank_latent: torch.Tensor, txt: torch.Tensor,
                     vec: torch.Tensor, cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
-                    solver: str = "euler") -> torch.Tensor:
+                    solver: str = "euler", step_cache=None) -> torch.Tensor:
     """SDEdit refinement of one image (visualcloze.py:184-237): start from noise*(1-s) + latent*s, everything masked,
     un-shifted grid from t0 = strength.  noise/latent/blank_latent: [1,16,h,w]; returns [1,16,h,w]."""
     dev = latent.device
@@ -58,7 +58,7 @@ def sdedit_upsample(model, noise: torch.Tensor, latent: torch.Tensor, blank_late
     cond = packing.pack_cond([blank_latent], [ones])                                   # :214
     fn = Sampler(create_transport("Linear", "velocity", do_shift=True)).sample_ode(
         sampling_method=solver, num_steps=steps, atol=1e-6, rtol=1e-3, reverse=False, do_shift=False,
-        time_shifting_factor=1.0, strength=strength)                                   # :184-193
+        time_shifting_factor=1.0, strength=strength, step_cache=step_cache)            # :184-193
     sample = fn(x0, model.forward, _kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]
     return packing.unpack_rows(sample, [(h, w)])[0]
 
@@ -66,7 +66,7 @@ def sdedit_upsample(model, noise: torch.Tensor, latent: torch.Tensor, blank_late
 @torch.no_grad()
 def sdedit_upsample_batch(model, noises: Sequence[torch.Tensor], latents: Sequence[torch.Tensor],
                           blank_latents: Sequence[torch.Tensor], txt: torch.Tensor, vec: torch.Tensor, cfg: float = 30.0,
-                          steps: int = 10, strength: float = 0.4, solver: str = "euler") -> List[torch.Tensor]:
+                          steps: int = 10, strength: float = 0.4, solver: str = "euler", step_cache=None) -> List[torch.Tensor]:
     """`sdedit_upsample` for K targets of ONE size and prompt advanced TOGETHER: the reference refines the masked cells of a
     grid one after the other (visualcloze.py:450-465), each an independent ODE solve over the same (T, N), so they stack into
     a per-GPU batch - one graph replay per solver step moves all of them (chunks of <= 4) and the GEMMs see M = K * L rows:
@@ -87,7 +87,7 @@ def sdedit_upsample_batch(model, noises: Sequence[torch.Tensor], latents: Sequen
     cond = torch.cat([packing.pack_cond([b], [ones]) for b in blank_latents], dim=0)
     fn = Sampler(create_transport("Linear", "velocity", do_shift=True)).sample_ode(
         sampling_method=solver, num_steps=steps, atol=1e-6, rtol=1e-3, reverse=False, do_shift=False,
-        time_shifting_factor=1.0, strength=strength)
+        time_shifting_factor=1.0, strength=strength, step_cache=step_cache)
     kw = _kwargs(img_ids, img_mask, txt.expand(K, -1, -1), vec.expand(K, -1), cond, cfg, dev)
     sample = fn(x0, model.forward, kw)[-1]
     return [packing.unpack_rows(sample[k:k + 1], [(h, w)])[0] for k in range(K)]
@@ -97,7 +97,8 @@ def sdedit_upsample_batch(model, noises: Sequence[torch.Tensor], latents: Sequen
 def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks: List[torch.Tensor],
                   t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, cfg: float = 30.0, steps: int = 30,
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
-                  solver: str = "euler", time_shifting_factor=1, rng: Optional[torch.Generator] = None) -> List[torch.Tensor]:
+                  solver: str = "euler", time_shifting_factor=1, rng: Optional[torch.Generator] = None,
+                  step_cache=None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -106,7 +107,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     DiagonalGaussian samples per row (None: drawn with torch.randn_like, as the reference's encode does).
     `rng`: the generator to draw from instead of a fresh one seeded with `seed` (the upsampling stage keeps drawing from
     the SAME generator, :450-458).  Returns the decoded rows `decode_rows` (default: all) as [3, H, W_row] tensors in
-    [0, 1] (:430-432)."""
+    [0, 1] (:430-432).  `step_cache`: a `transport.StepCache` or None (off, the default) - the opt-in first-block step cache of
+    the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`."""
     dev = row_images[0].device
     lat = []
     for i, img in enumerate(row_images):                                               # :377-378
@@ -119,7 +121,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     txt = t5(t5_ids)                                                                   # prepare_modified -> HFEmbedder
     vec, _ = clip(clip_ids)
     rows = denoise_grid(model, noise, lat, row_masks, txt, vec, cfg=cfg, steps=steps, solver=solver,
-                        time_shifting_factor=time_shifting_factor)
+                        time_shifting_factor=time_shifting_factor, step_cache=step_cache)
     out = []
     for i in (range(len(rows)) if decode_rows is None else decode_rows):
         img = ae.decode(rows[i])[0]                                                    # :430
@@ -150,7 +152,7 @@ def upsampling_size(target_size):
 @torch.no_grad()
 def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
                    rng: torch.Generator, cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
-                   encode_noise: Optional[Sequence[torch.Tensor]] = None, solver: str = "euler") -> torch.Tensor:
+                   encode_noise: Optional[Sequence[torch.Tensor]] = None, solver: str = "euler", step_cache=None) -> torch.Tensor:
     """`VisualClozeModel.upsampling` (visualcloze.py:147-245) for one image: resize on the host (PIL, bicubic - the
     default of `Image.resize`), VAE-encode the image and a blank, SDEdit from `strength` with everything masked, decode.
     image: PIL image or [3,H,W] tensor in [0,1]; t5_ids / clip_ids: the tokenised CONTENT prompt (prefix stripping and
@@ -171,7 +173,8 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
     noise = torch.randn([1, 16, latent.shape[-2], latent.shape[-1]], device=dev, generator=rng).to(torch.bfloat16)    # :217
     txt = t5(t5_ids)
     vec, _ = clip(clip_ids)
-    z = sdedit_upsample(model, noise, latent, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver)
+    z = sdedit_upsample(model, noise, latent, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver,
+                        step_cache=step_cache)
     img = ae.decode(z)[0]                                                              # :238
     return ((img.float() + 1.0) / 2.0).clamp_(0.0, 1.0)                                # :239-240
 
@@ -179,7 +182,7 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
 @torch.no_grad()
 def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
                     rng: torch.Generator, cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
-                    encode_noise: Optional[Sequence] = None, solver: str = "euler") -> List[torch.Tensor]:
+                    encode_noise: Optional[Sequence] = None, solver: str = "euler", step_cache=None) -> List[torch.Tensor]:
     """`upsample_image` for several images of one grid in ONE batched SDEdit solve (`sdedit_upsample_batch`).  Host work
     (resize), the VAE encodes and every random draw happen per image in the reference's order - image k: encode(image),
     encode(blank), noise from `rng` (visualcloze.py:200-217) - so each target starts from exactly the state the
@@ -205,7 +208,8 @@ def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: 
         noise.append(torch.randn([1, 16, lat[-1].shape[-2], lat[-1].shape[-1]], device=dev, generator=rng).to(torch.bfloat16))
     txt = t5(t5_ids)
     vec, _ = clip(clip_ids)
-    zs = sdedit_upsample_batch(model, noise, lat, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver)
+    zs = sdedit_upsample_batch(model, noise, lat, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver,
+                               step_cache=step_cache)
     return [((ae.decode(z)[0].float() + 1.0) / 2.0).clamp_(0.0, 1.0) for z in zs]     # :238-240
 
 
@@ -216,7 +220,7 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
                           content_clip_ids: Optional[torch.Tensor] = None, cfg: float = 30.0, steps: int = 30,
                           upsampling_steps: int = 10, upsampling_noise: float = 0.4, is_upsampling: bool = True,
                           encode_noise: Optional[List[torch.Tensor]] = None, upsample_encode_noise=None,
-                          solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True):
+                          solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True, step_cache=None):
     """Both stages of `process_images` chained (visualcloze.py:363-465): the grid is generated, its LAST row is decoded and
     quantised to 8 bits as `to_pil_image` does, every cell of that row whose `mask_position` is set is cropped
     (:452,461) and - with `is_upsampling` - refined by `upsample_image` at `target_size`, all noise coming from ONE
@@ -228,7 +232,7 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     last = len(row_images) - 1
     row = generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                         encode_noise=encode_noise, decode_rows=[last], solver=solver, time_shifting_factor=time_shifting_factor,
-                        rng=rng)[0]
+                        rng=rng, step_cache=step_cache)[0]
     pil = to_uint8_image(row)                                                          # :437-439
     ret_w, ret_h = pil.width, pil.height
     cells = [pil.crop((i * ret_w // grid_w, 0, (i + 1) * ret_w // grid_w, ret_h)) for i, m in enumerate(mask_position) if m]   # :452,461
@@ -236,7 +240,7 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     cclip = content_clip_ids if content_clip_ids is not None else clip_ids
     if is_upsampling and batch_targets and len(cells) > 1:
         return upsample_images(model, ae, t5, clip, cells, target_size, ct5, cclip, rng, cfg=cfg, steps=upsampling_steps,
-                               strength=upsampling_noise, encode_noise=upsample_encode_noise, solver=solver)
+                               strength=upsampling_noise, encode_noise=upsample_encode_noise, solver=solver, step_cache=step_cache)
     outs, k = [], 0
     for i, masked in enumerate(mask_position):
         if not masked:
@@ -246,7 +250,7 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
             en = None if upsample_encode_noise is None else upsample_encode_noise[k]
             outs.append(upsample_image(model, ae, t5, clip, cell, target_size, content_t5_ids if content_t5_ids is not None else t5_ids,
                                        content_clip_ids if content_clip_ids is not None else clip_ids, rng, cfg=cfg,
-                                       steps=upsampling_steps, strength=upsampling_noise, encode_noise=en, solver=solver))
+                                       steps=upsampling_steps, strength=upsampling_noise, encode_noise=en, solver=solver, step_cache=step_cache))
         else:
             import numpy as np
             outs.append(torch.from_numpy(np.asarray(cell, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0).to(dev))

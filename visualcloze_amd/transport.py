@@ -94,15 +94,54 @@ def _step_rk4(f, t0, t1, dt, y0):          # the 3/8 rule
 STEP_RULES = {"euler": _step_euler, "midpoint": _step_midpoint, "rk4": _step_rk4}
 
 
+class StepCache:
+    """Opt-in first-block step cache of the fused Euler loop (vc_flux_set_step_cache).  IT CHANGES RESULTS: an
+    evaluation whose first-block residual moved by less than `threshold` (relative L1 against the last computed evaluation's) is
+    replaced by that evaluation's remaining-blocks residual; at most `max_consecutive` evaluations in a row (-1: no limit).  Its
+    effect on image quality is unmeasured and no default threshold is recommended, hence none is offered."""
+    __slots__ = ("threshold", "max_consecutive")
+
+    def __init__(self, threshold: float, max_consecutive: int = 1):
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+            raise TypeError(f"StepCache: threshold must be a number, got {type(threshold).__name__}")
+        if isinstance(max_consecutive, bool) or not isinstance(max_consecutive, int):
+            raise TypeError(f"StepCache: max_consecutive must be an int, got {type(max_consecutive).__name__}")
+        if math.isnan(threshold) or threshold <= 0:
+            raise ValueError(f"StepCache: threshold must be positive (inf allowed), got {threshold}; pass step_cache=None for off")
+        if max_consecutive == 0 or max_consecutive < -1:
+            raise ValueError(f"StepCache: max_consecutive must be >= 1, or -1 for no limit, got {max_consecutive}")
+        object.__setattr__(self, "threshold", float(threshold))
+        object.__setattr__(self, "max_consecutive", int(max_consecutive))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("StepCache is immutable")
+
+    def __repr__(self):
+        return f"StepCache(threshold={self.threshold!r}, max_consecutive={self.max_consecutive})"
+
+    def __eq__(self, o):
+        return isinstance(o, StepCache) and (self.threshold, self.max_consecutive) == (o.threshold, o.max_consecutive)
+
+    def __hash__(self):
+        return hash((self.threshold, self.max_consecutive))
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
+        self.last_step_cache_stats = None      # of the last cached trajectory this sampler ran: one dict per chunk of samples
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False,
-                   do_shift=True, time_shifting_factor=None, strength=None, return_trajectory: bool = False):
+                   do_shift=True, time_shifting_factor=None, strength=None, return_trajectory: bool = False,
+                   step_cache: Optional[StepCache] = None):
         if sampling_method not in STEP_RULES:
             raise NotImplementedError(f"solver {sampling_method!r}: only the fixed-grid solvers {sorted(STEP_RULES)} are implemented "
                                       "(no adaptive or multistep methods)")
+        if step_cache is not None:
+            if not isinstance(step_cache, StepCache):
+                raise TypeError(f"step_cache must be a StepCache or None, got {type(step_cache).__name__}")
+            if sampling_method != "euler":
+                raise ValueError(f"step_cache works with sampling_method='euler' only, not {sampling_method!r}")
         t0, t1 = self.transport.check_interval(reverse=reverse)
         if strength is not None:
             t0 = (t1 - t0) * strength + t0
@@ -113,12 +152,20 @@ class Sampler:
             from .model import Flux
             owner = getattr(model, "__self__", None)
             if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward":
+                if step_cache is not None:      # never silently ignored: only the C handle's loop implements it
+                    if getattr(owner, "lora_mode", "merged") == "ref" or owner.handle() is None:
+                        raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' or the Python-ordered "
+                                         "plan (use_handle False)")
+                    if not _fusable(owner, x, sampling_method):
+                        raise ValueError(f"step_cache: a {x.dtype} state is stepped eagerly, where no cache exists")
                 if _fusable(owner, x, sampling_method):
-                    return _sample_fused(owner, x, dict(model_kwargs), t, return_trajectory, sampling_method)
+                    return _sample_fused(owner, x, dict(model_kwargs), t, return_trajectory, sampling_method, step_cache, self)
                 # stepped eagerly; the velocity of this model is a bf16 tensor as the reference's is under autocast
                 # (visualcloze.py:363) whatever dtype Flux.forward hands back to its caller: dt * f stays a bf16 product
                 fwd = model
                 model = lambda xin, **k: fwd(xin, **k).to(torch.bfloat16)  # noqa: E731
+            elif step_cache is not None:
+                raise ValueError("step_cache: only the fused loop of a visualcloze_amd.Flux implements it, not a foreign callable")
             return _sample_foreign(model, x, dict(model_kwargs), t, return_trajectory, sampling_method)
 
         return _sample
@@ -173,7 +220,7 @@ def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
 
 
 @torch.no_grad()
-def _sample_fused(flux, x, kw, t, return_trajectory, method="euler"):
+def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=None, sampler=None):
     eng = flux.engine()
     dev = eng.dev
     B, N, C = x.shape
@@ -204,6 +251,9 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler"):
     # the C handle runs the whole trajectory of a chunk in ONE call (vc_flux_sample_ode); the un-merged LoRA mode uses the
     # Python-ordered plan (bf16 states, Euler only: _fusable)
     h = flux.handle()
+    if h is not None:
+        h.set_step_cache(step_cache)               # None: off, whatever an earlier trajectory on this handle ran with
+    stats = []
     with torch.cuda.stream(st):
         s = st.cuda_stream
         for b0 in range(0, B, eng.MAX_BATCH):        # a chunk of samples advances together, one graph replay per step
@@ -215,6 +265,8 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler"):
                 xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()   # updated in place: never the caller's
                 tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
                 h.sample_ode(method, xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+                if step_cache is not None:
+                    stats.append(h.step_cache_stats(S))
                 if return_trajectory:
                     traj.append(torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)]))
                 out[sl].copy_(lay.img_rows_back(xs, sl))
@@ -237,6 +289,10 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler"):
                 traj.append(torch.stack(states))                  # [S, bs, N, C]
             out[sl].copy_(lay.img_rows_back(ws.XS.reshape(bs, N, C), sl))
     torch.cuda.current_stream().wait_stream(st)
+    if step_cache is not None:
+        flux.last_step_cache_stats = stats         # one dict per chunk of <= MAX_BATCH samples, in order
+        if sampler is not None:
+            sampler.last_step_cache_stats = stats
     if return_trajectory:
         return torch.cat((x.to(dev)[None], torch.cat(traj, dim=1).to(sdt)), dim=0)
     return out[None]
