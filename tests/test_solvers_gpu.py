@@ -1,6 +1,7 @@
 """-m gpu: the fixed-grid "midpoint" and "rk4" solvers in the fused sampling loop.
 
-  * vc_ode_stage alone against the literal torch expressions (transport.STEP_RULES), bit for bit;
+  * vc_ode_stage alone - and vc_euler_step / vc_euler_step_f32, the same kernel - against the literal torch expressions
+    (transport.STEP_RULES), bit for bit;
   * the fused loop (vc_flux_sample_ode: graph replays, device-side evaluation counter) == host-driven stepping through Flux.forward
     with those expressions, bit for bit, whole trajectories;
   * against the reference's own runs (tests/golden/solver_golden.npz).  Bound: 4 x floor_<method>, the reference's own bf16-vs-fp32
@@ -98,6 +99,40 @@ def test_ode_stage_equals_the_torch_expressions_bitwise(method, state, n, dt):
             if k is not None:
                 assert torch.equal(k[j], -vs[j])
     assert torch.equal(y, y1), f"{method}: {(y != y1).float().mean().item():.4f} of the states differ"
+
+
+# vc_euler_step / vc_euler_step_f32 run the same kernel as the Euler method: the literal rule again.  n = 1024 takes the 16-byte
+# path; n = 1027, and a state that starts one element into its allocation (an unaligned base), the element path.  The device
+# counter stands at 2 of a 3-entry dt table (Euler: one evaluation per step, dt = dts[counter]); without one, dt = dts[0].
+@pytest.mark.parametrize("counter", [True, False])
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("n", [1024, 1027])
+@pytest.mark.parametrize("state", ["bf16", "f32", "f32_shadow_only"])
+def test_euler_step_equals_the_torch_expression_bitwise(state, n, offset, counter):
+    from visualcloze_amd import hip
+    from visualcloze_amd.transport import STEP_RULES
+    dtype = torch.bfloat16 if state == "bf16" else torch.float32
+    g = torch.Generator().manual_seed(n + offset)
+    y0 = (torch.randn(n, generator=g) * 2).to(DEV, dtype)
+    v = torch.randn(n, generator=g).to(DEV, torch.bfloat16)
+    dts = torch.tensor([0.0371234, 9.0, -0.21347], dtype=torch.float32, device=DEV)
+    step = torch.tensor([2], dtype=torch.int32, device=DEV) if counter else None
+    dt_t = dts[2 if counter else 0]
+    y1 = y0 if state == "f32_shadow_only" else STEP_RULES["euler"](lambda t, y: -v, None, None, dt_t, y0)
+    assert y1.dtype == dtype
+    buf = torch.zeros(n + 8, dtype=dtype, device=DEV)                 # the state is a view; the elements around it stay zero
+    y = buf[offset:offset + n]
+    y.copy_(y0)
+    if state == "bf16":
+        hip.euler_step(y, v, dts, step)
+    else:
+        shadow = torch.zeros(n, dtype=torch.bfloat16, device=DEV)
+        hip.euler_step_f32(y, shadow, None if state == "f32_shadow_only" else v, dts, step)      # v None: shadow = bf16(x32) only
+    torch.cuda.synchronize()
+    assert torch.equal(y, y1), f"{(y != y1).float().mean().item():.4f} of the states differ"
+    assert not buf[:offset].any() and not buf[offset + n:].any()
+    if state != "bf16":
+        assert torch.equal(shadow, y1.to(torch.bfloat16))             # what img_in reads next
 
 
 def test_ode_stage_argument_errors():

@@ -1,5 +1,5 @@
-"""Per-step busy/idle analysis of a rocprofv3 --kernel-trace results .db: finds the repeating step (euler_kernel marks the
-end of each evaluation), and prints per-kernel time inside a steady-state step plus the idle gaps between kernels.
+"""Per-step busy/idle analysis of a rocprofv3 --kernel-trace results .db: finds the repeating step (the solver update,
+ode_stage_kernel, marks the end of each evaluation), and prints per-kernel time inside a steady-state step plus the idle gaps between kernels.
 
     python tools/rocprof_gaps.py /tmp/prof/x_results.db
 """
@@ -18,10 +18,10 @@ def main(path):
         names = [r[0] for r in c.execute("select name from sqlite_master where type in ('table','view')")]
         print("no 'kernels' view; tables/views:", names); return
     rows = [(short(n), s, e, g, w) for n, s, e, g, w in rows]
-    ends = [i for i, r in enumerate(rows) if r[0].startswith("euler_kernel")]
+    ends = [i for i, r in enumerate(rows) if r[0].startswith("ode_stage_kernel")]
     if len(ends) < 6:
         print("too few steps", len(ends)); return
-    # steady state: steps between the (n-11)th and the last euler kernel
+    # steady state: steps between the (n-11)th and the last update kernel
     lo, hi = ends[-11], ends[-1]
     nsteps = 10
     seg = rows[lo + 1: hi + 1]

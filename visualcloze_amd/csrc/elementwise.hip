@@ -1,7 +1,7 @@
 // Small elementwise kernels of the denoising path (all HBM/launch-bound, bf16 storage, f32 math).
 //   timestep_embedding  layers.py:28-49      silu / add3   MLPEmbedder + vec sum, model.py:102-107
-//   concat_cols         transport.py:193-196 (x || cond)   euler_step   torchdiffeq fixed-grid Euler update
-//   ode_stage           the stage combinations of the fixed-grid midpoint / rk4 steps (integrators.py:119, method=...)
+//   concat_cols         transport.py:193-196 (x || cond)
+//   ode_stage           the update of the fixed-grid Euler step and the stage combinations of midpoint / rk4 (integrators.py:119, method=...)
 #include "common.h"
 #include "vcloze_internal.h"
 
@@ -45,33 +45,6 @@ __global__ void concat_cols_kernel(const u32x4* __restrict__ x, int cxc, const u
   out[i] = (c < cxc) ? x[r * cxc + c] : cond[r * ccc + (c - cxc)];
 }
 
-__global__ void euler_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ v, const float* __restrict__ dts,
-                             const int* __restrict__ step_ptr, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  // dt is a 0-dim f32 tensor in the reference; multiplying a bf16 tensor by it casts dt to the common dtype
-  // (bf16) first, so the effective step is bf16(dt) (verified against torch: 100 % bitwise agreement)
-  const float dt = rbf(dts[step_ptr ? *step_ptr : 0]);
-  const float dy = rbf(dt * (-bf2f(v[i])));
-  x[i] = f2bf(bf2f(x[i]) + dy);
-}
-
-// The same update for a caller whose ODE state is f32 (integrators.py:119 keeps the state's dtype): y1 = y0 + dt * f0 with
-// f0 bf16 is f32(y0) + f32(bf16(bf16(dt) * f0)) in torch's type promotion; the bf16 shadow is what img_in reads next
-// (its Linear rounds the f32 input to bf16 under autocast, visualcloze.py:363).  v == nullptr: refresh the shadow only.
-__global__ void euler_f32_kernel(float* __restrict__ x32, bf16_t* __restrict__ shadow, const bf16_t* __restrict__ v,
-                                 const float* __restrict__ dts, const int* __restrict__ step_ptr, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float x = x32[i];
-  if (v) {
-    const float dt = rbf(dts[step_ptr ? *step_ptr : 0]);
-    x += rbf(dt * (-bf2f(v[i])));
-    x32[i] = x;
-  }
-  shadow[i] = f2bf(x);
-}
-
 // SDEdit start state (visualcloze.py:221): x0 = bf16(bf16(noise*(1-s)) + bf16(latent*s)), s a python float
 __global__ void sdedit_mix_kernel(const bf16_t* __restrict__ noise, const bf16_t* __restrict__ latent, float s,
                                   bf16_t* __restrict__ out, long n) {
@@ -103,20 +76,22 @@ __global__ void gate_residual_kernel(const bf16_t* __restrict__ y, long ldy, con
 
 __global__ void step_advance_kernel(int* step_ptr) { if (threadIdx.x == 0 && blockIdx.x == 0) *step_ptr += 1; }
 
-// ---- vc_ode_stage: every arithmetic line of the fixed-grid midpoint / rk4 (3/8 rule) steps that is not a model evaluation ----
+// ---- the solver update: every arithmetic line of a fixed-grid Euler / midpoint / rk4 (3/8 rule) step that is not a model evaluation ----
 // The step functions are torchdiffeq 0.2.x's fixed-grid solvers AS RECALLED (the package was not available to check against:
 // "unpinned against real torchdiffeq"), with f = -v the drift of transport.py:361-410 and torch's own roundings,
 // operation by operation, for the device-resident operands the sampler hands torch: a bf16 tensor times the 0-dim f32 DEVICE
-// tensor dt (or 0.5 * dt) multiplies by bf16(dt), a bf16 tensor times a Python float multiplies by the float UNROUNDED
-// (f32(1/3)), and every bf16 intermediate is materialised.  THE expressions, one place: ode_update = the bf16 term U that is added
-// to y0 (in bf16 for a bf16 state, in f32 for an f32 state - torch's promotion of f32 + bf16):
+// tensor dt (or 0.5 * dt) multiplies by bf16(dt) (verified against torch: 100 % bitwise agreement), a bf16 tensor times a Python
+// float multiplies by the float UNROUNDED (f32(1/3)), and every bf16 intermediate is materialised.  THE expressions, one place:
+// ode_update = the bf16 term U that is added to y0 (in bf16 for a bf16 state, in f32 for an f32 state - torch's promotion of
+// f32 + bf16; integrators.py:119 keeps the state's dtype):
+//   euler     stage 0: y1 = y0 + dt * f0                             (= the last midpoint stage)
 //   midpoint  stage 0: y_mid = y0 + f0 * half_dt                     stage 1: y1 = y0 + dt * f1
 //   rk4       stage 0: y0 + dt * k1 * (1/3)                          stage 1: y0 + dt * (k2 - k1 * (1/3))
 //             stage 2: y0 + dt * (k1 - k2 + k3)                      stage 3: y1 = y0 + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
 VC_DEV float ode_update(int method, int stage, float dtb, float hdb, float f, float k1, float k2, float k3) {
 #pragma clang fp contract(off)
   const float c13 = (float)(1.0 / 3.0);
-  if (method == VC_SOLVER_MIDPOINT) return stage == 0 ? rbf(f * hdb) : rbf(dtb * f);
+  if (method != VC_SOLVER_RK4) return method == VC_SOLVER_MIDPOINT && stage == 0 ? rbf(f * hdb) : rbf(dtb * f);
   switch (stage) {
     case 0: return rbf(rbf(dtb * f) * c13);
     case 1: return rbf(dtb * rbf(f - rbf(k1 * c13)));
@@ -126,19 +101,15 @@ VC_DEV float ode_update(int method, int stage, float dtb, float hdb, float f, fl
 }
 
 // One chunk of W elements per thread: W = 8 (16-byte accesses of the bf16 arrays, two of the f32 state) or 1.  Stage j keeps k_{j+1}
-// where a later stage reads it (rk4, j < 3), writes the next evaluation's bf16 input y_in, and the LAST stage updates the state.
+// where a later stage reads it (rk4, j < 3), writes the next evaluation's bf16 input y_in (the bf16 shadow of an f32 state: its
+// Linear rounds the f32 input to bf16 under autocast, visualcloze.py:363; null where the bf16 state itself is read next), and the
+// LAST stage updates the state.  v == nullptr: y_in = bf16(y) only, the state is untouched.
 template <bool F32, int W>
 __global__ void ode_stage_kernel(int method, int stage_arg, void* __restrict__ y, const bf16_t* __restrict__ v, bf16_t* __restrict__ k,
                                  bf16_t* __restrict__ y_in, const float* __restrict__ dts, const int* __restrict__ eval_ptr, long n) {
 #pragma clang fp contract(off)
   const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c * W >= n) return;
-  const int evals = method == VC_SOLVER_MIDPOINT ? 2 : 4;
-  const int e = eval_ptr ? *eval_ptr : 0;
-  const int stage = stage_arg >= 0 ? stage_arg : e % evals;
-  const float dt = dts[e / evals];
-  const float dtb = rbf(dt), hdb = rbf(0.5f * dt);
-  const bool rk4 = method == VC_SOLVER_RK4, last = stage == evals - 1;
   float f[W], k1[W], k2[W], k3[W], y0[W];
   auto load = [&](const bf16_t* p, float (&o)[W]) {
     if constexpr (W == 8) {
@@ -159,13 +130,6 @@ __global__ void ode_stage_kernel(int method, int stage_arg, void* __restrict__ y
       p[c] = f2bf(o[0]);
     }
   };
-  load(v, f);
-#pragma unroll
-  for (int i = 0; i < W; ++i) { f[i] = -f[i]; k1[i] = k2[i] = k3[i] = 0.0f; }       // the drift is -model(...): exact
-  if (rk4 && stage >= 1) load(k, k1);
-  if (rk4 && stage >= 2) load(k + n, k2);
-  if (rk4 && stage == 3) load(k + 2 * n, k3);
-  if (rk4 && !last) store(k + (long)stage * n, f);
   if constexpr (F32) {
     if constexpr (W == 8) {
       const f32x4 a = ((const f32x4*)y)[2 * c], b = ((const f32x4*)y)[2 * c + 1];
@@ -177,13 +141,27 @@ __global__ void ode_stage_kernel(int method, int stage_arg, void* __restrict__ y
   } else {
     load((const bf16_t*)y, y0);
   }
+  if (!v) { store(y_in, y0); return; }
+  const int evals = vc_evals_of(method);
+  const int e = eval_ptr ? *eval_ptr : 0;
+  const int stage = stage_arg >= 0 ? stage_arg : e % evals;
+  const float dt = dts[e / evals];
+  const float dtb = rbf(dt), hdb = rbf(0.5f * dt);
+  const bool rk4 = method == VC_SOLVER_RK4, last = stage == evals - 1;
+  load(v, f);
+#pragma unroll
+  for (int i = 0; i < W; ++i) { f[i] = -f[i]; k1[i] = k2[i] = k3[i] = 0.0f; }       // the drift is -model(...): exact
+  if (rk4 && stage >= 1) load(k, k1);
+  if (rk4 && stage >= 2) load(k + n, k2);
+  if (rk4 && stage == 3) load(k + 2 * n, k3);
+  if (rk4 && !last) store(k + (long)stage * n, f);
   float y1[W];
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     const float s = y0[i] + ode_update(method, stage, dtb, hdb, f[i], k1[i], k2[i], k3[i]);
     y1[i] = F32 ? s : rbf(s);
   }
-  store(y_in, y1);
+  if (y_in) store(y_in, y1);
   if (!last) return;
   if constexpr (F32) {
     if constexpr (W == 8) {
@@ -247,26 +225,10 @@ int vc_concat_cols_launch(const void* x, int cx, const void* cond, int cc, void*
   hipLaunchKernelGGL(concat_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)x, cx / 8, (const u32x4*)cond, cc / 8, (u32x4*)out, (long)rows);
   VC_CHECK_LAUNCH("concat_cols");
 }
-int vc_euler_launch(void* x, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
-  if (!x || !v || !dts || n <= 0) { snprintf(err, errlen, "euler_step: bad args"); return VC_ERR_ARG; }
-  hipLaunchKernelGGL(euler_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)v, dts, step_ptr, (long)n);
-  VC_CHECK_LAUNCH("euler_step");
-}
-int vc_euler_f32_launch(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s,
-                        char* err, int errlen) {
-  if (!x32 || !shadow || (v && !dts) || n <= 0) { snprintf(err, errlen, "euler_step_f32: bad args"); return VC_ERR_ARG; }
-  hipLaunchKernelGGL(euler_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x32, (bf16_t*)shadow, (const bf16_t*)v, dts,
-                     step_ptr, (long)n);
-  VC_CHECK_LAUNCH("euler_step_f32");
-}
-int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
-                        const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
-  const int evals = vc_evals_of(method);
-  if (evals < 2) { snprintf(err, errlen, "ode_stage: method %d is not VC_SOLVER_MIDPOINT or VC_SOLVER_RK4", method); return VC_ERR_ARG; }
-  if (!y || !v || !y_in || !dts || n <= 0 || stage >= evals || (stage < 0 && !eval_ptr) || (method == VC_SOLVER_RK4 && !k)) {
-    snprintf(err, errlen, "ode_stage: bad args");
-    return VC_ERR_ARG;
-  }
+// the one launch behind vc_euler_step, vc_euler_step_f32 and vc_ode_stage, which check their own arguments (`what` names the caller
+// in a launch error).  y_in may be null (the state alone is written), v may be null (y_in = bf16(y) alone, f32 state)
+int vc_ode_update_launch(const char* what, int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in,
+                         const float* dts, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
   // 16-byte accesses: every base 16-byte aligned and n a multiple of 8 (k2, k3 start n and 2n elements into k); else element-wise
   const uintptr_t bases = (uintptr_t)y | (uintptr_t)v | (uintptr_t)k | (uintptr_t)y_in;
   const bool vec = n % 8 == 0 && (bases & 15) == 0;
@@ -278,7 +240,28 @@ int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const
   if (state_is_bf16) { if (vec) VC_ODE_LAUNCH(false, 8); else VC_ODE_LAUNCH(false, 1); }
   else { if (vec) VC_ODE_LAUNCH(true, 8); else VC_ODE_LAUNCH(true, 1); }
 #undef VC_ODE_LAUNCH
-  VC_CHECK_LAUNCH("ode_stage");
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) { snprintf(err, errlen, "%s launch: %s", what, hipGetErrorString(he)); return VC_ERR_HIP; }
+  return VC_OK;
+}
+int vc_euler_launch(void* x, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (!x || !v || !dts || n <= 0) { snprintf(err, errlen, "euler_step: bad args"); return VC_ERR_ARG; }
+  return vc_ode_update_launch("euler_step", VC_SOLVER_EULER, 0, x, 1, v, nullptr, nullptr, dts, step_ptr, n, s, err, errlen);
+}
+int vc_euler_f32_launch(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s,
+                        char* err, int errlen) {
+  if (!x32 || !shadow || (v && !dts) || n <= 0) { snprintf(err, errlen, "euler_step_f32: bad args"); return VC_ERR_ARG; }
+  return vc_ode_update_launch("euler_step_f32", VC_SOLVER_EULER, 0, x32, 0, v, nullptr, shadow, dts, step_ptr, n, s, err, errlen);
+}
+int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
+                        const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
+  const int evals = vc_evals_of(method);
+  if (evals < 2) { snprintf(err, errlen, "ode_stage: method %d is not VC_SOLVER_MIDPOINT or VC_SOLVER_RK4", method); return VC_ERR_ARG; }
+  if (!y || !v || !y_in || !dts || n <= 0 || stage >= evals || (stage < 0 && !eval_ptr) || (method == VC_SOLVER_RK4 && !k)) {
+    snprintf(err, errlen, "ode_stage: bad args");
+    return VC_ERR_ARG;
+  }
+  return vc_ode_update_launch("ode_stage", method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, s, err, errlen);
 }
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen) {
   if (!step_ptr) { snprintf(err, errlen, "step_advance: null"); return VC_ERR_ARG; }

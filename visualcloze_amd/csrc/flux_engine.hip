@@ -12,7 +12,8 @@
 //   HID [B*L, mlp]      MLP hidden of the DoubleStream blocks (image rows first)
 //   MOD [S*B, n_mod]    every modulation vector of every block for every evaluation (row s*B + b, evaluation order)
 //   XS / COND / XIN / V the ODE state, the conditioning columns, x || cond, the velocity
-//   KS [3][B*N*out] / YIN   k1..k3 of an rk4 step / the input state of the next evaluation (midpoint, rk4: vc_ode_stage)
+//   KS [3][B*N*out] / YIN   k1..k3 of an rk4 step / the input state of the next evaluation (midpoint, rk4); every solver's update
+//                           is ONE kernel (ode_stage_kernel, elementwise.hip) behind ONE call (ode_update below)
 //   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
 #include "common.h"
@@ -52,6 +53,24 @@ struct Buffers {   // the workspace carve-up
   int64_t sk_ws_bytes = 0;
 };
 
+// vc_flux_set_option: every option of the plan, once.  OPTIONS below is the table that sets, clamps and compares them
+struct Options {
+  int attn_variant = -1, tile_cfg = 0, fuse_qnorm = 2, fuse_vt = 1, qkv_heads = 0, fuse_knorm = 0, logit_bound_milli = 0, mlp_first = 0, splitk = 1;
+};
+enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
+#define OPT(name, clamp) {#name, &Options::name, clamp}
+constexpr struct { const char* name; int Options::*member; Clamp clamp; } OPTIONS[] = {
+    OPT(attn_variant, ANY),      OPT(tile_cfg, ANY),   OPT(fuse_qnorm, ZERO_TO_2),
+    OPT(fuse_vt, BOOL),          OPT(qkv_heads, ZERO_OR_H),      // the bound qkv weights (linear1's first 3D rows) are head-permuted (vcloze_hip.h)
+    OPT(fuse_knorm, BOOL),       OPT(logit_bound_milli, AT_LEAST_0),
+    OPT(mlp_first, BOOL),        OPT(splitk, BOOL),              // split-K remainders (VcGemmArgs.splitk_ws) where the launcher's model takes them
+};
+#undef OPT
+inline bool operator==(const Options& a, const Options& b) {
+  for (const auto& o : OPTIONS) if (a.*o.member != b.*o.member) return false;
+  return true;
+}
+
 struct Flux : Buffers {
   VcFluxConfig cfg{};
   int D = 0, H = 0, mlp = 0;
@@ -64,8 +83,8 @@ struct Flux : Buffers {
   std::vector<DoubleW> dbl;
   std::vector<SingleW> sgl;
   int64_t final_mod = 0;
-  // options
-  int attn_variant = -1, tile_cfg = 0, fuse_qnorm = 2, fuse_vt = 1, qkv_heads = 0, fuse_knorm = 0, logit_bound_milli = 0, mlp_first = 0, splitk = 1, n_cu = 256;
+  Options opt;
+  int n_cu = 256;
   // prepared geometry + workspace carve-up
   bool prepared = false;
   bool ws_sized = false;     // vc_flux_workspace_bytes / vc_flux_prepare have answered with the current carve-up
@@ -78,11 +97,10 @@ struct Flux : Buffers {
   // whole step, so a cached trajectory never evicts a graph of its own)
   struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; } step;
   struct Key {
-    char* base; int B, T, N, S, ragged, gapped, variant, tile, fuse, fuse_vt, state_f32, qkv_heads, fuse_knorm, bound, mlp_first, splitk, method, cache; hipStream_t s;
+    char* base; int B, T, N, S, ragged, gapped, variant, state_f32, method, cache; Options opt; hipStream_t s;   // variant: resolved
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
-             variant == o.variant && tile == o.tile && fuse == o.fuse && fuse_vt == o.fuse_vt && state_f32 == o.state_f32 &&
-             qkv_heads == o.qkv_heads && fuse_knorm == o.fuse_knorm && bound == o.bound && mlp_first == o.mlp_first && splitk == o.splitk && method == o.method && cache == o.cache && s == o.s;
+             variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s;
     }
   } key{};
   std::vector<std::pair<Key, Step>> graphs;
@@ -290,17 +308,17 @@ int resolve(Flux& f, Err e) {
 int attention_variant(const Flux& f);
 // (where the one-wave-per-SIMD attention kernel runs: small geometries keep ONE pre-pass launch for q and k - the fused
 // epilogue needs the 256x192 tile, which their short M does not fill)
-bool kn_in_gemm(const Flux& f) { return f.fuse_knorm && f.qkv_heads > 0 && (attention_variant(f) & 8); }
-bool qn_in_gemm(const Flux& f) { return kn_in_gemm(f) && f.fuse_qnorm >= 2; }
-int qkv_epi(const Flux& f) { return f.fuse_vt || f.qkv_heads > 0 ? VC_EPI_QKV : VC_EPI_BIAS; }
+bool kn_in_gemm(const Flux& f) { return f.opt.fuse_knorm && f.opt.qkv_heads > 0 && (attention_variant(f) & 8); }
+bool qn_in_gemm(const Flux& f) { return kn_in_gemm(f) && f.opt.fuse_qnorm >= 2; }
+int qkv_epi(const Flux& f) { return f.opt.fuse_vt || f.opt.qkv_heads > 0 ? VC_EPI_QKV : VC_EPI_BIAS; }
 void with_vt(Flux& f, VcGemmProblem& p, int rows, int row0, const void* q_scale, const void* k_scale) {
-  if (f.fuse_vt) { p.vt = f.VT; p.vt_bstride = (int64_t)f.H * 128 * f.Lp; p.vt_col0 = 2 * f.D; p.vt_lpad = f.Lp; }
-  if (f.qkv_heads > 0) {
-    p.kn_heads = f.qkv_heads;
+  if (f.opt.fuse_vt) { p.vt = f.VT; p.vt_bstride = (int64_t)f.H * 128 * f.Lp; p.vt_col0 = 2 * f.D; p.vt_lpad = f.Lp; }
+  if (f.opt.qkv_heads > 0) {
+    p.kn_heads = f.opt.qkv_heads;
     if (kn_in_gemm(f)) { p.kn_scale = k_scale; p.kn_rope = f.ROPE; p.kn_rope_bstride = (int64_t)f.L * 128; }
     if (qn_in_gemm(f)) { p.qn_scale = q_scale; p.qn_prescale = 1; }
   }
-  if (f.fuse_vt || f.qkv_heads > 0) { p.vt_rpb = rows; p.vt_row0 = row0; }
+  if (f.opt.fuse_vt || f.opt.qkv_heads > 0) { p.vt_rpb = rows; p.vt_row0 = row0; }
 }
 
 VcGemmProblem prob(const void* A, int64_t lda, const Lin& w, void* C, int64_t ldc, int M) {
@@ -334,11 +352,11 @@ int gemm(Flux& f, const VcGemmProblem* ps, int n, int epi, const int32_t* step_p
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < n; ++i) a.p[i] = ps[i];
   a.nprob = n; a.epi = epi; a.step_ptr = step_ptr; a.gate_step_stride = gate_step_stride;
-  if (f.splitk) { a.splitk_ws = f.SK_WS; a.splitk_ws_bytes = f.sk_ws_bytes; }   // the launcher's cost model decides
+  if (f.opt.splitk) { a.splitk_ws = f.SK_WS; a.splitk_ws_bytes = f.sk_ws_bytes; }   // the launcher's cost model decides
   double flops = 0;
   for (int i = 0; i < n; ++i) flops += 2.0 * ps[i].M * ps[i].N * ps[i].K;
   TRY(prof_open(f, s, VC_LAUNCH_GEMM, epi, ps[0].N, ps[0].K, flops, 0, e));
-  TRY(vc_gemm_launch(a, f.tile_cfg, s, e.buf, e.len));
+  TRY(vc_gemm_launch(a, f.opt.tile_cfg, s, e.buf, e.len));
   return prof_close(f, s, e);
 }
 int lin(Flux& f, const Lin& w, const void* A, int64_t lda, void* C, int64_t ldc, int M, int epi, hipStream_t s, Err e) {
@@ -368,7 +386,7 @@ int ln1(Flux& f, const Ctx& c, int64_t mod, Err e) {                  // the joi
 }
 
 int attention_variant(const Flux& f) {
-  if (f.attn_variant >= 0) return f.attn_variant;
+  if (f.opt.attn_variant >= 0) return f.opt.attn_variant;
   // 28 = 12 + 16: one wave per SIMD, tail split, and - where the stream form of the kernel runs - the tail pieces combined
   // inside the launch (the flag words of ATT_SCRATCH are zeroed by vc_flux_prepare, and only this handle's launches, ordered on
   // one stream, touch it).  Fewer 256-query items than CUs (cfg 1: 168): the same kernel WITHOUT a split (8) - one item per
@@ -382,9 +400,9 @@ int attention_variant(const Flux& f) {
 // QKNorm + RoPE (+ V^T) and the joint attention over QKV -> CAT[:, :D] (layers.py:165-185 / 236-241)
 int attention(Flux& f, const Ctx& c, const void* q1, const void* k1, const void* q2, const void* k2, int split, float block_bound, Err e) {
   const int variant = attention_variant(f);
-  const bool fused_q = (variant & 8) && f.fuse_qnorm, q_done = qn_in_gemm(f);     // q_done: by the projection's epilogue, prescaled
+  const bool fused_q = (variant & 8) && f.opt.fuse_qnorm, q_done = qn_in_gemm(f);     // q_done: by the projection's epilogue, prescaled
   const int64_t ld = 3 * f.D, ldo = f.D + f.mlp;
-  const int parts = (kn_in_gemm(f) ? 0 : VC_QKN_K) | (fused_q ? 0 : VC_QKN_Q) | (f.fuse_vt ? 0 : VC_QKN_VT);
+  const int parts = (kn_in_gemm(f) ? 0 : VC_QKN_K) | (fused_q ? 0 : VC_QKN_Q) | (f.opt.fuse_vt ? 0 : VC_QKN_VT);
   if (parts)
     TRY(vc_qknorm_rope_vt_launch(f.QKV, ld, f.L * ld, q1, k1, q2, k2, split, f.ROPE, (int64_t)f.L * 128, f.VT, f.B, f.L, f.Lp, f.H,
                                  parts, c.s, e.buf, e.len));
@@ -400,9 +418,9 @@ int attention(Flux& f, const Ctx& c, const void* q1, const void* k1, const void*
   else if (fused_q) { a.q_scale = q1; a.q_scale2 = q2; a.split = split; a.rope = f.ROPE; a.rope_bstride = (int64_t)f.L * 128; }
   // option logit_bound_milli > 0 switches the bounded softmax on; every block is then held to ITS OWN bound (never above the
   // caller's): a checkpoint with a few outlier QK-norm scales runs the running-max template in those blocks only
-  const float cap = (float)f.logit_bound_milli * 1e-3f;
-  a.logit_bound = f.logit_bound_milli > 0 ? (block_bound < cap ? block_bound : cap) : 0.0f;
-  if (f.logit_bound_milli > 0 && !(block_bound < 1e30f)) a.logit_bound = 1e30f;       // (non-finite scales: no bound)
+  const float cap = (float)f.opt.logit_bound_milli * 1e-3f;
+  a.logit_bound = f.opt.logit_bound_milli > 0 ? (block_bound < cap ? block_bound : cap) : 0.0f;
+  if (f.opt.logit_bound_milli > 0 && !(block_bound < 1e30f)) a.logit_bound = 1e30f;       // (non-finite scales: no bound)
   TRY(prof_open(f, c.s, VC_LAUNCH_ATTENTION, variant, 0, 0, 4.0 * f.L * f.L * f.D * f.B, 0, e));     // the attention launch(es) alone
   TRY(vc_attention_launch(a, c.s, e.buf, e.len));
   return prof_close(f, c.s, e);
@@ -460,9 +478,9 @@ int single_block(Flux& f, const Ctx& c, const SingleW& w, Err e) {
   }
   // the attention kernel runs right behind the projection that wrote its operands, and the MLP-up GEMM right in front of the
   // linear2 that reads its 97 MB (option mlp_first = the reference's textual order, layers.py:236-243)
-  if (f.mlp_first) TRY(lin(f, w.mlp, f.XH, D, f.CAT + D, ldc, M, VC_EPI_GELU, c.s, e));
+  if (f.opt.mlp_first) TRY(lin(f, w.mlp, f.XH, D, f.CAT + D, ldc, M, VC_EPI_GELU, c.s, e));
   TRY(attention(f, c, w.qs, w.ks, nullptr, nullptr, 0, w.bound, e));
-  if (!f.mlp_first) TRY(lin(f, w.mlp, f.XH, D, f.CAT + D, ldc, M, VC_EPI_GELU, c.s, e));
+  if (!f.opt.mlp_first) TRY(lin(f, w.mlp, f.XH, D, f.CAT + D, ldc, M, VC_EPI_GELU, c.s, e));
   VcGemmProblem p = prob(f.CAT, ldc, w.lin2, f.X, D, M);
   p.res = f.X; p.ldres = D; p.gate = modp(f, w.mod, 2); p.gate_bstride = f.n_mod; p.rows_per_batch = f.L;
   return gemm(f, &p, 1, VC_EPI_GATE_RES, c.step_ptr, c.mss, c.s, e);
@@ -473,15 +491,28 @@ int d2d(void* dst, const void* src, int64_t bytes, hipStream_t s, Err e) {
   return VC_OK;
 }
 
-// Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it: the
-// Euler update of XS, or the midpoint / rk4 stage combination (state -> YIN, the input of the next evaluation).  step_ptr counts
-// EVALUATIONS (= steps for Euler).
+// Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it
+// (ode_update: the Euler step, or a midpoint / rk4 stage combination).  step_ptr counts EVALUATIONS (= steps for Euler).
 // in three pieces, which `evaluate` issues back to back (the plan of every evaluation without the step cache) and the cached step
 // issues with its own launches in between: the inputs, the blocks from double block `first` on, the last layer + update.
+// where the sample in flight keeps its ODE state (in the caller's dtype), and the bf16 rows the next evaluation reads: the state
+// itself for a bf16 Euler step, XS as the bf16 shadow of an f32 Euler state, else YIN - the stage input of a midpoint / rk4 step
+void* ode_state(Flux& f) { return f.state_f32 ? (void*)f.XS32 : (void*)f.XS; }
+int64_t ode_state_bytes(const Flux& f) { return (int64_t)f.B * f.N * f.cfg.out_channels * (f.state_f32 ? 4 : 2); }
+bf16_t* next_input(Flux& f) { return f.method == VC_SOLVER_EULER ? f.XS : f.YIN; }
+// the solver's update behind an evaluation (v = V), or with v null next_input = bf16(state) alone; next_input is not handed over
+// where it IS the state (the kernel's pointers are __restrict__)
+int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, Err e) {
+  void* y = ode_state(f);
+  bf16_t* y_in = next_input(f);
+  return vc_ode_update_launch("ode_update", f.method, -1, y, !f.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
+                              (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
+}
+
 int eval_inputs(Flux& f, bool concat, const void* img_rows, hipStream_t s, Err e) {
   const int B = f.B, T = f.T, N = f.N, D = f.D;
   const int in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
-  if (concat) TRY(vc_concat_cols_launch(f.method == VC_SOLVER_EULER ? f.XS : f.YIN, out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
+  if (concat) TRY(vc_concat_cols_launch(next_input(f), out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
   TRY(d2d(f.XT, f.TXT0, (int64_t)B * T * D * 2, s, e));
   return lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e);
 }
@@ -506,13 +537,8 @@ int eval_output(Flux& f, const Ctx& c, void* out, bool euler, Err e) {
   VcGemmProblem p = prob(f.XH + (int64_t)T * D, D, f.final_lin, out ? out : f.V, out_ch, B * N);
   p.a_rpb = N; p.a_bstride = (int64_t)L * D;
   TRY(gemm(f, &p, 1, VC_EPI_BIAS, nullptr, 0, s, e));
-  if (euler && f.method != VC_SOLVER_EULER) {
-    TRY(vc_ode_stage_launch(f.method, -1, f.state_f32 ? (void*)f.XS32 : (void*)f.XS, !f.state_f32, f.V, f.KS, f.YIN, f.DTS, step_ptr,
-                            (int64_t)B * N * out_ch, s, e.buf, e.len));
-    TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
-  } else if (euler) {
-    if (f.state_f32) TRY(vc_euler_f32_launch(f.XS32, f.XS, f.V, f.DTS, step_ptr, (int64_t)B * N * out_ch, s, e.buf, e.len));
-    else TRY(vc_euler_launch(f.XS, f.V, f.DTS, step_ptr, (int64_t)B * N * out_ch, s, e.buf, e.len));
+  if (euler) {
+    TRY(ode_update(f, f.V, step_ptr, s, e));
     TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
   }
   return VC_OK;
@@ -635,8 +661,7 @@ template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issu
   return VC_OK;
 }
 int step_graph(Flux& f, hipStream_t s, Err e) {
-  Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.tile_cfg, f.fuse_qnorm, f.fuse_vt, f.state_f32,
-              f.qkv_heads, f.fuse_knorm, f.logit_bound_milli, f.mlp_first, f.splitk, f.method, f.sc_active, s};
+  Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s};
   for (size_t i = 0; i < f.graphs.size(); ++i)
     if (f.graphs[i].first == k) {
       auto hit = f.graphs[i];
@@ -749,19 +774,19 @@ int64_t vc_flux_mod_offset_impl(void* handle, const char* name) {
 int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char* err, int errlen) {
   H(handle);
   if (!name) FAIL(VC_ERR_ARG, "flux_set_option: null name");
-  if (!strcmp(name, "attn_variant")) f.attn_variant = value;
-  else if (!strcmp(name, "tile_cfg")) f.tile_cfg = value;
-  else if (!strcmp(name, "fuse_qnorm")) f.fuse_qnorm = value < 0 ? 0 : value > 2 ? 2 : value;
-  else if (!strcmp(name, "fuse_vt")) f.fuse_vt = value != 0;
-  else if (!strcmp(name, "qkv_heads")) {      // the bound qkv weights (linear1's first 3D rows) are head-permuted (vcloze_hip.h)
-    if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H);
-    f.qkv_heads = value;
-  } else if (!strcmp(name, "fuse_knorm")) f.fuse_knorm = value != 0;
-  else if (!strcmp(name, "logit_bound_milli")) f.logit_bound_milli = value > 0 ? value : 0;
-  else if (!strcmp(name, "mlp_first")) f.mlp_first = value != 0;
-  else if (!strcmp(name, "splitk")) f.splitk = value != 0;      // split-K remainders (VcGemmArgs.splitk_ws) where the launcher's model takes them
-  else FAIL(VC_ERR_ARG, "flux_set_option: unknown option '%s'", name);
-  return VC_OK;
+  for (const auto& o : OPTIONS) {
+    if (strcmp(name, o.name)) continue;
+    switch (o.clamp) {
+      case BOOL: value = value != 0; break;
+      case AT_LEAST_0: value = value > 0 ? value : 0; break;
+      case ZERO_TO_2: value = value < 0 ? 0 : value > 2 ? 2 : value; break;
+      case ZERO_OR_H: if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H); break;
+      case ANY: break;
+    }
+    f.opt.*o.member = value;
+    return VC_OK;
+  }
+  FAIL(VC_ERR_ARG, "flux_set_option: unknown option '%s'", name);
 }
 
 int64_t vc_flux_workspace_bytes_impl(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps) {
@@ -946,13 +971,10 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   const int64_t n = (int64_t)B * f.N;
   f.state_f32 = !state_is_bf16;
   f.method = method; f.evals = E;
-  if (f.state_f32) {
-    TRY(d2d(f.XS32, x, n * f.cfg.out_channels * 4, s, e));
-    TRY(vc_euler_f32_launch(f.XS32, f.XS, nullptr, nullptr, nullptr, n * f.cfg.out_channels, s, e.buf, e.len));   // XS = bf16(XS32)
-  } else {
-    TRY(d2d(f.XS, x, n * f.cfg.out_channels * 2, s, e));
-  }
-  if (E > 1) TRY(d2d(f.YIN, f.XS, n * f.cfg.out_channels * 2, s, e));      // the first evaluation reads bf16(y0)
+  TRY(d2d(ode_state(f), x, ode_state_bytes(f), s, e));
+  // the first evaluation reads bf16(y0)
+  if (f.state_f32) TRY(ode_update(f, nullptr, nullptr, s, e));
+  else if (next_input(f) != f.XS) TRY(d2d(next_input(f), f.XS, ode_state_bytes(f), s, e));
   TRY(d2d(f.COND, cond, n * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
   HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
   f.sc_active = cached; f.sc_thr = f.sc_threshold; f.sc_lim = f.sc_max;
@@ -987,8 +1009,7 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
   if (n_steps < 0 || f.steps_done + n_steps > f.steps_total)
     FAIL(VC_ERR_ARG, "flux_sample_steps: %d more steps after %d of %d", n_steps, f.steps_done, f.steps_total);
   if (s && (!f.graph || f.key.s != s)) FAIL(VC_ERR_STATE, "flux_sample_steps: the step was captured on another stream");
-  const int64_t state_bytes = (int64_t)f.B * f.N * f.cfg.out_channels * (f.state_f32 ? 4 : 2);
-  const void* state = f.state_f32 ? (const void*)f.XS32 : (const void*)f.XS;
+  const int64_t state_bytes = ode_state_bytes(f);
   for (int i = 0; i < n_steps; ++i) {
     for (int j = 0; j < f.evals; ++j) {      // a step = `evals` replays; the stage is the device-side counter modulo evals
       if (f.sc_active) { TRY(cached_step(f, s, e)); continue; }
@@ -996,7 +1017,7 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
       else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
       ++f.sc_computed;
     }
-    if (trajectory) TRY(d2d((char*)trajectory + (int64_t)i * state_bytes, state, state_bytes, s, e));
+    if (trajectory) TRY(d2d((char*)trajectory + (int64_t)i * state_bytes, ode_state(f), state_bytes, s, e));
     ++f.steps_done;
   }
   return VC_OK;
@@ -1006,8 +1027,7 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
   H(handle);
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_sample_end: no sample in flight");
   if (!x_out) FAIL(VC_ERR_ARG, "flux_sample_end: null output");
-  if (f.state_f32) return d2d(x_out, f.XS32, (int64_t)f.B * f.N * f.cfg.out_channels * 4, s, e);
-  return d2d(x_out, f.XS, (int64_t)f.B * f.N * f.cfg.out_channels * 2, s, e);
+  return d2d(x_out, ode_state(f), ode_state_bytes(f), s, e);
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {

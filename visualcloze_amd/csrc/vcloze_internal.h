@@ -54,9 +54,11 @@ int vc_concat_cols_launch(const void* x, int cx, const void* cond, int cc, void*
 int vc_euler_launch(void* x, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_euler_f32_launch(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s,
                         char* err, int errlen);
-inline int vc_evals_of(int method) {   // model evaluations per solver step; 0 = not a VC_SOLVER_*
+__host__ __device__ inline int vc_evals_of(int method) {   // model evaluations per solver step; 0 = not a VC_SOLVER_*
   return method == VC_SOLVER_EULER ? 1 : method == VC_SOLVER_MIDPOINT ? 2 : method == VC_SOLVER_RK4 ? 4 : 0;
 }
+int vc_ode_update_launch(const char* what, int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in,
+                         const float* dts, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen);

@@ -6,6 +6,7 @@ in Python over the op-level ABI; it stays for the un-merged LoRA parity mode and
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -117,7 +118,6 @@ class FluxHandle:
 
     def set_options(self, attn_variant=None, tile_cfg=0, fuse_qnorm=2, fuse_vt=True, qkv_heads=None, fuse_knorm=False,
                     logit_bound=0.0, mlp_first=False, splitk=True) -> None:
-        import math
         wq = int(getattr(self.W, "qkv_heads", 0) or 0)
         if qkv_heads is None:
             qkv_heads = wq
@@ -204,13 +204,6 @@ class FluxHandle:
                                              stream if stream is not None else hip.cur_stream()), "vc_flux_forward")
 
     @staticmethod
-    def _state(x, state_is_bf16, what):
-        import torch
-        want = torch.bfloat16 if state_is_bf16 else torch.float32     # the ABI takes the state in the caller's dtype
-        if x.dtype != want:
-            raise hip.VclozeHipError(f"{what}: state_is_bf16={bool(state_is_bf16)} needs a {want} state tensor, got {x.dtype}")
-
-    @staticmethod
     def _method(method) -> int:
         if isinstance(method, str):
             if method not in hip.SOLVERS:
@@ -218,13 +211,21 @@ class FluxHandle:
             return hip.SOLVERS[method]
         return int(method)
 
-    def sample_begin(self, x, cond, t_grid, state_is_bf16: bool, stream, method="euler") -> None:
-        self._state(x, state_is_bf16, "vc_flux_sample_begin"); hip._bf16(cond, "cond")
-        if not (x.is_contiguous() and cond.is_contiguous()):
-            raise hip.VclozeHipError("vc_flux_sample: contiguous x / cond expected")
+    def _sample_args(self, what, method, x, cond, t_grid, state_is_bf16, trajectory=None) -> tuple:
+        """the checked leading arguments of vc_flux_sample_begin_ode / vc_flux_sample_ode"""
+        want = torch.bfloat16 if state_is_bf16 else torch.float32     # the ABI takes the state in the caller's dtype
+        for t, name in ((x, "state"), (trajectory, "trajectory")):
+            if t is not None and t.dtype != want:
+                raise hip.VclozeHipError(f"{what}: state_is_bf16={bool(state_is_bf16)} needs a {want} {name} tensor, got {t.dtype}")
+        hip._bf16(cond, "cond")
+        if not all(t.is_contiguous() for t in (x, cond, trajectory) if t is not None):
+            raise hip.VclozeHipError(f"{what}: contiguous x / cond / trajectory expected")
         t = _f32(t_grid).reshape(-1)
-        hip._check(hip.lib().vc_flux_sample_begin_ode(self.h, self._method(method), x.data_ptr(), cond.data_ptr(), _fp(t), t.size,
-                                                      int(bool(state_is_bf16)), stream), "vc_flux_sample_begin_ode")
+        return self.h, self._method(method), x.data_ptr(), cond.data_ptr(), _fp(t), t.size, int(bool(state_is_bf16))
+
+    def sample_begin(self, x, cond, t_grid, state_is_bf16: bool, stream, method="euler") -> None:
+        args = self._sample_args("vc_flux_sample_begin_ode", method, x, cond, t_grid, state_is_bf16)
+        hip._check(hip.lib().vc_flux_sample_begin_ode(*args, stream), "vc_flux_sample_begin_ode")
 
     def sample_steps(self, n: int, stream, trajectory=None) -> None:
         hip._check(hip.lib().vc_flux_sample_steps(self.h, n, hip._p(trajectory), stream), "vc_flux_sample_steps")
@@ -232,7 +233,6 @@ class FluxHandle:
     def profile(self, evaluations: int, stream) -> list:
         """vc_flux_profile: HIP-event times of the launches of `evaluations` evaluations at the current step of the sample in
         flight, class by class - a list of dicts (kind, epi, n, k, launches, flops, bytes, total_us, min_us, max_us)."""
-        import ctypes as C
         cap = 32
         out = (hip.FluxLaunchClass * cap)()
         n = C.c_int32(0)
@@ -243,25 +243,12 @@ class FluxHandle:
         hip._check(hip.lib().vc_flux_sample_end(self.h, x_out.data_ptr(), stream), "vc_flux_sample_end")
 
     def sample_ode(self, method, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
-        """vc_flux_sample_ode: as sample_euler with method "euler" | "midpoint" | "rk4" (or a VC_SOLVER_* code); the prepared
-        max_steps must hold (len(t_grid) - 1) * hip.solver_evals(method) evaluations; trajectory[i] = the state after STEP i"""
-        self._state(x, state_is_bf16, "vc_flux_sample_ode"); hip._bf16(cond, "cond")
-        if trajectory is not None:
-            self._state(trajectory, state_is_bf16, "vc_flux_sample_ode (trajectory)")
-        if not (x.is_contiguous() and cond.is_contiguous()) or (trajectory is not None and not trajectory.is_contiguous()):
-            raise hip.VclozeHipError("vc_flux_sample_ode: contiguous x / cond / trajectory expected")
-        t = _f32(t_grid).reshape(-1)
-        hip._check(hip.lib().vc_flux_sample_ode(self.h, self._method(method), x.data_ptr(), cond.data_ptr(), _fp(t), t.size,
-                                                int(bool(state_is_bf16)), hip._p(trajectory), stream), "vc_flux_sample_ode")
+        """vc_flux_sample_ode with method "euler" | "midpoint" | "rk4" (or a VC_SOLVER_* code).  x [B,N,C] in place (bf16, or f32
+        with state_is_bf16 False): x(t_grid[0]) -> x(t_grid[-1]); the prepared max_steps must hold (len(t_grid) - 1) *
+        hip.solver_evals(method) evaluations; trajectory: optional [S,B,N,C] buffer of the state's dtype, trajectory[i] = the state
+        after STEP i"""
+        args = self._sample_args("vc_flux_sample_ode", method, x, cond, t_grid, state_is_bf16, trajectory)
+        hip._check(hip.lib().vc_flux_sample_ode(*args, hip._p(trajectory), stream), "vc_flux_sample_ode")
 
     def sample_euler(self, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
-        """x [B,N,C] in place (bf16, or f32 with state_is_bf16 False): x(t_grid[0]) -> x(t_grid[-1]); trajectory: optional
-        [S,B,N,C] buffer of the state's dtype"""
-        self._state(x, state_is_bf16, "vc_flux_sample_euler"); hip._bf16(cond, "cond")
-        if trajectory is not None:
-            self._state(trajectory, state_is_bf16, "vc_flux_sample_euler (trajectory)")
-        if not (x.is_contiguous() and cond.is_contiguous()) or (trajectory is not None and not trajectory.is_contiguous()):
-            raise hip.VclozeHipError("vc_flux_sample_euler: contiguous x / cond / trajectory expected")
-        t = _f32(t_grid).reshape(-1)
-        hip._check(hip.lib().vc_flux_sample_euler(self.h, x.data_ptr(), cond.data_ptr(), _fp(t), t.size, int(bool(state_is_bf16)),
-                                                  hip._p(trajectory), stream), "vc_flux_sample_euler")
+        self.sample_ode("euler", x, cond, t_grid, state_is_bf16, stream, trajectory)

@@ -489,8 +489,10 @@ class Flux(nn.Module):
         if self._handle is None or self._handle.W is not eng.W:
             from .handle import FluxHandle
             self._handle = FluxHandle(self.params, eng.W, eng.dev)
-        self._handle.set_options(eng.attn_variant, eng.tile_cfg, eng.fuse_qnorm, eng.fuse_vt, eng.W.qkv_heads, eng.fuse_knorm,
-                                 eng.W.logit_bound if eng.bounded_softmax else 0.0, eng.mlp_first, eng.splitk)
+        self._handle.set_options(attn_variant=eng.attn_variant, tile_cfg=eng.tile_cfg, fuse_qnorm=eng.fuse_qnorm, fuse_vt=eng.fuse_vt,
+                                 qkv_heads=eng.W.qkv_heads, fuse_knorm=eng.fuse_knorm,
+                                 logit_bound=eng.W.logit_bound if eng.bounded_softmax else 0.0, mlp_first=eng.mlp_first,
+                                 splitk=eng.splitk)
         return self._handle
 
     # ------------------------------------------------------------------ the B1 boundary
