@@ -228,6 +228,18 @@ typedef struct VcAttention {
 } VcAttention;
 int vc_attention(const VcAttention* a, void* stream);
 int64_t vc_attention_scratch_bytes(void);
+/* The plan vc_attention would execute for these arguments on a device of n_cu compute units (n_cu <= 0: the current device's;
+ * 256 without a device), without launching anything and without touching a pointer (works without a GPU; detect by SYMBOL,
+ * VC_ABI_VERSION did not change).  The argument errors of vc_attention are returned the same way.
+ * out[0] = the variant the host engines choose by size for (B, L, H, n_cu), whatever a->variant says (28, 8 or 3);
+ * out[1] = kernel family: 0 = 8 waves x 32 queries, 1 = 4 waves x 32 queries, 2 = 64 queries per wave with one launch slot per
+ * item, 3 = its stream form; out[2] = 1: the template without a running max (logit_bound); out[3], out[4], out[5] = grid,
+ * threads and dynamic LDS bytes of the attention kernel; out[6] = query blocks per (sample, head); out[7] = work items;
+ * out[8] = full rounds in front of the tail split (-1 = no split), out[9] = tail items, out[10] = their (item, KV tile) units;
+ * out[11] = 1: pieces combined inside the launch (bit 16 honoured); out[12] = grid of the merge kernel (0 = none runs);
+ * out[13] = byte offset of the flag words in a vc_attention_scratch_bytes() buffer at n_cu; out[14] = the scratch bytes the
+ * split was granted on (0 = the call touches no scratch); out[15] = 0. */
+int vc_attention_plan(const VcAttention* a, int32_t n_cu, int32_t out[16]);
 
 /* timestep_embedding (layers.py:28-49): out[b, 0:half]=cos(1000*t*f), [half:]=sin, f host table. */
 int vc_timestep_embedding(const float* t, const float* freqs, void* out_bf16, int32_t n, int32_t half,

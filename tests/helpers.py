@@ -97,3 +97,45 @@ def gemm_plan_answer(lib, a, tile_cfg):
     out = (C.c_int32 * 8)()
     rc = lib.vc_gemm_plan(C.byref(a), tile_cfg, out)
     return list(out) if rc == 0 else [rc, lib.vc_last_error().decode()]
+
+
+def attn_scratch_states(n_cu: int):
+    """the attention scratch on offer, by state index of tests/golden/attn_plans.json.gz: none / one byte short of the 64-query
+    partials / exactly those / the whole buffer minus one byte / the whole buffer / a whole buffer's size behind a null pointer.
+    The sizes are written out here (not asked of the library): 2 pieces per CU of 68 KiB (attention64) or 4 of 66 KiB (attention),
+    the larger rounded up to 256, then 16 bytes of flag words per CU rounded up to 256."""
+    p64, p32 = n_cu * 2 * (65536 + 4096), n_cu * 4 * (16384 + 512) * 4
+    whole = (max(p64, p32) + 255) // 256 * 256 + (n_cu * 16 + 255) // 256 * 256
+    return [(0, 0), (0x1000, p64 - 1), (0x1000, p64), (0x1000, whole - 1), (0x1000, whole), (0, whole)]
+
+
+def attn_plan_case(group: dict, case: list):
+    """One case of tests/golden/attn_plans.json.gz -> (hip.Attention, n_cu, expected).  group = {"B", "L", "H", "n_cu", "o": {Attention
+    field: value}?}; case = [variant, mask, scratch state, query form, logit_bound, expected].  mask: bit 0 = kv_len, bit 1 = kv_gap;
+    query form: bit 0 = q_scale, bit 1 = q_scale2 (with split = L // 2), bit 2 = rope, bit 3 = q_prescaled.  Fields the group does not
+    name: every pointer 0x1000 (the planner never dereferences one), ld = 3 * 128 H, ldo = 128 H, sample strides L * ld and L * ldo,
+    Lpad = L rounded up to 64."""
+    from visualcloze_amd import hip
+    variant, mask, scratch, qform, bound, expected = case
+    B, L, H, n_cu = group["B"], group["L"], group["H"], group["n_cu"]
+    a = hip.Attention()
+    a.qkv = a.vt = a.out = 0x1000
+    a.B, a.L, a.H, a.Lpad, a.variant = B, L, H, (L + 63) // 64 * 64, variant
+    a.ld, a.ldo = 3 * 128 * H, 128 * H
+    a.bstride, a.out_bstride = L * a.ld, L * a.ldo
+    a.kv_len, a.kv_gap = 0x1000 if mask & 1 else 0, 0x1000 if mask & 2 else 0
+    a.scratch, a.scratch_bytes = attn_scratch_states(n_cu)[scratch]
+    a.q_scale, a.q_scale2, a.rope = 0x1000 if qform & 1 else 0, 0x1000 if qform & 2 else 0, 0x1000 if qform & 4 else 0
+    a.split, a.rope_bstride, a.q_prescaled = L // 2 if qform & 2 else 0, L * 128 if qform & 4 else 0, 1 if qform & 8 else 0
+    a.logit_bound = bound
+    for k, v in group.get("o", {}).items():
+        setattr(a, k, v)
+    return a, n_cu, expected
+
+
+def attn_plan_answer(lib, a, n_cu):
+    """what vc_attention_plan answers: the sixteen integers, or [return code, error text]"""
+    import ctypes as C
+    out = (C.c_int32 * 16)()
+    rc = lib.vc_attention_plan(C.byref(a), n_cu, out)
+    return list(out) if rc == 0 else [rc, lib.vc_last_error().decode()]

@@ -276,6 +276,76 @@ def test_gemm_plans_match_the_recorded_table():
     assert not wrong, f"{len(wrong)} of {n} plans differ from the table; the first: {wrong[:5]}"
 
 
+def test_attention_plans_match_the_recorded_table():
+    """tests/golden/attn_plans.json.gz holds what the attention launch functions decided at the commit its header names (the one
+    before csrc/attn_plan.hip existed, read out through a recording shim), over a sweep of geometries, CU counts, variant words,
+    masks, scratch states, query forms, logit bounds and strides (tests/golden/make_attn_plans.py): vc_attention_plan reproduces
+    every record - the sixteen integers, or the return code and the whole error text - exactly."""
+    import gzip
+    import json
+    from tests.helpers import attn_plan_answer, attn_plan_case
+    from visualcloze_amd import hip
+    L = hip.lib()
+    with gzip.open(os.path.join(REPO, "tests", "golden", "attn_plans.json.gz"), "rt") as f:
+        table = json.load(f)
+    n, wrong, families, splits_at_odd_cus = 0, [], set(), 0
+    for g in table["groups"]:
+        for case in g["cases"]:
+            a, n_cu, expected = attn_plan_case(g, case)
+            got = attn_plan_answer(L, a, n_cu)
+            n += 1
+            if got != expected:
+                wrong.append(({k: v for k, v in g.items() if k != "cases"}, case, got))
+            if len(expected) == 16:
+                families.add((expected[1], expected[2], expected[8] >= 0, expected[11]))
+                splits_at_odd_cus += expected[1] >= 2 and n_cu % 8 != 0 and expected[8] >= 0
+    assert n == table["header"]["cases"] and n >= 10000 and "recording shim" in table["header"]["recorded_by"]
+    assert not wrong, f"{len(wrong)} of {n} plans differ from the table; the first: {wrong[:5]}"
+    # the table reaches every kernel family and template, with and without a split, and the in-launch combine; a CU count that is
+    # no multiple of 8 never splits the 64-query kernel
+    assert {(f, b, s, 0) for f in (2, 3) for b in (0, 1) for s in (False, True)} | {(0, 0, False, 0), (1, 0, False, 0), (1, 0, True, 0),
+                                                                                   (3, 0, True, 1), (3, 1, True, 1)} == families
+    assert splits_at_odd_cus == 0
+
+
+def test_attention_plans_for_the_flux_geometries():
+    """vc_attention_plan at the BASELINE geometries (H = 24, 256 CUs), worked out by hand from the launch rules: out = [by-size variant,
+    family (0 / 1: 8 / 4 waves x 32 queries, 2 / 3: 64 queries per wave, per item / stream), bounded, grid, threads, LDS bytes, query
+    blocks, items, full rounds (-1: no split), tail items, tail units, in-launch combine, merge grid, flag offset, scratch bytes, 0]."""
+    from tests.helpers import attn_plan_answer, attn_plan_case
+    from visualcloze_amd import hip
+    lib = hip.lib()
+    QPRE, PART64, WHOLE = 8, 2, 4                   # query form / scratch states of tests/helpers.py:attn_plan_case
+    FLAGS, ALL, P64 = 256 * 270336, 256 * 270336 + 4096, 256 * 139264
+
+    def plan(L, variant, B=1, n_cu=256, scratch=WHOLE, qform=QPRE, bound=16.65, mask=0):
+        a, n_cu, _ = attn_plan_case({"B": B, "L": L, "H": 24, "n_cu": n_cu}, [variant, mask, scratch, qform if variant & 8 else 0, bound, None])
+        return attn_plan_answer(lib, a, n_cu)
+    # cfg 2 (L = 3968): 16 x 24 = 384 items of 256 queries >= 256 CUs -> 28; 48 items per XCD on 32 workgroups = 1 round + 16 tail items,
+    # cut into ceil(16 * 62 / 32) = 31 tiles per workgroup (+ 4 < 62): stream form, bounded, pieces combined in the launch
+    assert plan(3968, 28) == [28, 3, 1, 256, 256, 98304, 16, 384, 1, 128, 128 * 62, 1, 0, FLAGS, ALL, 0]
+    # the same without bit 16, on a scratch of the partials alone: a merge kernel of 16 blocks per tail slot; with raw queries: per item
+    assert plan(3968, 12, scratch=PART64) == [28, 3, 1, 256, 256, 98304, 16, 384, 1, 128, 128 * 62, 0, 256, FLAGS, P64, 0]
+    assert plan(3968, 28, qform=0, bound=0.0) == [28, 2, 0, 256, 256, 98304, 16, 384, 1, 128, 128 * 62, 0, 256, FLAGS, P64, 0]
+    # a scratch one byte short, or ragged samples: no split (one launch of min(items, CUs) workgroups)
+    assert plan(3968, 28, scratch=1)[8:13] == [-1, 0, 0, 0, 0] and plan(3968, 28, mask=1)[8:13] == [-1, 0, 0, 0, 0]
+    # cfg 1 (L = 1664): 7 x 24 = 168 items, under 256 but over 128 -> 8: one item per workgroup, nothing to split
+    assert plan(1664, 8) == [8, 3, 1, 168, 256, 98304, 7, 168, -1, 0, 0, 0, 0, FLAGS, 0, 0]
+    # cfg 3 (L = 6656: 624 items = 2 rounds + 14 per XCD) and cfg 5 (L = 7424: 696 items = 2 rounds + 23 per XCD)
+    assert plan(6656, 28) == [28, 3, 1, 256, 256, 98304, 26, 624, 2, 112, 112 * 104, 1, 0, FLAGS, ALL, 0]
+    assert plan(7424, 28) == [28, 3, 1, 256, 256, 98304, 29, 696, 2, 184, 184 * 116, 1, 0, FLAGS, ALL, 0]
+    # 7 CUs: a grid that is no multiple of 8 has no per-XCD schedule -> never split
+    assert plan(3968, 28, n_cu=7) == [28, 3, 1, 7, 256, 98304, 16, 384, -1, 0, 0, 0, 0, 7 * 270336, 0, 0]
+    # the 32-queries-per-wave family at cfg 2: 8 waves (0: one workgroup per item; 2: one per CU), 4 waves with the tail split
+    # (7: 744 items on 512 slots = 1 round + 232 items cut into ceil(232 * 62 / 512) = 29 tiles per block, one merge block per item)
+    assert plan(3968, 0) == [28, 0, 0, 384, 512, 65536, 16, 384, -1, 0, 0, 0, 0, FLAGS, 0, 0] and plan(3968, 2)[3] == 256
+    assert plan(3968, 7) == [28, 1, 0, 512, 256, 65536, 31, 744, 1, 232, 232 * 62, 0, 232, FLAGS, ALL, 0]
+    # a small geometry (L = 333: 48 items, under half the CUs) -> 3: 72 items of 128 queries, one workgroup each
+    assert plan(333, 3) == [3, 1, 0, 72, 256, 65536, 3, 72, -1, 0, 0, 0, 0, FLAGS, 0, 0]
+    # +4 without 1 and 2 is an error in the 32-query family only
+    assert plan(3968, 5) == [-1, "attention: the tail split (+4) exists for variant 3 only"] and len(plan(3968, 12)) == 16
+
+
 def test_procedural_torch_equals_numpy():
     """tests/procedural.py: the torch evaluation of the closed-form weights (what the GPU tests use at full width) is
     bit-identical to the numpy one (what the golden generators use), chunk boundary included."""

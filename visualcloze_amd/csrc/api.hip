@@ -65,7 +65,11 @@ int vc_attention(const VcAttention* a, void* stream) {
   if (!a) { snprintf(g_err, sizeof(g_err), "attention: null args"); return VC_ERR_ARG; }
   return vc_attention_launch(*a, S(stream), ERRBUF);
 }
-int64_t vc_attention_scratch_bytes(void) { return vc_attention_scratch_bytes_impl(); }
+int vc_attention_plan(const VcAttention* a, int32_t n_cu, int32_t out[16]) {
+  if (!a || !out) { snprintf(g_err, sizeof(g_err), "attention_plan: null argument"); return VC_ERR_ARG; }
+  return vcplan::attention_plan_words(*a, n_cu > 0 ? n_cu : vc_cu_count(), out, ERRBUF);
+}
+int64_t vc_attention_scratch_bytes(void) { return vcplan::attention_scratch_bytes(vc_cu_count()); }
 int vc_timestep_embedding(const float* t, const float* freqs, void* out_bf16, int32_t n, int32_t half,
                           int32_t round_t_bf16, void* stream) {
   return vc_temb_launch(t, freqs, out_bf16, n, half, round_t_bf16, S(stream), ERRBUF);

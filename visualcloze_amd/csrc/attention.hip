@@ -15,9 +15,10 @@
 // registers of a lane line up with 8 CONTIGUOUS keys per 16-key step -> P feeds PV with no cross-lane moves.
 // LDS images are lane-linear (DMA) with XOR slot swizzles applied on the source address and on the
 // ds_read_b128 address (K: slot ^= row&15 on 256-B rows; Vt: slot ^= (row>>1)&7 on 128-B rows).
-#include <algorithm>
 #include "common.h"
 #include "vcloze_internal.h"
+
+using namespace vcplan;      // the tile / partial-result constants (attn_plan.h) and the launch plan
 
 namespace {
 
@@ -37,16 +38,9 @@ struct AttnArgs {
   uint64_t* debug_ts;   // profiling builds only (-DVC_ATTN_TIMESTAMPS)
 };
 
-// one partial result: [wave 4][16 groups][lane 64][4] f32 accumulator fragments in register order, then [wave 4][lane 64]
-// (m, l) pairs; every store / load is 16 B (8 B) per lane, lane-contiguous
-constexpr int PART_O = 4 * 16 * 64 * 4;          // floats
-constexpr int PART_FLOATS = PART_O + 4 * 64 * 2;
 VC_DEV int chunk_begin(int c, int units, int chunks) { return (int)(((long)c * units) / chunks); }
 
-constexpr int KVB = 64;               // keys per tile
-constexpr int K_TILE = KVB * 256;     // bytes
-constexpr int V_TILE = 128 * KVB * 2; // bytes
-constexpr int STAGE = K_TILE + V_TILE;
+constexpr int STAGE = K_TILE + V_TILE;      // one buffer of the LDS ring (LDS32 = two)
 
 VC_DEV int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
@@ -384,74 +378,33 @@ static uint64_t* g_attn_debug_ts = nullptr;
 extern "C" void vc_debug_set_attn_ts(void* p) { g_attn_debug_ts = (uint64_t*)p; }
 #endif
 
-static int attn_cu_count() { return vc_cu_count(); }
-
-// [partials of whichever variant runs: the larger of the two layouts][flag words of attention64's in-launch combine, zero between
-// launches (VcAttention.variant bit 16): behind everything any other variant writes]
-int64_t vc_attention_flags_offset_impl() {
-  const int64_t parts = std::max((int64_t)2 * attn_cu_count() * 2 * PART_FLOATS * (int64_t)sizeof(float), vc_attention64_scratch_bytes_impl(attn_cu_count()));
-  return (parts + 255) & ~(int64_t)255;
-}
-int64_t vc_attention_scratch_bytes_impl() {
-  return vc_attention_flags_offset_impl() + ((vc_attention64_flags_bytes_impl(attn_cu_count()) + 255) & ~(int64_t)255);
-}
-
+// validate, plan (attn_plan.hip decides everything), then one launch per kernel family
 int vc_attention_launch(const VcAttention& A, hipStream_t s, char* err, int errlen) {
-  const void* qkv = A.qkv; const void* vt = A.vt; void* out = A.out; const int32_t* kv_len = A.kv_len;
-  const int64_t ld = A.ld, bstride = A.bstride, ldo = A.ldo, out_bstride = A.out_bstride;
-  const int32_t B = A.B, L = A.L, Lpad = A.Lpad, H = A.H;
-  int32_t variant = A.variant;
-  void* scratch = A.scratch; const int64_t scratch_bytes = A.scratch_bytes;
-  if (!qkv || !vt || !out) { snprintf(err, errlen, "attention: null pointer"); return VC_ERR_ARG; }
-  if (B <= 0 || L <= 0 || H <= 0) { snprintf(err, errlen, "attention: empty problem B=%d L=%d H=%d", B, L, H); return VC_ERR_ARG; }
-  if (Lpad < L || Lpad % KVB) { snprintf(err, errlen, "attention: Lpad=%d must be a multiple of %d and >= L=%d", Lpad, KVB, L); return VC_ERR_ARG; }
-  if (ld % 8 || ldo % 4 || bstride % 8) { snprintf(err, errlen, "attention: strides must keep 16-B row alignment"); return VC_ERR_ARG; }
-  if ((uint64_t)128 * (uint64_t)Lpad >= (1ull << 31)) { snprintf(err, errlen, "attention: Lpad too large"); return VC_ERR_ARG; }
-  if ((uint64_t)(Lpad + KVB) * (uint64_t)ld * 2ull >= (1ull << 32)) { snprintf(err, errlen, "attention: one sample's K rows exceed 32-bit byte offsets (L=%d ld=%ld)", L, (long)ld); return VC_ERR_ARG; }
-  if (A.q_scale && !(variant & 8)) { snprintf(err, errlen, "attention: in-kernel QKNorm + RoPE of the queries (q_scale) exists for variants 8 / 12 only"); return VC_ERR_ARG; }
-  if (A.kv_gap && !kv_len) { snprintf(err, errlen, "attention: kv_gap needs kv_len"); return VC_ERR_ARG; }
-  if (A.q_scale && !A.rope) { snprintf(err, errlen, "attention: q_scale given without a rope table"); return VC_ERR_ARG; }
-  if (A.q_prescaled && (!(variant & 8) || A.q_scale)) { snprintf(err, errlen, "attention: q_prescaled exists for variants 8 / 12 and excludes q_scale"); return VC_ERR_ARG; }
+  const int rc = validate_attention(A, err, errlen);
+  if (rc != VC_OK) return rc;
+  const AttnPlan pl = plan_attention(A, vc_cu_count());
+  if (pl.family == ATTN_64Q_ITEM || pl.family == ATTN_64Q_STREAM) return vc_attention64_launch(A, pl, g_attn_debug_ts, s, err, errlen);
   AttnArgs a;
-  a.qkv = (const bf16_t*)qkv; a.vt = (const bf16_t*)vt; a.out = (bf16_t*)out; a.kv_len = kv_len;
-  a.kv_gap = kv_len ? A.kv_gap : nullptr;
-  a.ld = ld; a.bstride = bstride; a.ldo = ldo; a.out_bstride = out_bstride;
-  a.B = B; a.L = L; a.Lpad = Lpad; a.H = H;
-  if (variant & 8)    // one wave per SIMD, 64 queries per wave (attention64.hip); +4 = tail split
-    return vc_attention64_launch(A, (variant & 4) != 0, attn_cu_count(), g_attn_debug_ts, s, err, errlen);
+  a.qkv = (const bf16_t*)A.qkv; a.vt = (const bf16_t*)A.vt; a.out = (bf16_t*)A.out; a.kv_len = A.kv_len;
+  a.kv_gap = A.kv_len ? A.kv_gap : nullptr;
+  a.ld = A.ld; a.bstride = A.bstride; a.ldo = A.ldo; a.out_bstride = A.out_bstride;
+  a.B = A.B; a.L = A.L; a.Lpad = A.Lpad; a.H = A.H; a.qblocks = pl.qblocks; a.items = pl.items;
+  a.full_rounds = pl.full_rounds; a.tail_items = pl.tail_items; a.tail_units = pl.tail_units; a.part = (float*)A.scratch;
   a.debug_ts = g_attn_debug_ts;
-  a.full_rounds = -1; a.tail_items = 0; a.tail_units = 0; a.part = (float*)scratch;
-  const int lds = 2 * STAGE;
   hipError_t e;
-  const bool persist = (variant & 2) != 0;   // +2: persistent grid with static item assignment (variants 2, 3)
-  const bool tail_split = (variant & 4) != 0; // +4 (with 1 and 2 = variant 7): tail items cut along the keys
-  if (tail_split && (variant & 3) != 3) { snprintf(err, errlen, "attention: the tail split (+4) exists for variant 3 only"); return VC_ERR_ARG; }
-  variant &= 1;
-  const int n_cu = attn_cu_count();
-  if (variant == 1) {  // 4 waves x 32 queries
-    a.qblocks = (L + 127) / 128;
-    static VcOncePerDevice done;
-    if (done.need()) { e = hipFuncSetAttribute((const void*)attn_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) goto fail; done.mark(); }
-    a.items = a.qblocks * H * B;
-    const int G = 2 * n_cu;
-    const int nkt = (L + KVB - 1) / KVB;
-    const int rounds = a.items / G, tail = a.items - rounds * G;
-    // cut the tail only where it shortens the critical path by more than the merge costs (~3 tiles): plain = one more
-    // round of nkt tiles for the blocks that draw a tail item, split = ceil(tail * nkt / G) tiles for every block
-    const int split_tiles = (int)(((long)tail * nkt + G - 1) / G);
-    if (tail_split && !kv_len && tail > 0 && scratch && scratch_bytes >= vc_attention_scratch_bytes_impl() && split_tiles + 3 < nkt) {
-      a.full_rounds = rounds; a.tail_items = tail; a.tail_units = tail * nkt;
-      hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(G), dim3(256), lds, s, a);
-      hipLaunchKernelGGL(attn_merge_kernel, dim3(tail), dim3(256), 0, s, a, G);
-    } else {
-      hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(std::min(a.items, persist ? G : a.items)), dim3(256), lds, s, a);
+  switch (pl.family) {
+    case ATTN_32Q_4W: {
+      static VcOncePerDevice done;
+      if (done.need()) { e = hipFuncSetAttribute((const void*)attn_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds); if (e != hipSuccess) goto fail; done.mark(); }
+      hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(pl.grid), dim3(pl.threads), pl.lds, s, a);
+      if (pl.merge_grid) hipLaunchKernelGGL(attn_merge_kernel, dim3(pl.merge_grid), dim3(256), 0, s, a, pl.grid);
+      break;
     }
-  } else {  // 8 waves x 32 queries
-    a.qblocks = (L + 255) / 256;
-    static VcOncePerDevice done8;
-    if (done8.need()) { e = hipFuncSetAttribute((const void*)attn_fwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) goto fail; done8.mark(); }
-    a.items = a.qblocks * H * B;
-    hipLaunchKernelGGL(attn_fwd_kernel<8>, dim3(std::min(a.items, persist ? n_cu : a.items)), dim3(512), lds, s, a);
+    default: {      // ATTN_32Q_8W
+      static VcOncePerDevice done8;
+      if (done8.need()) { e = hipFuncSetAttribute((const void*)attn_fwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds); if (e != hipSuccess) goto fail; done8.mark(); }
+      hipLaunchKernelGGL(attn_fwd_kernel<8>, dim3(pl.grid), dim3(pl.threads), pl.lds, s, a);
+    }
   }
   e = hipGetLastError();
   if (e == hipSuccess) return VC_OK;

@@ -40,11 +40,12 @@
 // V^T(t+2) and K(t+4) and waits with a COUNTED vmcnt(8), so every piece has a full tile of flight time.
 //
 // Audit after every change (Makefile target `audit64`): no spills, no scratch, no compiler-generated v_accvgpr_*.
-#include <algorithm>
 #include <type_traits>
 #include "common.h"
 #include "vcloze_internal.h"
 #include "attention64_sched8.h"      // a ring of eight V^T fragment registers (two 16-key steps)
+
+using namespace vcplan;      // the tile / partial-result constants, Sched64 (attn_plan.h) and the launch plan
 
 namespace {
 
@@ -72,22 +73,10 @@ struct Attn64Args {
 // in f32 (|x| <= 100: 2^100 * L fits), the result O / l is the same function.  Masked keys still take the extra k-step,
 // in the tiles that hold any.
 
-constexpr int KVB = 64;
-constexpr int K_TILE = KVB * 256, V_TILE = 128 * KVB * 2;
-constexpr int RING = 3;
-constexpr int V_RING0 = RING * K_TILE;              // 48 KB of K ring, then 48 KB of V^T ring
-constexpr int LDS64 = RING * (K_TILE + V_TILE);     // 96 KB
-constexpr int QW = 64;                              // queries per wave
-constexpr int QB = 4 * QW;                          // queries per work item
+constexpr int V_RING0 = RING * K_TILE;              // 48 KB of K ring, then 48 KB of V^T ring (LDS64 = 96 KB)
 
 constexpr int A_O = 0, A_Q = 128, A_K = 192;        // AGPR map
 
-// one partial result of the tail split: O^T fragments NORMALISED by the piece's own row sums, as f16 (11-bit mantissa:
-// 8x finer than the bf16 output; values are convex combinations of V) [wave 4][qb 2][16 groups][lane 64][4 x f16],
-// then [wave 4][qb 2][lane 64] (m, l) in f32.  Half the bytes of f32 accumulators: the pieces are written once and read
-// once through the Infinity Cache, 17 MB each way at cfg 2.
-constexpr int PART64_O_BYTES = 4 * 2 * 16 * 64 * 8;
-constexpr int PART64_BYTES = PART64_O_BYTES + 4 * 2 * 64 * 8;
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 VC_DEV int chunk_begin64(int c, int units, int chunks) { return (int)(((long)c * units) / chunks); }
 // one piece folded into the running combination of a tail item: acc = acc * keep + w * O_p with w = l_p 2^(m_p - m), keep =
@@ -103,28 +92,6 @@ VC_DEV void merge_fold64(float (&acc)[16][4], float& wsum, float& m, const f16x4
   for (int i = 0; i < 16; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[i][e] = __builtin_fmaf(w, (float)v[i][e], acc[i][e] * keep);
-}
-
-// Work schedule of the persistent grid, PER XCD (grid % 8 == 0; block b runs on XCD b % 8 - observed placement, used for
-// speed only).  XCD x owns the contiguous logical items [start, start + n) that xcd_remap gives it: all query blocks of a
-// head are neighbours there, so the K / V^T tiles of a head stream through ONE L2.  Its W = grid / 8 workgroups take
-// `rounds` whole items each (item start + r * W + slot); the remaining `tail` items are cut along the keys into W equal
-// chunks of (item, KV tile) units - inside the SAME XCD, so that the tail round re-reads K / V^T from the L2 that already
-// holds them (round 2 cut the tail across the whole grid: every XCD streamed every tail head, 204 MB fetched per launch
-// for 73 MB of operands).
-struct Sched64 {
-  int W, start, n, rounds, tail, units;
-};
-VC_DEV Sched64 sched64(int x, int G, int items, int nkt) {
-  Sched64 s;
-  s.W = G >> 3;
-  const int q = items >> 3, r = items & 7;
-  s.n = q + (x < r ? 1 : 0);
-  s.start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  s.rounds = s.n / s.W;
-  s.tail = s.n - s.rounds * s.W;
-  s.units = s.tail * nkt;
-  return s;
 }
 
 VC_DEV int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
@@ -1660,28 +1627,22 @@ __global__ __launch_bounds__(256) void attn64_merge_kernel(const Attn64Args a, i
 
 }  // namespace
 
-// the pieces (two per workgroup); the flag words of the in-launch combine (VcAttention.variant bit 16) sit at the END of the
-// whole attention scratch (vc_attention_flags_offset_impl, attention.hip), behind the partials of every other variant
-int64_t vc_attention64_scratch_bytes_impl(int n_cu) { return (int64_t)n_cu * 2 * PART64_BYTES; }
-int64_t vc_attention64_flags_bytes_impl(int n_cu) { return (int64_t)n_cu * 2 * 2 * 4; }
-
-int vc_attention64_launch(const VcAttention& A, bool tail_split, int n_cu, uint64_t* debug_ts, hipStream_t s, char* err, int errlen) {
+// one launch of the plan's kernel family and template (attn_plan.hip decided; the flag words of the in-launch combine sit at
+// the END of the whole attention scratch, behind the partials of every other variant), then the merge kernel where the plan has one
+int vc_attention64_launch(const VcAttention& A, const AttnPlan& pl, uint64_t* debug_ts, hipStream_t s, char* err, int errlen) {
   Attn64Args a;
   a.debug_ts = debug_ts;
-  const int32_t B = A.B, L = A.L, H = A.H;
-  const int32_t* kv_len = A.kv_len;
-  void* scratch = A.scratch; const int64_t scratch_bytes = A.scratch_bytes;
-  a.qkv = (const bf16_t*)A.qkv; a.vt = (const bf16_t*)A.vt; a.out = (bf16_t*)A.out; a.kv_len = kv_len;
-  a.kv_gap = kv_len ? A.kv_gap : nullptr;
+  a.qkv = (const bf16_t*)A.qkv; a.vt = (const bf16_t*)A.vt; a.out = (bf16_t*)A.out; a.kv_len = A.kv_len;
+  a.kv_gap = A.kv_len ? A.kv_gap : nullptr;
   a.ld = A.ld; a.bstride = A.bstride; a.ldo = A.ldo; a.out_bstride = A.out_bstride;
-  a.B = B; a.L = L; a.Lpad = A.Lpad; a.H = H;
+  a.B = A.B; a.L = A.L; a.Lpad = A.Lpad; a.H = A.H;
   a.q_scale = (const bf16_t*)A.q_scale; a.q_scale2 = (const bf16_t*)(A.q_scale2 ? A.q_scale2 : A.q_scale);
-  a.rope = A.rope; a.rope_bstride = A.rope_bstride; a.split = A.q_scale2 ? A.split : L;
+  a.rope = A.rope; a.rope_bstride = A.rope_bstride; a.split = A.q_scale2 ? A.split : A.L;
   a.q_pre = A.q_prescaled != 0;
-  a.inmerge = 0; a.flags = nullptr;
-  a.qblocks = (L + QB - 1) / QB;
-  a.items = a.qblocks * H * B;
-  a.full_rounds = -1; a.tail_items = 0; a.tail_units = 0; a.part = (float*)scratch;
+  a.qblocks = pl.qblocks; a.items = pl.items;
+  a.full_rounds = pl.full_rounds; a.tail_items = pl.tail_items; a.tail_units = pl.tail_units; a.part = (float*)A.scratch;
+  a.inmerge = pl.inmerge;
+  a.flags = pl.full_rounds >= 0 ? (uint32_t*)((char*)A.scratch + pl.flags_offset) : nullptr;
   static VcOncePerDevice done;
   hipError_t e;
   if (done.need()) {
@@ -1692,44 +1653,10 @@ int vc_attention64_launch(const VcAttention& A, bool tail_split, int n_cu, uint6
     if (e != hipSuccess) { snprintf(err, errlen, "attention64 attribute: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
     done.mark();
   }
-  // logits bounded by the caller (|x| <= logit_bound in the log2 domain): 2^x, a row's sum over L keys and O stay far inside
-  // f32 for bound <= 100, so the softmax needs no running max (kernel header)
-  const bool bounded = A.logit_bound > 0.0f && A.logit_bound <= 100.0f;
-  // bounded logits + prescaled queries (the product's launches wherever this kernel runs): the stream form
-  // (its LDS-DMA addresses are kernel-argument base + 32-bit byte offset)
-  const bool fits32 = ((uint64_t)B * (uint64_t)A.bstride + (uint64_t)L * (uint64_t)A.ld + 3u * (uint64_t)H * 128u) * 2u < (1ull << 32) &&
-                      (uint64_t)B * (uint64_t)H * 128u * (uint64_t)A.Lpad * 2u < (1ull << 32) && L >= 16;
-  const bool stream = a.q_pre && !A.q_scale && fits32;
-  void (*kern)(const Attn64Args) = stream ? (bounded ? attn64s_kernel<true> : attn64s_kernel<false>) : bounded ? attn64_kernel<true> : attn64_kernel<false>;
-  const int G = n_cu;
-  const int nkt = (L + KVB - 1) / KVB;
-  // the tail split is scheduled per XCD (Sched64): cut where some XCD has tail items and cutting shortens its critical
-  // path by more than the merge costs (~4 tiles): plain = one more round of nkt tiles for the workgroups that draw a tail
-  // item, split = ceil(tail * nkt / W) tiles for every workgroup of that XCD
-  int any_tail = 0, worst_split = 0;
-  if (G % 8 == 0)
-    for (int x = 0; x < 8; ++x) {
-      const int W = G / 8, q = a.items / 8, r = a.items % 8, n = q + (x < r ? 1 : 0), tail = n % W;
-      any_tail |= tail;
-      worst_split = std::max(worst_split, (int)(((long)tail * nkt + W - 1) / W));
-    }
-  if (tail_split && !kv_len && any_tail && scratch && scratch_bytes >= vc_attention64_scratch_bytes_impl(n_cu) && worst_split + 4 < nkt) {
-    const bool has_flags = scratch_bytes >= vc_attention_scratch_bytes_impl();       // the whole buffer, flag words at its end
-    a.full_rounds = a.items / G; a.tail_items = a.items - a.full_rounds * G; a.tail_units = a.tail_items * nkt;
-    // variant bit 16 (stream form only): the pieces are combined inside the launch - the caller vouches that the flag words at
-    // the end of the scratch were zero once and that nothing but these launches, one at a time, touches the scratch
-    a.inmerge = stream && (A.variant & 16) && has_flags ? 1 : 0;
-    a.flags = (uint32_t*)((char*)scratch + vc_attention_flags_offset_impl());
-    hipLaunchKernelGGL(kern, dim3(G), dim3(256), LDS64, s, a);
-    if (!a.inmerge) {
-      // XCD x has (items / 8 [+ 1]) % (G / 8) tail items: 16 blocks (8 XCDs x 2 query blocks) per tail slot that any XCD fills
-      const int W = G >> 3, qn = a.items >> 3, rn = a.items & 7;
-      const int tail_slots = std::max(rn ? (qn + 1) % W : 0, qn % W);
-      hipLaunchKernelGGL(attn64_merge_kernel, dim3(16 * tail_slots), dim3(256), 0, s, a, G);
-    }
-  } else {
-    hipLaunchKernelGGL(kern, dim3(std::min(a.items, G)), dim3(256), LDS64, s, a);
-  }
+  const bool stream = pl.family == ATTN_64Q_STREAM;
+  void (*kern)(const Attn64Args) = stream ? (pl.bounded ? attn64s_kernel<true> : attn64s_kernel<false>) : pl.bounded ? attn64_kernel<true> : attn64_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), pl.lds, s, a);
+  if (pl.merge_grid) hipLaunchKernelGGL(attn64_merge_kernel, dim3(pl.merge_grid), dim3(256), 0, s, a, pl.grid);
   e = hipGetLastError();
   if (e == hipSuccess) return VC_OK;
   snprintf(err, errlen, "attention64 launch: %s", hipGetErrorString(e));

@@ -182,7 +182,7 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
   f.XS32 = c.take<float>(B * N * out_ch);    // f32 master copy of the ODE state (state_is_bf16 == 0)
   f.KS = c.take<bf16_t>(3 * B * N * out_ch); f.YIN = c.take<bf16_t>(B * N * out_ch);   // midpoint / rk4 stages (vc_ode_stage)
   f.STEP = c.take<int32_t>(1);               f.KVLEN = c.take<int32_t>(B);  f.KVGAP = c.take<int32_t>(2 * B);
-  f.att_scratch_bytes = vc_attention_scratch_bytes_impl();
+  f.att_scratch_bytes = vcplan::attention_scratch_bytes(vc_cu_count());
   f.ATT_SCRATCH = c.take<char>(f.att_scratch_bytes);
   // one split-K scratch serves every geometry of a handle (all its launches are ordered on one stream): a caller-bound one
   // ("splitk_ws", vc_flux_bind_weight) keeps the 100 MB out of every cached workspace (advisor r04); without it, it is carved here
@@ -308,7 +308,7 @@ int resolve(Flux& f, Err e) {
 int attention_variant(const Flux& f);
 // (where the one-wave-per-SIMD attention kernel runs: small geometries keep ONE pre-pass launch for q and k - the fused
 // epilogue needs the 256x192 tile, which their short M does not fill)
-bool kn_in_gemm(const Flux& f) { return f.opt.fuse_knorm && f.opt.qkv_heads > 0 && (attention_variant(f) & 8); }
+bool kn_in_gemm(const Flux& f) { return f.opt.fuse_knorm && f.opt.qkv_heads > 0 && vcplan::decode_variant(attention_variant(f)).wave64; }
 bool qn_in_gemm(const Flux& f) { return kn_in_gemm(f) && f.opt.fuse_qnorm >= 2; }
 int qkv_epi(const Flux& f) { return f.opt.fuse_vt || f.opt.qkv_heads > 0 ? VC_EPI_QKV : VC_EPI_BIAS; }
 void with_vt(Flux& f, VcGemmProblem& p, int rows, int row0, const void* q_scale, const void* k_scale) {
@@ -387,20 +387,13 @@ int ln1(Flux& f, const Ctx& c, int64_t mod, Err e) {                  // the joi
 
 int attention_variant(const Flux& f) {
   if (f.opt.attn_variant >= 0) return f.opt.attn_variant;
-  // 28 = 12 + 16: one wave per SIMD, tail split, and - where the stream form of the kernel runs - the tail pieces combined
-  // inside the launch (the flag words of ATT_SCRATCH are zeroed by vc_flux_prepare, and only this handle's launches, ordered on
-  // one stream, touch it).  Fewer 256-query items than CUs (cfg 1: 168): the same kernel WITHOUT a split (8) - one item per
-  // workgroup beats the 32-queries-per-wave kernel down to half the CUs (round 6, cfg 1: 44.6-49.7 vs 56.3-59.4 us per launch
-  // in situ; per step +1.7 % on one box, +-0.1 % on another - the q / k norm moves from the pre-pass into the qkv GEMM's
-  // epilogue with it; cutting 168 items into 256 short pieces loses 1 %: profiles/r06o_ab_cfg1.log, r06q_ab_cfg1.log)
-  const int items = ((f.L + 255) / 256) * f.H * f.B;
-  return items >= f.n_cu ? 28 : 2 * items >= f.n_cu ? 8 : 3;
+  return vcplan::attention_variant_by_size(f.B, f.L, f.H, f.n_cu);
 }
 
 // QKNorm + RoPE (+ V^T) and the joint attention over QKV -> CAT[:, :D] (layers.py:165-185 / 236-241)
 int attention(Flux& f, const Ctx& c, const void* q1, const void* k1, const void* q2, const void* k2, int split, float block_bound, Err e) {
   const int variant = attention_variant(f);
-  const bool fused_q = (variant & 8) && f.opt.fuse_qnorm, q_done = qn_in_gemm(f);     // q_done: by the projection's epilogue, prescaled
+  const bool fused_q = vcplan::decode_variant(variant).wave64 && f.opt.fuse_qnorm, q_done = qn_in_gemm(f);     // q_done: by the projection's epilogue, prescaled
   const int64_t ld = 3 * f.D, ldo = f.D + f.mlp;
   const int parts = (kn_in_gemm(f) ? 0 : VC_QKN_K) | (fused_q ? 0 : VC_QKN_Q) | (f.opt.fuse_vt ? 0 : VC_QKN_VT);
   if (parts)
@@ -889,7 +882,7 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
   TRY(stage_end(f, s, e));
   HIP(hipMemsetAsync(f.VT, 0, (size_t)B * f.H * 128 * f.Lp * 2, s), "hipMemsetAsync");
   // the flag words of the attention kernel's in-launch combine: zero before the first launch (every launch leaves them zero)
-  HIP(hipMemsetAsync((char*)f.ATT_SCRATCH + vc_attention_flags_offset_impl(), 0, (size_t)vc_attention64_flags_bytes_impl(f.n_cu), s), "hipMemsetAsync");
+  HIP(hipMemsetAsync((char*)f.ATT_SCRATCH + vcplan::attention_flags_offset(vc_cu_count()), 0, (size_t)vcplan::attention64_flags_bytes(f.n_cu), s), "hipMemsetAsync");
   // step-invariant projections
   TRY(lin(f, f.txt_in, in->txt, f.cfg.context_in_dim, f.TXT0, D, B * T, VC_EPI_BIAS, s, e));
   if (f.cfg.guidance_embed) {

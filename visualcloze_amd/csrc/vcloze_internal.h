@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include "../../include/vcloze_hip.h"
+#include "attn_plan.h"
 
 // One-time per-(kernel, device) setup (hipFuncSetAttribute) and per-device properties: the handle API is a public C ABI, a host
 // may drive several GPUs from one process, so nothing of this may be remembered per process only.
@@ -29,11 +30,7 @@ inline int vc_cu_count() {          // compute units of the CURRENT device
 int vc_gemm_launch(VcGemmArgs a, int tile_cfg, hipStream_t s, char* err, int errlen);
 int vc_gemm_plan_impl(VcGemmArgs a, int tile_cfg, int32_t out[8], char* err, int errlen);
 int vc_attention_launch(const VcAttention& a, hipStream_t s, char* err, int errlen);
-int64_t vc_attention_scratch_bytes_impl();
-int64_t vc_attention_flags_offset_impl();
-int64_t vc_attention64_flags_bytes_impl(int n_cu);
-int vc_attention64_launch(const VcAttention& a, bool tail_split, int n_cu, uint64_t* debug_ts, hipStream_t s, char* err, int errlen);
-int64_t vc_attention64_scratch_bytes_impl(int n_cu);
+int vc_attention64_launch(const VcAttention& a, const vcplan::AttnPlan& plan, uint64_t* debug_ts, hipStream_t s, char* err, int errlen);
 int vc_ln_modulate2_launch(const VcLnStream* a, const VcLnStream* b, int64_t mod_bstride, int32_t D, const int32_t* step_ptr,
                            int64_t mod_step_stride, hipStream_t s, char* err, int errlen);
 int vc_ln_modulate_launch(const void* x, int64_t ldx, void* y, int64_t ldy, const void* shift, const void* scale,

@@ -343,11 +343,9 @@ class FluxEngine:
     def attention_variant(self, ws: Workspace) -> int:
         if self.attn_variant is not None:
             return self.attn_variant
-        # 28 = 12 + 16: tail pieces combined inside the launch where the stream form runs (hip.attention_scratch is zero-initialised);
-        # fewer 256-query items than CUs: the same kernel without a split (8) down to half the CUs (cfg 1), the
-        # 32-queries-per-wave kernel (3) below (csrc/flux_engine.hip attention_variant)
-        items = ((ws.L + 255) // 256) * self.H * ws.B
-        return 28 if items >= self.n_cu else 8 if 2 * items >= self.n_cu else 3
+        # by size, the launch planner's rule (csrc/attn_plan.hip attention_variant_by_size; hip.attention_scratch is zero-initialised
+        # for the in-launch combine of 28)
+        return hip.attention_variant_by_size(ws.B, ws.L, self.H, self.n_cu)
 
     def _block_bound(self, pf: str) -> float:
         """VcAttention.logit_bound of block `pf`: its own bound, capped by the model's (csrc/flux_engine.hip attention())"""

@@ -6,6 +6,7 @@ a missing library or a missing GPU raises (`VclozeHipError`)."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import subprocess
 from typing import Optional
@@ -120,6 +121,7 @@ SYMBOLS = {
     "vc_qknorm_rope_vt": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vc_attention": (C.c_int, [C.POINTER(Attention), _vp]),
     "vc_attention_scratch_bytes": (_i64, []),
+    "vc_attention_plan": (C.c_int, [C.POINTER(Attention), _i32, C.POINTER(C.c_int32)]),
     "vc_timestep_embedding": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vc_silu": (C.c_int, [_vp, _vp, _i64, _vp]),
     "vc_act2d": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
@@ -488,6 +490,24 @@ def attention(qkv, vt, out, L, H, kv_len=None, variant=0, stream=None, B=1, scra
         a.q_scale, a.q_scale2, a.split = qs.data_ptr(), _p(qs2), split
         a.rope, a.rope_bstride = rope.data_ptr(), L * 128 if rope.dim() == 4 else 0
     _check(lib().vc_attention(C.byref(a), stream if stream is not None else cur_stream()), "vc_attention")
+
+
+def attention_plan(a: Attention, n_cu: int = 0) -> list:
+    """vc_attention_plan: the sixteen integers of the launch plan of `a` on n_cu compute units (0 = the current device's);
+    no launch, no GPU needed, no pointer of `a` is dereferenced (include/vcloze_hip.h has the layout)."""
+    out = (C.c_int32 * 16)()
+    _check(lib().vc_attention_plan(C.byref(a), n_cu, out), "vc_attention_plan")
+    return list(out)
+
+
+@functools.lru_cache(maxsize=None)
+def attention_variant_by_size(B: int, L: int, H: int, n_cu: int) -> int:
+    """the variant the planner chooses by size (out[0] of the plan; 28, 8 or 3)"""
+    a = Attention()
+    a.qkv = a.vt = a.out = 0x1000          # never dereferenced by the planner
+    a.B, a.L, a.Lpad, a.H = B, L, (L + 63) // 64 * 64, H
+    a.ld, a.bstride, a.ldo, a.out_bstride = 3 * H * 128, L * 3 * H * 128, H * 128, L * H * 128
+    return attention_plan(a, n_cu)[0]
 
 
 def timestep_embedding(t_f32, freqs_f32, out_bf16, round_t_bf16=False, stream=None):
