@@ -312,6 +312,19 @@ int vc_residual_sub(const void* a, int64_t a_bstride, const void* b, int64_t b_b
                     int64_t n, void* stream);
 int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
                     int64_t n, void* stream);
+/* ---- true classifier-free guidance: the combine of Flux.forward_with_cfg (models/model.py:126-145), which runs forward on a batch
+ * whose first half is the conditional and whose second half the unconditional samples and returns
+ * cat([uncond_v + cfg_scale * (cond_v - uncond_v), uncond_v]).  Added without a change of VC_ABI_VERSION: detect by SYMBOL (look up
+ * vc_flux_set_cfg).  cond, uncond, out: n bf16 values each; with torch's roundings for bf16 tensors and a Python float, operation by
+ * operation,
+ *     out[i] = bf16( uncond[i] + bf16( f32(cfg_scale) * bf16( cond[i] - uncond[i] ) ) )
+ * every operation evaluated in f32 and rounded to bf16 (nearest even); cfg_scale is taken as f32 and NOT rounded to bf16; no fused
+ * multiply-add.  cfg_scale = 1 is therefore not the identity (cond - uncond is rounded).  out may BE cond or uncond exactly (each
+ * element is read before it is written); any other overlap of out with an input is VC_ERR_ARG, as are a null pointer, n <= 0 and a
+ * non-finite cfg_scale - all checked before the device is touched.  16-byte accesses need n % 8 == 0 and 16-byte aligned bases;
+ * anything else runs element-wise with the same results.  Flux.forward_with_cfg for a C caller = vc_flux_forward, then
+ * vc_cfg_combine(out, out + n, out, n, cfg_scale) with n = (B / 2) * N * out_channels. */
+int vc_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, void* stream);
 /* SDEdit start state x0 = noise*(1-s) + latent*s with the reference's bf16 roundings (visualcloze.py:221) */
 int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream);
 
@@ -508,6 +521,16 @@ int vc_flux_sample_begin_ode(void* handle, int32_t method, const void* x, const 
  * stats: of the trajectory in flight or just finished - *computed / *reused evaluation counts and, for the first `capacity`
  * evaluations, metrics[i] = the m of evaluation i (NaN where none existed: the first evaluation, or the cache off). */
 int vc_flux_set_step_cache(void* handle, float threshold, int32_t max_consecutive);
+/* ---- true CFG in the sampling loop: the drift is Flux.forward_with_cfg (models/model.py:126-145) instead of Flux.forward.  Off by
+ * default.  While on, EVERY evaluation of the loop (each stage of midpoint and rk4, bf16 and F32 states alike) combines its velocity
+ * V [B * N, out_channels] in place before the solver's update: with h = B / 2 the first h samples are the conditional half, the
+ * rest the unconditional half, V[:h] <- vc_cfg_combine(V[:h], V[h:], cfg_scale), V[h:] stays.  The solver then steps the whole
+ * B-sample state, both halves, as the reference's does; nothing of the conditional half reaches the unconditional one.
+ * A changed setting takes effect at the next vc_flux_sample_begin*, where - while on - an odd B, the step cache on and a non-finite
+ * cfg_scale are VC_ERR_ARG, checked before the device is touched.  The combine is one more node of the captured step, which is kept
+ * per (geometry, method, on, cfg_scale).  While off nothing changes: the same graph, the same workspace size, the same bits.
+ * vc_flux_forward and vc_flux_profile ignore the setting (forward_with_cfg = vc_flux_forward + vc_cfg_combine).  No new workspace. */
+int vc_flux_set_cfg(void* handle, int32_t on, float cfg_scale);
 int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity);
 
 /* ---- the plan's own stopwatch (ABI 10): HIP-event times of the launches of whole evaluations, class by class ----

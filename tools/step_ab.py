@@ -27,7 +27,8 @@ def load(name):
     path = hip.LIB_PATH if name == "main" else os.path.join(os.path.dirname(hip.LIB_PATH), f"libvcloze_hip_{name}.so")
     l = C.CDLL(path)
     for sym, (res, args) in hip.SYMBOLS.items():
-        if sym == "vc_flux_profile" and not hasattr(l, sym):      # an older library in the A/B
+        # an older library in the A/B: entry points added without a change of VC_ABI_VERSION are detected by symbol
+        if sym in ("vc_flux_profile", "vc_cfg_combine", "vc_flux_set_cfg") and not hasattr(l, sym):
             continue
         fn = getattr(l, sym)
         fn.restype, fn.argtypes = res, args

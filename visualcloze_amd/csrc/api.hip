@@ -108,6 +108,9 @@ int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, 
                  const float* dts, const int32_t* eval_ptr, int64_t n, void* stream) {
   return vc_ode_stage_launch(method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, S(stream), ERRBUF);
 }
+int vc_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, void* stream) {
+  return vc_cfg_combine_launch(cond, uncond, out, n, cfg_scale, S(stream), ERRBUF);
+}
 int vc_step_advance(int32_t* step_ptr, void* stream) { return vc_step_advance_launch(step_ptr, S(stream), ERRBUF); }
 int vc_residual_change(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch, int32_t B,
                        int64_t n, void* stream) {
@@ -215,6 +218,7 @@ int vc_flux_sample_end(void* handle, void* x_out, void* stream) { return vc_flux
 int vc_flux_set_step_cache(void* handle, float threshold, int32_t max_consecutive) {
   return vc_flux_set_step_cache_impl(handle, threshold, max_consecutive, ERRBUF);
 }
+int vc_flux_set_cfg(void* handle, int32_t on, float cfg_scale) { return vc_flux_set_cfg_impl(handle, on, cfg_scale, ERRBUF); }
 int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity) {
   return vc_flux_step_cache_stats_impl(handle, computed, reused, metrics, capacity, ERRBUF);
 }

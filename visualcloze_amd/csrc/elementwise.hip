@@ -2,6 +2,7 @@
 //   timestep_embedding  layers.py:28-49      silu / add3   MLPEmbedder + vec sum, model.py:102-107
 //   concat_cols         transport.py:193-196 (x || cond)
 //   ode_stage           the update of the fixed-grid Euler step and the stage combinations of midpoint / rk4 (integrators.py:119, method=...)
+//   cfg_combine         true classifier-free guidance over the two halves of a batch (Flux.forward_with_cfg, model.py:126-145)
 #include "common.h"
 #include "vcloze_internal.h"
 
@@ -177,6 +178,30 @@ __global__ void ode_stage_kernel(int method, int stage_arg, void* __restrict__ y
   }
 }
 
+// ---- true classifier-free guidance (Flux.forward_with_cfg, models/model.py:126-145): cond_v = uncond_v + cfg_scale * (cond_v - uncond_v) ----
+// with torch's roundings for bf16 tensors and a Python float, operation by operation: out = bf16(u + bf16(f32(s) * bf16(c - u))), every
+// op in f32, s NOT rounded to bf16, no fused multiply-add.  One chunk of W elements per thread (W = 8: 16-byte accesses, or 1); a
+// thread reads its chunk of c and u before it writes the same chunk of out, so out may BE c or u (no __restrict__)
+template <int W>
+__global__ void cfg_combine_kernel(const bf16_t* c, const bf16_t* u, bf16_t* out, float s, long n) {
+#pragma clang fp contract(off)
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t * W >= n) return;
+  if constexpr (W == 8) {
+    const u32x4 cw = ((const u32x4*)c)[t], uw = ((const u32x4*)u)[t];
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float ul = lo_bf(uw[i]), uh = hi_bf(uw[i]);
+      o[i] = pack2bf(ul + rbf(s * rbf(lo_bf(cw[i]) - ul)), uh + rbf(s * rbf(hi_bf(cw[i]) - uh)));
+    }
+    ((u32x4*)out)[t] = o;
+  } else {
+    const float uf = bf2f(u[t]);
+    out[t] = f2bf(uf + rbf(s * rbf(bf2f(c[t]) - uf)));
+  }
+}
+
 }  // namespace
 
 #define VC_CHECK_LAUNCH(name)                                                                     \
@@ -262,6 +287,24 @@ int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const
     return VC_ERR_ARG;
   }
   return vc_ode_update_launch("ode_stage", method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, s, err, errlen);
+}
+int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen) {
+  if (!cond || !uncond || !out) { snprintf(err, errlen, "cfg_combine: null pointer"); return VC_ERR_ARG; }
+  if (n <= 0) { snprintf(err, errlen, "cfg_combine: n = %lld must be positive", (long long)n); return VC_ERR_ARG; }
+  if (!(cfg_scale - cfg_scale == 0.0f)) { snprintf(err, errlen, "cfg_combine: cfg_scale is not finite"); return VC_ERR_ARG; }
+  // out may BE cond or uncond (each element is read before it is written); any other overlap would read written elements
+  const uintptr_t o = (uintptr_t)out, bytes = (uintptr_t)n * 2;
+  const uintptr_t ins[2] = {(uintptr_t)cond, (uintptr_t)uncond};
+  for (const uintptr_t a : ins) {
+    if (a != o && a < o + bytes && o < a + bytes) { snprintf(err, errlen, "cfg_combine: out partially overlaps an input (it may only BE cond or uncond)"); return VC_ERR_ARG; }
+  }
+  // 16-byte accesses: every base 16-byte aligned and n a multiple of 8; else element-wise (the idiom of vc_ode_update_launch)
+  const bool vec = n % 8 == 0 && (((uintptr_t)cond | (uintptr_t)uncond | o) & 15) == 0;
+  const long threads = vec ? n / 8 : n;
+  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  if (vec) hipLaunchKernelGGL(cfg_combine_kernel<8>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
+  else hipLaunchKernelGGL(cfg_combine_kernel<1>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
+  VC_CHECK_LAUNCH("cfg_combine");
 }
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen) {
   if (!step_ptr) { snprintf(err, errlen, "step_advance: null"); return VC_ERR_ARG; }

@@ -14,6 +14,8 @@
 //   XS / COND / XIN / V the ODE state, the conditioning columns, x || cond, the velocity
 //   KS [3][B*N*out] / YIN   k1..k3 of an rk4 step / the input state of the next evaluation (midpoint, rk4); every solver's update
 //                           is ONE kernel (ode_stage_kernel, elementwise.hip) behind ONE call (ode_update below)
+//                           with true CFG on (vc_flux_set_cfg) one more kernel in front of it: V's first half <- uncond + s * (cond - uncond),
+//                           in place (cfg_combine_kernel, elementwise.hip); no buffer of its own
 //   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
 #include "common.h"
@@ -98,9 +100,11 @@ struct Flux : Buffers {
   struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; } step;
   struct Key {
     char* base; int B, T, N, S, ragged, gapped, variant, state_f32, method, cache; Options opt; hipStream_t s;   // variant: resolved
+    int cfg; uint32_t cfg_bits;          // true CFG on, and the bits of its scale: a kernel argument of the captured combine
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
-             variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s;
+             variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s &&
+             cfg == o.cfg && cfg_bits == o.cfg_bits;
     }
   } key{};
   std::vector<std::pair<Key, Step>> graphs;
@@ -118,6 +122,10 @@ struct Flux : Buffers {
   int sc_computed = 0, sc_reused = 0;
   std::vector<float> sc_metrics;       // m of every evaluation of the trajectory (NaN where no P existed)
   float* sc_host = nullptr;            // pinned: the head graph's last node copies the metric here
+  // true CFG (Flux.forward_with_cfg, model.py:126-145).  cfg_on / cfg_scale: the caller's setting (vc_flux_set_cfg), which steers a
+  // trajectory from its sample_begin on (cfg_active, cfg_s)
+  bool cfg_on = false, cfg_active = false;
+  float cfg_scale = 1.0f, cfg_s = 1.0f;
   // host staging (pinned), reused once the copies that read it have completed
   char* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;
@@ -531,6 +539,10 @@ int eval_output(Flux& f, const Ctx& c, void* out, bool euler, Err e) {
   p.a_rpb = N; p.a_bstride = (int64_t)L * D;
   TRY(gemm(f, &p, 1, VC_EPI_BIAS, nullptr, 0, s, e));
   if (euler) {
+    if (f.cfg_active) {     // V is sample-major: its first half is the conditional samples' velocity, combined in place
+      const int64_t half = (int64_t)(B / 2) * N * out_ch;
+      TRY(vc_cfg_combine_launch(f.V, f.V + half, f.V, half, f.cfg_s, s, e.buf, e.len));
+    }
     TRY(ode_update(f, f.V, step_ptr, s, e));
     TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
   }
@@ -654,7 +666,9 @@ template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issu
   return VC_OK;
 }
 int step_graph(Flux& f, hipStream_t s, Err e) {
-  Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s};
+  Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s,
+               f.cfg_active, 0};
+  if (f.cfg_active) memcpy(&k.cfg_bits, &f.cfg_s, 4);
   for (size_t i = 0; i < f.graphs.size(); ++i)
     if (f.graphs[i].first == k) {
       auto hit = f.graphs[i];
@@ -942,6 +956,11 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   if (cached && f.dbl.empty()) FAIL(VC_ERR_ARG, "flux_sample: the step cache needs at least one double block");
   if (cached && !f.ws_cache)
     FAIL(VC_ERR_STATE, "flux_sample: the step cache was turned on after vc_flux_prepare: ask vc_flux_workspace_bytes and prepare again");
+  if (f.cfg_on) {
+    if (B % 2) FAIL(VC_ERR_ARG, "flux_sample: true CFG pairs the first half of the batch with the second: B = %d is odd", B);
+    if (cached) FAIL(VC_ERR_ARG, "flux_sample: true CFG does not work with the step cache: turn one off (vc_flux_set_cfg(handle, 0, 0) / vc_flux_set_step_cache(handle, 0, 0))");
+    if (!(f.cfg_scale - f.cfg_scale == 0.0f)) FAIL(VC_ERR_ARG, "flux_sample: the cfg_scale set by vc_flux_set_cfg is not finite");
+  }
   if (cached && !f.sc_host) HIP(hipHostMalloc((void**)&f.sc_host, 256, hipHostMallocDefault), "hipHostMalloc");
   const int SE = S * E;
   TRY(stage_begin(f, ((size_t)SE * B + S) * sizeof(float) + 512, e));
@@ -971,6 +990,7 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   TRY(d2d(f.COND, cond, n * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
   HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
   f.sc_active = cached; f.sc_thr = f.sc_threshold; f.sc_lim = f.sc_max;
+  f.cfg_active = f.cfg_on; f.cfg_s = f.cfg_on ? f.cfg_scale : 1.0f;
   f.sc_have = false; f.sc_run = f.sc_computed = f.sc_reused = 0;
   f.sc_metrics.clear();
   if (s) TRY(step_graph(f, s, e));
@@ -1028,6 +1048,13 @@ int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_conse
   if (threshold != threshold) FAIL(VC_ERR_ARG, "flux_set_step_cache: threshold is NaN");
   f.sc_threshold = threshold > 0.0f ? threshold : 0.0f;
   f.sc_max = max_consecutive;
+  return VC_OK;
+}
+
+int vc_flux_set_cfg_impl(void* handle, int32_t on, float cfg_scale, char* err, int errlen) {
+  H(handle);
+  f.cfg_on = on != 0;
+  f.cfg_scale = cfg_scale;       // held to finite at the next vc_flux_sample_begin*, where the setting takes effect
   return VC_OK;
 }
 

@@ -59,6 +59,7 @@ int vc_ode_update_launch(const char* what, int method, int stage, void* y, int s
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen);
+int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen);
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
                               int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride,
@@ -104,4 +105,5 @@ int vc_flux_profile_impl(void* handle, int32_t evaluations, VcFluxLaunchClass* o
                          char* err, int errlen);
 int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err, int errlen);
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen);
+int vc_flux_set_cfg_impl(void* handle, int32_t on, float cfg_scale, char* err, int errlen);
 int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity, char* err, int errlen);

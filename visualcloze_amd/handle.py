@@ -95,6 +95,7 @@ class FluxHandle:
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._opts: Dict[str, int] = {}
         self._step_cache = (0.0, 0)       # vc_flux_set_step_cache: off
+        self._cfg = None                  # vc_flux_set_cfg: off
         self.geom: Optional[Tuple[int, int, int, int]] = None
         self._host = _HostCopies()
         # the storage order of the bound qkv rows (head-permuted or natural) and the logit bound are PROPERTIES OF THE
@@ -141,6 +142,15 @@ class FluxHandle:
         if want != self._step_cache:
             hip._check(hip.lib().vc_flux_set_step_cache(self.h, want[0], want[1]), "vc_flux_set_step_cache")
             self._step_cache = want
+
+    def set_cfg(self, cfg_scale: Optional[float] = None) -> None:
+        """vc_flux_set_cfg: true classifier-free guidance in the sampling loop (the drift is Flux.forward_with_cfg) with this
+        scale, or None = off.  Takes effect at the next sample_begin / sample_ode; the batch then holds the conditional samples
+        first and the unconditional ones behind them (an even B)."""
+        want = None if cfg_scale is None else float(cfg_scale)
+        if want != self._cfg or (want is not None and want != want):
+            hip._check(hip.lib().vc_flux_set_cfg(self.h, int(want is not None), 0.0 if want is None else want), "vc_flux_set_cfg")
+            self._cfg = want
 
     def step_cache_stats(self, capacity: int = 256) -> dict:
         """vc_flux_step_cache_stats of the trajectory in flight or just finished: {"computed", "reused", "metrics"}; metrics[i] is

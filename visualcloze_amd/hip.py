@@ -137,6 +137,7 @@ SYMBOLS = {
     "vc_residual_change": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
+    "vc_cfg_combine": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _vp]),
     "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_float, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
@@ -171,6 +172,7 @@ SYMBOLS = {
     "vc_flux_sample_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
     "vc_flux_sample_begin_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
     "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
+    "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
     "vc_flux_profile": (C.c_int, [_vp, _i32, C.POINTER(FluxLaunchClass), _i32, C.POINTER(_i32), _vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
@@ -657,6 +659,22 @@ def residual_sub(a, b, out=None, stream=None):
 def residual_add(a, b, out=None, stream=None):
     """vc_residual_add: bf16(f32(a) + f32(b))"""
     return _residual_op(lib().vc_residual_add, "vc_residual_add", a, b, out, stream)
+
+
+def cfg_combine(cond, uncond, cfg_scale: float, out=None, stream=None):
+    """vc_cfg_combine: out = bf16(uncond + bf16(f32(cfg_scale) * bf16(cond - uncond))), the conditional half of
+    Flux.forward_with_cfg (model.py:126-145) with torch's roundings.  cond, uncond: contiguous bf16 tensors of one size; out: a new
+    tensor, or `cond` / `uncond` itself (in place)."""
+    _bf16(cond, "cond"); _bf16(uncond, "uncond")
+    out = torch.empty_like(cond) if out is None else out
+    _bf16(out, "out")
+    if not (cond.is_contiguous() and uncond.is_contiguous() and out.is_contiguous()):
+        raise VclozeHipError("vc_cfg_combine: contiguous tensors expected")
+    if not (cond.numel() == uncond.numel() == out.numel()):
+        raise VclozeHipError("vc_cfg_combine: cond, uncond and out must hold the same number of elements")
+    _check(lib().vc_cfg_combine(cond.data_ptr(), uncond.data_ptr(), out.data_ptr(), cond.numel(), float(cfg_scale),
+                                stream if stream is not None else cur_stream()), "vc_cfg_combine")
+    return out
 
 
 def sdedit_mix(noise, latent, strength, out=None, stream=None):

@@ -161,7 +161,8 @@ class MaskLayout:
     other op of Flux.forward is per-row, so each stream's rows are reordered VALID FIRST (stable), which leaves
         [txt valid | txt masked | img valid | img masked]
     = a prefix length kv_len = T + n_img plus one masked gap (n_txt, T) per sample, and the result rows are scattered
-    back.  Right-padded masks (all the reference's callers build, sampling.py:41-46,68-70,98) are the identity case."""
+    back.  `sl` selects the samples of a chunk: a slice, or a list of sample indices (the pairs of a true-CFG trajectory,
+    transport._sample_fused).  Right-padded masks (all the reference's callers build, sampling.py:41-46,68-70,98) are the identity case."""
 
     def __init__(self, txt_mask, img_mask, B: int, T: int, N: int):
         self.B, self.T, self.N = B, T, N
@@ -181,30 +182,34 @@ class MaskLayout:
             self.perm_i = pi
             self.inv_i = torch.argsort(pi, dim=1)
 
-    def kv_len(self, sl: slice) -> List[int]:
-        return [self.T + n for n in self.n_img[sl]]
+    @staticmethod
+    def _pick(values: list, sl) -> list:
+        return values[sl] if isinstance(sl, slice) else [values[i] for i in sl]
 
-    def kv_gap(self, sl: slice):
-        gaps = [(n, self.T) if n < self.T else (0, 0) for n in self.n_txt[sl]]
+    def kv_len(self, sl) -> List[int]:
+        return [self.T + n for n in self._pick(self.n_img, sl)]
+
+    def kv_gap(self, sl):
+        gaps = [(n, self.T) if n < self.T else (0, 0) for n in self._pick(self.n_txt, sl)]
         return gaps if any(hi > lo for lo, hi in gaps) else None
 
     @staticmethod
-    def _take(x: Tensor, perm, sl: slice) -> Tensor:
+    def _take(x: Tensor, perm, sl) -> Tensor:
         x = x[sl]
         if perm is None:
             return x
         idx = perm[sl].to(x.device)
         return torch.gather(x, 1, idx.reshape(idx.shape + (1,) * (x.dim() - 2)).expand(x.shape))
 
-    def txt_rows(self, x: Tensor, sl: slice) -> Tensor:
+    def txt_rows(self, x: Tensor, sl) -> Tensor:
         """rows of a [B, T, ...] text-stream tensor (txt, txt_ids) in kernel order"""
         return self._take(x, self.perm_t, sl)
 
-    def img_rows(self, x: Tensor, sl: slice) -> Tensor:
+    def img_rows(self, x: Tensor, sl) -> Tensor:
         """rows of a [B, N, ...] image-stream tensor (img / x, cond, img_ids) in kernel order"""
         return self._take(x, self.perm_i, sl)
 
-    def img_rows_back(self, x: Tensor, sl: slice) -> Tensor:
+    def img_rows_back(self, x: Tensor, sl) -> Tensor:
         """kernel-order [bs, N, ...] image-stream rows back in the caller's order"""
         if self.inv_i is None:
             return x
@@ -499,6 +504,28 @@ class Flux(nn.Module):
     @torch.no_grad()
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
                 txt_mask: Tensor = None, img_mask: Tensor = None, guidance: Optional[Tensor] = None) -> Tensor:
+        out = self._forward_bf16(img, img_ids, txt, txt_ids, timesteps, y, txt_mask, img_mask, guidance)
+        return out.to(img.dtype) if img.dtype.is_floating_point else out
+
+    @torch.no_grad()
+    def forward_with_cfg(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
+                         txt_mask: Tensor = None, img_mask: Tensor = None, guidance: Optional[Tensor] = None,
+                         cfg_scale: float = 1.0) -> Tensor:
+        """models/model.py:126-145: true classifier-free guidance over a batch whose first half is the conditional samples and
+        whose second half the unconditional ones (negative prompt, other y, other guidance).  `forward` runs on the batch as given
+        (the reference's `combined` is never used, so both halves keep their own state); returned is
+        cat([uncond_v + cfg_scale * (cond_v - uncond_v), uncond_v]).  The combine (vc_cfg_combine, torch's bf16 roundings) acts on
+        the kernels' bf16 output BEFORE the cast to the caller's dtype: the fused sampling loop sees the same bits."""
+        if img.ndim == 3 and img.shape[0] % 2:
+            raise ValueError(f"forward_with_cfg: the batch holds the conditional samples and then the unconditional ones, "
+                             f"got an odd batch of {img.shape[0]}")
+        out = self._forward_bf16(img, img_ids, txt, txt_ids, timesteps, y, txt_mask, img_mask, guidance)
+        h = out.shape[0] // 2
+        hip.cfg_combine(out[:h], out[h:], cfg_scale, out=out[:h])
+        return out.to(img.dtype) if img.dtype.is_floating_point else out
+
+    def _forward_bf16(self, img, img_ids, txt, txt_ids, timesteps, y, txt_mask=None, img_mask=None, guidance=None) -> Tensor:
+        """Flux.forward as the kernels leave it: bf16 [B, N, out_channels] on the engine's device"""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
@@ -531,7 +558,7 @@ class Flux(nn.Module):
             ws.XIN.copy_(bf(lay.img_rows(img, sl)).reshape(bs * N, -1))
             eng.eval_once(ws, None, euler=False, concat=False)
             out[sl].copy_(lay.img_rows_back(ws.V.reshape(bs, N, -1), sl))
-        return out.to(img.dtype) if img.dtype.is_floating_point else out
+        return out
 
 
 class FluxLoraWrapper(Flux):

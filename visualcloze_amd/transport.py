@@ -9,7 +9,9 @@ Only the configuration the inference pipeline uses is implemented (Linear path, 
 fixed-grid solvers "euler", "midpoint" and "rk4"; anything else raises NotImplementedError.  When `model` is the
 bound `forward` of a `visualcloze_amd.Flux`, the whole loop runs as hipGraph replays of one captured evaluation +
 the solver's update (Euler step / midpoint or rk4 stage combination) with zero host synchronisation inside the
-loop; a foreign callable is stepped eagerly with the same grid.
+loop; a foreign callable is stepped eagerly with the same grid.  The bound `forward_with_cfg` of a `visualcloze_amd.Flux`
+(true classifier-free guidance, model.py:126-145: `model_kwargs["cfg_scale"]`, conditional samples first, unconditional ones
+behind them) runs the same fused loop with the cross-sample combine as one more node of the captured step.
 
 The step rules (`STEP_RULES`) are torchdiffeq 0.2.x's fixed-grid solvers as recalled - unpinned against real
 torchdiffeq, which was not available to check against (as the Euler rule, tests/golden/make_golden.py).  They
@@ -151,6 +153,16 @@ class Sampler:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
             from .model import Flux
             owner = getattr(model, "__self__", None)
+            if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward_with_cfg":
+                if step_cache is not None:
+                    raise ValueError("step_cache works with Flux.forward only, not with forward_with_cfg (true CFG)")
+                kw = dict(model_kwargs)
+                cfg_scale = float(kw.pop("cfg_scale", 1.0))
+                if _cfg_fusable(owner, x, sampling_method, kw):
+                    return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, None, self, cfg_scale=cfg_scale)
+                # stepped eagerly (unequal image masks within a pair, no C handle, an f16 / f64 state): the same bf16 velocity
+                fwd = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k).to(torch.bfloat16)  # noqa: E731
+                return _sample_foreign(fwd, x, kw, t, return_trajectory, sampling_method)
             if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward":
                 if step_cache is not None:      # never silently ignored: only the C handle's loop implements it
                     if getattr(owner, "lora_mode", "merged") == "ref" or owner.handle() is None:
@@ -183,6 +195,31 @@ def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
     if x.dtype == torch.bfloat16:
         return True
     return x.dtype == torch.float32 and flux.handle() is not None
+
+
+def _cfg_fusable(flux, x: torch.Tensor, method: str, kw: dict) -> bool:
+    """True CFG runs fused through the C handle alone, on pairs (j, j + B/2) that advance in one chunk: `MaskLayout` permutes image
+    rows valid-first per sample, so the two samples of a pair must share their image mask for row i of one to be row i of the other
+    (text masks may differ: a negative prompt of another length).  Anything else is stepped eagerly through forward_with_cfg."""
+    if flux.handle() is None or not _fusable(flux, x, method):
+        return False
+    B = x.shape[0]
+    if B % 2:
+        return False              # forward_with_cfg raises for it
+    tm, im = kw.get("txt_mask"), kw.get("img_mask")
+    if tm is None or im is None:
+        return True
+    im = im.reshape(B, -1) != 0
+    return bool(torch.equal(im[:B // 2], im[B // 2:]))
+
+
+def cfg_chunks(B: int, max_batch: int) -> list:
+    """The chunks of a true-CFG batch (samples [0, B/2) conditional, [B/2, B) unconditional) as lists of sample indices: whole pairs
+    (j, j + B/2), as many as fit into `max_batch` samples, stacked conditional-first - cfg_chunks(6, 4) = [[0, 1, 3, 4], [2, 5]]."""
+    if B % 2 or max_batch < 2:
+        raise ValueError(f"true CFG needs an even batch and chunks of at least one pair, got B = {B}, max_batch = {max_batch}")
+    half, ppc = B // 2, max_batch // 2
+    return [list(range(p0, min(p0 + ppc, half))) + [j + half for j in range(p0, min(p0 + ppc, half))] for p0 in range(0, half, ppc)]
 
 
 def _solver_t_as_state(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -220,7 +257,9 @@ def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
 
 
 @torch.no_grad()
-def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=None, sampler=None):
+def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=None, sampler=None, cfg_scale=None):
+    """cfg_scale: None = the drift is Flux.forward; a number = Flux.forward_with_cfg with it (C handle only).  Samples then advance
+    in chunks of whole pairs (j, j + B/2), conditional samples first, and go back in the caller's order."""
     eng = flux.engine()
     dev = eng.dev
     B, N, C = x.shape
@@ -241,7 +280,7 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
     bf = lambda a: a.to(dev, torch.bfloat16).contiguous()  # noqa: E731
     sdt = x.dtype                                  # bf16, or f32 (handle path only): the state is stepped in ITS dtype
     out = torch.empty(B, N, C, dtype=sdt, device=dev)
-    traj = []
+    traj = torch.empty(S, B, N, C, dtype=sdt, device=dev) if return_trajectory else None
     gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
     from .model import MaskLayout, per_sample
     guidance = per_sample(guidance, B)
@@ -253,12 +292,18 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
     h = flux.handle()
     if h is not None:
         h.set_step_cache(step_cache)               # None: off, whatever an earlier trajectory on this handle ran with
+        h.set_cfg(cfg_scale)
+    elif cfg_scale is not None:
+        raise hip.VclozeHipError("true CFG in the fused loop needs the C handle")
+    if cfg_scale is None:
+        chunks = [slice(b0, min(b0 + eng.MAX_BATCH, B)) for b0 in range(0, B, eng.MAX_BATCH)]
+    else:
+        chunks = cfg_chunks(B, eng.MAX_BATCH)
     stats = []
     with torch.cuda.stream(st):
         s = st.cuda_stream
-        for b0 in range(0, B, eng.MAX_BATCH):        # a chunk of samples advances together, one graph replay per step
-            bs = min(eng.MAX_BATCH, B - b0)
-            sl = slice(b0, b0 + bs)
+        for sl in chunks:                            # a chunk of samples advances together, one graph replay per step
+            bs = len(range(B)[sl]) if isinstance(sl, slice) else len(sl)
             if h is not None:
                 h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
                           lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), S * E, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
@@ -268,8 +313,8 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
                 if step_cache is not None:
                     stats.append(h.step_cache_stats(S))
                 if return_trajectory:
-                    traj.append(torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)]))
-                out[sl].copy_(lay.img_rows_back(xs, sl))
+                    traj[:, sl] = torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)])
+                out[sl] = lay.img_rows_back(xs, sl)
                 continue
             ws = eng.workspace(T, N, S, bs)
             eng.prepare_sample(ws, bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
@@ -286,13 +331,15 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
                 if return_trajectory:
                     states.append(lay.img_rows_back(ws.XS.reshape(bs, N, C), sl).clone())
             if return_trajectory:
-                traj.append(torch.stack(states))                  # [S, bs, N, C]
+                traj[:, sl] = torch.stack(states)                 # [S, bs, N, C]
             out[sl].copy_(lay.img_rows_back(ws.XS.reshape(bs, N, C), sl))
+        if cfg_scale is not None:
+            h.set_cfg(None)                        # a later trajectory driven on this handle directly is a plain one again
     torch.cuda.current_stream().wait_stream(st)
     if step_cache is not None:
         flux.last_step_cache_stats = stats         # one dict per chunk of <= MAX_BATCH samples, in order
         if sampler is not None:
             sampler.last_step_cache_stats = stats
     if return_trajectory:
-        return torch.cat((x.to(dev)[None], torch.cat(traj, dim=1).to(sdt)), dim=0)
+        return torch.cat((x.to(dev)[None], traj), dim=0)
     return out[None]
