@@ -325,14 +325,18 @@ int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_b
  * anything else runs element-wise with the same results.  Flux.forward_with_cfg for a C caller = vc_flux_forward, then
  * vc_cfg_combine(out, out + n, out, n, cfg_scale) with n = (B / 2) * N * out_channels. */
 int vc_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, void* stream);
-/* SDEdit start state x0 = noise*(1-s) + latent*s with the reference's bf16 roundings (visualcloze.py:221) */
-int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream);
+/* SDEdit start state x0 = noise*(1-s) + latent*s with the reference's bf16 roundings (visualcloze.py:221).  strength is the
+ * reference's Python float, a double: the noise factor is f32(1.0 - s) with the subtraction in double, the latent factor
+ * f32(s) - the two f32 scalars torch multiplies the bf16 tensors by. */
+int vc_sdedit_mix(const void* noise, const void* latent, double strength, void* out, int64_t n, void* stream);
 
 /* ---- latent-grid packer / unpacker (the steps either side of the loop) ----
  * pack:   latent [C,h,w] bf16 -> tokens[(h/2)(w/2)][col0 .. col0+4C) of rows with stride ld
  *         ("c (h ph) (w pw) -> (h w) (c ph pw)", models/sampling.py:61, visualcloze.py:208-209,385-386)
  * mask:   pixel mask [H,W] bf16 -> [(H/16)(W/16)][col0 .. col0+256)  (8x8 unshuffle + 2x2 pack, visualcloze.py:381-382)
- * unpack: the inverse of pack (visualcloze.py:237,428) */
+ * unpack: the inverse of pack (visualcloze.py:237,428)
+ * ld and col0 are multiples of 8 and the token base is 16-byte aligned (16-byte accesses on the token side; the latent is read
+ * and written in 4-byte words, the mask in 16-byte vectors); anything else is VC_ERR_ARG. */
 int vc_pack_latent(const void* latent, void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, void* stream);
 int vc_pack_mask(const void* mask, void* tokens, int32_t H, int32_t W, int64_t ld, int32_t col0, void* stream);
 int vc_unpack_latent(const void* tokens, int64_t ld, int32_t col0, void* latent, int32_t C, int32_t h, int32_t w, void* stream);

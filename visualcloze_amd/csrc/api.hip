@@ -125,7 +125,7 @@ int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_b
   return vc_residual_op_launch(1, a, a_bstride, b, b_bstride, out, out_bstride, B, n, S(stream), ERRBUF);
 }
 
-int vc_sdedit_mix(const void* noise, const void* latent, float strength, void* out, int64_t n, void* stream) {
+int vc_sdedit_mix(const void* noise, const void* latent, double strength, void* out, int64_t n, void* stream) {
   return vc_sdedit_mix_launch(noise, latent, strength, out, n, S(stream), ERRBUF);
 }
 int vc_im2col3x3(const void* src, void* dst, int32_t H, int32_t W, int32_t C, int32_t up, void* stream) {

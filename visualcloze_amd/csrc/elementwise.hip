@@ -46,12 +46,14 @@ __global__ void concat_cols_kernel(const u32x4* __restrict__ x, int cxc, const u
   out[i] = (c < cxc) ? x[r * cxc + c] : cond[r * ccc + (c - cxc)];
 }
 
-// SDEdit start state (visualcloze.py:221): x0 = bf16(bf16(noise*(1-s)) + bf16(latent*s)), s a python float
-__global__ void sdedit_mix_kernel(const bf16_t* __restrict__ noise, const bf16_t* __restrict__ latent, float s,
+// SDEdit start state (visualcloze.py:221): x0 = bf16(bf16(noise*(1-s)) + bf16(latent*s)), s a python float (a double): torch
+// multiplies the bf16 tensors by c = f32(1.0 - s), the subtraction done in DOUBLE, and by f32(s).  The launcher forms both
+// factors from the double; 1.0f - f32(s) is a different f32 for 41 of the 99 strengths 0.01 .. 0.99.
+__global__ void sdedit_mix_kernel(const bf16_t* __restrict__ noise, const bf16_t* __restrict__ latent, float c, float s,
                                   bf16_t* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  out[i] = f2bf(rbf(bf2f(noise[i]) * (1.0f - s)) + rbf(bf2f(latent[i]) * s));
+  out[i] = f2bf(rbf(bf2f(noise[i]) * c) + rbf(bf2f(latent[i]) * s));
 }
 
 // y[m, n] = bf16(act(x[m, n])) on row views: act 0 = GELU(tanh), 1 = SiLU
@@ -311,8 +313,9 @@ int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errl
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, s, step_ptr);
   VC_CHECK_LAUNCH("step_advance");
 }
-int vc_sdedit_mix_launch(const void* noise, const void* latent, float strength, void* out, int64_t n, hipStream_t s, char* err, int errlen) {
+int vc_sdedit_mix_launch(const void* noise, const void* latent, double strength, void* out, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!noise || !latent || !out || n <= 0) { snprintf(err, errlen, "sdedit_mix: bad args"); return VC_ERR_ARG; }
-  hipLaunchKernelGGL(sdedit_mix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)noise, (const bf16_t*)latent, strength, (bf16_t*)out, (long)n);
+  hipLaunchKernelGGL(sdedit_mix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)noise, (const bf16_t*)latent,
+                     (float)(1.0 - strength), (float)strength, (bf16_t*)out, (long)n);
   VC_CHECK_LAUNCH("sdedit_mix");
 }

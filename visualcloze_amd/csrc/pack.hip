@@ -96,6 +96,8 @@ int vc_pack_latent_launch(const void* in, void* out, int C, int h, int w, int64_
   if (!in || !out || C <= 0 || h <= 0 || w <= 0 || (C & 1) || (h & 1) || (w & 1) || ld % 8 || col0 % 8) {
     snprintf(err, errlen, "pack_latent: need even C, h, w and 16-B aligned ld / col0 (C=%d h=%d w=%d)", C, h, w); return VC_ERR_ARG; }
   if (C > 64) { snprintf(err, errlen, "pack_latent: C=%d > 64 channels", C); return VC_ERR_ARG; }
+  if (((uintptr_t)out & 15) || ((uintptr_t)in & 3)) {   // 16-B vector stores on the token side, 4-B words on the map side
+    snprintf(err, errlen, "pack_latent: the token rows must be 16-byte aligned and the latent 4-byte aligned"); return VC_ERR_ARG; }
   PK_LAUNCH("pack_latent", pack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), (size_t)C * 2 * LDW * 4, (const bf16_t*)in, (bf16_t*)out, C, h, w, (long)ld, col0)
 }
 int vc_pack_mask_launch(const void* in, void* out, int H, int W, int64_t ld, int col0, hipStream_t s, char* err, int errlen) {
@@ -109,5 +111,7 @@ int vc_unpack_latent_launch(const void* in, int64_t ld, int col0, void* out, int
   if (!in || !out || C <= 0 || h <= 0 || w <= 0 || (C & 1) || (h & 1) || (w & 1) || ld % 8 || col0 % 8) {
     snprintf(err, errlen, "unpack_latent: need even C, h, w and 16-B aligned ld / col0"); return VC_ERR_ARG; }
   if (C > 64) { snprintf(err, errlen, "unpack_latent: C=%d > 64 channels", C); return VC_ERR_ARG; }
+  if (((uintptr_t)in & 15) || ((uintptr_t)out & 3)) {   // 16-B vector loads on the token side, 4-B words on the map side
+    snprintf(err, errlen, "unpack_latent: the token rows must be 16-byte aligned and the latent 4-byte aligned"); return VC_ERR_ARG; }
   PK_LAUNCH("unpack_latent", unpack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), (size_t)C * 2 * LDW * 4, (const bf16_t*)in, (long)ld, col0, (bf16_t*)out, C, h, w)
 }

@@ -67,7 +67,7 @@ int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void*
 int vc_pack_latent_launch(const void* in, void* out, int C, int h, int w, int64_t ld, int col0, hipStream_t s, char* err, int errlen);
 int vc_pack_mask_launch(const void* in, void* out, int H, int W, int64_t ld, int col0, hipStream_t s, char* err, int errlen);
 int vc_unpack_latent_launch(const void* in, int64_t ld, int col0, void* out, int C, int h, int w, hipStream_t s, char* err, int errlen);
-int vc_sdedit_mix_launch(const void* noise, const void* latent, float strength, void* out, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_sdedit_mix_launch(const void* noise, const void* latent, double strength, void* out, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_im2col3x3_launch(const void* src, void* dst, int H, int W, int C, int up, hipStream_t s, char* err, int errlen);
 int vc_groupnorm_launch(const void* x, const void* gamma, const void* beta, void* y, void* scratch, int64_t scratch_bytes,
                         int64_t HW, int C, int G, float eps, int swish, hipStream_t s, char* err, int errlen);

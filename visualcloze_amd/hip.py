@@ -138,7 +138,7 @@ SYMBOLS = {
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_cfg_combine": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _vp]),
-    "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_float, _vp, _i64, _vp]),
+    "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_double, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
     "vc_unpack_latent": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
