@@ -560,6 +560,80 @@ typedef struct VcFluxLaunchClass {
 } VcFluxLaunchClass;
 int vc_flux_profile(void* handle, int32_t evaluations, VcFluxLaunchClass* out, int32_t capacity, int32_t* count, void* stream);
 
+/* ---- autoencoder handle: AutoEncoder.decode / AutoEncoder.encode (models/modules/autoencoder.py:277-311) behind one call each ----
+ * Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up vc_vae_create.
+ * vc_vae_decode replaces AutoEncoder.decode (autoencoder.py:306-308: z / scale_factor + shift_factor, then Decoder.forward :237-259)
+ * vc_vae_encode replaces AutoEncoder.encode (autoencoder.py:301-304: Encoder.forward :159-180, DiagonalGaussian :268-275, then
+ *               scale_factor * (z - shift_factor))
+ * The launch plan is the one visualcloze_amd/vae.py spells in Python over the op-level entry points above (vc_conv3x3, vc_groupnorm,
+ * vc_gemm, vc_softmax_rows, vc_transpose, vc_nchw_to_nhwc, vc_nhwc_to_nchw, vc_gaussian_sample, vc_pack_latent, vc_unpack_latent): the
+ * same kernels in the same order, so the two give the same bits.  ONE image per call, activations NHWC bf16.  Every activation lives
+ * in a caller-provided workspace.  The handle OWNS the prepared weights: device copies in the GEMM's operand layout, made by
+ * vc_vae_bind_weight and freed by vc_vae_destroy (this is the one place where the library allocates device memory), and the captured
+ * hipGraphs.  One handle per device; not thread-safe per handle; the encoder and the decoder halves have separate workspace
+ * regions, each half serves one stream at a time. */
+typedef struct VcVaeConfig {    /* AutoEncoderParams, autoencoder.py:8-18, without `resolution` (the plan is built per image size) */
+  int32_t in_channels, ch, out_ch;
+  int32_t ch_mult[8];           /* the first n_ch_mult entries; every ch * ch_mult[i] a multiple of 64 */
+  int32_t n_ch_mult;            /* 1..8: the image is 2^(n_ch_mult - 1) times the latent */
+  int32_t num_res_blocks, z_channels;
+  float scale_factor, shift_factor;
+} VcVaeConfig;
+/* sizeof(VcVaeConfig) as this library was compiled (vc_struct_sizes keeps its seven entries) */
+void vc_vae_struct_sizes(int32_t out[1]);
+/* host-only: needs no device */
+int vc_vae_create(const VcVaeConfig* cfg, void** handle);
+int vc_vae_destroy(void* handle);
+/* the weights the handle expects, in the order of AutoEncoder.state_dict(): index 0, 1, ... until VC_ERR_ARG.  name receives the
+ * module path - the state_dict key of the module's weight without the trailing ".weight" ("decoder.up.3.block.0.conv1",
+ * "encoder.mid.attn_1.norm", ...); its ".bias" key is the same path.  Host-only. */
+int vc_vae_weight_name(void* handle, int32_t index, char* name, int32_t namelen);
+/* name: a module path as above (a trailing ".weight" is accepted).  w / bias: the tensors of the module's ".weight" / ".bias" keys
+ * AS A CHECKPOINT STORES THEM, contiguous, both bf16 or both F32 (is_f32); shape HOST [ndim] = the weight's shape: [O, I, k, k] of an
+ * nn.Conv2d (k = 3, or 1 for nin_shortcut and the attention projections), [C] of an nn.GroupNorm.  The call rounds to bf16 and
+ * writes the handle's own copy - a convolution as [O_pad8, k * k * I_pad64] with K ordered (dy, dx, c), the operand layout of
+ * vc_conv3x3 - with two small kernels on `stream`, which it synchronises: w and bias may be released when it returns.  An unknown
+ * name, a shape other than the module's, or a null pointer is VC_ERR_ARG with the name in the message (nothing is launched).
+ * Binding again replaces the copy and drops the captured plans. */
+int vc_vae_bind_weight(void* handle, const char* name, const void* w, const void* bias, int32_t is_f32, const int64_t* shape,
+                       int32_t ndim, void* stream);
+/* H, W: the IMAGE size in pixels, multiples of 2^(n_ch_mult - 1) (the latent is [z_channels, H / f, W / f]).  which: */
+#define VC_VAE_ENCODER 1
+#define VC_VAE_DECODER 2   /* VC_VAE_ENCODER | VC_VAE_DECODER = both */
+/* Host-only; a bad size or `which` is VC_ERR_ARG. */
+int vc_vae_workspace_bytes(void* handle, int32_t H, int32_t W, int32_t which, int64_t* bytes);
+/* Carves the activation maps (each with the zero row vc_conv3x3 reads), the GroupNorm scratch and the attention buffers of the
+ * chosen halves out of `workspace` (device memory, >= vc_vae_workspace_bytes, 256-B aligned, the caller's while decode / encode
+ * calls follow) and fills the residual gate of ones - the only thing a plan reads that it does not write.  The handle serves ONE
+ * prepared (H, W, which, workspace) at a time; preparing another and coming back keeps the captured plans of both.  A workspace
+ * that is too small is VC_ERR_ARG and nothing is launched.  The fill is asynchronous on `stream`: a decode / encode call on ANOTHER
+ * stream must be ordered behind it by the caller (an event, or a synchronise).  The carve-up depends on `which` (the decoder's
+ * buffers start the workspace when it is prepared alone, and follow the encoder's otherwise), and so do the captured plans: a
+ * workspace prepared again with another `which` gets plans of its own, the earlier ones serve again once the earlier `which` is
+ * prepared again (which also refills the gate). */
+int vc_vae_prepare(void* handle, int32_t H, int32_t W, int32_t which, void* workspace, int64_t workspace_bytes, void* stream);
+/* latent_form: what the sampler leaves / what the sampler reads */
+#define VC_VAE_LATENT_BF16 0   /* [z_channels, H / f, W / f] bf16, contiguous */
+#define VC_VAE_LATENT_F32 1    /* the same in F32 (decode only) */
+#define VC_VAE_TOKENS 2        /* packed tokens [(h / 2) (w / 2)][col0 .. col0 + 4 z_channels) of bf16 rows with stride ld, as
+                                  vc_unpack_latent reads and vc_pack_latent writes them (ld, col0 multiples of 8; even h, w) */
+/* pixels [out_ch, H, W] (bf16, or F32 with pixels_is_f32) = decoder(latent / scale_factor + shift_factor).  ld, col0: VC_VAE_TOKENS only.
+ * An unbound decoder weight is VC_ERR_STATE naming the first missing key; so is a call before vc_vae_prepare with VC_VAE_DECODER.
+ * With a stream, the call is ONE hipGraph launch: the plan for (workspace, H, W, which, direction, forms, the caller's pointers, stream) is
+ * captured on first use - after one un-captured run that sets the kernels' attributes - and kept in a list of 8, most recently used
+ * first; the pointers are kernel arguments of the graph, so a caller that keeps its buffers hits the list, and one that rotates
+ * them pays a capture (no second un-captured run: that happens once per size, direction and forms) per new set of pointers.  stream == NULL runs
+ * the same plan un-captured on the default stream. */
+int vc_vae_decode(void* handle, const void* latent, int32_t latent_form, int64_t ld, int32_t col0, void* pixels, int32_t pixels_is_f32,
+                  void* stream);
+/* latent = scale_factor * ((mean + exp(0.5 * logvar) * noise) - shift_factor) of pixels [in_channels, H, W] (bf16 or F32); noise
+ * [z_channels, H / f, W / f] bf16 is an INPUT as in vc_gaussian_sample, NULL = the mean (the mode of latent_dist).  latent_form
+ * VC_VAE_LATENT_BF16 or VC_VAE_TOKENS (the packing then happens inside).  Errors and graph capture as vc_vae_decode. */
+int vc_vae_encode(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t latent_form,
+                  int64_t ld, int32_t col0, void* stream);
+/* captured plans the handle holds (0..8); -1 for a null handle */
+int vc_vae_plan_count(void* handle);
+
 /* ---- hipGraph helpers: capture the launches issued on `stream` between begin/end ---- */
 int vc_stream_create(void** stream);
 int vc_stream_destroy(void* stream);

@@ -234,6 +234,31 @@ int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t
   return vc_flux_sample_ode(handle, VC_SOLVER_EULER, x, cond, t_grid, n_points, state_is_bf16, trajectory, stream);
 }
 
+/* ---- autoencoder handle (vae_engine.hip) ---- */
+void vc_vae_struct_sizes(int32_t out[1]) { out[0] = (int32_t)sizeof(VcVaeConfig); }
+int vc_vae_create(const VcVaeConfig* cfg, void** handle) { return vc_vae_create_impl(cfg, handle, ERRBUF); }
+int vc_vae_destroy(void* handle) { return vc_vae_destroy_impl(handle, ERRBUF); }
+int vc_vae_weight_name(void* handle, int32_t index, char* name, int32_t namelen) { return vc_vae_weight_name_impl(handle, index, name, namelen, ERRBUF); }
+int vc_vae_bind_weight(void* handle, const char* name, const void* w, const void* bias, int32_t is_f32, const int64_t* shape, int32_t ndim,
+                       void* stream) {
+  return vc_vae_bind_weight_impl(handle, name, w, bias, is_f32, shape, ndim, S(stream), ERRBUF);
+}
+int vc_vae_workspace_bytes(void* handle, int32_t H, int32_t W, int32_t which, int64_t* bytes) {
+  return vc_vae_workspace_bytes_impl(handle, H, W, which, bytes, ERRBUF);
+}
+int vc_vae_prepare(void* handle, int32_t H, int32_t W, int32_t which, void* workspace, int64_t workspace_bytes, void* stream) {
+  return vc_vae_prepare_impl(handle, H, W, which, workspace, workspace_bytes, S(stream), ERRBUF);
+}
+int vc_vae_decode(void* handle, const void* latent, int32_t latent_form, int64_t ld, int32_t col0, void* pixels, int32_t pixels_is_f32,
+                  void* stream) {
+  return vc_vae_decode_impl(handle, latent, latent_form, ld, col0, pixels, pixels_is_f32, S(stream), ERRBUF);
+}
+int vc_vae_encode(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t latent_form,
+                  int64_t ld, int32_t col0, void* stream) {
+  return vc_vae_encode_impl(handle, pixels, pixels_is_f32, noise, latent, latent_form, ld, col0, S(stream), ERRBUF);
+}
+int vc_vae_plan_count(void* handle) { return vc_vae_plan_count_impl(handle); }
+
 /* ---- streams / graphs / events ---- */
 int vc_stream_create(void** stream) {
   if (!stream) { snprintf(g_err, sizeof(g_err), "stream_create: null"); return VC_ERR_ARG; }

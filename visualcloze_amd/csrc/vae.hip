@@ -238,6 +238,48 @@ __global__ void gaussian_sample_kernel(const bf16_t* __restrict__ mom, int Cp, c
   out[i] = f2bf(scale * rbf(z - shift));
 }
 
+// ---- one-time weight preparation of the autoencoder handle (vae_engine.hip; the re-layout visualcloze_amd/vae.py does in torch) ----
+// nn.Conv2d weight [O, I, k, k] (f32 or bf16, as a checkpoint stores it) -> the GEMM operand [Op, k*k, Ip] bf16 with K ordered
+// (dy, dx, c) like the taps vc_conv3x3 gathers; rows >= O and channels >= I are zero.  One 16-byte store per thread; the reads
+// are a gather with stride k*k (run once per weight, not on the hot path).
+__global__ void conv_weight_relayout_kernel(const void* __restrict__ src, int src_f32, bf16_t* __restrict__ dst, int O, int I, int kk,
+                                            int Op, int Ip) {
+  const int cpr = Ip >> 3;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)Op * kk * cpr) return;
+  const int c8 = (int)(i % cpr);
+  const int t = (int)((i / cpr) % kk);
+  const int o = (int)(i / ((long)cpr * kk));
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c = c8 * 8 + e;
+    v[e] = 0.f;
+    if (o < O && c < I) {
+      const long j = ((long)o * I + c) * kk + t;
+      v[e] = src_f32 ? ((const float*)src)[j] : bf2f(((const bf16_t*)src)[j]);
+    }
+  }
+  u32x4 w;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) w[e] = pack2bf(v[2 * e], v[2 * e + 1]);
+  *(u32x4*)(dst + i * 8) = w;
+}
+
+// 16-byte zero stores: the zero row behind an activation map and the zero pads of the attention operands (what vae.py does with
+// torch's zero_()).  A kernel rather than a memset, so that a captured plan is a chain of kernel nodes only.
+__global__ void zero_fill_kernel(u32x4* __restrict__ p, long n16) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n16) p[i] = u32x4{0u, 0u, 0u, 0u};
+}
+
+// dst[i] = bf16(src[i]) for i < n, 0 for n <= i < n_pad: biases and GroupNorm affines (a few hundred values, once per weight)
+__global__ void cast_pad_kernel(const void* __restrict__ src, int src_f32, bf16_t* __restrict__ dst, int n, int n_pad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pad) return;
+  dst[i] = i < n ? (src_f32 ? f2bf(((const float*)src)[i]) : ((const bf16_t*)src)[i]) : (bf16_t)0;
+}
+
 }  // namespace
 
 #define VAE_LAUNCH_CHECK(what)                                                                   \
@@ -318,5 +360,30 @@ int vc_gaussian_sample_launch(const void* moments, int Cp, const void* noise, vo
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)moments, Cp,
                      (const bf16_t*)noise, (bf16_t*)out, Z, (long)HW, scale, shift);
   VAE_LAUNCH_CHECK("gaussian_sample");
+  return VC_OK;
+}
+
+int vc_vae_weight_relayout_launch(const void* w, int w_f32, void* dst, int O, int I, int kk, int Op, int Ip, hipStream_t s, char* err, int errlen) {
+  if (!w || !dst) { snprintf(err, errlen, "vae weight relayout: null pointer"); return VC_ERR_ARG; }
+  if (O <= 0 || I <= 0 || kk <= 0 || Op < O || Ip < I || Ip % 8) { snprintf(err, errlen, "vae weight relayout: bad shape O=%d I=%d kk=%d Op=%d Ip=%d", O, I, kk, Op, Ip); return VC_ERR_ARG; }
+  const long total = (long)Op * kk * (Ip >> 3);
+  hipLaunchKernelGGL(conv_weight_relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, w_f32, (bf16_t*)dst, O, I, kk, Op, Ip);
+  VAE_LAUNCH_CHECK("vae weight relayout");
+  return VC_OK;
+}
+
+int vc_vae_cast_pad_launch(const void* src, int src_f32, void* dst, int n, int n_pad, hipStream_t s, char* err, int errlen) {
+  if (!src || !dst) { snprintf(err, errlen, "vae cast: null pointer"); return VC_ERR_ARG; }
+  if (n <= 0 || n_pad < n) { snprintf(err, errlen, "vae cast: bad size n=%d n_pad=%d", n, n_pad); return VC_ERR_ARG; }
+  hipLaunchKernelGGL(cast_pad_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, src, src_f32, (bf16_t*)dst, n, n_pad);
+  VAE_LAUNCH_CHECK("vae cast");
+  return VC_OK;
+}
+
+int vc_zero_fill_launch(void* p, int64_t bytes, hipStream_t s, char* err, int errlen) {
+  if (!p || bytes <= 0 || bytes % 16 || ((uintptr_t)p & 15)) { snprintf(err, errlen, "zero fill: a 16-byte aligned pointer and a multiple of 16 bytes expected (%ld)", (long)bytes); return VC_ERR_ARG; }
+  const long n16 = bytes / 16;
+  hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (u32x4*)p, n16);
+  VAE_LAUNCH_CHECK("zero fill");
   return VC_OK;
 }

@@ -78,6 +78,9 @@ int vc_nchw_to_nhwc_launch(const void* src, int src_f32, void* dst, int C, int C
 int vc_nhwc_to_nchw_launch(const void* src, void* dst, int dst_f32, int C, int Cp, int64_t HW, hipStream_t s, char* err, int errlen);
 int vc_gaussian_sample_launch(const void* moments, int Cp, const void* noise, void* out, int Z, int64_t HW, float scale, float shift,
                               hipStream_t s, char* err, int errlen);
+int vc_vae_weight_relayout_launch(const void* w, int w_f32, void* dst, int O, int I, int kk, int Op, int Ip, hipStream_t s, char* err, int errlen);
+int vc_vae_cast_pad_launch(const void* src, int src_f32, void* dst, int n, int n_pad, hipStream_t s, char* err, int errlen);
+int vc_zero_fill_launch(void* p, int64_t bytes, hipStream_t s, char* err, int errlen);
 int vc_embedding_launch(const int32_t* ids, const void* table, int64_t ldt, int V, void* out, int L, int D, hipStream_t s, char* err, int errlen);
 int vc_rownorm_launch(const void* x, const void* w, const void* b, void* y, int rows, int D, float eps, int affine_ln, hipStream_t s, char* err, int errlen);
 int vc_ewise_launch(const void* a, const void* b, void* y, int64_t n, int op, hipStream_t s, char* err, int errlen);
@@ -107,3 +110,18 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen);
 int vc_flux_set_cfg_impl(void* handle, int32_t on, float cfg_scale, char* err, int errlen);
 int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity, char* err, int errlen);
+
+// vae_engine.hip: the autoencoder handle
+int vc_vae_create_impl(const VcVaeConfig* cfg, void** handle, char* err, int errlen);
+int vc_vae_destroy_impl(void* handle, char* err, int errlen);
+int vc_vae_weight_name_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen);
+int vc_vae_bind_weight_impl(void* handle, const char* name, const void* w, const void* bias, int32_t is_f32, const int64_t* shape, int32_t ndim,
+                            hipStream_t s, char* err, int errlen);
+int vc_vae_workspace_bytes_impl(void* handle, int32_t H, int32_t W, int32_t which, int64_t* bytes, char* err, int errlen);
+int vc_vae_prepare_impl(void* handle, int32_t H, int32_t W, int32_t which, void* workspace, int64_t workspace_bytes, hipStream_t s,
+                        char* err, int errlen);
+int vc_vae_decode_impl(void* handle, const void* latent, int32_t latent_form, int64_t ld, int32_t col0, void* pixels, int32_t pixels_is_f32,
+                       hipStream_t s, char* err, int errlen);
+int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t latent_form, int64_t ld,
+                       int32_t col0, hipStream_t s, char* err, int errlen);
+int vc_vae_plan_count_impl(void* handle);

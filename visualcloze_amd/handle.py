@@ -262,3 +262,181 @@ class FluxHandle:
 
     def sample_euler(self, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
         self.sample_ode("euler", x, cond, t_grid, state_is_bf16, stream, trajectory)
+
+
+class VaeHandle:
+    """The autoencoder handle of include/vcloze_hip.h (vc_vae_*) behind torch tensors: `AutoEncoder.decode` / `.encode` of ONE
+    image as one C call each, one hipGraph launch once the plan is captured.  The launch plan lives in csrc/vae_engine.hip;
+    `vae.AutoEncoder`'s own Python-ordered plan is its parity twin (same kernels, same order, same bits).  This class binds the
+    module's parameters as `state_dict()` stores them (the library re-lays them out), owns the workspace per image size and - since
+    a captured plan holds its argument pointers - one set of input / output tensors per (size, direction, form): arguments are copied
+    in, results are returned as fresh tensors."""
+
+    def __init__(self, ae, dev: Optional[torch.device] = None):
+        enc, dec = ae.encoder, ae.decoder
+        self.dev = torch.device(dev) if dev is not None else next(ae.parameters()).device
+        widths = [lvl.block[0].out_channels for lvl in dec.up]
+        mult = [w // dec.ch for w in widths]
+        self.cfg = hip.VaeConfig(enc.in_channels, dec.ch, dec.out_ch, (C.c_int32 * 8)(*mult), len(mult), enc.num_res_blocks, dec.z_channels,
+                                 float(ae.scale_factor), float(ae.shift_factor))
+        self.f, self.z, self.in_ch, self.out_ch = dec.ffactor, dec.z_channels, enc.in_channels, dec.out_ch
+        self.h = C.c_void_p()
+        hip._check(hip.lib().vc_vae_create(C.byref(self.cfg), C.byref(self.h)), "vc_vae_create")
+        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._io: Dict[tuple, tuple] = {}
+        self._prepared = None
+        self._side = None
+        sd = ae.state_dict()
+        names = self.weight_names()
+        if [k for k in sd if k.endswith(".weight")] != [n + ".weight" for n in names]:
+            raise hip.VclozeHipError("the module's state_dict keys differ from the weights libvcloze_hip.so expects for this configuration")
+        with torch.cuda.device(self.dev):
+            for n in names:
+                self.bind(n, sd[n + ".weight"], sd[n + ".bias"])
+
+    def weight_names(self) -> list:
+        out, buf = [], C.create_string_buffer(160)
+        while hip.lib().vc_vae_weight_name(self.h, len(out), buf, 160) == 0:
+            out.append(buf.value.decode())
+        return out
+
+    def bind(self, name: str, w: torch.Tensor, b: torch.Tensor, stream=None) -> None:
+        """vc_vae_bind_weight: w / b as the checkpoint stores them (bf16 or f32, any device - moved to the handle's first)"""
+        w, b = w.detach().to(self.dev).contiguous(), b.detach().to(self.dev).contiguous()
+        if w.dtype not in (torch.bfloat16, torch.float32):
+            w = w.float()
+        b = b.to(w.dtype)
+        shape = (C.c_int64 * w.dim())(*w.shape)
+        hip._check(hip.lib().vc_vae_bind_weight(self.h, name.encode(), w.data_ptr(), b.data_ptr(), int(w.dtype == torch.float32), shape,
+                                                w.dim(), stream if stream is not None else hip.cur_stream()), f"vc_vae_bind_weight({name})")
+        self._io.clear()
+
+    def __del__(self):
+        try:
+            if self.h:
+                hip.lib().vc_vae_destroy(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+    def plan_count(self) -> int:
+        return hip.lib().vc_vae_plan_count(self.h)
+
+    def workspace_bytes(self, H: int, W: int, which: int = hip.VAE_ENCODER | hip.VAE_DECODER) -> int:
+        n = C.c_int64(0)
+        hip._check(hip.lib().vc_vae_workspace_bytes(self.h, H, W, which, C.byref(n)), "vc_vae_workspace_bytes")
+        return n.value
+
+    def prepare(self, H: int, W: int, which: int = hip.VAE_ENCODER | hip.VAE_DECODER, stream=None) -> None:
+        """vc_vae_prepare for a (H, W)-pixel image; the workspaces of the last four (size, halves) are kept (a two-stage pipeline alternates)"""
+        key = (H, W, which)
+        if self._prepared == key:
+            return
+        ws = self._ws.get(key)
+        if ws is None:
+            if len(self._ws) >= 4:              # two image sizes (a two-stage pipeline) x two halves
+                self._ws.clear(); self._io.clear()
+            ws = torch.empty(self.workspace_bytes(H, W, which) + 256, dtype=torch.uint8, device=self.dev)
+            self._ws[key] = ws
+        base = (ws.data_ptr() + 255) & ~255
+        hip._check(hip.lib().vc_vae_prepare(self.h, H, W, which, base, ws.numel() - (base - ws.data_ptr()),
+                                            stream), "vc_vae_prepare")
+        self._prepared = key
+
+    def _stream(self, stream):
+        """(the hipStream_t value to pass, the torch stream the plan runs on when that is not torch's current stream, else None).
+        stream 0 = torch's current stream; when that is the null stream - on which the library runs un-captured - the captured
+        plan runs on a stream of the handle's own.  Any other value is taken as the caller's hipStream_t.  The copies into and out
+        of the argument slots run on torch's current stream, so a plan on another stream is ordered behind and in front of it
+        (`_join`).  None = the un-captured path, on the null stream."""
+        cur = torch.cuda.current_stream(self.dev)
+        if stream is None:
+            cur.synchronize()
+            return None, None
+        if stream == 0 and cur.cuda_stream != 0:
+            return cur.cuda_stream, None
+        if stream != 0 and stream == cur.cuda_stream:
+            return stream, None
+        if stream == 0:
+            if self._side is None:
+                self._side = torch.cuda.Stream(self.dev)
+            other = self._side
+        else:
+            other = torch.cuda.ExternalStream(stream, device=self.dev)
+        other.wait_stream(cur)
+        return other.cuda_stream, other
+
+    def _join(self, stream, other) -> None:
+        if stream is None:
+            torch.cuda.synchronize(self.dev)
+        elif other is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(other)
+
+    def _slot(self, key: tuple, shapes) -> tuple:
+        """the persistent argument tensors of one (size, direction, form): a captured plan is keyed on their addresses"""
+        io = self._io.get(key)
+        if io is None:
+            io = tuple(None if s is None else torch.empty(s[0], dtype=s[1], device=self.dev) for s in shapes)
+            self._io[key] = io
+        return io
+
+    def decode(self, z: torch.Tensor, stream=0, pixels_f32: bool = False, which: int = hip.VAE_DECODER) -> torch.Tensor:
+        """z [z_channels, h, w] bf16 / f32 -> pixels [out_ch, f h, f w] bf16 (or f32).  `which`: the halves the workspace of this
+        size is prepared for - by default only the one the call needs (a decode-only user never allocates the encoder's maps).  stream: a hipStream_t value, 0 = torch's
+        current stream (captured), None = the library's un-captured path on the default stream."""
+        if z.dim() != 3 or z.shape[0] != self.z or z.dtype not in (torch.bfloat16, torch.float32):
+            raise hip.VclozeHipError(f"VaeHandle.decode: [{self.z}, h, w] bf16 / f32 latent expected, got {z.dtype} {tuple(z.shape)}")
+        h, w = z.shape[-2:]
+        H, W = self.f * h, self.f * w
+        pdt = torch.float32 if pixels_f32 else torch.bfloat16
+        zin, px = self._slot((H, W, "dec", z.dtype, pdt), (((self.z, h, w), z.dtype), ((self.out_ch, H, W), pdt)))
+        zin.copy_(z)
+        s, cur = self._stream(stream)
+        self.prepare(H, W, which, stream=s)
+        form = hip.VAE_LATENT_F32 if z.dtype == torch.float32 else hip.VAE_LATENT_BF16
+        hip._check(hip.lib().vc_vae_decode(self.h, zin.data_ptr(), form, 0, 0, px.data_ptr(), int(pixels_f32), s), "vc_vae_decode")
+        self._join(stream, cur)
+        return px.clone()
+
+    def decode_tokens(self, tokens: torch.Tensor, h: int, w: int, col0: int = 0, stream=0, which: int = hip.VAE_DECODER) -> torch.Tensor:
+        """tokens [(h/2)(w/2), >= col0 + 4 z] bf16 rows as the sampler leaves them -> pixels [out_ch, f h, f w] bf16"""
+        hip._bf16(tokens, "tokens")
+        if tokens.dim() != 2 or tokens.stride(1) != 1 or tokens.shape[0] != (h // 2) * (w // 2):
+            raise hip.VclozeHipError("VaeHandle.decode_tokens: [(h/2)(w/2), cols] rows with contiguous columns expected")
+        H, W = self.f * h, self.f * w
+        tin, px = self._slot((H, W, "dect", tuple(tokens.shape)), ((tuple(tokens.shape), torch.bfloat16), ((self.out_ch, H, W), torch.bfloat16)))
+        tin.copy_(tokens)
+        s, cur = self._stream(stream)
+        self.prepare(H, W, which, stream=s)
+        hip._check(hip.lib().vc_vae_decode(self.h, tin.data_ptr(), hip.VAE_TOKENS, tin.stride(0), col0, px.data_ptr(), 0, s), "vc_vae_decode")
+        self._join(stream, cur)
+        return px.clone()
+
+    def encode(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, stream=0, tokens: Optional[torch.Tensor] = None, col0: int = 0,
+               which: int = hip.VAE_ENCODER) -> torch.Tensor:
+        """x [in_channels, H, W] bf16 / f32, noise [z_channels, H/f, W/f] bf16 or None (the mean) -> latent [z_channels, H/f, W/f]
+        bf16; with `tokens` (bf16 rows [(h/2)(w/2), >= col0 + 4 z]) a copy of it whose columns col0.. hold the packed latent"""
+        if x.dim() != 3 or x.shape[0] != self.in_ch or x.dtype not in (torch.bfloat16, torch.float32):
+            raise hip.VclozeHipError(f"VaeHandle.encode: [{self.in_ch}, H, W] bf16 / f32 pixels expected, got {x.dtype} {tuple(x.shape)}")
+        H, W = x.shape[-2:]
+        h, w = H // self.f, W // self.f
+        tshape = None if tokens is None else (tuple(tokens.shape), torch.bfloat16)
+        xin, nin, out, tok = self._slot((H, W, "enc", x.dtype, noise is not None, tshape),
+                                        (((self.in_ch, H, W), x.dtype), None if noise is None else ((self.z, h, w), torch.bfloat16),
+                                         ((self.z, h, w), torch.bfloat16), tshape))
+        xin.copy_(x)
+        if noise is not None:
+            nin.copy_(noise.reshape(self.z, h, w))
+        if tokens is not None:
+            tok.copy_(tokens)
+        s, cur = self._stream(stream)
+        self.prepare(H, W, which, stream=s)
+        if tokens is not None:
+            hip._check(hip.lib().vc_vae_encode(self.h, xin.data_ptr(), int(x.dtype == torch.float32), hip._p(nin), tok.data_ptr(), hip.VAE_TOKENS,
+                                               tok.stride(0), col0, s), "vc_vae_encode")
+            self._join(stream, cur)
+            return tok.clone()
+        hip._check(hip.lib().vc_vae_encode(self.h, xin.data_ptr(), int(x.dtype == torch.float32), hip._p(nin), out.data_ptr(),
+                                           hip.VAE_LATENT_BF16, 0, 0, s), "vc_vae_encode")
+        self._join(stream, cur)
+        return out.clone()

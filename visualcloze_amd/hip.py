@@ -98,6 +98,16 @@ class FluxInputs(C.Structure):
                 ("guidance_is_bf16", C.c_int32), ("_pad", C.c_int32)]
 
 
+class VaeConfig(C.Structure):
+    """VcVaeConfig of include/vcloze_hip.h."""
+    _fields_ = [("in_channels", C.c_int32), ("ch", C.c_int32), ("out_ch", C.c_int32), ("ch_mult", C.c_int32 * 8), ("n_ch_mult", C.c_int32),
+                ("num_res_blocks", C.c_int32), ("z_channels", C.c_int32), ("scale_factor", C.c_float), ("shift_factor", C.c_float)]
+
+
+VAE_ENCODER, VAE_DECODER = 1, 2                             # VC_VAE_ENCODER / VC_VAE_DECODER (`which` of vc_vae_prepare)
+VAE_LATENT_BF16, VAE_LATENT_F32, VAE_TOKENS = 0, 1, 2       # VC_VAE_LATENT_* / VC_VAE_TOKENS (latent_form)
+
+
 # every symbol include/vcloze_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 class FluxLaunchClass(C.Structure):          # VcFluxLaunchClass (vc_flux_profile)
@@ -175,6 +185,16 @@ SYMBOLS = {
     "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
     "vc_flux_profile": (C.c_int, [_vp, _i32, C.POINTER(FluxLaunchClass), _i32, C.POINTER(_i32), _vp]),
+    "vc_vae_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_vae_create": (C.c_int, [C.POINTER(VaeConfig), C.POINTER(_vp)]),
+    "vc_vae_destroy": (C.c_int, [_vp]),
+    "vc_vae_weight_name": (C.c_int, [_vp, _i32, C.c_char_p, _i32]),
+    "vc_vae_bind_weight": (C.c_int, [_vp, C.c_char_p, _vp, _vp, _i32, C.POINTER(_i64), _i32, _vp]),
+    "vc_vae_workspace_bytes": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_i64)]),
+    "vc_vae_prepare": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "vc_vae_decode": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
+    "vc_vae_encode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp]),
+    "vc_vae_plan_count": (C.c_int, [_vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
     "vc_stream_sync": (C.c_int, [_vp]),
@@ -220,6 +240,10 @@ def lib() -> C.CDLL:
         if list(sizes) != [C.sizeof(GemmProblem), C.sizeof(GemmArgs), C.sizeof(LnStream), C.sizeof(Attention),
                            C.sizeof(FluxConfig), C.sizeof(FluxInputs), C.sizeof(FluxLaunchClass)]:
             raise VclozeHipError(f"libvcloze_hip.so struct sizes {list(sizes)} differ from the ctypes mirrors - rebuild")
+        vsize = (C.c_int32 * 1)()
+        l.vc_vae_struct_sizes(vsize)
+        if vsize[0] != C.sizeof(VaeConfig):
+            raise VclozeHipError(f"libvcloze_hip.so sizeof(VcVaeConfig) {vsize[0]} differs from the ctypes mirror - rebuild")
         _lib = l
     return _lib
 

@@ -375,12 +375,42 @@ class AutoEncoder(nn.Module):
                                z_channels=params.z_channels)
         self.scale_factor = params.scale_factor
         self.shift_factor = params.shift_factor
+        # opt-in, like Flux.use_handle: True routes encode / decode through the library's autoencoder handle (vc_vae_*,
+        # handle.VaeHandle: the same launch plan kept in csrc/vae_engine.hip, one hipGraph launch per image) instead of the
+        # Python-ordered plan below, which stays the default and the handle's parity twin - the two give the same bits
+        self.use_handle = False
+        self.__dict__["_vae_handle"] = None
+
+    def __getstate__(self):
+        """copy.deepcopy / pickling: the cached VaeHandle owns a C handle and device memory and stays with THIS module (a copy
+        builds its own on first use)"""
+        state = self.__dict__.copy()
+        state["_vae_handle"] = None
+        return state
+
+    def handle(self):
+        """the `handle.VaeHandle` over this module's parameters, rebuilt when a parameter was replaced or written"""
+        from .handle import VaeHandle
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        c = self.__dict__["_vae_handle"]
+        if c is None or c[0] != key:
+            c = (key, VaeHandle(self))
+            self.__dict__["_vae_handle"] = c
+        return c[1]
 
     def encode(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, sample: bool = True) -> torch.Tensor:
         hip.require_gpu()
         enc = self.encoder
         if x.dim() != 4 or x.shape[1] != enc.in_channels:
             raise ValueError(f"encode expects [B, {enc.in_channels}, H, W], got {tuple(x.shape)}")
+        if self.use_handle:
+            f = 2 ** (enc.num_resolutions - 1)
+            if x.shape[-2] % f or x.shape[-1] % f:
+                raise ValueError(f"Encoder: image size {x.shape[-2]}x{x.shape[-1]} must be a multiple of {f}")
+            hd, zs = self.handle(), (enc.z_channels, x.shape[-2] // f, x.shape[-1] // f)
+            return torch.stack([hd.encode(xi, None if not sample else (noise[i] if noise is not None else
+                                                                       torch.randn(zs, dtype=torch.bfloat16, device=x.device)).to(torch.bfloat16))
+                                for i, xi in enumerate(x)])
         outs = []
         for i, xi in enumerate(x):
             mom, h, w = enc._moments_one(xi.contiguous())
@@ -396,6 +426,9 @@ class AutoEncoder(nn.Module):
         hip.require_gpu()
         if z.dim() != 4 or z.shape[1] != self.decoder.z_channels:
             raise ValueError(f"decode expects [B, {self.decoder.z_channels}, h, w], got {tuple(z.shape)}")
+        if self.use_handle:
+            hd = self.handle()
+            return torch.stack([hd.decode(zi) for zi in z])
         return torch.stack([self.decoder._decode_one(zi.contiguous(), self.scale_factor, self.shift_factor) for zi in z])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
