@@ -1,9 +1,10 @@
-"""Per-element fp64 error budgets for the bf16 glue kernels (vae.hip, text.hip, pack.hip, elementwise.hip).
+"""Per-element fp64 error budgets for the bf16 kernels: the glue kernels (vae.hip, text.hip, pack.hip, elementwise.hip) and the hot
+path of a Flux step (gemm.hip, norm.hip, attention.hip, attention64.hip).
 
 A kernel that stores bf16(f(x)) computed in f32 differs from the fp64 value of f by at most half a bf16 ulp per rounding
 point plus whatever its f32 arithmetic adds.  `assert_within_budget` checks exactly that, for EVERY element, against the
 element's own magnitude - never against the largest element of the tensor, where an error in the small elements of a row
-(another group's statistics, a dropped tail chunk) would pass unseen.
+(another group's statistics, a dropped tail chunk, one product or one key lost) would pass unseen.
 
     |got - ref64| <= sum over rounding points r of (1/2 + 1/64) * gain_r * ulp_bf16(mag_r)  +  f32_terms  +  floor
 
@@ -14,12 +15,17 @@ element's own magnitude - never against the largest element of the tensor, where
   gain_r     |d out / d intermediate_r|, 1 unless the entry of `mags` is a (mag, gain) pair
   1/64 ulp   f32 arithmetic between two roundings and the exp2 / rcp intrinsics: relative errors of 2^-22 .. 2^-17,
              far below 2^-15 = 1/64 of the SMALLEST relative size of a bf16 ulp (2^-9 .. 2^-8 is half an ulp)
-  f32_terms  f32 reductions and cancelling f32 sums: n_serial * 2^-24 * sum|terms|, propagated to the output by the caller
+  f32_terms  f32 reductions and cancelling f32 sums: n_serial * 2^-24 * sum|terms|, propagated to the output by the caller.
+             Where the order of a sum is the hardware's or the launch plan's business (the matrix pipe, split-K slices, stream
+             pieces, attention's tail pieces) the term is the order-independent (n - 1) * eps * sum|terms|, and for sums the
+             matrix pipe accumulates eps = 2^-23 per addition (EPS_MFMA): neither the kernels nor the hardware guides
+             establish round-to-nearest for its accumulate, so truncation is allowed for
   floor      absolute slack for results below any bf16 a kernel's f32 intrinsics resolve (denormal products)
 
-The `*_case` functions below build (ref64, mags, f32_terms) for each kernel from its header comment; tests/test_budget_cpu.py
-shows that torch's own CPU results meet every one of them and that a 2-ulp error in one small element, or one group's mean
-moved by 2^-6 std, does not.  No constant here was fitted to what a GPU returned.
+The `*_case` functions below build (ref64, mags, f32_terms) for each kernel from its header comment and its code;
+tests/test_budget_cpu.py shows that torch's own CPU results (and f32 emulations of the kernels' rounding sequences) meet every
+one of them and that a subtly wrong result - a 2-ulp error in one small element, one group's mean moved by 2^-6 std, one
+product of a GEMM or one key of an attention row lost - does not.  No constant here was fitted to what a GPU returned.
 """
 import math
 
@@ -27,6 +33,7 @@ import torch
 
 HALF = 0.5 + 1.0 / 64.0
 EPS24 = 2.0 ** -24
+EPS_MFMA = 2.0 ** -23      # one addition of the matrix pipe's f32 accumulate (rounding mode not established: see above)
 
 
 def ulp_bf16(m):
@@ -45,20 +52,30 @@ def rbf64(x):
     return torch.round(x / q) * q                          # x / q is exact (q a power of two); round() is half-to-even
 
 
+STORE = "store"      # entry of `mags`: the final store, rounded at the LARGEST magnitude the stored value can have
+
+
 def budget(ref64, roundings=1, mags=None, f32_terms=None, floor=1e-30):
+    """An entry of `mags` is a magnitude, a (magnitude, gain) pair, None (= |ref64|) or STORE: the store of a value that earlier
+    rounding points have already moved rounds at |ref64| + (everything budgeted before it), not at |ref64| - a value that sits
+    half an ulp below a power of two in fp64 is stored from the binade above it as often as not, where the ulp is twice as
+    large.  (An intermediate rounding point behind another one gets the same treatment from its case builder.)"""
     ref64 = torch.as_tensor(ref64, dtype=torch.float64)
     mags = list(mags) if mags is not None else []
     assert len(mags) <= roundings
     total = torch.zeros_like(ref64)
+    if f32_terms is not None:
+        total = total + torch.as_tensor(f32_terms, dtype=torch.float64).abs()
     for r in range(roundings):
         m = mags[r] if r < len(mags) else None
         gain = 1.0
-        if isinstance(m, tuple):
+        if isinstance(m, str):
+            assert m == STORE and r == roundings - 1
+            m = ref64.abs() + total
+        elif isinstance(m, tuple):
             m, gain = m
         m = ref64.abs() if m is None else torch.as_tensor(m, dtype=torch.float64).abs()
         total = total + HALF * torch.as_tensor(gain, dtype=torch.float64).abs() * ulp_bf16(m)
-    if f32_terms is not None:
-        total = total + torch.as_tensor(f32_terms, dtype=torch.float64).abs()
     return total + floor
 
 
@@ -280,3 +297,269 @@ def act_values(n):
     u, z = (torch.rand(max(n, 6), generator=g) - 0.5) * 200.0, torch.randn(max(n, 6), generator=g) * 3.0
     v = torch.cat([torch.tensor([0.0, -0.0, 100.0, -100.0, 12.0, -12.0]), torch.stack([u, z], dim=1).flatten()])
     return v.to(torch.bfloat16)                                        # +-0 and the extremes first, then wide and narrow values in turn
+
+
+# ---------------------------------------------------------------- GEMM (gemm.hip)
+def _dact(fn, t):
+    """|d fn / d t| in fp64 (autograd on the fp64 formula: no hand-written derivative to get wrong)"""
+    t = t.detach().clone().requires_grad_(True)
+    fn(t).sum().backward()
+    return t.grad.abs()
+
+
+def gemm_case(a, w, bias, epi, res=None, gate=None):
+    """a [M, K], w [N, K], bias [N] or None (bf16 values); gate broadcastable to [M, N] (a row per batch element), res [M, N].
+    gemm.hip header: t = bf16(acc + b), acc = sum_k a w in f32 on the matrix pipe (the products of two bf16 values are exact
+    in f32), then  EPI_BIAS / EPI_QKV  y = t (EPI_QKV only moves the V columns: same value wherever it lands),
+    EPI_GELU  y = bf16(gelu_tanh(t)),  EPI_SILU  y = bf16(silu(t)),  EPI_GATE_RES  y = bf16(res + bf16(gate * t)).
+    Rounding points:
+      t            at |acc + b|; gain |act'(t)| (fp64, autograd) for GELU / SiLU, |gate| for GATE_RES
+      gate * t     GATE_RES only, at |gate * t|
+      the store    GELU / SiLU / GATE_RES, at |y| + what the points before it can have moved it by (STORE)
+    f32_terms: (K + 1) * EPS_MFMA * (sum_k |a w| + |b|), times the same gain: K products and the bias are K + 1 terms, summed
+    in an order that depends on the tile family (bias first or last), the MFMA's internal order and the split of K into slices or
+    stream pieces - the bound holds for every order, and it does not shrink with |acc + b| when the sum cancels.  The single f32
+    operations of the epilogues (gate * t, res + ., the activations' intrinsics) sit inside the 1/64 ulp of their rounding."""
+    a64, w64 = a.to(torch.float64), w.to(torch.float64)
+    K = a64.shape[1]
+    acc = a64 @ w64.t()
+    mass = a64.abs() @ w64.abs().t()
+    if bias is not None:
+        acc = acc + bias.to(torch.float64).reshape(1, -1)
+        mass = mass + bias.to(torch.float64).abs().reshape(1, -1)
+    t = acc
+    f32 = (K + 1) * EPS_MFMA * mass
+    t_mag = t.abs() + f32                              # what is rounded is the f32 sum, not acc + b
+    if epi in (0, 4):
+        return t, [t_mag], f32
+    if epi in (1, 3):
+        fn = gelu_tanh64 if epi == 1 else silu64
+        g = _dact(fn, t)
+        return fn(t), [(t_mag, g), STORE], f32 * g
+    assert epi == 2
+    g64 = gate.to(torch.float64).expand_as(t) if gate.dim() == 2 else gate.to(torch.float64).reshape(1, -1).expand_as(t)
+    gt_mag = g64.abs() * (t_mag + HALF * ulp_bf16(t_mag))          # gate times the ROUNDED t
+    return res.to(torch.float64) + g64 * t, [(t_mag, g64.abs()), gt_mag, STORE], f32 * g64.abs()
+
+
+# ---------------------------------------------------------------- ln_modulate (norm.hip)
+def ln_modulate_case(x, shift, scale, eps=1e-6):
+    """x [rows, D]; shift, scale [D] or [rows, D] (the row's modulation).  y = bf16(bf16(1 + scale) * LN(x) + shift) (norm.hip
+    header).  bf16(1 + scale) is reproducible (one f32 add of a bf16 value, one rounding) and is applied inside the reference
+    with torch f32 / bf16 ops; one budgeted rounding, the store.  f32_terms as layernorm_case, none of which scales with y, with
+    a = bf16(1 + scale) for the weight and the shift for the bias.  Serial length of the mean and variance sums
+    (ln_modulate_kernel: one wave per row, a lane adds the 8 elements of each of its ceil(D / 512) chunks, then wave_sum's 6
+    butterfly steps): row_serial(D); the mean's division by D is one more operation."""
+    x = x.to(torch.float64)
+    a = (1.0 + scale.float()).to(torch.bfloat16).to(torch.float64)
+    a = a.reshape(1, -1) if a.dim() == 1 else a
+    sh = shift.to(torch.float64)
+    sh = sh.reshape(1, -1) if sh.dim() == 1 else sh
+    mean = x.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(-1, keepdim=True) + eps)
+    xh = (x - mean) * rstd * a
+    n = row_serial(x.shape[1])
+    f32 = EPS24 * (4.0 * (xh.abs() + sh.abs()) + (n + 1) * x.abs().mean(-1, keepdim=True) * rstd * a.abs() + (0.5 * n + 2.0) * xh.abs())
+    return xh + sh, [STORE], f32.expand_as(xh)
+
+
+# ---------------------------------------------------------------- QKNorm + RoPE (norm.hip, common.h qknorm_rope8)
+QK_PRESCALE = 128 ** -0.5 * 1.4426950408889634      # VC_QK_PRESCALE: 128^-0.5 * log2(e)
+
+
+def qknorm_rope_case(x, scale, rope, prescale=False, eps=1e-6):
+    """x [L, H, 128] (the q or the k columns of the qkv rows), scale [128] or [L, 1, 128] (the row's stream), rope [L, 64, 2] =
+    (cos, sin).  common.h qknorm_rope8: rrms = rsq(sum(x^2) / 128 + 1e-6); t = bf16(bf16(x * rrms) * scale); the interleaved
+    pairs are rotated, re = cos t0 - sin t1, im = sin t0 + cos t1 (written-out FMAs), and the rotated value times `post` is
+    rounded ONCE: post = 1, or 128^-0.5 * log2(e) with QKN_QPRE (and in attention64.hip's in-kernel query norm, which folds the
+    scale in the same way).  Rounding points of an output element (re shown; im has cos and sin swapped):
+      x0 * rrms    gain |scale0 cos| post        t0 = . * scale0    gain |cos| post
+      x1 * rrms    gain |scale1 sin| post        t1 = . * scale1    gain |sin| post
+      the store    at |post * re| + what the four points before it can have moved it by (STORE)
+    f32_terms, relative to |cos t0| + |sin t1| (NOT to the result: the rotation's two products can cancel), times post:
+      2 * 2^-24        the product and the FMA of the rotation
+      (12 / 2 + 3)     rrms: a sum of 128 non-negative squares, 8 serial FMAs per lane and 4 butterfly steps over the row's 16
+                       lanes, relative error <= 12 * 2^-24, half of it in rrms; the FMA with 1/128 and 1e-6 and the 1-ulp v_rsq"""
+    x = x.to(torch.float64)
+    L, H, D = x.shape
+    g = scale.to(torch.float64)
+    g = g.reshape(1, 1, D) if g.dim() == 1 else g
+    post = QK_PRESCALE if prescale else 1.0
+    rrms = 1.0 / torch.sqrt((x * x).mean(-1, keepdim=True) + eps)
+    xn = x * rrms
+    t = (xn * g).reshape(L, H, D // 2, 2)
+    xn, gp = xn.reshape(L, H, D // 2, 2), g.expand(L, H, D).reshape(L, H, D // 2, 2)
+    co, si = rope.to(torch.float64)[:, None, :, 0], rope.to(torch.float64)[:, None, :, 1]
+    t0, t1, x0, x1, g0, g1 = t[..., 0], t[..., 1], xn[..., 0], xn[..., 1], gp[..., 0], gp[..., 1]
+    st = lambda re, im: torch.stack([re, im], -1).reshape(L, H, D)  # noqa: E731
+    ref = st(co * t0 - si * t1, si * t0 + co * t1) * post
+    ca, sa = co.abs() * post, si.abs() * post
+    tm0, tm1 = t0.abs() + g0.abs() * HALF * ulp_bf16(x0), t1.abs() + g1.abs() * HALF * ulp_bf16(x1)      # scale times the ROUNDED x * rrms
+    mags = [(st(x0, x0), st(g0.abs() * ca, g0.abs() * sa)), (st(tm0, tm0), st(ca.expand_as(t0), sa.expand_as(t0))),
+            (st(x1, x1), st(g1.abs() * sa, g1.abs() * ca)), (st(tm1, tm1), st(sa.expand_as(t1), ca.expand_as(t1))), STORE]
+    f32 = (2.0 + 12 / 2 + 3.0) * EPS24 * st(ca * t0.abs() + sa * t1.abs(), sa * t0.abs() + ca * t1.abs())
+    return ref, mags, f32
+
+
+# ---------------------------------------------------------------- attention (attention.hip, attention64.hip)
+def attention_route(q="stored", partial=None, pieces=0):
+    """q        how the kernel treats the query rows it reads:
+                  "stored"     attention.hip (variants 0-7): the bf16 rows as they are, the scale c applied to the f32 logit
+                  "scale"      attention64.hip after the pre-pass: bf16(c * q), one rounding ("rounded to bf16 once more")
+                  "prescaled"  VcAttention.q_prescaled: the rows hold c * q already; the reference takes them as they are (c = 1)
+       partial  None, "f32" (attention.hip's tail split: un-normalised f32 pieces) or "f16" (attention64.hip: pieces normalised
+                by their own row sums and stored as f16, attn_plan.h PART64_O_BYTES)
+       pieces   an upper bound of the number of pieces of one item (0: one per 64-key tile)"""
+    assert q in ("stored", "scale", "prescaled") and partial in (None, "f32", "f16")
+    return {"q": q, "partial": partial, "pieces": pieces}
+
+
+def attention_case(q, k, v, live, route, rows=None, chunk=32, q_err=None):
+    """One (sample, head): q [Lq, 128], k, v [Lk, 128] (the bf16 values the kernel reads), live [Lk] bool (keys below kv_len and
+    outside kv_gap), route = attention_route(...); rows: the query rows to evaluate (default all).  Masked QUERY rows are the
+    caller's: they must be exactly 0.  fp64: s = c q.k (log2 domain, c = 128^-0.5 * log2(e), 1 on the prescaled route),
+    w = softmax2(s) over the live keys, o = sum_j w_j v_j.  Budget per element (i, d), to first order:
+      logit      an error dl_j of logit j moves o by ln2 * w_j * dl_j * (v_j - o):  ln2 * sum_j w_ij dl_ij |v_jd - o_id| with
+                   dl_ij = sum_d' HALF * ulp_bf16(c q_id') |k_jd'|                 the query's one rounding after the scale (route
+                                                                                  "scale"; absent for "stored" and "prescaled")
+                         + 130 * EPS_MFMA * (sum_d' |c q_id' k_jd'| + m_i)        128 products summed by the matrix pipe in its own
+                           order, the reference point m (attention64: subtracted by a 9th k-step of the same accumulator;
+                           attention.hip: one f32 multiply by c and one subtract) - m_i = (1 + 2^-8) max_j |s_ij| bounds any
+                           reference point the online softmax can hold.  The VALUE of m cancels (a softmax is the same function for
+                           any reference point, and attention64 keeps m bf16-exact so that what the pipe subtracts is what the row
+                           sum and O are scaled by); what does not cancel is that the accumulator's additions are rounded at
+                           magnitudes that include m, which is why m_i stands beside the products in this term
+                   q_err (optional, [rows, 128], with route "prescaled" and q given in fp64): the queries are not an input but
+                   the result of a norm inside the kernel (attention64's q_norm); q is then the fp64 value of that norm
+                   (qknorm_rope_case(prescale=True)) and q_err its per-element budget: dl_ij += sum_d' q_err_id' |k_jd'|
+      probability P goes to the P.V product as bf16 while the row sum l adds the f32 probabilities: only the numerator is rounded,
+                 HALF * 2^-7 * sum_j w_ij |v_jd| - the reference point is deferred (P may sit up to 2^8 above 1), so P's binade is
+                 not known and the worst relative size of half an ulp, 2^-8 = 2^-7 / 2, is taken.  The 1/64 in HALF covers v_exp
+      sums       (n_live + 64) * EPS_MFMA * sum_j w_ij |v_jd|: the f32 sums of O (matrix pipe) and l over n_live keys, the
+                 rescales of the online softmax (at most one per 64-key tile, far fewer), the reciprocal and the final multiply
+      tail split "f16": 2^-11 * sum_j w_ij |v_jd| + 2^-25 (half an f16 ulp of every normalised piece, half the f16 subnormal
+                 spacing), and for both kinds (4 * pieces + 2) * EPS_MFMA * sum_j w_ij |v_jd| for the merge (per piece one exp2,
+                 the weight's multiply and two FMAs; the reciprocal and the final multiply)
+      store      one rounding at |o| + everything above (STORE)
+    The [rows, Lk, 128] intermediate of the logit term is built `chunk` query rows at a time."""
+    dev = q.device
+    q64, k64, v64 = q.to(torch.float64), k.to(torch.float64), v.to(torch.float64)
+    if rows is not None:
+        q64 = q64[rows]
+    c = 1.0 if route["q"] == "prescaled" else QK_PRESCALE
+    live = live.to(dev)
+    n_live = int(live.sum())
+    cq = c * q64
+    s = (cq @ k64.t()).masked_fill(~live[None, :], -math.inf)
+    w = torch.softmax(s * math.log(2.0), dim=-1)
+    o = w @ v64
+    wv = w @ v64.abs()
+    m_i = (1.0 + 2.0 ** -8) * s.masked_fill(~live[None, :], 0.0).abs().amax(-1, keepdim=True)
+    dl = 130.0 * EPS_MFMA * (cq.abs() @ k64.abs().t() + m_i)
+    if route["q"] == "scale":
+        dl = dl + (HALF * ulp_bf16(cq)) @ k64.abs().t()
+    if q_err is not None:
+        assert route["q"] == "prescaled"
+        dl = dl + q_err.to(torch.float64) @ k64.abs().t()
+    wdl = w * dl
+    logit = torch.empty_like(o)
+    for r0 in range(0, q64.shape[0], chunk):
+        r1 = min(r0 + chunk, q64.shape[0])
+        logit[r0:r1] = torch.einsum("rj,rjd->rd", wdl[r0:r1], (v64[None, :, :] - o[r0:r1, None, :]).abs())
+    f32 = math.log(2.0) * logit + (HALF * 2.0 ** -7 + (n_live + 64) * EPS_MFMA) * wv
+    if route["partial"] is not None:
+        pieces = route["pieces"] or -(-k64.shape[0] // 64)
+        f32 = f32 + (4 * pieces + 2) * EPS_MFMA * wv
+        if route["partial"] == "f16":
+            f32 = f32 + 2.0 ** -11 * wv + 2.0 ** -25
+    return o, [STORE], f32
+
+
+def gemm_inputs(M, N, K, kind, seed=0):
+    """(a [M, K], w [N, K], bias [N], res [M, N], gate [N]) bf16 on the CPU.  kind:
+      "cancel"  seeded normal a, w scaled by K^-1/2: acc cancels, the f32 term of the budget matters
+      "same"    |a|, |w|, |bias|: nothing cancels, the budget is close to one rounding
+      "exact"   integer-valued a (0, +-1 .. +-3), w (0, +-1, +-2), bias (-8 .. 8), sparse enough that sum_k |a w| + |b| <= 255 for
+                every output (the caller asserts it): every partial sum is an integer below 2^8 in any order, so EPI_BIAS is exact"""
+    g = torch.Generator().manual_seed(1000 * seed + M + 7 * N + 13 * K)
+    if kind == "exact":
+        p = min(0.5, 4.0 / math.sqrt(K))
+        rs = lambda *shape: torch.where(torch.rand(*shape, generator=g) < 0.5, -1.0, 1.0)  # noqa: E731
+        a = torch.randint(1, 4, (M, K), generator=g).float() * rs(M, K) * (torch.rand(M, K, generator=g) < p)
+        w = torch.randint(1, 3, (N, K), generator=g).float() * rs(N, K) * (torch.rand(N, K, generator=g) < p)
+        bias = torch.randint(-8, 9, (N,), generator=g).float()
+    else:
+        a, w, bias = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * K ** -0.5, torch.randn(N, generator=g)
+        if kind == "same":
+            a, w, bias = a.abs(), w.abs(), bias.abs()
+    res, gate = torch.randn(M, N, generator=g), torch.randn(N, generator=g)
+    return tuple(t.to(torch.bfloat16) for t in (a, w, bias, res, gate))
+
+
+def rope_angles(L, seed=0):
+    """[L, 64, 2] f32 (cos, sin): seeded angles, with row 0 at angle 0 (sin = 0), row 1 (if any) at pi / 2 (cos ~ 0: 6e-17 in
+    fp64, 4e-8 after the f32 rounding) and row 2 at pi"""
+    g = torch.Generator().manual_seed(77 + L + seed)
+    ang = torch.rand(L, 64, generator=g, dtype=torch.float64) * 2 * math.pi
+    for i, v in enumerate((0.0, math.pi / 2, math.pi)[:L]):
+        ang[i] = v
+    return torch.stack([torch.cos(ang), torch.sin(ang)], -1).float().contiguous()
+
+
+def attn_inputs(L, kind, seed=0):
+    """(q, k, v) [L, 128] bf16 on the CPU for one (sample, head).  "normed": |q| = |k| = sqrt(128) as after QKNorm (what the
+    bounded form requires); "peaked": normed, and each query is partly aligned with one key through a seeded permutation (q_i =
+    normed(0.5 k_perm(i) + noise): logit ~ 6 in the log2 domain above the rest), so a few keys carry most of the weight."""
+    g = torch.Generator().manual_seed(31 * L + seed)
+    nrm = lambda t: t / t.pow(2).mean(-1, keepdim=True).sqrt()  # noqa: E731
+    q, k, v = torch.randn(L, 128, generator=g), nrm(torch.randn(L, 128, generator=g)), torch.randn(L, 128, generator=g)
+    if kind == "peaked":
+        q = 0.5 * k[torch.randperm(L, generator=g)] + q
+    else:
+        assert kind == "normed"
+    return nrm(q).to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
+
+
+def live_mask(L, kv_len=None, gap=None):
+    live = torch.ones(L, dtype=torch.bool)
+    if kv_len is not None:
+        live[kv_len:] = False
+    if gap is not None:
+        live[gap[0]:gap[1]] = False
+    return live
+
+
+def one_hot_inputs(L, live, seed=0):
+    """(q, k [L, 128], partner [L], v(head) -> [L, 128]) bf16 on the CPU: q_i = 4 u_partner(i), k_j = u_j with seeded +-1 vectors u;
+    `partner` is a seeded permutation of the live indices (every live key is some live query's partner; a masked query row gets a
+    live key too).  The aligned logit is 128 * bf16(4 c) = 65.5 in the log2 domain EXACTLY (4 c = 0.5101 rounds to 131 / 256, and the
+    same value comes out of c * 512 in f32), a bf16 value: the running max lands on it and P = 1; without a running max P = 2^65.5,
+    whose bf16 rounding is 2^-13 away - in both cases the output row rounds to the partner's V row bit for bit.  Every MASKED key
+    gets k = 1.5 u_partner(i) of a seeded live query i (logit 98.25 <= 100, above i's true partner) and V = 64: a leak is a gross
+    error.  v(head): magnitudes 1 + n / 128, seeded signs, rows distinct (asserted)."""
+    g = torch.Generator().manual_seed(977 * L + seed)
+    u = torch.where(torch.rand(L, 128, generator=g) < 0.5, -1.0, 1.0)
+    idx = live.nonzero().flatten()
+    dead = (~live).nonzero().flatten()
+    partner = torch.zeros(L, dtype=torch.long)
+    partner[idx] = idx[torch.randperm(len(idx), generator=g)]
+    partner[dead] = idx[torch.randint(len(idx), (len(dead),), generator=g)]
+    k = u.clone()
+    k[dead] = 1.5 * u[partner[idx[torch.randint(len(idx), (len(dead),), generator=g)]]]
+
+    def v(head):
+        gv = torch.Generator().manual_seed(977 * L + seed + 31 * (head + 1))
+        x = (1.0 + torch.randint(0, 128, (L, 128), generator=gv) / 128.0) * torch.where(torch.rand(L, 128, generator=gv) < 0.5, -1.0, 1.0)
+        assert torch.unique(x, dim=0).shape[0] == L
+        x[dead] = 64.0
+        return x.to(torch.bfloat16)
+    return (4.0 * u[partner]).to(torch.bfloat16), k.to(torch.bfloat16), partner, v
+
+
+def one_hot_stray_weight(q, k, live, partner):
+    """fp64: the largest share of a live row's softmax weight that keys other than its partner hold"""
+    s = (QK_PRESCALE * q.to(torch.float64)) @ k.to(torch.float64).t()
+    s = s.masked_fill(~live.to(s.device)[None, :], -math.inf)
+    w = torch.softmax(s * math.log(2.0), dim=-1)
+    own = w.gather(1, partner.to(s.device)[:, None])[:, 0]
+    return float((1.0 - own)[live.to(s.device)].max())

@@ -1,5 +1,6 @@
-"""tests/budget.py on a machine without a GPU: every budget the glue-kernel tests (test_glue_gpu.py) apply is one that torch's
-own CPU result meets at the same shapes, and one that a subtly wrong result does not meet."""
+"""tests/budget.py on a machine without a GPU: every budget the glue-kernel tests (test_glue_gpu.py) and the hot-path tests
+(test_hotpath_gpu.py: GEMM, ln_modulate, QKNorm + RoPE, attention) apply is one that torch's own CPU result - or an f32 emulation
+of the kernel's rounding sequence - meets at the same shapes, and one that a subtly wrong result does not meet."""
 import math
 
 import pytest
@@ -135,3 +136,317 @@ def test_torch_gaussian_sample_meets_budget():
     got = (zs.float() * torch.tensor(0.3611, dtype=torch.float32)).to(torch.bfloat16)
     ref, mags, _ = B.gaussian_case(mean, logvar, noise, 0.3611, 0.1159)
     B.assert_within_budget(got, ref, len(mags), mags, what="gaussian_sample")
+
+
+# ================================================================ the hot path: GEMM, block norms, attention
+def old_check_passes(got, ref, tol=2e-2):
+    """the criterion of check() in tests/test_ops_gpu.py: |err| <= tol * max|ref| and relative L2 <= tol"""
+    got, ref = got.double(), ref.double()
+    return bool((got - ref).abs().max() <= tol * (ref.abs().max() + 1e-12)) and bool((got - ref).norm() / ref.norm() <= tol)
+
+
+def rb(x):
+    return x.to(torch.bfloat16).float()
+
+
+def gemm_epilogue(y, epi, res, gate):
+    """each epilogue's bf16 sequence on an f32 acc + bias (gemm.hip header), torch f32 ops"""
+    t = rb(y)
+    if epi == 1:
+        return rb(F.gelu(t, approximate="tanh"))
+    if epi == 3:
+        return rb(F.silu(t))
+    if epi == 2:
+        g = gate.float() if gate.dim() == 2 else gate.float()[None, :]
+        return rb(res.float() + rb(g * t))
+    return t
+
+
+def gemm_sliced(a, w, bias, S, bias_first=True, bias_every_slice=False, drop=None):
+    """the f32 product summed as S K-slices of whole 64-wide K-tiles (unequal where nk % S != 0), the bias in front or behind"""
+    K = a.shape[1]
+    nk = K // 64
+    cuts = [64 * (s * nk // S) for s in range(S + 1)]
+    acc = torch.zeros(a.shape[0], w.shape[0])
+    if bias_first:
+        acc = acc + bias.float()
+    for s in range(S):
+        part = a[:, cuts[s]:cuts[s + 1]].float() @ w[:, cuts[s]:cuts[s + 1]].float().t()
+        if bias_every_slice and s > 0:
+            part = part + bias.float()
+        acc = acc + part
+    if not bias_first:
+        acc = acc + bias.float()
+    return acc
+
+
+HOT_GEMM_SHAPES = [(1, 8, 64), (37, 64, 128), (129, 200, 192), (257, 264, 320), (37, 200, 1024)]
+
+
+@pytest.mark.parametrize("kind", ["cancel", "same", "exact"])
+@pytest.mark.parametrize("M,N,K", HOT_GEMM_SHAPES)
+def test_torch_gemm_meets_budget(M, N, K, kind):
+    """torch's f32 matmul + each epilogue's bf16 sequence, the same product summed in 2, 3 and 8 K-slices, bias first and last"""
+    a, w, bias, res, gate = B.gemm_inputs(M, N, K, kind)
+    for epi in (0, 1, 2, 3, 4):
+        ref, mags, f32 = B.gemm_case(a, w, bias, epi, res, gate)
+        accs = [a.float() @ w.float().t() + bias.float()]
+        for S in (2, 3, 8):
+            if K // 64 >= S:
+                accs += [gemm_sliced(a, w, bias, S, True), gemm_sliced(a, w, bias, S, False)]
+        if epi == 1:      # torch's 0.5 x (1 + tanh u) loses 2^-24 |x| where tanh u ~ -1 (test_torch_activations_meet_budget): torch's alone
+            f32 = f32 + 2.0 * B.EPS24 * mags[0][0].abs()
+        for i, y in enumerate(accs):
+            got = gemm_epilogue(y, epi, res, gate)
+            B.assert_within_budget(got, ref, len(mags), mags, f32, what=f"gemm {M}x{N}x{K} {kind} epi {epi} order {i}")
+            if kind == "exact" and epi in (0, 4):
+                mass = a.double().abs() @ w.double().abs().t() + bias.double().abs()
+                assert float(mass.max()) <= 255.0
+                assert torch.equal(got.double(), ref)
+
+
+def test_gemm_budget_rejects_subtle_faults():
+    # one product dropped from one output element at K = 256 (the median |a w| of that element: ~0.03 beside |t| ~ 1)
+    a, w, bias, res, gate = B.gemm_inputs(37, 64, 256, "cancel")
+    ref, mags, f32 = B.gemm_case(a, w, bias, 0)
+    acc = a.float() @ w.float().t() + bias.float()
+    prod = a[5].float() * w[9].float()
+    kk = int(prod.abs().argsort()[128])
+    bad = acc.clone()
+    bad[5, 9] -= prod[kk]
+    B.assert_within_budget(rb(acc), ref, 1, mags, f32)
+    assert old_check_passes(rb(bad), ref)
+    with pytest.raises(AssertionError):
+        B.assert_within_budget(rb(bad), ref, 1, mags, f32)
+    # one 64-wide K-tile dropped from one 4-column group at K = 1024 (row 3, columns 8 .. 11, K-tile 5): errors ~ N(0, 1/16)
+    a, w, bias, res, gate = B.gemm_inputs(37, 200, 1024, "cancel")
+    ref, mags, f32 = B.gemm_case(a, w, bias, 0)
+    acc = a.float() @ w.float().t() + bias.float()
+    bad = acc.clone()
+    bad[3, 8:12] -= a[3, 320:384].float() @ w[8:12, 320:384].float().t()
+    with pytest.raises(AssertionError):
+        B.assert_within_budget(rb(bad), ref, 1, mags, f32)
+    assert not old_check_passes(rb(bad), ref)      # check() catches this one: one of the four errors exceeds 2e-2 max|ref| ~ 0.1
+    # the bias added to both slices of a two-way split: every element off by its bias - check() catches that too (relative L2 ~ 0.7)
+    bad = gemm_sliced(a, w, bias, 2, True, bias_every_slice=True)
+    assert not old_check_passes(rb(bad), ref)
+    with pytest.raises(AssertionError):
+        B.assert_within_budget(rb(bad), ref, 1, mags, f32)
+    # the gate of batch element 0 used for a row of batch element 1 (GATE_RES, rows_per_batch = 20: row 20 is the first of batch 1)
+    gates = torch.stack([gate, gate.flip(0)])
+    grow = gates[(torch.arange(37) >= 20).long()]
+    ref, mags, f32 = B.gemm_case(a, w, bias, 2, res, grow)
+    B.assert_within_budget(gemm_epilogue(acc, 2, res, grow), ref, len(mags), mags, f32)
+    wrong = grow.clone()
+    wrong[20] = gates[0]
+    bad = gemm_epilogue(acc, 2, res, wrong)
+    with pytest.raises(AssertionError):
+        B.assert_within_budget(bad, ref, len(mags), mags, f32)
+    # (one row of 37 with another gate: errors of |g0 - g1| |t| ~ 1 - check() catches it on the max criterion)
+    assert not old_check_passes(bad, ref)
+
+
+def ln_modulate_f32(x, shift, scale, cols=None):
+    """F.layer_norm + modulate as norm.hip rounds it; cols: the (faulty) number of columns the mean is taken over"""
+    xf = x.float()
+    D = x.shape[1]
+    if cols is None:
+        ln = F.layer_norm(xf, (D,), eps=1e-6)
+    else:
+        mean = xf[:, :cols].mean(-1, keepdim=True)
+        ln = (xf - mean) * torch.rsqrt(((xf - mean) ** 2).mean(-1, keepdim=True) + 1e-6)
+    return rb(rb(1 + scale.float()) * ln + shift.float())
+
+
+@pytest.mark.parametrize("D", [8, 256, 3072, 4096])
+def test_torch_ln_modulate_meets_budget(D):
+    """F.layer_norm + modulate at a DC offset of 16 standard deviations (norm_inputs): the offset test_hotpath_gpu.py holds the
+    kernel to is one that plain f32 torch meets; and the mean taken over D - 8 columns does not."""
+    for rows in (1, 3, 10):
+        x, w, b = B.norm_inputs(rows, D)
+        scale = (w.float() - 1.25).to(torch.bfloat16)            # in [-0.75, 0.75): 1 + scale is not a bf16 value
+        ref, mags, f32 = B.ln_modulate_case(x, b, scale)
+        B.assert_within_budget(ln_modulate_f32(x, b, scale), ref, 1, mags, f32, what=f"ln_modulate D={D} rows={rows}")
+        if D >= 256:
+            bad = ln_modulate_f32(x, b, scale, cols=D - 8)
+            assert old_check_passes(bad, ref)
+            with pytest.raises(AssertionError):
+                B.assert_within_budget(bad, ref, 1, mags, f32)
+
+
+def qkn_inputs(L, H, seed=0):
+    g = torch.Generator().manual_seed(5 * L + H + seed)
+    x = torch.randn(L, 3 * H * 128, generator=g)
+    x[L // 2, :128] *= 1e-4                                        # one head row of very small values against the 1e-6 epsilon
+    sc = [(1 + 0.1 * torch.randn(128, generator=g)).to(torch.bfloat16) for _ in range(2)]
+    return x.to(torch.bfloat16), sc[0], sc[1]
+
+
+@pytest.mark.parametrize("L,H", [(1, 1), (40, 3), (64, 1), (333, 9)])
+def test_qknorm_rope_ref_meets_budget(L, H):
+    from tests import ref_ops as R
+    qkv, qs, ks = qkn_inputs(L, H)
+    rope = B.rope_angles(L)
+    qr, kr, _ = R.qknorm_rope_ref(qkv, qs, ks, rope, H)
+    x = qkv.reshape(L, 3, H, 128)
+    for got, part, sc in ((qr, 0, qs), (kr, 1, ks)):
+        ref, mags, f32 = B.qknorm_rope_case(x[:, part], sc, rope)
+        B.assert_within_budget(got, ref, len(mags), mags, f32, what=f"qknorm_rope L={L} H={H} part={part}")
+    # QKN_QPRE: the rotated value times 128^-0.5 * log2(e), rounded once (the f32 sequence of qknorm_rope8)
+    t = x[:, 0].float()
+    t = rb(rb(t * torch.rsqrt((t * t).mean(-1, keepdim=True) + 1e-6)) * qs.float()).reshape(L, H, 64, 2)
+    co, si = rope[:, None, :, 0], rope[:, None, :, 1]
+    c32 = torch.tensor(B.QK_PRESCALE, dtype=torch.float32)
+    got = rb(torch.stack([(co * t[..., 0] - si * t[..., 1]) * c32, (si * t[..., 0] + co * t[..., 1]) * c32], -1).reshape(L, H, 128))
+    ref, mags, f32 = B.qknorm_rope_case(x[:, 0], qs, rope, prescale=True)
+    B.assert_within_budget(got, ref, len(mags), mags, f32, what=f"qknorm_rope prescaled L={L} H={H}")
+
+
+def test_qknorm_budget_rejects_scale_of_the_other_stream():
+    """the second stream's scale (2 bf16 ulps away: 1.6 %) used one row too early at `split`: check() passes it"""
+    from tests import ref_ops as R
+    L, H, split = 40, 3, 16
+    qkv, qs, _ = qkn_inputs(L, H)
+    qs2 = (qs.float() * (1 + 2.0 ** -6)).to(torch.bfloat16)
+    rope = B.rope_angles(L)
+    rows = lambda s: torch.where((torch.arange(L) < s)[:, None, None], qs.float()[None, None], qs2.float()[None, None]).to(torch.bfloat16)  # noqa: E731
+    qa, _, _ = R.qknorm_rope_ref(qkv, qs, qs, rope, H)
+    qb, _, _ = R.qknorm_rope_ref(qkv, qs2, qs2, rope, H)
+    ref, mags, f32 = B.qknorm_rope_case(qkv.reshape(L, 3, H, 128)[:, 0], rows(split), rope)
+    B.assert_within_budget(torch.cat([qa[:split], qb[split:]]), ref, len(mags), mags, f32)
+    bad = torch.cat([qa[:split - 1], qb[split - 1:]])
+    assert old_check_passes(bad, ref)
+    with pytest.raises(AssertionError):
+        B.assert_within_budget(bad, ref, len(mags), mags, f32)
+
+
+def attn_emulate(q, k, v, live, qmode, pieces=1, l_fault=None):
+    """f32 emulation of the kernels' rounding sequence for one (sample, head): the query scaled and rounded once ("scale"), or
+    the scale applied to the f32 logit ("stored"), or none ("prescaled"); P = 2^(s - m) rounded to bf16 for P.V while l adds the
+    f32 probabilities; bf16 store.  pieces > 1: the keys cut into that many ranges of whole 64-key tiles, each piece normalised by
+    its own l and rounded to f16, combined as merge_fold64 does.  l_fault = (piece, key): that piece's l is off by key's weight."""
+    c32 = torch.tensor(B.QK_PRESCALE, dtype=torch.float32)
+    qf, kf, vf = q.float(), k.float(), v.float()
+    if qmode == "scale":
+        s = rb(qf * c32) @ kf.t()
+    elif qmode == "stored":
+        s = (qf @ kf.t()) * c32
+    else:
+        s = qf @ kf.t()
+    s = s.masked_fill(~live[None, :], -math.inf)
+    nkt = -(-k.shape[0] // 64)
+    cuts = [64 * (p * nkt // pieces) for p in range(pieces + 1)]
+    parts = []
+    for p in range(pieces):
+        sp = s[:, cuts[p]:cuts[p + 1]]
+        m = sp.amax(-1, keepdim=True).clamp_min(-1e30)
+        m = (m.to(torch.bfloat16).float() + 0.0)                       # attention64 keeps its reference point bf16-representable
+        pe = torch.exp2(sp - m)
+        l = pe.sum(-1, keepdim=True)
+        if l_fault is not None and l_fault[0] == p:
+            l = l + pe[:, l_fault[1] - cuts[p]][:, None]
+        parts.append((m, l, rb(pe) @ vf[cuts[p]:cuts[p + 1]]))
+    if pieces == 1:
+        m, l, o = parts[0]
+        return (o / l).to(torch.bfloat16)
+    mt = torch.stack([m for m, _, _ in parts]).amax(0)
+    acc, wsum = 0.0, 0.0
+    for m, l, o in parts:
+        wgt = l * torch.exp2(m - mt)
+        on = torch.where(l > 0, o / l, torch.zeros_like(o)).to(torch.float16).float()
+        acc, wsum = acc + wgt * on, wsum + wgt
+    return (acc / wsum).to(torch.bfloat16)
+
+
+ATTN_CPU_CASES = [(1, None, None), (63, None, None), (64, None, None), (65, None, None), (200, None, None), (333, 301, None),
+                  (320, None, (0, 128)), (512, 470, (100, 230))]
+
+
+@pytest.mark.parametrize("kind", ["normed", "peaked"])
+@pytest.mark.parametrize("L,kv_len,gap", ATTN_CPU_CASES)
+def test_attention_emulation_meets_budget(L, kv_len, gap, kind):
+    q, k, v = B.attn_inputs(L, kind)
+    live = B.live_mask(L, kv_len, gap)
+    for qmode in ("stored", "scale", "prescaled"):
+        ref, mags, f32 = B.attention_case(q, k, v, live, B.attention_route(qmode))
+        B.assert_within_budget(attn_emulate(q, k, v, live, qmode), ref, 1, mags, f32, what=f"attention L={L} {kind} q={qmode}")
+    L2 = 1000                                                            # 16 key tiles: two and seven key ranges (no masks: attn_plan.hip)
+    if L == 200:
+        q, k, v = B.attn_inputs(L2, kind)
+        live = B.live_mask(L2)
+        for pieces in (2, 7):
+            ref, mags, f32 = B.attention_case(q, k, v, live, B.attention_route("prescaled", "f16", pieces))
+            B.assert_within_budget(attn_emulate(q, k, v, live, "prescaled", pieces), ref, 1, mags, f32, what=f"attention {pieces} pieces {kind}")
+
+
+@pytest.mark.parametrize("L,kv_len,gap", [(65, 65, None), (333, 301, (40, 100)), (1000, 1000, (100, 230))])
+def test_attention_budget_rejects_one_key(L, kv_len, gap):
+    """An off-by-one at kv_len, at a kv_gap edge or at a tail-piece boundary moves output (i, d) by w_ij |v_jd - o_id|.  Half of
+    V's columns carry a common offset of 4 (outputs ~ 4, which set max|ref| and the L2 norm), the other half are zero-mean.
+    L = 65: the faulted key has a quarter of the norm (an even weight of ~ 1.5 % in every row): check() passes every fault, the
+    per-element budget none.  L = 333, 1000: a key of even weight (0.3 %, 0.1 %) is inside what the bf16 rounding of P allows in the
+    worst case (HALF * 2^-7 sum w |v|), so the keys are left as seeded - heavy in some rows - and the budget rejects every fault.
+    check() passes all of those too, except key 300 dropped at L = 333 (heavy enough in one row for its max criterion) and the
+    tail piece's l at L = 1000; each outcome is asserted."""
+    q, k, v = B.attn_inputs(L + 1, "normed")
+    v = torch.cat([v[:, :64].float() + 4.0, v[:, 64:].float()], 1).to(torch.bfloat16)
+    live = B.live_mask(L + 1, kv_len, gap)
+    route = B.attention_route("scale")
+    faults = {"last live key dropped": (kv_len - 1, False), "key kv_len let in": (kv_len, True)}
+    if gap is not None:
+        faults["key at gap_hi dropped"] = (gap[1], False)
+    for name, (j, val) in faults.items():
+        kk = k.clone()
+        if L == 65:
+            kk[j] = (kk[j].float() * 0.25).to(torch.bfloat16)
+        ref, mags, f32 = B.attention_case(q, kk, v, live, route)
+        B.assert_within_budget(attn_emulate(q, kk, v, live, "scale"), ref, 1, mags, f32)
+        wrong = live.clone()
+        wrong[j] = val
+        bad = attn_emulate(q, kk, v, wrong, "scale")
+        assert old_check_passes(bad[live], ref[live]) == ((L, j) != (333, 300)), name
+        with pytest.raises(AssertionError):
+            B.assert_within_budget(bad[live], ref[live], 1, mags, f32[live], what=name)
+    if L == 1000:      # one tail piece's l off by one key's weight (piece 3 of 7, key 500): check() catches this one on its max criterion too
+        live = B.live_mask(L + 1, kv_len)
+        route = B.attention_route("prescaled", "f16", 7)
+        ref, mags, f32 = B.attention_case(q, k, v, live, route)
+        B.assert_within_budget(attn_emulate(q, k, v, live, "prescaled", 7), ref, 1, mags, f32)
+        bad = attn_emulate(q, k, v, live, "prescaled", 7, l_fault=(3, 500))
+        assert not old_check_passes(bad[live], ref[live])
+        with pytest.raises(AssertionError):
+            B.assert_within_budget(bad[live], ref[live], 1, mags, f32[live])
+
+
+@pytest.mark.parametrize("L,H", [(65, 2), (333, 1)])
+def test_attention_emulation_with_in_kernel_query_norm_meets_budget(L, H):
+    """attention64's q_norm route: the reference query is the fp64 value of QKNorm + RoPE times c, its error allowance the budget of
+    qknorm_rope_case(prescale=True) (attention_case q_err); the emulation feeds the f32 sequence of qknorm_rope8 to the attention."""
+    qkv, qs, _ = qkn_inputs(L, H)
+    rope = B.rope_angles(L)
+    x = qkv.reshape(L, 3, H, 128)
+    t = x[:, 0].float()
+    t = rb(rb(t * torch.rsqrt((t * t).mean(-1, keepdim=True) + 1e-6)) * qs.float()).reshape(L, H, 64, 2)
+    co, si = rope[:, None, :, 0], rope[:, None, :, 1]
+    c32 = torch.tensor(B.QK_PRESCALE, dtype=torch.float32)
+    qpre = torch.stack([(co * t[..., 0] - si * t[..., 1]) * c32, (si * t[..., 0] + co * t[..., 1]) * c32], -1).reshape(L, H, 128).to(torch.bfloat16)
+    qref, mags, f32 = B.qknorm_rope_case(x[:, 0], qs, rope, prescale=True)
+    qerr = B.budget(qref, len(mags), mags, f32)
+    live = B.live_mask(L, L - 7, (3, 20))
+    for h in range(H):
+        k, v = x[:, 1, h], x[:, 2, h]
+        ref, m, f = B.attention_case(qref[:, h], k, v, live, B.attention_route("prescaled"), q_err=qerr[:, h])
+        B.assert_within_budget(attn_emulate(qpre[:, h], k, v, live, "prescaled"), ref, 1, m, f, what=f"attention q_norm L={L} h={h}")
+
+
+def test_one_hot_inputs_hold_their_precondition():
+    """budget.one_hot_inputs: every live row's stray weight is far below 2^-12, every live key is some live row's partner, and the f32
+    emulation returns the partner's V row bit for bit with and without a running max."""
+    for L, kv_len, gap in ATTN_CPU_CASES:
+        live = B.live_mask(L, kv_len, gap)
+        q, k, partner, vf = B.one_hot_inputs(L, live)
+        assert B.one_hot_stray_weight(q, k, live, partner) <= 2.0 ** -12
+        assert sorted(partner[live].tolist()) == live.nonzero().flatten().tolist()
+        v = vf(0)
+        for qmode in ("stored", "scale"):
+            assert B.bits_equal(attn_emulate(q, k, v, live, qmode)[live], v[partner][live])
