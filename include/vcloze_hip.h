@@ -383,13 +383,30 @@ int vc_gaussian_sample(const void* moments, int32_t Cp, const void* noise, void*
  * rmsnorm:    y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))), f32 statistics, D <= 4096   (T5LayerNorm)
  * layernorm:  y = bf16((x - mean) * rstd * w + b), f32 statistics, D <= 4096              (nn.LayerNorm, CLIP)
  * mul / add:  y = bf16(a * b) / bf16(a + b), n % 8 == 0          (T5DenseGatedActDense product; CLIP token + position)
- * quick_gelu: y = bf16(x * bf16(sigmoid(bf16(1.702 * x))))                                (CLIP hidden_act) */
+ * quick_gelu: y = bf16(x * bf16(sigmoid(bf16(1.702 * x))))                                (CLIP hidden_act)
+ * t5_relative_buckets: HOST-ONLY, no device: out HOST [2 L - 1], out[(j - i) + L - 1] = the bucket of relative position key j - query i
+ *             (T5Attention._relative_position_bucket, bidirectional) in the f32 arithmetic transformers runs it in - the table that
+ *             visualcloze_amd/text.py::t5_relative_buckets holds as [L, L].  num_buckets even in 4..128, max_distance > num_buckets / 4.
+ * t5_position_bias: out[h * L + i, j] = table[bucket(j - i), h]: the [H * L, L] bias operand of vc_softmax_rows from
+ *             relative_attention_bias.weight [num_buckets, H] (row stride ld) - a pure gather, bit-exact; the buckets are computed on
+ *             the host as above and travel as kernel arguments (no upload, no allocation).  L % 8 == 0.
+ *             Replaces: buckets -> fancy index -> permute -> contiguous in torch (T5Attention.compute_bias).
+ * clip_embed: out [Lp, D]: rows i < L = bf16(f32(tok[clamp(ids[i])]) + f32(pos[i])) (CLIPTextEmbeddings), rows L..Lp-1 = tok[0] plus a
+ *             position row of zeros (the padding of the 64-row GEMM tiles; causal masking keeps it out of rows < L).  One launch for
+ *             vc_embedding over zero-padded ids + a zeroed position buffer + its first L rows copied in + vc_add: the same bits.
+ * clip_pool:  pooled [D] = hidden[e, :], e = the first i < L with ids[i] == eos_token_id, 0 if there is none (pooler_output of
+ *             CLIPTextTransformer.forward: argmax over (ids == eos)) - on the device, no host read-back. */
 int vc_embedding(const int32_t* ids, const void* table, int64_t ld_table, int32_t vocab, void* out, int32_t L, int32_t D, void* stream);
 int vc_rmsnorm(const void* x, const void* weight, void* y, int32_t rows, int32_t D, float eps, void* stream);
 int vc_layernorm(const void* x, const void* weight, const void* bias, void* y, int32_t rows, int32_t D, float eps, void* stream);
 int vc_mul(const void* a, const void* b, void* y, int64_t n, void* stream);
 int vc_add(const void* a, const void* b, void* y, int64_t n, void* stream);
 int vc_quick_gelu(const void* x, void* y, int64_t n, void* stream);
+int vc_t5_relative_buckets(int32_t L, int32_t num_buckets, int32_t max_distance, int32_t* out);
+int vc_t5_position_bias(const void* table, int64_t ld, int32_t H, int32_t L, int32_t num_buckets, int32_t max_distance, void* out, void* stream);
+int vc_clip_embed(const int32_t* ids, const void* tok, int64_t ld_tok, int32_t vocab, const void* pos, int64_t ld_pos, void* out, int32_t L,
+                  int32_t Lp, int32_t D, void* stream);
+int vc_clip_pool(const int32_t* ids, const void* hidden, int64_t ld, int32_t L, int32_t D, int32_t eos_token_id, void* pooled, void* stream);
 
 /* ---- LoRA merge (ABI 11): LinearLora (models/modules/lora.py:66-67 the factor pair, :92-98 its forward) folded into ONE weight ----
  *   out[o, i]   = bf16( f32(W[o, i]) + scale * acc[o, i] ),   acc[o, i] = sum_k f32(B[o, k]) * f32(A[k, i])
@@ -633,6 +650,65 @@ int vc_vae_encode(void* handle, const void* pixels, int32_t pixels_is_f32, const
                   int64_t ld, int32_t col0, void* stream);
 /* captured plans the handle holds (0..8); -1 for a null handle */
 int vc_vae_plan_count(void* handle);
+
+/* ---- text-encoder handle: T5EncoderModel / CLIPTextModel behind one call (HFEmbedder.forward, models/modules/conditioner.py:5-37;
+ * loaded by load_t5 / load_clip of models/util.py, called from prepare_modified of models/sampling.py) ----
+ * Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up vc_text_create.
+ * One handle is ONE encoder: VC_TEXT_T5 yields last_hidden_state (VcFluxInputs.txt), VC_TEXT_CLIP yields last_hidden_state and
+ * pooler_output (VcFluxInputs.y).  Tokenisation stays host work: the handle takes token ids.  The launch plan is the one
+ * visualcloze_amd/text.py spells in Python over the op-level entry points above (vc_embedding / vc_clip_embed, vc_rmsnorm / vc_layernorm,
+ * vc_gemm - all heads of a layer in one batched launch -, vc_softmax_rows, vc_transpose, vc_mul, vc_quick_gelu, vc_clip_pool): the same
+ * kernels, the same problem structs, the same order, so the two give the same bits.  bf16 everywhere.  The handle holds NO device
+ * memory: tensors are bound by pointer, every activation lives in a caller-provided workspace; it owns the captured hipGraphs.  One
+ * handle per device; not thread-safe per handle; it serves one stream at a time. */
+#define VC_TEXT_T5 1
+#define VC_TEXT_CLIP 2
+typedef struct VcTextConfig {   /* T5Config / CLIPTextConfig of transformers, the fields the encoders read */
+  int32_t kind;                 /* VC_TEXT_T5 or VC_TEXT_CLIP */
+  int32_t vocab_size;
+  int32_t d_model;              /* CLIP: hidden_size.  A multiple of 64, <= 4096 */
+  int32_t d_kv;                 /* the head width, a multiple of 64.  CLIP: 0 or d_model / num_heads */
+  int32_t d_ff;                 /* CLIP: intermediate_size.  A multiple of 64 */
+  int32_t num_layers, num_heads;
+  int32_t num_buckets, max_distance;     /* T5: relative_attention_num_buckets / relative_attention_max_distance */
+  int32_t max_positions, eos_token_id;   /* CLIP: max_position_embeddings; the id whose hidden row is the pooled output */
+  float eps;                    /* layer_norm_epsilon / layer_norm_eps */
+} VcTextConfig;
+/* sizeof(VcTextConfig) as this library was compiled */
+void vc_text_struct_sizes(int32_t out[1]);
+/* host-only: need no device.  A null config, an unknown kind or a width the GEMM does not take is VC_ERR_ARG. */
+int vc_text_create(const VcTextConfig* cfg, void** handle);
+int vc_text_destroy(void* handle);
+/* the tensors the handle expects: the FULL state_dict() keys of the encoder, in order: index 0, 1, ... until VC_ERR_ARG
+ * ("shared.weight", "encoder.block.0.layer.0.SelfAttention.q.weight", ... / "text_model.embeddings.token_embedding.weight", ...,
+ * "text_model.encoder.layers.0.self_attn.k_proj.bias", ...).  T5 lists both tied keys: the plan reads "shared.weight";
+ * "encoder.embed_tokens.weight" is accepted, shape-checked and never read (it need not be bound).  Host-only. */
+int vc_text_weight_name(void* handle, int32_t index, char* name, int32_t namelen);
+/* ptr: the tensor of state_dict key `key`, bf16, contiguous, 16-byte aligned, device memory; shape HOST [ndim] = its shape ([out, in]
+ * of a Linear / Embedding weight, [n] of a bias or norm weight).  Bound BY POINTER as in vc_flux_bind_weight: no copy, no launch, the
+ * caller keeps it alive while bound.  An unknown key, a shape other than the module's or a null pointer is VC_ERR_ARG with the key in
+ * the message.  Binding again drops the captured plans (and T5's bias table is rebuilt by the next encode).  Host-only. */
+int vc_text_bind_tensor(void* handle, const char* key, const void* ptr, const int64_t* shape, int32_t ndim);
+/* L: ids per prompt.  T5: a multiple of 64 (the pipeline pads to 512; padding is attended, as with attention_mask=None).
+ * CLIP: 1..max_positions; the rows are padded to ceil64(L) inside.  Host-only; a bad L is VC_ERR_ARG. */
+int vc_text_workspace_bytes(void* handle, int32_t L, int64_t* bytes);
+/* Carves the activations (x, n, q, k, v, S, V^T, O, the FF pair), the resident ids / output staging buffers and T5's [H L, L] bias
+ * table out of `workspace` (device memory, >= vc_text_workspace_bytes, 256-B aligned, the caller's while encode calls follow), fills
+ * the residual gate of ones and - T5, with relative_attention_bias bound - builds the bias table with vc_t5_position_bias: once per
+ * prepare, not per prompt.  The handle serves ONE prepared (L, workspace) at a time; preparing another and coming back keeps the
+ * captured plans of both.  A workspace that is too small is VC_ERR_ARG and nothing is launched.  The fills are asynchronous on
+ * `stream`: an encode on ANOTHER stream must be ordered behind them by the caller. */
+int vc_text_prepare(void* handle, int32_t L, void* workspace, int64_t workspace_bytes, void* stream);
+/* ids: DEVICE int32 [n_prompts][L].  hidden: [n_prompts][L][d_model] bf16 or NULL.  pooled: CLIP [n_prompts][d_model] bf16 or NULL; T5:
+ * must be NULL (VC_ERR_ARG); hidden and pooled both NULL is VC_ERR_ARG.  An unbound tensor is VC_ERR_STATE naming the first missing key,
+ * a call before vc_text_prepare is VC_ERR_STATE; all of that is checked before anything is launched.  Per prompt: the ids are copied
+ * into the resident buffer, the plan runs, the results are copied out.  With a stream the plan is ONE hipGraph launch - a chain of
+ * kernel nodes over workspace-resident buffers, the copies stay outside it - captured on first use per (workspace, L, stream) after one
+ * un-captured run that sets the kernels' attributes, and kept in a list of 8, most recently used first: rotating ids / hidden / pooled
+ * pointers never re-captures.  stream == NULL runs the same launches un-captured on the default stream. */
+int vc_text_encode(void* handle, const int32_t* ids, int32_t n_prompts, void* hidden, void* pooled, void* stream);
+/* captured plans the handle holds (0..8); -1 for a null handle */
+int vc_text_plan_count(void* handle);
 
 /* ---- hipGraph helpers: capture the launches issued on `stream` between begin/end ---- */
 int vc_stream_create(void** stream);

@@ -151,6 +151,19 @@ int vc_layernorm(const void* x, const void* weight, const void* bias, void* y, i
 int vc_mul(const void* a, const void* b, void* y, int64_t n, void* stream) { return vc_ewise_launch(a, b, y, n, 0, S(stream), ERRBUF); }
 int vc_add(const void* a, const void* b, void* y, int64_t n, void* stream) { return vc_ewise_launch(a, b, y, n, 1, S(stream), ERRBUF); }
 int vc_quick_gelu(const void* x, void* y, int64_t n, void* stream) { return vc_ewise_launch(x, nullptr, y, n, 2, S(stream), ERRBUF); }
+int vc_t5_relative_buckets(int32_t L, int32_t num_buckets, int32_t max_distance, int32_t* out) {
+  return vc_t5_relative_buckets_impl(L, num_buckets, max_distance, out, ERRBUF);
+}
+int vc_t5_position_bias(const void* table, int64_t ld, int32_t H, int32_t L, int32_t num_buckets, int32_t max_distance, void* out, void* stream) {
+  return vc_t5_position_bias_launch(table, ld, H, L, num_buckets, max_distance, out, S(stream), ERRBUF);
+}
+int vc_clip_embed(const int32_t* ids, const void* tok, int64_t ld_tok, int32_t vocab, const void* pos, int64_t ld_pos, void* out, int32_t L,
+                  int32_t Lp, int32_t D, void* stream) {
+  return vc_clip_embed_launch(ids, tok, ld_tok, vocab, pos, ld_pos, out, L, Lp, D, S(stream), ERRBUF);
+}
+int vc_clip_pool(const int32_t* ids, const void* hidden, int64_t ld, int32_t L, int32_t D, int32_t eos_token_id, void* pooled, void* stream) {
+  return vc_clip_pool_launch(ids, hidden, ld, L, D, eos_token_id, pooled, S(stream), ERRBUF);
+}
 int vc_transpose(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int32_t rows, int32_t cols, void* stream) {
   return vc_transpose_launch(src, ld_src, dst, ld_dst, rows, cols, S(stream), ERRBUF);
 }
@@ -258,6 +271,23 @@ int vc_vae_encode(void* handle, const void* pixels, int32_t pixels_is_f32, const
   return vc_vae_encode_impl(handle, pixels, pixels_is_f32, noise, latent, latent_form, ld, col0, S(stream), ERRBUF);
 }
 int vc_vae_plan_count(void* handle) { return vc_vae_plan_count_impl(handle); }
+
+/* ---- text-encoder handle (text_engine.hip) ---- */
+void vc_text_struct_sizes(int32_t out[1]) { out[0] = (int32_t)sizeof(VcTextConfig); }
+int vc_text_create(const VcTextConfig* cfg, void** handle) { return vc_text_create_impl(cfg, handle, ERRBUF); }
+int vc_text_destroy(void* handle) { return vc_text_destroy_impl(handle, ERRBUF); }
+int vc_text_weight_name(void* handle, int32_t index, char* name, int32_t namelen) { return vc_text_weight_name_impl(handle, index, name, namelen, ERRBUF); }
+int vc_text_bind_tensor(void* handle, const char* key, const void* ptr, const int64_t* shape, int32_t ndim) {
+  return vc_text_bind_tensor_impl(handle, key, ptr, shape, ndim, ERRBUF);
+}
+int vc_text_workspace_bytes(void* handle, int32_t L, int64_t* bytes) { return vc_text_workspace_bytes_impl(handle, L, bytes, ERRBUF); }
+int vc_text_prepare(void* handle, int32_t L, void* workspace, int64_t workspace_bytes, void* stream) {
+  return vc_text_prepare_impl(handle, L, workspace, workspace_bytes, S(stream), ERRBUF);
+}
+int vc_text_encode(void* handle, const int32_t* ids, int32_t n_prompts, void* hidden, void* pooled, void* stream) {
+  return vc_text_encode_impl(handle, ids, n_prompts, hidden, pooled, S(stream), ERRBUF);
+}
+int vc_text_plan_count(void* handle) { return vc_text_plan_count_impl(handle); }
 
 /* ---- streams / graphs / events ---- */
 int vc_stream_create(void** stream) {

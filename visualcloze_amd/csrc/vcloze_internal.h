@@ -84,6 +84,15 @@ int vc_zero_fill_launch(void* p, int64_t bytes, hipStream_t s, char* err, int er
 int vc_embedding_launch(const int32_t* ids, const void* table, int64_t ldt, int V, void* out, int L, int D, hipStream_t s, char* err, int errlen);
 int vc_rownorm_launch(const void* x, const void* w, const void* b, void* y, int rows, int D, float eps, int affine_ln, hipStream_t s, char* err, int errlen);
 int vc_ewise_launch(const void* a, const void* b, void* y, int64_t n, int op, hipStream_t s, char* err, int errlen);
+// T5's relative-position buckets as kernel arguments: the bucket of distance d >= max_exact is max_exact + #{k : at[k] <= d}
+constexpr int VC_T5_MAX_STEPS = 31;      // num_buckets <= 128
+struct VcT5Steps { int32_t n; int32_t at[VC_T5_MAX_STEPS]; };
+int vc_t5_relative_buckets_impl(int L, int num_buckets, int max_distance, int32_t* out, char* err, int errlen);
+int vc_t5_position_bias_launch(const void* table, int64_t ld, int H, int L, int num_buckets, int max_distance, void* out, hipStream_t s,
+                               char* err, int errlen);
+int vc_clip_embed_launch(const int32_t* ids, const void* tok, int64_t ldt, int V, const void* pos, int64_t ldp, void* out, int L, int Lp, int D,
+                         hipStream_t s, char* err, int errlen);
+int vc_clip_pool_launch(const int32_t* ids, const void* hidden, int64_t ld, int L, int D, int eos, void* pooled, hipStream_t s, char* err, int errlen);
 int vc_conv3x3_launch(const void* x, const void* w, const void* bias, void* out, int64_t ldc, const void* res, int64_t ldres,
                       const void* gate, int H, int W, int C, int O, int mode, hipStream_t s, char* err, int errlen);
 int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
@@ -125,3 +134,13 @@ int vc_vae_decode_impl(void* handle, const void* latent, int32_t latent_form, in
 int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t latent_form, int64_t ld,
                        int32_t col0, hipStream_t s, char* err, int errlen);
 int vc_vae_plan_count_impl(void* handle);
+
+// text_engine.hip: the text-encoder handle
+int vc_text_create_impl(const VcTextConfig* cfg, void** handle, char* err, int errlen);
+int vc_text_destroy_impl(void* handle, char* err, int errlen);
+int vc_text_weight_name_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen);
+int vc_text_bind_tensor_impl(void* handle, const char* key, const void* ptr, const int64_t* shape, int32_t ndim, char* err, int errlen);
+int vc_text_workspace_bytes_impl(void* handle, int32_t L, int64_t* bytes, char* err, int errlen);
+int vc_text_prepare_impl(void* handle, int32_t L, void* workspace, int64_t workspace_bytes, hipStream_t s, char* err, int errlen);
+int vc_text_encode_impl(void* handle, const int32_t* ids, int32_t n_prompts, void* hidden, void* pooled, hipStream_t s, char* err, int errlen);
+int vc_text_plan_count_impl(void* handle);

@@ -440,3 +440,108 @@ class VaeHandle:
                                            hip.VAE_LATENT_BF16, 0, 0, s), "vc_vae_encode")
         self._join(stream, cur)
         return out.clone()
+
+
+class TextHandle:
+    """The text-encoder handle of include/vcloze_hip.h (vc_text_*) behind torch tensors: `T5EncoderModel.forward` /
+    `CLIPTextModel.forward` as one C call, one hipGraph launch per prompt once the plan is captured.  The launch plan lives in
+    csrc/text_engine.hip; the modules' own Python-ordered plan (text.py) is its parity twin (same kernels, same order, same bits).
+    This class binds the module's bf16 parameters BY POINTER under their state_dict() keys (it keeps them alive; nothing is
+    copied) and owns one workspace per sequence length.  The captured plan reads and writes workspace-resident buffers only, so ids
+    go in and results come back as the caller's / fresh tensors."""
+
+    def __init__(self, model, dev: Optional[torch.device] = None):
+        from . import text
+        c = model.cfg
+        self.dev = torch.device(dev) if dev is not None else next(model.parameters()).device
+        if isinstance(c, text.T5Config):
+            self.cfg = hip.TextConfig(hip.TEXT_T5, c.vocab_size, c.d_model, c.d_kv, c.d_ff, c.num_layers, c.num_heads,
+                                      c.relative_attention_num_buckets, c.relative_attention_max_distance, 0, 0, c.layer_norm_epsilon)
+        else:
+            self.cfg = hip.TextConfig(hip.TEXT_CLIP, c.vocab_size, c.hidden_size, c.hidden_size // c.num_attention_heads, c.intermediate_size,
+                                      c.num_hidden_layers, c.num_attention_heads, 0, 0, c.max_position_embeddings, c.eos_token_id,
+                                      c.layer_norm_eps)
+        self.is_t5, self.D = self.cfg.kind == hip.TEXT_T5, self.cfg.d_model
+        self.h = C.c_void_p()
+        hip._check(hip.lib().vc_text_create(C.byref(self.cfg), C.byref(self.h)), "vc_text_create")
+        self._ws: Dict[int, torch.Tensor] = {}
+        self._prepared = None
+        self._side = None
+        self._bound: Dict[str, torch.Tensor] = {}
+        sd = model.state_dict()
+        names = self.weight_names()
+        if list(sd) != names:
+            raise hip.VclozeHipError("the module's state_dict keys differ from the tensors libvcloze_hip.so expects for this configuration")
+        for n in names:
+            self.bind(n, sd[n])
+
+    def weight_names(self) -> list:
+        out, buf = [], C.create_string_buffer(160)
+        while hip.lib().vc_text_weight_name(self.h, len(out), buf, 160) == 0:
+            out.append(buf.value.decode())
+        return out
+
+    def bind(self, key: str, t: torch.Tensor) -> None:
+        """vc_text_bind_tensor: a bf16 tensor on the handle's device, bound by pointer and kept alive here"""
+        t = t.detach()
+        hip._bf16(t, key)
+        if t.device != self.dev or not t.is_contiguous():
+            raise hip.VclozeHipError(f"{key}: a contiguous tensor on {self.dev} expected")
+        shape = (C.c_int64 * t.dim())(*t.shape)
+        hip._check(hip.lib().vc_text_bind_tensor(self.h, key.encode(), t.data_ptr(), shape, t.dim()), f"vc_text_bind_tensor({key})")
+        self._bound[key] = t
+
+    def __del__(self):
+        try:
+            if self.h:
+                hip.lib().vc_text_destroy(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+    def plan_count(self) -> int:
+        return hip.lib().vc_text_plan_count(self.h)
+
+    def workspace_bytes(self, L: int) -> int:
+        n = C.c_int64(0)
+        hip._check(hip.lib().vc_text_workspace_bytes(self.h, L, C.byref(n)), "vc_text_workspace_bytes")
+        return n.value
+
+    def prepare(self, L: int, stream=None) -> None:
+        """vc_text_prepare for prompts of L ids; the workspaces of the last four lengths are kept"""
+        if self._prepared == L:
+            return
+        ws = self._ws.get(L)
+        if ws is None:
+            if len(self._ws) >= 4:
+                self._ws.clear()
+            ws = torch.empty(self.workspace_bytes(L) + 256, dtype=torch.uint8, device=self.dev)
+            self._ws[L] = ws
+        base = (ws.data_ptr() + 255) & ~255
+        self._prepared = None
+        hip._check(hip.lib().vc_text_prepare(self.h, L, base, ws.numel() - (base - ws.data_ptr()), stream), "vc_text_prepare")
+        self._prepared = L
+
+    _stream = VaeHandle._stream
+    _join = VaeHandle._join
+
+    def encode(self, ids: torch.Tensor, stream=0, want_hidden: bool = True, want_pooled: Optional[bool] = None):
+        """ids [n, L] (any integer dtype) -> (hidden [n, L, D] bf16 or None, pooled [n, D] bf16 or None); pooled: CLIP only (its
+        default there).  stream: a hipStream_t value, 0 = torch's current stream (captured), None = the library's un-captured path on
+        the default stream."""
+        if ids.dim() != 2 or ids.device != self.dev:
+            raise hip.VclozeHipError(f"TextHandle.encode: ids [n, L] on {self.dev} expected, got {tuple(ids.shape)} on {ids.device}")
+        want_pooled = (not self.is_t5) if want_pooled is None else want_pooled
+        ids = ids.to(torch.int32).contiguous()
+        n, L = ids.shape
+        hidden = torch.empty(n, L, self.D, dtype=torch.bfloat16, device=self.dev) if want_hidden else None
+        pooled = torch.empty(n, self.D, dtype=torch.bfloat16, device=self.dev) if want_pooled else None
+        s, cur = self._stream(stream)
+        self.prepare(L, stream=s)
+        hip._check(hip.lib().vc_text_encode(self.h, ids.data_ptr(), n, hip._p(hidden), hip._p(pooled), s), "vc_text_encode")
+        self._join(stream, cur)
+        if cur is not None:              # the plan ran on another stream: its tensors must outlive that stream's work
+            for t in (ids, hidden, pooled):
+                if t is not None:
+                    t.record_stream(cur)
+        return hidden, pooled

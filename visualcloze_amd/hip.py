@@ -108,6 +108,16 @@ VAE_ENCODER, VAE_DECODER = 1, 2                             # VC_VAE_ENCODER / V
 VAE_LATENT_BF16, VAE_LATENT_F32, VAE_TOKENS = 0, 1, 2       # VC_VAE_LATENT_* / VC_VAE_TOKENS (latent_form)
 
 
+class TextConfig(C.Structure):
+    """VcTextConfig of include/vcloze_hip.h."""
+    _fields_ = [("kind", C.c_int32), ("vocab_size", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("d_ff", C.c_int32),
+                ("num_layers", C.c_int32), ("num_heads", C.c_int32), ("num_buckets", C.c_int32), ("max_distance", C.c_int32),
+                ("max_positions", C.c_int32), ("eos_token_id", C.c_int32), ("eps", C.c_float)]
+
+
+TEXT_T5, TEXT_CLIP = 1, 2                                   # VC_TEXT_T5 / VC_TEXT_CLIP (VcTextConfig.kind)
+
+
 # every symbol include/vcloze_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 class FluxLaunchClass(C.Structure):          # VcFluxLaunchClass (vc_flux_profile)
@@ -162,6 +172,10 @@ SYMBOLS = {
     "vc_mul": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "vc_add": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "vc_quick_gelu": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "vc_t5_relative_buckets": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32)]),
+    "vc_t5_position_bias": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "vc_clip_embed": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
+    "vc_clip_pool": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "vc_transpose": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "vc_nchw_to_nhwc": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, C.c_float, C.c_float, _vp]),
     "vc_nhwc_to_nchw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp]),
@@ -195,6 +209,15 @@ SYMBOLS = {
     "vc_vae_decode": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
     "vc_vae_encode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp]),
     "vc_vae_plan_count": (C.c_int, [_vp]),
+    "vc_text_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_text_create": (C.c_int, [C.POINTER(TextConfig), C.POINTER(_vp)]),
+    "vc_text_destroy": (C.c_int, [_vp]),
+    "vc_text_weight_name": (C.c_int, [_vp, _i32, C.c_char_p, _i32]),
+    "vc_text_bind_tensor": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i32]),
+    "vc_text_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
+    "vc_text_prepare": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
+    "vc_text_encode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "vc_text_plan_count": (C.c_int, [_vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
     "vc_stream_sync": (C.c_int, [_vp]),
@@ -244,6 +267,9 @@ def lib() -> C.CDLL:
         l.vc_vae_struct_sizes(vsize)
         if vsize[0] != C.sizeof(VaeConfig):
             raise VclozeHipError(f"libvcloze_hip.so sizeof(VcVaeConfig) {vsize[0]} differs from the ctypes mirror - rebuild")
+        l.vc_text_struct_sizes(vsize)
+        if vsize[0] != C.sizeof(TextConfig):
+            raise VclozeHipError(f"libvcloze_hip.so sizeof(VcTextConfig) {vsize[0]} differs from the ctypes mirror - rebuild")
         _lib = l
     return _lib
 
@@ -848,6 +874,57 @@ def add(a, b, y, stream=None):
 
 def quick_gelu(x, y, stream=None):
     _ew(lib().vc_quick_gelu, "vc_quick_gelu", x, None, y, stream)
+
+
+def t5_relative_buckets(L: int, num_buckets: int, max_distance: int) -> list:
+    """vc_t5_relative_buckets: the 2L - 1 bucket ids of relative positions -(L-1) .. L-1 (no GPU needed)"""
+    out = (C.c_int32 * (2 * L - 1))()
+    _check(lib().vc_t5_relative_buckets(L, num_buckets, max_distance, out), "vc_t5_relative_buckets")
+    return list(out)
+
+
+def t5_position_bias(table, L: int, max_distance: int, out=None, stream=None):
+    """table: relative_attention_bias.weight [num_buckets, H] bf16 -> out [H * L, L] bf16, out[h * L + i, j] = table[bucket(j - i), h]"""
+    _bf16(table, "table")
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise VclozeHipError("t5_position_bias: table [num_buckets, H] with contiguous rows expected")
+    nb, H = table.shape
+    out = torch.empty(H * L, L, dtype=torch.bfloat16, device=table.device) if out is None else out
+    _bf16(out, "out")
+    if tuple(out.shape) != (H * L, L) or not out.is_contiguous():
+        raise VclozeHipError("t5_position_bias: contiguous out [H * L, L] expected")
+    _check(lib().vc_t5_position_bias(table.data_ptr(), table.stride(0), H, L, nb, max_distance, out.data_ptr(),
+                                     stream if stream is not None else cur_stream()), "vc_t5_position_bias")
+    return out
+
+
+def clip_embed(ids, tok, pos, out, stream=None):
+    """ids [L] int32, tok [vocab, D], pos [>= L, D], out [Lp >= L, D]: rows < L = tok[ids] + pos, the rest tok[0]"""
+    _bf16(tok, "tok"); _bf16(pos, "pos"); _bf16(out, "out")
+    if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous():
+        raise VclozeHipError("clip_embed: ids must be a contiguous CUDA int32 vector")
+    L, D = ids.shape[0], tok.shape[1]
+    if tok.stride(1) != 1 or pos.stride(1) != 1 or pos.shape[0] < L or pos.shape[1] != D or not out.is_contiguous() or out.shape[1] != D \
+            or out.shape[0] < L:
+        raise VclozeHipError("clip_embed: tok [V, D], pos [>= L, D] and contiguous out [Lp >= L, D] expected")
+    _check(lib().vc_clip_embed(ids.data_ptr(), tok.data_ptr(), tok.stride(0), tok.shape[0], pos.data_ptr(), pos.stride(0), out.data_ptr(),
+                               L, out.shape[0], D, stream if stream is not None else cur_stream()), "vc_clip_embed")
+
+
+def clip_pool(ids, hidden, eos_token_id: int, pooled=None, stream=None):
+    """pooled [D] = hidden[first i with ids[i] == eos_token_id, or 0]; hidden [>= L, D] rows"""
+    _bf16(hidden, "hidden")
+    if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous():
+        raise VclozeHipError("clip_pool: ids must be a contiguous CUDA int32 vector")
+    if hidden.dim() != 2 or hidden.stride(1) != 1 or hidden.shape[0] < ids.shape[0]:
+        raise VclozeHipError("clip_pool: hidden [>= L, D] with contiguous rows expected")
+    pooled = torch.empty(hidden.shape[1], dtype=torch.bfloat16, device=hidden.device) if pooled is None else pooled
+    _bf16(pooled, "pooled")
+    if tuple(pooled.shape) != (hidden.shape[1],) or not pooled.is_contiguous():
+        raise VclozeHipError("clip_pool: contiguous pooled [D] expected")
+    _check(lib().vc_clip_pool(ids.data_ptr(), hidden.data_ptr(), hidden.stride(0), ids.shape[0], hidden.shape[1], int(eos_token_id),
+                              pooled.data_ptr(), stream if stream is not None else cur_stream()), "vc_clip_pool")
+    return pooled
 
 
 def transpose(src, dst, stream=None):

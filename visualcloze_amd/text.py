@@ -82,6 +82,31 @@ def _bf(t):
 class _Exec:
     """Shared launch helpers: activations are [L, D] bf16 row-major."""
 
+    # opt-in, like AutoEncoder.use_handle: True routes forward through the library's text-encoder handle (vc_text_*,
+    # handle.TextHandle: the same launch plan kept in csrc/text_engine.hip, one hipGraph launch per prompt) when every parameter is
+    # bf16, instead of the Python-ordered plan below, which stays the default and the handle's parity twin - the same bits
+    use_handle = False
+
+    def _state_without_handle(self):
+        """copy.deepcopy / pickling (the classes' __getstate__): the cached TextHandle owns a C handle and stays with THIS module (a
+        copy builds its own on first use)"""
+        state = self.__dict__.copy()
+        state["_text_handle"] = None
+        return state
+
+    def handle(self):
+        """the `handle.TextHandle` over this module's parameters, rebuilt when a parameter was replaced or written"""
+        from .handle import TextHandle
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        c = self.__dict__.get("_text_handle")
+        if c is None or c[0] != key:
+            c = (key, TextHandle(self))
+            self.__dict__["_text_handle"] = c
+        return c[1]
+
+    def _handle_serves(self) -> bool:
+        return bool(self.use_handle) and all(p.dtype == torch.bfloat16 for p in self.parameters())
+
     def _scratch(self, dev, name, shape, dtype=torch.bfloat16):
         pool = self.__dict__.setdefault("_pool", {})
         t = pool.get(name)
@@ -208,11 +233,15 @@ class T5EncoderModel(nn.Module, _Exec):
             cache["key"] = key
         return cache["t"]
 
+    __getstate__ = _Exec._state_without_handle
+
     def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
         hip.require_gpu()
         cfg = self.cfg
         if input_ids.dim() != 2 or input_ids.shape[1] % 64:
             raise ValueError(f"T5EncoderModel expects input_ids [B, L] with L % 64 == 0, got {tuple(input_ids.shape)}")
+        if self._handle_serves():
+            return self.handle().encode(input_ids)[0]
         outs = []
         for ids in input_ids:
             outs.append(self._encode_one(ids.to(torch.int32).contiguous()))
@@ -331,11 +360,16 @@ class CLIPTextModel(nn.Module, _Exec):
         self.cfg = cfg
         self.text_model = _CLIPTextTransformer(cfg)
 
+    __getstate__ = _Exec._state_without_handle
+
     def forward(self, input_ids: torch.Tensor):
         hip.require_gpu()
         cfg = self.cfg
         if input_ids.dim() != 2 or input_ids.shape[1] > cfg.max_position_embeddings:
             raise ValueError(f"CLIPTextModel expects input_ids [B, L <= {cfg.max_position_embeddings}], got {tuple(input_ids.shape)}")
+        if self._handle_serves():
+            hs, pooled = self.handle().encode(input_ids)
+            return pooled, hs
         hs = torch.stack([self._encode_one(ids.to(torch.int32).contiguous()) for ids in input_ids])
         # pooled = hidden state at the EOS token (first occurrence), CLIPTextTransformer.forward
         eos = (input_ids == cfg.eos_token_id).int().argmax(dim=-1)
