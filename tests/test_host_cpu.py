@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -25,6 +27,20 @@ def test_abi_exports_every_declared_symbol():
     exported = {ln.split()[-1] for ln in nm.splitlines() if " T " in ln and ln.split()[-1].startswith("vc_")}
     assert exported == declared, exported ^ declared
     assert hip.lib().vc_abi_version() == hip.ABI_VERSION
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_plan_cache_rule_as_a_sanitized_host_program(tmp_path):
+    """csrc/plan_cache.h - the most-recently-used list of captured plans of the three handle engines - needs nothing from HIP:
+    tests/c_abi/plan_cache_check.cpp (its own main, plans are ints, "drop" appends to a log) holds it to the documented rule at the
+    capacities 4 and 8 under AddressSanitizer and UBSan.  The program runs directly, on the host."""
+    exe = str(tmp_path / "plan_cache_check")
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-I" + os.path.join(REPO, "visualcloze_amd", "csrc"),
+           os.path.join(REPO, "tests", "c_abi", "plan_cache_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "plan_cache ok" and not r.stderr, r.stdout + r.stderr
 
 
 def test_struct_layout_matches_header():

@@ -292,6 +292,35 @@ def test_plan_count_per_workspace_and_length_and_zero_after_a_rebind(hip, t5, re
     assert hd.plan_count() == 0 and torch.equal(hd.encode(ref["t5", 64]["ids"])[0], a) and torch.equal(a, ref["t5", 64]["hidden"])
 
 
+def test_the_ninth_workspace_evicts_the_least_recently_used_plan(hip, t5, ref):
+    """The list of captured plans holds 8, most recently used first (include/vcloze_hip.h).  One handle through the raw ABI, L = 64,
+    nine workspaces: the ninth plan evicts the first workspace's, which is then captured again - with the same bits."""
+    from visualcloze_amd.handle import TextHandle
+    L = hip.lib()
+    hd = TextHandle(t5[0])
+    stream = torch.cuda.Stream()
+    st = stream.cuda_stream
+    r = ref["t5", 64]
+    ids = r["ids"][0].to(torch.int32).contiguous()
+    need = hd.workspace_bytes(64)
+    wss = [torch.empty(need + 256, dtype=torch.uint8, device=DEV) for _ in range(9)]
+    outs = [torch.full((64, TINY_T5["d_model"]), float("nan"), dtype=torch.bfloat16, device=DEV) for _ in range(10)]
+    torch.cuda.synchronize()
+
+    def encode(ws, out):
+        base = (ws.data_ptr() + 255) & ~255
+        assert L.vc_text_prepare(hd.h, 64, base, need, st) == 0, L.vc_last_error()
+        assert L.vc_text_encode(hd.h, ids.data_ptr(), 1, out.data_ptr(), None, st) == 0, L.vc_last_error()
+        return L.vc_text_plan_count(hd.h)
+
+    assert [encode(ws, out) for ws, out in zip(wss, outs)] == [1, 2, 3, 4, 5, 6, 7, 8, 8]
+    assert encode(wss[0], outs[9]) == 8                  # its plan was the least recently used one: evicted, captured again
+    stream.synchronize()
+    for out in outs:
+        assert torch.equal(out, outs[0])
+    assert torch.equal(outs[0], r["hidden"][0])
+
+
 def test_errors_are_reported_before_anything_is_launched(hip, t5, t5_handle, ref):
     L = hip.lib()
     stream = torch.cuda.Stream()                         # a stream of its own: on the null stream nothing would be captured

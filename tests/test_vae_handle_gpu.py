@@ -167,6 +167,38 @@ def test_one_workspace_prepared_again_with_other_halves_gets_plans_of_its_own(hi
     assert torch.equal(decode(), want2) and hd.plan_count() == 3                # back: the first plan serves again
 
 
+def test_the_ninth_plan_evicts_the_least_recently_used_one(hip, ae, ref):
+    """The list of captured plans holds 8, most recently used first (include/vcloze_hip.h).  One handle, one prepared workspace, one
+    stream, the same latent into nine output tensors: nine keys.  The ninth evicts the first, which is then captured again."""
+    from visualcloze_amd.handle import VaeHandle
+    L = hip.lib()
+    hd = VaeHandle(ae)
+    r = ref["sq"]
+    need = hd.workspace_bytes(8, 8, hip.VAE_DECODER)
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=DEV)
+    base = (ws.data_ptr() + 255) & ~255
+    z = r["z"][0].contiguous()
+    pxs = [torch.full((3, 8, 8), float("nan"), dtype=torch.bfloat16, device=DEV) for _ in range(9)]
+    st = torch.cuda.Stream()
+    s = st.cuda_stream
+    torch.cuda.synchronize()
+    hip._check(L.vc_vae_prepare(hd.h, 8, 8, hip.VAE_DECODER, base, need, s), "vc_vae_prepare")
+
+    def decode(px):
+        hip._check(L.vc_vae_decode(hd.h, z.data_ptr(), 0, 0, 0, px.data_ptr(), 0, s), "vc_vae_decode")
+        return hd.plan_count()
+
+    assert [decode(px) for px in pxs] == [1, 2, 3, 4, 5, 6, 7, 8, 8]
+    st.synchronize()
+    for px in pxs:
+        assert torch.equal(px, r["decode"])
+    pxs[0].fill_(float("nan"))
+    torch.cuda.synchronize()
+    assert decode(pxs[0]) == 8                           # its plan was the least recently used one: evicted, captured again
+    st.synchronize()
+    assert torch.equal(pxs[0], r["decode"])
+
+
 def test_a_stream_that_is_not_the_current_one_is_ordered(handle, ref):
     r = ref["rect"]
     st = torch.cuda.Stream()

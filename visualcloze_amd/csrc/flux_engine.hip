@@ -20,6 +20,7 @@
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
 #include "common.h"
 #include "vcloze_internal.h"
+#include "engine_core.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -38,10 +39,6 @@ struct Lin {
 // bound: the block's own logit bound, 1.02 sqrt(128) log2(e) max|query_norm.scale| max|key_norm.scale| (both streams of a double block)
 struct DoubleW { Lin qkv[2], proj[2], mlp0[2], mlp2[2]; const void* qs[2]; const void* ks[2]; int64_t mod[2]; float bound; };  // [0] = img, [1] = txt
 struct SingleW { Lin qkv, mlp, lin2; const void* qs; const void* ks; int64_t mod; float bound; };
-
-struct Err {
-  char* buf; int len;
-};
 
 struct Buffers {   // the workspace carve-up
   bf16_t *XI, *XT, *X, *XH, *QKV, *VT, *CAT, *HID, *TXT0, *XIN, *V, *XS, *COND, *MOD, *TEMB, *H1, *TVEC, *GVEC, *YVEC, *VEC, *GE, *GH, *YH, *KS, *YIN;
@@ -93,11 +90,12 @@ struct Flux : Buffers {
   int B = 0, T = 0, N = 0, L = 0, Lp = 0, S = 0;
   bool ragged = false, gapped = false;
   char* base = nullptr;
-  // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
-  hipGraphExec_t graph = nullptr;      // = graphs.front().second.g[0] while a sample is in flight
   // a captured step: ONE graph (g[0]), or with the step cache on three - head, tail-compute, tail-reuse (an entry of `graphs` is a
-  // whole step, so a cached trajectory never evicts a graph of its own)
+  // whole step, so a cached trajectory never evicts a graph of its own).  step: the one of the sample in flight
   struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; } step;
+  struct DropStep {
+    void operator()(const Step& st) const { for (auto ge : st.g) DropExec()(ge); }
+  };
   struct Key {
     char* base; int B, T, N, S, ragged, gapped, variant, state_f32, method, cache; Options opt; hipStream_t s;   // variant: resolved
     int cfg; uint32_t cfg_bits;          // true CFG on, and the bits of its scale: a kernel argument of the captured combine
@@ -107,7 +105,8 @@ struct Flux : Buffers {
              cfg == o.cfg && cfg_bits == o.cfg_bits;
     }
   } key{};
-  std::vector<std::pair<Key, Step>> graphs;
+  // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
+  PlanCache<Key, Step, 4, DropStep> graphs;
   // sampling state
   int steps_total = 0, steps_done = 0;
   bool state_f32 = false;              // the sample in flight steps an f32 state (XS32; XS is its bf16 shadow)
@@ -139,34 +138,7 @@ struct Flux : Buffers {
   std::vector<ProfRec> prof_recs;
 };
 
-#define FAIL(code, ...)                         \
-  do {                                          \
-    snprintf(e.buf, e.len, __VA_ARGS__);        \
-    return code;                                \
-  } while (0)
-#define TRY(x)                \
-  do {                        \
-    int rc_ = (x);            \
-    if (rc_ != VC_OK) return rc_; \
-  } while (0)
-#define HIP(x, what)                                                        \
-  do {                                                                      \
-    hipError_t he_ = (x);                                                   \
-    if (he_ != hipSuccess) FAIL(VC_ERR_HIP, what ": %s", hipGetErrorString(he_)); \
-  } while (0)
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 // ---------------------------------------------------------------- workspace
-struct Carver {
-  char* base; int64_t off = 0;
-  template <class T> T* take(int64_t count) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += align256(count * (int64_t)sizeof(T));
-    return p;
-  }
-};
-
 int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S) {
   const int64_t D = g.D, H = g.H, mlp = g.mlp, L = T + N, Lp = (L + 63) / 64 * 64;
   const int64_t in_ch = g.cfg.in_channels, out_ch = g.cfg.out_channels;
@@ -637,47 +609,25 @@ int time_precompute(Flux& f, int S, int timesteps_is_bf16, hipStream_t s, Err e)
   return lin(f, f.modulation, f.H1, D, f.MOD, f.n_mod, M, VC_EPI_BIAS, s, e);
 }
 
-constexpr size_t MAX_GRAPHS = 4;      // captured STEPS (Flux::Step: one graph, or the three of a cached step)
 void drop_prof(Flux& f) {
   for (auto ev : f.prof_ev) (void)hipEventDestroy(ev);
   f.prof_ev.clear();
 }
 void drop_graph(Flux& f) {
-  for (auto& g : f.graphs)
-    for (auto ge : g.second.g) if (ge) (void)hipGraphExecDestroy(ge);
   f.graphs.clear();
-  f.graph = nullptr;
   f.step = Flux::Step{};
 }
 
 // the hipGraph of ONE evaluation + the solver's update behind it (Euler: one solver step): everything that depends on the
 // evaluation (modulation rows, dt, the stage of a midpoint / rk4 step) is indexed on the device by STEP
-// capture what `issue` launches on `s` into an instantiated graph
-template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue) {
-  HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
-  const int rc = issue();
-  hipGraph_t g = nullptr;
-  hipError_t he = hipStreamEndCapture(s, &g);
-  if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-  HIP(he, "hipStreamEndCapture");
-  he = hipGraphInstantiate(&out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  HIP(he, "hipGraphInstantiate");
-  return VC_OK;
-}
 int step_graph(Flux& f, hipStream_t s, Err e) {
   Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s,
                f.cfg_active, 0};
   if (f.cfg_active) memcpy(&k.cfg_bits, &f.cfg_s, 4);
-  for (size_t i = 0; i < f.graphs.size(); ++i)
-    if (f.graphs[i].first == k) {
-      auto hit = f.graphs[i];
-      f.graphs.erase(f.graphs.begin() + i);
-      f.graphs.insert(f.graphs.begin(), hit);
-      f.step = hit.second; f.graph = f.step.g[0]; f.key = k;
-      return VC_OK;
-    }
-  f.graph = nullptr;
+  if (const Flux::Step* hit = f.graphs.find(k)) {
+    f.step = *hit; f.key = k;
+    return VC_OK;
+  }
   f.step = Flux::Step{};
   Flux::Step st;
   int rc = VC_OK;
@@ -696,24 +646,15 @@ int step_graph(Flux& f, hipStream_t s, Err e) {
     if (rc == VC_OK) rc = capture(s, st.g[2], e, [&] { return cache_tail_reuse(f, true, s, e); });
   }
   if (rc != VC_OK) {
-    for (auto ge : st.g) if (ge) (void)hipGraphExecDestroy(ge);
+    Flux::DropStep()(st);          // the graphs of a half-captured step
     return rc;
   }
-  if (f.graphs.size() >= MAX_GRAPHS) {
-    for (auto ge : f.graphs.back().second.g) if (ge) (void)hipGraphExecDestroy(ge);
-    f.graphs.pop_back();
-  }
-  f.graphs.insert(f.graphs.begin(), {k, st});
-  f.step = st; f.graph = st.g[0]; f.key = k;
+  f.graphs.insert(k, st);
+  f.step = st; f.key = k;
   return VC_OK;
 }
 
 }  // namespace
-
-#define H(handle)                                                         \
-  Err e{err, errlen};                                                     \
-  if (!(handle)) FAIL(VC_ERR_ARG, "flux: null handle");                   \
-  Flux& f = *(Flux*)(handle)
 
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen) {
   Err e{err, errlen};
@@ -741,7 +682,7 @@ int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int e
 }
 
 int vc_flux_destroy_impl(void* handle, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (f.staged_pending) (void)hipEventSynchronize(f.staged);
   drop_graph(f);
   drop_prof(f);
@@ -754,7 +695,7 @@ int vc_flux_destroy_impl(void* handle, char* err, int errlen) {
 
 int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, const void* bias, int32_t rows, int32_t cols, int64_t ldw,
                              char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!name || !w || rows <= 0 || cols <= 0 || ldw < cols) FAIL(VC_ERR_ARG, "flux_bind_weight: bad arguments for '%s'", name ? name : "?");
   // the optional split-K scratch decides whether 100 MB are carved into EVERY workspace: binding it for the first time after a
   // workspace has been sized would silently change the carve-up of buffers the caller already holds (advisor r05)
@@ -779,7 +720,7 @@ int64_t vc_flux_mod_offset_impl(void* handle, const char* name) {
 }
 
 int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!name) FAIL(VC_ERR_ARG, "flux_set_option: null name");
   for (const auto& o : OPTIONS) {
     if (strcmp(name, o.name)) continue;
@@ -804,7 +745,7 @@ int64_t vc_flux_workspace_bytes_impl(void* handle, int32_t B, int32_t T, int32_t
 }
 
 int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, int64_t workspace_bytes, hipStream_t s, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!in || !workspace) FAIL(VC_ERR_ARG, "flux_prepare: null argument");
   f.ws_sized = true;
   const int B = in->B, T = in->T, N = in->N, S = in->max_steps;
@@ -812,7 +753,7 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
   if (!in->txt || !in->y || !in->img_ids || !in->txt_ids) FAIL(VC_ERR_ARG, "flux_prepare: txt, y, img_ids, txt_ids are required");
   if (f.cfg.guidance_embed && !in->guidance) FAIL(VC_ERR_ARG, "Didn't get guidance strength for guidance distilled model.");
   if (in->kv_gap && !in->kv_len) FAIL(VC_ERR_ARG, "flux_prepare: kv_gap needs kv_len");
-  if ((uintptr_t)workspace & 255) FAIL(VC_ERR_ARG, "flux_prepare: workspace must be 256-byte aligned");
+  if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "flux_prepare: workspace must be 256-byte aligned");
   TRY(resolve(f, e));
   f.prepared = false;
   const int64_t need = carve(f, f, (char*)workspace, B, T, N, S);
@@ -913,7 +854,7 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
 
 int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, int32_t timesteps_is_bf16, void* out, hipStream_t s,
                          char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_forward: call vc_flux_prepare first");
   if (!img || !timesteps || !out) FAIL(VC_ERR_ARG, "flux_forward: null argument");
   TRY(stage_begin(f, f.B * sizeof(float) + 256, e));
@@ -942,7 +883,7 @@ void stage_times(int method, float t0, float t1, float dt, float* out) {
 
 int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
                               int32_t state_is_bf16, hipStream_t s, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   const int E = vc_evals_of(method);
   if (!E) FAIL(VC_ERR_ARG, "flux_sample: unknown solver method %d (VC_SOLVER_EULER, VC_SOLVER_MIDPOINT, VC_SOLVER_RK4)", method);
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample: call vc_flux_prepare first");
@@ -1017,16 +958,16 @@ static int cached_step(Flux& f, hipStream_t s, Err e) {
 }
 
 int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, hipStream_t s, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_sample_steps: call vc_flux_sample_begin first");
   if (n_steps < 0 || f.steps_done + n_steps > f.steps_total)
     FAIL(VC_ERR_ARG, "flux_sample_steps: %d more steps after %d of %d", n_steps, f.steps_done, f.steps_total);
-  if (s && (!f.graph || f.key.s != s)) FAIL(VC_ERR_STATE, "flux_sample_steps: the step was captured on another stream");
+  if (s && (!f.step.g[0] || f.key.s != s)) FAIL(VC_ERR_STATE, "flux_sample_steps: the step was captured on another stream");
   const int64_t state_bytes = ode_state_bytes(f);
   for (int i = 0; i < n_steps; ++i) {
     for (int j = 0; j < f.evals; ++j) {      // a step = `evals` replays; the stage is the device-side counter modulo evals
       if (f.sc_active) { TRY(cached_step(f, s, e)); continue; }
-      if (s) HIP(hipGraphLaunch(f.graph, s), "hipGraphLaunch");
+      if (s) HIP(hipGraphLaunch(f.step.g[0], s), "hipGraphLaunch");
       else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
       ++f.sc_computed;
     }
@@ -1037,14 +978,14 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
 }
 
 int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_sample_end: no sample in flight");
   if (!x_out) FAIL(VC_ERR_ARG, "flux_sample_end: null output");
   return d2d(x_out, ode_state(f), ode_state_bytes(f), s, e);
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (threshold != threshold) FAIL(VC_ERR_ARG, "flux_set_step_cache: threshold is NaN");
   f.sc_threshold = threshold > 0.0f ? threshold : 0.0f;
   f.sc_max = max_consecutive;
@@ -1052,14 +993,14 @@ int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_conse
 }
 
 int vc_flux_set_cfg_impl(void* handle, int32_t on, float cfg_scale, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   f.cfg_on = on != 0;
   f.cfg_scale = cfg_scale;       // held to finite at the next vc_flux_sample_begin*, where the setting takes effect
   return VC_OK;
 }
 
 int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity, char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (capacity < 0 || (capacity > 0 && !metrics)) FAIL(VC_ERR_ARG, "flux_step_cache_stats: bad arguments");
   if (computed) *computed = f.sc_computed;
   if (reused) *reused = f.sc_reused;
@@ -1073,7 +1014,7 @@ int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reus
 // (the trajectory's state, its step counter and its graph are left as they are).
 int vc_flux_profile_impl(void* handle, int32_t evaluations, VcFluxLaunchClass* out, int32_t capacity, int32_t* count, hipStream_t s,
                          char* err, int errlen) {
-  H(handle);
+  HANDLE(Flux, f, "flux");
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_profile: call vc_flux_sample_begin first");
   if (!out || !count || capacity <= 0 || evaluations <= 0) FAIL(VC_ERR_ARG, "flux_profile: bad argument");
   TRY(evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e));       // warm: caches and clocks as inside a trajectory

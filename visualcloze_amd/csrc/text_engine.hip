@@ -16,6 +16,7 @@
 //   ONES [D]        the gate of `x + h`         BIAS [H L, L]    T5's position bias
 #include "common.h"
 #include "vcloze_internal.h"
+#include "engine_core.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -23,27 +24,6 @@
 #include <vector>
 
 namespace {
-
-struct Err {
-  char* buf; int len;
-};
-#define FAIL(code, ...)                         \
-  do {                                          \
-    snprintf(e.buf, e.len, __VA_ARGS__);        \
-    return code;                                \
-  } while (0)
-#define TRY(x)                \
-  do {                        \
-    int rc_ = (x);            \
-    if (rc_ != VC_OK) return rc_; \
-  } while (0)
-#define HIP(x, what)                                                        \
-  do {                                                                      \
-    hipError_t he_ = (x);                                                   \
-    if (he_ != hipSuccess) FAIL(VC_ERR_HIP, what ": %s", hipGetErrorString(he_)); \
-  } while (0)
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 // one state_dict entry
 struct Tensor {
@@ -78,15 +58,9 @@ struct Text {
     char* base; int L; hipStream_t s;
     bool operator==(const Key& o) const { return base == o.base && L == o.L && s == o.s; }
   };
-  std::vector<std::pair<Key, hipGraphExec_t>> plans;
+  PlanCache<Key, hipGraphExec_t, 8, DropExec> plans;
   std::vector<int> warmed;   // the L whose launches have run un-captured once on this handle (kernel attributes are set on a first launch)
 };
-constexpr size_t MAX_PLANS = 8;
-
-void drop_plans(Text& v) {
-  for (auto& p : v.plans) if (p.second) (void)hipGraphExecDestroy(p.second);
-  v.plans.clear();
-}
 
 // ---------------------------------------------------------------- the state dict of text.T5EncoderModel / text.CLIPTextModel, in order
 int add(Text& v, const std::string& key, int64_t d0, int64_t d1 = 0, bool read = true) {
@@ -270,53 +244,9 @@ int64_t carve(const Text& v, int L, char* base, char* ptr[NBUF]) {
   bytes[FA] = bytes[FB] = R * F * 2;
   bytes[ONES] = D * 2;
   bytes[BIAS] = t5 ? bytes[S] : 0;
-  int64_t off = 0;
-  for (int i = 0; i < NBUF; ++i) {
-    ptr[i] = base && bytes[i] ? base + off : nullptr;
-    off += align256(bytes[i]);
-  }
-  return off;
-}
-
-template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue) {
-  HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
-  const int rc = issue();
-  hipGraph_t g = nullptr;
-  hipError_t he = hipStreamEndCapture(s, &g);
-  if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-  HIP(he, "hipStreamEndCapture");
-  he = hipGraphInstantiate(&out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  HIP(he, "hipGraphInstantiate");
-  return VC_OK;
-}
-
-// one prompt's launches as the plan of key k: un-captured on the default stream for a null stream, else ONE launch of its captured graph
-template <class F> int run_plan(Text& v, const Text::Key& k, Err e, F issue) {
-  if (!k.s) return issue();
-  for (size_t i = 0; i < v.plans.size(); ++i)
-    if (v.plans[i].first == k) {
-      auto hit = v.plans[i];
-      v.plans.erase(v.plans.begin() + i);
-      v.plans.insert(v.plans.begin(), hit);
-      HIP(hipGraphLaunch(hit.second, k.s), "hipGraphLaunch");
-      return VC_OK;
-    }
-  bool warm = false;
-  for (int w : v.warmed) warm = warm || w == k.L;
-  if (!warm) {               // outside capture first: kernel attributes are set on a kernel's first launch
-    TRY(issue());
-    v.warmed.push_back(k.L);
-  }
-  hipGraphExec_t ge = nullptr;
-  TRY(capture(k.s, ge, e, issue));
-  if (v.plans.size() >= MAX_PLANS) {
-    if (v.plans.back().second) (void)hipGraphExecDestroy(v.plans.back().second);
-    v.plans.pop_back();
-  }
-  v.plans.insert(v.plans.begin(), {k, ge});
-  HIP(hipGraphLaunch(ge, k.s), "hipGraphLaunch");
-  return VC_OK;
+  Carver c{base};
+  for (int i = 0; i < NBUF; ++i) ptr[i] = c.bytes(bytes[i]);
+  return c.off;
 }
 
 int build_bias(Text& v, hipStream_t s, Err e) {
@@ -327,11 +257,6 @@ int build_bias(Text& v, hipStream_t s, Err e) {
 }
 
 }  // namespace
-
-#define TEXT(handle)                                                      \
-  Err e{err, errlen};                                                    \
-  if (!(handle)) FAIL(VC_ERR_ARG, "text: null handle");                  \
-  Text& v = *(Text*)(handle)
 
 int vc_text_create_impl(const VcTextConfig* cfg, void** handle, char* err, int errlen) {
   Err e{err, errlen};
@@ -364,14 +289,14 @@ int vc_text_create_impl(const VcTextConfig* cfg, void** handle, char* err, int e
 }
 
 int vc_text_destroy_impl(void* handle, char* err, int errlen) {
-  TEXT(handle);
-  drop_plans(v);
+  HANDLE(Text, v, "text");
+  v.plans.clear();
   delete &v;
   return VC_OK;
 }
 
 int vc_text_weight_name_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen) {
-  TEXT(handle);
+  HANDLE(Text, v, "text");
   if (index < 0 || index >= (int)v.t.size()) FAIL(VC_ERR_ARG, "text_weight_name: index %d outside 0..%d", index, (int)v.t.size() - 1);
   if (!name || namelen <= (int)v.t[index].key.size()) FAIL(VC_ERR_ARG, "text_weight_name: name buffer too small");
   strcpy(name, v.t[index].key.c_str());
@@ -379,7 +304,7 @@ int vc_text_weight_name_impl(void* handle, int32_t index, char* name, int32_t na
 }
 
 int vc_text_bind_tensor_impl(void* handle, const char* key, const void* ptr, const int64_t* shape, int32_t ndim, char* err, int errlen) {
-  TEXT(handle);
+  HANDLE(Text, v, "text");
   if (!key) FAIL(VC_ERR_ARG, "text_bind_tensor: null key");
   auto it = v.by_key.find(key);
   if (it == v.by_key.end()) FAIL(VC_ERR_ARG, "text_bind_tensor: unknown key '%s'", key);
@@ -390,14 +315,14 @@ int vc_text_bind_tensor_impl(void* handle, const char* key, const void* ptr, con
     FAIL(VC_ERR_ARG, "text_bind_tensor: '%s' has shape [%ld]", key, (long)t.shape[0]);
   }
   if ((uintptr_t)ptr & 15) FAIL(VC_ERR_ARG, "text_bind_tensor: '%s' must be 16-byte aligned", key);
-  drop_plans(v);             // a captured plan holds the old pointer
+  v.plans.clear();           // a captured plan holds the old pointer
   t.p = (const bf16_t*)ptr;
   if (it->second == v.rel) v.bias_ready = false;
   return VC_OK;
 }
 
 int vc_text_workspace_bytes_impl(void* handle, int32_t L, int64_t* bytes, char* err, int errlen) {
-  TEXT(handle);
+  HANDLE(Text, v, "text");
   if (!bytes) FAIL(VC_ERR_ARG, "text_workspace_bytes: null result pointer");
   TRY(check_len(v, L, e, "text_workspace_bytes"));
   char* none[NBUF];
@@ -406,9 +331,9 @@ int vc_text_workspace_bytes_impl(void* handle, int32_t L, int64_t* bytes, char* 
 }
 
 int vc_text_prepare_impl(void* handle, int32_t L, void* workspace, int64_t workspace_bytes, hipStream_t s, char* err, int errlen) {
-  TEXT(handle);
+  HANDLE(Text, v, "text");
   TRY(check_len(v, L, e, "text_prepare"));
-  if (!workspace || ((uintptr_t)workspace & 255)) FAIL(VC_ERR_ARG, "text_prepare: the workspace must be a 256-byte aligned device pointer");
+  if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "text_prepare: the workspace must be a 256-byte aligned device pointer");
   char* ptr[NBUF];
   const int64_t need = carve(v, L, (char*)workspace, ptr);
   if (workspace_bytes < need) FAIL(VC_ERR_ARG, "text_prepare: workspace too small (%ld < %ld bytes)", (long)workspace_bytes, (long)need);
@@ -423,7 +348,7 @@ int vc_text_prepare_impl(void* handle, int32_t L, void* workspace, int64_t works
 }
 
 int vc_text_encode_impl(void* handle, const int32_t* ids, int32_t n_prompts, void* hidden, void* pooled, hipStream_t s, char* err, int errlen) {
-  TEXT(handle);
+  HANDLE(Text, v, "text");
   const bool t5 = v.cfg.kind == VC_TEXT_T5;
   if (!ids || n_prompts <= 0) FAIL(VC_ERR_ARG, "text_encode: null ids or no prompt");
   if (t5 && pooled) FAIL(VC_ERR_ARG, "text_encode: a T5 handle has no pooled output (pooled must be NULL)");
@@ -436,7 +361,7 @@ int vc_text_encode_impl(void* handle, const int32_t* ids, int32_t n_prompts, voi
   const int64_t row = (int64_t)v.D * 2;
   for (int i = 0; i < n_prompts; ++i) {        // the copies stay outside the graph: it is a chain of kernel nodes over resident buffers
     HIP(hipMemcpyAsync(v.ptr[IDS], ids + (int64_t)i * v.L, (size_t)v.L * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(ids)");
-    TRY(run_plan(v, k, e, [&] {
+    TRY(run_captured(v.plans, v.warmed, k, k.L, e, [&] {   // one prompt's launches
       Run r{v, s, e};
       return t5 ? t5_plan(r) : clip_plan(r);
     }));

@@ -15,6 +15,7 @@
 //   ONES [max C]                the gate of `x + h` (autoencoder.py:82) for the fused residual epilogue
 #include "common.h"
 #include "vcloze_internal.h"
+#include "engine_core.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -22,28 +23,6 @@
 #include <vector>
 
 namespace {
-
-struct Err {
-  char* buf; int len;
-};
-#define FAIL(code, ...)                         \
-  do {                                          \
-    snprintf(e.buf, e.len, __VA_ARGS__);        \
-    return code;                                \
-  } while (0)
-#define TRY(x)                \
-  do {                        \
-    int rc_ = (x);            \
-    if (rc_ != VC_OK) return rc_; \
-  } while (0)
-#define HIP(x, what)                                                        \
-  do {                                                                      \
-    hipError_t he_ = (x);                                                   \
-    if (he_ != hipSuccess) FAIL(VC_ERR_HIP, what ": %s", hipGetErrorString(he_)); \
-  } while (0)
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline int pad_to(int n, int m) { return (n + m - 1) / m * m; }
 
 constexpr int GN_GROUPS = 32;          // nn.GroupNorm(32, C, eps=1e-6), autoencoder.py:21-22
 constexpr float GN_EPS = 1e-6f;
@@ -95,7 +74,7 @@ struct Vae {
              noise == o.noise && out == o.out && ld == o.ld && col0 == o.col0 && s == o.s;
     }
   };
-  std::vector<std::pair<Key, hipGraphExec_t>> plans;
+  PlanCache<Key, hipGraphExec_t, 8, DropExec> plans;
   // plan shapes that have run un-captured once on this handle (H, W, dir, form, pix_f32, noise given): the run that sets the
   // kernels' attributes is needed once per set of launches, not once per set of argument pointers
   struct Shape {
@@ -104,12 +83,6 @@ struct Vae {
   };
   std::vector<Shape> warmed;
 };
-constexpr size_t MAX_PLANS = 8;
-
-void drop_plans(Vae& v) {
-  for (auto& p : v.plans) if (p.second) (void)hipGraphExecDestroy(p.second);
-  v.plans.clear();
-}
 
 // ---------------------------------------------------------------- the module tree (autoencoder.py:109-259), in state-dict order
 int add_mod(Vae& v, const std::string& name, int k, int cin, int cout) {
@@ -434,55 +407,10 @@ int size_sides(Vae& v, int H, int W, int which, Side out[2], Err e) {
   return VC_OK;
 }
 int64_t carve(Side sides[2], char* base) {
-  int64_t off = 0;
+  Carver c{base};
   for (int dir = 0; dir < 2; ++dir)
-    for (int i = 0; i < NBUF; ++i) {
-      sides[dir].ptr[i] = base && sides[dir].bytes[i] ? base + off : nullptr;
-      off += align256(sides[dir].bytes[i]);
-    }
-  return off;
-}
-
-template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue) {
-  HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
-  const int rc = issue();
-  hipGraph_t g = nullptr;
-  hipError_t he = hipStreamEndCapture(s, &g);
-  if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-  HIP(he, "hipStreamEndCapture");
-  he = hipGraphInstantiate(&out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  HIP(he, "hipGraphInstantiate");
-  return VC_OK;
-}
-
-// run `issue` as the plan of key k: un-captured on the default stream for a null stream, else ONE launch of its captured graph
-template <class F> int run_plan(Vae& v, const Vae::Key& k, Err e, F issue) {
-  if (!k.s) return issue();
-  for (size_t i = 0; i < v.plans.size(); ++i)
-    if (v.plans[i].first == k) {
-      auto hit = v.plans[i];
-      v.plans.erase(v.plans.begin() + i);
-      v.plans.insert(v.plans.begin(), hit);
-      HIP(hipGraphLaunch(hit.second, k.s), "hipGraphLaunch");
-      return VC_OK;
-    }
-  const Vae::Shape shape{k.H, k.W, k.dir, k.form, k.pix_f32, k.noise != nullptr};
-  bool warm = false;
-  for (const auto& w : v.warmed) warm = warm || w == shape;
-  if (!warm) {               // outside capture first: kernel attributes are set on a kernel's first launch
-    TRY(issue());
-    v.warmed.push_back(shape);
-  }
-  hipGraphExec_t ge = nullptr;
-  TRY(capture(k.s, ge, e, issue));
-  if (v.plans.size() >= MAX_PLANS) {
-    if (v.plans.back().second) (void)hipGraphExecDestroy(v.plans.back().second);
-    v.plans.pop_back();
-  }
-  v.plans.insert(v.plans.begin(), {k, ge});
-  HIP(hipGraphLaunch(ge, k.s), "hipGraphLaunch");
-  return VC_OK;
+    for (int i = 0; i < NBUF; ++i) sides[dir].ptr[i] = c.bytes(sides[dir].bytes[i]);
+  return c.off;
 }
 
 // the checks every decode / encode call makes before anything is launched
@@ -505,11 +433,6 @@ int check_tokens(const Vae& v, int64_t ld, int col0, const void* tokens, Err e, 
 }
 
 }  // namespace
-
-#define VAE(handle)                                                        \
-  Err e{err, errlen};                                                    \
-  if (!(handle)) FAIL(VC_ERR_ARG, "vae: null handle");                   \
-  Vae& v = *(Vae*)(handle)
 
 int vc_vae_create_impl(const VcVaeConfig* cfg, void** handle, char* err, int errlen) {
   Err e{err, errlen};
@@ -535,15 +458,15 @@ int vc_vae_create_impl(const VcVaeConfig* cfg, void** handle, char* err, int err
 }
 
 int vc_vae_destroy_impl(void* handle, char* err, int errlen) {
-  VAE(handle);
-  drop_plans(v);
+  HANDLE(Vae, v, "vae");
+  v.plans.clear();
   for (auto& m : v.mods) if (m.mem) (void)hipFree(m.mem);
   delete &v;
   return VC_OK;
 }
 
 int vc_vae_weight_name_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   if (index < 0 || index >= (int)v.mods.size()) FAIL(VC_ERR_ARG, "vae_weight_name: index %d outside 0..%d", index, (int)v.mods.size() - 1);
   if (!name || namelen <= (int)v.mods[index].name.size()) FAIL(VC_ERR_ARG, "vae_weight_name: name buffer too small");
   strcpy(name, v.mods[index].name.c_str());
@@ -552,7 +475,7 @@ int vc_vae_weight_name_impl(void* handle, int32_t index, char* name, int32_t nam
 
 int vc_vae_bind_weight_impl(void* handle, const char* name, const void* w, const void* bias, int32_t is_f32, const int64_t* shape, int32_t ndim,
                             hipStream_t s, char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   if (!name) FAIL(VC_ERR_ARG, "vae_bind_weight: null name");
   std::string key(name);
   if (key.size() > 7 && key.compare(key.size() - 7, 7, ".weight") == 0) key.resize(key.size() - 7);
@@ -576,14 +499,14 @@ int vc_vae_bind_weight_impl(void* handle, const char* name, const void* w, const
   if (rc == VC_OK) rc = vc_vae_cast_pad_launch(bias, is_f32 != 0, db, m.cout, Op, s, err, errlen);
   if (rc == VC_OK && hipStreamSynchronize(s) != hipSuccess) { snprintf(err, errlen, "vae_bind_weight: hipStreamSynchronize failed for '%s'", name); rc = VC_ERR_HIP; }
   if (rc != VC_OK) { (void)hipFree(mem); return rc; }
-  drop_plans(v);             // a captured plan holds the old copy's pointers
+  v.plans.clear();           // a captured plan holds the old copy's pointers
   if (m.mem) (void)hipFree(m.mem);
   m.mem = mem; m.w = dw; m.b = db;
   return VC_OK;
 }
 
 int vc_vae_workspace_bytes_impl(void* handle, int32_t H, int32_t W, int32_t which, int64_t* bytes, char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   if (!bytes) FAIL(VC_ERR_ARG, "vae_workspace_bytes: null result pointer");
   TRY(check_size(v, H, W, which, e, "vae_workspace_bytes"));
   Side sides[2];
@@ -594,9 +517,9 @@ int vc_vae_workspace_bytes_impl(void* handle, int32_t H, int32_t W, int32_t whic
 
 int vc_vae_prepare_impl(void* handle, int32_t H, int32_t W, int32_t which, void* workspace, int64_t workspace_bytes, hipStream_t s,
                         char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   TRY(check_size(v, H, W, which, e, "vae_prepare"));
-  if (!workspace || ((uintptr_t)workspace & 255)) FAIL(VC_ERR_ARG, "vae_prepare: the workspace must be a 256-byte aligned device pointer");
+  if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "vae_prepare: the workspace must be a 256-byte aligned device pointer");
   Side sides[2];
   TRY(size_sides(v, H, W, which, sides, e));
   const int64_t need = carve(sides, (char*)workspace);
@@ -613,7 +536,7 @@ int vc_vae_prepare_impl(void* handle, int32_t H, int32_t W, int32_t which, void*
 
 int vc_vae_decode_impl(void* handle, const void* latent, int32_t form, int64_t ld, int32_t col0, void* pixels, int32_t pixels_is_f32,
                        hipStream_t s, char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   if (!latent || !pixels) FAIL(VC_ERR_ARG, "vae_decode: null pointer");
   if (form != VC_VAE_LATENT_BF16 && form != VC_VAE_LATENT_F32 && form != VC_VAE_TOKENS) FAIL(VC_ERR_ARG, "vae_decode: unknown latent_form %d", form);
   TRY(ready(v, DIR_DECODE, e, "vae_decode"));
@@ -621,7 +544,7 @@ int vc_vae_decode_impl(void* handle, const void* latent, int32_t form, int64_t l
   else { ld = 0; col0 = 0; }
   pixels_is_f32 = pixels_is_f32 != 0;
   Vae::Key k{v.base, v.H, v.W, v.which, DIR_DECODE, form, pixels_is_f32, latent, nullptr, pixels, ld, col0, s};
-  return run_plan(v, k, e, [&] {
+  return run_captured(v.plans, v.warmed, k, Vae::Shape{k.H, k.W, k.dir, k.form, k.pix_f32, 0}, e, [&] {
     Run r{v, v.side[DIR_DECODE], false, s, e};
     return decode_plan(r, v.H, v.W, latent, form, ld, col0, pixels, pixels_is_f32);
   });
@@ -629,7 +552,7 @@ int vc_vae_decode_impl(void* handle, const void* latent, int32_t form, int64_t l
 
 int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t form, int64_t ld,
                        int32_t col0, hipStream_t s, char* err, int errlen) {
-  VAE(handle);
+  HANDLE(Vae, v, "vae");
   if (!latent || !pixels) FAIL(VC_ERR_ARG, "vae_encode: null pointer");
   if (form != VC_VAE_LATENT_BF16 && form != VC_VAE_TOKENS) FAIL(VC_ERR_ARG, "vae_encode: latent_form must be VC_VAE_LATENT_BF16 or VC_VAE_TOKENS, got %d", form);
   TRY(ready(v, DIR_ENCODE, e, "vae_encode"));
@@ -637,7 +560,7 @@ int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, 
   else { ld = 0; col0 = 0; }
   pixels_is_f32 = pixels_is_f32 != 0;
   Vae::Key k{v.base, v.H, v.W, v.which, DIR_ENCODE, form, pixels_is_f32, pixels, noise, latent, ld, col0, s};
-  return run_plan(v, k, e, [&] {
+  return run_captured(v.plans, v.warmed, k, Vae::Shape{k.H, k.W, k.dir, k.form, k.pix_f32, noise != nullptr}, e, [&] {
     Run r{v, v.side[DIR_ENCODE], false, s, e};
     return encode_plan(r, v.H, v.W, pixels, pixels_is_f32, noise, latent, form, ld, col0);
   });

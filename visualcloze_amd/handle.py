@@ -60,7 +60,64 @@ def _ip(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-class FluxHandle:
+class _Handle:
+    """What the three handles share: the `vc_*_destroy` / `vc_*_weight_name` calls named by the class attributes, the aligned base of
+    a workspace tensor and the stream a captured plan runs on."""
+    _destroy: str = ""
+    _weight_name: str = ""      # (FluxHandle binds by reference-module path: the ABI has no vc_flux_weight_name)
+
+    def __del__(self):
+        try:
+            if self.h:
+                getattr(hip.lib(), self._destroy)(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+    def weight_names(self) -> list:
+        out, buf = [], C.create_string_buffer(160)
+        while getattr(hip.lib(), self._weight_name)(self.h, len(out), buf, 160) == 0:
+            out.append(buf.value.decode())
+        return out
+
+    @staticmethod
+    def _aligned(ws: torch.Tensor) -> Tuple[int, int]:
+        """(the first 256-byte aligned address inside ws, the bytes of ws behind it)"""
+        base = (ws.data_ptr() + 255) & ~255
+        return base, ws.numel() - (base - ws.data_ptr())
+
+    def _stream(self, stream):
+        """(the hipStream_t value to pass, the torch stream the plan runs on when that is not torch's current stream, else None).
+        stream 0 = torch's current stream; when that is the null stream - on which the library runs un-captured - the captured
+        plan runs on a stream of the handle's own.  Any other value is taken as the caller's hipStream_t.  The copies into and out
+        of the argument slots run on torch's current stream, so a plan on another stream is ordered behind and in front of it
+        (`_join`).  None = the un-captured path, on the null stream."""
+        cur = torch.cuda.current_stream(self.dev)
+        if stream is None:
+            cur.synchronize()
+            return None, None
+        if stream == 0 and cur.cuda_stream != 0:
+            return cur.cuda_stream, None
+        if stream != 0 and stream == cur.cuda_stream:
+            return stream, None
+        if stream == 0:
+            if self._side is None:
+                self._side = torch.cuda.Stream(self.dev)
+            other = self._side
+        else:
+            other = torch.cuda.ExternalStream(stream, device=self.dev)
+        other.wait_stream(cur)
+        return other.cuda_stream, other
+
+    def _join(self, stream, other) -> None:
+        if stream is None:
+            torch.cuda.synchronize(self.dev)
+        elif other is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(other)
+
+
+class FluxHandle(_Handle):
+    _destroy = "vc_flux_destroy"
     MAX_BATCH = 4      # samples per launch sequence, as engine.FluxEngine
 
     def __init__(self, params, weights, dev: torch.device):
@@ -108,14 +165,6 @@ class FluxHandle:
             raise hip.VclozeHipError(f"{name}: weight rows / bias must be contiguous")
         hip._check(hip.lib().vc_flux_bind_weight(self.h, name.encode(), w.data_ptr(), hip._p(b), rows, cols,
                                                  w.stride(0) if w.dim() == 2 else cols), f"vc_flux_bind_weight({name})")
-
-    def __del__(self):
-        try:
-            if self.h:
-                hip.lib().vc_flux_destroy(self.h)
-                self.h = C.c_void_p()
-        except Exception:
-            pass
 
     def set_options(self, attn_variant=None, tile_cfg=0, fuse_qnorm=2, fuse_vt=True, qkv_heads=None, fuse_knorm=False,
                     logit_bound=0.0, mlp_first=False, splitk=True) -> None:
@@ -194,10 +243,10 @@ class FluxHandle:
             if kv is None:
                 kv = np.full(B, T + N, np.int32)
         ws = self.workspace(B, T, N, max_steps)
-        base = (ws.data_ptr() + 255) & ~255
+        base, nbytes = self._aligned(ws)
         inp = hip.FluxInputs(B, T, N, max_steps, txt.data_ptr(), y.data_ptr(), _fp(g), _fp(ii), _fp(ti), _ip(kv), _ip(gp),
                              int(bool(guidance_is_bf16)), 0)
-        hip._check(hip.lib().vc_flux_prepare(self.h, C.byref(inp), base, ws.numel() - (base - ws.data_ptr()),
+        hip._check(hip.lib().vc_flux_prepare(self.h, C.byref(inp), base, nbytes,
                                              stream if stream is not None else hip.cur_stream()), "vc_flux_prepare")
         self.geom = (B, T, N, max_steps)
         self._keep = (txt, y, ws)
@@ -264,13 +313,14 @@ class FluxHandle:
         self.sample_ode("euler", x, cond, t_grid, state_is_bf16, stream, trajectory)
 
 
-class VaeHandle:
+class VaeHandle(_Handle):
     """The autoencoder handle of include/vcloze_hip.h (vc_vae_*) behind torch tensors: `AutoEncoder.decode` / `.encode` of ONE
     image as one C call each, one hipGraph launch once the plan is captured.  The launch plan lives in csrc/vae_engine.hip;
     `vae.AutoEncoder`'s own Python-ordered plan is its parity twin (same kernels, same order, same bits).  This class binds the
     module's parameters as `state_dict()` stores them (the library re-lays them out), owns the workspace per image size and - since
     a captured plan holds its argument pointers - one set of input / output tensors per (size, direction, form): arguments are copied
     in, results are returned as fresh tensors."""
+    _destroy, _weight_name = "vc_vae_destroy", "vc_vae_weight_name"
 
     def __init__(self, ae, dev: Optional[torch.device] = None):
         enc, dec = ae.encoder, ae.decoder
@@ -294,12 +344,6 @@ class VaeHandle:
             for n in names:
                 self.bind(n, sd[n + ".weight"], sd[n + ".bias"])
 
-    def weight_names(self) -> list:
-        out, buf = [], C.create_string_buffer(160)
-        while hip.lib().vc_vae_weight_name(self.h, len(out), buf, 160) == 0:
-            out.append(buf.value.decode())
-        return out
-
     def bind(self, name: str, w: torch.Tensor, b: torch.Tensor, stream=None) -> None:
         """vc_vae_bind_weight: w / b as the checkpoint stores them (bf16 or f32, any device - moved to the handle's first)"""
         w, b = w.detach().to(self.dev).contiguous(), b.detach().to(self.dev).contiguous()
@@ -310,14 +354,6 @@ class VaeHandle:
         hip._check(hip.lib().vc_vae_bind_weight(self.h, name.encode(), w.data_ptr(), b.data_ptr(), int(w.dtype == torch.float32), shape,
                                                 w.dim(), stream if stream is not None else hip.cur_stream()), f"vc_vae_bind_weight({name})")
         self._io.clear()
-
-    def __del__(self):
-        try:
-            if self.h:
-                hip.lib().vc_vae_destroy(self.h)
-                self.h = C.c_void_p()
-        except Exception:
-            pass
 
     def plan_count(self) -> int:
         return hip.lib().vc_vae_plan_count(self.h)
@@ -338,39 +374,8 @@ class VaeHandle:
                 self._ws.clear(); self._io.clear()
             ws = torch.empty(self.workspace_bytes(H, W, which) + 256, dtype=torch.uint8, device=self.dev)
             self._ws[key] = ws
-        base = (ws.data_ptr() + 255) & ~255
-        hip._check(hip.lib().vc_vae_prepare(self.h, H, W, which, base, ws.numel() - (base - ws.data_ptr()),
-                                            stream), "vc_vae_prepare")
+        hip._check(hip.lib().vc_vae_prepare(self.h, H, W, which, *self._aligned(ws), stream), "vc_vae_prepare")
         self._prepared = key
-
-    def _stream(self, stream):
-        """(the hipStream_t value to pass, the torch stream the plan runs on when that is not torch's current stream, else None).
-        stream 0 = torch's current stream; when that is the null stream - on which the library runs un-captured - the captured
-        plan runs on a stream of the handle's own.  Any other value is taken as the caller's hipStream_t.  The copies into and out
-        of the argument slots run on torch's current stream, so a plan on another stream is ordered behind and in front of it
-        (`_join`).  None = the un-captured path, on the null stream."""
-        cur = torch.cuda.current_stream(self.dev)
-        if stream is None:
-            cur.synchronize()
-            return None, None
-        if stream == 0 and cur.cuda_stream != 0:
-            return cur.cuda_stream, None
-        if stream != 0 and stream == cur.cuda_stream:
-            return stream, None
-        if stream == 0:
-            if self._side is None:
-                self._side = torch.cuda.Stream(self.dev)
-            other = self._side
-        else:
-            other = torch.cuda.ExternalStream(stream, device=self.dev)
-        other.wait_stream(cur)
-        return other.cuda_stream, other
-
-    def _join(self, stream, other) -> None:
-        if stream is None:
-            torch.cuda.synchronize(self.dev)
-        elif other is not None:
-            torch.cuda.current_stream(self.dev).wait_stream(other)
 
     def _slot(self, key: tuple, shapes) -> tuple:
         """the persistent argument tensors of one (size, direction, form): a captured plan is keyed on their addresses"""
@@ -442,13 +447,14 @@ class VaeHandle:
         return out.clone()
 
 
-class TextHandle:
+class TextHandle(_Handle):
     """The text-encoder handle of include/vcloze_hip.h (vc_text_*) behind torch tensors: `T5EncoderModel.forward` /
     `CLIPTextModel.forward` as one C call, one hipGraph launch per prompt once the plan is captured.  The launch plan lives in
     csrc/text_engine.hip; the modules' own Python-ordered plan (text.py) is its parity twin (same kernels, same order, same bits).
     This class binds the module's bf16 parameters BY POINTER under their state_dict() keys (it keeps them alive; nothing is
     copied) and owns one workspace per sequence length.  The captured plan reads and writes workspace-resident buffers only, so ids
     go in and results come back as the caller's / fresh tensors."""
+    _destroy, _weight_name = "vc_text_destroy", "vc_text_weight_name"
 
     def __init__(self, model, dev: Optional[torch.device] = None):
         from . import text
@@ -475,12 +481,6 @@ class TextHandle:
         for n in names:
             self.bind(n, sd[n])
 
-    def weight_names(self) -> list:
-        out, buf = [], C.create_string_buffer(160)
-        while hip.lib().vc_text_weight_name(self.h, len(out), buf, 160) == 0:
-            out.append(buf.value.decode())
-        return out
-
     def bind(self, key: str, t: torch.Tensor) -> None:
         """vc_text_bind_tensor: a bf16 tensor on the handle's device, bound by pointer and kept alive here"""
         t = t.detach()
@@ -490,14 +490,6 @@ class TextHandle:
         shape = (C.c_int64 * t.dim())(*t.shape)
         hip._check(hip.lib().vc_text_bind_tensor(self.h, key.encode(), t.data_ptr(), shape, t.dim()), f"vc_text_bind_tensor({key})")
         self._bound[key] = t
-
-    def __del__(self):
-        try:
-            if self.h:
-                hip.lib().vc_text_destroy(self.h)
-                self.h = C.c_void_p()
-        except Exception:
-            pass
 
     def plan_count(self) -> int:
         return hip.lib().vc_text_plan_count(self.h)
@@ -517,13 +509,9 @@ class TextHandle:
                 self._ws.clear()
             ws = torch.empty(self.workspace_bytes(L) + 256, dtype=torch.uint8, device=self.dev)
             self._ws[L] = ws
-        base = (ws.data_ptr() + 255) & ~255
         self._prepared = None
-        hip._check(hip.lib().vc_text_prepare(self.h, L, base, ws.numel() - (base - ws.data_ptr()), stream), "vc_text_prepare")
+        hip._check(hip.lib().vc_text_prepare(self.h, L, *self._aligned(ws), stream), "vc_text_prepare")
         self._prepared = L
-
-    _stream = VaeHandle._stream
-    _join = VaeHandle._join
 
     def encode(self, ids: torch.Tensor, stream=0, want_hidden: bool = True, want_pooled: Optional[bool] = None):
         """ids [n, L] (any integer dtype) -> (hidden [n, L, D] bf16 or None, pooled [n, D] bf16 or None); pooled: CLIP only (its
