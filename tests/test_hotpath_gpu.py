@@ -7,6 +7,7 @@ untouched, and runs twice where the route is documented as reproducible.  Shapes
 import pytest
 import torch
 
+from tests import attn_schedule as S
 from tests import budget as B
 
 pytestmark = pytest.mark.gpu
@@ -376,10 +377,10 @@ def test_attention_in_kernel_query_norm_within_budget(hip, variant, L, kv_len, g
             within(got[lv], (ref[lv.to(ref.device)], mags, f32[lv.to(ref.device)]), f"attention v{variant} q_norm lb={lb} L={L} b={b} h={h}")
 
 
-def tail_plan(hip, L, H, variant, prescaled):
+def tail_plan(hip, L, H, variant, prescaled, Bn=1):
     a = hip.Attention()
     a.qkv = a.vt = a.out = a.scratch = 0x1000                              # never dereferenced by the planner
-    a.B, a.L, a.Lpad, a.H, a.variant = 1, L, (L + 63) // 64 * 64, H, variant
+    a.B, a.L, a.Lpad, a.H, a.variant = Bn, L, (L + 63) // 64 * 64, H, variant
     a.ld, a.bstride, a.ldo, a.out_bstride = 3 * H * 128, L * 3 * H * 128, H * 128, L * H * 128
     a.scratch_bytes = hip.lib().vc_attention_scratch_bytes()
     a.q_prescaled, a.logit_bound = int(prescaled), 0.0
@@ -502,3 +503,126 @@ def test_attention_one_hot_tail_split(hip, variant, which):
     assert plan[8] >= 0 and plan[9] > 0, plan
     routes = [(variant, lb, "prescaled") for lb in (0.0, 100.0)] if pre else [(7, 0.0, "stored")]
     one_hot_run(hip, L, H, 1, [(None, None)], routes, None, None)
+
+
+# ---------------------------------------------------------------- attention: the tail split at uneven, sparse and batched schedules
+# (name, family, (B, H) candidates, classes of tests/attn_schedule.py the geometry must have, the pick at 256 CUs as (B, L, H))
+EDGE_GEOMS = [
+    ("uneven_sparse", 64, [(1, 1), (1, 3)], {"uneven", "xcd_without_tail", "empty_chunks"}, (1, 321, 1)),
+    ("uneven_sparse_sample_1", 64, [(2, 1), (2, 3)], {"uneven", "xcd_without_tail", "empty_chunks", "tail_sample_ge1"}, (2, 321, 1)),
+    ("nine_pieces_uneven", 64, [(1, 1), (1, 3)], {"uneven", "pieces_ge_9"}, (1, 513, 1)),
+    ("w_pieces", 64, [(1, 1), (1, 2)], {"pieces_eq_W"}, (1, 1985, 1)),
+    ("uneven_behind_a_round_batch", 64, [(3, 11), (3, 7), (2, 11)], {"uneven", "behind_whole_round", "batch", "tail_sample_ge1"}, (3, 2049, 11)),
+    ("even_behind_a_round_batch", 64, [(3, 24), (2, 24)], {"even", "behind_whole_round", "batch", "tail_sample_ge1"}, (3, 769, 24)),
+    ("v7_sparse", 32, [(1, 1), (1, 3)], {"empty_chunks"}, (1, 257, 1)),
+    ("v7_sparse_batch", 32, [(2, 1), (2, 3)], {"empty_chunks", "batch", "tail_sample_ge1"}, (2, 257, 1)),
+]
+EDGE_NAMES = [g[0] for g in EDGE_GEOMS]
+_edge_cache = {}
+
+
+def edge_geometry(hip, name):
+    """(B, L, H, family, largest piece count) of an edge class at THIS device's CU count: the first (B, H) candidate, and the
+    smallest L <= 3000 with it, whose classes (tests/attn_schedule.py, run for this CU count) include the wanted ones and for which
+    vc_attention_plan reports a split.  None is a failure, not a skip; only a CU count that is no multiple of 8 skips (the
+    planner never splits the 64-query family there, and the classes are defined on the per-XCD schedule)."""
+    n_cu = hip.device_cus(DEV)
+    if n_cu % 8:
+        pytest.skip(f"{n_cu} CUs: no multiple of 8, no per-XCD schedule")
+    if name not in _edge_cache:
+        _, family, cands, want, at256 = next(g for g in EDGE_GEOMS if g[0] == name)
+        pick = next(((Bn, L, H) for Bn, H in cands for L in range(65, 3001) if want <= S.classes(Bn, L, H, n_cu, family)), None)
+        assert pick is not None, f"{name}: no geometry with L <= 3000 has the classes {sorted(want)} at {n_cu} CUs"
+        if n_cu == 256:
+            assert pick == at256, (name, pick, at256)
+        Bn, L, H = pick
+        g = S.geom(Bn, L, H, n_cu, family)
+        rs = (S.plan64 if family == 64 else S.plan32)(g)
+        for v in ((12, 28) if family == 64 else (7,)):
+            plan = tail_plan(hip, L, H, v, v != 7, Bn)
+            assert plan[8:11] == [rs["full_rounds"], rs["tail_items"], rs["tail_units"]] and plan[11] == (v == 28), (name, v, plan, rs)
+            assert plan[12] == (0 if v == 28 else rs["merge_grid"]), (name, v, plan, rs)
+            print(f"edge class {name}: (B, L, H) = {pick} at {n_cu} CUs, variant {v} plan {plan[:13]}")
+        assert want <= S.classes(Bn, L, H, n_cu, family)
+        _edge_cache[name] = (Bn, L, H, family, S.max_pieces(g, family))
+        print(f"edge class {name}: items {g.items}, {g.nkt} tiles, classes {sorted(S.classes(Bn, L, H, n_cu, family))}, at most {_edge_cache[name][4]} pieces per item")
+    return _edge_cache[name]
+
+
+def flags_all_zero(hip, plan):
+    """the flag words of the in-launch combine: from plan word 13 to the end of the attention scratch"""
+    return int(hip.attention_scratch(torch.device(DEV))[plan[13]:].to(torch.int32).sum()) == 0
+
+
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_attention_one_hot_edge_schedules(hip, name):
+    """The one-hot test (every live key is some row's partner: ALL rows of all heads and samples, bit for bit) at the schedules that
+    H = 24 and B = 1 never produce: XCDs with different shares or no tail at all, fewer (item, tile) units than workgroups - empty
+    chunks, and workgroups of variant 28 that own a combine task but no work - , 9 and W pieces per item, tail items of samples 1 and
+    2.  A tile lost, doubled or given to the wrong item, head or sample is a wrong V row (V differs by head and sample).  Variants
+    12 and 28 prescaled, with a running max and at logit_bound 100, and 12 with the scale route (the per-item kernel's writer);
+    variant 7 stored.  Twice each (one_hot_run); the flag words are zero afterwards."""
+    Bn, L, H, family, _ = edge_geometry(hip, name)
+    if family == 64:
+        routes = [(v, lb, "prescaled") for v in (12, 28) for lb in (0.0, 100.0)] + [(12, 0.0, "scale")]
+    else:
+        routes = [(7, 0.0, "stored")]
+    one_hot_run(hip, L, H, Bn, [(None, None)] * Bn, routes, None, None)
+    assert flags_all_zero(hip, tail_plan(hip, L, H, routes[0][0], family == 64, Bn)), "flag words left set"
+
+
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_attention_edge_schedules_within_budget(hip, name):
+    """Normed data at the same geometries against budget.attention_case, ALL heads of all samples; all rows where L <= 1024, else the
+    512-row rule of test_attention_tail_split_within_budget.  The route's piece count is the restatement's largest.  Variant 28
+    equals variant 12 bit for bit, every route twice with the same bits, the out pad stays NaN, the flag words end zero."""
+    Bn, L, H, family, pieces = edge_geometry(hip, name)
+    pre = family == 64
+    D = H * 128
+    g = torch.Generator().manual_seed(L + 7 * Bn + H)
+    x = torch.randn(Bn * L, 3, H, 128, generator=g)
+    x[:, :2] = x[:, :2] / x[:, :2].pow(2).mean(-1, keepdim=True).sqrt()
+    qkv = x.reshape(Bn * L, 3 * D).to(BF)
+    if pre:
+        qkv[:, :D] = (qkv[:, :D].float() * C32).to(BF)
+    qd = qkv.to(DEV)
+    vt = torch.zeros(Bn, H, 128, (L + 63) // 64 * 64, dtype=BF, device=DEV)
+    vt[:, :, :, :L] = qd[:, 2 * D:].reshape(Bn, L, H, 128).permute(0, 2, 3, 1)
+    outs = {}
+    for variant in ((12, 28) if pre else (7,)):
+        for lb in ((0.0, 40.0) if pre else (0.0,)):
+            two = []
+            for _ in range(2):
+                buf = torch.full((Bn * L, D + 8), NAN, dtype=BF, device=DEV)
+                hip.attention(qd, vt, buf[:, :D], L, H, variant=variant, B=Bn, q_prescaled=pre, logit_bound=lb)
+                torch.cuda.synchronize()
+                assert untouched(buf[:, D:], NAN), "pad columns of out written"
+                two.append(buf[:, :D].cpu())
+            assert B.bits_equal(two[0], two[1]), f"{name} v{variant} lb={lb}: not reproducible from launch to launch"
+            outs[(variant, lb)] = two[0]
+        assert flags_all_zero(hip, tail_plan(hip, L, H, variant, pre, Bn)), "flag words left set"
+    if pre:
+        for lb in (0.0, 40.0):
+            assert B.bits_equal(outs[(28, lb)], outs[(12, lb)]), f"{name} lb={lb}: the in-launch combine differs from the merge kernel"
+    if L <= 1024:
+        rows = torch.arange(L)
+    else:
+        must = sorted({0, 255, 256, L - 1} | set(range(0, L, 64)))
+        extra = torch.randperm(L, generator=g)[:max(0, 512 - len(must))].tolist()
+        rows = torch.tensor(sorted(set(must) | set(extra))[:max(512, len(must))])
+        assert set(must) <= set(rows.tolist())
+    live = torch.ones(L, dtype=torch.bool)
+    route = B.attention_route("prescaled" if pre else "stored", "f16" if pre else "f32", pieces=pieces)
+    worst = {}
+    for b in range(Bn):
+        for h in range(H):
+            r = slice(b * L, (b + 1) * L)
+            q, k, v = qd[r, h * 128:(h + 1) * 128], qd[r, (H + h) * 128:(H + h + 1) * 128], qd[r, (2 * H + h) * 128:(2 * H + h + 1) * 128]
+            assert float((q.double() @ k.double().t()).abs().max()) * (1.0 if pre else B.QK_PRESCALE) < 40.0
+            case = B.attention_case(q, k, v, live, route, rows=rows.to(DEV))
+            for (variant, lb), out in outs.items():
+                if variant == 28:
+                    continue                                                # the bits of variant 12, asserted above
+                w = within(out[r][rows, h * 128:(h + 1) * 128], case, f"attention {name} v{variant} lb={lb} (B, L, H)=({Bn}, {L}, {H}) b={b} h={h}")
+                worst[(variant, lb)] = max(worst.get((variant, lb), 0.0), w)
+    print(f"edge class {name} (B, L, H) = ({Bn}, {L}, {H}): worst error / budget per route {worst}")

@@ -761,6 +761,94 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(const Attn64Args a) {
 #endif
 }
 
+// The in-launch combine of the stream form (Attn64Args.inmerge): task (tail item `it` of this XCD, query block qb) -> workgroup
+// slot (2 it + qb) % W: out = sum_p l_p O_p / sum_p l_p over the item's pieces in chunk order - the arithmetic and the order of
+// attn64_merge_kernel (merge_fold64: bit-identical), the pieces written by workgroups of this launch.  Every polled word is zero
+// before a launch and zero again after it: a flag is consumed by exactly one task, which clears it.  EVERY workgroup of the grid
+// runs this, also one without any work of its own: with fewer (item, tile) units than workgroups the owner of a task can be a
+// workgroup whose chunk is empty.
+VC_DEV void attn64s_combine(const Attn64Args& a, int G, int nkt_all) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lq = lane & 31, hh = lane >> 5;
+  const int L = a.L;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const Sched64 sc = sched64(xcd, G, a.items, nkt_all);
+  for (int T = slot; T < 2 * sc.tail; T += sc.W) {
+    const int it = T >> 1, qb = T & 1;
+    const int u0 = it * nkt_all, u1 = u0 + nkt_all;
+    int c = (int)(((long)u0 * sc.W) / sc.units);
+    while (c > 0 && chunk_begin64(c, sc.units, sc.W) > u0) --c;
+    while (c + 1 < sc.W && chunk_begin64(c + 1, sc.units, sc.W) <= u0) ++c;
+    if (chunk_begin64(c + 1, sc.units, sc.W) >= u1) continue;      // the whole item ran inside one chunk: already written
+    auto next_chunk = [&](int cc) __attribute__((always_inline)) {
+      while (cc < sc.W && chunk_begin64(cc, sc.units, sc.W) < u1 && chunk_begin64(cc + 1, sc.units, sc.W) == chunk_begin64(cc, sc.units, sc.W)) ++cc;
+      return (cc < sc.W && chunk_begin64(cc, sc.units, sc.W) < u1) ? cc : -1;
+    };
+    const long ml_off = PART64_O_BYTES + ((wave * 2 + qb) * 64 + lane) * 8;
+    const long o_off = ((long)(wave * 2 + qb) * 16 * 64 + lane) * 8;
+    float acc[16][4];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][e] = 0.f;
+    float wsum = 0.f, m = -INFINITY;
+    // the item's pieces in chunk order, FOUR at a time (two or three in all at the product's geometries; up to W when an
+    // XCD has a single tail item): all flags of a batch first, then ALL its loads in flight together (a chain of memory
+    // round trips otherwise), then the folds in order
+    constexpr int MAXP = 4;
+    for (int cc = next_chunk(c); cc >= 0;) {
+      int pcs[MAXP], np = 0;
+      for (; cc >= 0 && np < MAXP; cc = next_chunk(cc + 1))
+        pcs[np++] = (cc * 8 + xcd) * 2 + (it - chunk_begin64(cc, sc.units, sc.W) / nkt_all);
+      // ONE relaxed agent-scope read of every flag of the batch, all in flight together (the pieces were published ~60 tiles
+      // ago: nothing spins in practice); what is not there yet is polled, bounded - a piece that never arrives costs wrong
+      // rows, not a hung GPU
+      uint32_t fl[MAXP];
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j) fl[j] = j < np ? __hip_atomic_load(a.flags + pcs[j] * 2 + qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j)
+        if (j < np && fl[j] != 1u)
+          for (unsigned spins = 0; __hip_atomic_load(a.flags + pcs[j] * 2 + qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u; ++spins) {
+            __builtin_amdgcn_s_sleep(16);
+            if (spins > (1u << 20)) break;
+          }
+      f16x4 v[MAXP][16];
+      f32x2 ml[MAXP];
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j)
+        if (j < np) {
+          const char* pp = (const char*)a.part + (long)pcs[j] * PART64_BYTES;
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            v[j][i] = __builtin_bit_cast(f16x4, __hip_atomic_load((const uint64_t*)(pp + o_off + i * 512), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+          ml[j] = __builtin_bit_cast(f32x2, __hip_atomic_load((const uint64_t*)(pp + ml_off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j)
+        if (j < np) merge_fold64(acc, wsum, m, v[j], ml[j]);
+      __syncthreads();               // every wave has seen the flags and holds its part of the pieces
+      if (tid == 0)
+        for (int j = 0; j < np; ++j) __hip_atomic_store(a.flags + pcs[j] * 2 + qb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int id = sc.start + sc.rounds * sc.W + it;
+    const int qb_i = id % a.qblocks, bh = id / a.qblocks;
+    const int h = bh % a.H, b = bh / a.H;
+    const int q = qb_i * QB + wave * QW + qb * 32 + lq;
+    const float inv = 1.0f / wsum;
+    bf16_t* orow = a.out + (long)b * a.out_bstride + (long)min(q, L - 1) * a.ldo + h * 128 + hh * 8;
+#pragma unroll
+    for (int mm = 0; mm < 8; ++mm) {
+      uint32_t x0 = v_cvt_pk(acc[2 * mm][0] * inv, acc[2 * mm][1] * inv), x1 = v_cvt_pk(acc[2 * mm][2] * inv, acc[2 * mm][3] * inv);
+      uint32_t y0 = v_cvt_pk(acc[2 * mm + 1][0] * inv, acc[2 * mm + 1][1] * inv), y1 = v_cvt_pk(acc[2 * mm + 1][2] * inv, acc[2 * mm + 1][3] * inv);
+      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x0), "+v"(y0));
+      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x1), "+v"(y1));
+      const u32x4 wv = {x0, x1, y0, y1};
+      if (q < L) *(u32x4*)(orow + mm * 16) = wv;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // STREAM form of the bounded-logit kernel (round 6): the product's launches at cfg 2 / 3 / 5 - bounded logits AND queries that
 // arrive normalised, rotated and scaled from the qkv GEMM's epilogue (VcAttention.q_prescaled), so an item has no arithmetic
@@ -866,7 +954,10 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
   };
 #define VC_SEG_ADVANCE do { c_id = n_id; c_kt0 = n_kt0; c_kt1 = n_kt1; c_piece = n_piece; c_kvlen = n_kvlen; c_gap_lo = n_gap_lo; \
                             c_gap_hi = n_gap_hi; c_ko = n_ko; c_vo = n_vo; have_next = next_seg(); } while (0)
-  if (!next_seg()) return;
+  if (!next_seg()) {      // no work of its own (an empty chunk, no whole round): its combine tasks remain
+    if (a.inmerge) attn64s_combine(a, G, nkt_all);
+    return;
+  }
   VC_SEG_ADVANCE;
 
   using I0 = std::integral_constant<int, 0>;
@@ -1329,8 +1420,10 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
   // ---- a.inmerge: a piece is PUBLISHED (flag = 1 for both query blocks) once its stores are complete in every wave: not by
   // draining the LDS-DMA stream behind store_out, but one item later - every step in between ended with a counted vmcnt
   // that covers the (older) stores and a barrier ----
+  // (only where the pieces are combined in this launch: without a.inmerge the merge kernel reads no flag, and a word left at 1
+  // would be taken for a finished piece by the next launch that does combine)
   auto publish = [&](int piece) __attribute__((always_inline)) {
-    if (tid == 0) {
+    if (a.inmerge && tid == 0) {
       __hip_atomic_store(a.flags + piece * 2 + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(a.flags + piece * 2 + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1445,10 +1538,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
     if (hard) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's look-ahead pieces land before the ring restarts
   }
   // =================================== a.inmerge: the tail items' pieces are combined here ===================================
-  // task (tail item `it` of this XCD, query block qb) -> workgroup slot (2 it + qb) % W: out = sum_p l_p O_p / sum_p l_p over the
-  // item's pieces in chunk order - the arithmetic and the order of attn64_merge_kernel (merge_fold64: bit-identical), the pieces
-  // written by workgroups of this launch many tiles ago.  Every polled word is zero before a launch and zero again after it: a
-  // flag is consumed by exactly one task, which clears it.  (Requesting the first task's pieces before the workgroup's last O
+  // (attn64s_combine; the pieces were written many tiles ago.  Requesting the first task's pieces before the workgroup's last O
   // goes out - to run their round trips under those stores - was built: 136 more live registers across store_out, 924
   // compiler-generated accumulator moves; not kept.)
   if (a.inmerge) {
@@ -1457,82 +1547,7 @@ __global__ __launch_bounds__(256, 1) void attn64s_kernel(const Attn64Args a) {
       __syncthreads();
       publish(pub);
     }
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const Sched64 sc = sched64(xcd, G, a.items, nkt_all);
-    for (int T = slot; T < 2 * sc.tail; T += sc.W) {
-      const int it = T >> 1, qb = T & 1;
-      const int u0 = it * nkt_all, u1 = u0 + nkt_all;
-      int c = (int)(((long)u0 * sc.W) / sc.units);
-      while (c > 0 && chunk_begin64(c, sc.units, sc.W) > u0) --c;
-      while (c + 1 < sc.W && chunk_begin64(c + 1, sc.units, sc.W) <= u0) ++c;
-      if (chunk_begin64(c + 1, sc.units, sc.W) >= u1) continue;      // the whole item ran inside one chunk: already written
-      auto next_chunk = [&](int cc) __attribute__((always_inline)) {
-        while (cc < sc.W && chunk_begin64(cc, sc.units, sc.W) < u1 && chunk_begin64(cc + 1, sc.units, sc.W) == chunk_begin64(cc, sc.units, sc.W)) ++cc;
-        return (cc < sc.W && chunk_begin64(cc, sc.units, sc.W) < u1) ? cc : -1;
-      };
-      const long ml_off = PART64_O_BYTES + ((wave * 2 + qb) * 64 + lane) * 8;
-      const long o_off = ((long)(wave * 2 + qb) * 16 * 64 + lane) * 8;
-      float acc[16][4];
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][e] = 0.f;
-      float wsum = 0.f, m = -INFINITY;
-      // the item's pieces in chunk order, FOUR at a time (two or three in all at the product's geometries; up to W when an
-      // XCD has a single tail item): all flags of a batch first, then ALL its loads in flight together (a chain of memory
-      // round trips otherwise), then the folds in order
-      constexpr int MAXP = 4;
-      for (int cc = next_chunk(c); cc >= 0;) {
-        int pcs[MAXP], np = 0;
-        for (; cc >= 0 && np < MAXP; cc = next_chunk(cc + 1))
-          pcs[np++] = (cc * 8 + xcd) * 2 + (it - chunk_begin64(cc, sc.units, sc.W) / nkt_all);
-        // ONE relaxed agent-scope read of every flag of the batch, all in flight together (the pieces were published ~60 tiles
-        // ago: nothing spins in practice); what is not there yet is polled, bounded - a piece that never arrives costs wrong
-        // rows, not a hung GPU
-        uint32_t fl[MAXP];
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j) fl[j] = j < np ? __hip_atomic_load(a.flags + pcs[j] * 2 + qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j)
-          if (j < np && fl[j] != 1u)
-            for (unsigned spins = 0; __hip_atomic_load(a.flags + pcs[j] * 2 + qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u; ++spins) {
-              __builtin_amdgcn_s_sleep(16);
-              if (spins > (1u << 20)) break;
-            }
-        f16x4 v[MAXP][16];
-        f32x2 ml[MAXP];
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j)
-          if (j < np) {
-            const char* pp = (const char*)a.part + (long)pcs[j] * PART64_BYTES;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              v[j][i] = __builtin_bit_cast(f16x4, __hip_atomic_load((const uint64_t*)(pp + o_off + i * 512), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            ml[j] = __builtin_bit_cast(f32x2, __hip_atomic_load((const uint64_t*)(pp + ml_off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-          }
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j)
-          if (j < np) merge_fold64(acc, wsum, m, v[j], ml[j]);
-        __syncthreads();               // every wave has seen the flags and holds its part of the pieces
-        if (tid == 0)
-          for (int j = 0; j < np; ++j) __hip_atomic_store(a.flags + pcs[j] * 2 + qb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const int id = sc.start + sc.rounds * sc.W + it;
-      const int qb_i = id % a.qblocks, bh = id / a.qblocks;
-      const int h = bh % a.H, b = bh / a.H;
-      const int q = qb_i * QB + wave * QW + qb * 32 + lq;
-      const float inv = 1.0f / wsum;
-      bf16_t* orow = a.out + (long)b * a.out_bstride + (long)min(q, L - 1) * a.ldo + h * 128 + hh * 8;
-#pragma unroll
-      for (int mm = 0; mm < 8; ++mm) {
-        uint32_t x0 = v_cvt_pk(acc[2 * mm][0] * inv, acc[2 * mm][1] * inv), x1 = v_cvt_pk(acc[2 * mm][2] * inv, acc[2 * mm][3] * inv);
-        uint32_t y0 = v_cvt_pk(acc[2 * mm + 1][0] * inv, acc[2 * mm + 1][1] * inv), y1 = v_cvt_pk(acc[2 * mm + 1][2] * inv, acc[2 * mm + 1][3] * inv);
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x0), "+v"(y0));
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x1), "+v"(y1));
-        const u32x4 wv = {x0, x1, y0, y1};
-        if (q < L) *(u32x4*)(orow + mm * 16) = wv;
-      }
-    }
+    attn64s_combine(a, G, nkt_all);
   }
 #ifdef VC_ATTN_TIMESTAMPS
   if (a.debug_ts && tid == 0) {
