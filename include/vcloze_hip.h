@@ -341,6 +341,46 @@ int vc_pack_latent(const void* latent, void* tokens, int32_t C, int32_t h, int32
 int vc_pack_mask(const void* mask, void* tokens, int32_t H, int32_t W, int64_t ld, int32_t col0, void* stream);
 int vc_unpack_latent(const void* tokens, int64_t ld, int32_t col0, void* latent, int32_t C, int32_t h, int32_t w, void* stream);
 
+/* ---- noise source: a counter-based Gaussian stream of this library's own (csrc/rng.hip) ----
+ * The reference draws its noise with torch.randn(generator=...) (visualcloze.py:217,394-399) and torch.randn_like (autoencoder.py:272);
+ * torch's device stream depends on the grid torch picks from the device's properties and cannot be restated by a host without
+ * torch.  This stream can: every element depends on (seed, position) ONLY - not on the launch geometry, not on how a draw is
+ * split into calls, not on the memory layout it is written in.  It is NOT torch's stream: a seed here does not reproduce the
+ * images torch's generator gives for the same seed.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry
+ * points by SYMBOL - look up vc_randn.
+ *
+ * THE STREAM (the contract).  Element at stream position p = offset + i, offset a uint64, offset + n does not wrap:
+ *   block    b = p >> 2
+ *   counter  (lo32(b), hi32(b), 0, 0)
+ *   key      (lo32(seed), hi32(seed))
+ * Philox4x32-10: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl increments W = (0x9E3779B9, 0xBB67AE85), ten rounds, giving
+ * x0..x3.  One round is
+ *   c <- (hi(M1*c2)^c1^k0, lo(M1*c2), hi(M0*c0)^c3^k1, lo(M0*c0))
+ * followed by k += W.  Known answers (counter | key | output):
+ *   00000000 00000000 00000000 00000000 | 00000000 00000000 | 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   ffffffff ffffffff ffffffff ffffffff | ffffffff ffffffff | 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   243f6a88 85a308d3 13198a2e 03707344 | a4093822 299f31d0 | d16cfe09 94fdcceb 5001e420 24126ea1
+ * Normals: two Box-Muller pairs per block, in f32:
+ *   u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1],  u2 = (x1 >> 8) * 2^-24 in [0, 1)      (both exact in f32)
+ *   r = sqrt(-2 ln u1),  z0 = r cos(2 pi u2),  z1 = r sin(2 pi u2);  z2, z3 the same from x2, x3
+ * Element p is z[p & 3].  u1 = 1 gives r = 0; the largest possible r is sqrt(48 ln 2) ~ 5.77: no inf or NaN can occur.
+ * VC_RNG_U32 words are exact; the normals of a restatement agree with the device's to f32 arithmetic (tests/noise_ref.py,
+ * tests/test_noise_gpu.py: within 1/64 bf16 ulp of r of the fp64 value, plus the bf16 store's half ulp). */
+#define VC_RNG_BF16 0  /* the f32 normal rounded to nearest-even, as torch.randn(...).to(bf16) rounds */
+#define VC_RNG_F32 1
+#define VC_RNG_U32 2   /* the raw word x[p & 3] (exact tests) */
+/* out[i] = element offset + i of the stream of `seed`, i < n.  Any n >= 1, any offset, any base aligned to the element size (2 / 4
+ * / 4 bytes); stores are 16 bytes wide wherever the base and the phase offset & 3 allow, the element-wise head and tail give the
+ * same values.  seed and offset are by-value kernel arguments: the call is legal under stream capture, and A REPLAYED GRAPH
+ * REPEATS ITS NOISE - a caller who wants fresh noise per replay draws outside the graph.  Arguments are checked before the device
+ * is touched (VC_ERR_ARG: null pointer, n <= 0, unknown dtype, offset + n wrapping, misaligned base). */
+int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+/* The sampler's start state x(t0) in one launch, no intermediate tensor: latent element (c, y, x) of a [C, h, w] draw takes stream
+ * position offset + (c*h + y)*w + x and is written as bf16 straight into the packed-token layout of vc_pack_latent, under its
+ * ld / col0 / alignment rules (even C, h, w; ld and col0 multiples of 8; 16-byte aligned token base).  Bit-identical to a
+ * VC_RNG_BF16 draw of C*h*w elements into [C, h, w] followed by vc_pack_latent. */
+int vc_randn_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t offset, void* stream);
+
 /* ---- VAE decoder glue (reference twin models/modules/autoencoder.py): activations are NHWC bf16
  * [H*W, C], C % 8 == 0; the 3x3 convolutions and 1x1 projections themselves are vc_gemm over these buffers. ----
  * im2col3x3:   src [Hs*Ws, C] -> dst [H*W, 9*C], column (dy*3+dx)*C + c of row (y,x) = src(y+dy-1, x+dx-1), zero outside

@@ -195,6 +195,12 @@ int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora
   return vc_lora_merge_launch(w, w_is_f32, ldw, lora_a, lda, lora_b, ldb, scale, out, ldo, bias, bias_is_f32, lora_b_bias, bias_out,
                               out_features, in_features, rank, S(stream), ERRBUF);
 }
+int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
+  return vc_randn_launch(out, dtype, n, seed, offset, S(stream), ERRBUF);
+}
+int vc_randn_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t offset, void* stream) {
+  return vc_randn_tokens_launch(tokens, C, h, w, ld, col0, seed, offset, S(stream), ERRBUF);
+}
 
 /* ---- handle API (flux_engine.hip) ---- */
 int vc_flux_create(const VcFluxConfig* cfg, void** handle) { return vc_flux_create_impl(cfg, handle, ERRBUF); }

@@ -1,0 +1,173 @@
+// Noise source: the counter-based Gaussian stream of include/vcloze_hip.h (Philox4x32-10 + Box-Muller in f32).
+//   randn          out[i] = element offset + i of the stream of `seed`, as bf16 / f32 / the raw 32-bit word
+//   randn_tokens   a [C, h, w] draw written as bf16 straight into pack_latent's token layout (pack.hip): the sampler's x(t0)
+// Every element depends on (seed, position) only: a thread recomputes the Philox block(s) of whatever positions it stores, so
+// the launch geometry, the split of a draw into calls and the layout written do not show in the values.  Store-rate kernels
+// (about 100 integer and 20 float operations per block of 4 outputs): the draws of a grid are ~0.2 M values, nothing here is
+// tuned beyond 16-byte stores and a capped grid.  seed / offset are kernel arguments by value: legal under stream capture, and
+// a replayed graph repeats its noise.
+//
+// Precision: ln, sqrt and sin/cos are the PRECISE device functions (logf, sqrtf, sincospif on the exact argument 2*u2, a few f32
+// ulps each), not the bare v_log_f32 / v_sin_f32 approximations, whose error near u1 = 1 (ln u1 -> 0) and absolute error of the
+// sine no guide states: the stream is a contract a host restates, and the budget of tests/test_noise_gpu.py (1/64 bf16 ulp of r
+// against the fp64 value, i.e. >= 2^-14 r) is met with room by ~6 f32 roundings (2^-21 r), whatever u1 and u2.
+#include "common.h"
+#include "vcloze_internal.h"
+
+namespace {
+
+constexpr uint32_t PH_M0 = 0xD2511F53u, PH_M1 = 0xCD9E8D57u, PH_W0 = 0x9E3779B9u, PH_W1 = 0xBB67AE85u;
+constexpr int RNG_MAX_BLOCKS = 2048;      // 8 workgroups of 256 per CU of a 256-CU device; the grid-stride loop takes the rest
+
+// x0..x3 of block b: counter (lo32(b), hi32(b), 0, 0), key (k0, k1) = (lo32(seed), hi32(seed))
+VC_DEV void philox4x32_10(uint64_t b, uint32_t k0, uint32_t k1, uint32_t (&x)[4]) {
+  uint32_t c0 = (uint32_t)b, c1 = (uint32_t)(b >> 32), c2 = 0, c3 = 0;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(PH_M0, c0), l0 = PH_M0 * c0, h1 = __umulhi(PH_M1, c2), l1 = PH_M1 * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += PH_W0; k1 += PH_W1;
+  }
+  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+// one Box-Muller pair: u1 in (0, 1] and u2 in [0, 1) are exact in f32 (24-bit integers times 2^-24)
+VC_DEV void normal_pair(uint32_t xa, uint32_t xb, float& za, float& zb) {
+  const float u1 = (float)((xa >> 8) + 1u) * 0x1p-24f, u2 = (float)(xb >> 8) * 0x1p-24f;
+  const float r = sqrtf(0.0f - 2.0f * logf(u1));        // u1 = 1: r = +0
+  float s, c;
+  sincospif(2.0f * u2, &s, &c);
+  za = r * c; zb = r * s;
+}
+
+// the four 32-bit words block b stores: the raw words (VC_RNG_U32) or the f32 bit patterns of z0..z3
+template <int DT>
+VC_DEV void block_words(uint64_t b, uint32_t k0, uint32_t k1, uint32_t (&v)[4]) {
+  philox4x32_10(b, k0, k1, v);
+  if (DT != VC_RNG_U32) {
+    float z[4];
+    normal_pair(v[0], v[1], z[0], z[1]);
+    normal_pair(v[2], v[3], z[2], z[3]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = __builtin_bit_cast(uint32_t, z[e]);
+  }
+}
+VC_DEV uint32_t pick(const uint32_t (&v)[4], uint32_t j) { return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3]; }
+VC_DEV uint32_t pack2(uint32_t flo, uint32_t fhi) { return pack2bf(__builtin_bit_cast(float, flo), __builtin_bit_cast(float, fhi)); }
+
+// Work items: `nvec` 16-byte chunks first (elements head + w*E ..: out + head is 16-byte aligned and offset + head a multiple
+// of 4, so a chunk is one (f32 / u32) or two (bf16) whole blocks), then the n - nvec*E single elements of the head and the tail.
+// Where the phase does not allow chunks (offset + head not a multiple of 4) the host passes head = n, nvec = 0.
+template <int DT>
+__global__ __launch_bounds__(256) void randn_kernel(void* __restrict__ out, long n, uint64_t seed, uint64_t offset, long head, long nvec) {
+  constexpr int E = DT == VC_RNG_BF16 ? 8 : 4;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const long total = nvec + (n - nvec * E);
+  for (long wi = blockIdx.x * 256L + threadIdx.x; wi < total; wi += gridDim.x * 256L) {
+    if (wi < nvec) {
+      const long i = head + wi * E;
+      const uint64_t b = (offset + (uint64_t)i) >> 2;
+      uint32_t v[4];
+      block_words<DT>(b, k0, k1, v);
+      u32x4 o;
+      if (DT == VC_RNG_BF16) {
+        uint32_t v2[4];
+        block_words<DT>(b + 1, k0, k1, v2);
+        o[0] = pack2(v[0], v[1]); o[1] = pack2(v[2], v[3]); o[2] = pack2(v2[0], v2[1]); o[3] = pack2(v2[2], v2[3]);
+        *(u32x4*)((bf16_t*)out + i) = o;
+      } else {
+        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+        *(u32x4*)((uint32_t*)out + i) = o;
+      }
+    } else {
+      const long s = wi - nvec, i = s < head ? s : s + nvec * E;     // the head, then the tail behind the chunks
+      const uint64_t p = offset + (uint64_t)i;
+      uint32_t v[4];
+      block_words<DT>(p >> 2, k0, k1, v);
+      const uint32_t word = pick(v, (uint32_t)p & 3u);
+      if (DT == VC_RNG_BF16) ((bf16_t*)out)[i] = f2bf(__builtin_bit_cast(float, word));
+      else ((uint32_t*)out)[i] = word;
+    }
+  }
+}
+
+// out[tok * ld + col0 + c*4 + ph*2 + pw] = bf16(z(offset + (c*h + 2*hh + ph)*w + 2*ww + pw)),  tok = hh*(w/2) + ww: a thread
+// writes one 16-byte chunk (2 channels x 2 x 2) of a token row; each of its four words is the pair (pw 0, pw 1) at consecutive
+// positions, one block unless the pair starts at the last element of one
+__global__ __launch_bounds__(256) void randn_tokens_kernel(bf16_t* __restrict__ out, int C, int h, int w, long ld, int col0, uint64_t seed,
+                                                          uint64_t offset) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const int w2 = w >> 1, cpt = C >> 1;
+  const long total = (long)(h >> 1) * w2 * cpt;
+  for (long wi = blockIdx.x * 256L + threadIdx.x; wi < total; wi += gridDim.x * 256L) {
+    const long tok = wi / cpt;
+    const int ck = (int)(wi - tok * cpt), hh = (int)(tok / w2), ww = (int)(tok - (long)hh * w2);
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 2 * ck + (e >> 1), ph = e & 1;
+      const uint64_t p = offset + ((uint64_t)c * h + 2 * hh + ph) * w + 2 * ww;
+      const uint32_t j = (uint32_t)p & 3u;
+      uint32_t v[4];
+      block_words<VC_RNG_BF16>(p >> 2, k0, k1, v);
+      uint32_t hi = pick(v, (j + 1) & 3u);
+      if (j == 3) {
+        uint32_t v2[4];
+        block_words<VC_RNG_BF16>((p >> 2) + 1, k0, k1, v2);
+        hi = v2[0];
+      }
+      o[e] = pack2(pick(v, j), hi);
+    }
+    *(u32x4*)(out + tok * ld + col0 + ck * 8) = o;
+  }
+}
+
+int grid_for(long total) { return (int)((total + 255) / 256 < RNG_MAX_BLOCKS ? (total + 255) / 256 : RNG_MAX_BLOCKS); }
+
+}  // namespace
+
+#define RNG_LAUNCHED(name)                                                                                          \
+  {                                                                                                                 \
+    hipError_t e_ = hipGetLastError();                                                                              \
+    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }  \
+  }                                                                                                                 \
+  return VC_OK;
+
+int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen) {
+  if (!out) { snprintf(err, errlen, "randn: null output pointer"); return VC_ERR_ARG; }
+  if (n <= 0) { snprintf(err, errlen, "randn: n = %lld, need n >= 1", (long long)n); return VC_ERR_ARG; }
+  if (dtype != VC_RNG_BF16 && dtype != VC_RNG_F32 && dtype != VC_RNG_U32) {
+    snprintf(err, errlen, "randn: unknown dtype %d (VC_RNG_BF16, VC_RNG_F32, VC_RNG_U32)", dtype); return VC_ERR_ARG; }
+  if ((uint64_t)n - 1 > UINT64_MAX - offset) {          // the last position is offset + n - 1
+    snprintf(err, errlen, "randn: offset + n wraps the 64-bit stream position (offset=%llu n=%lld)", (unsigned long long)offset, (long long)n);
+    return VC_ERR_ARG; }
+  const int es = dtype == VC_RNG_BF16 ? 2 : 4, E = 16 / es;
+  if ((uintptr_t)out % es) { snprintf(err, errlen, "randn: the output must be aligned to its %d-byte elements", es); return VC_ERR_ARG; }
+  long head = (long)((E - (int)((uintptr_t)out / es % E)) % E);      // elements before the first 16-byte boundary
+  if (head > n) head = n;
+  long nvec = (n - head) / E;
+  if ((offset + (uint64_t)head) & 3) { head = n; nvec = 0; }          // the 16-byte chunks would straddle blocks: element-wise
+  const int grid = grid_for(nvec + (n - nvec * E));
+  if (dtype == VC_RNG_BF16) hipLaunchKernelGGL(randn_kernel<VC_RNG_BF16>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
+  else if (dtype == VC_RNG_F32) hipLaunchKernelGGL(randn_kernel<VC_RNG_F32>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
+  else hipLaunchKernelGGL(randn_kernel<VC_RNG_U32>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
+  RNG_LAUNCHED("randn")
+}
+
+int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
+                           int errlen) {
+  if (!tokens) { snprintf(err, errlen, "randn_tokens: null token pointer"); return VC_ERR_ARG; }
+  if (C <= 0 || h <= 0 || w <= 0 || (C & 1) || (h & 1) || (w & 1)) {
+    snprintf(err, errlen, "randn_tokens: need positive even C, h, w (C=%d h=%d w=%d)", C, h, w); return VC_ERR_ARG; }
+  if (ld <= 0 || col0 < 0 || ld % 8 || col0 % 8 || (int64_t)col0 + 4 * (int64_t)C > ld) {
+    snprintf(err, errlen, "randn_tokens: ld and col0 must be multiples of 8 with col0 + 4C <= ld (ld=%lld col0=%d C=%d)", (long long)ld, col0, C);
+    return VC_ERR_ARG; }
+  if ((uintptr_t)tokens & 15) { snprintf(err, errlen, "randn_tokens: the token rows must be 16-byte aligned"); return VC_ERR_ARG; }
+  const unsigned __int128 n = (unsigned __int128)C * (unsigned)h * (unsigned)w;
+  if (n - 1 > (unsigned __int128)(UINT64_MAX - offset)) {
+    snprintf(err, errlen, "randn_tokens: offset + C*h*w wraps the 64-bit stream position (offset=%llu)", (unsigned long long)offset);
+    return VC_ERR_ARG; }
+  hipLaunchKernelGGL(randn_tokens_kernel, dim3(grid_for((long)(h / 2) * (w / 2) * (C / 2))), dim3(256), 0, s, (bf16_t*)tokens, C, h, w, (long)ld,
+                     col0, seed, offset);
+  RNG_LAUNCHED("randn_tokens")
+}

@@ -98,6 +98,9 @@ int vc_conv3x3_launch(const void* x, const void* w, const void* bias, void* out,
 int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
                          float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
                          void* bias_out, int32_t out_features, int32_t in_features, int32_t rank, hipStream_t s, char* err, int errlen);
+int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen);
+int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
+                           int errlen);
 
 // flux_engine.hip: the handle API
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen);

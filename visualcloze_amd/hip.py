@@ -180,6 +180,8 @@ SYMBOLS = {
     "vc_nchw_to_nhwc": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, C.c_float, C.c_float, _vp]),
     "vc_nhwc_to_nchw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp]),
     "vc_gaussian_sample": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp]),
+    "vc_randn": (C.c_int, [_vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp]),
+    "vc_randn_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, C.c_uint64, C.c_uint64, _vp]),
     "vc_lora_merge": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vc_flux_create": (C.c_int, [C.POINTER(FluxConfig), C.POINTER(_vp)]),
     "vc_flux_destroy": (C.c_int, [_vp]),
@@ -768,6 +770,54 @@ def unpack_latent(tokens, latent, col0=0, stream=None):
         raise VclozeHipError(f"unpack_latent: C={Cc} > 64 channels (the tile staged through LDS holds 64)")
     _check(lib().vc_unpack_latent(tokens.data_ptr(), tokens.stride(0), col0, latent.data_ptr(), Cc, h, w,
                                   stream if stream is not None else cur_stream()), "vc_unpack_latent")
+
+
+# ---- noise source (csrc/rng.hip): the library's own counter-based Gaussian stream, NOT torch's ----
+RNG_BF16, RNG_F32, RNG_U32 = 0, 1, 2                        # VC_RNG_*
+RNG_MAX_BLOCKS = 2048                                       # workgroups of 256 threads per launch; a grid-stride loop takes the rest
+_RNG_DTYPES = {torch.bfloat16: RNG_BF16, torch.float32: RNG_F32, torch.int32: RNG_U32}
+
+
+def _u64(v, name: str) -> int:
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise VclozeHipError(f"{name} = {v}: an unsigned 64-bit value expected")
+    return v
+
+
+def randn(shape, seed, offset=0, dtype=torch.bfloat16, device=None, out=None, stream=None):
+    """vc_randn: elements offset .. offset + numel of the Gaussian stream of `seed` (include/vcloze_hip.h has the contract: Philox4x32-10
+    + Box-Muller in f32; every element depends on (seed, position) only).  dtype: torch.bfloat16 (the f32 normal rounded to
+    nearest-even), torch.float32, or torch.int32 = the raw 32-bit Philox words (VC_RNG_U32, for exact tests).  `out`: a contiguous
+    device tensor to fill instead of a new one (any base aligned to its element size; `shape` may be None).  Captured in a graph, a
+    replay repeats the same noise."""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device if device is not None else "cuda")
+    elif shape is not None and tuple(out.shape) != tuple(shape):
+        raise VclozeHipError(f"randn: out has shape {tuple(out.shape)}, not {tuple(shape)}")
+    if out.dtype not in _RNG_DTYPES or not out.is_cuda or not out.is_contiguous():
+        raise VclozeHipError(f"randn: a contiguous CUDA bf16 / f32 / int32 tensor expected, got {out.dtype} on {out.device}")
+    if stream is None and out.device.index != torch.cuda.current_device():
+        raise VclozeHipError(f"randn: the tensor is on {out.device}, the current stream on cuda:{torch.cuda.current_device()}")
+    _check(lib().vc_randn(out.data_ptr(), _RNG_DTYPES[out.dtype], out.numel(), _u64(seed, "seed"), _u64(offset, "offset"),
+                          stream if stream is not None else cur_stream()), "vc_randn")
+    return out
+
+
+def randn_tokens(C_, h, w, seed, offset=0, tokens=None, col0=0, device=None, stream=None):
+    """vc_randn_tokens: a [C_, h, w] draw at stream positions offset + (c*h + y)*w + x, written as bf16 into tokens[:, col0:col0+4C_]
+    in pack_latent's layout - bit-identical to pack_latent(randn([C_, h, w], seed, offset), tokens, col0) in one launch.  tokens:
+    [(h/2)(w/2), >= col0 + 4C_] bf16 rows (last dim contiguous), or None for a new [(h/2)(w/2), 4C_] tensor.  Returns tokens."""
+    if tokens is None:
+        tokens = torch.empty((h // 2) * (w // 2), col0 + 4 * C_, dtype=torch.bfloat16, device=device if device is not None else "cuda")
+    _bf16(tokens, "tokens")
+    if tokens.dim() != 2 or tokens.stride(1) != 1 or tokens.shape[0] != (h // 2) * (w // 2) or tokens.shape[1] < col0 + 4 * C_:
+        raise VclozeHipError(f"randn_tokens: [(h/2)(w/2), >= col0 + 4C] token rows with contiguous last dim expected, got {tuple(tokens.shape)}")
+    if stream is None and tokens.device.index != torch.cuda.current_device():
+        raise VclozeHipError(f"randn_tokens: the tensor is on {tokens.device}, the current stream on cuda:{torch.cuda.current_device()}")
+    _check(lib().vc_randn_tokens(tokens.data_ptr(), C_, h, w, tokens.stride(0), col0, _u64(seed, "seed"), _u64(offset, "offset"),
+                                 stream if stream is not None else cur_stream()), "vc_randn_tokens")
+    return tokens
 
 
 # ---- VAE decoder glue (activations NHWC bf16 [H*W, C]) ----

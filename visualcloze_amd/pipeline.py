@@ -12,12 +12,64 @@ caller: inputs are row tensors in [-1, 1] and token ids.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import torch
 
 from . import hip, packing
 from .transport import Sampler, create_transport
+
+
+class NoiseStream:
+    """The counterpart of `torch.Generator` over the library's own noise source (`hip.randn`, vc_randn of include/vcloze_hip.h:
+    Philox4x32-10 + Box-Muller, every element a function of (seed, stream position) only).  `randn` draws at the current
+    `offset` and advances it by the number of elements drawn, so a sequence of draws is one contiguous stretch of the stream: a
+    caller without torch reproduces every tensor from (seed, offset) with vc_randn / vc_randn_tokens.  It is NOT torch's stream:
+    the images of a seed here are not the images `torch.Generator.manual_seed` gives for the same seed.  Pass one as `rng` to
+    `generate_grid`, `upsample_image(s)` or `generate_and_upsample`; the default noise stays torch's."""
+
+    def __init__(self, seed: int, offset: int = 0, device=None):
+        self.seed = int(seed)
+        self.device = device
+        self.offset = offset
+
+    @property
+    def offset(self) -> int:
+        """the stream position of the next draw (readable and settable)"""
+        return self._offset
+
+    @offset.setter
+    def offset(self, value: int) -> None:
+        value = int(value)
+        if not 0 <= value < 1 << 64:
+            raise ValueError(f"NoiseStream.offset = {value}: an unsigned 64-bit stream position expected")
+        self._offset = value
+
+    def randn(self, shape, dtype=torch.bfloat16, device=None) -> torch.Tensor:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        if n < 1 or self._offset + n > 1 << 64:
+            raise ValueError(f"NoiseStream.randn: {n} elements at offset {self._offset} leave the 64-bit stream")
+        out = hip.randn(tuple(shape), self.seed, self._offset, dtype=dtype, device=device if device is not None else self.device)
+        self._offset += n
+        return out
+
+
+def _draw(rng, shape, dev) -> torch.Tensor:
+    """one bf16 noise tensor from `rng`: a NoiseStream, or a torch.Generator as the reference draws (f32, then .to(bf16))"""
+    if isinstance(rng, NoiseStream):
+        return rng.randn(shape, torch.bfloat16, device=dev)
+    return torch.randn(shape, device=dev, generator=rng).to(torch.bfloat16)
+
+
+def _encode(ae, px, noise, rng) -> torch.Tensor:
+    """ae.encode of [1, 3, H, W]; with a NoiseStream and no `noise` given, the DiagonalGaussian draw (autoencoder.py:272) comes
+    from the stream too, where the reference's `.sample()` makes it"""
+    if noise is None and isinstance(rng, NoiseStream):
+        f = 2 ** (ae.encoder.num_resolutions - 1)
+        noise = rng.randn([1, ae.encoder.z_channels, px.shape[-2] // f, px.shape[-1] // f], torch.bfloat16, device=px.device)
+    return ae.encode(px, noise=noise)
 
 
 def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
@@ -97,7 +149,7 @@ def sdedit_upsample_batch(model, noises: Sequence[torch.Tensor], latents: Sequen
 def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks: List[torch.Tensor],
                   t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, cfg: float = 30.0, steps: int = 30,
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
-                  solver: str = "euler", time_shifting_factor=1, rng: Optional[torch.Generator] = None,
+                  solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
                   step_cache=None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
@@ -106,18 +158,19 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     `torch.Generator(device).manual_seed(seed)` + one `torch.randn` per row (:394-399).  `encode_noise` are the VAE's
     DiagonalGaussian samples per row (None: drawn with torch.randn_like, as the reference's encode does).
     `rng`: the generator to draw from instead of a fresh one seeded with `seed` (the upsampling stage keeps drawing from
-    the SAME generator, :450-458).  Returns the decoded rows `decode_rows` (default: all) as [3, H, W_row] tensors in
-    [0, 1] (:430-432).  `step_cache`: a `transport.StepCache` or None (off, the default) - the opt-in first-block step cache of
+    the SAME generator, :450-458), or a `NoiseStream`: every draw then comes from the library's own stream in the reference's
+    order of draws - the DiagonalGaussian draw of each row's encode (:377; unless `encode_noise` gives it), then one start-noise
+    tensor per row (:395-399) - each a contiguous stretch of the stream.  Returns the decoded rows `decode_rows` (default: all) as
+    [3, H, W_row] tensors in [0, 1] (:430-432).  `step_cache`: a `transport.StepCache` or None (off, the default) - the opt-in first-block step cache of
     the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`."""
     dev = row_images[0].device
     lat = []
     for i, img in enumerate(row_images):                                               # :377-378
         n = None if encode_noise is None else encode_noise[i]
-        lat.append(ae.encode(img[None].to(torch.bfloat16), noise=n))
+        lat.append(_encode(ae, img[None].to(torch.bfloat16), n, rng))
     if rng is None:
         rng = torch.Generator(device=dev).manual_seed(int(seed))                       # :394
-    noise = [torch.randn([1, 16, img.shape[-2] // 8, img.shape[-1] // 8], device=dev, generator=rng).to(torch.bfloat16)
-             for img in row_images]                                                    # :395-399
+    noise = [_draw(rng, [1, 16, img.shape[-2] // 8, img.shape[-1] // 8], dev) for img in row_images]     # :395-399
     txt = t5(t5_ids)                                                                   # prepare_modified -> HFEmbedder
     vec, _ = clip(clip_ids)
     rows = denoise_grid(model, noise, lat, row_masks, txt, vec, cfg=cfg, steps=steps, solver=solver,
@@ -151,13 +204,14 @@ def upsampling_size(target_size):
 
 @torch.no_grad()
 def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
-                   rng: torch.Generator, cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
+                   rng: Union[torch.Generator, NoiseStream], cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
                    encode_noise: Optional[Sequence[torch.Tensor]] = None, solver: str = "euler", step_cache=None) -> torch.Tensor:
     """`VisualClozeModel.upsampling` (visualcloze.py:147-245) for one image: resize on the host (PIL, bicubic - the
     default of `Image.resize`), VAE-encode the image and a blank, SDEdit from `strength` with everything masked, decode.
     image: PIL image or [3,H,W] tensor in [0,1]; t5_ids / clip_ids: the tokenised CONTENT prompt (prefix stripping and
     tokenisation are host work, :149-163); `encode_noise`: the two DiagonalGaussian draws (image, blank) or None for
-    torch.randn_like as the reference's `.sample()`.  Returns [3, h, w] in [0, 1]."""
+    torch.randn_like as the reference's `.sample()`; `rng`: a torch.Generator, or a `NoiseStream`, from which the draws then come
+    in the reference's order - encode(image), encode(blank), start noise (:200-217).  Returns [3, h, w] in [0, 1]."""
     import numpy as np
     dev = next(ae.parameters()).device
     if torch.is_tensor(image):
@@ -168,9 +222,9 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
         return px.to(dev)                                                              # :180-181
     px = ((px - 0.5) / 0.5).to(dev, torch.bfloat16)                                    # Normalize(0.5, 0.5)
     n_img, n_blank = (None, None) if encode_noise is None else encode_noise
-    latent = ae.encode(px[None], noise=None if n_img is None else n_img[None] if n_img.dim() == 3 else n_img)      # :200,202
-    blank = ae.encode(torch.zeros_like(px)[None], noise=None if n_blank is None else n_blank[None] if n_blank.dim() == 3 else n_blank)
-    noise = torch.randn([1, 16, latent.shape[-2], latent.shape[-1]], device=dev, generator=rng).to(torch.bfloat16)    # :217
+    latent = _encode(ae, px[None], None if n_img is None else n_img[None] if n_img.dim() == 3 else n_img, rng)     # :200,202
+    blank = _encode(ae, torch.zeros_like(px)[None], None if n_blank is None else n_blank[None] if n_blank.dim() == 3 else n_blank, rng)
+    noise = _draw(rng, [1, 16, latent.shape[-2], latent.shape[-1]], dev)               # :217
     txt = t5(t5_ids)
     vec, _ = clip(clip_ids)
     z = sdedit_upsample(model, noise, latent, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver,
@@ -181,7 +235,7 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
 
 @torch.no_grad()
 def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
-                    rng: torch.Generator, cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
+                    rng: Union[torch.Generator, NoiseStream], cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
                     encode_noise: Optional[Sequence] = None, solver: str = "euler", step_cache=None) -> List[torch.Tensor]:
     """`upsample_image` for several images of one grid in ONE batched SDEdit solve (`sdedit_upsample_batch`).  Host work
     (resize), the VAE encodes and every random draw happen per image in the reference's order - image k: encode(image),
@@ -203,9 +257,9 @@ def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: 
         px = ((px - 0.5) / 0.5).to(dev, torch.bfloat16)
         n_img, n_blank = (None, None) if encode_noise is None or encode_noise[k] is None else encode_noise[k]
         nz = lambda n: None if n is None else n[None] if n.dim() == 3 else n  # noqa: E731
-        lat.append(ae.encode(px[None], noise=nz(n_img)))
-        blank.append(ae.encode(torch.zeros_like(px)[None], noise=nz(n_blank)))
-        noise.append(torch.randn([1, 16, lat[-1].shape[-2], lat[-1].shape[-1]], device=dev, generator=rng).to(torch.bfloat16))
+        lat.append(_encode(ae, px[None], nz(n_img), rng))
+        blank.append(_encode(ae, torch.zeros_like(px)[None], nz(n_blank), rng))
+        noise.append(_draw(rng, [1, 16, lat[-1].shape[-2], lat[-1].shape[-1]], dev))
     txt = t5(t5_ids)
     vec, _ = clip(clip_ids)
     zs = sdedit_upsample_batch(model, noise, lat, blank, txt, vec, cfg=cfg, steps=steps, strength=strength, solver=solver,
@@ -220,15 +274,19 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
                           content_clip_ids: Optional[torch.Tensor] = None, cfg: float = 30.0, steps: int = 30,
                           upsampling_steps: int = 10, upsampling_noise: float = 0.4, is_upsampling: bool = True,
                           encode_noise: Optional[List[torch.Tensor]] = None, upsample_encode_noise=None,
-                          solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True, step_cache=None):
+                          solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True, step_cache=None,
+                          rng: Union[torch.Generator, NoiseStream, None] = None):
     """Both stages of `process_images` chained (visualcloze.py:363-465): the grid is generated, its LAST row is decoded and
     quantised to 8 bits as `to_pil_image` does, every cell of that row whose `mask_position` is set is cropped
     (:452,461) and - with `is_upsampling` - refined by `upsample_image` at `target_size`, all noise coming from ONE
     generator seeded with `seed` (:394,456).  `batch_targets` (default): the masked cells are refined TOGETHER, one graph replay
     per solver step for all of them (`upsample_images`; same draws in the same order, per-target results equal up to bf16
-    noise); False = one after the other as the reference loops.  Returns the output images as [3, h, w] tensors in [0, 1]."""
+    noise); False = one after the other as the reference loops.  `rng`: the generator both stages draw from instead of a fresh
+    torch.Generator seeded with `seed` - a `NoiseStream` puts every draw of both stages on the library's own stream, in the
+    reference's order.  Returns the output images as [3, h, w] tensors in [0, 1]."""
     dev = row_images[0].device
-    rng = torch.Generator(device=dev).manual_seed(int(seed))
+    if rng is None:
+        rng = torch.Generator(device=dev).manual_seed(int(seed))
     last = len(row_images) - 1
     row = generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                         encode_noise=encode_noise, decode_rows=[last], solver=solver, time_shifting_factor=time_shifting_factor,
