@@ -474,7 +474,8 @@ int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora
  * The handle holds no tensor: weights are zero-copy views bound by name, every activation lives in a caller-provided
  * workspace.  It does own small host-side state (a pinned staging buffer, the captured hipGraph of one solver step, events).
  * One handle per device per process; not thread-safe per handle.  bf16 everywhere, LoRA pairs already folded into the
- * bound weights (W + s*B@A, lora.py:92-98; the un-merged parity mode stays on the op-level API).  A C caller gets there from a
+ * bound weights (W + s*B@A, lora.py:92-98) - or, with option "lora_mode" 1, bound next to the un-merged base weights and executed
+ * as the reference's LinearLora does (vc_flux_bind_lora below).  A C caller gets to the merged form from a
  * LoRA checkpoint with one vc_lora_merge call per Linear - in place on its own copy of the base weight, or with `out` pointing at
  * the Linear's rows of the stacked "modulation" matrix - and binds the results. */
 typedef struct VcFluxConfig {   /* FluxParams, models/model.py:18-32 */
@@ -515,8 +516,53 @@ int64_t vc_flux_mod_offset(void* handle, const char* module_name);
  * the value, 16330 * max|query_norm.scale| * max|key_norm.scale| over all blocks rounded up, is a CAP: each attention launch gets
  * the smaller of it and its OWN block's bound, which the library computes from the bound QK-norm scales when it resolves the
  * weights (one 256-byte read-back per scale vector), so a checkpoint with outlier scales in a few blocks runs the running-max
- * template in those blocks only); "mlp_first", "splitk" (1: split-K / stream remainders where the launcher takes them). */
+ * template in those blocks only); "mlp_first", "splitk" (1: split-K / stream remainders where the launcher takes them);
+ * "lora_mode" (0; 1: un-merged LoRA execution, see vc_flux_bind_lora). */
 int vc_flux_set_option(void* handle, const char* name, int32_t value);
+
+/* ---- un-merged LoRA execution: LinearLora.forward (models/modules/lora.py:92-98) with the reference's three roundings, the parity
+ * mode of the handle.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up
+ * vc_flux_bind_lora.  Off by default; while off nothing changes (the same launches, the same workspace size, the same bits).
+ * vc_flux_set_option(handle, "lora_mode", 1): the weights bound by vc_flux_bind_weight are the UN-MERGED base weights (the stacked
+ * "modulation" matrix included, qkv rows in their natural order: "qkv_heads" 0), and every Linear runs as
+ *     y = bf16(x W^T + b);  h = bf16(x A^T);  y = bf16(y + bf16(bf16(h B^T + b_B) * scale));  out = epilogue(y)
+ * - three vc_gemm launches (the last one with VC_EPI_GATE_RES: y as the residual, the scale as a bf16 gate vector) and the Linear's
+ * own epilogue (GELU, SiLU, gated residual: vc_act2d / vc_gate_residual; QK-norm + RoPE + V^T: vc_qknorm_rope_vt) as a pass of its
+ * own; no split-K.  A Linear without a bound pair runs the first launch and its pass.  In mode 0 bound pairs are ignored.
+ * The mode changes the workspace (three scratch matrices and the scale vector behind everything else): set it, THEN ask
+ * vc_flux_workspace_bytes and prepare; a switch un-prepares the handle, and between vc_flux_sample_begin* and vc_flux_sample_end
+ * it is refused (VC_ERR_STATE).  The sampling loop (batches, F32 states, midpoint / rk4, true CFG, the step cache) runs either mode.
+ * vc_flux_bind_lora: name as for vc_flux_bind_weight - a Linear whose weight is bound already (VC_ERR_STATE otherwise), or a module of
+ * the stacked modulation matrix ("double_blocks.0.img_mod.lin", ...: the names of vc_flux_mod_offset); "single_blocks.i.linear1" takes
+ * ONE pair for its 3 * hidden + mlp rows.  lora_a [rank, in_features] (row stride lda), lora_b [out_features, rank] (ldb),
+ * lora_b_bias [out_features] or NULL: bf16 device memory the caller keeps alive.  rank: a multiple of 64, the GEMM's K granularity
+ * (zero-pad the factors); out_features / in_features must be those of the bound weight; anything else is VC_ERR_ARG naming the
+ * argument, nothing is launched.  lora_a == lora_b == NULL removes the pair.  Binding un-prepares the handle (the widest rank sizes
+ * the scratch).
+ * vc_flux_set_lora_scale: the scale of EVERY pair (default 1.0).  It must be a bf16 value (1, 0.5, 0.75, ...: the reference rounds
+ * bf16(lora_out * scale) once, and so does a bf16 gate only then), else VC_ERR_ARG.  Host only: no re-bind, no re-merge, no
+ * re-capture.  vc_flux_prepare writes the value into the scale vector (one fill launch), which keeps its place in that workspace, so
+ * a step captured there replays with the new scale.  vc_flux_prepare also runs txt_in, vector_in and guidance_in and parks their
+ * results in the workspace, and vc_flux_sample_begin* every modulation row of the trajectory - all un-merged Linears that read the
+ * scale.  Hence: in mode 1 a CHANGED scale on a prepared handle makes vc_flux_forward / vc_flux_sample_begin* return VC_ERR_STATE
+ * until vc_flux_prepare has been called again (never old-scale projections under a new-scale body), and between
+ * vc_flux_sample_begin* and vc_flux_sample_end the call itself is VC_ERR_STATE. */
+int vc_flux_bind_lora(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                      const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank);
+int vc_flux_set_lora_scale(void* handle, float scale);
+/* ---- per-block taps: the residual streams after img_in / txt_in ("img_in", "txt_in"), after DoubleStream block i ("double.{i}.img",
+ * "double.{i}.txt") and after SingleStream block i ("single.{i}": the joint stream, per sample the text rows, then the image rows).
+ * Detect by SYMBOL (vc_flux_set_tap).  dst: the caller's bf16 device buffer of vc_flux_tap_shape's rows x cols (rows in the engine's
+ * order, samples stacked; the shape is that of the prepared geometry: VC_ERR_STATE before vc_flux_prepare), NULL removes the tap.
+ * A tap is ONE device-to-device copy on the evaluation's own stream directly behind the block - no second stream, no branch in the
+ * captured step, of which it is a node: the tap set is part of the key a captured step is kept under, and takes effect at the next
+ * vc_flux_forward / vc_flux_sample_begin*; between vc_flux_sample_begin* and vc_flux_sample_end a change is VC_ERR_STATE (the
+ * captured step of the trajectory keeps its copy node: dst must stay valid until vc_flux_sample_end).  With no tap set the plan is
+ * launch for launch what it was.  During a trajectory a tap
+ * holds the value of the last evaluation issued (a stage of midpoint / rk4 included; an evaluation the step cache reuses runs block
+ * 0 only and leaves the later taps as they were).  An unknown name or a block index beyond the model's depth is VC_ERR_ARG. */
+int vc_flux_set_tap(void* handle, const char* name, void* dst);
+int vc_flux_tap_shape(void* handle, const char* name, int64_t* rows, int32_t* cols);
 int64_t vc_flux_workspace_bytes(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps);
 
 typedef struct VcFluxInputs {   /* everything of model_kwargs that does not change along the trajectory */
@@ -602,7 +648,9 @@ int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, f
  * its predecessor in the step leaves them.  Synchronises `stream`; entries come in order of first appearance.
  * Reference: there is none (the reference times whole pipelines, visualcloze.py); replaces the Python-ordered twin of the plan
  * (visualcloze_amd/engine.py) as the thing bench.py times. */
-enum { VC_LAUNCH_GEMM = 1, VC_LAUNCH_ATTENTION = 2, VC_LAUNCH_LN_MODULATE = 3 };
+enum { VC_LAUNCH_GEMM = 1, VC_LAUNCH_ATTENTION = 2, VC_LAUNCH_LN_MODULATE = 3,
+       VC_LAUNCH_PASS = 4,   /* lora_mode 1: the epilogue of a Linear as its own pass (epi = its VC_EPI_*, n = the columns) */
+       VC_LAUNCH_TAP = 5 };  /* the copies of all taps, one class */
 typedef struct VcFluxLaunchClass {
   int32_t kind;        /* VC_LAUNCH_* */
   int32_t epi;         /* GEMM: the VC_EPI_* of the launch; attention: the VcAttention.variant that ran; else 0 */
@@ -610,7 +658,7 @@ typedef struct VcFluxLaunchClass {
   int32_t launches;    /* launches of this class in the timed evaluations */
   int32_t reserved;
   double flops;        /* their arithmetic: 2 M N K over all problems (GEMM), 4 L^2 D B (attention: masked keys included), else 0 */
-  double bytes;        /* LayerNorm-modulate: rows read + rows written; else 0 */
+  double bytes;        /* LayerNorm-modulate, pass, tap: rows read + rows written; else 0 */
   float total_us;      /* sum of the launches' event times (an attention launch: the kernel and, where one runs, its merge kernel) */
   float min_us, max_us;
   float reserved2;

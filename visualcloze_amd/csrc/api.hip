@@ -208,6 +208,15 @@ int vc_flux_destroy(void* handle) { return vc_flux_destroy_impl(handle, ERRBUF);
 int vc_flux_bind_weight(void* handle, const char* name, const void* w, const void* bias, int32_t rows, int32_t cols, int64_t ldw) {
   return vc_flux_bind_weight_impl(handle, name, w, bias, rows, cols, ldw, ERRBUF);
 }
+int vc_flux_bind_lora(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                      const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank) {
+  return vc_flux_bind_lora_impl(handle, name, lora_a, lda, lora_b, ldb, lora_b_bias, out_features, in_features, rank, ERRBUF);
+}
+int vc_flux_set_lora_scale(void* handle, float scale) { return vc_flux_set_lora_scale_impl(handle, scale, ERRBUF); }
+int vc_flux_set_tap(void* handle, const char* name, void* dst) { return vc_flux_set_tap_impl(handle, name, dst, ERRBUF); }
+int vc_flux_tap_shape(void* handle, const char* name, int64_t* rows, int32_t* cols) {
+  return vc_flux_tap_shape_impl(handle, name, rows, cols, ERRBUF);
+}
 int64_t vc_flux_mod_offset(void* handle, const char* module_name) { return vc_flux_mod_offset_impl(handle, module_name); }
 int vc_flux_set_option(void* handle, const char* name, int32_t value) { return vc_flux_set_option_impl(handle, name, value, ERRBUF); }
 int64_t vc_flux_workspace_bytes(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps) {

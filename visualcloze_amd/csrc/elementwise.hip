@@ -77,6 +77,12 @@ __global__ void gate_residual_kernel(const bf16_t* __restrict__ y, long ldy, con
   out[m * ldo + n] = f2bf(bf2f(res[m * ldres + n]) + rbf(bf2f(g[n]) * bf2f(y[m * ldy + n])));
 }
 
+// p[i] = bf16(v): the lora scale as the gate vector of the un-merged mode (vc_flux_set_lora_scale)
+__global__ void fill_bf16_kernel(bf16_t* __restrict__ p, float v, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = f2bf(v);
+}
+
 __global__ void step_advance_kernel(int* step_ptr) { if (threadIdx.x == 0 && blockIdx.x == 0) *step_ptr += 1; }
 
 // ---- the solver update: every arithmetic line of a fixed-grid Euler / midpoint / rk4 (3/8 rule) step that is not a model evaluation ----
@@ -307,6 +313,11 @@ int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64
   if (vec) hipLaunchKernelGGL(cfg_combine_kernel<8>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
   else hipLaunchKernelGGL(cfg_combine_kernel<1>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
   VC_CHECK_LAUNCH("cfg_combine");
+}
+int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (!p || n <= 0) { snprintf(err, errlen, "fill_bf16: bad args"); return VC_ERR_ARG; }
+  hipLaunchKernelGGL(fill_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)p, value, (long)n);
+  VC_CHECK_LAUNCH("fill_bf16");
 }
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen) {
   if (!step_ptr) { snprintf(err, errlen, "step_advance: null"); return VC_ERR_ARG; }

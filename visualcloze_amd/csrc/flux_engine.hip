@@ -18,6 +18,9 @@
 //                           in place (cfg_combine_kernel, elementwise.hip); no buffer of its own
 //   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
+//   LY / LY2 / LH / LSCALE  only in the un-merged LoRA mode (option lora_mode 1), behind everything else: base_out, base_out + lora
+//                           and lora_A(x) of the Linear being run, and the lora scale as a bf16 vector (the gate operand of the
+//                           gated-residual epilogue that adds the lora branch; refilled by vc_flux_set_lora_scale)
 #include "common.h"
 #include "vcloze_internal.h"
 #include "engine_core.h"
@@ -28,6 +31,13 @@
 #include <vector>
 
 namespace {
+
+// a bound LoRA pair (vc_flux_bind_lora): lora_A [rank, in], lora_B [out, rank], lora_B's bias [out] or null
+struct Lora {
+  const void* a = nullptr; const void* b = nullptr; const void* bb = nullptr;
+  int rank = 0, out = 0, in = 0;
+  int64_t lda = 0, ldb = 0;
+};
 
 struct Lin {
   const void* w = nullptr;
@@ -45,6 +55,8 @@ struct Buffers {   // the workspace carve-up
   float *ROPE, *TS, *DTS, *G32, *FREQS, *XS32;
   int32_t *STEP, *KVLEN, *KVGAP;
   bf16_t *SC_P = nullptr, *SC_R = nullptr, *SC_RS = nullptr;      // step cache (carved only while it is on)
+  bf16_t *LY = nullptr, *LY2 = nullptr, *LH = nullptr, *LSCALE = nullptr;   // un-merged LoRA mode (carved only while it is on)
+  int64_t ly_elems = 0, lh_elems = 0, lscale_elems = 0;
   float *SC_PART = nullptr, *SC_METRIC = nullptr;
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
@@ -55,6 +67,7 @@ struct Buffers {   // the workspace carve-up
 // vc_flux_set_option: every option of the plan, once.  OPTIONS below is the table that sets, clamps and compares them
 struct Options {
   int attn_variant = -1, tile_cfg = 0, fuse_qnorm = 2, fuse_vt = 1, qkv_heads = 0, fuse_knorm = 0, logit_bound_milli = 0, mlp_first = 0, splitk = 1;
+  int lora_mode = 0;
 };
 enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
 #define OPT(name, clamp) {#name, &Options::name, clamp}
@@ -63,6 +76,7 @@ constexpr struct { const char* name; int Options::*member; Clamp clamp; } OPTION
     OPT(fuse_vt, BOOL),          OPT(qkv_heads, ZERO_OR_H),      // the bound qkv weights (linear1's first 3D rows) are head-permuted (vcloze_hip.h)
     OPT(fuse_knorm, BOOL),       OPT(logit_bound_milli, AT_LEAST_0),
     OPT(mlp_first, BOOL),        OPT(splitk, BOOL),              // split-K remainders (VcGemmArgs.splitk_ws) where the launcher's model takes them
+    OPT(lora_mode, BOOL),                                        // 1: every Linear runs un-merged (lora_linear below)
 };
 #undef OPT
 inline bool operator==(const Options& a, const Options& b) {
@@ -76,6 +90,18 @@ struct Flux : Buffers {
   int64_t n_mod = 0;
   std::unordered_map<std::string, Lin> bound;
   std::unordered_map<std::string, int64_t> mod_off;
+  // un-merged LoRA mode: the bound pairs by module path; resolved, the pair of the Linear whose weight rows start at an address
+  // (linear1's two row ranges and the rows of every modulation Linear inside the stacked matrix have their own), and the
+  // modulation Linears one by one, in stacking order
+  std::unordered_map<std::string, Lora> lora;
+  std::unordered_map<const void*, Lora> lora_of;
+  std::vector<std::pair<Lin, int64_t>> mods;
+  float lora_scale = 1.0f;
+  bool scale_stale = false;            // the scale changed after vc_flux_prepare ran txt_in / vector_in / guidance_in with the old one
+  // per-block taps (vc_flux_set_tap): the caller's buffer of tap i, or null - img_in, txt_in, then (img, txt) of every double
+  // block, then every single block
+  std::vector<void*> taps;
+  bool in_flight = false;              // between vc_flux_sample_begin* and vc_flux_sample_end
   // resolved at prepare time
   bool resolved = false;
   Lin img_in, txt_in, time_in[2], vector_in[2], guidance_in[2], final_lin, modulation;
@@ -99,10 +125,11 @@ struct Flux : Buffers {
   struct Key {
     char* base; int B, T, N, S, ragged, gapped, variant, state_f32, method, cache; Options opt; hipStream_t s;   // variant: resolved
     int cfg; uint32_t cfg_bits;          // true CFG on, and the bits of its scale: a kernel argument of the captured combine
+    std::vector<void*> taps;             // the tap set: every tap is a copy node of the captured step
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
              variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s &&
-             cfg == o.cfg && cfg_bits == o.cfg_bits;
+             cfg == o.cfg && cfg_bits == o.cfg_bits && taps == o.taps;
     }
   } key{};
   // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
@@ -173,6 +200,16 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
     f.SC_P = c.take<bf16_t>(B * N * D); f.SC_R = c.take<bf16_t>(B * N * D); f.SC_RS = c.take<bf16_t>(B * N * D);
     f.SC_PART = c.take<float>((int64_t)B * 2 * VC_RESIDUAL_CHANGE_MAX_BLOCKS); f.SC_METRIC = c.take<float>(1);
   }
+  if (g.opt.lora_mode) {   // likewise: the widest Linear over the block rows, the modulation Linears over the (evaluation, sample) rows
+    const int64_t wide = std::max<int64_t>({3 * D, mlp, D, out_ch}), rows = std::max<int64_t>(B * L, (int64_t)S * B);
+    int64_t rank = 64;
+    for (const auto& kv : g.lora) rank = std::max<int64_t>(rank, kv.second.rank);
+    f.ly_elems = std::max<int64_t>(B * L * wide, (int64_t)S * B * 6 * D);
+    f.lh_elems = rows * rank;
+    f.lscale_elems = std::max<int64_t>(wide, 6 * D);
+    f.LY = c.take<bf16_t>(f.ly_elems); f.LY2 = c.take<bf16_t>(f.ly_elems);
+    f.LH = c.take<bf16_t>(f.lh_elems); f.LSCALE = c.take<bf16_t>(f.lscale_elems);
+  }
   return c.off;
 }
 
@@ -225,9 +262,25 @@ int scale_absmax(const void* dev, double& out, Err e) {
 // roundings on the way (model.py / engine.py compute the same number for the Python-ordered plan)
 inline float logit_bound_of(double qmax, double kmax) { return (float)(1.02 * 11.313708498984761 * 1.4426950408889634 * qmax * kmax); }
 
+// the pair bound for module `name` belongs to the Linear `l`, whose rows are [row0, row0 + l.N) of that module's
+int attach_lora(Flux& f, const std::string& name, const Lin& l, int row0, Err e) {
+  auto it = f.lora.find(name);
+  if (it == f.lora.end()) return VC_OK;
+  Lora lo = it->second;
+  if (lo.in != l.K || row0 + l.N > lo.out)
+    FAIL(VC_ERR_ARG, "flux: LoRA pair of '%s' is [%d, r] x [r, %d], its Linear takes %d inputs", name.c_str(), lo.out, lo.in, l.K);
+  lo.b = (const bf16_t*)lo.b + (int64_t)row0 * lo.ldb;
+  if (lo.bb) lo.bb = (const bf16_t*)lo.bb + row0;
+  lo.out = l.N;
+  f.lora_of[l.w] = lo;
+  return VC_OK;
+}
+
 int resolve(Flux& f, Err e) {
   if (f.resolved) return VC_OK;
   const int D = f.D, mlp = f.mlp;
+  f.lora_of.clear();
+  f.mods.clear();
   TRY(find(f, "img_in", f.img_in, D, f.cfg.in_channels, false, e));
   TRY(find(f, "txt_in", f.txt_in, D, f.cfg.context_in_dim, false, e));
   TRY(find(f, "time_in.in_layer", f.time_in[0], D, 256, false, e));
@@ -277,6 +330,46 @@ int resolve(Flux& f, Err e) {
     w.bound = logit_bound_of(q, k);
   }
   f.final_mod = f.mod_off["final_layer.adaLN_modulation.1"];
+  {  // the LoRA pairs (read in lora_mode 1 only)
+    const char* plain[] = {"img_in", "txt_in", "final_layer.linear"};
+    const Lin* plain_l[] = {&f.img_in, &f.txt_in, &f.final_lin};
+    for (int i = 0; i < 3; ++i) TRY(attach_lora(f, plain[i], *plain_l[i], 0, e));
+    const char* emb[] = {"time_in", "vector_in", "guidance_in"};
+    Lin* emb_l[] = {f.time_in, f.vector_in, f.guidance_in};
+    for (int i = 0; i < (f.cfg.guidance_embed ? 3 : 2); ++i) {
+      TRY(attach_lora(f, std::string(emb[i]) + ".in_layer", emb_l[i][0], 0, e));
+      TRY(attach_lora(f, std::string(emb[i]) + ".out_layer", emb_l[i][1], 0, e));
+    }
+    for (int i = 0; i < f.cfg.depth; ++i) {
+      const std::string pf = "double_blocks." + std::to_string(i) + ".";
+      const char* st[2] = {"img", "txt"};
+      for (int k = 0; k < 2; ++k) {
+        TRY(attach_lora(f, pf + st[k] + "_attn.qkv", f.dbl[i].qkv[k], 0, e));
+        TRY(attach_lora(f, pf + st[k] + "_attn.proj", f.dbl[i].proj[k], 0, e));
+        TRY(attach_lora(f, pf + st[k] + "_mlp.0", f.dbl[i].mlp0[k], 0, e));
+        TRY(attach_lora(f, pf + st[k] + "_mlp.2", f.dbl[i].mlp2[k], 0, e));
+      }
+    }
+    for (int i = 0; i < f.cfg.depth_single_blocks; ++i) {
+      const std::string pf = "single_blocks." + std::to_string(i) + ".";
+      TRY(attach_lora(f, pf + "linear1", f.sgl[i].qkv, 0, e));          // linear1's two row ranges share lora_A
+      TRY(attach_lora(f, pf + "linear1", f.sgl[i].mlp, 3 * D, e));
+      TRY(attach_lora(f, pf + "linear2", f.sgl[i].lin2, 0, e));
+    }
+    // every modulation Linear as the rows of the stacked matrix it owns, in stacking order
+    std::vector<std::pair<int64_t, std::string>> order;
+    for (const auto& kv : f.mod_off) order.push_back({kv.second, kv.first});
+    std::sort(order.begin(), order.end());
+    for (size_t i = 0; i < order.size(); ++i) {
+      const int64_t off = order[i].first, end = i + 1 < order.size() ? order[i + 1].first : f.n_mod;
+      Lin l = f.modulation;
+      l.N = (int)(end - off);
+      l.w = (const bf16_t*)f.modulation.w + off * f.modulation.ldw;
+      l.b = f.modulation.b ? (const void*)((const bf16_t*)f.modulation.b + off) : nullptr;
+      TRY(attach_lora(f, order[i].second, l, 0, e));
+      f.mods.push_back({l, off});
+    }
+  }
   f.resolved = true;
   return VC_OK;
 }
@@ -288,17 +381,21 @@ int resolve(Flux& f, Err e) {
 int attention_variant(const Flux& f);
 // (where the one-wave-per-SIMD attention kernel runs: small geometries keep ONE pre-pass launch for q and k - the fused
 // epilogue needs the 256x192 tile, which their short M does not fill)
-bool kn_in_gemm(const Flux& f) { return f.opt.fuse_knorm && f.opt.qkv_heads > 0 && vcplan::decode_variant(attention_variant(f)).wave64; }
+// (the un-merged LoRA mode completes a Linear's output only after a second GEMM: nothing rides the projection's epilogue there)
+bool vt_in_gemm(const Flux& f) { return f.opt.fuse_vt && !f.opt.lora_mode; }
+bool kn_in_gemm(const Flux& f) {
+  return f.opt.fuse_knorm && f.opt.qkv_heads > 0 && !f.opt.lora_mode && vcplan::decode_variant(attention_variant(f)).wave64;
+}
 bool qn_in_gemm(const Flux& f) { return kn_in_gemm(f) && f.opt.fuse_qnorm >= 2; }
-int qkv_epi(const Flux& f) { return f.opt.fuse_vt || f.opt.qkv_heads > 0 ? VC_EPI_QKV : VC_EPI_BIAS; }
+int qkv_epi(const Flux& f) { return vt_in_gemm(f) || f.opt.qkv_heads > 0 ? VC_EPI_QKV : VC_EPI_BIAS; }
 void with_vt(Flux& f, VcGemmProblem& p, int rows, int row0, const void* q_scale, const void* k_scale) {
-  if (f.opt.fuse_vt) { p.vt = f.VT; p.vt_bstride = (int64_t)f.H * 128 * f.Lp; p.vt_col0 = 2 * f.D; p.vt_lpad = f.Lp; }
+  if (vt_in_gemm(f)) { p.vt = f.VT; p.vt_bstride = (int64_t)f.H * 128 * f.Lp; p.vt_col0 = 2 * f.D; p.vt_lpad = f.Lp; }
   if (f.opt.qkv_heads > 0) {
     p.kn_heads = f.opt.qkv_heads;
     if (kn_in_gemm(f)) { p.kn_scale = k_scale; p.kn_rope = f.ROPE; p.kn_rope_bstride = (int64_t)f.L * 128; }
     if (qn_in_gemm(f)) { p.qn_scale = q_scale; p.qn_prescale = 1; }
   }
-  if (f.opt.fuse_vt || f.opt.qkv_heads > 0) { p.vt_rpb = rows; p.vt_row0 = row0; }
+  if (vt_in_gemm(f) || f.opt.qkv_heads > 0) { p.vt_rpb = rows; p.vt_row0 = row0; }
 }
 
 VcGemmProblem prob(const void* A, int64_t lda, const Lin& w, void* C, int64_t ldc, int M) {
@@ -327,7 +424,78 @@ int prof_open(Flux& f, hipStream_t s, int kind, int epi, int n, int k, double fl
 }
 int prof_close(Flux& f, hipStream_t s, Err e) { return f.prof_on ? prof_event(f, s, e) : VC_OK; }
 
+int gemm1(Flux& f, const VcGemmProblem& p, int epi, hipStream_t s, Err e) {     // one problem, no split-K scratch
+  VcGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p[0] = p; a.nprob = 1; a.epi = epi;
+  TRY(prof_open(f, s, VC_LAUNCH_GEMM, epi, p.N, p.K, 2.0 * p.M * p.N * p.K, 0, e));
+  TRY(vc_gemm_launch(a, f.opt.tile_cfg, s, e.buf, e.len));
+  return prof_close(f, s, e);
+}
+
+// lora_mode 1: LinearLora.forward with the reference's three roundings (models/modules/lora.py:92-98), then the Linear's epilogue as
+// its own pass -
+//   y = bf16(x W^T + b);  h = bf16(x A^T);  y = bf16(y + bf16(bf16(h B^T + b_B) * scale));  C = epilogue(y)
+// the lora branch joins through the gated-residual epilogue with the scale vector as its gate.  `p` is the problem the merged plan
+// would launch with `epi`: its A / C row descriptions, its residual and its gate.  A Linear without a pair runs the first step alone.
+int lora_linear(Flux& f, VcGemmProblem p, int epi, const int32_t* step_ptr, int64_t gate_step_stride, hipStream_t s, Err e) {
+  if (epi == VC_EPI_QKV) FAIL(VC_ERR_STATE, "flux: lora_mode 1 runs no fused qkv epilogue");
+  if (f.B == 1) { p.a_rpb = p.c_rpb = 0; p.a_bstride = p.c_bstride = 0; }        // one sample: plain rows
+  const int M = p.M, N = p.N;
+  const bool plain = epi == VC_EPI_BIAS;
+  auto it = f.lora_of.find(p.W);
+  const Lora* lo = it == f.lora_of.end() ? nullptr : &it->second;
+  // scratch rows: those of C where C's are batch-strided (a residual must share C's layout), else M plain rows of N
+  const bool strided = plain && p.c_rpb > 0;
+  const int64_t ldy = strided ? p.ldc : N;
+  const int64_t extent = strided ? (int64_t)((M - 1) / p.c_rpb) * p.c_bstride + (int64_t)p.c_rpb * p.ldc : (int64_t)M * N;
+  if (extent > f.ly_elems || (lo && ((int64_t)M * lo->rank > f.lh_elems || N > f.lscale_elems)))
+    FAIL(VC_ERR_STATE, "flux: the workspace was sized before lora_mode / the LoRA ranks changed: ask vc_flux_workspace_bytes and prepare again");
+  VcGemmProblem base = p;
+  base.res = nullptr; base.gate = nullptr; base.ldres = 0; base.gate_bstride = 0; base.rows_per_batch = M;
+  bf16_t* y = (bf16_t*)p.C;
+  if (!(plain && !lo)) { y = f.LY; base.C = y; base.ldc = ldy; if (!strided) { base.c_rpb = 0; base.c_bstride = 0; } }
+  TRY(gemm1(f, base, VC_EPI_BIAS, s, e));                                              // base_out
+  if (lo) {
+    VcGemmProblem a = base;                                                            // lora_A(x)
+    a.W = lo->a; a.ldw = lo->lda; a.bias = nullptr; a.N = lo->rank;
+    a.C = f.LH; a.ldc = lo->rank; a.c_rpb = 0; a.c_bstride = 0;
+    TRY(gemm1(f, a, VC_EPI_BIAS, s, e));
+    VcGemmProblem b;                                                                   // base_out + lora_B(.) * scale
+    memset(&b, 0, sizeof(b));
+    b.A = f.LH; b.lda = lo->rank; b.W = lo->b; b.ldw = lo->ldb; b.bias = lo->bb;
+    b.M = M; b.N = N; b.K = lo->rank; b.rows_per_batch = M;
+    b.res = y; b.ldres = ldy; b.gate = f.LSCALE;
+    if (plain) { b.C = p.C; b.ldc = p.ldc; b.c_rpb = p.c_rpb; b.c_bstride = p.c_bstride; }
+    else { b.C = f.LY2; b.ldc = N; }
+    TRY(gemm1(f, b, VC_EPI_GATE_RES, s, e));
+    y = (bf16_t*)b.C;
+  }
+  if (plain) return VC_OK;
+  const double bytes = 4.0 * M * N;
+  if (epi == VC_EPI_GELU || epi == VC_EPI_SILU) {
+    TRY(prof_open(f, s, VC_LAUNCH_PASS, epi, N, 0, 0, bytes, e));
+    TRY(vc_act2d_launch(y, N, p.C, p.ldc, M, N, epi == VC_EPI_GELU ? 0 : 1, s, e.buf, e.len));
+    return prof_close(f, s, e);
+  }
+  // the gated residual: one pass per sample (the gate is the sample's modulation row)
+  const int rpb = p.rows_per_batch;
+  for (int r0 = 0; r0 < M; r0 += rpb) {
+    const int rows = std::min(rpb, M - r0);
+    TRY(prof_open(f, s, VC_LAUNCH_PASS, epi, N, 0, 0, 6.0 * rows * N, e));
+    TRY(vc_gate_residual_launch(y + (int64_t)r0 * N, N, (const bf16_t*)p.res + (int64_t)r0 * p.ldres, p.ldres,
+                                (const bf16_t*)p.gate + (int64_t)(r0 / rpb) * p.gate_bstride, (bf16_t*)p.C + (int64_t)r0 * p.ldc, p.ldc,
+                                rows, N, step_ptr, gate_step_stride, s, e.buf, e.len));
+    TRY(prof_close(f, s, e));
+  }
+  return VC_OK;
+}
+
 int gemm(Flux& f, const VcGemmProblem* ps, int n, int epi, const int32_t* step_ptr, int64_t gate_step_stride, hipStream_t s, Err e) {
+  if (f.opt.lora_mode) {      // one Linear after the other, as the reference's modules run
+    for (int i = 0; i < n; ++i) TRY(lora_linear(f, ps[i], epi, step_ptr, gate_step_stride, s, e));
+    return VC_OK;
+  }
   VcGemmArgs a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < n; ++i) a.p[i] = ps[i];
@@ -375,7 +543,7 @@ int attention(Flux& f, const Ctx& c, const void* q1, const void* k1, const void*
   const int variant = attention_variant(f);
   const bool fused_q = vcplan::decode_variant(variant).wave64 && f.opt.fuse_qnorm, q_done = qn_in_gemm(f);     // q_done: by the projection's epilogue, prescaled
   const int64_t ld = 3 * f.D, ldo = f.D + f.mlp;
-  const int parts = (kn_in_gemm(f) ? 0 : VC_QKN_K) | (fused_q ? 0 : VC_QKN_Q) | (f.opt.fuse_vt ? 0 : VC_QKN_VT);
+  const int parts = (kn_in_gemm(f) ? 0 : VC_QKN_K) | (fused_q ? 0 : VC_QKN_Q) | (vt_in_gemm(f) ? 0 : VC_QKN_VT);
   if (parts)
     TRY(vc_qknorm_rope_vt_launch(f.QKV, ld, f.L * ld, q1, k1, q2, k2, split, f.ROPE, (int64_t)f.L * 128, f.VT, f.B, f.L, f.Lp, f.H,
                                  parts, c.s, e.buf, e.len));
@@ -464,6 +632,18 @@ int d2d(void* dst, const void* src, int64_t bytes, hipStream_t s, Err e) {
   return VC_OK;
 }
 
+// vc_flux_set_tap: tap `idx` <- `bytes` of a residual stream, one copy node on the evaluation's own stream
+int tap(Flux& f, size_t idx, const void* src, int64_t bytes, hipStream_t s, Err e) {
+  if (idx >= f.taps.size() || !f.taps[idx]) return VC_OK;
+  TRY(prof_open(f, s, VC_LAUNCH_TAP, 0, 0, 0, 0, 2.0 * bytes, e));         // every tap in ONE launch class
+  TRY(d2d(f.taps[idx], src, bytes, s, e));
+  return prof_close(f, s, e);
+}
+int tap_double(Flux& f, size_t i, hipStream_t s, Err e) {
+  TRY(tap(f, 2 + 2 * i, f.XI, (int64_t)f.B * f.N * f.D * 2, s, e));
+  return tap(f, 3 + 2 * i, f.XT, (int64_t)f.B * f.T * f.D * 2, s, e);
+}
+
 // Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it
 // (ode_update: the Euler step, or a midpoint / rk4 stage combination).  step_ptr counts EVALUATIONS (= steps for Euler).
 // in three pieces, which `evaluate` issues back to back (the plan of every evaluation without the step cache) and the cached step
@@ -487,17 +667,22 @@ int eval_inputs(Flux& f, bool concat, const void* img_rows, hipStream_t s, Err e
   const int in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
   if (concat) TRY(vc_concat_cols_launch(next_input(f), out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
   TRY(d2d(f.XT, f.TXT0, (int64_t)B * T * D * 2, s, e));
-  return lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e);
+  TRY(lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e));
+  TRY(tap(f, 0, f.XI, (int64_t)B * N * D * 2, s, e));
+  return tap(f, 1, f.XT, (int64_t)B * T * D * 2, s, e);
 }
 int eval_blocks(Flux& f, const Ctx& c, size_t first, Err e) {
   const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
   hipStream_t s = c.s;
-  for (size_t i = first; i < f.dbl.size(); ++i) TRY(double_block(f, c, f.dbl[i], e));
+  for (size_t i = first; i < f.dbl.size(); ++i) { TRY(double_block(f, c, f.dbl[i], e)); TRY(tap_double(f, i, s, e)); }
   for (int b = 0; b < B; ++b) {   // cat((txt, img), 1) per sample (model.py:116)
     TRY(d2d(f.X + (int64_t)b * L * D, f.XT + (int64_t)b * T * D, (int64_t)T * D * 2, s, e));
     TRY(d2d(f.X + ((int64_t)b * L + T) * D, f.XI + (int64_t)b * N * D, (int64_t)N * D * 2, s, e));
   }
-  for (auto& w : f.sgl) TRY(single_block(f, c, w, e));
+  for (size_t i = 0; i < f.sgl.size(); ++i) {
+    TRY(single_block(f, c, f.sgl[i], e));
+    TRY(tap(f, 2 + 2 * f.dbl.size() + i, f.X, (int64_t)B * L * D * 2, s, e));
+  }
   return VC_OK;
 }
 int eval_output(Flux& f, const Ctx& c, void* out, bool euler, Err e) {
@@ -536,6 +721,7 @@ int cache_head(Flux& f, hipStream_t s, Err e) {
   TRY(eval_inputs(f, true, nullptr, s, e));
   TRY(d2d(f.X, f.XI, f.B * nd * 2, s, e));                                   // h0
   TRY(double_block(f, c, f.dbl[0], e));                                      // XI = h1
+  TRY(tap_double(f, 0, s, e));
   TRY(vc_residual_change_launch(f.X, f.XI, f.SC_P, f.SC_RS, nullptr, f.SC_METRIC, f.SC_PART, f.B, nd, s, e.buf, e.len));
   HIP(hipMemcpyAsync(f.sc_host, f.SC_METRIC, sizeof(float), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
   return VC_OK;
@@ -606,7 +792,9 @@ int time_precompute(Flux& f, int S, int timesteps_is_bf16, hipStream_t s, Err e)
   else
     TRY(vc_add3_launch(f.TVEC, f.YVEC, nullptr, f.VEC, (int64_t)M * D, (int64_t)B * D, 1, s, e.buf, e.len));
   TRY(vc_silu_launch(f.VEC, f.H1, (int64_t)M * D, s, e.buf, e.len));
-  return lin(f, f.modulation, f.H1, D, f.MOD, f.n_mod, M, VC_EPI_BIAS, s, e);
+  if (!f.opt.lora_mode) return lin(f, f.modulation, f.H1, D, f.MOD, f.n_mod, M, VC_EPI_BIAS, s, e);
+  for (const auto& m : f.mods) TRY(lin(f, m.first, f.H1, D, f.MOD + m.second, f.n_mod, M, VC_EPI_BIAS, s, e));   // each on its own columns of MOD
+  return VC_OK;
 }
 
 void drop_prof(Flux& f) {
@@ -622,8 +810,9 @@ void drop_graph(Flux& f) {
 // evaluation (modulation rows, dt, the stage of a midpoint / rk4 step) is indexed on the device by STEP
 int step_graph(Flux& f, hipStream_t s, Err e) {
   Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s,
-               f.cfg_active, 0};
+               f.cfg_active, 0, {}};
   if (f.cfg_active) memcpy(&k.cfg_bits, &f.cfg_s, 4);
+  k.taps = f.taps;
   if (const Flux::Step* hit = f.graphs.find(k)) {
     f.step = *hit; f.key = k;
     return VC_OK;
@@ -654,6 +843,14 @@ int step_graph(Flux& f, hipStream_t s, Err e) {
   return VC_OK;
 }
 
+// lora_mode 1: what vc_flux_prepare parked in the workspace (txt_in, vector_in, guidance_in) ran with the scale of that moment
+int fresh_scale(const Flux& f, const char* what, Err e) {
+  if (f.opt.lora_mode && f.scale_stale)
+    FAIL(VC_ERR_STATE, "%s: the lora scale changed after vc_flux_prepare, whose txt_in / vector_in / guidance_in projections ran with the old "
+                       "one: call vc_flux_prepare again (captured steps are kept)", what);
+  return VC_OK;
+}
+
 }  // namespace
 
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen) {
@@ -669,6 +866,7 @@ int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int e
   f->cfg = *cfg;
   f->D = cfg->hidden_size; f->H = cfg->num_heads; f->mlp = cfg->mlp_hidden;
   layout_modulation(*f);
+  f->taps.assign(2 + 2 * (size_t)cfg->depth + (size_t)cfg->depth_single_blocks, nullptr);
   int dev = 0;
   hipDeviceProp_t p;
   if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) {
@@ -711,6 +909,98 @@ int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, cons
   return VC_OK;
 }
 
+int vc_flux_bind_lora_impl(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                           const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!name) FAIL(VC_ERR_ARG, "flux_bind_lora: null name");
+  if (!lora_a && !lora_b) {           // unbind
+    f.lora.erase(name);
+  } else {
+    if (!lora_a || !lora_b) FAIL(VC_ERR_ARG, "flux_bind_lora: lora_a and lora_b of '%s' must both be given", name);
+    if (rank <= 0 || rank % 64)
+      FAIL(VC_ERR_ARG, "flux_bind_lora: rank = %d of '%s' must be a positive multiple of 64, the GEMM's K granularity (zero-pad the factors)", rank, name);
+    int out = 0, in = 0;              // what the Linear is: a module of the stacked modulation matrix, or a bound weight
+    auto mo = f.mod_off.find(name);
+    if (mo != f.mod_off.end()) {
+      int64_t end = f.n_mod;
+      for (const auto& kv : f.mod_off) if (kv.second > mo->second && kv.second < end) end = kv.second;
+      out = (int)(end - mo->second); in = f.D;
+    } else {
+      auto it = f.bound.find(name);
+      if (it == f.bound.end()) FAIL(VC_ERR_STATE, "flux_bind_lora: name = '%s' is no Linear bound by vc_flux_bind_weight (bind the weight first)", name);
+      out = it->second.N; in = it->second.K;
+    }
+    if (out_features != out || in_features != in)
+      FAIL(VC_ERR_ARG, "flux_bind_lora: out_features, in_features = %d, %d of '%s', its weight is [%d, %d]", out_features, in_features, name, out, in);
+    if (lda < in || ldb < rank || lda % 8 || ldb % 8)
+      FAIL(VC_ERR_ARG, "flux_bind_lora: lda = %lld, ldb = %lld of '%s' must be multiples of 8, at least in_features and rank", (long long)lda, (long long)ldb, name);
+    Lora lo;
+    lo.a = lora_a; lo.b = lora_b; lo.bb = lora_b_bias; lo.rank = rank; lo.out = out; lo.in = in; lo.lda = lda; lo.ldb = ldb;
+    f.lora[name] = lo;
+  }
+  f.resolved = false;
+  f.prepared = false;   // the widest rank sizes the workspace
+  drop_graph(f);
+  return VC_OK;
+}
+
+int vc_flux_set_lora_scale_impl(void* handle, float scale, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!(scale - scale == 0.0f) || bf16_round(scale) != scale)
+    FAIL(VC_ERR_ARG, "flux_set_lora_scale: scale = %.9g is not a bf16 value; the un-merged mode applies it as a bf16 vector and would round it "
+                     "(merge with vc_lora_merge, which applies any scale in f32)", scale);
+  if (f.in_flight)      // the trajectory's modulation rows and its step-invariant projections ran with the old scale
+    FAIL(VC_ERR_STATE, "flux_set_lora_scale: scale cannot change between vc_flux_sample_begin and vc_flux_sample_end");
+  // host only.  The next vc_flux_prepare writes the value into the scale vector, which keeps its place in that workspace: a step
+  // captured there replays with it.  Until then the prepared state is of the old scale and forward / sample_begin refuse it
+  if (scale != f.lora_scale && f.prepared) f.scale_stale = true;
+  f.lora_scale = scale;
+  return VC_OK;
+}
+
+// "img_in", "txt_in", "double.{i}.img", "double.{i}.txt", "single.{i}" -> the tap's index
+static int tap_index(Flux& f, const char* what, const char* name, size_t& idx, Err e) {
+  if (!name) FAIL(VC_ERR_ARG, "%s: null name", what);
+  int i = -1, n = 0;
+  char st[4] = "";
+  if (!strcmp(name, "img_in")) { idx = 0; return VC_OK; }
+  if (!strcmp(name, "txt_in")) { idx = 1; return VC_OK; }
+  if (sscanf(name, "double.%d.%3[a-z]%n", &i, st, &n) == 2 && !name[n] && i >= 0 && (!strcmp(st, "img") || !strcmp(st, "txt"))) {
+    if (i >= f.cfg.depth) FAIL(VC_ERR_ARG, "%s: name = '%s', the model has %d double blocks", what, name, f.cfg.depth);
+    idx = 2 + 2 * (size_t)i + (st[0] == 't');
+    return VC_OK;
+  }
+  n = 0;
+  if (sscanf(name, "single.%d%n", &i, &n) == 1 && !name[n] && i >= 0) {
+    if (i >= f.cfg.depth_single_blocks) FAIL(VC_ERR_ARG, "%s: name = '%s', the model has %d single blocks", what, name, f.cfg.depth_single_blocks);
+    idx = 2 + 2 * (size_t)f.cfg.depth + (size_t)i;
+    return VC_OK;
+  }
+  FAIL(VC_ERR_ARG, "%s: unknown tap name = '%s' (img_in, txt_in, double.{i}.img, double.{i}.txt, single.{i})", what, name);
+}
+
+int vc_flux_set_tap_impl(void* handle, const char* name, void* dst, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  size_t idx = 0;
+  TRY(tap_index(f, "flux_set_tap", name, idx, e));
+  if (f.in_flight && f.taps[idx] != dst)      // the captured step of the trajectory keeps copying to the old buffer
+    FAIL(VC_ERR_STATE, "flux_set_tap: the tap '%s' cannot change between vc_flux_sample_begin and vc_flux_sample_end", name);
+  f.taps[idx] = dst;
+  return VC_OK;
+}
+
+int vc_flux_tap_shape_impl(void* handle, const char* name, int64_t* rows, int32_t* cols, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  size_t idx = 0;
+  TRY(tap_index(f, "flux_tap_shape", name, idx, e));
+  if (!rows || !cols) FAIL(VC_ERR_ARG, "flux_tap_shape: null rows / cols");
+  if (!f.prepared) FAIL(VC_ERR_STATE, "flux_tap_shape: call vc_flux_prepare first (the rows are those of the prepared geometry)");
+  const size_t first_single = 2 + 2 * (size_t)f.cfg.depth;
+  *rows = (int64_t)f.B * (idx >= first_single ? f.L : idx % 2 ? f.T : f.N);
+  *cols = f.D;
+  return VC_OK;
+}
+
 int64_t vc_flux_mod_offset_impl(void* handle, const char* name) {
   if (!handle) return -1;
   Flux& f = *(Flux*)handle;
@@ -730,6 +1020,11 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
       case ZERO_TO_2: value = value < 0 ? 0 : value > 2 ? 2 : value; break;
       case ZERO_OR_H: if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H); break;
       case ANY: break;
+    }
+    if (o.member == &Options::lora_mode && value != f.opt.lora_mode) {
+      if (f.in_flight)
+        FAIL(VC_ERR_STATE, "flux_set_option: lora_mode cannot change between vc_flux_sample_begin and vc_flux_sample_end");
+      f.prepared = false;    // the workspace carve-up differs: vc_flux_workspace_bytes + vc_flux_prepare again
     }
     f.opt.*o.member = value;
     return VC_OK;
@@ -755,7 +1050,11 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
   if (in->kv_gap && !in->kv_len) FAIL(VC_ERR_ARG, "flux_prepare: kv_gap needs kv_len");
   if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "flux_prepare: workspace must be 256-byte aligned");
   TRY(resolve(f, e));
+  if (f.opt.lora_mode && f.opt.qkv_heads > 0)
+    FAIL(VC_ERR_ARG, "flux_prepare: lora_mode 1 takes the qkv weights in their natural row order (option qkv_heads 0)");
   f.prepared = false;
+  f.in_flight = false;
+  f.scale_stale = false;
   const int64_t need = carve(f, f, (char*)workspace, B, T, N, S);
   if (workspace_bytes < need) FAIL(VC_ERR_ARG, "flux_prepare: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   f.base = (char*)workspace;
@@ -838,6 +1137,7 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
   HIP(hipMemsetAsync(f.VT, 0, (size_t)B * f.H * 128 * f.Lp * 2, s), "hipMemsetAsync");
   // the flag words of the attention kernel's in-launch combine: zero before the first launch (every launch leaves them zero)
   HIP(hipMemsetAsync((char*)f.ATT_SCRATCH + vcplan::attention_flags_offset(vc_cu_count()), 0, (size_t)vcplan::attention64_flags_bytes(f.n_cu), s), "hipMemsetAsync");
+  if (f.opt.lora_mode) TRY(vc_fill_bf16_launch(f.LSCALE, f.lora_scale, f.lscale_elems, s, e.buf, e.len));
   // step-invariant projections
   TRY(lin(f, f.txt_in, in->txt, f.cfg.context_in_dim, f.TXT0, D, B * T, VC_EPI_BIAS, s, e));
   if (f.cfg.guidance_embed) {
@@ -856,6 +1156,7 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
                          char* err, int errlen) {
   HANDLE(Flux, f, "flux");
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_forward: call vc_flux_prepare first");
+  TRY(fresh_scale(f, "flux_forward", e));
   if (!img || !timesteps || !out) FAIL(VC_ERR_ARG, "flux_forward: null argument");
   TRY(stage_begin(f, f.B * sizeof(float) + 256, e));
   float* ts = stage_take<float>(f, f.B);
@@ -864,6 +1165,7 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
   TRY(stage_end(f, s, e));
   TRY(time_precompute(f, 1, timesteps_is_bf16, s, e));
   f.steps_total = f.steps_done = 0;   // MOD now holds this evaluation's rows, not a trajectory's
+  f.in_flight = false;
   return evaluate(f, nullptr, false, img, out, false, s, e);
 }
 
@@ -887,6 +1189,7 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   const int E = vc_evals_of(method);
   if (!E) FAIL(VC_ERR_ARG, "flux_sample: unknown solver method %d (VC_SOLVER_EULER, VC_SOLVER_MIDPOINT, VC_SOLVER_RK4)", method);
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample: call vc_flux_prepare first");
+  TRY(fresh_scale(f, "flux_sample", e));
   if (!x || !cond || !t_grid) FAIL(VC_ERR_ARG, "flux_sample: null argument");
   const int S = n_points - 1, B = f.B;
   if (S < 1 || (int64_t)S * E > f.S)
@@ -938,6 +1241,7 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   // no P yet: the first metric is read against zeros (and reported as NaN), never against an earlier trajectory's residual
   if (cached) HIP(hipMemsetAsync(f.SC_P, 0, (size_t)n * f.D * 2, s), "hipMemsetAsync");
   f.steps_total = S; f.steps_done = 0;
+  f.in_flight = true;
   return VC_OK;
 }
 
@@ -981,6 +1285,7 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
   HANDLE(Flux, f, "flux");
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_sample_end: no sample in flight");
   if (!x_out) FAIL(VC_ERR_ARG, "flux_sample_end: null output");
+  f.in_flight = false;
   return d2d(x_out, ode_state(f), ode_state_bytes(f), s, e);
 }
 

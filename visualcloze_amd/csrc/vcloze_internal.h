@@ -59,6 +59,7 @@ int vc_ode_update_launch(const char* what, int method, int stage, void* y, int s
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen);
+int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen);
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
                               int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
@@ -107,6 +108,11 @@ int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int e
 int vc_flux_destroy_impl(void* handle, char* err, int errlen);
 int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, const void* bias, int32_t rows, int32_t cols, int64_t ldw,
                              char* err, int errlen);
+int vc_flux_bind_lora_impl(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                           const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank, char* err, int errlen);
+int vc_flux_set_lora_scale_impl(void* handle, float scale, char* err, int errlen);
+int vc_flux_set_tap_impl(void* handle, const char* name, void* dst, char* err, int errlen);
+int vc_flux_tap_shape_impl(void* handle, const char* name, int64_t* rows, int32_t* cols, char* err, int errlen);
 int64_t vc_flux_mod_offset_impl(void* handle, const char* name);
 int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char* err, int errlen);
 int64_t vc_flux_workspace_bytes_impl(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps);

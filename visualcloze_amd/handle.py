@@ -1,8 +1,9 @@
 """`FluxHandle`: the handle API of include/vcloze_hip.h (vc_flux_*) behind torch tensors — Flux.forward and the whole
 fixed-grid solver loop (Euler, midpoint, rk4) as ONE C call each.  The launch plan lives in csrc/flux_engine.hip; this class
 binds the prepared (bf16, LoRA-merged) weights by reference-module path, owns the workspace tensors and converts the
-host-side inputs (ids, timesteps, masks) to the plain arrays the ABI takes.  `engine.FluxEngine` is the same plan spelt
-in Python over the op-level ABI; it stays for the un-merged LoRA parity mode and for per-block taps."""
+host-side inputs (ids, timesteps, masks) to the plain arrays the ABI takes.  Over un-merged weights (`PreparedWeights.ref`) it binds
+the base weights and the LoRA pairs and runs the handle's un-merged mode (vc_flux_bind_lora, option lora_mode 1).
+`engine.FluxEngine` is the same plan spelt in Python over the op-level ABI: the parity twin of both modes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -151,6 +152,22 @@ class FluxHandle(_Handle):
         hip._check(L.vc_flux_bind_weight(self.h, b"splitk_ws", self._sk_ws.data_ptr(), None, 1, nf, nf), "vc_flux_bind_weight(splitk_ws)")
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._opts: Dict[str, int] = {}
+        self._lora: Dict[str, tuple] = {}
+        self._taps: Dict[str, torch.Tensor] = {}
+        self.lora_mode = 0
+        if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
+            scales = []
+            for name, R in weights.ref.items():
+                if name.endswith(".linear1.qkv") or name.endswith(".linear1.mlp") or R.A is None:
+                    continue                                # (row ranges of linear1, whose pair is bound whole)
+                self.bind_lora(name, R.A, R.B, R.bB)
+                scales.append(R.scale[:1])
+            self.set_lora_mode(1)
+            if scales:
+                sc = set(torch.cat(scales).float().cpu().tolist())
+                if len(sc) != 1:
+                    raise hip.VclozeHipError(f"the handle's un-merged mode applies ONE lora scale to every Linear, the model holds {sorted(sc)}")
+                self.set_lora_scale(sc.pop())
         self._step_cache = (0.0, 0)       # vc_flux_set_step_cache: off
         self._cfg = None                  # vc_flux_set_cfg: off
         self.geom: Optional[Tuple[int, int, int, int]] = None
@@ -183,6 +200,75 @@ class FluxHandle(_Handle):
             if self._opts.get(k) != v:
                 hip._check(hip.lib().vc_flux_set_option(self.h, k.encode(), v), f"vc_flux_set_option({k})")
                 self._opts[k] = v
+
+    def bind_lora(self, name: str, lora_a, lora_b, lora_b_bias=None) -> None:
+        """vc_flux_bind_lora: the pair of Linear `name` (bound already) - lora_a [r, in], lora_b [out, r], lora_b's bias [out] or
+        None, bf16 on the handle's device, kept alive here.  A rank that is no multiple of 64 is zero-padded (new tensors).  Both
+        None removes the pair."""
+        if lora_a is None and lora_b is None:
+            hip._check(hip.lib().vc_flux_bind_lora(self.h, name.encode(), None, 0, None, 0, None, 0, 0, 0), f"vc_flux_bind_lora({name})")
+            self._lora.pop(name, None)
+            self._ws.clear()
+            self.geom = None
+            return
+        hip._bf16(lora_a, name + ".lora_A"); hip._bf16(lora_b, name + ".lora_B")
+        r = lora_a.shape[0]
+        if r % 64:
+            rk = (r + 63) // 64 * 64
+            A = torch.zeros(rk, lora_a.shape[1], dtype=torch.bfloat16, device=lora_a.device)
+            Bm = torch.zeros(lora_b.shape[0], rk, dtype=torch.bfloat16, device=lora_b.device)
+            A[:r], Bm[:, :r] = lora_a, lora_b
+            lora_a, lora_b = A, Bm
+        if lora_a.stride(1) != 1 or lora_b.stride(1) != 1 or (lora_b_bias is not None and not lora_b_bias.is_contiguous()):
+            raise hip.VclozeHipError(f"{name}: LoRA factor rows / bias must be contiguous")
+        if lora_b_bias is not None:
+            hip._bf16(lora_b_bias, name + ".lora_B.bias")
+        hip._check(hip.lib().vc_flux_bind_lora(self.h, name.encode(), lora_a.data_ptr(), lora_a.stride(0), lora_b.data_ptr(),
+                                               lora_b.stride(0), hip._p(lora_b_bias), lora_b.shape[0], lora_a.shape[1], lora_a.shape[0]),
+                   f"vc_flux_bind_lora({name})")
+        self._lora[name] = (lora_a, lora_b, lora_b_bias)
+        self._ws.clear()          # the widest rank sizes the scratch
+        self.geom = None
+
+    def set_lora_mode(self, mode: int) -> None:
+        """vc_flux_set_option("lora_mode"): 1 = the bound weights are un-merged base weights and every Linear runs LinearLora's
+        three roundings (lora.py:92-98); 0 = plain Linears.  A switch needs a new prepare (other workspace size)."""
+        hip._check(hip.lib().vc_flux_set_option(self.h, b"lora_mode", int(mode)), "vc_flux_set_option(lora_mode)")
+        if int(bool(mode)) != self.lora_mode:
+            self.lora_mode = int(bool(mode))
+            self._ws.clear()
+            self.geom = None
+
+    def set_lora_scale(self, scale: float) -> None:
+        """vc_flux_set_lora_scale: the scale of every pair; a bf16 value, anything else is refused, and so is a change while a
+        trajectory is in flight.  Call `prepare` again after a change (forward / sample_* refuse a prepared state of the old scale);
+        captured steps stay and replay with the new scale."""
+        hip._check(hip.lib().vc_flux_set_lora_scale(self.h, float(scale)), "vc_flux_set_lora_scale")
+
+    def tap_shape(self, name: str) -> Tuple[int, int]:
+        rows, cols = C.c_int64(0), C.c_int32(0)
+        hip._check(hip.lib().vc_flux_tap_shape(self.h, name.encode(), C.byref(rows), C.byref(cols)), f"vc_flux_tap_shape({name})")
+        return rows.value, cols.value
+
+    def set_tap(self, name: str, dst: Optional[torch.Tensor]) -> None:
+        """vc_flux_set_tap: `dst` (bf16, contiguous, tap_shape(name) elements, kept alive here) receives the residual stream `name` -
+        img_in, txt_in, double.{i}.img, double.{i}.txt, single.{i} - of every evaluation issued from the next forward / sample_begin on;
+        None removes the tap."""
+        if dst is not None:
+            hip._bf16(dst, name)
+            rows, cols = self.tap_shape(name)
+            if not dst.is_contiguous() or dst.numel() != rows * cols:
+                raise hip.VclozeHipError(f"set_tap({name}): a contiguous bf16 buffer of {rows} x {cols} expected, got {tuple(dst.shape)}")
+        hip._check(hip.lib().vc_flux_set_tap(self.h, name.encode(), hip._p(dst)), f"vc_flux_set_tap({name})")
+        if dst is None:
+            self._taps.pop(name, None)
+        else:
+            self._taps[name] = dst
+
+    def tap_names(self) -> list:
+        p = self.params
+        return (["img_in", "txt_in"] + [f"double.{i}.{st}" for i in range(p.depth) for st in ("img", "txt")]
+                + [f"single.{i}" for i in range(p.depth_single_blocks)])
 
     def set_step_cache(self, step_cache=None) -> None:
         """vc_flux_set_step_cache: a `transport.StepCache` (or anything with .threshold / .max_consecutive), or None = off.

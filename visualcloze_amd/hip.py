@@ -126,7 +126,7 @@ class FluxLaunchClass(C.Structure):          # VcFluxLaunchClass (vc_flux_profil
                 ("reserved2", C.c_float)]
 
 
-LAUNCH_GEMM, LAUNCH_ATTENTION, LAUNCH_LN_MODULATE = 1, 2, 3
+LAUNCH_GEMM, LAUNCH_ATTENTION, LAUNCH_LN_MODULATE, LAUNCH_PASS, LAUNCH_TAP = 1, 2, 3, 4, 5
 
 SYMBOLS = {
     "vc_abi_version": (C.c_int, []),
@@ -186,6 +186,10 @@ SYMBOLS = {
     "vc_flux_create": (C.c_int, [C.POINTER(FluxConfig), C.POINTER(_vp)]),
     "vc_flux_destroy": (C.c_int, [_vp]),
     "vc_flux_bind_weight": (C.c_int, [_vp, C.c_char_p, _vp, _vp, _i32, _i32, _i64]),
+    "vc_flux_bind_lora": (C.c_int, [_vp, C.c_char_p, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32]),
+    "vc_flux_set_lora_scale": (C.c_int, [_vp, C.c_float]),
+    "vc_flux_set_tap": (C.c_int, [_vp, C.c_char_p, _vp]),
+    "vc_flux_tap_shape": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64), C.POINTER(_i32)]),
     "vc_flux_mod_offset": (_i64, [_vp, C.c_char_p]),
     "vc_flux_set_option": (C.c_int, [_vp, C.c_char_p, _i32]),
     "vc_flux_workspace_bytes": (_i64, [_vp, _i32, _i32, _i32, _i32]),

@@ -166,7 +166,7 @@ class MaskLayout:
 
     def __init__(self, txt_mask, img_mask, B: int, T: int, N: int):
         self.B, self.T, self.N = B, T, N
-        self.perm_t = self.perm_i = self.inv_i = None
+        self.perm_t = self.perm_i = self.inv_i = self.inv_t = None
         if txt_mask is None or img_mask is None:
             self.n_txt, self.n_img = [T] * B, [N] * B
             return
@@ -178,6 +178,7 @@ class MaskLayout:
         pi = torch.sort((~im).to(torch.uint8), dim=1, stable=True).indices
         if not torch.equal(pt, torch.arange(T).expand(B, T)):
             self.perm_t = pt
+            self.inv_t = torch.argsort(pt, dim=1)
         if not torch.equal(pi, torch.arange(N).expand(B, N)):
             self.perm_i = pi
             self.inv_i = torch.argsort(pi, dim=1)
@@ -211,9 +212,17 @@ class MaskLayout:
 
     def img_rows_back(self, x: Tensor, sl) -> Tensor:
         """kernel-order [bs, N, ...] image-stream rows back in the caller's order"""
-        if self.inv_i is None:
+        return self._back(x, self.inv_i, sl)
+
+    def txt_rows_back(self, x: Tensor, sl) -> Tensor:
+        """kernel-order [bs, T, ...] text-stream rows back in the caller's order (per-block taps)"""
+        return self._back(x, self.inv_t, sl)
+
+    @staticmethod
+    def _back(x: Tensor, inv, sl) -> Tensor:
+        if inv is None:
             return x
-        idx = self.inv_i[sl].to(x.device)
+        idx = inv[sl].to(x.device)
         return torch.gather(x, 1, idx.reshape(idx.shape + (1,) * (x.dim() - 2)).expand(x.shape))
 
 
@@ -269,6 +278,10 @@ class Flux(nn.Module):
         # reference does - base GEMM, two skinny GEMMs, three bf16 roundings (models/modules/lora.py:92-98) - so that
         # the merge's one-rounding deviation is a choice, not a necessity; slower (+8 % FLOPs, unfused epilogues).
         self.lora_mode = "merged"
+        # who runs lora_mode "ref": "python" = the Python-ordered plan (engine.FluxEngine: one sample per launch sequence, Euler on a
+        # bf16 state only), "handle" = the C handle's un-merged mode (vc_flux_bind_lora, option lora_mode 1: the same launches in the
+        # same order, and with them batches, f32 states, midpoint / rk4, true CFG, the step cache and a runtime lora scale)
+        self.ref_plan = "python"
         # the prepared qkv weights (merged mode) are stored HEAD-PERMUTED - every key head inside one 192-column GEMM tile -
         # so that QKNorm + RoPE of k can ride the projection's epilogue (hip.qkv_head_permutation, VcGemmProblem.kn_heads)
         self.qkv_permute = True
@@ -286,6 +299,28 @@ class Flux(nn.Module):
     def _weights_fingerprint(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple(
             m.scale for _, m in self._linears()) + (self.lora_mode, self.qkv_permute, self.lora_merge)
+
+    def _check_ref_plan(self) -> None:
+        if self.ref_plan not in ("python", "handle"):
+            raise ValueError(f"ref_plan must be 'python' or 'handle', got {self.ref_plan!r}")
+
+    def set_lora_scale(self, scale: float) -> None:
+        """models/model.py:172-175.  With lora_mode "ref" on the C handle (ref_plan "handle") a prepared model takes the new scale
+        at run time - vc_flux_set_lora_scale: no re-preparation of the weights, captured steps stay, the next forward's vc_flux_prepare fills it in - and, as that mode promises the
+        reference's roundings, refuses a scale that is no bf16 value.  Otherwise the next forward re-prepares (merged mode: re-merges)."""
+        assert isinstance(scale, float), "scalar value must be a float"
+        self._check_ref_plan()
+        live = (self.lora_mode == "ref" and self.ref_plan == "handle" and self._handle is not None and self._engine is not None
+                and self._handle.W is self._engine.W and self._fingerprint == self._weights_fingerprint())
+        if live:
+            self._handle.set_lora_scale(scale)            # raises for a scale bf16 cannot hold, before anything changes
+            for R in self._engine.W.ref.values():         # the twin's operands say the same
+                if R.scale is not None:
+                    R.scale.fill_(scale)
+        for _, m in self._linears():
+            m.set_scale(scale=scale)
+        if live:
+            self._fingerprint = self._weights_fingerprint()
 
     @staticmethod
     @torch.no_grad()
@@ -362,6 +397,7 @@ class Flux(nn.Module):
             raise ValueError(f"lora_mode must be 'merged' or 'ref', got {self.lora_mode!r}")
         if self.lora_merge not in ("torch", "hip"):
             raise ValueError(f"lora_merge must be 'torch' or 'hip', got {self.lora_merge!r}")
+        self._check_ref_plan()
         w, b, ref = {}, {}, ({} if self.lora_mode == "ref" else None)
         bf = lambda t: None if t is None else t.detach().to(torch.bfloat16).contiguous()  # noqa: E731
         # all modulation projections are stacked: one GEMM yields every shift/scale/gate of a step.  Their merged rows
@@ -487,9 +523,11 @@ class Flux(nn.Module):
 
     def handle(self):
         """The C-side engine (`handle.FluxHandle`) over the prepared weights, or None when this model runs the
-        Python-ordered plan (use_handle False, un-merged LoRA mode).  Test / A-B knobs set on `engine()` apply to both."""
+        Python-ordered plan (use_handle False, or the un-merged LoRA mode unless ref_plan is "handle").  Test / A-B knobs set on
+        `engine()` apply to both."""
+        self._check_ref_plan()
         eng = self.engine()
-        if not self.use_handle or eng.W.ref is not None:
+        if not self.use_handle or (eng.W.ref is not None and self.ref_plan != "handle"):
             return None
         if self._handle is None or self._handle.W is not eng.W:
             from .handle import FluxHandle
@@ -541,8 +579,9 @@ class Flux(nn.Module):
         timesteps = per_sample(timesteps, B)
         lay = MaskLayout(txt_mask, img_mask, B, T, N)
         h = self.handle()
-        for b0 in range(0, B, eng.MAX_BATCH):          # samples of a chunk run as ONE stacked launch sequence
-            bs = min(eng.MAX_BATCH, B - b0)
+        mb = self.max_batch()
+        for b0 in range(0, B, mb):                     # samples of a chunk run as ONE stacked launch sequence
+            bs = min(mb, B - b0)
             sl = slice(b0, b0 + bs)
             if h is not None:                           # one C call per chunk: vc_flux_prepare + vc_flux_forward
                 h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
@@ -560,6 +599,60 @@ class Flux(nn.Module):
             out[sl].copy_(lay.img_rows_back(ws.V.reshape(bs, N, -1), sl))
         return out
 
+    def max_batch(self) -> int:
+        """samples per launch sequence: the engine's (one in the Python-ordered un-merged mode), the handle's where it runs that mode"""
+        eng, h = self.engine(), self.handle()
+        return h.MAX_BATCH if h is not None and eng.W.ref is not None else eng.MAX_BATCH
+
+    @torch.no_grad()
+    def block_taps(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
+                   txt_mask: Tensor = None, img_mask: Tensor = None, guidance: Optional[Tensor] = None) -> dict:
+        """One `forward` through the C handle with every per-block tap set (vc_flux_set_tap): the residual streams after img_in /
+        txt_in ("img_in" [B, N, D], "txt_in" [B, T, D]), after every DoubleStream block ("double.{i}.img", "double.{i}.txt") and after
+        every SingleStream block ("single.{i}" [B, T + N, D]: text rows, then image rows), as bf16 device tensors in the CALLER's row
+        order (the reference's), plus "out" [B, N, out_channels].  Either LoRA mode; the taps are cleared afterwards."""
+        h = self.handle()
+        if h is None:
+            raise hip.VclozeHipError("block_taps needs the C handle (use_handle True; with lora_mode 'ref': ref_plan 'handle')")
+        if img.ndim != 3 or txt.ndim != 3:
+            raise ValueError("Input img and txt tensors must have 3 dimensions.")
+        if self.params.guidance_embed and guidance is None:
+            raise ValueError("Didn't get guidance strength for guidance distilled model.")
+        eng = self.engine()
+        B, N, _ = img.shape
+        T, D, dev = txt.shape[1], self.hidden_size, eng.dev
+        bf = lambda t: t.to(dev, torch.bfloat16).contiguous()  # noqa: E731
+        gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
+        guidance, timesteps = per_sample(guidance, B), per_sample(timesteps, B)
+        lay = MaskLayout(txt_mask, img_mask, B, T, N)
+        names = h.tap_names()
+        parts = {n: [] for n in names + ["out"]}
+        mb = self.max_batch()
+        for b0 in range(0, B, mb):
+            bs = min(mb, B - b0)
+            sl = slice(b0, b0 + bs)
+            h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
+                      lay.img_rows(img_ids, sl), lay.txt_rows(txt_ids, sl), 1, lay.kv_len(sl), lay.kv_gap(sl))
+            bufs = {n: torch.empty(*h.tap_shape(n), dtype=torch.bfloat16, device=dev) for n in names}
+            try:
+                for n, t in bufs.items():
+                    h.set_tap(n, t)
+                o = torch.empty(bs, N, self.out_channels, dtype=torch.bfloat16, device=dev)
+                h.forward(bf(lay.img_rows(img, sl)), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
+            finally:
+                for n in names:
+                    h.set_tap(n, None)
+            parts["out"].append(lay.img_rows_back(o, sl))
+            for n, t in bufs.items():
+                if n.startswith("single."):
+                    j = t.reshape(bs, T + N, D)
+                    parts[n].append(torch.cat((lay.txt_rows_back(j[:, :T], sl), lay.img_rows_back(j[:, T:], sl)), dim=1))
+                elif n == "txt_in" or n.endswith(".txt"):
+                    parts[n].append(lay.txt_rows_back(t.reshape(bs, T, D), sl))
+                else:
+                    parts[n].append(lay.img_rows_back(t.reshape(bs, N, D), sl))
+        return {n: torch.cat(v, dim=0) for n, v in parts.items()}
+
 
 class FluxLoraWrapper(Flux):
     """models/model.py:154-175: Flux with a LoRA pair on EVERY Linear (`replace_linear_with_lora`)."""
@@ -569,7 +662,3 @@ class FluxLoraWrapper(Flux):
         self.lora_rank = lora_rank
         for _, m in list(self._linears()):
             m.add_lora(lora_rank, lora_scale)
-
-    def set_lora_scale(self, scale: float) -> None:
-        for _, m in self._linears():
-            m.set_scale(scale=scale)

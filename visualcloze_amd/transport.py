@@ -165,9 +165,9 @@ class Sampler:
                 return _sample_foreign(fwd, x, kw, t, return_trajectory, sampling_method)
             if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward":
                 if step_cache is not None:      # never silently ignored: only the C handle's loop implements it
-                    if getattr(owner, "lora_mode", "merged") == "ref" or owner.handle() is None:
-                        raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' or the Python-ordered "
-                                         "plan (use_handle False)")
+                    if owner.handle() is None:
+                        raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' (unless ref_plan='handle') "
+                                         "or the Python-ordered plan (use_handle False)")
                     if not _fusable(owner, x, sampling_method):
                         raise ValueError(f"step_cache: a {x.dtype} state is stepped eagerly, where no cache exists")
                 if _fusable(owner, x, sampling_method):
@@ -186,9 +186,9 @@ class Sampler:
 def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
     """The fused loop steps a bf16 state (the pipeline's, visualcloze.py:399) or - through the C handle - an f32 one IN f32
     (integrators.py:119 keeps the caller's state dtype).  Anything else (f16 / f64 states, an f32 state in the un-merged LoRA
-    parity mode whose plan is ordered from Python) is stepped eagerly through Flux.forward with torch's own promotion rules:
+    parity mode where its plan is ordered from Python, ref_plan="python") is stepped eagerly through Flux.forward with torch's own promotion rules:
     never a silent per-step rounding of the caller's state.  The Python-ordered plan (engine.py: use_handle False, or the
-    un-merged LoRA parity mode lora_mode="ref") knows the Euler update only: "midpoint" / "rk4" without the C handle are
+    un-merged LoRA parity mode lora_mode="ref" unless ref_plan="handle") knows the Euler update only: "midpoint" / "rk4" without the C handle are
     stepped eagerly too, one Flux.forward per stage through `_sample_foreign`."""
     if method != "euler" and flux.handle() is None:
         return False
@@ -288,17 +288,18 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
     st = eng.stream
     st.wait_stream(torch.cuda.current_stream())
     # the C handle runs the whole trajectory of a chunk in ONE call (vc_flux_sample_ode); the un-merged LoRA mode uses the
-    # Python-ordered plan (bf16 states, Euler only: _fusable)
+    # Python-ordered plan (bf16 states, Euler only: _fusable) unless ref_plan is "handle"
     h = flux.handle()
     if h is not None:
         h.set_step_cache(step_cache)               # None: off, whatever an earlier trajectory on this handle ran with
         h.set_cfg(cfg_scale)
     elif cfg_scale is not None:
         raise hip.VclozeHipError("true CFG in the fused loop needs the C handle")
+    mb = flux.max_batch()
     if cfg_scale is None:
-        chunks = [slice(b0, min(b0 + eng.MAX_BATCH, B)) for b0 in range(0, B, eng.MAX_BATCH)]
+        chunks = [slice(b0, min(b0 + mb, B)) for b0 in range(0, B, mb)]
     else:
-        chunks = cfg_chunks(B, eng.MAX_BATCH)
+        chunks = cfg_chunks(B, mb)
     stats = []
     with torch.cuda.stream(st):
         s = st.cuda_stream
