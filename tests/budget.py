@@ -342,6 +342,102 @@ def gemm_case(a, w, bias, epi, res=None, gate=None):
     return res.to(torch.float64) + g64 * t, [(t_mag, g64.abs()), gt_mag, STORE], f32 * g64.abs()
 
 
+# ---------------------------------------------------------------- conv3x3 (gemm.hip, CONV = true)
+def conv3x3_case(x, w, bias, H, W, mode, res=None, gate=None):
+    """x [Hs*Ws + 1, C] NHWC map with its zero row, w [O, 9C] with K ordered (dy, dx, c), bias [O], res [H*W, O], gate [O] (bf16
+    values); (H, W) is the OUTPUT map.  mode 0: same size; 1: nearest 2x upsampling first; 2: pad (0, 1, 0, 1) + stride 2.
+    The convolution is the GEMM's arithmetic with another A loader, so the case is gemm_case over the fp64 im2col matrix -
+    built here with F.unfold on the fp64 NCHW map, by no kernel of the project - with K = 9C and epi 0 (bias) or 2 (res + gate * .);
+    no constant of its own.  That the matrix spells the convolution is asserted on the spot: ref64 equals F.conv2d's fp64 value
+    (weight reordered to [O, C, 3, 3] by a view and a permute) to 1e-12 of the magnitudes summed."""
+    import torch.nn.functional as F
+    C, O = x.shape[1], w.shape[0]
+    hs, ws = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W) if mode == 2 else (H, W)
+    assert x.shape[0] == hs * ws + 1 and w.shape[1] == 9 * C and not bool(x[-1].to(torch.float64).abs().any())
+    img = x[:-1].to(torch.float64).reshape(hs, ws, C).permute(2, 0, 1)[None]
+    if mode == 1:
+        img = F.interpolate(img, scale_factor=2, mode="nearest")
+    if mode == 2:
+        img, stride, pad = F.pad(img, (0, 1, 0, 1)), 2, 0
+    else:
+        stride, pad = 1, 1
+    col = F.unfold(img, kernel_size=3, padding=pad, stride=stride)[0]                      # [(c, tap), H*W]
+    col = col.reshape(C, 9, H * W).permute(2, 1, 0).reshape(H * W, 9 * C)                    # -> [pixel, (tap, c)]
+    ref, mags, f32 = gemm_case(col, w, bias, 0 if res is None else 2, res, gate)
+    w4 = w.to(torch.float64).reshape(O, 3, 3, C).permute(0, 3, 1, 2)
+    conv = F.conv2d(img, w4, None if bias is None else bias.to(torch.float64), stride=stride, padding=pad)
+    assert conv.shape == (1, O, H, W), conv.shape
+    conv = conv[0].permute(1, 2, 0).reshape(H * W, O)
+    mass = col.abs() @ w.to(torch.float64).abs().t() + (0.0 if bias is None else bias.to(torch.float64).abs().reshape(1, -1))
+    if res is not None:
+        g64 = gate.to(torch.float64).reshape(1, -1)
+        conv, mass = res.to(torch.float64) + g64 * conv, res.to(torch.float64).abs() + g64.abs() * mass
+    assert bool(((ref - conv).abs() <= 1e-12 * mass).all()), "im2col + GEMM and F.conv2d disagree in fp64"
+    return ref, mags, f32
+
+
+# ---------------------------------------------------------------- unfused attention (vae.py _attn, text.py _heads_attention)
+def unfused_attention_case(q, k, v, scale, bias=None, causal=False, pad_to=None):
+    """One head of the chain S GEMM -> softmax_rows -> transpose -> P.V GEMM: q, k, v [L, dh] (the bf16 values the GEMMs read),
+    bias [L, L] (bf16 values) or None, causal: row i sees the keys j <= i; pad_to: K of the P.V product where the plan pads it
+    with zero columns (default L).  The chain stores every intermediate as bf16:
+      s = bf16(q.k) over K = dh;  v_ = bf16(scale * s) (no rounding at scale == 1: softmax_logits), then bf16(v_ + bias);
+      P = bf16(softmax(v_));  O = bf16(sum_j P_j V_j)
+    fp64: softmax(scale * q.k + bias) over the visible keys, times V, no rounding inside.  Budget, derived as attention_case's:
+      logit      E_ij = scale * (HALF * ulp(|s_ij| + f32_ij) + f32_ij)    the S GEMM, f32_ij = (dh + 1) * EPS_MFMA * sum|q k|, and its store
+                      + HALF * ulp(scale * |s_ij|)                        the scaled logit's store (absent at scale == 1)
+                      + HALF * ulp(|scale * s_ij + b_ij|)                 the biased logit's store (with a bias)
+                 each ulp taken at the magnitude plus what the roundings before it can have moved it by;
+                 a softmax whose logits move by at most E moves by  dP_ij <= P_ij * expm1(E_ij + sum_k P_ik E_ik)  (the first order
+                 P_ij * (e_ij - sum_k P_ik e_ik), with expm1 because E reaches ~2e-2 at |s| ~ 100: a bf16 logit of 100 has ulp 0.5)
+      softmax    cols * 2^-24 * P_ij, as softmax_case (cols = L: the f32 sum of the row's exponentials)
+      P's store  HALF * ulp(P_ij): P is stored normalised, so its binade is known (unlike attention_case's deferred one)
+      output     sum_j (dP_ij + softmax_ij + HALF * ulp(P_ij)) |V_jd| + (K + 1) * EPS_MFMA * sum_j P_ij |V_jd| (K = pad_to), then STORE"""
+    q64, k64, v64 = q.to(torch.float64), k.to(torch.float64), v.to(torch.float64)
+    L, dh = q64.shape
+    Kp = L if pad_to is None else pad_to
+    s = q64 @ k64.t()
+    f32s = (dh + 1) * EPS_MFMA * (q64.abs() @ k64.abs().t())
+    s_mag = s.abs() + f32s
+    E = abs(scale) * (HALF * ulp_bf16(s_mag) + f32s)
+    z_mag = abs(scale) * (s_mag + HALF * ulp_bf16(s_mag))
+    z = scale * s
+    if scale != 1.0:
+        E = E + HALF * ulp_bf16(z_mag)
+        z_mag = z_mag + HALF * ulp_bf16(z_mag)
+    if bias is not None:
+        b64 = bias.to(torch.float64)
+        z = z + b64
+        E = E + HALF * ulp_bf16(z.abs() + E)
+    if causal:
+        hidden = torch.arange(L).reshape(1, L) > torch.arange(L).reshape(L, 1)
+        z = z.masked_fill(hidden, -math.inf)
+        E = E.masked_fill(hidden, 0.0)
+    P = torch.softmax(z, dim=-1)
+    dP = P * torch.expm1(E + (P * E).sum(-1, keepdim=True)) + L * EPS24 * P
+    dP = dP + HALF * ulp_bf16(P + dP)
+    va = v64.abs()
+    return P @ v64, [STORE], dP @ va + (Kp + 1) * EPS_MFMA * ((P + dP) @ va)
+
+
+def unfused_attention_inputs(L, dh, seed=0):
+    """(q, k, v [L, dh], bias [L, L], other head's bias [L, L]) bf16 on the CPU.  q = 4 * randn (the logits q.k reach ~ +-100 at
+    dh = 64), every third row 1/32 of that (a flat softmax row beside the peaked ones); keys 0 and 1 are the same vector and the
+    queries 0 and 1 are 2x and 1/2 of it: two rows on which two keys tie, at the row's largest logit.  Every key holds half of a
+    common +-1 vector u and query 2 is -u: a row whose logits are all ~ -dh^0.5 / 2 after the dh^-0.5 scale, on which a pad column of
+    logit 0 that took part in the softmax outweighs the real keys (on a flat row of 256 keys it weighs 1/257, about the rounding)."""
+    g = torch.Generator().manual_seed(4099 * L + dh + seed)
+    q, k, v = 4.0 * torch.randn(L, dh, generator=g), torch.randn(L, dh, generator=g), torch.randn(L, dh, generator=g)
+    q[1::3] *= 1.0 / 32.0
+    u = torch.where(torch.rand(dh, generator=g) < 0.5, -1.0, 1.0)
+    k = k + 0.5 * u
+    if L > 2:
+        k[1] = k[0]
+        q[0], q[1], q[2] = 2.0 * k[0], 0.5 * k[0], -u
+    bias, other = 2.0 * torch.randn(L, L, generator=g), 2.0 * torch.randn(L, L, generator=g)
+    return tuple(t.to(torch.bfloat16) for t in (q, k, v, bias, other))
+
+
 # ---------------------------------------------------------------- ln_modulate (norm.hip)
 def ln_modulate_case(x, shift, scale, eps=1e-6):
     """x [rows, D]; shift, scale [D] or [rows, D] (the row's modulation).  y = bf16(bf16(1 + scale) * LN(x) + shift) (norm.hip

@@ -26,6 +26,26 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm()).item()
 
 
+# sentinel-filled output buffers of the kernel tests: everything a kernel must not write is checked to be untouched
+def sentinel(shape, value=7.0):
+    return torch.full(shape, value, dtype=torch.bfloat16, device="cuda:0")
+
+
+def untouched(buf, value=7.0):
+    """every element still holds the sentinel's bit pattern"""
+    from tests.budget import bits_equal
+    return bits_equal(buf, torch.full(buf.shape, value, dtype=torch.bfloat16))
+
+
+def patterned(shape):
+    """bf16 tensor whose element i holds bit pattern i + 1: every value distinct, none a NaN (numel < 0x7F80)"""
+    n = 1
+    for s in shape:
+        n *= s
+    assert n < 0x7F80
+    return (torch.arange(n, dtype=torch.int32) + 1).to(torch.int16).view(torch.bfloat16).reshape(shape)
+
+
 def smoke() -> None:
     from visualcloze_amd import hip
     hip.require_gpu()

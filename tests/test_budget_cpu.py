@@ -450,3 +450,94 @@ def test_one_hot_inputs_hold_their_precondition():
         v = vf(0)
         for qmode in ("stored", "scale"):
             assert B.bits_equal(attn_emulate(q, k, v, live, qmode)[live], v[partner][live])
+
+
+# ---------------------------------------------------------------- conv3x3_case
+@pytest.mark.parametrize("mode,H,W", [(0, 1, 1), (0, 5, 7), (1, 2, 2), (1, 6, 10), (2, 1, 1), (2, 3, 5)])
+@pytest.mark.parametrize("with_res", [False, True])
+def test_conv3x3_case_is_the_convolution(mode, H, W, with_res):
+    """budget.conv3x3_case: its im2col matrix (F.unfold, fp64) times the weight IS F.conv2d's fp64 value (asserted inside the
+    builder), torch's own f32 convolution rounded to bf16 meets the budget, and the convolution with dy and dx
+    swapped does not."""
+    C, O = 64, 24
+    hs, ws = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W) if mode == 2 else (H, W)
+    g = torch.Generator().manual_seed(100 * mode + 10 * H + W)
+    x = torch.zeros(hs * ws + 1, C, dtype=torch.bfloat16)
+    x[:-1] = torch.randn(hs * ws, C, generator=g).to(torch.bfloat16)
+    w, bias = (torch.randn(O, 9 * C, generator=g) * (9 * C) ** -0.5).to(torch.bfloat16), torch.randn(O, generator=g).to(torch.bfloat16)
+    res = torch.randn(H * W, O, generator=g).to(torch.bfloat16) if with_res else None
+    gate = torch.randn(O, generator=g).to(torch.bfloat16) if with_res else None
+    ref, mags, f32 = B.conv3x3_case(x, w, bias, H, W, mode, res, gate)
+
+    def torch_conv(wt):
+        img = x[:-1].float().reshape(hs, ws, C).permute(2, 0, 1)[None]
+        if mode == 1:
+            img = F.interpolate(img, scale_factor=2, mode="nearest")
+        if mode == 2:
+            img = F.pad(img, (0, 1, 0, 1))
+        y = F.conv2d(img, wt.float().reshape(O, 3, 3, C).permute(0, 3, 1, 2), bias.float(), stride=2 if mode == 2 else 1,
+                     padding=0 if mode == 2 else 1)[0].permute(1, 2, 0).reshape(H * W, O)
+        return gemm_epilogue(y, 2 if with_res else 0, res, gate)
+    B.assert_within_budget(torch_conv(w), ref, len(mags), mags, f32, what=f"conv2d mode={mode} {H}x{W}")
+    swapped = w.reshape(O, 3, 3, C).transpose(1, 2).reshape(O, 9 * C)
+    if (mode, H, W) != (0, 1, 1):                                    # a 1x1 map sees the centre tap alone
+        with pytest.raises(AssertionError, match="over budget"):
+            B.assert_within_budget(torch_conv(swapped), ref, len(mags), mags, f32)
+
+
+# ---------------------------------------------------------------- unfused_attention_case
+def chain_emulate(q, k, v, scale, bias=None, causal=False, drop_last=False, extra_zero=False, swap=None):
+    """The unfused chain in torch: f32 matmul of the bf16 values, every store rounded with .to(bfloat16) - s = bf16(q k^T),
+    v_ = bf16(scale * s) [+ bias, rounded again] (budget.softmax_logits: the kernel's own sequence), P = bf16(softmax(v_)),
+    O = bf16(P V).  Faults: drop_last (the last key takes no part), extra_zero (one more key with logit 0 and a zero V row: a
+    pad column that took part in the softmax), swap = j (V rows j and j + 1 exchanged)."""
+    L = q.shape[0]
+    s = (q.float() @ k.float().t()).to(torch.bfloat16)
+    z = B.softmax_logits(s, scale, bias).float()
+    if causal:
+        z = z.masked_fill(torch.arange(L).reshape(1, L) > torch.arange(L).reshape(L, 1), -math.inf)
+    if drop_last:
+        z[:, -1] = -math.inf
+    if extra_zero:
+        z = torch.cat([z, torch.zeros(L, 1)], dim=1)
+    P = torch.softmax(z, dim=-1).to(torch.bfloat16)[:, :L]
+    vv = v.float().clone()
+    if swap is not None:
+        vv[[swap, swap + 1]] = vv[[swap + 1, swap]]
+    return (P.float() @ vv).to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("L,dh", [(35, 64), (77, 64), (256, 128)])
+def test_unfused_attention_emulation_meets_budget(L, dh, with_bias, causal):
+    """The torch emulation of the chain meets budget.unfused_attention_case at scale = dh^-0.5 (VAE, CLIP) and at scale = 1
+    (T5: no rounding of the scaled logit, logits of ~ +-100 with a bf16 ulp of 0.5).  Measured here: worst/budget 0.63 over
+    all 24 cases (0.25 .. 0.63)."""
+    q, k, v, bias, _ = B.unfused_attention_inputs(L, dh)
+    for scale in (dh ** -0.5, 1.0):
+        b = bias if with_bias else None
+        ref, mags, f32 = B.unfused_attention_case(q, k, v, scale, b, causal)
+        got = chain_emulate(q, k, v, scale, b, causal)
+        what = f"chain L={L} dh={dh} scale={scale:.4f} bias={with_bias} causal={causal}"
+        print(what, "worst/budget", B.worst_ratio(got, ref, 1, mags, f32))
+        B.assert_within_budget(got, ref, 1, mags, f32, what=what)
+
+
+@pytest.mark.parametrize("L,dh", [(35, 64), (77, 64), (256, 128)])
+def test_unfused_attention_budget_rejects_four_faults(L, dh):
+    """The last key dropped; one extra key with logit 0 (a pad column that took part); V rows j and j + 1 swapped for one j; the
+    bias of the next head used for this one: each is outside the budget, at every shape, and the sound emulation inside it."""
+    q, k, v, bias, other = B.unfused_attention_inputs(L, dh)
+    scale = dh ** -0.5
+    ref, mags, f32 = B.unfused_attention_case(q, k, v, scale, bias)
+    B.assert_within_budget(chain_emulate(q, k, v, scale, bias), ref, 1, mags, f32)
+    for fault in ({"drop_last": True}, {"extra_zero": True}, {"swap": L // 2}):
+        with pytest.raises(AssertionError, match="over budget"):
+            B.assert_within_budget(chain_emulate(q, k, v, scale, bias, **fault), ref, 1, mags, f32, what=str(fault))
+    with pytest.raises(AssertionError, match="over budget"):
+        B.assert_within_budget(chain_emulate(q, k, v, scale, other), ref, 1, mags, f32, what="bias of the next head")
+    ref, mags, f32 = B.unfused_attention_case(q, k, v, scale)                            # and without a bias
+    for fault in ({"drop_last": True}, {"extra_zero": True}, {"swap": L // 2}):
+        with pytest.raises(AssertionError, match="over budget"):
+            B.assert_within_budget(chain_emulate(q, k, v, scale, **fault), ref, 1, mags, f32, what=str(fault))

@@ -8,6 +8,7 @@ import torch
 
 from oracle import flux_oracle as FO
 from tests import budget as B
+from tests.helpers import patterned, sentinel, untouched
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -19,24 +20,6 @@ def hip():
     from visualcloze_amd import hip as h
     h.require_gpu()
     return h
-
-
-def sentinel(shape, value=7.0):
-    return torch.full(shape, value, dtype=BF, device=DEV)
-
-
-def untouched(buf, value=7.0):
-    """every element still holds the sentinel's bit pattern"""
-    return B.bits_equal(buf, torch.full(buf.shape, value, dtype=BF))
-
-
-def patterned(shape):
-    """bf16 tensor whose element i holds bit pattern i + 1: every value distinct, none a NaN (numel < 0x7F80)"""
-    n = 1
-    for s in shape:
-        n *= s
-    assert n < 0x7F80
-    return (torch.arange(n, dtype=torch.int32) + 1).to(torch.int16).view(BF).reshape(shape)
 
 
 # ---------------------------------------------------------------- GroupNorm

@@ -31,6 +31,27 @@ def bf(t):
     return t.to(torch.bfloat16).to(DEV)
 
 
+# Per-pixel view beside the rel_l2 lines: on the border ring and on the interior, the largest per-pixel error (largest channel
+# of the pixel) of the HIP result against the fp32 oracle is at most PIXEL_M times that of the oracle's OWN bf16 run on the same
+# region.  One wrong border pixel is O(1) against a yardstick of O(1e-2) and 1/4096 of a 64x64 output's energy, which rel_l2
+# does not see.  PIXEL_M = twice the largest ratio measured on the MI355X over the three tests that use it (see their
+# docstrings), rounded up to one significant digit: 2 * 1.232 = 2.46 -> 3.
+PIXEL_M = 3.0
+
+
+def assert_pixels_within_bf16_noise(out, o16, o32, ring, what):
+    out, o16, o32 = (t.double().cpu().reshape(-1, *t.shape[-2:]) for t in (out, o16, o32))
+    e_hip, e_16 = (out - o32).abs().amax(0), (o16 - o32).abs().amax(0)
+    H, W = e_hip.shape
+    assert 2 * ring < H and 2 * ring < W
+    inner = torch.zeros(H, W, dtype=torch.bool)
+    inner[ring:H - ring, ring:W - ring] = True
+    for name, mask in (("ring", ~inner), ("interior", inner)):
+        hip_err, yard = float(e_hip[mask].max()), float(e_16[mask].max())
+        print(f"{what} {name}: hip {hip_err:.4e} bf16 oracle {yard:.4e} ratio {hip_err / yard:.3f}")
+        assert hip_err <= PIXEL_M * yard, (what, name, hip_err, yard)
+
+
 @pytest.mark.parametrize("H,W,C", [(4, 4, 64), (3, 5, 128), (1, 1, 8)])
 def test_im2col3x3_stride2_is_exact(hip, H, W, C):
     """Downsample: pad (0,1,0,1) then 3x3 stride 2 (autoencoder.py:91-95)."""
@@ -122,7 +143,8 @@ def test_tiny_decode_matches_reference_golden_and_oracle(hip, name):
 
 
 def test_flux_width_decoder_matches_oracle(hip):
-    """Full FLUX AutoEncoder geometry (ch 128, mult 1-2-4-4, 2 res blocks, z 16) on an 8x8 latent -> 64x64 image."""
+    """Full FLUX AutoEncoder geometry (ch 128, mult 1-2-4-4, 2 res blocks, z 16) on an 8x8 latent -> 64x64 image.
+    Per-pixel ratios measured on the MI355X (HIP / bf16 oracle, both against fp32): ring 1.019, interior 1.089."""
     from visualcloze_amd.vae import FLUX_AE, AutoEncoder, AutoEncoderParams
     ae = AutoEncoder(AutoEncoderParams(**FLUX_AE))
     sd = {k: procedural_ae_param(k, v.shape) for k, v in ae.state_dict().items()}
@@ -135,6 +157,7 @@ def test_flux_width_decoder_matches_oracle(hip):
     o16 = VO.decode(sd, z, FLUX_AE, "bf16")
     noise = rel_l2(o16, o32)
     assert rel_l2(out, o32) <= 3.0 * noise + 2e-3, (rel_l2(out, o32), noise)
+    assert_pixels_within_bf16_noise(out, o16, o32, 16, "flux-width decode")          # 16 pixels = two latent pixels
     out2 = ae.decode(z.to(DEV).to(torch.bfloat16)).float().cpu()
     assert torch.equal(out, out2)
 
@@ -172,6 +195,7 @@ def test_gaussian_sample_kernel_rounding(hip):
 
 
 def test_flux_width_encoder_matches_oracle(hip):
+    """Per-pixel ratios measured on the MI355X (HIP / bf16 oracle, both against fp32): ring 0.805, interior 1.232."""
     from visualcloze_amd.vae import FLUX_AE, AutoEncoder, AutoEncoderParams
     ae = AutoEncoder(AutoEncoderParams(**FLUX_AE))
     sd = {k: procedural_ae_param(k, v.shape) for k, v in ae.state_dict().items()}
@@ -185,10 +209,12 @@ def test_flux_width_encoder_matches_oracle(hip):
     noise = rel_l2(o16, o32)
     assert mom.shape == (1, 32, 8, 8)
     assert rel_l2(mom, o32) <= 3.0 * noise + 2e-3, (rel_l2(mom, o32), noise)
+    assert_pixels_within_bf16_noise(mom, o16, o32, 2, "flux-width encode")
 
 
 def test_decoder_attention_with_odd_token_count(hip):
-    """h*w not a multiple of 8 (a 400x400-pixel image has a 50x50 latent): padded key rows / score columns stay zero."""
+    """h*w not a multiple of 8 (a 400x400-pixel image has a 50x50 latent): padded key rows / score columns stay zero.
+    Per-pixel ratios measured on the MI355X (HIP / bf16 oracle, both against fp32): ring 0.713, interior 1.140."""
     ae, sd = tiny_model()
     z = ptensor((1, TINY_AE["z_channels"], 5, 7), 51, q=5, kmax=96)
     out = ae.decode(z.to(DEV).to(torch.bfloat16)).float().cpu()
@@ -197,6 +223,7 @@ def test_decoder_attention_with_odd_token_count(hip):
     noise = rel_l2(o16, o32)
     assert out.shape == o32.shape
     assert rel_l2(out, o32) <= 3.0 * noise + 2e-3, (rel_l2(out, o32), noise)
+    assert_pixels_within_bf16_noise(out, o16, o32, 2 * (out.shape[-1] // 7), "tiny decode 5x7")   # two latent pixels
 
 
 @pytest.mark.parametrize("H,W,C,O,mode", [(4, 4, 64, 64, 0), (9, 13, 128, 200, 0), (8, 12, 64, 72, 1), (3, 5, 64, 8, 2),

@@ -847,6 +847,8 @@ def conv3x3(x, w, bias, out, H, W, up=False, down=False, res=None, gate=None, st
             or tuple(out.shape) != (H * W, O) or out.stride(1) != 1:
         raise VclozeHipError("conv3x3: x [Hs*Ws + 1, C] (last row zero), w [O, 9C], out [H*W, O] expected")
     if res is not None:
+        if gate is None:
+            raise VclozeHipError("conv3x3: res needs a gate")
         _bf16(res, "res"); _bf16(gate, "gate")
     _check(lib().vc_conv3x3(x.data_ptr(), w.data_ptr(), _p(bias), out.data_ptr(), out.stride(0), _p(res),
                             res.stride(0) if res is not None else 0, _p(gate), H, W, Cc, O, 1 if up else 2 if down else 0,

@@ -135,15 +135,19 @@ class _Exec:
         """softmax(scale * q_h k_h^T (+ bias_h, causal)) v_h for every head; q, k, v, result are [L, H*dh].  The H per-head
         products are ONE batched launch each (VcGemmArgs.batch = H: head h reads its dh columns of q / k, writes its [L, L]
         slab of S; then S_h . V_h^T into its dh columns of O) - two GEMM launches per layer instead of 2 * H / 4 grouped ones
-        (T5-XXL: 768 -> 48 per prompt)."""
+        (T5-XXL: 768 -> 48 per prompt).  L is a multiple of 8 (N of the S product); the K of the P.V product is L rounded up to
+        64, as in the VAE's attention: at L % 64 == 0, which the two encoders keep to, the launches are the same as without it."""
         dev = q.device
-        s = self._scratch(dev, "S" + tag, (H * L, L))
-        p = hip.make_problem(q[:, :dh], k[:, :dh], None, s[:L])
+        Lp = (L + 63) // 64 * 64                             # K of the P.V product: the pad columns of S and V^T stay zero
+        s = self._scratch(dev, "S" + tag, (H * L, Lp))
+        vt = self._scratch(dev, "VT" + tag, (H * dh, Lp))
+        if Lp != L:
+            s.zero_(); vt.zero_()
+        p = hip.make_problem(q[:, :dh], k[:, :dh], None, s[:L, :L])
         p.a_zstride, p.w_zstride, p.c_zstride = dh, dh, L * s.stride(0)
         hip.gemm(p, epi=hip.EPI_BIAS, batch=H)
-        hip.softmax_rows(s, scale, bias=bias, causal_period=causal_period)
-        vt = self._scratch(dev, "VT" + tag, (H * dh, L))
-        hip.transpose(v, vt)
+        hip.softmax_rows(s[:, :L], scale, bias=bias, causal_period=causal_period)
+        hip.transpose(v, vt[:, :L])
         o = self._scratch(dev, "O" + tag, (L, H * dh))
         p = hip.make_problem(s[:L], vt[:dh], None, o[:, :dh])
         p.a_zstride, p.w_zstride, p.c_zstride = L * s.stride(0), dh * vt.stride(0), dh
