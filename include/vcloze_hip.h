@@ -798,6 +798,126 @@ int vc_text_encode(void* handle, const int32_t* ids, int32_t n_prompts, void* hi
 /* captured plans the handle holds (0..8); -1 for a null handle */
 int vc_text_plan_count(void* handle);
 
+/* ---- the grid: the host rules, the pixel epilogue and the handle that turn the pieces above into images ----
+ * Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up vc_grid_create.
+ *
+ * HOST RULES (no device, like vc_solver_evals).
+ * vc_time_grid: the solver's n_points time points, F32, bit for bit what the pipeline's sampler builds (ode.__init__ + ode.sample,
+ *   transport/integrators.py:99-101,113-116; time_shift of transport/utils.py:33-39), every step rounded as torch rounds it:
+ *     1. torch.linspace(t0, t1, n_points) in f32: step = (f32(t1) - f32(t0)) / (n_points - 1); point i < n_points / 2 is
+ *        fma(step, i, f32(t0)), every other point fma(-step, n_points - 1 - i, f32(t1)) - the two-sided formula, each point ONE
+ *        fused multiply-add, as torch's kernel evaluates it;
+ *     2. time_shifting_factor f != 0:  t <- t / ((t + f32(f)) - f32(f) * t), four f32 operations;
+ *     3. do_shift != 0:  mu = m * n_tokens + b in double with m = (1.15 - 0.5) / (4096 - 256), b = 0.5 - m * 256 (get_lin_function),
+ *        E = f32(exp(mu)), and per point u = 1 - t; r = (1 / u) - 1; t <- 1 - (1 / (E + r)) * E, all f32 - torch divides a number by
+ *        a tensor as reciprocal times number.  The endpoints pass through inf arithmetic to exactly 0 and 1.
+ *   Apart from the fused multiply-adds of step 1 nothing is contracted.  n_points < 2, n_tokens < 1, t0 >= t1, a non-finite
+ *   t0 / t1 / time_shifting_factor or a null `out` is VC_ERR_ARG.
+ * vc_grid_tokens: the image tokens of a sample of `rows` grid rows with LATENT sizes lat_h[i] x lat_w[i] (even, positive):
+ *   sum (lat_h[i] / 2) * (lat_w[i] / 2); VC_ERR_ARG (negative) for rows < 1, a null pointer or an odd / non-positive size.
+ * vc_grid_img_ids: out HOST [vc_grid_tokens][3] F32 = the img_ids of prepare_modified (models/sampling.py:56-59) for that sample:
+ *   per row j, in token order (y outer, x inner): (j + 1, y, x).  What VcFluxInputs.img_ids takes for B = 1. */
+int vc_time_grid(int32_t n_points, int32_t n_tokens, double t0, double t1, int32_t do_shift, double time_shifting_factor, float* out);
+int64_t vc_grid_tokens(int32_t rows, const int32_t* lat_h, const int32_t* lat_w);
+int vc_grid_img_ids(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, float* out);
+
+/* PIXELS OUT: the last step of both stages (visualcloze.py:238-240,430-432 and to_pil_image of :437-439) in one launch.
+ * img [3, H, W] bf16 (or F32 with img_is_f32) is the VAE's decoded image in [-1, 1]; the column window [x0, x0 + w) of it - the crop
+ * of cell i of a row of grid_w cells is x0 = i * W / grid_w (:452,461) - leaves as
+ *   VC_PIXELS_F32: out F32 [3, H, w],  v = clamp((f32(img) + 1) / 2, 0, 1)         ((img.float() + 1.0) / 2.0).clamp_(0.0, 1.0)
+ *   VC_PIXELS_U8:  out 8-bit [H, w, 3], (uint8)(v * 255), TRUNCATING               (pic.mul(255).byte() of torchvision's to_pil_image)
+ * bit for bit the torch expressions (the sum and the product are rounded separately, nothing is contracted; a NaN stays a NaN in the
+ * F32 form).  16-byte accesses when x0, w and W are multiples of 16 and both bases are 16-byte aligned; anything else runs
+ * element-wise with the same results.  0 < H, W < 65536, 0 <= x0, 1 <= w, x0 + w <= W; out must not overlap img; violations and null
+ * pointers are VC_ERR_ARG, checked before the device is touched. */
+#define VC_PIXELS_F32 0
+#define VC_PIXELS_U8 1
+int vc_pixels_out(const void* img, int32_t img_is_f32, int32_t H, int32_t W, int32_t x0, int32_t w, void* out, int32_t out_form,
+                  void* stream);
+
+/* THE HANDLE: VisualClozeModel.process_images' tensor path (visualcloze.py:363-434) and `upsampling`'s (:184-240) as ONE call each,
+ * composed of the entry points above in the order visualcloze_amd/pipeline.py composes them (generate_grid with
+ * rng = NoiseStream(seed); upsample_images): the same kernels on the same operands, so the same bits.  The handle BORROWS its four
+ * sub-handles (it never destroys them; they must outlive it, with their weights bound): whatever is set on the Flux handle - LoRA
+ * mode and scale, taps, the step cache, true CFG (leave it off: the grid runs B = 1) - acts as it does in vc_flux_sample_ode.  It
+ * prepares the sub-handles inside ITS workspace on every call: a caller who also drives a sub-handle directly prepares that one again
+ * afterwards.  Image loading, resizing (the bicubic Image.resize between the stages, :179), prefix stripping and tokenisation stay
+ * host work.  Needs an autoencoder of 8x reduction (n_ch_mult 4) with 4 * z_channels == the Flux out_channels and
+ * in_channels - out_channels == 4 * z_channels + 256, a T5 of d_model == context_in_dim and a CLIP of d_model == vec_in_dim
+ * (VC_ERR_ARG from vc_grid_create otherwise).  One handle per device; not thread-safe; one stream at a time. */
+#define VC_GRID_MAX_ROWS 16
+#define VC_GRID_SDEDIT_CHUNK 4   /* samples per solve of vc_grid_sdedit: the per-GPU batch limit the pipeline runs the Flux handle with */
+typedef struct VcGridConfig {
+  void* flux;   /* vc_flux_create */
+  void* vae;    /* vc_vae_create */
+  void* t5;     /* vc_text_create, VC_TEXT_T5 */
+  void* clip;   /* vc_text_create, VC_TEXT_CLIP */
+} VcGridConfig;
+typedef struct VcGridJob {
+  int32_t rows;                              /* 1..VC_GRID_MAX_ROWS grid rows */
+  int32_t pixels_is_f32;                     /* the row pixels are F32 instead of bf16 */
+  int32_t height[VC_GRID_MAX_ROWS];          /* per row, pixels: multiples of 16 */
+  int32_t width[VC_GRID_MAX_ROWS];
+  const void* pixels[VC_GRID_MAX_ROWS];      /* per row, device [3, H, W] in [-1, 1]: the images of the row side by side */
+  const void* masks[VC_GRID_MAX_ROWS];       /* per row, device bf16 [H, W]: the pixel fill mask, 1 = generate */
+  int32_t decode[VC_GRID_MAX_ROWS];          /* != 0: this row is decoded into out_rows[row] */
+  const int32_t* t5_ids;                     /* HOST [t5_len]; t5_len a multiple of 64 (the pipeline pads to 512) */
+  const int32_t* clip_ids;                   /* HOST [clip_len] */
+  int32_t t5_len, clip_len;
+  uint64_t seed, noise_offset;               /* the library's noise stream (vc_randn): every draw of the job, in the reference's order -
+                                                per row the DiagonalGaussian draw of its encode (z_channels * H/8 * W/8 elements,
+                                                autoencoder.py:272), then per row the start noise (:394-399), each a contiguous stretch */
+  uint64_t* noise_offset_out;                /* HOST or NULL: receives the stream position behind the last draw */
+  float guidance;                            /* rounded to bf16 as visualcloze.py:413 holds it */
+  int32_t n_points;                          /* the pipeline's "steps": time POINTS of the solver, >= 2 */
+  int32_t method;                            /* VC_SOLVER_* */
+  int32_t out_form;                          /* VC_PIXELS_F32 or VC_PIXELS_U8 */
+  int32_t max_evals;                         /* model evaluations the workspace is sized for; 0 = what this job needs,
+                                                (n_points - 1) * vc_solver_evals(method) */
+  int32_t _pad;
+  double time_shifting_factor;               /* 0 = none; the pipeline's default is 1 */
+} VcGridJob;
+typedef struct VcGridSdedit {                /* `upsampling` for `count` targets of ONE size and prompt, refined together */
+  int32_t count;                             /* 1..VC_GRID_MAX_ROWS targets */
+  int32_t pixels_is_f32;
+  int32_t height, width;                     /* multiples of 16: the FINAL size - the images arrive resized */
+  const void* pixels[VC_GRID_MAX_ROWS];      /* per target, device [3, H, W] in [-1, 1] */
+  const int32_t* t5_ids;                     /* HOST: the content prompt */
+  const int32_t* clip_ids;
+  int32_t t5_len, clip_len;
+  uint64_t seed, noise_offset;               /* per target: the draw of encode(image), of encode(blank), the start noise (:200-217) */
+  uint64_t* noise_offset_out;
+  float guidance;
+  int32_t n_points, method, out_form, max_evals;
+  int32_t _pad;
+  double strength;                           /* (0, 1): the un-shifted grid runs from t0 = strength; >= 1 returns the input converted */
+} VcGridSdedit;
+/* sizeof(VcGridConfig), sizeof(VcGridJob), sizeof(VcGridSdedit) as this library was compiled */
+void vc_grid_struct_sizes(int32_t out[3]);
+/* host-only */
+int vc_grid_create(const VcGridConfig* cfg, void** handle);
+int vc_grid_destroy(void* handle);
+/* The bytes vc_grid_generate (vc_grid_sdedit) needs for this job: the sub-handles' own *_workspace_bytes (the autoencoder at the
+ * job's largest row, both halves; T5 and CLIP at the ids' lengths; Flux at B = 1 - the sdedit job: min(count, VC_GRID_SDEDIT_CHUNK) -
+ * and max_evals) plus the intermediates (cond, the state, the prompt embeddings, staged pixels).  Host-only; the job is checked as
+ * the run checks it. */
+int vc_grid_workspace_bytes(void* handle, const VcGridJob* job, int64_t* bytes);
+int vc_grid_sdedit_workspace_bytes(void* handle, const VcGridSdedit* job, int64_t* bytes);
+/* out_rows HOST [rows] of device pointers: out_rows[i] receives row i ([3, H, W] F32 or [H, W, 3] 8-bit) where decode[i] != 0; the
+ * other entries are not read.  workspace: device memory, 256-B aligned, >= vc_grid_workspace_bytes, the caller's during the call -
+ * and, kept between calls, what lets the sub-handles' captured plans serve again: a second job of the same geometry in the same
+ * workspace captures nothing (each row's encode and each decoded row's decode is one plan of the autoencoder's list of 8).
+ * Every argument error - a null handle or pointer, rows or count outside 1..VC_GRID_MAX_ROWS, a size that is no multiple of 16,
+ * n_points < 2, an unknown method or out_form, (n_points - 1) * vc_solver_evals(method) > max_evals, a workspace that is too small
+ * or misaligned, ids' lengths the encoders refuse, a draw that leaves the 64-bit stream - is VC_ERR_ARG with a message, found
+ * before the device is touched. */
+int vc_grid_generate(void* handle, const VcGridJob* job, void* workspace, int64_t workspace_bytes, void* const* out_rows, void* stream);
+/* out_images HOST [count] of device pointers, each [3, H, W] F32 or [H, W, 3] 8-bit.  Per target, in the reference's order:
+ * encode(image), encode(blank) - a zero image - and the start noise; vc_sdedit_mix; cond = the blank latent and an all-ones mask;
+ * the grid vc_time_grid(n_points, tokens, strength, 1, 0, 1.0); one batched solve per VC_GRID_SDEDIT_CHUNK targets; decode;
+ * vc_pixels_out.  strength >= 1: the input pixels converted, nothing drawn (visualcloze.py:180-181). */
+int vc_grid_sdedit(void* handle, const VcGridSdedit* job, void* workspace, int64_t workspace_bytes, void* const* out_images, void* stream);
+
 /* ---- hipGraph helpers: capture the launches issued on `stream` between begin/end ---- */
 int vc_stream_create(void** stream);
 int vc_stream_destroy(void* stream);

@@ -304,6 +304,34 @@ int vc_text_encode(void* handle, const int32_t* ids, int32_t n_prompts, void* hi
 }
 int vc_text_plan_count(void* handle) { return vc_text_plan_count_impl(handle); }
 
+/* ---- the grid: host rules (grid_rules.hip), pixel epilogue (pixels_out.hip), handle (grid_engine.hip) ---- */
+int vc_time_grid(int32_t n_points, int32_t n_tokens, double t0, double t1, int32_t do_shift, double time_shifting_factor, float* out) {
+  return vc_time_grid_impl(n_points, n_tokens, t0, t1, do_shift, time_shifting_factor, out, ERRBUF);
+}
+int64_t vc_grid_tokens(int32_t rows, const int32_t* lat_h, const int32_t* lat_w) { return vc_grid_tokens_impl(rows, lat_h, lat_w, ERRBUF); }
+int vc_grid_img_ids(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, float* out) {
+  return vc_grid_img_ids_impl(rows, lat_h, lat_w, out, ERRBUF);
+}
+int vc_pixels_out(const void* img, int32_t img_is_f32, int32_t H, int32_t W, int32_t x0, int32_t w, void* out, int32_t out_form,
+                  void* stream) {
+  return vc_pixels_out_launch(img, img_is_f32, H, W, x0, w, out, out_form, S(stream), ERRBUF);
+}
+void vc_grid_struct_sizes(int32_t out[3]) {
+  out[0] = (int32_t)sizeof(VcGridConfig); out[1] = (int32_t)sizeof(VcGridJob); out[2] = (int32_t)sizeof(VcGridSdedit);
+}
+int vc_grid_create(const VcGridConfig* cfg, void** handle) { return vc_grid_create_impl(cfg, handle, ERRBUF); }
+int vc_grid_destroy(void* handle) { return vc_grid_destroy_impl(handle, ERRBUF); }
+int vc_grid_workspace_bytes(void* handle, const VcGridJob* job, int64_t* bytes) { return vc_grid_workspace_bytes_impl(handle, job, bytes, ERRBUF); }
+int vc_grid_sdedit_workspace_bytes(void* handle, const VcGridSdedit* job, int64_t* bytes) {
+  return vc_grid_sdedit_workspace_bytes_impl(handle, job, bytes, ERRBUF);
+}
+int vc_grid_generate(void* handle, const VcGridJob* job, void* workspace, int64_t workspace_bytes, void* const* out_rows, void* stream) {
+  return vc_grid_generate_impl(handle, job, workspace, workspace_bytes, out_rows, S(stream), ERRBUF);
+}
+int vc_grid_sdedit(void* handle, const VcGridSdedit* job, void* workspace, int64_t workspace_bytes, void* const* out_images, void* stream) {
+  return vc_grid_sdedit_impl(handle, job, workspace, workspace_bytes, out_images, S(stream), ERRBUF);
+}
+
 /* ---- streams / graphs / events ---- */
 int vc_stream_create(void** stream) {
   if (!stream) { snprintf(g_err, sizeof(g_err), "stream_create: null"); return VC_ERR_ARG; }

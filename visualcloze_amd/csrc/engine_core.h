@@ -1,5 +1,5 @@
-// What the handle engines (flux_engine.hip, vae_engine.hip, text_engine.hip) share: error reporting, the workspace carve-up, stream
-// capture and the run of a captured plan.  Host code only, for those three files alone (each gets its own internal copy): no
+// What the handle engines (flux_engine.hip, vae_engine.hip, text_engine.hip, grid_engine.hip) share: error reporting, the workspace carve-up, stream
+// capture and the run of a captured plan.  Host code only, for those four files alone (each gets its own internal copy): no
 // kernel translation unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1032,6 +1032,8 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
   FAIL(VC_ERR_ARG, "flux_set_option: unknown option '%s'", name);
 }
 
+const VcFluxConfig* vc_flux_config_impl(void* handle) { return handle ? &((Flux*)handle)->cfg : nullptr; }   // grid_engine.hip reads the geometry
+
 int64_t vc_flux_workspace_bytes_impl(void* handle, int32_t B, int32_t T, int32_t N, int32_t max_steps) {
   if (!handle || B <= 0 || T <= 0 || N <= 0 || max_steps <= 0) return -1;
   Buffers tmp;                    // carve into a scratch copy: the pointers of the live handle stay as they are

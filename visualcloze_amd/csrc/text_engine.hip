@@ -371,4 +371,5 @@ int vc_text_encode_impl(void* handle, const int32_t* ids, int32_t n_prompts, voi
   return VC_OK;
 }
 
+const VcTextConfig* vc_text_config_impl(void* handle) { return handle ? &((Text*)handle)->cfg : nullptr; }   // grid_engine.hip reads the geometry
 int vc_text_plan_count_impl(void* handle) { return handle ? (int)((Text*)handle)->plans.size() : -1; }

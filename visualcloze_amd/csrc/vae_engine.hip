@@ -566,4 +566,5 @@ int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, 
   });
 }
 
+const VcVaeConfig* vc_vae_config_impl(void* handle) { return handle ? &((Vae*)handle)->cfg : nullptr; }   // grid_engine.hip reads the geometry
 int vc_vae_plan_count_impl(void* handle) { return handle ? (int)((Vae*)handle)->plans.size() : -1; }

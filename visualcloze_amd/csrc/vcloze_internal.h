@@ -102,8 +102,16 @@ int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const voi
 int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen);
 int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
                            int errlen);
+int vc_pixels_out_launch(const void* img, int img_is_f32, int H, int W, int x0, int w, void* out, int out_form, hipStream_t s, char* err,
+                         int errlen);
+// grid_rules.hip: the host rules of one grid (no device)
+int vc_time_grid_impl(int32_t n_points, int32_t n_tokens, double t0, double t1, int32_t do_shift, double time_shifting_factor, float* out,
+                      char* err, int errlen);
+int64_t vc_grid_tokens_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, char* err, int errlen);
+int vc_grid_img_ids_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, float* out, char* err, int errlen);
 
 // flux_engine.hip: the handle API
+const VcFluxConfig* vc_flux_config_impl(void* handle);
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen);
 int vc_flux_destroy_impl(void* handle, char* err, int errlen);
 int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, const void* bias, int32_t rows, int32_t cols, int64_t ldw,
@@ -143,6 +151,7 @@ int vc_vae_decode_impl(void* handle, const void* latent, int32_t latent_form, in
 int vc_vae_encode_impl(void* handle, const void* pixels, int32_t pixels_is_f32, const void* noise, void* latent, int32_t latent_form, int64_t ld,
                        int32_t col0, hipStream_t s, char* err, int errlen);
 int vc_vae_plan_count_impl(void* handle);
+const VcVaeConfig* vc_vae_config_impl(void* handle);
 
 // text_engine.hip: the text-encoder handle
 int vc_text_create_impl(const VcTextConfig* cfg, void** handle, char* err, int errlen);
@@ -153,3 +162,14 @@ int vc_text_workspace_bytes_impl(void* handle, int32_t L, int64_t* bytes, char* 
 int vc_text_prepare_impl(void* handle, int32_t L, void* workspace, int64_t workspace_bytes, hipStream_t s, char* err, int errlen);
 int vc_text_encode_impl(void* handle, const int32_t* ids, int32_t n_prompts, void* hidden, void* pooled, hipStream_t s, char* err, int errlen);
 int vc_text_plan_count_impl(void* handle);
+const VcTextConfig* vc_text_config_impl(void* handle);
+
+// grid_engine.hip: the grid handle
+int vc_grid_create_impl(const VcGridConfig* cfg, void** handle, char* err, int errlen);
+int vc_grid_destroy_impl(void* handle, char* err, int errlen);
+int vc_grid_workspace_bytes_impl(void* handle, const VcGridJob* job, int64_t* bytes, char* err, int errlen);
+int vc_grid_sdedit_workspace_bytes_impl(void* handle, const VcGridSdedit* job, int64_t* bytes, char* err, int errlen);
+int vc_grid_generate_impl(void* handle, const VcGridJob* job, void* workspace, int64_t workspace_bytes, void* const* out_rows, hipStream_t s,
+                          char* err, int errlen);
+int vc_grid_sdedit_impl(void* handle, const VcGridSdedit* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
+                        hipStream_t s, char* err, int errlen);

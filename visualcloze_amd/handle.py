@@ -619,3 +619,132 @@ class TextHandle(_Handle):
                 if t is not None:
                     t.record_stream(cur)
         return hidden, pooled
+
+
+class GridHandle(_Handle):
+    """The grid handle of include/vcloze_hip.h (vc_grid_*) behind torch tensors: one grid - pixels and token ids in, pixels out - as
+    ONE C call (`generate`), and the SDEdit upsampling of K cells as one more (`sdedit`).  The composition lives in
+    csrc/grid_engine.hip; `pipeline.generate_grid` / `pipeline.upsample_images` with a `NoiseStream` and the three sub-handles on are
+    its parity twin (same kernels, same operands, same bits).  It borrows the C handles of `model.handle()`, `ae.handle()`,
+    `t5.handle()` and `clip.handle()` (it keeps those wrappers, and with them the bound weights, alive), owns ONE workspace that only ever grows - kept between calls, so
+    a second job of the same geometry finds every captured plan again - and, because the C call prepares the sub-handles inside that
+    workspace, tells their Python wrappers to prepare again before their next direct use."""
+    _destroy = "vc_grid_destroy"
+
+    def __init__(self, model, ae, t5, clip):
+        self.flux, self.vae, self.t5, self.clip = model.handle(), ae.handle(), t5.handle(), clip.handle()
+        if self.flux is None:
+            raise hip.VclozeHipError("GridHandle needs the Flux C handle (use_handle True; with lora_mode 'ref': ref_plan 'handle')")
+        self.dev = self.flux.dev
+        self.h = C.c_void_p()
+        cfg = hip.GridConfig(self.flux.h.value, self.vae.h.value, self.t5.h.value, self.clip.h.value)
+        hip._check(hip.lib().vc_grid_create(C.byref(cfg), C.byref(self.h)), "vc_grid_create")
+        self._ws: Optional[torch.Tensor] = None
+        self._side = None
+
+    def _workspace(self, need: int) -> Tuple[int, int]:
+        if self._ws is None or self._aligned(self._ws)[1] < need:
+            self._ws = None
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.dev)
+        return self._aligned(self._ws)
+
+    @staticmethod
+    def _ids(ids: torch.Tensor, name: str) -> np.ndarray:
+        if ids.dim() == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.dim() != 1:
+            raise hip.VclozeHipError(f"GridHandle: {name} [1, L] or [L] expected, got {tuple(ids.shape)}")
+        return np.ascontiguousarray(ids.detach().to("cpu", torch.int32).numpy())
+
+    def _pixels(self, imgs: Sequence[torch.Tensor]) -> list:
+        out = []
+        for t in imgs:
+            if t.dim() != 3 or t.shape[0] != 3 or t.device != self.dev:
+                raise hip.VclozeHipError(f"GridHandle: [3, H, W] pixels on {self.dev} expected, got {tuple(t.shape)} on {t.device}")
+            out.append(t.to(torch.bfloat16).contiguous())      # as pipeline.generate_grid hands them to the encoder
+        return out
+
+    def _run(self, call, what, job, bytes_fn, shapes, uint8, stream):
+        """size the workspace, allocate the outputs, run `call` on the plan's stream; returns (outputs, stream position after)"""
+        need = C.c_int64(0)
+        hip._check(bytes_fn(self.h, C.byref(job), C.byref(need)), what + "_workspace_bytes")
+        base, nbytes = self._workspace(need.value)
+        outs = [None if s is None else torch.empty((s[1], s[2], 3) if uint8 else s, dtype=torch.uint8 if uint8 else torch.float32, device=self.dev)
+                for s in shapes]
+        ptrs = (C.c_void_p * len(outs))(*[None if o is None else o.data_ptr() for o in outs])
+        after = C.c_uint64(0)
+        job.noise_offset_out = C.pointer(after)
+        s, cur = self._stream(stream)
+        try:
+            hip._check(call(self.h, C.byref(job), base, nbytes, ptrs, s), what)
+        finally:
+            # the sub-handles are now prepared inside this handle's workspace: their wrappers must not trust what they remember
+            self.vae._prepared = self.t5._prepared = self.clip._prepared = None
+            self.flux.geom = None
+            self._join(stream, cur)
+        if cur is not None:
+            for o in outs:
+                if o is not None:
+                    o.record_stream(cur)
+        return [o for o in outs if o is not None], after.value
+
+    def generate(self, row_images: Sequence[torch.Tensor], row_masks: Sequence[torch.Tensor], t5_ids: torch.Tensor, clip_ids: torch.Tensor,
+                 seed: int, noise_offset: int = 0, cfg: float = 30.0, steps: int = 30, solver="euler", time_shifting_factor=1,
+                 decode_rows: Optional[Sequence[int]] = None, uint8: bool = False, max_evals: int = 0, stream=0):
+        """vc_grid_generate: row_images[i] [3, H, W_row] in [-1, 1], row_masks[i] [..., H, W_row] (1 = generate), ids [1, L]; the
+        noise comes from the library's stream of `seed` from `noise_offset` on.  Returns (the rows `decode_rows` (default: all, in
+        row order) as f32 [3, H, W_row] in [0, 1] - or with `uint8` as [H, W_row, 3] bytes -, the stream position after the last draw)."""
+        R = len(row_images)
+        if not 1 <= R <= hip.GRID_MAX_ROWS or len(row_masks) != R:
+            raise hip.VclozeHipError(f"GridHandle.generate: 1..{hip.GRID_MAX_ROWS} rows with one mask each expected, got {R} / {len(row_masks)}")
+        px = self._pixels(row_images)
+        masks = []
+        for m, p in zip(row_masks, px):
+            m = m.reshape(m.shape[-2], m.shape[-1]).to(self.dev, torch.bfloat16).contiguous()
+            if m.shape != p.shape[-2:]:
+                raise hip.VclozeHipError(f"GridHandle.generate: mask {tuple(m.shape)} for a row of {tuple(p.shape[-2:])} pixels")
+            masks.append(m.clone() if m.data_ptr() % 16 else m)
+        want = set(range(R)) if decode_rows is None else {int(i) for i in decode_rows}
+        if not want <= set(range(R)):
+            raise hip.VclozeHipError(f"GridHandle.generate: decode_rows {sorted(want)} outside the {R} rows")
+        t5a, clipa = self._ids(t5_ids, "t5_ids"), self._ids(clip_ids, "clip_ids")
+        job = hip.GridJob()
+        job.rows, job.pixels_is_f32 = R, 0
+        for i in range(R):
+            job.height[i], job.width[i] = px[i].shape[-2:]
+            job.pixels[i], job.masks[i], job.decode[i] = px[i].data_ptr(), masks[i].data_ptr(), int(i in want)
+        job.t5_ids, job.clip_ids, job.t5_len, job.clip_len = _ip(t5a), _ip(clipa), t5a.size, clipa.size
+        job.seed, job.noise_offset = hip._u64(seed, "seed"), hip._u64(noise_offset, "noise_offset")
+        job.guidance, job.n_points, job.method = float(cfg), int(steps), FluxHandle._method(solver)
+        job.out_form, job.max_evals = hip.PIXELS_U8 if uint8 else hip.PIXELS_F32, int(max_evals)
+        job.time_shifting_factor = float(time_shifting_factor or 0.0)
+        shapes = [tuple(px[i].shape) if i in want else None for i in range(R)]
+        L = hip.lib()
+        outs, after = self._run(L.vc_grid_generate, "vc_grid_generate", job, L.vc_grid_workspace_bytes, shapes, uint8, stream)
+        if decode_rows is not None:             # in the caller's order, as pipeline.generate_grid returns them
+            by_row = dict(zip(sorted(want), outs))
+            outs = [by_row[int(i)] for i in decode_rows]
+        return outs, after
+
+    def sdedit(self, images: Sequence[torch.Tensor], t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, noise_offset: int = 0,
+               cfg: float = 30.0, steps: int = 10, strength: float = 0.4, solver="euler", uint8: bool = False, max_evals: int = 0, stream=0):
+        """vc_grid_sdedit: K images [3, H, W] in [-1, 1] of ONE size, already at their final size, refined together from `strength`
+        under the content prompt.  Returns (K images, f32 [3, H, W] in [0, 1] or `uint8` [H, W, 3], the stream position after)."""
+        K = len(images)
+        if not 1 <= K <= hip.GRID_MAX_ROWS:
+            raise hip.VclozeHipError(f"GridHandle.sdedit: 1..{hip.GRID_MAX_ROWS} images expected, got {K}")
+        px = self._pixels(images)
+        if any(p.shape != px[0].shape for p in px):
+            raise hip.VclozeHipError("GridHandle.sdedit: all targets must share one size")
+        t5a, clipa = self._ids(t5_ids, "t5_ids"), self._ids(clip_ids, "clip_ids")
+        job = hip.GridSdedit()
+        job.count, job.pixels_is_f32 = K, 0
+        job.height, job.width = px[0].shape[-2:]
+        for k in range(K):
+            job.pixels[k] = px[k].data_ptr()
+        job.t5_ids, job.clip_ids, job.t5_len, job.clip_len = _ip(t5a), _ip(clipa), t5a.size, clipa.size
+        job.seed, job.noise_offset = hip._u64(seed, "seed"), hip._u64(noise_offset, "noise_offset")
+        job.guidance, job.n_points, job.method = float(cfg), int(steps), FluxHandle._method(solver)
+        job.out_form, job.max_evals, job.strength = hip.PIXELS_U8 if uint8 else hip.PIXELS_F32, int(max_evals), float(strength)
+        L = hip.lib()
+        return self._run(L.vc_grid_sdedit, "vc_grid_sdedit", job, L.vc_grid_sdedit_workspace_bytes, [tuple(p.shape) for p in px], uint8, stream)

@@ -117,6 +117,33 @@ class TextConfig(C.Structure):
 
 TEXT_T5, TEXT_CLIP = 1, 2                                   # VC_TEXT_T5 / VC_TEXT_CLIP (VcTextConfig.kind)
 
+GRID_MAX_ROWS, GRID_SDEDIT_CHUNK = 16, 4                    # VC_GRID_MAX_ROWS / VC_GRID_SDEDIT_CHUNK
+PIXELS_F32, PIXELS_U8 = 0, 1                                # VC_PIXELS_* (out_form of vc_pixels_out and of the grid jobs)
+
+
+class GridConfig(C.Structure):
+    """VcGridConfig of include/vcloze_hip.h: the four borrowed sub-handles."""
+    _fields_ = [("flux", C.c_void_p), ("vae", C.c_void_p), ("t5", C.c_void_p), ("clip", C.c_void_p)]
+
+
+class GridJob(C.Structure):
+    """VcGridJob of include/vcloze_hip.h."""
+    _fields_ = [("rows", C.c_int32), ("pixels_is_f32", C.c_int32), ("height", C.c_int32 * GRID_MAX_ROWS), ("width", C.c_int32 * GRID_MAX_ROWS),
+                ("pixels", C.c_void_p * GRID_MAX_ROWS), ("masks", C.c_void_p * GRID_MAX_ROWS), ("decode", C.c_int32 * GRID_MAX_ROWS),
+                ("t5_ids", C.POINTER(C.c_int32)), ("clip_ids", C.POINTER(C.c_int32)), ("t5_len", C.c_int32), ("clip_len", C.c_int32),
+                ("seed", C.c_uint64), ("noise_offset", C.c_uint64), ("noise_offset_out", C.POINTER(C.c_uint64)),
+                ("guidance", C.c_float), ("n_points", C.c_int32), ("method", C.c_int32), ("out_form", C.c_int32), ("max_evals", C.c_int32),
+                ("_pad", C.c_int32), ("time_shifting_factor", C.c_double)]
+
+
+class GridSdedit(C.Structure):
+    """VcGridSdedit of include/vcloze_hip.h."""
+    _fields_ = [("count", C.c_int32), ("pixels_is_f32", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("pixels", C.c_void_p * GRID_MAX_ROWS), ("t5_ids", C.POINTER(C.c_int32)), ("clip_ids", C.POINTER(C.c_int32)),
+                ("t5_len", C.c_int32), ("clip_len", C.c_int32), ("seed", C.c_uint64), ("noise_offset", C.c_uint64),
+                ("noise_offset_out", C.POINTER(C.c_uint64)), ("guidance", C.c_float), ("n_points", C.c_int32), ("method", C.c_int32),
+                ("out_form", C.c_int32), ("max_evals", C.c_int32), ("_pad", C.c_int32), ("strength", C.c_double)]
+
 
 # every symbol include/vcloze_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -224,6 +251,17 @@ SYMBOLS = {
     "vc_text_prepare": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),
     "vc_text_encode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "vc_text_plan_count": (C.c_int, [_vp]),
+    "vc_time_grid": (C.c_int, [_i32, _i32, C.c_double, C.c_double, _i32, C.c_double, C.POINTER(C.c_float)]),
+    "vc_grid_tokens": (_i64, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_grid_img_ids": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float)]),
+    "vc_pixels_out": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "vc_grid_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_grid_create": (C.c_int, [C.POINTER(GridConfig), C.POINTER(_vp)]),
+    "vc_grid_destroy": (C.c_int, [_vp]),
+    "vc_grid_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridJob), C.POINTER(_i64)]),
+    "vc_grid_sdedit_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridSdedit), C.POINTER(_i64)]),
+    "vc_grid_generate": (C.c_int, [_vp, C.POINTER(GridJob), _vp, _i64, C.POINTER(_vp), _vp]),
+    "vc_grid_sdedit": (C.c_int, [_vp, C.POINTER(GridSdedit), _vp, _i64, C.POINTER(_vp), _vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
     "vc_stream_sync": (C.c_int, [_vp]),
@@ -276,6 +314,10 @@ def lib() -> C.CDLL:
         l.vc_text_struct_sizes(vsize)
         if vsize[0] != C.sizeof(TextConfig):
             raise VclozeHipError(f"libvcloze_hip.so sizeof(VcTextConfig) {vsize[0]} differs from the ctypes mirror - rebuild")
+        gsize = (C.c_int32 * 3)()
+        l.vc_grid_struct_sizes(gsize)
+        if list(gsize) != [C.sizeof(GridConfig), C.sizeof(GridJob), C.sizeof(GridSdedit)]:
+            raise VclozeHipError(f"libvcloze_hip.so grid struct sizes {list(gsize)} differ from the ctypes mirrors - rebuild")
         _lib = l
     return _lib
 
@@ -774,6 +816,52 @@ def unpack_latent(tokens, latent, col0=0, stream=None):
         raise VclozeHipError(f"unpack_latent: C={Cc} > 64 channels (the tile staged through LDS holds 64)")
     _check(lib().vc_unpack_latent(tokens.data_ptr(), tokens.stride(0), col0, latent.data_ptr(), Cc, h, w,
                                   stream if stream is not None else cur_stream()), "vc_unpack_latent")
+
+
+# ---- the grid's host rules (csrc/grid_rules.hip; no GPU needed) and its pixel epilogue (csrc/pixels_out.hip) ----
+def time_grid(n_points: int, n_tokens: int, t0: float = 0.0, t1: float = 1.0, do_shift: bool = True, time_shifting_factor=1.0) -> torch.Tensor:
+    """vc_time_grid: the solver's n_points f32 time points, bit for bit transport.solver_time_grid(n_points, n_tokens, t0, t1, do_shift,
+    time_shifting_factor) (None or 0 = no factor).  A CPU tensor."""
+    out = torch.empty(max(int(n_points), 0), dtype=torch.float32)
+    _check(lib().vc_time_grid(int(n_points), int(n_tokens), float(t0), float(t1), int(bool(do_shift)), float(time_shifting_factor or 0.0),
+                              C.cast(out.data_ptr(), C.POINTER(C.c_float)) if out.numel() else None), "vc_time_grid")
+    return out
+
+
+def grid_tokens(rows_hw) -> int:
+    """vc_grid_tokens: the image tokens of one sample whose grid rows have the LATENT sizes rows_hw = [(h, w), ...]"""
+    k = len(rows_hw)
+    hs, ws = (C.c_int32 * max(k, 1))(*[int(h) for h, _ in rows_hw]), (C.c_int32 * max(k, 1))(*[int(w) for _, w in rows_hw])
+    n = lib().vc_grid_tokens(k, hs, ws)
+    _check(0 if n >= 0 else int(n), "vc_grid_tokens")
+    return int(n)
+
+
+def grid_img_ids(rows_hw) -> torch.Tensor:
+    """vc_grid_img_ids: [tokens, 3] f32 (CPU) = packing.grid_img_ids(rows_hw): axis 0 the row index + 1, axes 1 / 2 y and x"""
+    k = len(rows_hw)
+    hs, ws = (C.c_int32 * max(k, 1))(*[int(h) for h, _ in rows_hw]), (C.c_int32 * max(k, 1))(*[int(w) for _, w in rows_hw])
+    out = torch.empty(grid_tokens(rows_hw), 3, dtype=torch.float32)
+    _check(lib().vc_grid_img_ids(k, hs, ws, C.cast(out.data_ptr(), C.POINTER(C.c_float))), "vc_grid_img_ids")
+    return out
+
+
+def pixels_out(img, x0: int = 0, w: Optional[int] = None, uint8: bool = False, out=None, stream=None):
+    """vc_pixels_out: columns [x0, x0 + w) of the decoded image img [3, H, W] (bf16 or f32, in [-1, 1]) as f32 [3, H, w] in [0, 1] =
+    ((img.float() + 1.0) / 2.0).clamp_(0.0, 1.0), or with `uint8` as [H, w, 3] bytes = that .mul(255).to(torch.uint8) (truncating),
+    HWC as PIL takes it."""
+    if img.dim() != 3 or img.shape[0] != 3 or not img.is_cuda or img.dtype not in (torch.bfloat16, torch.float32) or not img.is_contiguous():
+        raise VclozeHipError(f"pixels_out: a contiguous CUDA [3, H, W] bf16 / f32 image expected, got {img.dtype} {tuple(img.shape)} on {img.device}")
+    H, W = img.shape[-2:]
+    w = W - x0 if w is None else w
+    shape, dt = ((H, w, 3), torch.uint8) if uint8 else ((3, H, w), torch.float32)
+    if out is None:
+        out = torch.empty([max(int(d), 0) for d in shape], dtype=dt, device=img.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dt or not out.is_contiguous() or out.device != img.device:
+        raise VclozeHipError(f"pixels_out: out must be a contiguous {dt} tensor of shape {tuple(shape)} on {img.device}")
+    _check(lib().vc_pixels_out(img.data_ptr(), int(img.dtype == torch.float32), H, W, int(x0), int(w), out.data_ptr(),
+                               PIXELS_U8 if uint8 else PIXELS_F32, stream if stream is not None else cur_stream()), "vc_pixels_out")
+    return out
 
 
 # ---- noise source (csrc/rng.hip): the library's own counter-based Gaussian stream, NOT torch's ----

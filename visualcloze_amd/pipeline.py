@@ -12,6 +12,7 @@ caller: inputs are row tensors in [-1, 1] and token ids.
 """
 from __future__ import annotations
 
+import weakref
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -70,6 +71,30 @@ def _encode(ae, px, noise, rng) -> torch.Tensor:
         f = 2 ** (ae.encoder.num_resolutions - 1)
         noise = rng.randn([1, ae.encoder.z_channels, px.shape[-2] // f, px.shape[-1] // f], torch.bfloat16, device=px.device)
     return ae.encode(px, noise=noise)
+
+
+_GRID_HANDLES = weakref.WeakKeyDictionary()        # model -> (the four sub-handles' identities, GridHandle)
+
+
+def _grid_handle(model, ae, t5, clip, rng, what: str, **unsupported):
+    """the `handle.GridHandle` over the four modules' C handles for `use_grid_handle=True`, kept per model while those handles
+    live.  The switch is never silently ignored: it needs the library's noise stream and all three `use_handle` switches on."""
+    if not isinstance(rng, NoiseStream):
+        raise ValueError(f"{what}(use_grid_handle=True) draws from the library's stream: pass rng=NoiseStream(seed)")
+    for name, v in unsupported.items():
+        if v is not None:
+            raise ValueError(f"{what}(use_grid_handle=True) draws every noise tensor itself: {name} must be None")
+    if not (getattr(model, "use_handle", False) and model.handle() is not None and getattr(ae, "use_handle", False)
+            and t5._handle_serves() and clip._handle_serves()):
+        raise ValueError(f"{what}(use_grid_handle=True) needs the C handles of all four modules: model.use_handle, ae.use_handle, "
+                         "t5.use_handle and clip.use_handle True (bf16 text encoders; with lora_mode 'ref': ref_plan 'handle')")
+    from .handle import GridHandle
+    key = tuple(id(h) for h in (model.handle(), ae.handle(), t5.handle(), clip.handle()))
+    c = _GRID_HANDLES.get(model)
+    if c is None or c[0] != key:
+        c = (key, GridHandle(model, ae, t5, clip))
+        _GRID_HANDLES[model] = c
+    return c[1]
 
 
 def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
@@ -150,7 +175,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
                   t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, cfg: float = 30.0, steps: int = 30,
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
                   solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
-                  step_cache=None) -> List[torch.Tensor]:
+                  step_cache=None, use_grid_handle: bool = False) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -162,7 +187,19 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     order of draws - the DiagonalGaussian draw of each row's encode (:377; unless `encode_noise` gives it), then one start-noise
     tensor per row (:395-399) - each a contiguous stretch of the stream.  Returns the decoded rows `decode_rows` (default: all) as
     [3, H, W_row] tensors in [0, 1] (:430-432).  `step_cache`: a `transport.StepCache` or None (off, the default) - the opt-in first-block step cache of
-    the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`."""
+    the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`.
+    `use_grid_handle`: opt-in, off by default - the whole function as ONE call of the library's grid handle (vc_grid_generate,
+    `handle.GridHandle`: the same composition kept in csrc/grid_engine.hip, the same bits).  Valid only with a `NoiseStream` and the
+    use_handle switches of all four modules on (ValueError otherwise); `rng.offset` advances as it does here."""
+    if use_grid_handle:
+        gh = _grid_handle(model, ae, t5, clip, rng, "generate_grid", encode_noise=encode_noise)
+        if step_cache is not None and solver != "euler":
+            raise ValueError(f"step_cache works with sampling_method='euler' only, not {solver!r}")
+        gh.flux.set_step_cache(step_cache)             # what Sampler.sample_ode sets before a trajectory on this handle
+        gh.flux.set_cfg(None)
+        out, rng.offset = gh.generate(row_images, row_masks, t5_ids, clip_ids, rng.seed, rng.offset, cfg=cfg, steps=steps, solver=solver,
+                                      time_shifting_factor=time_shifting_factor, decode_rows=decode_rows)
+        return out
     dev = row_images[0].device
     lat = []
     for i, img in enumerate(row_images):                                               # :377-378
@@ -236,11 +273,14 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
 @torch.no_grad()
 def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
                     rng: Union[torch.Generator, NoiseStream], cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
-                    encode_noise: Optional[Sequence] = None, solver: str = "euler", step_cache=None) -> List[torch.Tensor]:
+                    encode_noise: Optional[Sequence] = None, solver: str = "euler", step_cache=None,
+                    use_grid_handle: bool = False) -> List[torch.Tensor]:
     """`upsample_image` for several images of one grid in ONE batched SDEdit solve (`sdedit_upsample_batch`).  Host work
     (resize), the VAE encodes and every random draw happen per image in the reference's order - image k: encode(image),
     encode(blank), noise from `rng` (visualcloze.py:200-217) - so each target starts from exactly the state the
-    one-at-a-time loop gives it; the prompt is encoded once (it is the same for every target, :458)."""
+    one-at-a-time loop gives it; the prompt is encoded once (it is the same for every target, :458).  `use_grid_handle`: opt-in -
+    everything behind the host resize as ONE call of the library's grid handle (vc_grid_sdedit), under the conditions of
+    `generate_grid`'s switch; the same bits."""
     import numpy as np
     dev = next(ae.parameters()).device
     size = upsampling_size(target_size)
@@ -250,8 +290,17 @@ def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: 
             image = to_uint8_image(image)
         image = image.convert("RGB").resize(size)                                      # :179
         pxs.append(torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0))
+    gh = _grid_handle(model, ae, t5, clip, rng, "upsample_images", encode_noise=encode_noise) if use_grid_handle else None
     if strength >= 1.0:
         return [px.to(dev) for px in pxs]                                              # :180-181
+    if gh is not None:
+        if step_cache is not None and solver != "euler":
+            raise ValueError(f"step_cache works with sampling_method='euler' only, not {solver!r}")
+        gh.flux.set_step_cache(step_cache)
+        gh.flux.set_cfg(None)
+        out, rng.offset = gh.sdedit([((px - 0.5) / 0.5).to(dev, torch.bfloat16) for px in pxs], t5_ids, clip_ids, rng.seed, rng.offset,
+                                    cfg=cfg, steps=steps, strength=strength, solver=solver)
+        return out
     lat, blank, noise = [], [], []
     for k, px in enumerate(pxs):
         px = ((px - 0.5) / 0.5).to(dev, torch.bfloat16)
@@ -275,7 +324,7 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
                           upsampling_steps: int = 10, upsampling_noise: float = 0.4, is_upsampling: bool = True,
                           encode_noise: Optional[List[torch.Tensor]] = None, upsample_encode_noise=None,
                           solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True, step_cache=None,
-                          rng: Union[torch.Generator, NoiseStream, None] = None):
+                          rng: Union[torch.Generator, NoiseStream, None] = None, use_grid_handle: bool = False):
     """Both stages of `process_images` chained (visualcloze.py:363-465): the grid is generated, its LAST row is decoded and
     quantised to 8 bits as `to_pil_image` does, every cell of that row whose `mask_position` is set is cropped
     (:452,461) and - with `is_upsampling` - refined by `upsample_image` at `target_size`, all noise coming from ONE
@@ -283,14 +332,18 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     per solver step for all of them (`upsample_images`; same draws in the same order, per-target results equal up to bf16
     noise); False = one after the other as the reference loops.  `rng`: the generator both stages draw from instead of a fresh
     torch.Generator seeded with `seed` - a `NoiseStream` puts every draw of both stages on the library's own stream, in the
-    reference's order.  Returns the output images as [3, h, w] tensors in [0, 1]."""
+    reference's order.  `use_grid_handle`: opt-in - both stages through the library's grid handle (vc_grid_generate, then vc_grid_sdedit
+    per batch of targets; the crop and the resize between them stay here), under the conditions of `generate_grid`'s switch; the same
+    bits.  Returns the output images as [3, h, w] tensors in [0, 1]."""
+    if use_grid_handle:
+        _grid_handle(model, ae, t5, clip, rng, "generate_and_upsample", encode_noise=encode_noise, upsample_encode_noise=upsample_encode_noise)
     dev = row_images[0].device
     if rng is None:
         rng = torch.Generator(device=dev).manual_seed(int(seed))
     last = len(row_images) - 1
     row = generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                         encode_noise=encode_noise, decode_rows=[last], solver=solver, time_shifting_factor=time_shifting_factor,
-                        rng=rng, step_cache=step_cache)[0]
+                        rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle)[0]
     pil = to_uint8_image(row)                                                          # :437-439
     ret_w, ret_h = pil.width, pil.height
     cells = [pil.crop((i * ret_w // grid_w, 0, (i + 1) * ret_w // grid_w, ret_h)) for i, m in enumerate(mask_position) if m]   # :452,461
@@ -298,13 +351,17 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     cclip = content_clip_ids if content_clip_ids is not None else clip_ids
     if is_upsampling and batch_targets and len(cells) > 1:
         return upsample_images(model, ae, t5, clip, cells, target_size, ct5, cclip, rng, cfg=cfg, steps=upsampling_steps,
-                               strength=upsampling_noise, encode_noise=upsample_encode_noise, solver=solver, step_cache=step_cache)
+                               strength=upsampling_noise, encode_noise=upsample_encode_noise, solver=solver, step_cache=step_cache,
+                               use_grid_handle=use_grid_handle)
     outs, k = [], 0
     for i, masked in enumerate(mask_position):
         if not masked:
             continue
         cell = pil.crop((i * ret_w // grid_w, 0, (i + 1) * ret_w // grid_w, ret_h))    # :452,461
-        if is_upsampling:
+        if is_upsampling and use_grid_handle:          # one target: a batch of one through vc_grid_sdedit
+            outs += upsample_images(model, ae, t5, clip, [cell], target_size, ct5, cclip, rng, cfg=cfg, steps=upsampling_steps,
+                                    strength=upsampling_noise, solver=solver, step_cache=step_cache, use_grid_handle=True)
+        elif is_upsampling:
             en = None if upsample_encode_noise is None else upsample_encode_noise[k]
             outs.append(upsample_image(model, ae, t5, clip, cell, target_size, content_t5_ids if content_t5_ids is not None else t5_ids,
                                        content_clip_ids if content_clip_ids is not None else clip_ids, rng, cfg=cfg,
