@@ -841,8 +841,8 @@ int vc_pixels_out(const void* img, int32_t img_is_f32, int32_t H, int32_t W, int
  * sub-handles (it never destroys them; they must outlive it, with their weights bound): whatever is set on the Flux handle - LoRA
  * mode and scale, taps, the step cache, true CFG (leave it off: the grid runs B = 1) - acts as it does in vc_flux_sample_ode.  It
  * prepares the sub-handles inside ITS workspace on every call: a caller who also drives a sub-handle directly prepares that one again
- * afterwards.  Image loading, resizing (the bicubic Image.resize between the stages, :179), prefix stripping and tokenisation stay
- * host work.  Needs an autoencoder of 8x reduction (n_ch_mult 4) with 4 * z_channels == the Flux out_channels and
+ * afterwards.  Image decoding, prefix stripping and tokenisation stay host work; resizing does not (the photo front end below takes
+ * 8-bit images).  Needs an autoencoder of 8x reduction (n_ch_mult 4) with 4 * z_channels == the Flux out_channels and
  * in_channels - out_channels == 4 * z_channels + 256, a T5 of d_model == context_in_dim and a CLIP of d_model == vec_in_dim
  * (VC_ERR_ARG from vc_grid_create otherwise).  One handle per device; not thread-safe; one stream at a time. */
 #define VC_GRID_MAX_ROWS 16
@@ -917,6 +917,135 @@ int vc_grid_generate(void* handle, const VcGridJob* job, void* workspace, int64_
  * the grid vc_time_grid(n_points, tokens, strength, 1, 0, 1.0); one batched solve per VC_GRID_SDEDIT_CHUNK targets; decode;
  * vc_pixels_out.  strength >= 1: the input pixels converted, nothing drawn (visualcloze.py:180-181). */
 int vc_grid_sdedit(void* handle, const VcGridSdedit* job, void* workspace, int64_t workspace_bytes, void* const* out_images, void* stream);
+
+/* ---- the photo front end: 8-bit photographs in.  Resampling, pixels in, the size rules and two more calls of the grid handle ----
+ * Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up vc_resample_u8.
+ *
+ * RESAMPLING.  vc_resample_u8 resizes an 8-bit image src [H, W, 3] to dst [h, w, 3] with a separable filter in fixed point.  The
+ * rule is the library's own and is stated here in full; it is the rule Pillow's Image.resize applies to 8-bit images, so the bytes
+ * are Pillow's (the tests hold the tables to PIL.Image.resize byte for byte).  Per axis - horizontal first, then vertical, with an
+ * 8-BIT intermediate [H, w, 3]; an axis whose size does not change is skipped, and if neither changes dst is a copy of src - with
+ * `in` and `out` the sizes along the axis, everything in double:
+ *     scale = in / out;   fs = max(scale, 1);   support = S * fs,  S = 2 (VC_FILTER_BICUBIC) or 3 (VC_FILTER_LANCZOS)
+ *     for the output index xx:   c = (xx + 0.5) * scale
+ *         xmin = max((int)(c - support + 0.5), 0);    len = min((int)(c + support + 0.5), in) - xmin
+ *         k[x] = f((x + xmin - c + 0.5) * (1 / fs))   for x < len, then divided by their sum (summed in index order; a sum of 0
+ *                                                     leaves them as they are)
+ *         ki[x] = (int)(0.5 + k[x] * 2^22) for k[x] >= 0, (int)(-0.5 + k[x] * 2^22) otherwise
+ *     bicubic, a = -0.5:  f(x) = ((a + 2)|x| - (a + 3)) x^2 + 1 for |x| < 1,  (((|x| - 5)|x| + 8)|x| - 4) a for |x| < 2,  else 0
+ *     Lanczos:            f(x) = sinc(x) sinc(x / 3) for -3 <= x < 3, else 0;  sinc(0) = 1, sinc(x) = sin(pi x) / (pi x)
+ *     output byte = clip to 0..255 of (2^21 + sum over x < len of pixel[xmin + x] * ki[x]) >> 22   (int32, arithmetic shift)
+ * The tables hold kmax = (int)ceil(support) * 2 + 1 weights per output index (vc_resample_kmax); entries from len on are 0.
+ *
+ * vc_resample_kmax, vc_resample_coeffs, vc_resample_tmp_bytes are HOST-ONLY (no device, like vc_solver_evals).  vc_resample_coeffs
+ * fills xmin[out], len[out], ki[out][kmax] for one axis; kmax must be vc_resample_kmax's value.  vc_resample_tmp_bytes is the size
+ * of the device scratch `tmp` of vc_resample_u8 (the two axes' tables and the intermediate; 256-B aligned, never 0); it returns a
+ * negative VC_ERR_ARG on bad arguments.  vc_resample_u8 builds the tables on the host, stages them through pinned memory and
+ * uploads them on `stream` ahead of its (at most two) kernels; because of that upload it cannot be captured into a graph.  Sizes
+ * outside 1..65535, an unknown filter, a null pointer, overlap of src, dst and tmp or a tmp that is too small or misaligned are
+ * VC_ERR_ARG, found before the device is touched. */
+#define VC_FILTER_BICUBIC 0
+#define VC_FILTER_LANCZOS 1
+int vc_resample_kmax(int32_t in, int32_t out, int32_t filter);
+int vc_resample_coeffs(int32_t in, int32_t out, int32_t filter, int32_t* xmin, int32_t* len, int32_t* ki, int32_t kmax);
+int64_t vc_resample_tmp_bytes(int32_t H, int32_t W, int32_t h, int32_t w, int32_t filter);
+int vc_resample_u8(const void* src, int32_t H, int32_t W, void* dst, int32_t h, int32_t w, int32_t filter, void* tmp, int64_t tmp_bytes,
+                   void* stream);
+
+/* PIXELS IN: the inverse of vc_pixels_out.  src 8-bit [H, W, 3]; the crop window of h x w pixels whose corner is (left, top) may
+ * reach OUTSIDE the image, where it reads 0 (Image.crop); it is written to the columns [x0, x0 + w) of the row tensor out
+ * [3, h, Wrow], bf16 (or F32 with out_is_f32), as ToTensor and Normalize(0.5, 0.5) give it (visualcloze.py:133-137):
+ *     v = (f32(byte) / 255 - 0.5) / 0.5      a true division, each operation rounded in f32, nothing contracted; then, for the
+ *                                            bf16 form, rounded to nearest even (:377)
+ * src == NULL (H, W, left, top ignored) writes the blank cell: byte 0, v = -1.  vc_mask_fill sets the same window of the row's
+ * bf16 pixel mask [h, Wrow] to value = 0 or 1 (:369-374).  1 <= h, Wrow <= 65535, 0 <= x0, 1 <= w, x0 + w <= Wrow, image sizes in
+ * 1..65535, |left|, |top| <= 65535; violations, a null out / mask, a misaligned base, out overlapping src are VC_ERR_ARG, found
+ * before the device is touched. */
+int vc_pixels_in(const void* src, int32_t H, int32_t W, int32_t left, int32_t top, void* out, int32_t out_is_f32, int32_t h,
+                 int32_t Wrow, int32_t x0, int32_t w, void* stream);
+int vc_mask_fill(void* mask, int32_t h, int32_t Wrow, int32_t x0, int32_t w, int32_t value, void* stream);
+
+/* SIZE RULES (HOST-ONLY): what visualcloze.py:28-75,298-360,166-180 compute with Python floats and ints, restated in double with
+ * truncation by (int) and floor division where Python floors.
+ * vc_fit_size: the size an image of w x h is fitted to at `resolution` R:  ar = w / h;  nh = (int)pow(R * R / ar, 0.5);
+ *   nw = (int)(nh * ar);  both then max(n / 16, 1) * 16.
+ * vc_grid_layout: the plan of every cell of a grid of grid_h x grid_w cells, row-major; cell_w[i] = cell_h[i] = 0 marks an absent
+ *   image.  A row's reference size is the fitted size of its first present image.  A present cell is resized with
+ *   VC_FILTER_LANCZOS to its fitted size (fit_w x fit_h), then with VC_FILTER_BICUBIC to cover_w x cover_h - fit_w <= fit_h:
+ *   (ref_w, (int)(ref_w / fit_w * fit_h)), else ((int)(ref_h / fit_h * fit_w), ref_h) - and centre-cropped to the reference size
+ *   at (crop_left, crop_top) = floor((cover - ref) / 2), NEGATIVE when the image is smaller than the reference size (the window
+ *   then reaches outside, which reads 0).  An absent cell is black at the reference size - resolution x resolution in a row
+ *   without any image - and carries mask = 1; above the last row it is VC_ERR_ARG.  cell_w x cell_h is the size after the crop.
+ *   If the grid has more than one column and more than one cell is masked, every cell is resized once more (bicubic) to
+ *   final_w x final_h, in cell order with a running width:  new_w starts at the last row's reference width (384 if it has none);
+ *   per cell new_h = (int)(cell_h * (new_w / cell_w)), new_w = (int)(new_w / 16) * 16, new_h = (int)(new_h / 16) * 16.  Otherwise
+ *   final = cell.  A size that leaves 1..65535 is VC_ERR_ARG; so is a row whose cells differ in final height (they would not
+ *   make one row tensor) or width (the reference sizes every cell's mask by the row's first cell).
+ * vc_upsampling_size: the size the cells are refined at, from the size of the last row's first image (0, 0 = none: 1024 x 1024):
+ *   above 1024^2 pixels  ar = w / h;  h = (int)pow(1024 * 1024 / ar, 0.5);  w = (int)(h * ar);  then both / 16 * 16. */
+typedef struct VcCellPlan {
+  int32_t present;                 /* 0: an absent image (black, masked) */
+  int32_t fit_w, fit_h;            /* VC_FILTER_LANCZOS target */
+  int32_t cover_w, cover_h;        /* VC_FILTER_BICUBIC target */
+  int32_t crop_left, crop_top;     /* corner of the centre crop inside cover_w x cover_h; may be negative */
+  int32_t cell_w, cell_h;          /* the cropped cell = the row's reference size */
+  int32_t final_w, final_h;        /* after the second bicubic pass; = cell_w x cell_h where there is none */
+  int32_t mask;                    /* 1: this cell is generated */
+} VcCellPlan;
+int vc_fit_size(int32_t w, int32_t h, int32_t resolution, int32_t* nw, int32_t* nh);
+int vc_grid_layout(int32_t grid_h, int32_t grid_w, const int32_t* cell_w, const int32_t* cell_h, int32_t resolution, VcCellPlan* out);
+int vc_upsampling_size(int32_t orig_w, int32_t orig_h, int32_t* w, int32_t* h);
+
+/* THE GRID HANDLE FROM PHOTOGRAPHS.  Two calls over vc_grid_generate and vc_grid_sdedit; they add no model work of their own.
+ * vc_grid_generate_photos: per cell a device 8-bit [H, W, 3] image or NULL; it runs vc_grid_layout, the resamples, vc_pixels_in and
+ *   vc_mask_fill into row tensors and masks in the FRONT part of its workspace, then exactly vc_grid_generate on the rest (same
+ *   noise stream, same outputs, same errors).  Rows must come to multiples of 16 pixels.
+ * vc_grid_sdedit_u8: `count` 8-bit cells [cell_h, cell_w, 3] of one size - what vc_pixels_out with VC_PIXELS_U8 and a cell's column
+ *   window writes - resized (bicubic) to height x width (vc_upsampling_size) and passed through vc_pixels_in, then exactly
+ *   vc_grid_sdedit.  strength >= 1: out_images receive the RESIZED 8-bit images (visualcloze.py:180-182), out_form must be
+ *   VC_PIXELS_U8, nothing is drawn.
+ * The workspace is kept between calls as for vc_grid_generate: a second job of the same geometry captures nothing.  Argument errors
+ * are VC_ERR_ARG with a message, found before the device is touched. */
+typedef struct VcGridPhotos {
+  int32_t grid_h, grid_w;                    /* 1..VC_GRID_MAX_ROWS each */
+  int32_t resolution;                        /* the reference's default is 384 */
+  int32_t out_form;                          /* VC_PIXELS_F32 or VC_PIXELS_U8 */
+  const void* const* images;                 /* HOST [grid_h * grid_w], row-major: device 8-bit [H, W, 3], or NULL = absent */
+  const int32_t* width;                      /* HOST [grid_h * grid_w]; not read where the image is NULL */
+  const int32_t* height;
+  int32_t decode[VC_GRID_MAX_ROWS];          /* as VcGridJob */
+  const int32_t* t5_ids;
+  const int32_t* clip_ids;
+  int32_t t5_len, clip_len;
+  uint64_t seed, noise_offset;
+  uint64_t* noise_offset_out;
+  float guidance;
+  int32_t n_points, method, max_evals;
+  double time_shifting_factor;
+} VcGridPhotos;
+typedef struct VcGridSdeditU8 {
+  int32_t count;                             /* 1..VC_GRID_MAX_ROWS cells */
+  int32_t cell_h, cell_w;                    /* the size of every cell */
+  int32_t height, width;                     /* the target: multiples of 16 */
+  int32_t out_form;
+  const void* pixels[VC_GRID_MAX_ROWS];      /* per cell, device 8-bit [cell_h, cell_w, 3] */
+  const int32_t* t5_ids;                     /* as VcGridSdedit from here on */
+  const int32_t* clip_ids;
+  int32_t t5_len, clip_len;
+  uint64_t seed, noise_offset;
+  uint64_t* noise_offset_out;
+  float guidance;
+  int32_t n_points, method, max_evals;
+  double strength;
+} VcGridSdeditU8;
+/* sizeof(VcCellPlan), sizeof(VcGridPhotos), sizeof(VcGridSdeditU8) as this library was compiled */
+void vc_photo_struct_sizes(int32_t out[3]);
+int vc_grid_photos_workspace_bytes(void* handle, const VcGridPhotos* job, int64_t* bytes);
+int vc_grid_sdedit_u8_workspace_bytes(void* handle, const VcGridSdeditU8* job, int64_t* bytes);
+int vc_grid_generate_photos(void* handle, const VcGridPhotos* job, void* workspace, int64_t workspace_bytes, void* const* out_rows,
+                            void* stream);
+int vc_grid_sdedit_u8(void* handle, const VcGridSdeditU8* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
+                      void* stream);
 
 /* ---- hipGraph helpers: capture the launches issued on `stream` between begin/end ---- */
 int vc_stream_create(void** stream);

@@ -332,6 +332,46 @@ int vc_grid_sdedit(void* handle, const VcGridSdedit* job, void* workspace, int64
   return vc_grid_sdedit_impl(handle, job, workspace, workspace_bytes, out_images, S(stream), ERRBUF);
 }
 
+/* ---- the photo front end: resample.hip, pixels_in.hip, the size rules of grid_rules.hip, two more calls of grid_engine.hip ---- */
+int vc_resample_kmax(int32_t in, int32_t out, int32_t filter) { return vc_resample_kmax_impl(in, out, filter, ERRBUF); }
+int vc_resample_coeffs(int32_t in, int32_t out, int32_t filter, int32_t* xmin, int32_t* len, int32_t* ki, int32_t kmax) {
+  return vc_resample_coeffs_impl(in, out, filter, xmin, len, ki, kmax, ERRBUF);
+}
+int64_t vc_resample_tmp_bytes(int32_t H, int32_t W, int32_t h, int32_t w, int32_t filter) { return vc_resample_tmp_bytes_impl(H, W, h, w, filter, ERRBUF); }
+int vc_resample_u8(const void* src, int32_t H, int32_t W, void* dst, int32_t h, int32_t w, int32_t filter, void* tmp, int64_t tmp_bytes,
+                   void* stream) {
+  return vc_resample_u8_launch(src, H, W, dst, h, w, filter, tmp, tmp_bytes, S(stream), ERRBUF);
+}
+int vc_pixels_in(const void* src, int32_t H, int32_t W, int32_t left, int32_t top, void* out, int32_t out_is_f32, int32_t h,
+                 int32_t Wrow, int32_t x0, int32_t w, void* stream) {
+  return vc_pixels_in_launch(src, H, W, left, top, out, out_is_f32, h, Wrow, x0, w, S(stream), ERRBUF);
+}
+int vc_mask_fill(void* mask, int32_t h, int32_t Wrow, int32_t x0, int32_t w, int32_t value, void* stream) {
+  return vc_mask_fill_launch(mask, h, Wrow, x0, w, value, S(stream), ERRBUF);
+}
+int vc_fit_size(int32_t w, int32_t h, int32_t resolution, int32_t* nw, int32_t* nh) { return vc_fit_size_impl(w, h, resolution, nw, nh, ERRBUF); }
+int vc_grid_layout(int32_t grid_h, int32_t grid_w, const int32_t* cell_w, const int32_t* cell_h, int32_t resolution, VcCellPlan* out) {
+  return vc_grid_layout_impl(grid_h, grid_w, cell_w, cell_h, resolution, out, ERRBUF);
+}
+int vc_upsampling_size(int32_t orig_w, int32_t orig_h, int32_t* w, int32_t* h) { return vc_upsampling_size_impl(orig_w, orig_h, w, h, ERRBUF); }
+void vc_photo_struct_sizes(int32_t out[3]) {
+  out[0] = (int32_t)sizeof(VcCellPlan); out[1] = (int32_t)sizeof(VcGridPhotos); out[2] = (int32_t)sizeof(VcGridSdeditU8);
+}
+int vc_grid_photos_workspace_bytes(void* handle, const VcGridPhotos* job, int64_t* bytes) {
+  return vc_grid_photos_workspace_bytes_impl(handle, job, bytes, ERRBUF);
+}
+int vc_grid_sdedit_u8_workspace_bytes(void* handle, const VcGridSdeditU8* job, int64_t* bytes) {
+  return vc_grid_sdedit_u8_workspace_bytes_impl(handle, job, bytes, ERRBUF);
+}
+int vc_grid_generate_photos(void* handle, const VcGridPhotos* job, void* workspace, int64_t workspace_bytes, void* const* out_rows,
+                            void* stream) {
+  return vc_grid_generate_photos_impl(handle, job, workspace, workspace_bytes, out_rows, S(stream), ERRBUF);
+}
+int vc_grid_sdedit_u8(void* handle, const VcGridSdeditU8* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
+                      void* stream) {
+  return vc_grid_sdedit_u8_impl(handle, job, workspace, workspace_bytes, out_images, S(stream), ERRBUF);
+}
+
 /* ---- streams / graphs / events ---- */
 int vc_stream_create(void** stream) {
   if (!stream) { snprintf(g_err, sizeof(g_err), "stream_create: null"); return VC_ERR_ARG; }

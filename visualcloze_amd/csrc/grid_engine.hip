@@ -13,6 +13,9 @@
 //   ENOISE  bf16 [z, h, w] of the largest item (the DiagonalGaussian draw)     PIN      the item's pixels, staged (plans are keyed
 //   PX      bf16 [3, H, W] of the largest item (the decoder's output)                   on workspace addresses only)
 //   sdedit only:  LAT NOISE bf16 [tok, C]    ZERO bf16 [3, H, W]    ONES bf16 [H, W]
+// The photo calls (vc_grid_generate_photos, vc_grid_sdedit_u8) put their own part in FRONT of that: the row (target) tensors and
+// masks they build from 8-bit images, the 8-bit intermediates of the resamples and vc_resample_u8's tmp; the rest is handed to
+// vc_grid_generate / vc_grid_sdedit as their workspace.
 #include "common.h"
 #include "vcloze_internal.h"
 #include "engine_core.h"
@@ -362,4 +365,237 @@ int vc_grid_sdedit_impl(void* handle, const VcGridSdedit* job, void* workspace, 
   for (int k = 0; k < K; ++k) TRY(decode_item(g, q, b, H, W, b.x + k * n * g.C, out_images[k], s, e));   // :237-240
   if (job->noise_offset_out) *job->noise_offset_out = pos;
   return VC_OK;
+}
+
+// ---- the photo front end: 8-bit images in.  The layout rule (grid_rules.hip), vc_resample_u8, vc_pixels_in and vc_mask_fill build
+// the row tensors in the front part of the workspace, then the job is vc_grid_generate's / vc_grid_sdedit's own.
+namespace {
+
+struct PhotoBufs {
+  bf16_t* rows[VC_GRID_MAX_ROWS] = {};
+  bf16_t* masks[VC_GRID_MAX_ROWS] = {};
+  unsigned char *fit = nullptr, *cover = nullptr, *cell = nullptr, *fin = nullptr;
+  char* tmp = nullptr;
+  int64_t tmp_b = 0;
+};
+
+struct PhotoPlan {
+  std::vector<VcCellPlan> cells;
+  VcGridJob job;                       // the job vc_grid_generate runs: rows, sizes, the pointers into the workspace
+};
+
+int64_t tmp_for(int H, int W, int h, int w, int filter) {
+  char scratch[8];
+  const int64_t n = vc_resample_tmp_bytes_impl(H, W, h, w, filter, scratch, (int)sizeof(scratch));
+  return n < 0 ? 0 : n;
+}
+
+// the layout and the carve-up of the photo part; a null base only adds up
+int plan_photos(const VcGridPhotos* job, char* base, PhotoPlan& pp, PhotoBufs& pb, int64_t* front, Err e) {
+  if (!job) FAIL(VC_ERR_ARG, "grid_generate_photos: null job");
+  if (!job->images || !job->width || !job->height) FAIL(VC_ERR_ARG, "grid_generate_photos: null images, width or height list");
+  if (job->grid_h < 1 || job->grid_h > VC_GRID_MAX_ROWS || job->grid_w < 1 || job->grid_w > VC_GRID_MAX_ROWS)
+    FAIL(VC_ERR_ARG, "grid_generate_photos: a grid of %dx%d cells, 1..%d rows and columns expected", job->grid_h, job->grid_w, VC_GRID_MAX_ROWS);
+  const int gh = job->grid_h, gw = job->grid_w, n = gh * gw;
+  std::vector<int32_t> cw((size_t)n), ch((size_t)n);
+  for (int c = 0; c < n; ++c) {
+    const bool has = job->images[c] != nullptr;
+    if (has && (job->width[c] < 1 || job->height[c] < 1)) FAIL(VC_ERR_ARG, "grid_generate_photos: image %d is %dx%d", c, job->width[c], job->height[c]);
+    cw[c] = has ? job->width[c] : 0;
+    ch[c] = has ? job->height[c] : 0;
+  }
+  pp.cells.assign((size_t)n, VcCellPlan{});
+  TRY(vc_grid_layout_impl(gh, gw, cw.data(), ch.data(), job->resolution, pp.cells.data(), e.buf, e.len));
+  VcGridJob& j = pp.job;
+  memset(&j, 0, sizeof(j));
+  j.rows = gh;
+  j.t5_ids = job->t5_ids; j.clip_ids = job->clip_ids; j.t5_len = job->t5_len; j.clip_len = job->clip_len;
+  j.seed = job->seed; j.noise_offset = job->noise_offset; j.noise_offset_out = job->noise_offset_out;
+  j.guidance = job->guidance; j.n_points = job->n_points; j.method = job->method; j.out_form = job->out_form; j.max_evals = job->max_evals;
+  j.time_shifting_factor = job->time_shifting_factor;
+  Carver c{base};
+  pb = PhotoBufs{};
+  int64_t fit = 0, cover = 0, cell = 0, fin = 0;
+  for (int i = 0; i < gh; ++i) {
+    int W = 0;
+    for (int k = 0; k < gw; ++k) W += pp.cells[i * gw + k].final_w;
+    const int H = pp.cells[i * gw].final_h;
+    if (H % 16 || W % 16 || W >= 65536) FAIL(VC_ERR_ARG, "grid_generate_photos: row %d comes to %dx%d pixels, multiples of 16 below 65536 expected", i, H, W);
+    j.height[i] = H; j.width[i] = W; j.decode[i] = job->decode[i];
+    pb.rows[i] = c.take<bf16_t>((int64_t)3 * H * W);
+    pb.masks[i] = c.take<bf16_t>((int64_t)H * W);
+    j.pixels[i] = pb.rows[i] ? (const void*)pb.rows[i] : (const void*)(uintptr_t)256;    // sizing only: any aligned non-null value
+    j.masks[i] = pb.masks[i] ? (const void*)pb.masks[i] : (const void*)(uintptr_t)256;
+  }
+  for (int k = 0; k < n; ++k) {
+    const VcCellPlan& p = pp.cells[k];
+    const bool again = p.final_w != p.cell_w || p.final_h != p.cell_h;
+    if (!p.present) continue;
+    fit = std::max(fit, (int64_t)p.fit_w * p.fit_h * 3);
+    cover = std::max(cover, (int64_t)p.cover_w * p.cover_h * 3);
+    pb.tmp_b = std::max(pb.tmp_b, tmp_for(ch[k], cw[k], p.fit_h, p.fit_w, VC_FILTER_LANCZOS));
+    pb.tmp_b = std::max(pb.tmp_b, tmp_for(p.fit_h, p.fit_w, p.cover_h, p.cover_w, VC_FILTER_BICUBIC));
+    if (again) {
+      cell = std::max(cell, (int64_t)p.cell_w * p.cell_h * 3);
+      fin = std::max(fin, (int64_t)p.final_w * p.final_h * 3);
+      pb.tmp_b = std::max(pb.tmp_b, tmp_for(p.cell_h, p.cell_w, p.final_h, p.final_w, VC_FILTER_BICUBIC));
+    }
+  }
+  pb.fit = (unsigned char*)c.bytes(fit);
+  pb.cover = (unsigned char*)c.bytes(cover);
+  pb.cell = (unsigned char*)c.bytes(cell);
+  pb.fin = (unsigned char*)c.bytes(fin);
+  pb.tmp = c.bytes(pb.tmp_b);
+  *front = c.off;
+  return VC_OK;
+}
+
+}  // namespace
+
+int vc_grid_photos_workspace_bytes_impl(void* handle, const VcGridPhotos* job, int64_t* bytes, char* err, int errlen) {
+  HANDLE(Grid, g, "grid");
+  if (!bytes) FAIL(VC_ERR_ARG, "grid_photos_workspace_bytes: null result pointer");
+  PhotoPlan pp;
+  PhotoBufs pb;
+  int64_t front = 0, rest = 0;
+  TRY(plan_photos(job, nullptr, pp, pb, &front, e));
+  Geo q;
+  Bufs b;
+  TRY(geo_of(g, &pp.job, q, e));
+  TRY(carve(g, q, nullptr, b, &rest, err, errlen));
+  *bytes = front + rest;
+  return VC_OK;
+}
+
+int vc_grid_generate_photos_impl(void* handle, const VcGridPhotos* job, void* workspace, int64_t workspace_bytes, void* const* out_rows,
+                                 hipStream_t s, char* err, int errlen) {
+  HANDLE(Grid, g, "grid");
+  if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "grid_generate_photos: the workspace must be a 256-byte aligned device pointer");
+  PhotoPlan pp;
+  PhotoBufs pb;
+  int64_t front = 0;
+  TRY(plan_photos(job, (char*)workspace, pp, pb, &front, e));
+  if (workspace_bytes < front) FAIL(VC_ERR_ARG, "grid_generate_photos: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)front);
+  {                                              // everything vc_grid_generate would refuse, before the device is touched
+    Geo q;
+    Bufs b;
+    TRY(admit(g, &pp.job, pp.job.decode, (char*)workspace + front, workspace_bytes - front, out_rows, q, b, e, "grid_generate_photos"));
+  }
+  const int gh = job->grid_h, gw = job->grid_w;
+  for (int i = 0; i < gh; ++i) {
+    const int H = pp.job.height[i], W = pp.job.width[i];
+    int x0 = 0;
+    for (int k = 0; k < gw; ++k) {
+      const int c = i * gw + k;
+      const VcCellPlan& p = pp.cells[c];
+      if (!p.present) {                          // :339-344 a black cell, to be generated
+        TRY(vc_pixels_in_launch(nullptr, 0, 0, 0, 0, pb.rows[i], 0, H, W, x0, p.final_w, s, err, errlen));
+      } else {
+        // :316,325 LANCZOS to the fitted size, :327-331 bicubic to cover the row's reference size, centre crop
+        TRY(vc_resample_u8_launch(job->images[c], job->height[c], job->width[c], pb.fit, p.fit_h, p.fit_w, VC_FILTER_LANCZOS, pb.tmp, pb.tmp_b, s, err, errlen));
+        TRY(vc_resample_u8_launch(pb.fit, p.fit_h, p.fit_w, pb.cover, p.cover_h, p.cover_w, VC_FILTER_BICUBIC, pb.tmp, pb.tmp_b, s, err, errlen));
+        if (p.final_w == p.cell_w && p.final_h == p.cell_h) {
+          TRY(vc_pixels_in_launch(pb.cover, p.cover_h, p.cover_w, p.crop_left, p.crop_top, pb.rows[i], 0, H, W, x0, p.final_w, s, err, errlen));
+        } else {                                 // :350-360 the cropped cell resized once more: the crop as bytes first (outside = 0)
+          HIP(hipMemsetAsync(pb.cell, 0, (size_t)p.cell_w * p.cell_h * 3, s), "hipMemsetAsync(cell)");
+          const int sx = std::max(p.crop_left, 0), sy = std::max(p.crop_top, 0), dx = std::max(-p.crop_left, 0), dy = std::max(-p.crop_top, 0);
+          const int cw_ = std::min(p.cover_w - sx, p.cell_w - dx), ch_ = std::min(p.cover_h - sy, p.cell_h - dy);
+          if (cw_ > 0 && ch_ > 0)
+            HIP(hipMemcpy2DAsync(pb.cell + ((size_t)dy * p.cell_w + dx) * 3, (size_t)p.cell_w * 3, pb.cover + ((size_t)sy * p.cover_w + sx) * 3,
+                                 (size_t)p.cover_w * 3, (size_t)cw_ * 3, (size_t)ch_, hipMemcpyDeviceToDevice, s), "hipMemcpy2DAsync(crop)");
+          TRY(vc_resample_u8_launch(pb.cell, p.cell_h, p.cell_w, pb.fin, p.final_h, p.final_w, VC_FILTER_BICUBIC, pb.tmp, pb.tmp_b, s, err, errlen));
+          TRY(vc_pixels_in_launch(pb.fin, p.final_h, p.final_w, 0, 0, pb.rows[i], 0, H, W, x0, p.final_w, s, err, errlen));
+        }
+      }
+      TRY(vc_mask_fill_launch(pb.masks[i], H, W, x0, p.final_w, p.mask, s, err, errlen));   // :369-374
+      x0 += p.final_w;
+    }
+  }
+  return vc_grid_generate_impl(handle, &pp.job, (char*)workspace + front, workspace_bytes - front, out_rows, s, err, errlen);
+}
+
+namespace {
+
+struct U8Bufs {
+  bf16_t* px[VC_GRID_MAX_ROWS] = {};
+  unsigned char* resized = nullptr;
+  char* tmp = nullptr;
+  int64_t tmp_b = 0;
+};
+
+int plan_u8(const VcGridSdeditU8* job, char* base, VcGridSdedit& j, U8Bufs& ub, int64_t* front, Err e) {
+  if (!job) FAIL(VC_ERR_ARG, "grid_sdedit_u8: null job");
+  if (job->count < 1 || job->count > VC_GRID_MAX_ROWS) FAIL(VC_ERR_ARG, "grid_sdedit_u8: count = %d outside 1..%d", job->count, VC_GRID_MAX_ROWS);
+  if (job->cell_h < 1 || job->cell_w < 1 || job->cell_h > 65535 || job->cell_w > 65535)
+    FAIL(VC_ERR_ARG, "grid_sdedit_u8: cells of %dx%d pixels, sizes in 1..65535 expected", job->cell_h, job->cell_w);
+  const int H = job->height, W = job->width;
+  if (H <= 0 || W <= 0 || H % 16 || W % 16 || H >= 65536 || W >= 65536)
+    FAIL(VC_ERR_ARG, "grid_sdedit_u8: the target is %dx%d pixels, positive multiples of 16 below 65536 expected", H, W);
+  if (!(job->strength >= 0.0) || !(job->strength - job->strength == 0.0)) FAIL(VC_ERR_ARG, "grid_sdedit_u8: strength must be finite and not negative");
+  if (job->strength >= 1.0 && job->out_form != VC_PIXELS_U8)
+    FAIL(VC_ERR_ARG, "grid_sdedit_u8: strength >= 1 returns the resized 8-bit images: out_form must be VC_PIXELS_U8");
+  for (int k = 0; k < job->count; ++k)
+    if (!job->pixels[k]) FAIL(VC_ERR_ARG, "grid_sdedit_u8: null pixels of cell %d", k);
+  memset(&j, 0, sizeof(j));
+  j.count = job->count; j.height = H; j.width = W;
+  j.t5_ids = job->t5_ids; j.clip_ids = job->clip_ids; j.t5_len = job->t5_len; j.clip_len = job->clip_len;
+  j.seed = job->seed; j.noise_offset = job->noise_offset; j.noise_offset_out = job->noise_offset_out;
+  j.guidance = job->guidance; j.n_points = job->n_points; j.method = job->method; j.out_form = job->out_form; j.max_evals = job->max_evals;
+  j.strength = job->strength;
+  Carver c{base};
+  ub = U8Bufs{};
+  for (int k = 0; k < job->count; ++k) {
+    ub.px[k] = c.take<bf16_t>((int64_t)3 * H * W);
+    j.pixels[k] = ub.px[k] ? (const void*)ub.px[k] : (const void*)(uintptr_t)256;
+  }
+  ub.resized = (unsigned char*)c.bytes((int64_t)3 * H * W);
+  ub.tmp_b = tmp_for(job->cell_h, job->cell_w, H, W, VC_FILTER_BICUBIC);
+  ub.tmp = c.bytes(ub.tmp_b);
+  *front = c.off;
+  return VC_OK;
+}
+
+}  // namespace
+
+int vc_grid_sdedit_u8_workspace_bytes_impl(void* handle, const VcGridSdeditU8* job, int64_t* bytes, char* err, int errlen) {
+  HANDLE(Grid, g, "grid");
+  if (!bytes) FAIL(VC_ERR_ARG, "grid_sdedit_u8_workspace_bytes: null result pointer");
+  VcGridSdedit j;
+  U8Bufs ub;
+  int64_t front = 0, rest = 0;
+  TRY(plan_u8(job, nullptr, j, ub, &front, e));
+  Geo q;
+  Bufs b;
+  TRY(geo_of(g, &j, q, e));
+  TRY(carve(g, q, nullptr, b, &rest, err, errlen));
+  *bytes = front + rest;
+  return VC_OK;
+}
+
+int vc_grid_sdedit_u8_impl(void* handle, const VcGridSdeditU8* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
+                           hipStream_t s, char* err, int errlen) {
+  HANDLE(Grid, g, "grid");
+  if (!aligned256(workspace)) FAIL(VC_ERR_ARG, "grid_sdedit_u8: the workspace must be a 256-byte aligned device pointer");
+  VcGridSdedit j;
+  U8Bufs ub;
+  int64_t front = 0;
+  TRY(plan_u8(job, (char*)workspace, j, ub, &front, e));
+  if (workspace_bytes < front) FAIL(VC_ERR_ARG, "grid_sdedit_u8: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)front);
+  {
+    Geo q;
+    Bufs b;
+    TRY(admit(g, &j, nullptr, (char*)workspace + front, workspace_bytes - front, out_images, q, b, e, "grid_sdedit_u8"));
+  }
+  const int H = j.height, W = j.width;
+  if (job->strength >= 1.0) {                    // visualcloze.py:180-182: the resized image goes back as it is
+    for (int k = 0; k < j.count; ++k)
+      TRY(vc_resample_u8_launch(job->pixels[k], job->cell_h, job->cell_w, out_images[k], H, W, VC_FILTER_BICUBIC, ub.tmp, ub.tmp_b, s, err, errlen));
+    if (job->noise_offset_out) *job->noise_offset_out = job->noise_offset;
+    return VC_OK;
+  }
+  for (int k = 0; k < j.count; ++k) {            // :180 Image.resize (bicubic), then ToTensor / Normalize
+    TRY(vc_resample_u8_launch(job->pixels[k], job->cell_h, job->cell_w, ub.resized, H, W, VC_FILTER_BICUBIC, ub.tmp, ub.tmp_b, s, err, errlen));
+    TRY(vc_pixels_in_launch(ub.resized, H, W, 0, 0, ub.px[k], 0, H, W, 0, W, s, err, errlen));
+  }
+  return vc_grid_sdedit_impl(handle, &j, (char*)workspace + front, workspace_bytes - front, out_images, s, err, errlen);
 }

@@ -4,6 +4,9 @@
 // written out, where torch's own kernel fuses.
 #include "vcloze_internal.h"
 #include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -84,5 +87,142 @@ int vc_grid_img_ids_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_
         *p++ = (float)y;
         *p++ = (float)x;
       }
+  return VC_OK;
+}
+
+// ---- the photo front end's size rules (include/vcloze_hip.h: vc_fit_size, vc_grid_layout, vc_upsampling_size): Python's float and
+// integer arithmetic of visualcloze.py:28-75,298-360,166-180 restated - doubles, truncation by (int), floor division where Python floors
+namespace {
+int floordiv2(int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); }
+bool side_ok(int v) { return v >= 1 && v <= 65535; }
+void fit_size(int w, int h, int resolution, int* nw, int* nh) {
+#pragma clang fp contract(off)
+  const double ar = (double)w / (double)h;
+  const double area = (double)resolution * (double)resolution;
+  const int new_h = (int)pow(area / ar, 0.5);
+  const int new_w = (int)((double)new_h * ar);
+  *nw = std::max(new_w / 16, 1) * 16;
+  *nh = std::max(new_h / 16, 1) * 16;
+}
+}  // namespace
+
+int vc_fit_size_impl(int32_t w, int32_t h, int32_t resolution, int32_t* nw, int32_t* nh, char* err, int errlen) {
+  if (!nw || !nh) { snprintf(err, errlen, "fit_size: null result pointer"); return VC_ERR_ARG; }
+  if (!side_ok(w) || !side_ok(h) || !side_ok(resolution)) {
+    snprintf(err, errlen, "fit_size: size %dx%d and resolution %d must lie in 1..65535", w, h, resolution);
+    return VC_ERR_ARG;
+  }
+  int a, b;
+  fit_size(w, h, resolution, &a, &b);
+  if (!side_ok(a) || !side_ok(b)) { snprintf(err, errlen, "fit_size: %dx%d at resolution %d gives %dx%d, outside 1..65535", w, h, resolution, a, b); return VC_ERR_ARG; }
+  *nw = a;
+  *nh = b;
+  return VC_OK;
+}
+
+int vc_grid_layout_impl(int32_t grid_h, int32_t grid_w, const int32_t* cell_w, const int32_t* cell_h, int32_t resolution, VcCellPlan* out,
+                        char* err, int errlen) {
+#pragma clang fp contract(off)
+  if (!cell_w || !cell_h || !out) { snprintf(err, errlen, "grid_layout: null pointer"); return VC_ERR_ARG; }
+  if (grid_h < 1 || grid_h > VC_GRID_MAX_ROWS || grid_w < 1 || grid_w > VC_GRID_MAX_ROWS) {
+    snprintf(err, errlen, "grid_layout: a grid of %dx%d cells, 1..%d rows and columns expected", grid_h, grid_w, VC_GRID_MAX_ROWS);
+    return VC_ERR_ARG;
+  }
+  if (!side_ok(resolution)) { snprintf(err, errlen, "grid_layout: resolution %d must lie in 1..65535", resolution); return VC_ERR_ARG; }
+  const int n = grid_h * grid_w;
+  for (int c = 0; c < n; ++c) {
+    const bool absent = cell_w[c] == 0 && cell_h[c] == 0;
+    if (!absent && (!side_ok(cell_w[c]) || !side_ok(cell_h[c]))) {
+      snprintf(err, errlen, "grid_layout: cell %d is %dx%d, sizes in 1..65535 or 0x0 for an absent image expected", c, cell_w[c], cell_h[c]);
+      return VC_ERR_ARG;
+    }
+    if (absent && c < n - grid_w) { snprintf(err, errlen, "grid_layout: cell %d is absent: every image of the in-context rows is needed", c); return VC_ERR_ARG; }
+  }
+  std::vector<VcCellPlan> plan((size_t)n);
+  int target_w = 0, masked = 0;
+  for (int i = 0; i < grid_h; ++i) {
+    int ref_w = 0, ref_h = 0;
+    for (int j = 0; j < grid_w && !ref_w; ++j)
+      if (cell_w[i * grid_w + j]) fit_size(cell_w[i * grid_w + j], cell_h[i * grid_w + j], resolution, &ref_w, &ref_h);
+    if (i == grid_h - 1) target_w = ref_w;
+    for (int j = 0; j < grid_w; ++j) {
+      const int c = i * grid_w + j;
+      VcCellPlan p;
+      memset(&p, 0, sizeof(p));
+      if (cell_w[c]) {
+        p.present = 1;
+        fit_size(cell_w[c], cell_h[c], resolution, &p.fit_w, &p.fit_h);
+        if (p.fit_w <= p.fit_h) {
+          p.cover_w = ref_w;
+          p.cover_h = (int)((double)ref_w / (double)p.fit_w * (double)p.fit_h);
+        } else {
+          p.cover_w = (int)((double)ref_h / (double)p.fit_h * (double)p.fit_w);
+          p.cover_h = ref_h;
+        }
+        p.crop_left = floordiv2(p.cover_w - ref_w);
+        p.crop_top = floordiv2(p.cover_h - ref_h);
+        p.cell_w = ref_w;
+        p.cell_h = ref_h;
+        if (!side_ok(p.fit_w) || !side_ok(p.fit_h) || !side_ok(p.cover_w) || !side_ok(p.cover_h)) {
+          snprintf(err, errlen, "grid_layout: cell %d resizes to %dx%d, then %dx%d: outside 1..65535", c, p.fit_w, p.fit_h, p.cover_w, p.cover_h);
+          return VC_ERR_ARG;
+        }
+      } else {
+        p.cell_w = ref_w ? ref_w : resolution;
+        p.cell_h = ref_w ? ref_h : resolution;
+        p.mask = 1;
+        ++masked;
+      }
+      p.final_w = p.cell_w;
+      p.final_h = p.cell_h;
+      plan[c] = p;
+    }
+  }
+  if (grid_w > 1 && masked > 1) {                 // the second pass over EVERY cell, new_w running from cell to cell
+    int new_w = target_w ? target_w : 384;
+    for (int c = 0; c < n; ++c) {
+      int new_h = (int)((double)plan[c].cell_h * ((double)new_w / (double)plan[c].cell_w));
+      new_w = (int)((double)new_w / 16.0) * 16;
+      new_h = (int)((double)new_h / 16.0) * 16;
+      if (!side_ok(new_w) || !side_ok(new_h)) {
+        snprintf(err, errlen, "grid_layout: the second pass resizes cell %d to %dx%d: outside 1..65535", c, new_w, new_h);
+        return VC_ERR_ARG;
+      }
+      plan[c].final_w = new_w;
+      plan[c].final_h = new_h;
+    }
+  }
+  // A row is ONE tensor: its cells must agree in height (the reference's torch.cat fails otherwise) - and in width, because the
+  // reference sizes every cell's mask by the row's FIRST cell (:369-371), so with unequal widths its mask would not fit its row.
+  // Neither can happen with the rules above as they stand (new_w is a multiple of 16 from the first cell on); the check guards them.
+  for (int i = 0; i < grid_h; ++i)
+    for (int j = 1; j < grid_w; ++j) {
+      const VcCellPlan &a = plan[i * grid_w], &b = plan[i * grid_w + j];
+      if (a.final_h != b.final_h || a.final_w != b.final_w) {
+        snprintf(err, errlen, "grid_layout: row %d holds cells of %dx%d and %dx%d: they do not make one row tensor", i, a.final_w, a.final_h, b.final_w, b.final_h);
+        return VC_ERR_ARG;
+      }
+    }
+  memcpy(out, plan.data(), (size_t)n * sizeof(VcCellPlan));
+  return VC_OK;
+}
+
+int vc_upsampling_size_impl(int32_t orig_w, int32_t orig_h, int32_t* w, int32_t* h, char* err, int errlen) {
+#pragma clang fp contract(off)
+  if (!w || !h) { snprintf(err, errlen, "upsampling_size: null result pointer"); return VC_ERR_ARG; }
+  const bool none = orig_w == 0 && orig_h == 0;
+  if (!none && (!side_ok(orig_w) || !side_ok(orig_h))) {
+    snprintf(err, errlen, "upsampling_size: size %dx%d, sizes in 1..65535 or 0x0 for none expected", orig_w, orig_h);
+    return VC_ERR_ARG;
+  }
+  int tw = none ? 1024 : orig_w, th = none ? 1024 : orig_h;
+  if ((int64_t)tw * th > 1024 * 1024) {
+    const double ar = (double)tw / (double)th;
+    const int new_h = (int)pow((double)(1024 * 1024) / ar, 0.5);
+    tw = (int)((double)new_h * ar);
+    th = new_h;
+  }
+  *w = tw / 16 * 16;
+  *h = th / 16 * 16;
   return VC_OK;
 }

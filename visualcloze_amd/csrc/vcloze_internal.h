@@ -104,7 +104,20 @@ int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int co
                            int errlen);
 int vc_pixels_out_launch(const void* img, int img_is_f32, int H, int W, int x0, int w, void* out, int out_form, hipStream_t s, char* err,
                          int errlen);
+// resample.hip, pixels_in.hip: the photo front end's kernels
+int vc_resample_kmax_impl(int in, int out, int filter, char* err, int errlen);
+int vc_resample_coeffs_impl(int in, int out, int filter, int32_t* xmin, int32_t* len, int32_t* ki, int kmax, char* err, int errlen);
+int64_t vc_resample_tmp_bytes_impl(int H, int W, int h, int w, int filter, char* err, int errlen);
+int vc_resample_u8_launch(const void* src, int H, int W, void* dst, int h, int w, int filter, void* tmp, int64_t tmp_bytes, hipStream_t s,
+                          char* err, int errlen);
+int vc_pixels_in_launch(const void* src, int H, int W, int left, int top, void* out, int out_is_f32, int h, int Wrow, int x0, int w,
+                        hipStream_t s, char* err, int errlen);
+int vc_mask_fill_launch(void* mask, int h, int Wrow, int x0, int w, int value, hipStream_t s, char* err, int errlen);
 // grid_rules.hip: the host rules of one grid (no device)
+int vc_fit_size_impl(int32_t w, int32_t h, int32_t resolution, int32_t* nw, int32_t* nh, char* err, int errlen);
+int vc_grid_layout_impl(int32_t grid_h, int32_t grid_w, const int32_t* cell_w, const int32_t* cell_h, int32_t resolution, VcCellPlan* out,
+                        char* err, int errlen);
+int vc_upsampling_size_impl(int32_t orig_w, int32_t orig_h, int32_t* w, int32_t* h, char* err, int errlen);
 int vc_time_grid_impl(int32_t n_points, int32_t n_tokens, double t0, double t1, int32_t do_shift, double time_shifting_factor, float* out,
                       char* err, int errlen);
 int64_t vc_grid_tokens_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, char* err, int errlen);
@@ -173,3 +186,9 @@ int vc_grid_generate_impl(void* handle, const VcGridJob* job, void* workspace, i
                           char* err, int errlen);
 int vc_grid_sdedit_impl(void* handle, const VcGridSdedit* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
                         hipStream_t s, char* err, int errlen);
+int vc_grid_photos_workspace_bytes_impl(void* handle, const VcGridPhotos* job, int64_t* bytes, char* err, int errlen);
+int vc_grid_sdedit_u8_workspace_bytes_impl(void* handle, const VcGridSdeditU8* job, int64_t* bytes, char* err, int errlen);
+int vc_grid_generate_photos_impl(void* handle, const VcGridPhotos* job, void* workspace, int64_t workspace_bytes, void* const* out_rows,
+                                 hipStream_t s, char* err, int errlen);
+int vc_grid_sdedit_u8_impl(void* handle, const VcGridSdeditU8* job, void* workspace, int64_t workspace_bytes, void* const* out_images,
+                           hipStream_t s, char* err, int errlen);

@@ -748,3 +748,72 @@ class GridHandle(_Handle):
         job.out_form, job.max_evals, job.strength = hip.PIXELS_U8 if uint8 else hip.PIXELS_F32, int(max_evals), float(strength)
         L = hip.lib()
         return self._run(L.vc_grid_sdedit, "vc_grid_sdedit", job, L.vc_grid_sdedit_workspace_bytes, [tuple(p.shape) for p in px], uint8, stream)
+
+    @staticmethod
+    def _u8(t: torch.Tensor, dev, what: str) -> torch.Tensor:
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.device != dev:
+            raise hip.VclozeHipError(f"GridHandle.{what}: [H, W, 3] uint8 images on {dev} expected, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    def generate_photos(self, images: Sequence[Sequence[Optional[torch.Tensor]]], resolution: int, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
+                        seed: int, noise_offset: int = 0, cfg: float = 30.0, steps: int = 30, solver="euler", time_shifting_factor=1,
+                        decode_rows: Optional[Sequence[int]] = None, uint8: bool = False, max_evals: int = 0, stream=0):
+        """vc_grid_generate_photos: images[i][j] the photograph of row i, column j as a device uint8 [H, W, 3] tensor, or None where it
+        is absent (last row only: the cell to generate).  The layout rule, the LANCZOS / bicubic resamples, the centre crop,
+        ToTensor / Normalize and the masks run on the device, then `generate`'s path.  Returns what `generate` returns."""
+        R = len(images)
+        gw = len(images[0]) if R else 0
+        if not 1 <= R <= hip.GRID_MAX_ROWS or not 1 <= gw <= hip.GRID_MAX_ROWS or any(len(r) != gw for r in images):
+            raise hip.VclozeHipError(f"GridHandle.generate_photos: 1..{hip.GRID_MAX_ROWS} rows of equally many cells expected")
+        flat = [None if t is None else self._u8(t, self.dev, "generate_photos") for r in images for t in r]
+        plans = hip.grid_layout([[None if t is None else (t.shape[1], t.shape[0]) for t in r] for r in images], resolution)
+        want = set(range(R)) if decode_rows is None else {int(i) for i in decode_rows}
+        if not want <= set(range(R)):
+            raise hip.VclozeHipError(f"GridHandle.generate_photos: decode_rows {sorted(want)} outside the {R} rows")
+        t5a, clipa = self._ids(t5_ids, "t5_ids"), self._ids(clip_ids, "clip_ids")
+        n = R * gw
+        ptrs = (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in flat])
+        ws = (C.c_int32 * n)(*[0 if t is None else t.shape[1] for t in flat])
+        hs = (C.c_int32 * n)(*[0 if t is None else t.shape[0] for t in flat])
+        job = hip.GridPhotos()
+        job.grid_h, job.grid_w, job.resolution = R, gw, int(resolution)
+        job.images, job.width, job.height = ptrs, ws, hs
+        for i in range(R):
+            job.decode[i] = int(i in want)
+        job.t5_ids, job.clip_ids, job.t5_len, job.clip_len = _ip(t5a), _ip(clipa), t5a.size, clipa.size
+        job.seed, job.noise_offset = hip._u64(seed, "seed"), hip._u64(noise_offset, "noise_offset")
+        job.guidance, job.n_points, job.method = float(cfg), int(steps), FluxHandle._method(solver)
+        job.out_form, job.max_evals = hip.PIXELS_U8 if uint8 else hip.PIXELS_F32, int(max_evals)
+        job.time_shifting_factor = float(time_shifting_factor or 0.0)
+        shapes = [(3, plans[i][0].final_h, sum(c.final_w for c in plans[i])) if i in want else None for i in range(R)]
+        L = hip.lib()
+        outs, after = self._run(L.vc_grid_generate_photos, "vc_grid_generate_photos", job, L.vc_grid_photos_workspace_bytes, shapes, uint8, stream)
+        if decode_rows is not None:
+            by_row = dict(zip(sorted(want), outs))
+            outs = [by_row[int(i)] for i in decode_rows]
+        return outs, after
+
+    def sdedit_u8(self, cells: Sequence[torch.Tensor], size, t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, noise_offset: int = 0,
+                  cfg: float = 30.0, steps: int = 10, strength: float = 0.4, solver="euler", uint8: bool = False, max_evals: int = 0, stream=0):
+        """vc_grid_sdedit_u8: K device uint8 cells [h, w, 3] of ONE size - what `hip.pixels_out(..., uint8=True)` writes - resized
+        (bicubic, Pillow's bytes) to size = (w, h) = `hip.upsampling_size(...)` on the device, then `sdedit`'s path.  strength >= 1
+        returns the resized uint8 images (needs `uint8`).  Returns what `sdedit` returns."""
+        K = len(cells)
+        if not 1 <= K <= hip.GRID_MAX_ROWS:
+            raise hip.VclozeHipError(f"GridHandle.sdedit_u8: 1..{hip.GRID_MAX_ROWS} cells expected, got {K}")
+        px = [self._u8(t, self.dev, "sdedit_u8") for t in cells]
+        if any(p.shape != px[0].shape for p in px):
+            raise hip.VclozeHipError("GridHandle.sdedit_u8: all cells must share one size")
+        t5a, clipa = self._ids(t5_ids, "t5_ids"), self._ids(clip_ids, "clip_ids")
+        job = hip.GridSdeditU8()
+        job.count, job.cell_h, job.cell_w = K, px[0].shape[0], px[0].shape[1]
+        job.width, job.height = int(size[0]), int(size[1])
+        for k in range(K):
+            job.pixels[k] = px[k].data_ptr()
+        job.t5_ids, job.clip_ids, job.t5_len, job.clip_len = _ip(t5a), _ip(clipa), t5a.size, clipa.size
+        job.seed, job.noise_offset = hip._u64(seed, "seed"), hip._u64(noise_offset, "noise_offset")
+        job.guidance, job.n_points, job.method = float(cfg), int(steps), FluxHandle._method(solver)
+        job.out_form, job.max_evals, job.strength = hip.PIXELS_U8 if uint8 else hip.PIXELS_F32, int(max_evals), float(strength)
+        L = hip.lib()
+        return self._run(L.vc_grid_sdedit_u8, "vc_grid_sdedit_u8", job, L.vc_grid_sdedit_u8_workspace_bytes,
+                         [(3, job.height, job.width)] * K, uint8, stream)

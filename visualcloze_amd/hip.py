@@ -145,6 +145,35 @@ class GridSdedit(C.Structure):
                 ("out_form", C.c_int32), ("max_evals", C.c_int32), ("_pad", C.c_int32), ("strength", C.c_double)]
 
 
+FILTER_BICUBIC, FILTER_LANCZOS = 0, 1                       # VC_FILTER_* (vc_resample_u8)
+FILTERS = {"bicubic": FILTER_BICUBIC, "lanczos": FILTER_LANCZOS}
+
+
+class CellPlan(C.Structure):
+    """VcCellPlan of include/vcloze_hip.h: what vc_grid_layout says about one cell."""
+    _fields_ = [(n, C.c_int32) for n in ("present", "fit_w", "fit_h", "cover_w", "cover_h", "crop_left", "crop_top", "cell_w", "cell_h",
+                                         "final_w", "final_h", "mask")]
+
+
+class GridPhotos(C.Structure):
+    """VcGridPhotos of include/vcloze_hip.h."""
+    _fields_ = [("grid_h", C.c_int32), ("grid_w", C.c_int32), ("resolution", C.c_int32), ("out_form", C.c_int32),
+                ("images", C.POINTER(C.c_void_p)), ("width", C.POINTER(C.c_int32)), ("height", C.POINTER(C.c_int32)),
+                ("decode", C.c_int32 * GRID_MAX_ROWS), ("t5_ids", C.POINTER(C.c_int32)), ("clip_ids", C.POINTER(C.c_int32)),
+                ("t5_len", C.c_int32), ("clip_len", C.c_int32), ("seed", C.c_uint64), ("noise_offset", C.c_uint64),
+                ("noise_offset_out", C.POINTER(C.c_uint64)), ("guidance", C.c_float), ("n_points", C.c_int32), ("method", C.c_int32),
+                ("max_evals", C.c_int32), ("time_shifting_factor", C.c_double)]
+
+
+class GridSdeditU8(C.Structure):
+    """VcGridSdeditU8 of include/vcloze_hip.h."""
+    _fields_ = [("count", C.c_int32), ("cell_h", C.c_int32), ("cell_w", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_form", C.c_int32), ("pixels", C.c_void_p * GRID_MAX_ROWS), ("t5_ids", C.POINTER(C.c_int32)),
+                ("clip_ids", C.POINTER(C.c_int32)), ("t5_len", C.c_int32), ("clip_len", C.c_int32), ("seed", C.c_uint64),
+                ("noise_offset", C.c_uint64), ("noise_offset_out", C.POINTER(C.c_uint64)), ("guidance", C.c_float), ("n_points", C.c_int32),
+                ("method", C.c_int32), ("max_evals", C.c_int32), ("strength", C.c_double)]
+
+
 # every symbol include/vcloze_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 class FluxLaunchClass(C.Structure):          # VcFluxLaunchClass (vc_flux_profile)
@@ -262,6 +291,20 @@ SYMBOLS = {
     "vc_grid_sdedit_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridSdedit), C.POINTER(_i64)]),
     "vc_grid_generate": (C.c_int, [_vp, C.POINTER(GridJob), _vp, _i64, C.POINTER(_vp), _vp]),
     "vc_grid_sdedit": (C.c_int, [_vp, C.POINTER(GridSdedit), _vp, _i64, C.POINTER(_vp), _vp]),
+    "vc_resample_kmax": (C.c_int, [_i32, _i32, _i32]),
+    "vc_resample_coeffs": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32]),
+    "vc_resample_tmp_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "vc_resample_u8": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "vc_pixels_in": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vc_mask_fill": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vc_fit_size": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_grid_layout": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(CellPlan)]),
+    "vc_upsampling_size": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_photo_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_grid_photos_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridPhotos), C.POINTER(_i64)]),
+    "vc_grid_sdedit_u8_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridSdeditU8), C.POINTER(_i64)]),
+    "vc_grid_generate_photos": (C.c_int, [_vp, C.POINTER(GridPhotos), _vp, _i64, C.POINTER(_vp), _vp]),
+    "vc_grid_sdedit_u8": (C.c_int, [_vp, C.POINTER(GridSdeditU8), _vp, _i64, C.POINTER(_vp), _vp]),
     "vc_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "vc_stream_destroy": (C.c_int, [_vp]),
     "vc_stream_sync": (C.c_int, [_vp]),
@@ -318,6 +361,9 @@ def lib() -> C.CDLL:
         l.vc_grid_struct_sizes(gsize)
         if list(gsize) != [C.sizeof(GridConfig), C.sizeof(GridJob), C.sizeof(GridSdedit)]:
             raise VclozeHipError(f"libvcloze_hip.so grid struct sizes {list(gsize)} differ from the ctypes mirrors - rebuild")
+        l.vc_photo_struct_sizes(gsize)
+        if list(gsize) != [C.sizeof(CellPlan), C.sizeof(GridPhotos), C.sizeof(GridSdeditU8)]:
+            raise VclozeHipError(f"libvcloze_hip.so photo struct sizes {list(gsize)} differ from the ctypes mirrors - rebuild")
         _lib = l
     return _lib
 
@@ -862,6 +908,105 @@ def pixels_out(img, x0: int = 0, w: Optional[int] = None, uint8: bool = False, o
     _check(lib().vc_pixels_out(img.data_ptr(), int(img.dtype == torch.float32), H, W, int(x0), int(w), out.data_ptr(),
                                PIXELS_U8 if uint8 else PIXELS_F32, stream if stream is not None else cur_stream()), "vc_pixels_out")
     return out
+
+
+# ---- the photo front end: resampling (csrc/resample.hip), pixels in (csrc/pixels_in.hip), the size rules (csrc/grid_rules.hip) ----
+def _filter(f) -> int:
+    if f in FILTERS:
+        return FILTERS[f]
+    if f in FILTERS.values():
+        return int(f)
+    raise VclozeHipError(f"unknown filter {f!r}: 'bicubic' or 'lanczos' expected")
+
+
+def resample_coeffs(n_in: int, n_out: int, filter="bicubic"):
+    """vc_resample_coeffs (host-only): the tables of one axis as int32 CPU tensors (xmin [out], len [out], ki [out, kmax])"""
+    f = _filter(filter)
+    kmax = lib().vc_resample_kmax(int(n_in), int(n_out), f)
+    _check(0 if kmax >= 0 else kmax, "vc_resample_kmax")
+    xmin, ln = torch.empty(n_out, dtype=torch.int32), torch.empty(n_out, dtype=torch.int32)
+    ki = torch.empty(n_out, kmax, dtype=torch.int32)
+    ip = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_int32))  # noqa: E731
+    _check(lib().vc_resample_coeffs(int(n_in), int(n_out), f, ip(xmin), ip(ln), ip(ki), kmax), "vc_resample_coeffs")
+    return xmin, ln, ki
+
+
+def resample_u8(img, size, filter="bicubic", out=None, stream=None):
+    """vc_resample_u8: img [H, W, 3] uint8 on the device resized to size = (w, h) - PIL's order - as [h, w, 3] uint8, byte for byte
+    what PIL.Image.resize gives with BICUBIC / LANCZOS."""
+    if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8 or not img.is_cuda or not img.is_contiguous():
+        raise VclozeHipError(f"resample_u8: a contiguous CUDA [H, W, 3] uint8 image expected, got {img.dtype} {tuple(img.shape)} on {img.device}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    w, h = int(size[0]), int(size[1])
+    f = _filter(filter)
+    need = lib().vc_resample_tmp_bytes(H, W, h, w, f)
+    _check(0 if need >= 0 else int(need), "vc_resample_tmp_bytes")
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=torch.uint8, device=img.device)
+    if tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != img.device:
+        raise VclozeHipError(f"resample_u8: out must be a contiguous uint8 tensor of shape {(h, w, 3)} on {img.device}")
+    tmp = torch.empty(need + 256, dtype=torch.uint8, device=img.device)
+    base = (tmp.data_ptr() + 255) & ~255
+    _check(lib().vc_resample_u8(img.data_ptr(), H, W, out.data_ptr(), h, w, f, base, need, stream if stream is not None else cur_stream()),
+           "vc_resample_u8")
+    return out
+
+
+def pixels_in(img, size, left: int = 0, top: int = 0, out=None, x0: int = 0, dtype=torch.bfloat16, stream=None):
+    """vc_pixels_in: the window of size = (w, h) at (left, top) of img [H, W, 3] uint8 (it may reach outside: 0 there; img None: the
+    blank cell) as ToTensor + Normalize(0.5, 0.5) give it, written to the columns [x0, x0 + w) of `out` [3, h, Wrow] (bf16 or f32;
+    None: a new [3, h, w] tensor of `dtype`).  Returns out."""
+    w, h = int(size[0]), int(size[1])
+    if img is not None and (img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8 or not img.is_cuda or not img.is_contiguous()):
+        raise VclozeHipError(f"pixels_in: a contiguous CUDA [H, W, 3] uint8 image expected, got {img.dtype} {tuple(img.shape)} on {img.device}")
+    if out is None:
+        out = torch.empty(3, max(h, 0), max(w, 0), dtype=dtype, device=img.device if img is not None else "cuda")
+    if out.dim() != 3 or out.shape[0] != 3 or out.shape[1] != h or out.dtype not in (torch.bfloat16, torch.float32) or not out.is_cuda \
+            or not out.is_contiguous():
+        raise VclozeHipError(f"pixels_in: out must be a contiguous CUDA [3, {h}, Wrow] bf16 / f32 tensor, got {out.dtype} {tuple(out.shape)}")
+    H, W = (int(img.shape[0]), int(img.shape[1])) if img is not None else (0, 0)
+    _check(lib().vc_pixels_in(None if img is None else img.data_ptr(), H, W, int(left), int(top), out.data_ptr(), int(out.dtype == torch.float32),
+                              h, int(out.shape[2]), int(x0), w, stream if stream is not None else cur_stream()), "vc_pixels_in")
+    return out
+
+
+def mask_fill(mask, x0: int, w: int, value: int, stream=None):
+    """vc_mask_fill: the columns [x0, x0 + w) of the bf16 pixel mask [h, Wrow] set to 0 or 1"""
+    if mask.dim() != 2 or mask.dtype != torch.bfloat16 or not mask.is_cuda or not mask.is_contiguous():
+        raise VclozeHipError(f"mask_fill: a contiguous CUDA [h, Wrow] bf16 mask expected, got {mask.dtype} {tuple(mask.shape)}")
+    _check(lib().vc_mask_fill(mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1]), int(x0), int(w), int(value),
+                              stream if stream is not None else cur_stream()), "vc_mask_fill")
+    return mask
+
+
+def fit_size(w: int, h: int, resolution: int):
+    """vc_fit_size (host-only): the (w, h) an image of w x h is fitted to at `resolution`"""
+    a, b = C.c_int32(), C.c_int32()
+    _check(lib().vc_fit_size(int(w), int(h), int(resolution), C.byref(a), C.byref(b)), "vc_fit_size")
+    return a.value, b.value
+
+
+def grid_layout(sizes, resolution: int):
+    """vc_grid_layout (host-only): sizes[i][j] = (w, h) of the image in row i, column j, or None where it is absent; returns the
+    CellPlan of every cell, rows of lists"""
+    gh, gw = len(sizes), len(sizes[0]) if sizes else 0
+    if any(len(r) != gw for r in sizes):
+        raise VclozeHipError("grid_layout: every row must hold the same number of cells")
+    flat = [c for r in sizes for c in r]
+    n = max(len(flat), 1)
+    ws = (C.c_int32 * n)(*[0 if c is None else int(c[0]) for c in flat])
+    hs = (C.c_int32 * n)(*[0 if c is None else int(c[1]) for c in flat])
+    out = (CellPlan * n)()
+    _check(lib().vc_grid_layout(gh, gw, ws, hs, int(resolution), out), "vc_grid_layout")
+    return [[out[i * gw + j] for j in range(gw)] for i in range(gh)]
+
+
+def upsampling_size(target_size):
+    """vc_upsampling_size (host-only): pipeline.upsampling_size - (w, h) or None in, (w, h) out"""
+    w, h = (0, 0) if target_size is None else (int(target_size[0]), int(target_size[1]))
+    a, b = C.c_int32(), C.c_int32()
+    _check(lib().vc_upsampling_size(w, h, C.byref(a), C.byref(b)), "vc_upsampling_size")
+    return a.value, b.value
 
 
 # ---- noise source (csrc/rng.hip): the library's own counter-based Gaussian stream, NOT torch's ----

@@ -7,8 +7,10 @@
 
 `generate_grid` chains the whole tensor path of `process_images` (visualcloze.py:363-434): VAE-encode the grid rows,
 pack latents + fill masks into `cond`, draw the per-row noise, encode the prompt with T5 / CLIP, run the fused sampler,
-unpack, VAE-decode and map to [0, 1].  Image loading / resizing (PIL) and tokenisation are host work and stay with the
-caller: inputs are row tensors in [-1, 1] and token ids.
+unpack, VAE-decode and map to [0, 1].  Image decoding, prefix stripping and tokenisation are host work and stay with the caller:
+inputs are row tensors in [-1, 1] and token ids.  `preprocess_grid` makes the row tensors from photographs - with PIL as the
+reference does, or with `device_resize=True` on the device (the library's resampler gives Pillow's bytes) - and the
+`device_resize` switch of the upsampling functions does the same for the resize between the stages.
 """
 from __future__ import annotations
 
@@ -239,6 +241,111 @@ def upsampling_size(target_size):
     return (target_size[0] // 16) * 16, (target_size[1] // 16) * 16
 
 
+def fit_size(w: int, h: int, resolution: int):
+    """The size rule of `resize_with_aspect_ratio` (visualcloze.py:52-60): about resolution^2 pixels at the image's aspect ratio,
+    both sides multiples of 16.  (w, h) in, (w, h) out."""
+    aspect = w / h
+    new_h = int((resolution * resolution / aspect) ** 0.5)
+    new_w = int(new_h * aspect)
+    return max(new_w // 16, 1) * 16, max(new_h // 16, 1) * 16
+
+
+def _u8_tensor(image, dev=None) -> torch.Tensor:
+    """a PIL image, a [3, H, W] tensor in [0, 1] or a uint8 [H, W, 3] tensor as uint8 [H, W, 3] (on `dev` if given)"""
+    import numpy as np
+    if torch.is_tensor(image) and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3:
+        t = image
+    elif torch.is_tensor(image):
+        t = image.detach().float().mul(255).to(torch.uint8).permute(1, 2, 0)           # to_pil_image's truncation, :437-439
+    else:
+        t = torch.from_numpy(np.asarray(image.convert("RGB"), dtype=np.uint8).copy())
+    return t.contiguous() if dev is None else t.to(dev).contiguous()
+
+
+def preprocess_grid(images, resolution: int = 384, device_resize: bool = False, device="cuda"):
+    """The image half of `process_images` (visualcloze.py:298-374): images[i][j] the image of grid row i, column j - a PIL image or
+    decoded bytes as a uint8 [H, W, 3] tensor - or None for a cell to generate (last row only).  Every image is fitted to `resolution` (LANCZOS), resized to cover its row's reference
+    size (bicubic) and centre-cropped; an absent cell is black and masked; with more than one masked cell everything is resized
+    once more (:350-360).  Returns (row_images, row_masks) as `generate_grid` takes them: bf16 [3, H, W_row] in [-1, 1] and bf16
+    [1, 1, H, W_row] on `device`.  `device_resize=False`: PIL does the resizing, as the reference; True: only the decoded bytes go
+    to the device, and vc_grid_layout, vc_resample_u8, vc_pixels_in and vc_mask_fill do the rest there - the same bits."""
+    gh, gw = len(images), len(images[0])
+    if any(len(r) != gw for r in images):
+        raise ValueError("preprocess_grid: every row must hold the same number of cells")
+    if device_resize:
+        return _preprocess_grid_device([[None if im is None else _u8_tensor(im, device) for im in row] for row in images], resolution, device)
+    import numpy as np
+    from PIL import Image
+    images = [[None if im is None else Image.fromarray(im.cpu().numpy()) if torch.is_tensor(im) else im.convert("RGB") for im in row]
+              for row in images]
+    cells, mask_position, target_w = [], [], None
+    for i, row in enumerate(images):
+        first = next((im for im in row if im is not None), None)
+        ref = None if first is None else fit_size(first.width, first.height, resolution)
+        if i == gh - 1 and ref is not None:
+            target_w = ref[0]
+        for im in row:
+            if im is None:
+                if i != gh - 1:
+                    raise ValueError(f"preprocess_grid: row {i} lacks an image; only cells of the last row may be None")
+                cells.append(Image.new("RGB", ref if ref else (resolution, resolution), (0, 0, 0)))
+                mask_position.append(1)
+                continue
+            t = im.resize(fit_size(im.width, im.height, resolution), Image.LANCZOS)
+            if t.width <= t.height:
+                t = t.resize((ref[0], int(ref[0] / t.width * t.height)))
+            else:
+                t = t.resize((int(ref[1] / t.height * t.width), ref[1]))
+            left, top = (t.width - ref[0]) // 2, (t.height - ref[1]) // 2
+            cells.append(t.crop((left, top, left + ref[0], top + ref[1])))
+            if i == gh - 1:
+                mask_position.append(0)
+    if len(mask_position) > 1 and sum(mask_position) > 1:
+        width = 384 if target_w is None else target_w                                  # a running width, shared by all cells
+        for k, c in enumerate(cells):
+            height = int(c.height * (width / c.width))                                  # from the width BEFORE it is rounded
+            width, height = int(width / 16) * 16, int(height / 16) * 16
+            cells[k] = c.resize((width, height))
+    rows, masks = [], []
+    for i in range(gh):
+        px = [torch.from_numpy(np.asarray(c, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0) for c in cells[i * gw:(i + 1) * gw]]
+        px = [(p - 0.5) / 0.5 for p in px]                                             # ToTensor, Normalize(0.5, 0.5), :133-137
+        ms = [torch.full((1, 1, px[0].shape[1], px[0].shape[2]), float(m if i == gh - 1 else 0)) for m in mask_position]
+        rows.append(torch.cat(px, dim=2).to(device, torch.bfloat16))
+        masks.append(torch.cat(ms, dim=3).to(device, torch.bfloat16))
+    return rows, masks
+
+
+def _preprocess_grid_device(images, resolution: int, device):
+    """`images`: uint8 [H, W, 3] tensors on `device` or None"""
+    plans = hip.grid_layout([[None if im is None else (im.shape[1], im.shape[0]) for im in row] for row in images], resolution)
+    rows, masks = [], []
+    for row, plan in zip(images, plans):
+        H, W = plan[0].final_h, sum(p.final_w for p in plan)
+        out = torch.empty(3, H, W, dtype=torch.bfloat16, device=device)
+        mask = torch.empty(H, W, dtype=torch.bfloat16, device=device)
+        x0 = 0
+        for im, p in zip(row, plan):
+            if im is None:
+                hip.pixels_in(None, (p.final_w, H), out=out, x0=x0)
+            else:
+                t = hip.resample_u8(im, (p.fit_w, p.fit_h), "lanczos")
+                t = hip.resample_u8(t, (p.cover_w, p.cover_h), "bicubic")
+                if (p.final_w, p.final_h) == (p.cell_w, p.cell_h):
+                    hip.pixels_in(t, (p.cell_w, p.cell_h), p.crop_left, p.crop_top, out=out, x0=x0)
+                else:                                                                   # the crop as bytes (outside = 0), resized again
+                    cell = torch.zeros(p.cell_h, p.cell_w, 3, dtype=torch.uint8, device=device)
+                    sx, sy, dx, dy = max(p.crop_left, 0), max(p.crop_top, 0), max(-p.crop_left, 0), max(-p.crop_top, 0)
+                    cw, ch = min(p.cover_w - sx, p.cell_w - dx), min(p.cover_h - sy, p.cell_h - dy)
+                    cell[dy:dy + ch, dx:dx + cw] = t[sy:sy + ch, sx:sx + cw]
+                    hip.pixels_in(hip.resample_u8(cell, (p.final_w, p.final_h), "bicubic"), (p.final_w, p.final_h), out=out, x0=x0)
+            hip.mask_fill(mask, x0, p.final_w, p.mask)
+            x0 += p.final_w
+        rows.append(out)
+        masks.append(mask[None, None])
+    return rows, masks
+
+
 @torch.no_grad()
 def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
                    rng: Union[torch.Generator, NoiseStream], cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
@@ -274,23 +381,31 @@ def upsample_image(model, ae, t5, clip, image, target_size, t5_ids: torch.Tensor
 def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: torch.Tensor, clip_ids: torch.Tensor,
                     rng: Union[torch.Generator, NoiseStream], cfg: float = 30.0, steps: int = 10, strength: float = 0.4,
                     encode_noise: Optional[Sequence] = None, solver: str = "euler", step_cache=None,
-                    use_grid_handle: bool = False) -> List[torch.Tensor]:
+                    use_grid_handle: bool = False, device_resize: bool = False) -> List[torch.Tensor]:
     """`upsample_image` for several images of one grid in ONE batched SDEdit solve (`sdedit_upsample_batch`).  Host work
     (resize), the VAE encodes and every random draw happen per image in the reference's order - image k: encode(image),
     encode(blank), noise from `rng` (visualcloze.py:200-217) - so each target starts from exactly the state the
     one-at-a-time loop gives it; the prompt is encoded once (it is the same for every target, :458).  `use_grid_handle`: opt-in -
     everything behind the host resize as ONE call of the library's grid handle (vc_grid_sdedit), under the conditions of
-    `generate_grid`'s switch; the same bits."""
+    `generate_grid`'s switch; the same bits.  `device_resize`: opt-in, off by default - the bicubic resize runs on the device
+    (vc_resample_u8: Pillow's bytes, so the same bits again); the images may then also be uint8 [H, W, 3] tensors, and those on the
+    device never leave it with the grid handle on (vc_grid_sdedit_u8); without the handle only the PIL `resize` is replaced."""
     import numpy as np
     dev = next(ae.parameters()).device
     size = upsampling_size(target_size)
-    pxs = []
-    for image in images:
-        if torch.is_tensor(image):
-            image = to_uint8_image(image)
-        image = image.convert("RGB").resize(size)                                      # :179
-        pxs.append(torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0))
     gh = _grid_handle(model, ae, t5, clip, rng, "upsample_images", encode_noise=encode_noise) if use_grid_handle else None
+    pxs, cells = [], []
+    for image in images:
+        if device_resize:
+            cells.append(_u8_tensor(image, dev))
+            if gh is not None and strength < 1.0:
+                continue                                                               # resized inside vc_grid_sdedit_u8
+            arr = hip.resample_u8(cells[-1], size).cpu().numpy()
+        else:
+            if torch.is_tensor(image):
+                image = to_uint8_image(image)
+            arr = np.asarray(image.convert("RGB").resize(size), dtype=np.uint8).copy()  # :179
+        pxs.append(torch.from_numpy(arr).permute(2, 0, 1).float().div(255.0))
     if strength >= 1.0:
         return [px.to(dev) for px in pxs]                                              # :180-181
     if gh is not None:
@@ -298,6 +413,10 @@ def upsample_images(model, ae, t5, clip, images: Sequence, target_size, t5_ids: 
             raise ValueError(f"step_cache works with sampling_method='euler' only, not {solver!r}")
         gh.flux.set_step_cache(step_cache)
         gh.flux.set_cfg(None)
+        if device_resize:
+            out, rng.offset = gh.sdedit_u8(cells, size, t5_ids, clip_ids, rng.seed, rng.offset, cfg=cfg, steps=steps, strength=strength,
+                                           solver=solver)
+            return out
         out, rng.offset = gh.sdedit([((px - 0.5) / 0.5).to(dev, torch.bfloat16) for px in pxs], t5_ids, clip_ids, rng.seed, rng.offset,
                                     cfg=cfg, steps=steps, strength=strength, solver=solver)
         return out
@@ -324,7 +443,8 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
                           upsampling_steps: int = 10, upsampling_noise: float = 0.4, is_upsampling: bool = True,
                           encode_noise: Optional[List[torch.Tensor]] = None, upsample_encode_noise=None,
                           solver: str = "euler", time_shifting_factor=1, batch_targets: bool = True, step_cache=None,
-                          rng: Union[torch.Generator, NoiseStream, None] = None, use_grid_handle: bool = False):
+                          rng: Union[torch.Generator, NoiseStream, None] = None, use_grid_handle: bool = False,
+                          device_resize: bool = False):
     """Both stages of `process_images` chained (visualcloze.py:363-465): the grid is generated, its LAST row is decoded and
     quantised to 8 bits as `to_pil_image` does, every cell of that row whose `mask_position` is set is cropped
     (:452,461) and - with `is_upsampling` - refined by `upsample_image` at `target_size`, all noise coming from ONE
@@ -334,7 +454,10 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     torch.Generator seeded with `seed` - a `NoiseStream` puts every draw of both stages on the library's own stream, in the
     reference's order.  `use_grid_handle`: opt-in - both stages through the library's grid handle (vc_grid_generate, then vc_grid_sdedit
     per batch of targets; the crop and the resize between them stay here), under the conditions of `generate_grid`'s switch; the same
-    bits.  Returns the output images as [3, h, w] tensors in [0, 1]."""
+    bits.  `device_resize`: opt-in, off by default - the quantised last row stays on the device, its cells are cropped there and
+    resized by the library (`upsample_images(device_resize=True)`; with the grid handle: vc_grid_sdedit_u8), Pillow's bytes and so
+    the same bits; every masked cell then goes through `upsample_images`, one at a time where `batch_targets` is off.
+    Returns the output images as [3, h, w] tensors in [0, 1]."""
     if use_grid_handle:
         _grid_handle(model, ae, t5, clip, rng, "generate_and_upsample", encode_noise=encode_noise, upsample_encode_noise=upsample_encode_noise)
     dev = row_images[0].device
@@ -344,6 +467,11 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
     row = generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                         encode_noise=encode_noise, decode_rows=[last], solver=solver, time_shifting_factor=time_shifting_factor,
                         rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle)[0]
+    if device_resize:
+        return _upsample_cells_on_device(model, ae, t5, clip, _u8_tensor(row), grid_w, mask_position, target_size,
+                                         content_t5_ids if content_t5_ids is not None else t5_ids,
+                                         content_clip_ids if content_clip_ids is not None else clip_ids, rng, cfg, upsampling_steps,
+                                         upsampling_noise, is_upsampling, upsample_encode_noise, solver, batch_targets, step_cache, use_grid_handle)
     pil = to_uint8_image(row)                                                          # :437-439
     ret_w, ret_h = pil.width, pil.height
     cells = [pil.crop((i * ret_w // grid_w, 0, (i + 1) * ret_w // grid_w, ret_h)) for i, m in enumerate(mask_position) if m]   # :452,461
@@ -370,4 +498,21 @@ def generate_and_upsample(model, ae, t5, clip, row_images: List[torch.Tensor], r
             import numpy as np
             outs.append(torch.from_numpy(np.asarray(cell, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255.0).to(dev))
         k += 1
+    return outs
+
+
+def _upsample_cells_on_device(model, ae, t5, clip, row_u8, grid_w, mask_position, target_size, ct5, cclip, rng, cfg, steps, strength,
+                              is_upsampling, encode_noise, solver, batch_targets, step_cache, use_grid_handle):
+    """the second stage of `generate_and_upsample(device_resize=True)`: row_u8 [H, W, 3] uint8 on the device, the quantised last row"""
+    ret_w = row_u8.shape[1]
+    cells = [row_u8[:, i * ret_w // grid_w:(i + 1) * ret_w // grid_w].contiguous() for i, m in enumerate(mask_position) if m]    # :452,461
+    if not is_upsampling:
+        return [c.permute(2, 0, 1).cpu().float().div(255.0).to(row_u8.device) for c in cells]
+    kw = dict(cfg=cfg, steps=steps, strength=strength, solver=solver, step_cache=step_cache, use_grid_handle=use_grid_handle, device_resize=True)
+    if batch_targets and len(cells) > 1:
+        return upsample_images(model, ae, t5, clip, cells, target_size, ct5, cclip, rng, encode_noise=encode_noise, **kw)
+    outs = []
+    for k, cell in enumerate(cells):
+        outs += upsample_images(model, ae, t5, clip, [cell], target_size, ct5, cclip, rng,
+                                encode_noise=None if encode_noise is None else [encode_noise[k]], **kw)
     return outs
