@@ -294,6 +294,36 @@ int vc_solver_evals(int method);
  * 16-byte accesses need n % 8 == 0 and 16-byte aligned bases; anything else runs element-wise with the same results. */
 int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, const void* v, void* k, void* y_in,
                  const float* dts, const int32_t* eval_ptr, int64_t n, void* stream);
+/* ---- the adaptive Dormand-Prince 5(4) solve: what an error-controlled odeint runs between model evaluations.  Added WITHOUT a
+ * change of VC_ABI_VERSION: detect these entry points (vc_dopri5_stage, vc_dopri5_error_ratio, vc_dopri5_interp,
+ * vc_flux_sample_dopri5, vc_flux_dopri5_log) by SYMBOL - look up vc_dopri5_stage.  VC_SOLVER_* has no code for it and
+ * vc_solver_evals / vc_flux_sample_ode keep refusing anything but the fixed-grid methods.
+ * With f(t, y) = -model(bf16(y) || cond, 1 - f32(t)): every k is stored in bf16 (the model's output dtype), the state y is F32.  The
+ * tableau is SciPy's RK45.C / .A / .B / .E and torchdiffeq's DPS_C_MID (written out in csrc/dopri5.hip), each coefficient a double
+ * rounded once to f32; every sum runs left to right over the non-zero coefficients, one f32 operation after the other, no fused
+ * multiply-add, so a torch f32 expression of the same shape gives the same bits (transport.dopri5_integrate is that expression).
+ * The controller is torchdiffeq's as recalled, unpinned against real torchdiffeq (the package was not available to check against); it is
+ * pinned to SciPy in the tableau and in single steps only.
+ * stage: k [7][n] bf16; stage s = 0..6 stores k[s] = -v (v NULL: k[s] is in place already - k1 of a step is the last step's k7,
+ *        first same as last) and forms, for s <= 4, y_s = y0 + dt * (a_{s+2,1} k1 + .. + a_{s+2,s+1} k_{s+1}), the state of the NEXT
+ *        evaluation; s = 5 forms y1 = y0 + dt * (b1 k1 + .. + b6 k6); s = 6 only stores k7 = f(t1, y1).  stage 7 (v NULL) forms the
+ *        probe state y0 + dt * k1 of the initial step size.  stage < 0: *eval_ptr, the device-side evaluation counter, so one
+ *        captured launch serves every stage (a counter outside 0..7 writes nothing).  dt = *dt_ptr (device).  The formed state goes
+ *        to y_stage (F32) and, rounded, to y_in (bf16, what img_in reads); either may be NULL.  Buffers must not overlap.
+ * error_ratio: out[0] = sqrt(mean(q^2)) over ALL n elements, summed in f32 in a fixed order (two-pass block reduction, no atomics:
+ *        repeated runs give the same bits).  scratch: VC_DOPRI5_MAX_BLOCKS F32 of device memory.
+ *        mode 0: q = dt * (e1 k1 + .. + e7 k7) / (atol + rtol * max(|y0|, |y1|)), the error ratio of a step;
+ *        mode 1, 2, 3: q = a / (atol + rtol * |y0|) with a = y0, k1, k2 - k1 - the norms d0, d1 and h0 * d2 of the initial step size.
+ * interp: the dense output at theta in [0, 1] of the step t0 -> t0 + dt, the quartic through (y0, f0 = k1, y_mid, y1, f1 = k7) with
+ *        y_mid = y0 + dt * (DPS_C_MID . k), evaluated as torchdiffeq's _interp_fit / _interp_evaluate; theta = 0 and theta = 1 return
+ *        y0 and y1 themselves.  out: n values, bf16 (out_is_bf16, rounded once) or F32. */
+#define VC_DOPRI5_MAX_BLOCKS 256
+int vc_dopri5_stage(int32_t stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr, float* y_stage,
+                    void* y_in, int64_t n, void* stream);
+int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
+                          float* out, float* scratch, int64_t n, void* stream);
+int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
+                     int64_t n, void* stream);
 /* ---- the three elementwise passes of the first-block step cache (vc_flux_set_step_cache below; the rule is this library's own,
  * DESIGN.md section 4).  Added without a change of VC_ABI_VERSION, like the solver entry points: detect by SYMBOL (look up
  * vc_flux_set_step_cache).  bf16 storage, f32 math, 16-byte accesses: n, every sample stride a multiple of 8, bases 16-byte aligned
@@ -610,6 +640,37 @@ int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, 
                        int32_t state_is_bf16, void* trajectory, void* stream);
 int vc_flux_sample_begin_ode(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points,
                              int32_t state_is_bf16, void* stream);
+/* ---- the adaptive solve: Dormand-Prince 5(4) with step-size control around the same captured evaluation.  OPT-IN: set
+ * vc_flux_set_option(handle, "adaptive", 1) BEFORE vc_flux_workspace_bytes / vc_flux_prepare - it adds k [7], y0 and y1 (F32) and a
+ * few words to the workspace - and prepare with max_steps >= 7 (the modulation rows of one attempt: k1's row and six evaluations).
+ * With the option off nothing changes: the same graphs, workspace bytes and bits.  Detect by SYMBOL (look up vc_dopri5_stage).
+ * x [B, N, out_channels]: in = x(t_grid[0]), out = x(t_grid[n_points - 1]); trajectory: NULL or [n_points - 1][B][N][out_channels]
+ * receiving x(t_grid[1..]); both bf16 (state_is_bf16) or F32.  The controller is torchdiffeq's as recalled, unpinned against real
+ * torchdiffeq (see vc_dopri5_stage above for what is pinned to SciPy):
+ *   state   F32 inside whatever the caller's dtype: a bf16 state is widened on entry and rounded ONCE per output.  A departure:
+ *           torchdiffeq would carry a bf16 state in bf16, where rtol = 1e-3 lies below the format's resolution.
+ *   time    t and dt live on the host in double; the model sees 1 - f32(t).
+ *   first step (Hairer, order 4; two evaluations)  scale = atol + rtol |y0|, d0 = rms(y0 / scale), d1 = rms(f0 / scale),
+ *           h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 d0 / d1;  f1 = f(t0 + h0, y0 + h0 f0);  d2 = rms((f1 - f0) / scale) / h0;
+ *           h1 = max(1e-6, 1e-3 h0) if max(d1, d2) <= 1e-15 else (0.01 / max(d1, d2))^(1/5);  dt = min(100 h0, h1)
+ *   attempt the six stage times and dt go up, the modulation rows are refilled, the captured evaluation is replayed six times
+ *           (its last node is vc_dopri5_stage on the device-side counter), the error ratio is reduced and ONE stream
+ *           synchronisation reads its 4 bytes from pinned memory
+ *   decision  accept iff ratio <= 1;  dt_next = 10 dt if ratio == 0, else dt * min(10, max(0.9 / ratio^(1/5), ratio < 1 ? 1 : 0.2))
+ *   errors  a NaN ratio, t + dt == t, or more than max_attempts attempts: VC_ERR_STATE with a message; the handle stays usable
+ *   outputs steps are NOT clamped to the output times: a step runs past them and t_grid[1..] come from vc_dopri5_interp inside the
+ *           accepted step that covers them.  The last step may overshoot t_grid[n_points - 1], so the model may be evaluated at
+ *           timesteps = 1 - t < 0.
+ *   ONE step size is shared by all samples of the call (the norm runs over the whole [B, N, out_channels] state, as torchdiffeq's
+ *           does over its tensor): a sample's result depends on which samples share its call.
+ * True CFG (vc_flux_set_cfg: the solver steps both halves), the un-merged LoRA mode and taps work unchanged; the step cache on is
+ * VC_ERR_ARG.  Synchronises `stream` once per attempt (three more times for the first step).
+ * log: of the last vc_flux_sample_dopri5 - for attempt i < min(capacity, *attempts): t[i], dt[i] (double), ratio[i], accepted[i];
+ * *evaluations = every model evaluation it ran (2 + 6 per attempt).  Any array may be NULL. */
+int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                          float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream);
+int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                       int32_t* evaluations);
 
 /* ---- first-block step cache of the Euler loop: OPT-IN, off by default.  IT CHANGES RESULTS: a reused evaluation is an
  * approximation, not the model.  Its effect on image quality is unmeasured (only random-init weights were available) and no default

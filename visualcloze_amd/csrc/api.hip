@@ -108,6 +108,18 @@ int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, 
                  const float* dts, const int32_t* eval_ptr, int64_t n, void* stream) {
   return vc_ode_stage_launch(method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, S(stream), ERRBUF);
 }
+int vc_dopri5_stage(int32_t stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr, float* y_stage,
+                    void* y_in, int64_t n, void* stream) {
+  return vc_dopri5_stage_launch(stage, y0, k, v, dt_ptr, eval_ptr, y_stage, y_in, n, S(stream), ERRBUF);
+}
+int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
+                          float* out, float* scratch, int64_t n, void* stream) {
+  return vc_dopri5_error_ratio_launch(mode, y0, y1, k, dt_ptr, rtol, atol, out, scratch, n, S(stream), ERRBUF);
+}
+int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
+                     int64_t n, void* stream) {
+  return vc_dopri5_interp_launch(y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF);
+}
 int vc_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, void* stream) {
   return vc_cfg_combine_launch(cond, uncond, out, n, cfg_scale, S(stream), ERRBUF);
 }
@@ -256,6 +268,14 @@ int vc_flux_sample_ode(void* handle, int32_t method, void* x, const void* cond, 
   if (rc == VC_OK) rc = vc_flux_sample_steps_impl(handle, n_points - 1, trajectory, S(stream), ERRBUF);
   if (rc == VC_OK) rc = vc_flux_sample_end_impl(handle, x, S(stream), ERRBUF);
   return rc;
+}
+int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                          float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream) {
+  return vc_flux_sample_dopri5_impl(handle, x, cond, t_grid, n_points, state_is_bf16, rtol, atol, max_attempts, trajectory, S(stream), ERRBUF);
+}
+int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                       int32_t* evaluations) {
+  return vc_flux_dopri5_log_impl(handle, t, dt, ratio, accepted, capacity, attempts, evaluations, ERRBUF);
 }
 int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                          void* trajectory, void* stream) {

@@ -18,6 +18,8 @@
 //                           in place (cfg_combine_kernel, elementwise.hip); no buffer of its own
 //   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
+//   AD_K [7][B*N*out] / AD_Y0 / AD_Y1 (f32)  only with option adaptive 1, behind the step cache's: k1..k7, the state and the step's
+//                           end state of the adaptive solve (vc_flux_sample_dopri5, dopri5.hip), its dt, norms and reduction scratch
 //   LY / LY2 / LH / LSCALE  only in the un-merged LoRA mode (option lora_mode 1), behind everything else: base_out, base_out + lora
 //                           and lora_A(x) of the Linear being run, and the lora scale as a bf16 vector (the gate operand of the
 //                           gated-residual epilogue that adds the lora branch; refilled by vc_flux_set_lora_scale)
@@ -58,6 +60,8 @@ struct Buffers {   // the workspace carve-up
   bf16_t *LY = nullptr, *LY2 = nullptr, *LH = nullptr, *LSCALE = nullptr;   // un-merged LoRA mode (carved only while it is on)
   int64_t ly_elems = 0, lh_elems = 0, lscale_elems = 0;
   float *SC_PART = nullptr, *SC_METRIC = nullptr;
+  bf16_t* AD_K = nullptr;                                          // adaptive solve (carved only while option adaptive is on)
+  float *AD_Y0 = nullptr, *AD_Y1 = nullptr, *AD_DT = nullptr, *AD_OUT = nullptr, *AD_PART = nullptr;
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
   void* SK_WS = nullptr;               // f32 partial tiles of split-K GEMM remainders (VcGemmArgs.splitk_ws)
@@ -68,6 +72,7 @@ struct Buffers {   // the workspace carve-up
 struct Options {
   int attn_variant = -1, tile_cfg = 0, fuse_qnorm = 2, fuse_vt = 1, qkv_heads = 0, fuse_knorm = 0, logit_bound_milli = 0, mlp_first = 0, splitk = 1;
   int lora_mode = 0;
+  int adaptive = 0;
 };
 enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
 #define OPT(name, clamp) {#name, &Options::name, clamp}
@@ -77,6 +82,7 @@ constexpr struct { const char* name; int Options::*member; Clamp clamp; } OPTION
     OPT(fuse_knorm, BOOL),       OPT(logit_bound_milli, AT_LEAST_0),
     OPT(mlp_first, BOOL),        OPT(splitk, BOOL),              // split-K remainders (VcGemmArgs.splitk_ws) where the launcher's model takes them
     OPT(lora_mode, BOOL),                                        // 1: every Linear runs un-merged (lora_linear below)
+    OPT(adaptive, BOOL),                                         // 1: the workspace holds the adaptive solve's buffers (vc_flux_sample_dopri5)
 };
 #undef OPT
 inline bool operator==(const Options& a, const Options& b) {
@@ -152,6 +158,11 @@ struct Flux : Buffers {
   // trajectory from its sample_begin on (cfg_active, cfg_s)
   bool cfg_on = false, cfg_active = false;
   float cfg_scale = 1.0f, cfg_s = 1.0f;
+  // the adaptive solve (vc_flux_sample_dopri5): the pinned words its norms are read from, and the log of the last run
+  float* ad_host = nullptr;
+  struct Attempt { double t, dt; float ratio; int accepted; };
+  std::vector<Attempt> ad_log;
+  int ad_evals = 0;
   // host staging (pinned), reused once the copies that read it have completed
   char* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;
@@ -199,6 +210,11 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
   if (g.sc_on()) {    // behind everything else: with the cache off the carve-up and its size are what they always were
     f.SC_P = c.take<bf16_t>(B * N * D); f.SC_R = c.take<bf16_t>(B * N * D); f.SC_RS = c.take<bf16_t>(B * N * D);
     f.SC_PART = c.take<float>((int64_t)B * 2 * VC_RESIDUAL_CHANGE_MAX_BLOCKS); f.SC_METRIC = c.take<float>(1);
+  }
+  if (g.opt.adaptive) {    // likewise
+    const int64_t n = (int64_t)B * N * out_ch;
+    f.AD_K = c.take<bf16_t>(7 * n); f.AD_Y0 = c.take<float>(n); f.AD_Y1 = c.take<float>(n);
+    f.AD_DT = c.take<float>(1); f.AD_OUT = c.take<float>(4); f.AD_PART = c.take<float>(VC_DOPRI5_MAX_BLOCKS);
   }
   if (g.opt.lora_mode) {   // likewise: the widest Linear over the block rows, the modulation Linears over the (evaluation, sample) rows
     const int64_t wide = std::max<int64_t>({3 * D, mlp, D, out_ch}), rows = std::max<int64_t>(B * L, (int64_t)S * B);
@@ -650,12 +666,16 @@ int tap_double(Flux& f, size_t i, hipStream_t s, Err e) {
 // issues with its own launches in between: the inputs, the blocks from double block `first` on, the last layer + update.
 // where the sample in flight keeps its ODE state (in the caller's dtype), and the bf16 rows the next evaluation reads: the state
 // itself for a bf16 Euler step, XS as the bf16 shadow of an f32 Euler state, else YIN - the stage input of a midpoint / rk4 step
+constexpr int SOLVER_DOPRI5 = 100;     // Flux::method of the adaptive solve: no VC_SOLVER_* code (vc_solver_evals keeps refusing it)
 void* ode_state(Flux& f) { return f.state_f32 ? (void*)f.XS32 : (void*)f.XS; }
 int64_t ode_state_bytes(const Flux& f) { return (int64_t)f.B * f.N * f.cfg.out_channels * (f.state_f32 ? 4 : 2); }
 bf16_t* next_input(Flux& f) { return f.method == VC_SOLVER_EULER ? f.XS : f.YIN; }
 // the solver's update behind an evaluation (v = V), or with v null next_input = bf16(state) alone; next_input is not handed over
 // where it IS the state (the kernel's pointers are __restrict__)
 int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, Err e) {
+  if (f.method == SOLVER_DOPRI5)      // the stage of the adaptive solve is the device-side counter itself
+    return vc_dopri5_stage_launch(-1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
+                                  e.buf, e.len);
   void* y = ode_state(f);
   bf16_t* y_in = next_input(f);
   return vc_ode_update_launch("ode_update", f.method, -1, y, !f.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
@@ -886,6 +906,7 @@ int vc_flux_destroy_impl(void* handle, char* err, int errlen) {
   drop_prof(f);
   if (f.pinned) (void)hipHostFree(f.pinned);
   if (f.sc_host) (void)hipHostFree(f.sc_host);
+  if (f.ad_host) (void)hipHostFree(f.ad_host);
   if (f.staged) (void)hipEventDestroy(f.staged);
   delete &f;
   return VC_OK;
@@ -1021,9 +1042,9 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
       case ZERO_OR_H: if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H); break;
       case ANY: break;
     }
-    if (o.member == &Options::lora_mode && value != f.opt.lora_mode) {
+    if ((o.member == &Options::lora_mode || o.member == &Options::adaptive) && value != f.opt.*o.member) {
       if (f.in_flight)
-        FAIL(VC_ERR_STATE, "flux_set_option: lora_mode cannot change between vc_flux_sample_begin and vc_flux_sample_end");
+        FAIL(VC_ERR_STATE, "flux_set_option: %s cannot change between vc_flux_sample_begin and vc_flux_sample_end", o.name);
       f.prepared = false;    // the workspace carve-up differs: vc_flux_workspace_bytes + vc_flux_prepare again
     }
     f.opt.*o.member = value;
@@ -1289,6 +1310,166 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
   if (!x_out) FAIL(VC_ERR_ARG, "flux_sample_end: null output");
   f.in_flight = false;
   return d2d(x_out, ode_state(f), ode_state_bytes(f), s, e);
+}
+
+// ---------------------------------------------------------------- the adaptive solve (vcloze_hip.h: vc_flux_sample_dopri5)
+// the times of the seven modulation rows of a step t -> t + dt (row = the device-side counter = the stage of the evaluation): k1's
+// own (its evaluation is the last step's seventh), then c2..c6 and t + dt again for k7; the model sees 1 - f32(t)
+static int dopri5_rows(Flux& f, double t, double dt, hipStream_t s, Err e) {
+  static const double C[7] = {0.0, 1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0, 1.0};
+  const int B = f.B;
+  TRY(stage_begin(f, (size_t)7 * B * sizeof(float) + 1024, e));
+  float* ts = stage_take<float>(f, (size_t)7 * B);
+  float* hdt = stage_take<float>(f, 1);
+  for (int j = 0; j < 7; ++j) {
+    const float tm = 1.0f - (float)(t + C[j] * dt);
+    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = tm;
+  }
+  *hdt = (float)dt;
+  TRY(stage_send(f, f.TS, ts, (size_t)7 * B * sizeof(float), s, e));
+  TRY(stage_send(f, f.AD_DT, hdt, sizeof(float), s, e));
+  TRY(stage_end(f, s, e));
+  return time_precompute(f, 7, 0, s, e);
+}
+// `count` replays of the captured evaluation (+ its stage node) with the counter starting at `first`
+static int dopri5_evals(Flux& f, int first, int count, hipStream_t s, Err e) {
+  HIP(hipMemsetD32Async((hipDeviceptr_t)f.STEP, first, 1, s), "hipMemsetD32Async");
+  for (int j = 0; j < count; ++j) {
+    if (s) HIP(hipGraphLaunch(f.step.g[0], s), "hipGraphLaunch");
+    else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
+  }
+  f.ad_evals += count;
+  return VC_OK;
+}
+// the first `count` words of AD_OUT -> the host: the ONE synchronisation of an attempt
+static int dopri5_read(Flux& f, int count, hipStream_t s, Err e) {
+  HIP(hipMemcpyAsync(f.ad_host, f.AD_OUT, count * sizeof(float), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
+  HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return VC_OK;
+}
+
+static int dopri5_run(Flux& f, void* x, const float* t_grid, int n_points, int out_bf16, float rtol, float atol, int max_attempts,
+                      void* trajectory, hipStream_t s, Err e) {
+  const int64_t n = (int64_t)f.B * f.N * f.cfg.out_channels, out_bytes = n * (out_bf16 ? 2 : 4);
+  const volatile float* host = f.ad_host;
+  double t = t_grid[0];
+  // k1 = f(t0, y0): the counter at 0 stores it (the caller set the rows of t0 with dt = 0: the state the stage node forms is y0)
+  TRY(dopri5_evals(f, 0, 1, s, e));
+  // the initial step size
+  TRY(vc_dopri5_error_ratio_launch(1, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+  TRY(vc_dopri5_error_ratio_launch(2, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT + 1, f.AD_PART, n, s, e.buf, e.len));
+  TRY(dopri5_read(f, 2, s, e));
+  const double d0 = host[0], d1 = host[1];
+  if (d0 != d0 || d1 != d1) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the state or the model's output at t_grid[0] is not finite");
+  const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  TRY(dopri5_rows(f, t, h0, s, e));                       // (row 1 stands at t0 + c2 h0; the probe wants t0 + h0: row 5)
+  TRY(vc_dopri5_stage_launch(7, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, nullptr, f.YIN, n, s, e.buf, e.len));
+  TRY(dopri5_evals(f, 5, 1, s, e));                       // its k lands in k6 (and the state it forms is not used)
+  // d2 reads the probe from k2: the slots are free until the first attempt
+  TRY(d2d(f.AD_K + n, f.AD_K + 5 * n, n * 2, s, e));
+  TRY(vc_dopri5_error_ratio_launch(3, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+  TRY(dopri5_read(f, 1, s, e));
+  const double d2 = (double)host[0] / h0;
+  if (d2 != d2) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the model's output at t_grid[0] + h0 is not finite");
+  const double dmax = d1 > d2 ? d1 : d2;
+  const double h1 = dmax <= 1e-15 ? std::max(1e-6, h0 * 1e-3) : pow(0.01 / dmax, 1.0 / 5.0);
+  double dt = std::min(100.0 * h0, h1);
+  int next_out = 1;
+  while (next_out < n_points) {
+    if ((int)f.ad_log.size() >= max_attempts)
+      FAIL(VC_ERR_STATE, "flux_sample_dopri5: more than max_attempts = %d attempts (t = %.9g of [%.9g, %.9g], dt = %.3g)", max_attempts, t,
+           (double)t_grid[0], (double)t_grid[n_points - 1], dt);
+    if (t + dt == t) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the step size underflowed (t = %.17g, dt = %.3g)", t, dt);
+    TRY(dopri5_rows(f, t, dt, s, e));
+    TRY(vc_dopri5_stage_launch(0, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, f.AD_Y1, f.YIN, n, s, e.buf, e.len));   // k1 is in place
+    TRY(dopri5_evals(f, 1, 6, s, e));
+    TRY(vc_dopri5_error_ratio_launch(0, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+    TRY(dopri5_read(f, 1, s, e));
+    const float ratio32 = host[0];
+    const double ratio = ratio32;
+    const bool accept = ratio <= 1.0;
+    f.ad_log.push_back(Flux::Attempt{t, dt, ratio32, accept});
+    if (ratio != ratio) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the error ratio of the step at t = %.9g, dt = %.3g is NaN", t, dt);
+    if (accept) {
+      const double t1 = t + dt;
+      for (; next_out < n_points && (double)t_grid[next_out] <= t1; ++next_out) {
+        const bool last = next_out == n_points - 1;
+        if (!trajectory && !last) continue;
+        double theta = ((double)t_grid[next_out] - t) / dt;
+        theta = theta < 0.0 ? 0.0 : theta > 1.0 ? 1.0 : theta;
+        void* dst = trajectory ? (void*)((char*)trajectory + (int64_t)(next_out - 1) * out_bytes) : x;
+        TRY(vc_dopri5_interp_launch(f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, (float)theta, dst, out_bf16, n, s, e.buf, e.len));
+        if (trajectory && last) TRY(d2d(x, dst, out_bytes, s, e));
+      }
+      TRY(d2d(f.AD_Y0, f.AD_Y1, n * 4, s, e));
+      TRY(d2d(f.AD_K, f.AD_K + 6 * n, n * 2, s, e));        // first same as last
+      t = t1;
+    }
+    double factor = 10.0;
+    if (ratio != 0.0) factor = std::min(10.0, std::max(0.9 / pow(ratio, 1.0 / 5.0), ratio < 1.0 ? 1.0 : 0.2));
+    dt *= factor;
+  }
+  return VC_OK;
+}
+
+int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                               float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample_dopri5: call vc_flux_prepare first");
+  TRY(fresh_scale(f, "flux_sample_dopri5", e));
+  if (!x || !cond || !t_grid) FAIL(VC_ERR_ARG, "flux_sample_dopri5: null argument");
+  if (!f.opt.adaptive || !f.AD_K)
+    FAIL(VC_ERR_STATE, "flux_sample_dopri5: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
+                       "(the workspace holds no buffers of the adaptive solve)");
+  if (f.S < 7) FAIL(VC_ERR_ARG, "flux_sample_dopri5: the workspace was prepared with max_steps = %d, the adaptive solve needs 7", f.S);
+  if (n_points < 2) FAIL(VC_ERR_ARG, "flux_sample_dopri5: n_points = %d, at least 2 expected", n_points);
+  for (int i = 1; i < n_points; ++i)
+    if (!(t_grid[i] > t_grid[i - 1])) FAIL(VC_ERR_ARG, "flux_sample_dopri5: t_grid must increase strictly (index %d)", i);
+  if (!(rtol >= 0.0f) || !(atol >= 0.0f) || !(rtol + atol > 0.0f) || !(rtol + atol - (rtol + atol) == 0.0f))
+    FAIL(VC_ERR_ARG, "flux_sample_dopri5: rtol = %g and atol = %g must be finite, non-negative and not both zero", rtol, atol);
+  if (max_attempts < 1) FAIL(VC_ERR_ARG, "flux_sample_dopri5: max_attempts = %d must be positive", max_attempts);
+  if (f.sc_on())
+    FAIL(VC_ERR_ARG, "flux_sample_dopri5: the step cache works with VC_SOLVER_EULER only: turn it off with vc_flux_set_step_cache(handle, 0, 0)");
+  if (f.cfg_on) {
+    if (f.B % 2) FAIL(VC_ERR_ARG, "flux_sample_dopri5: true CFG pairs the first half of the batch with the second: B = %d is odd", f.B);
+    if (!(f.cfg_scale - f.cfg_scale == 0.0f)) FAIL(VC_ERR_ARG, "flux_sample_dopri5: the cfg_scale set by vc_flux_set_cfg is not finite");
+  }
+  if (!f.ad_host) HIP(hipHostMalloc((void**)&f.ad_host, 256, hipHostMallocDefault), "hipHostMalloc");
+  const int64_t n = (int64_t)f.B * f.N * f.cfg.out_channels;
+  f.in_flight = false;
+  f.steps_total = f.steps_done = 0;             // an earlier trajectory's tables are overwritten: steps / end refuse from here on
+  f.state_f32 = true;
+  f.method = SOLVER_DOPRI5; f.evals = 1;
+  f.sc_active = false;
+  f.cfg_active = f.cfg_on; f.cfg_s = f.cfg_on ? f.cfg_scale : 1.0f;
+  f.ad_log.clear();
+  f.ad_evals = 0;
+  TRY(vc_dopri5_load_launch(x, state_is_bf16, f.AD_Y0, f.YIN, n, s, e.buf, e.len));
+  TRY(d2d(f.COND, cond, (int64_t)f.B * f.N * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
+  {  // the warm-up evaluation of a new capture indexes the modulation rows by the counter and reads dt: both defined first
+    HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
+    TRY(dopri5_rows(f, (double)t_grid[0], 0.0, s, e));
+  }
+  if (s) TRY(step_graph(f, s, e));
+  const int rc = dopri5_run(f, x, t_grid, n_points, state_is_bf16 != 0, rtol, atol, max_attempts, trajectory, s, e);
+  f.method = VC_SOLVER_EULER;
+  return rc;
+}
+
+int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                            int32_t* evaluations, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (capacity < 0) FAIL(VC_ERR_ARG, "flux_dopri5_log: capacity = %d is negative", capacity);
+  const int count = std::min<int>(capacity, (int)f.ad_log.size());
+  for (int i = 0; i < count; ++i) {
+    if (t) t[i] = f.ad_log[i].t;
+    if (dt) dt[i] = f.ad_log[i].dt;
+    if (ratio) ratio[i] = f.ad_log[i].ratio;
+    if (accepted) accepted[i] = f.ad_log[i].accepted;
+  }
+  if (attempts) *attempts = (int32_t)f.ad_log.size();
+  if (evaluations) *evaluations = f.ad_evals;
+  return VC_OK;
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {

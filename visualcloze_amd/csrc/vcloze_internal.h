@@ -59,6 +59,14 @@ int vc_ode_update_launch(const char* what, int method, int stage, void* y, int s
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen);
+// dopri5.hip: the adaptive solve's kernels (vc_dopri5_load_launch: the caller's state -> the f32 state and its bf16 shadow)
+int vc_dopri5_stage_launch(int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr, float* y_stage,
+                           void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_dopri5_error_ratio_launch(int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
+                                 float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_dopri5_interp_launch(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int out_is_bf16,
+                            int64_t n, hipStream_t s, char* err, int errlen);
+int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen);
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
@@ -149,6 +157,10 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen);
 int vc_flux_set_cfg_impl(void* handle, int32_t on, float cfg_scale, char* err, int errlen);
 int vc_flux_step_cache_stats_impl(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity, char* err, int errlen);
+int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                               float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
+int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                            int32_t* evaluations, char* err, int errlen);
 
 // vae_engine.hip: the autoencoder handle
 int vc_vae_create_impl(const VcVaeConfig* cfg, void** handle, char* err, int errlen);

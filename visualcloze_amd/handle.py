@@ -155,6 +155,7 @@ class FluxHandle(_Handle):
         self._lora: Dict[str, tuple] = {}
         self._taps: Dict[str, torch.Tensor] = {}
         self.lora_mode = 0
+        self.adaptive = 0
         if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
             scales = []
             for name, R in weights.ref.items():
@@ -239,6 +240,14 @@ class FluxHandle(_Handle):
             self._ws.clear()
             self.geom = None
 
+    def set_adaptive(self, on: bool) -> None:
+        """vc_flux_set_option("adaptive"): 1 = the workspace holds the buffers of the adaptive solve (`sample_dopri5`).  A switch needs
+        a new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
+        hip._check(hip.lib().vc_flux_set_option(self.h, b"adaptive", int(bool(on))), "vc_flux_set_option(adaptive)")
+        if int(bool(on)) != self.adaptive:
+            self.adaptive = int(bool(on))
+            self.geom = None
+
     def set_lora_scale(self, scale: float) -> None:
         """vc_flux_set_lora_scale: the scale of every pair; a bf16 value, anything else is refused, and so is a change while a
         trajectory is in flight.  Call `prepare` again after a change (forward / sample_* refuse a prepared state of the old scale);
@@ -297,7 +306,7 @@ class FluxHandle(_Handle):
         return {"computed": c.value, "reused": r.value, "metrics": [float(m[i]) for i in range(n)]}
 
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
-        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0)
+        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ())
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:
@@ -397,6 +406,26 @@ class FluxHandle(_Handle):
 
     def sample_euler(self, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
         self.sample_ode("euler", x, cond, t_grid, state_is_bf16, stream, trajectory)
+
+    def sample_dopri5(self, x, cond, t_grid, state_is_bf16: bool, stream, rtol: float = 1e-3, atol: float = 1e-6,
+                      max_attempts: int = 1000, trajectory=None) -> None:
+        """vc_flux_sample_dopri5 (after `set_adaptive(True)` and a prepare with max_steps >= 7): x [B,N,C] in place, x(t_grid[0]) ->
+        x(t_grid[-1]) by the adaptive Dormand-Prince 5(4) solve; trajectory: optional [len(t_grid) - 1, B, N, C] buffer receiving
+        x(t_grid[1:]) (dense output).  The state is stepped in f32 whatever its dtype.  `dopri5_log()` tells what the solve did."""
+        args = self._sample_args("vc_flux_sample_dopri5", 0, x, cond, t_grid, state_is_bf16, trajectory)
+        hip._check(hip.lib().vc_flux_sample_dopri5(args[0], *args[2:], float(rtol), float(atol), int(max_attempts), hip._p(trajectory), stream),
+                   "vc_flux_sample_dopri5")
+
+    def dopri5_log(self) -> dict:
+        """vc_flux_dopri5_log of the last `sample_dopri5`: {"attempts": [(t, dt, ratio, accepted), ...], "evaluations", "rejected"}"""
+        n, ev = C.c_int32(0), C.c_int32(0)
+        L = hip.lib()
+        hip._check(L.vc_flux_dopri5_log(self.h, None, None, None, None, 0, C.byref(n), C.byref(ev)), "vc_flux_dopri5_log")
+        cap = max(n.value, 1)
+        t, dt, r, a = (C.c_double * cap)(), (C.c_double * cap)(), (C.c_float * cap)(), (C.c_int32 * cap)()
+        hip._check(L.vc_flux_dopri5_log(self.h, t, dt, r, a, cap, C.byref(n), C.byref(ev)), "vc_flux_dopri5_log")
+        att = [(t[i], dt[i], float(r[i]), bool(a[i])) for i in range(n.value)]
+        return {"attempts": att, "evaluations": ev.value, "rejected": sum(1 for x in att if not x[3])}
 
 
 class VaeHandle(_Handle):

@@ -210,6 +210,9 @@ SYMBOLS = {
     "vc_step_advance": (C.c_int, [_vp, _vp]),
     "vc_solver_evals": (C.c_int, [C.c_int]),
     "vc_ode_stage": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "vc_dopri5_stage": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "vc_dopri5_error_ratio": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp]),
+    "vc_dopri5_interp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _i32, _i64, _vp]),
     "vc_residual_change": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
@@ -257,6 +260,9 @@ SYMBOLS = {
     "vc_flux_sample_end": (C.c_int, [_vp, _vp, _vp]),
     "vc_flux_sample_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
     "vc_flux_sample_begin_ode": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
+    "vc_flux_sample_dopri5": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp]),
+    "vc_flux_dopri5_log": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(_i32), _i32,
+                                     C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
     "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
@@ -753,6 +759,68 @@ def ode_stage(method, stage: int, y, v, k, y_in, dts, eval_ptr=None, stream=None
 
 def step_advance(step_ptr, stream=None):
     _check(lib().vc_step_advance(step_ptr.data_ptr(), stream if stream is not None else cur_stream()), "vc_step_advance")
+
+
+DOPRI5_MAX_BLOCKS = 256              # VC_DOPRI5_MAX_BLOCKS
+
+
+def _dopri5_f32(what, **tensors):
+    for name, t in tensors.items():
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise VclozeHipError(f"{what}: {name} must be a contiguous CUDA f32 tensor")
+
+
+def _dopri5_k(what, k, n):
+    _bf16(k, "k")
+    if not k.is_contiguous() or k.numel() != 7 * n:
+        raise VclozeHipError(f"{what}: k must be a contiguous bf16 [7, n] tensor")
+
+
+def dopri5_stage(stage: int, y0, k, v, dt, eval_ptr=None, y_stage=None, y_in=None, stream=None):
+    """vc_dopri5_stage: k[stage] = -v (v None: in place already) and the next evaluation's state y0 + dt * (row of the tableau) ->
+    y_stage (f32) / y_in (bf16); stage 5 forms y1, stage 6 only stores k7, stage 7 (v None) the probe state y0 + dt * k1;
+    stage < 0: eval_ptr[0] on the device.  y0: f32 [n], k: bf16 [7, n], dt: f32 [1] on the device."""
+    n = y0.numel()
+    _dopri5_f32("vc_dopri5_stage", y0=y0, dt=dt, y_stage=y_stage)
+    _dopri5_k("vc_dopri5_stage", k, n)
+    for name, t in (("v", v), ("y_in", y_in)):
+        if t is not None:
+            _bf16(t, name)
+            if not t.is_contiguous() or t.numel() != n:
+                raise VclozeHipError(f"vc_dopri5_stage: {name} must be contiguous and hold n values")
+    if y_stage is not None and y_stage.numel() != n:
+        raise VclozeHipError("vc_dopri5_stage: y_stage must hold n values")
+    _check(lib().vc_dopri5_stage(int(stage), y0.data_ptr(), k.data_ptr(), _p(v), dt.data_ptr(), _p(eval_ptr), _p(y_stage), _p(y_in), n,
+                                 stream if stream is not None else cur_stream()), "vc_dopri5_stage")
+
+
+def dopri5_error_ratio(y0, y1, k, dt, rtol: float, atol: float, mode: int = 0, out=None, stream=None):
+    """vc_dopri5_error_ratio: out[0] = sqrt(mean(q^2)) over all n elements in a fixed order (f32 [1], returned).  mode 0: the error
+    ratio of the step (y0, y1, k, dt); modes 1, 2, 3: the initial-step norms of y0, k1, k2 - k1 over atol + rtol |y0|."""
+    n = y0.numel()
+    _dopri5_f32("vc_dopri5_error_ratio", y0=y0, y1=y1, dt=dt, out=out)
+    if k is not None:
+        _dopri5_k("vc_dopri5_error_ratio", k, n)
+    if y1 is not None and y1.numel() != n:
+        raise VclozeHipError("vc_dopri5_error_ratio: y1 must hold n values")
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=y0.device)
+    scratch = torch.empty(DOPRI5_MAX_BLOCKS, dtype=torch.float32, device=y0.device)
+    _check(lib().vc_dopri5_error_ratio(int(mode), y0.data_ptr(), _p(y1), _p(k), _p(dt), float(rtol), float(atol), out.data_ptr(),
+                                       scratch.data_ptr(), n, stream if stream is not None else cur_stream()), "vc_dopri5_error_ratio")
+    return out
+
+
+def dopri5_interp(y0, y1, k, dt, theta: float, out=None, dtype=torch.float32, stream=None):
+    """vc_dopri5_interp: the dense output of the step (y0, y1, k, dt) at theta in [0, 1] -> out (f32 or bf16, n values)"""
+    n = y0.numel()
+    _dopri5_f32("vc_dopri5_interp", y0=y0, y1=y1, dt=dt)
+    _dopri5_k("vc_dopri5_interp", k, n)
+    out = out if out is not None else torch.empty(y0.shape, dtype=dtype, device=y0.device)
+    if out.dtype not in (torch.float32, torch.bfloat16) or not (out.is_cuda and out.is_contiguous()) or out.numel() != n or y1.numel() != n:
+        raise VclozeHipError("vc_dopri5_interp: y1 and a contiguous f32 / bf16 out of n values expected")
+    _check(lib().vc_dopri5_interp(y0.data_ptr(), y1.data_ptr(), k.data_ptr(), dt.data_ptr(), float(theta), out.data_ptr(),
+                                  int(out.dtype == torch.bfloat16), n, stream if stream is not None else cur_stream()), "vc_dopri5_interp")
+    return out
 
 
 RESIDUAL_CHANGE_MAX_BLOCKS = 256     # VC_RESIDUAL_CHANGE_MAX_BLOCKS

@@ -109,13 +109,25 @@ def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
 @torch.no_grad()
 def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[torch.Tensor],
                  mask_rows: List[torch.Tensor], txt: torch.Tensor, vec: torch.Tensor, cfg: float = 30.0,
-                 steps: int = 30, solver: str = "euler", time_shifting_factor=1, step_cache=None) -> List[torch.Tensor]:
+                 steps: int = 30, solver: str = "euler", time_shifting_factor=1, step_cache=None,
+                 adaptive: Optional[dict] = None) -> List[torch.Tensor]:
     """One grid: per-row noise [1,16,h,w], VAE latents of the grid rows (already shifted/scaled), per-row PIXEL
-    fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w]."""
+    fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w].
+    `adaptive`: None, or dict(rtol=, atol=[, max_attempts=]) - the error-controlled Dormand-Prince 5(4) solve
+    (`Sampler.sample_ode_adaptive`) instead of `solver`; `steps` then only places the end time's grid."""
     dev = noise_rows[0].device
     img, img_ids, img_mask = packing.prepare_grid([noise_rows])                       # visualcloze.py:403
     cond = packing.pack_cond(cond_latent_rows, mask_rows)                              # :381-389
-    fn = Sampler(create_transport("Linear", "velocity", do_shift=True)).sample_ode(
+    sampler = Sampler(create_transport("Linear", "velocity", do_shift=True))
+    if adaptive is not None:
+        if step_cache is not None:
+            raise ValueError("adaptive: the step cache works with the fixed-grid Euler loop only")
+        fn = sampler.sample_ode_adaptive(num_steps=steps, do_shift=True, time_shifting_factor=time_shifting_factor, **adaptive)
+        model.last_adaptive_log = None
+        samples = fn(img, model.forward, _kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]
+        model.last_adaptive_log = sampler.last_adaptive_log
+        return packing.unpack_rows(samples, [tuple(r.shape[-2:]) for r in noise_rows])
+    fn = sampler.sample_ode(
         sampling_method=solver, num_steps=steps, atol=1e-6, rtol=1e-3, reverse=False, do_shift=True,
         time_shifting_factor=time_shifting_factor, step_cache=step_cache)              # :284-292
     samples = fn(img, model.forward, _kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]   # :415-420
@@ -177,7 +189,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
                   t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, cfg: float = 30.0, steps: int = 30,
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
                   solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
-                  step_cache=None, use_grid_handle: bool = False) -> List[torch.Tensor]:
+                  step_cache=None, use_grid_handle: bool = False, adaptive: Optional[dict] = None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -192,7 +204,12 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`.
     `use_grid_handle`: opt-in, off by default - the whole function as ONE call of the library's grid handle (vc_grid_generate,
     `handle.GridHandle`: the same composition kept in csrc/grid_engine.hip, the same bits).  Valid only with a `NoiseStream` and the
-    use_handle switches of all four modules on (ValueError otherwise); `rng.offset` advances as it does here."""
+    use_handle switches of all four modules on (ValueError otherwise); `rng.offset` advances as it does here.
+    `adaptive`: None (the default), or dict(rtol=, atol=) - denoise with the error-controlled Dormand-Prince 5(4) solve instead of
+    `solver` (`denoise_grid`); `model.last_adaptive_log` tells what it did.  Refused together with use_grid_handle=True: the grid
+    handle runs the fixed-grid solvers only."""
+    if adaptive is not None and use_grid_handle:
+        raise ValueError("generate_grid(adaptive=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid solvers only")
     if use_grid_handle:
         gh = _grid_handle(model, ae, t5, clip, rng, "generate_grid", encode_noise=encode_noise)
         if step_cache is not None and solver != "euler":
@@ -213,7 +230,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     txt = t5(t5_ids)                                                                   # prepare_modified -> HFEmbedder
     vec, _ = clip(clip_ids)
     rows = denoise_grid(model, noise, lat, row_masks, txt, vec, cfg=cfg, steps=steps, solver=solver,
-                        time_shifting_factor=time_shifting_factor, step_cache=step_cache)
+                        time_shifting_factor=time_shifting_factor, step_cache=step_cache, adaptive=adaptive)
     out = []
     for i in (range(len(rows)) if decode_rows is None else decode_rows):
         img = ae.decode(rows[i])[0]                                                    # :430

@@ -13,6 +13,10 @@ loop; a foreign callable is stepped eagerly with the same grid.  The bound `forw
 (true classifier-free guidance, model.py:126-145: `model_kwargs["cfg_scale"]`, conditional samples first, unconditional ones
 behind them) runs the same fused loop with the cross-sample combine as one more node of the captured step.
 
+`Sampler.sample_ode_adaptive` is the error-controlled solve the reference's `sample_ode` defaults to ("dopri5"), under a name of its
+own - `sample_ode(sampling_method="dopri5")` keeps raising: adaptive Dormand-Prince 5(4), fused through vc_flux_sample_dopri5 for a
+`visualcloze_amd.Flux` with the C handle, `dopri5_integrate` (the same rule in plain torch) for any other callable.
+
 The step rules (`STEP_RULES`) are torchdiffeq 0.2.x's fixed-grid solvers as recalled - unpinned against real
 torchdiffeq, which was not available to check against (as the Euler rule, tests/golden/make_golden.py).  They
 are written ONCE, as the literal torch expressions: a correction is a one-line change here and in
@@ -96,6 +100,169 @@ def _step_rk4(f, t0, t1, dt, y0):          # the 3/8 rule
 STEP_RULES = {"euler": _step_euler, "midpoint": _step_midpoint, "rk4": _step_rk4}
 
 
+# ---- the adaptive Dormand-Prince 5(4) solve (vc_flux_sample_dopri5): the same rule in plain torch, for any callable.  The tableau is
+# SciPy's RK45.C / .A / .B / .E (tests/test_dopri5_cpu.py pins it, and single steps, against SciPy) plus torchdiffeq's DPS_C_MID; the
+# controller is torchdiffeq's as recalled - unpinned against real torchdiffeq, which was not available to check against.
+DOPRI5_C = (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0)
+DOPRI5_A = ((1 / 5,),
+            (3 / 40, 9 / 40),
+            (44 / 45, -56 / 15, 32 / 9),
+            (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
+            (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656))
+DOPRI5_B = (35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84)
+DOPRI5_E = (-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40)
+DOPRI5_C_MID = (6025192743 / 30085553152 / 2, 0.0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2,
+                187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2)
+
+
+class Dopri5Error(RuntimeError):
+    """the adaptive solve gave up: a NaN error ratio, a step size that underflowed, or more than max_attempts attempts"""
+
+
+def _dopri5_combine(row, ks):
+    """sum of row[j] * ks[j] over the non-zero coefficients, left to right (csrc/dopri5.hip: dp_combine - the same bits in f32)"""
+    acc = None
+    for c, k in zip(row, ks):
+        if c == 0.0:
+            continue
+        term = c * k
+        acc = term if acc is None else acc + term
+    return acc
+
+
+def _f32(v: float) -> float:
+    """a Python float rounded to f32: the scalar an f32 kernel argument holds"""
+    return float(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+
+
+def _scalar(v: float, y: torch.Tensor) -> float:
+    return _f32(v) if y.dtype == torch.float32 else float(v)
+
+
+def dopri5_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor):
+    """One Dormand-Prince step from (t, y0) with k1 = f(t, y0): -> (y1, [k1..k7]); k7 = f(t + dt, y1) is the next step's k1.
+    Every k is converted to the state's dtype, every sum is taken left to right."""
+    h = _scalar(dt, y0)
+    ks = [k1.to(y0.dtype)]
+    for i, row in enumerate(DOPRI5_A):
+        ks.append(f(t + DOPRI5_C[i + 1] * dt, y0 + h * _dopri5_combine(row, ks)).to(y0.dtype))
+    y1 = y0 + h * _dopri5_combine(DOPRI5_B, ks)
+    ks.append(f(t + dt, y1).to(y0.dtype))
+    return y1, ks
+
+
+def dopri5_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float) -> float:
+    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements"""
+    err = _scalar(dt, y0) * _dopri5_combine(DOPRI5_E, ks)
+    tol = _scalar(atol, y0) + _scalar(rtol, y0) * torch.maximum(y0.abs(), y1.abs())
+    q = err / tol
+    return float((q * q).mean().sqrt())
+
+
+def dopri5_interp(y0, y1, ks, dt: float, theta: float):
+    """The dense output at theta in [0, 1]: the quartic through (y0, f0, y_mid, y1, f1) as torchdiffeq fits and evaluates it; theta = 0
+    and theta = 1 return y0 and y1 themselves.  For an f32 state the scalars are f32, as in csrc/dopri5.hip."""
+    x = _scalar(theta, y0)
+    if x == 0.0:
+        return y0.clone()
+    if x == 1.0:
+        return y1.clone()
+    f32 = y0.dtype == torch.float32
+    h = _scalar(dt, y0)
+    f0, f1 = ks[0], ks[6]
+    y_mid = y0 + h * _dopri5_combine(DOPRI5_C_MID, ks)
+    a = (2 * h * (f1 - f0) - 8 * (y1 + y0)) + 16 * y_mid
+    b = ((h * (5 * f0 - 3 * f1) + 18 * y0) + 14 * y1) - 32 * y_mid
+    c = ((h * (f1 - 4 * f0) - 11 * y0) - 5 * y1) + 16 * y_mid
+    d = h * f0
+    xp = x
+    out = y0 + xp * d
+    for coeff in (c, b, a):
+        xp = _f32(xp * x) if f32 else xp * x          # (the product of two f32 values in double, rounded once: the f32 product)
+        out = out + xp * coeff
+    return out
+
+
+def dopri5_controller(dt: float, ratio: float):
+    """-> (accepted, dt_next): accept iff ratio <= 1; dt_next = 10 dt for ratio 0, else dt * min(10, max(0.9 / ratio^(1/5), 1 if
+    ratio < 1 else 0.2)).  A NaN ratio raises Dopri5Error."""
+    if ratio != ratio:
+        raise Dopri5Error(f"dopri5: the error ratio of a step of dt = {dt:.3g} is NaN")
+    if ratio == 0.0:
+        return True, dt * 10.0
+    return ratio <= 1.0, dt * min(10.0, max(0.9 / math.pow(ratio, 1.0 / 5.0), 1.0 if ratio < 1.0 else 0.2))
+
+
+def _rms(a) -> float:
+    return float((a * a).mean().sqrt())
+
+
+def dopri5_initial_step(f, t0: float, y0, f0, rtol: float, atol: float) -> float:
+    """Hairer's starting step size for order 4 (one more evaluation)"""
+    scale = _scalar(atol, y0) + _scalar(rtol, y0) * y0.abs()
+    f0 = f0.to(y0.dtype)
+    d0, d1 = _rms(y0 / scale), _rms(f0 / scale)
+    if d0 != d0 or d1 != d1:
+        raise Dopri5Error("dopri5: the state or the drift at the first time is not finite")
+    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
+    f1 = f(t0 + h0, y0 + _scalar(h0, y0) * f0).to(y0.dtype)
+    d2 = _rms((f1 - f0) / scale) / h0
+    if d2 != d2:
+        raise Dopri5Error("dopri5: the drift at the first time + h0 is not finite")
+    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else math.pow(0.01 / max(d1, d2), 1.0 / 5.0)
+    return min(100.0 * h0, h1)
+
+
+def dopri5_integrate(f, y0: torch.Tensor, t, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
+                     log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
+    """The adaptive Dormand-Prince 5(4) solve of y' = f(t, y) from y(t[0]) = y0: -> [len(t), ...] = y at every t (t[0]: y0 itself;
+    the others by dense output inside the accepted step that covers them - steps are not clamped to the output times, so f may be
+    evaluated past t[-1]).  t: increasing Python floats (or a 1-d tensor); f takes a Python float and the state and returns the drift.
+    The state keeps its dtype (f32 or f64); one step size serves the whole tensor.  `forced_dts`: replay a given attempt sequence -
+    a list of dt, or of (dt, accepted) pairs, one per attempt: no initial-step search, no controller.  `log` (a list) receives
+    (t, dt, ratio, accepted) per attempt; `on_attempt(t, dt, y0, y1, ks)` sees every attempt's tensors.  Raises Dopri5Error on a NaN ratio, an underflowed step or more than max_attempts attempts."""
+    ts = [float(v) for v in (t.tolist() if torch.is_tensor(t) else t)]
+    if len(ts) < 2 or any(b <= a for a, b in zip(ts, ts[1:])):
+        raise ValueError("dopri5_integrate: t must hold at least two strictly increasing times")
+    if y0.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"dopri5_integrate: an f32 or f64 state expected, got {y0.dtype}")
+    log = log if log is not None else []
+    tc = ts[0]
+    k1 = f(tc, y0).to(y0.dtype)
+    forced = None if forced_dts is None else list(forced_dts)
+    dt = None if forced is not None else dopri5_initial_step(f, tc, y0, k1, rtol, atol)
+    outs, nxt, attempts = [y0], 1, 0
+    while nxt < len(ts):
+        if forced is not None:
+            if attempts >= len(forced):
+                raise Dopri5Error(f"dopri5: the {len(forced)} forced attempts end at t = {tc!r}, before t[{nxt}] = {ts[nxt]!r}")
+            item = forced[attempts]
+            dt, accept_as = (float(item[0]), bool(item[1])) if isinstance(item, (tuple, list)) else (float(item), None)
+        if attempts >= max_attempts:
+            raise Dopri5Error(f"dopri5: more than max_attempts = {max_attempts} attempts (t = {tc!r}, dt = {dt:.3g})")
+        if tc + dt == tc:
+            raise Dopri5Error(f"dopri5: the step size underflowed (t = {tc!r}, dt = {dt:.3g})")
+        attempts += 1
+        y1, ks = dopri5_step(f, tc, dt, y0, k1)
+        ratio = dopri5_error_ratio(y0, y1, ks, dt, rtol, atol)
+        if on_attempt is not None:
+            on_attempt(tc, dt, y0, y1, ks)
+        if forced is not None and accept_as is not None:
+            accepted, dt_next = accept_as, None
+            log.append((tc, dt, ratio, accepted))
+        else:
+            log.append((tc, dt, ratio, ratio <= 1.0))
+            accepted, dt_next = dopri5_controller(dt, ratio)
+        if accepted:
+            t1 = tc + dt
+            while nxt < len(ts) and ts[nxt] <= t1:
+                outs.append(dopri5_interp(y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
+                nxt += 1
+            y0, k1, tc = y1, ks[6], t1
+        dt = dt_next
+    return torch.stack(outs)
+
+
 class StepCache:
     """Opt-in first-block step cache of the fused Euler loop (vc_flux_set_step_cache).  IT CHANGES RESULTS: an
     evaluation whose first-block residual moved by less than `threshold` (relative L1 against the last computed evaluation's) is
@@ -132,6 +299,7 @@ class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
         self.last_step_cache_stats = None      # of the last cached trajectory this sampler ran: one dict per chunk of samples
+        self.last_adaptive_log = None          # of the last sample_ode_adaptive run: one dict per chunk of samples
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False,
                    do_shift=True, time_shifting_factor=None, strength=None, return_trajectory: bool = False,
@@ -181,6 +349,133 @@ class Sampler:
             return _sample_foreign(model, x, dict(model_kwargs), t, return_trajectory, sampling_method)
 
         return _sample
+
+    def sample_ode_adaptive(self, *, num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, do_shift=True, time_shifting_factor=None,
+                            strength=None, return_trajectory: bool = False, max_attempts: int = 1000):
+        """The error-controlled solve the reference's sample_ode defaults to (sampling_method="dopri5", atol, rtol), under a name of
+        its own: sample_ode("dopri5") keeps raising.  Adaptive Dormand-Prince 5(4) (`dopri5_integrate`); `num_steps` only places the
+        OUTPUT times - the solver chooses its own steps and reads the outputs off its dense output.  Fused (vc_flux_sample_dopri5:
+        replays of one captured evaluation, one 4-byte host read per attempt) for the bound forward / forward_with_cfg of a
+        visualcloze_amd.Flux that has the C handle and a bf16 or f32 state, eager otherwise.  The state is stepped in f32 (f64 for an
+        f64 caller) and rounded once per output.  `sampler.last_adaptive_log` holds, per chunk of samples,
+        {"attempts": [(t, dt, ratio, accepted)], "evaluations", "rejected"} of the last run."""
+        t0, t1 = self.transport.check_interval(reverse=reverse)
+        if strength is not None:
+            t0 = (t1 - t0) * strength + t0
+        assert t0 < t1, "ODE sampler has to be in forward time"
+
+        def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
+            t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
+            from .model import Flux
+            owner, name = getattr(model, "__self__", None), getattr(model, "__name__", "")
+            kw = dict(model_kwargs)
+            is_flux = isinstance(owner, Flux) and name in ("forward", "forward_with_cfg")
+            cfg_scale = float(kw.pop("cfg_scale", 1.0)) if is_flux and name == "forward_with_cfg" else None
+            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
+            if fused and cfg_scale is not None:
+                fused = _cfg_fusable(owner, x, "euler", kw)
+            if fused:
+                out, logs = _sample_adaptive_fused(owner, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale)
+            else:
+                if cfg_scale is not None:
+                    model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
+                out, log = _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=is_flux)
+                logs = [log]
+            self.last_adaptive_log = logs
+            return out
+
+        return _sample
+
+
+def _adaptive_drift(model, x, kw, bf16_out: bool):
+    """f(t, y) = -model(y in the caller's dtype || cond, timesteps = 1 - f32(t)) for a Python-float t (vcloze_hip.h)"""
+    cond = kw.pop("cond", None)
+
+    def f(t, y):
+        tm = torch.tensor(1.0) - torch.tensor(t, dtype=torch.float64).to(torch.float32)        # the f32 subtraction
+        ym = y.to(x.dtype)
+        xin = torch.cat((ym, cond), dim=-1) if cond is not None else ym
+        v = model(xin, timesteps=torch.ones(y.size(0), device=y.device) * tm.to(y.device), **kw)
+        assert v.shape == y.shape, "Output shape from ODE solver must match input shape"
+        return -(v.to(torch.bfloat16) if bf16_out else v)
+    return f
+
+
+def _log_dict(attempts, evaluations):
+    return {"attempts": list(attempts), "evaluations": evaluations, "rejected": sum(1 for a in attempts if not a[3])}
+
+
+def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=False, forced_dts=None,
+                             on_attempt=None):
+    """Any callable: transport.dopri5_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
+    calls = []
+    drift = _adaptive_drift(model, x, kw, bf16_out)
+    f = lambda tt, y: (calls.append(tt), drift(tt, y))[1]  # noqa: E731
+    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
+    log = []
+    out = dopri5_integrate(f, y0, t.to(torch.float32), rtol, atol, max_attempts, forced_dts=forced_dts, log=log,
+                           on_attempt=on_attempt).to(x.dtype)
+    return (out if return_trajectory else out[-1:]), _log_dict(log, len(calls))
+
+
+@torch.no_grad()
+def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None):
+    """vc_flux_sample_dopri5 per chunk of samples (true CFG: chunks of whole pairs): ONE step size per chunk, so a sample's result
+    depends on the samples it shares a chunk with."""
+    eng = flux.engine()
+    dev = eng.dev
+    B, N, C = x.shape
+    cond = kw.get("cond")
+    if cond is None:
+        raise hip.VclozeHipError("fused sampler expects model_kwargs['cond'] (x || cond feeds img_in)")
+    if C + cond.shape[-1] != flux.in_channels:
+        raise hip.VclozeHipError(f"x ({C}) || cond ({cond.shape[-1]}) does not match in_channels {flux.in_channels}")
+    txt, y, guidance = kw["txt"], kw["y"], kw.get("guidance")
+    if flux.params.guidance_embed and guidance is None:
+        raise ValueError("Didn't get guidance strength for guidance distilled model.")
+    T, S = txt.shape[1], len(t) - 1
+    t32 = t.to(torch.float32)
+    bf = lambda a: a.to(dev, torch.bfloat16).contiguous()  # noqa: E731
+    sdt = x.dtype
+    out = torch.empty(B, N, C, dtype=sdt, device=dev)
+    traj = torch.empty(S, B, N, C, dtype=sdt, device=dev) if return_trajectory else None
+    gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
+    from .model import MaskLayout, per_sample
+    guidance = per_sample(guidance, B)
+    lay = MaskLayout(kw.get("txt_mask"), kw.get("img_mask"), B, T, N)
+    st = eng.stream
+    st.wait_stream(torch.cuda.current_stream())
+    h = flux.handle()
+    h.set_step_cache(None)
+    h.set_cfg(cfg_scale)
+    h.set_adaptive(True)
+    mb = flux.max_batch()
+    chunks = [slice(b0, min(b0 + mb, B)) for b0 in range(0, B, mb)] if cfg_scale is None else cfg_chunks(B, mb)
+    logs = []
+    try:
+        with torch.cuda.stream(st):
+            s = st.cuda_stream
+            for sl in chunks:
+                bs = len(range(B)[sl]) if isinstance(sl, slice) else len(sl)
+                h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
+                          lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), 7, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
+                xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()
+                tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
+                try:
+                    h.sample_dopri5(xs, bf(lay.img_rows(cond, sl)), t32, sdt == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
+                finally:
+                    logs.append(h.dopri5_log())
+                if return_trajectory:
+                    traj[:, sl] = torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)])
+                out[sl] = lay.img_rows_back(xs, sl)
+    finally:
+        h.set_adaptive(False)                      # a later fixed-grid trajectory sizes its workspace as it always did
+        if cfg_scale is not None:
+            h.set_cfg(None)
+        torch.cuda.current_stream().wait_stream(st)
+    if return_trajectory:
+        return torch.cat((x.to(dev)[None], traj), dim=0), logs
+    return out[None], logs
 
 
 def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
