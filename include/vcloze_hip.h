@@ -497,6 +497,19 @@ int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora
                   float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias, void* bias_out,
                   int32_t out_features, int32_t in_features, int32_t rank, void* stream);
 
+/* vc_lora_merge_qkv: vc_lora_merge with the result's rows stored HEAD-PERMUTED, the order VcGemmProblem.kn_heads describes and
+ * option "qkv_heads" announces.  Added WITHOUT a change of VC_ABI_VERSION: detect by SYMBOL (look up vc_flux_load_tensor).  With
+ * H = qkv_heads and D = 128 * H, row r of the merged weight (and element r of bias_out) is stored at row
+ *     r < 2D:        192 * (r / 128) + r % 128
+ *     2D <= r < 3D:  192 * (u / 64) + 128 + u % 64,   u = r - 2D
+ *     r >= 3D:       r                                  (the MLP rows of a SingleStream block's linear1)
+ * The arithmetic, the roundings and the order of the sums are vc_lora_merge's; only the store address differs.  out (and bias_out)
+ * must not overlap w (bias) AT ALL - there is no in-place form, the piece a wave writes is not the piece it read - and
+ * out_features >= 3 * 128 * qkv_heads; both are VC_ERR_ARG.  qkv_heads == 0 is vc_lora_merge, in-place form included. */
+int vc_lora_merge_qkv(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                      float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias, void* bias_out,
+                      int32_t out_features, int32_t in_features, int32_t rank, int32_t qkv_heads, void* stream);
+
 /* ---- handle API: the whole of Flux.forward, and the whole fixed-grid Euler loop, behind one call each ----
  * vc_flux_forward       replaces Flux.forward                      (models/model.py:85-124)
  * vc_flux_sample_euler  replaces odeint(method="euler") over it    (transport/integrators.py:106-120, transport.py:361-410:
@@ -580,6 +593,46 @@ int vc_flux_set_option(void* handle, const char* name, int32_t value);
 int vc_flux_bind_lora(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
                       const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank);
 int vc_flux_set_lora_scale(void* handle, float scale);
+
+/* ---- a checkpoint AS STORED: from the tensors of FluxLoraWrapper.state_dict() (models/model.py:154-175; the checkpoints
+ * models/util.py:409-411 and visualcloze.py:111-112 load) in device memory to the bound, merged set - what Flux.prepare does with
+ * torch, behind the handle.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry points by SYMBOL - look up
+ * vc_flux_load_tensor.  No new struct.  Reading the file (.safetensors, .pth) stays with the caller, as image decoding does.
+ *   vc_flux_load_key     host only: key `index` (0, 1, ... until VC_ERR_ARG) of the state_dict the handle's VcFluxConfig implies, in
+ *                        state_dict order, with its shape: for every Linear `<path>.weight` [out, in], `<path>.bias` [out],
+ *                        `<path>.lora_A.weight` [rank, in], `<path>.lora_B.weight` [out, rank], `<path>.lora_B.bias` [out], and the
+ *                        QK-norm scales `...norm.query_norm.scale` / `...norm.key_norm.scale` [128].  The rank dimension is reported
+ *                        as -1: it is free per Linear.  name receives at most namelen - 1 characters and a terminator.
+ *   vc_flux_load_tensor  host only, launches nothing: records the device tensor `ptr` under `key` - dense, row-major, as stored.
+ *                        Weights, biases and scales are bf16 or F32 (is_f32); LoRA factors and lora_B.bias are bf16 (vc_lora_merge's
+ *                        rule).  An unknown key, a shape other than the key's (rank 0 .. 512, equal between a Linear's two factors)
+ *                        or an F32 factor is VC_ERR_ARG naming the key, and nothing is recorded.  ptr == NULL forgets the key.
+ *                        The pointers must stay valid until vc_flux_load_finish has returned and its stream work is done.
+ *   vc_flux_load_bytes   host only: the size of the arena the prepared set takes, every tensor 256-byte aligned (c = round up to 256):
+ *                          sum over the Linears outside the modulation stack of  c(2 out in) + c(2 out)          merged weight, bias
+ *                          + c(2 n_mod hidden) + c(2 n_mod)                      the stacked modulation matrix and its bias
+ *                          + 256 n_scales + c(4 n_scales)                        the bf16 scales, their F32 maxima
+ *                        n_mod = vc_flux_mod_offset(handle, NULL), n_scales = 4 depth + 2 depth_single_blocks.
+ *   vc_flux_load_finish  one vc_lora_merge_qkv launch per Linear with `lora_scale` (any F32 value) - qkv_heads = num_heads for every
+ *                        `*_attn.qkv` and `linear1`, out = the Linear's rows of the stacked matrix for the modulation Linears, rank 0
+ *                        for a Linear without a recorded pair (a lora_B.bias counts only with its pair; a Linear without any bias is
+ *                        bound without one, zeros in the stacked bias) - then ONE launch that casts every scale vector to bf16 and
+ *                        takes its max|.|, then one read of those maxima.  The results are bound under the names of
+ *                        vc_flux_bind_weight, and the options that describe them are set: "qkv_heads" = num_heads, "fuse_knorm" 1,
+ *                        "logit_bound_milli" = the largest block's 1.02 sqrt(128) log2(e) max|q scale| max|k scale| (held as F32)
+ *                        times 1000, rounded up - or 0 where a scale is NaN or that value is not below 2e9.  The handle is
+ *                        un-prepared (vc_flux_prepare again); "timestep_freqs" and "splitk_ws" stay separate binds.  A weight or
+ *                        scale that was never recorded, or one factor without the other, is VC_ERR_STATE naming the first missing
+ *                        key; option "lora_mode" 1, a NULL or misaligned arena or one smaller than vc_flux_load_bytes is VC_ERR_ARG;
+ *                        between vc_flux_sample_begin* and vc_flux_sample_end the call is VC_ERR_STATE - all found before the device
+ *                        is touched.  Synchronises `stream` once, at its end.  A second call - another lora_scale, re-recorded
+ *                        tensors - merges again into the arena given: the way to change a merged LoRA without a framework.
+ *   vc_flux_bound        host only: what is bound under a vc_flux_bind_weight name (any of the outputs may be NULL), or VC_ERR_STATE. */
+int vc_flux_load_key(void* handle, int32_t index, char* name, int32_t namelen, int64_t* shape, int32_t* ndim);
+int vc_flux_load_tensor(void* handle, const char* key, const void* ptr, int32_t is_f32, const int64_t* shape, int32_t ndim);
+int64_t vc_flux_load_bytes(void* handle);
+int vc_flux_load_finish(void* handle, float lora_scale, void* arena, int64_t arena_bytes, void* stream);
+int vc_flux_bound(void* handle, const char* name, const void** w, const void** bias, int32_t* rows, int32_t* cols, int64_t* ldw);
 /* ---- per-block taps: the residual streams after img_in / txt_in ("img_in", "txt_in"), after DoubleStream block i ("double.{i}.img",
  * "double.{i}.txt") and after SingleStream block i ("single.{i}": the joint stream, per sample the text rows, then the image rows).
  * Detect by SYMBOL (vc_flux_set_tap).  dst: the caller's bf16 device buffer of vc_flux_tap_shape's rows x cols (rows in the engine's

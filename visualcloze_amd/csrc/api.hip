@@ -207,6 +207,12 @@ int vc_lora_merge(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora
   return vc_lora_merge_launch(w, w_is_f32, ldw, lora_a, lda, lora_b, ldb, scale, out, ldo, bias, bias_is_f32, lora_b_bias, bias_out,
                               out_features, in_features, rank, S(stream), ERRBUF);
 }
+int vc_lora_merge_qkv(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                      float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias, void* bias_out,
+                      int32_t out_features, int32_t in_features, int32_t rank, int32_t qkv_heads, void* stream) {
+  return vc_lora_merge_qkv_launch(w, w_is_f32, ldw, lora_a, lda, lora_b, ldb, scale, out, ldo, bias, bias_is_f32, lora_b_bias, bias_out,
+                                  out_features, in_features, rank, qkv_heads, S(stream), ERRBUF);
+}
 int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
   return vc_randn_launch(out, dtype, n, seed, offset, S(stream), ERRBUF);
 }
@@ -223,6 +229,19 @@ int vc_flux_bind_weight(void* handle, const char* name, const void* w, const voi
 int vc_flux_bind_lora(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
                       const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank) {
   return vc_flux_bind_lora_impl(handle, name, lora_a, lda, lora_b, ldb, lora_b_bias, out_features, in_features, rank, ERRBUF);
+}
+int vc_flux_load_key(void* handle, int32_t index, char* name, int32_t namelen, int64_t* shape, int32_t* ndim) {
+  return vc_flux_load_key_impl(handle, index, name, namelen, shape, ndim, ERRBUF);
+}
+int vc_flux_load_tensor(void* handle, const char* key, const void* ptr, int32_t is_f32, const int64_t* shape, int32_t ndim) {
+  return vc_flux_load_tensor_impl(handle, key, ptr, is_f32, shape, ndim, ERRBUF);
+}
+int64_t vc_flux_load_bytes(void* handle) { return vc_flux_load_bytes_impl(handle); }
+int vc_flux_load_finish(void* handle, float lora_scale, void* arena, int64_t arena_bytes, void* stream) {
+  return vc_flux_load_finish_impl(handle, lora_scale, arena, arena_bytes, S(stream), ERRBUF);
+}
+int vc_flux_bound(void* handle, const char* name, const void** w, const void** bias, int32_t* rows, int32_t* cols, int64_t* ldw) {
+  return vc_flux_bound_impl(handle, name, w, bias, rows, cols, ldw, ERRBUF);
 }
 int vc_flux_set_lora_scale(void* handle, float scale) { return vc_flux_set_lora_scale_impl(handle, scale, ERRBUF); }
 int vc_flux_set_tap(void* handle, const char* name, void* dst) { return vc_flux_set_tap_impl(handle, name, dst, ERRBUF); }

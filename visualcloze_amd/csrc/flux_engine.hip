@@ -26,6 +26,7 @@
 #include "common.h"
 #include "vcloze_internal.h"
 #include "engine_core.h"
+#include "flux_keys.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -102,6 +103,10 @@ struct Flux : Buffers {
   std::unordered_map<std::string, Lora> lora;
   std::unordered_map<const void*, Lora> lora_of;
   std::vector<std::pair<Lin, int64_t>> mods;
+  // vc_flux_load_*: the state_dict keys of this configuration (flux_keys.h) and the caller's tensors recorded under them, by key index
+  vckeys::Table keys;
+  struct Loaded { const void* p; int f32; int64_t shape[2]; };
+  std::unordered_map<int, Loaded> loaded;
   float lora_scale = 1.0f;
   bool scale_stale = false;            // the scale changed after vc_flux_prepare ran txt_in / vector_in / guidance_in with the old one
   // per-block taps (vc_flux_set_tap): the caller's buffer of tap i, or null - img_in, txt_in, then (img, txt) of every double
@@ -786,6 +791,7 @@ int stage_send(Flux& f, void* dst, const void* staged, size_t bytes, hipStream_t
   return VC_OK;
 }
 int stage_end(Flux& f, hipStream_t s, Err e) {
+  if (!f.staged) HIP(hipEventCreateWithFlags(&f.staged, hipEventDisableTiming), "hipEventCreate");
   HIP(hipEventRecord(f.staged, s), "hipEventRecord");
   f.staged_pending = true;
   return VC_OK;
@@ -886,15 +892,16 @@ int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int e
   f->cfg = *cfg;
   f->D = cfg->hidden_size; f->H = cfg->num_heads; f->mlp = cfg->mlp_hidden;
   layout_modulation(*f);
+  f->keys = vckeys::build(*cfg);
   f->taps.assign(2 + 2 * (size_t)cfg->depth + (size_t)cfg->depth_single_blocks, nullptr);
+  // without a ROCm device the handle still answers its host-only calls (vc_flux_mod_offset, vc_flux_load_key / _tensor / _bytes,
+  // vc_flux_bound); whatever touches the device then fails with the runtime's own error
   int dev = 0;
   hipDeviceProp_t p;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) {
-    delete f;
-    FAIL(VC_ERR_HIP, "flux_create: no ROCm device");
+  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) {
+    f->n_cu = p.multiProcessorCount;
+    if (hipEventCreateWithFlags(&f->staged, hipEventDisableTiming) != hipSuccess) { delete f; FAIL(VC_ERR_HIP, "flux_create: hipEventCreate failed"); }
   }
-  f->n_cu = p.multiProcessorCount;
-  if (hipEventCreateWithFlags(&f->staged, hipEventDisableTiming) != hipSuccess) { delete f; FAIL(VC_ERR_HIP, "flux_create: hipEventCreate failed"); }
   *handle = f;
   return VC_OK;
 }
@@ -927,6 +934,149 @@ int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, cons
   f.resolved = false;
   f.prepared = false;   // the resolved per-block tables are rebuilt by the next vc_flux_prepare
   drop_graph(f);        // a captured step holds the old pointers
+  return VC_OK;
+}
+
+// ---------------------------------------------------------------- a checkpoint as stored -> the bound set (vc_flux_load_*)
+int vc_flux_load_key_impl(void* handle, int32_t index, char* name, int32_t namelen, int64_t* shape, int32_t* ndim, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  return vckeys::describe(f.keys, index, name, namelen, shape, ndim, err, errlen);
+}
+
+int vc_flux_load_tensor_impl(void* handle, const char* key, const void* ptr, int32_t is_f32, const int64_t* shape, int32_t ndim, char* err,
+                             int errlen) {
+  HANDLE(Flux, f, "flux");
+  const int idx = vckeys::find(f.keys, key);
+  if (idx < 0) FAIL(VC_ERR_ARG, "flux_load_tensor: key = '%s' is no state_dict key of this model (vc_flux_load_key lists them)", key ? key : "(null)");
+  if (!ptr) { f.loaded.erase(idx); return VC_OK; }
+  const vckeys::Key& k = f.keys.keys[idx];
+  TRY(vckeys::check_shape(k, shape, ndim, err, errlen));
+  const bool factor = k.kind == vckeys::LORA_A || k.kind == vckeys::LORA_B || k.kind == vckeys::LORA_B_BIAS;
+  if (factor && is_f32)
+    FAIL(VC_ERR_ARG, "flux_load_tensor: is_f32 = 1 for '%s': LoRA factors are merged on the bf16 matrix cores and must be stored as bf16", key);
+  if (k.kind == vckeys::LORA_A || k.kind == vckeys::LORA_B) {      // one rank per Linear
+    const int key0 = f.keys.linears[k.owner].key0;
+    auto other = f.loaded.find(key0 + (k.kind == vckeys::LORA_A ? vckeys::LORA_B : vckeys::LORA_A));
+    const int64_t rank = shape[k.kind == vckeys::LORA_A ? 0 : 1];
+    if (other != f.loaded.end() && other->second.shape[k.kind == vckeys::LORA_A ? 1 : 0] != rank)
+      FAIL(VC_ERR_ARG, "flux_load_tensor: rank = %lld of '%s' differs from the rank %lld of the Linear's other factor", (long long)rank, key,
+           (long long)other->second.shape[k.kind == vckeys::LORA_A ? 1 : 0]);
+  }
+  f.loaded[idx] = Flux::Loaded{ptr, is_f32 != 0, {shape[0], ndim > 1 ? shape[1] : 0}};
+  return VC_OK;
+}
+
+int64_t vc_flux_load_bytes_impl(void* handle) { return handle ? vckeys::arena_bytes(((Flux*)handle)->keys, ((Flux*)handle)->D) : -1; }
+
+int vc_flux_load_finish_impl(void* handle, float lora_scale, void* arena, int64_t arena_bytes, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  const vckeys::Table& t = f.keys;
+  // ---- every check before the device is touched
+  if (f.opt.lora_mode)
+    FAIL(VC_ERR_ARG, "flux_load_finish: option lora_mode = 1 runs un-merged weights (vc_flux_bind_weight + vc_flux_bind_lora); this call merges");
+  if (f.in_flight) FAIL(VC_ERR_STATE, "flux_load_finish: the weights cannot change between vc_flux_sample_begin and vc_flux_sample_end");
+  const int64_t need = vckeys::arena_bytes(t, f.D);
+  if (!aligned256(arena)) FAIL(VC_ERR_ARG, "flux_load_finish: arena must be a 256-byte aligned device pointer");
+  if (arena_bytes < need)
+    FAIL(VC_ERR_ARG, "flux_load_finish: arena_bytes = %lld, the prepared set takes %lld (vc_flux_load_bytes)", (long long)arena_bytes, (long long)need);
+  auto have = [&](int idx) -> const Flux::Loaded* {
+    auto it = f.loaded.find(idx);
+    return it == f.loaded.end() ? nullptr : &it->second;
+  };
+  for (size_t i = 0; i < t.keys.size(); ++i)
+    if ((t.keys[i].kind == vckeys::WEIGHT || t.keys[i].kind == vckeys::SCALE) && !have((int)i))
+      FAIL(VC_ERR_STATE, "flux_load_finish: '%s' was never recorded (vc_flux_load_tensor)", t.keys[i].name.c_str());
+  for (const vckeys::Linear& l : t.linears)
+    if (!have(l.key0 + vckeys::LORA_A) != !have(l.key0 + vckeys::LORA_B))
+      FAIL(VC_ERR_STATE, "flux_load_finish: '%s' was recorded without the Linear's other factor",
+           t.keys[l.key0 + (have(l.key0 + vckeys::LORA_A) ? vckeys::LORA_A : vckeys::LORA_B)].name.c_str());
+  // ---- the arena: the formula of vc_flux_load_bytes, in its order
+  Carver c{(char*)arena};
+  std::vector<std::pair<std::string, Lin>> bind;
+  std::vector<bf16_t*> wout(t.linears.size()), bout(t.linears.size());
+  for (size_t i = 0; i < t.linears.size(); ++i) {
+    const vckeys::Linear& l = t.linears[i];
+    if (l.mod_off >= 0) continue;
+    wout[i] = c.take<bf16_t>((int64_t)l.out * l.in);
+    bout[i] = c.take<bf16_t>(l.out);
+  }
+  bf16_t* mod_w = c.take<bf16_t>(t.n_mod * f.D);
+  bf16_t* mod_b = c.take<bf16_t>(t.n_mod);
+  const int n_scales = (int)t.scales.size();
+  bf16_t* scales = c.take<bf16_t>((int64_t)128 * n_scales);       // 256 bytes each
+  float* amax = c.take<float>(n_scales);
+  // ---- one merge launch per Linear (a modulation Linear without any bias leaves zeros in the stacked bias, as Flux.prepare does)
+  HIP(hipMemsetAsync(mod_b, 0, (size_t)t.n_mod * 2, s), "hipMemsetAsync");
+  for (size_t i = 0; i < t.linears.size(); ++i) {
+    const vckeys::Linear& l = t.linears[i];
+    const Flux::Loaded *w = have(l.key0 + vckeys::WEIGHT), *b = have(l.key0 + vckeys::BIAS), *la = have(l.key0 + vckeys::LORA_A),
+                       *lb = have(l.key0 + vckeys::LORA_B), *lbb = have(l.key0 + vckeys::LORA_B_BIAS);
+    const int rank = la ? (int)la->shape[0] : 0;
+    if (!rank) la = lb = lbb = nullptr;                            // no pair: a conversion / copy (lora_B.bias belongs to the pair)
+    const bool mod = l.mod_off >= 0;
+    bf16_t* out = mod ? mod_w + l.mod_off * f.D : wout[i];
+    bf16_t* bias_out = !(b || lbb) ? nullptr : mod ? mod_b + l.mod_off : bout[i];
+    TRY(vc_lora_merge_qkv_launch(w->p, w->f32, l.in, la ? la->p : nullptr, l.in, lb ? lb->p : nullptr, rank, lora_scale, out, mod ? f.D : l.in,
+                                 b ? b->p : nullptr, b ? b->f32 : 0, lbb ? lbb->p : nullptr, bias_out, l.out, l.in, rank, l.qkv ? f.H : 0, s,
+                                 err, errlen));
+    if (!mod) { Lin x; x.w = out; x.b = bias_out; x.N = l.out; x.K = l.in; x.ldw = l.in; bind.push_back({l.name, x}); }
+  }
+  { Lin x; x.w = mod_w; x.b = mod_b; x.N = (int)t.n_mod; x.K = f.D; x.ldw = f.D; bind.push_back({"modulation", x}); }
+  // ---- the scales: one launch (per VC_SCALE_VECTORS of them), one read of their maxima
+  for (int i0 = 0; i0 < n_scales; i0 += VC_SCALE_VECTORS) {
+    VcScaleVectors v;
+    memset(&v, 0, sizeof(v));
+    const int n = std::min(VC_SCALE_VECTORS, n_scales - i0);
+    for (int i = 0; i < n; ++i) {
+      const Flux::Loaded* sc = have(vckeys::find(t, t.scales[i0 + i].c_str()));
+      v.src[i] = sc->p; v.f32[i] = (uint8_t)sc->f32;
+    }
+    TRY(vc_scale_cast_launch(v, n, scales + (int64_t)128 * i0, 128, amax + i0, s, err, errlen));
+  }
+  std::vector<float> mx(n_scales);
+  HIP(hipMemcpyAsync(mx.data(), amax, sizeof(float) * n_scales, hipMemcpyDeviceToHost, s), "hipMemcpyAsync (QK-norm maxima)");
+  HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
+  // the cap Flux.prepare / Flux.handle() hand over: the largest per-block bound, in thousandths, rounded up; 0 (no bounded softmax
+  // anywhere) where a scale is NaN or the bound leaves the option's range.  A double block's four vectors, then a single block's two
+  float cap = 0.0f;
+  for (int i = 0; i < n_scales;) {
+    const int per = i < 4 * f.cfg.depth ? 4 : 2;
+    double q = 0, k = 0;
+    bool nan = false;
+    for (int j = 0; j < per; ++j) {
+      const float v = mx[i + j];
+      if (v != v) nan = true;
+      else if (j % 2 == 0) q = std::max(q, (double)v);
+      else k = std::max(k, (double)v);
+    }
+    cap = std::max(cap, nan ? 1e30f : logit_bound_of(q, k));
+    i += per;
+  }
+  const int milli = cap > 0.0f && cap < 2e6f ? (int)ceil((double)cap * 1000.0) : 0;
+  // ---- bind, as vc_flux_bind_weight would
+  for (auto& kv : bind) f.bound[kv.first] = kv.second;
+  for (int i = 0; i < n_scales; ++i) {
+    Lin x; x.w = scales + (int64_t)128 * i; x.b = nullptr; x.N = 1; x.K = 128; x.ldw = 128;
+    f.bound[t.scales[i]] = x;
+  }
+  f.opt.qkv_heads = f.H; f.opt.fuse_knorm = 1; f.opt.logit_bound_milli = milli;
+  f.resolved = false;
+  f.prepared = false;
+  drop_graph(f);
+  return VC_OK;
+}
+
+int vc_flux_bound_impl(void* handle, const char* name, const void** w, const void** bias, int32_t* rows, int32_t* cols, int64_t* ldw, char* err,
+                       int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!name) FAIL(VC_ERR_ARG, "flux_bound: null name");
+  auto it = f.bound.find(name);
+  if (it == f.bound.end()) FAIL(VC_ERR_STATE, "flux_bound: nothing is bound under '%s'", name);
+  if (w) *w = it->second.w;
+  if (bias) *bias = it->second.b;
+  if (rows) *rows = it->second.N;
+  if (cols) *cols = it->second.K;
+  if (ldw) *ldw = it->second.ldw;
   return VC_OK;
 }
 

@@ -22,6 +22,10 @@
 // MFMA row that reads it, 0..15) - the 16 lanes ds_read_b128 serves together then touch 16 different chunks.
 // Shapes: any O, I, 1 <= R <= 512; VEC = every base 16-byte aligned, I and every row stride multiples of 8 elements - otherwise
 // the same kernel runs with element-wise global accesses (the tiny test model, in = 12).  R == 0: a conversion / copy of W.
+// PERM (vc_lora_merge_qkv, qkv_heads = H > 0): the same arithmetic, and row r of the result is STORED at row dest_row(r) - the
+// head-permuted order of VcGemmProblem.kn_heads (the inverse of hip.qkv_head_permutation), rows >= 3 * 128 H (linear1's MLP rows)
+// where they were.  A wave's 16 rows start at a multiple of 16, which divides 64 and 128: they stay 16 consecutive rows, and every
+// access keeps its width.  No in-place form: the piece a wave writes is not the piece it read.
 #include "common.h"
 #include "vcloze_internal.h"
 
@@ -42,7 +46,14 @@ struct LoraMergeArgs {
   int O, I, R;
   int ks;            // LDS row length in elements: R rounded up to 128 (0 with R == 0)
   int rows_per_wg;   // multiple of 128
+  int qd;            // PERM only: 128 * qkv_heads
 };
+// where row r of a qkv weight [3 * D + ..., K] goes: 2H blocks of 192 rows = [query / key head t | V rows 64 t .. 64 t + 63]
+VC_DEV int dest_row(int r, int D) {
+  if (r < 2 * D) return 192 * (r >> 7) + (r & 127);
+  if (r < 3 * D) return 192 * ((r - 2 * D) >> 6) + 128 + ((r - 2 * D) & 63);
+  return r;
+}
 
 // 8 consecutive bf16 of a row of n elements starting at col, zero beyond n
 template <bool VEC>
@@ -64,7 +75,7 @@ VC_DEV float scale_add(float w, float s, float d) {
   return w + sd;
 }
 
-template <bool VEC, bool WF32>
+template <bool VEC, bool WF32, bool PERM>
 __global__ __launch_bounds__(LM_THREADS) void lora_merge_kernel(const LoraMergeArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lm_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(LM_THREADS) void lora_merge_kernel(const LoraMergeA
       }
     }
     if (!ok) continue;
-    bf16_t* orow = p.out + (int64_t)o * p.ldo;
+    bf16_t* orow = p.out + (int64_t)(PERM ? dest_row(o, p.qd) : o) * p.ldo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int col = i0 + 32 * q + 8 * g;
@@ -178,12 +189,12 @@ __global__ __launch_bounds__(LM_THREADS) void lora_merge_kernel(const LoraMergeA
   }
 }
 
-// bias_out[o] = bf16(b[o] + s * bB[o]);  b NULL = 0;  bB NULL: a conversion / copy of b
-__global__ __launch_bounds__(256) void lora_bias_kernel(const void* b, int b_f32, const bf16_t* bB, float s, bf16_t* out, int n) {
+// bias_out[o] = bf16(b[o] + s * bB[o]);  b NULL = 0;  bB NULL: a conversion / copy of b;  qd > 0: stored at dest_row(o)
+__global__ __launch_bounds__(256) void lora_bias_kernel(const void* b, int b_f32, const bf16_t* bB, float s, bf16_t* out, int n, int qd) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= n) return;
   const float v = !b ? 0.0f : b_f32 ? ((const float*)b)[o] : bf2f(((const bf16_t*)b)[o]);
-  out[o] = f2bf(bB ? scale_add(v, s, bf2f(bB[o])) : v);
+  out[qd ? dest_row(o, qd) : o] = f2bf(bB ? scale_add(v, s, bf2f(bB[o])) : v);
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -198,19 +209,22 @@ inline bool overlap(uintptr_t alo, uintptr_t ahi, uintptr_t blo, uintptr_t bhi) 
 
 #define LM_FAIL(...) do { snprintf(err, errlen, __VA_ARGS__); return VC_ERR_ARG; } while (0)
 
-int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
-                         float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
-                         void* bias_out, int32_t O, int32_t I, int32_t R, hipStream_t s, char* err, int errlen) {
+int vc_lora_merge_qkv_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                             float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
+                             void* bias_out, int32_t O, int32_t I, int32_t R, int32_t qkv_heads, hipStream_t s, char* err, int errlen) {
   // ---- every check before the first HIP call
   if (O <= 0 || I <= 0) LM_FAIL("lora_merge: out_features and in_features must be positive (got %d, %d)", O, I);
   if (R < 0 || R > LM_MAX_RANK) LM_FAIL("lora_merge: rank %d outside 0 .. %d", R, LM_MAX_RANK);
   if (!w || !out) LM_FAIL("lora_merge: null weight or out");
+  if (qkv_heads < 0 || (int64_t)qkv_heads * 384 > O)
+    LM_FAIL("lora_merge: qkv_heads = %d needs out_features >= 3 * 128 * qkv_heads, got %d", qkv_heads, O);
   if (R > 0 && (!lora_a || !lora_b)) LM_FAIL("lora_merge: null LoRA factor with rank %d", R);
   if (ldw < I || ldo < I) LM_FAIL("lora_merge: row stride of weight (%lld) or out (%lld) shorter than a row of %d", (long long)ldw, (long long)ldo, I);
   if (R > 0 && (lda < I || ldb < R)) LM_FAIL("lora_merge: row stride of lora_a (%lld, row %d) or lora_b (%lld, row %d) shorter than a row", (long long)lda, I, (long long)ldb, R);
   uintptr_t wlo, whi, olo, ohi;
   span(w, O, I, ldw, w_is_f32 ? 4 : 2, &wlo, &whi);
   span(out, O, I, ldo, 2, &olo, &ohi);
+  if (qkv_heads > 0 && overlap(wlo, whi, olo, ohi)) LM_FAIL("lora_merge: out overlaps weight (with qkv_heads > 0 there is no in-place form)");
   if (out == w) {
     if (w_is_f32) LM_FAIL("lora_merge: an f32 weight cannot be merged in place (out is bf16)");
     if (ldo != ldw) LM_FAIL("lora_merge: in place (out == weight) needs equal row strides, got %lld and %lld", (long long)ldw, (long long)ldo);
@@ -227,6 +241,7 @@ int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const voi
   if (!bias_out && (bias || lora_b_bias)) LM_FAIL("lora_merge: a bias was passed but bias_out is null");
   if (bias_out && !bias && !lora_b_bias) LM_FAIL("lora_merge: bias_out without bias or lora_b_bias");
   if (bias_out && bias_out == bias && bias_is_f32) LM_FAIL("lora_merge: an f32 bias cannot be merged in place (bias_out is bf16)");
+  if (bias_out && bias_out == bias && qkv_heads > 0) LM_FAIL("lora_merge: bias_out overlaps bias (with qkv_heads > 0 there is no in-place form)");
   if (bias_out) {
     uintptr_t blo = (uintptr_t)bias_out, bhi = blo + (uintptr_t)O * 2;
     if (overlap(blo, bhi, olo, ohi)) LM_FAIL("lora_merge: bias_out overlaps out");
@@ -241,6 +256,7 @@ int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const voi
   p.ldw = ldw; p.lda = lda; p.ldb = ldb; p.ldo = ldo;
   p.s = scale; p.O = O; p.I = I; p.R = R;
   p.ks = (R + 127) / 128 * 128;
+  p.qd = 128 * qkv_heads;
   // rows per workgroup: 256, halved to 128 (one pass of the 8 waves) while the launch has fewer than 1024 workgroups.  Measured
   // on MI355X the choice moves the time by a few per cent either way (thresholds 256 / 512 / 1024 at 3072 x 3072 .. 9216 x 3072).
   const int strips = (I + LM_TI - 1) / LM_TI;
@@ -250,11 +266,14 @@ int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const voi
   p.rows_per_wg = rows;
   const bool vec = aligned16(w) && aligned16(out) && I % 8 == 0 && ldw % 8 == 0 && ldo % 8 == 0 &&
                    (R == 0 || (aligned16(lora_a) && aligned16(lora_b) && lda % 8 == 0 && ldb % 8 == 0));
-  void (*fn)(const LoraMergeArgs) = vec ? (w_is_f32 ? lora_merge_kernel<true, true> : lora_merge_kernel<true, false>)
-                                        : (w_is_f32 ? lora_merge_kernel<false, true> : lora_merge_kernel<false, false>);
+  void (*const fns[8])(const LoraMergeArgs) = {
+      lora_merge_kernel<false, false, false>, lora_merge_kernel<false, true, false>, lora_merge_kernel<true, false, false>,
+      lora_merge_kernel<true, true, false>,   lora_merge_kernel<false, false, true>, lora_merge_kernel<false, true, true>,
+      lora_merge_kernel<true, false, true>,   lora_merge_kernel<true, true, true>};
   const int lds = LM_TI * p.ks * 2;     // 32 KiB per 128 of rank: 128 KiB at rank 512
-  static VcOncePerDevice attr_done[4];
-  const int slot = (vec ? 2 : 0) + (w_is_f32 ? 1 : 0);
+  static VcOncePerDevice attr_done[8];
+  const int slot = (qkv_heads > 0 ? 4 : 0) + (vec ? 2 : 0) + (w_is_f32 ? 1 : 0);
+  void (*fn)(const LoraMergeArgs) = fns[slot];
   if (attr_done[slot].need()) {
     hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LM_TI * LM_MAX_RANK * 2);
     if (e != hipSuccess) { snprintf(err, errlen, "lora_merge: hipFuncSetAttribute: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
@@ -264,9 +283,16 @@ int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const voi
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && bias_out) {
     hipLaunchKernelGGL(lora_bias_kernel, dim3((O + 255) / 256), dim3(256), 0, s, bias, bias_is_f32, (const bf16_t*)lora_b_bias, scale,
-                       (bf16_t*)bias_out, O);
+                       (bf16_t*)bias_out, O, p.qd);
     e = hipGetLastError();
   }
   if (e != hipSuccess) { snprintf(err, errlen, "lora_merge: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
   return VC_OK;
+}
+
+int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                         float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
+                         void* bias_out, int32_t O, int32_t I, int32_t R, hipStream_t s, char* err, int errlen) {
+  return vc_lora_merge_qkv_launch(w, w_is_f32, ldw, lora_a, lda, lora_b, ldb, scale, out, ldo, bias, bias_is_f32, lora_b_bias, bias_out, O, I,
+                                  R, 0, s, err, errlen);
 }

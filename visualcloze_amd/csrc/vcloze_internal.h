@@ -107,6 +107,15 @@ int vc_conv3x3_launch(const void* x, const void* w, const void* bias, void* out,
 int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
                          float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
                          void* bias_out, int32_t out_features, int32_t in_features, int32_t rank, hipStream_t s, char* err, int errlen);
+// the same with the result's rows stored head-permuted (vc_lora_merge_qkv; qkv_heads 0 = vc_lora_merge_launch)
+int vc_lora_merge_qkv_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
+                             float scale, void* out, int64_t ldo, const void* bias, int32_t bias_is_f32, const void* lora_b_bias,
+                             void* bias_out, int32_t out_features, int32_t in_features, int32_t rank, int32_t qkv_heads, hipStream_t s,
+                             char* err, int errlen);
+// flux_load.hip: n <= VC_SCALE_VECTORS vectors of 128 values (bf16, or f32 where f32[i]) -> bf16 rows of `out` and max|.| of each
+constexpr int VC_SCALE_VECTORS = 256;
+struct VcScaleVectors { const void* src[VC_SCALE_VECTORS]; uint8_t f32[VC_SCALE_VECTORS]; };
+int vc_scale_cast_launch(const VcScaleVectors& v, int n, void* out, int64_t out_stride, float* amax, hipStream_t s, char* err, int errlen);
 int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen);
 int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
                            int errlen);
@@ -139,6 +148,13 @@ int vc_flux_bind_weight_impl(void* handle, const char* name, const void* w, cons
                              char* err, int errlen);
 int vc_flux_bind_lora_impl(void* handle, const char* name, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,
                            const void* lora_b_bias, int32_t out_features, int32_t in_features, int32_t rank, char* err, int errlen);
+int vc_flux_load_key_impl(void* handle, int32_t index, char* name, int32_t namelen, int64_t* shape, int32_t* ndim, char* err, int errlen);
+int vc_flux_load_tensor_impl(void* handle, const char* key, const void* ptr, int32_t is_f32, const int64_t* shape, int32_t ndim, char* err,
+                             int errlen);
+int64_t vc_flux_load_bytes_impl(void* handle);
+int vc_flux_load_finish_impl(void* handle, float lora_scale, void* arena, int64_t arena_bytes, hipStream_t s, char* err, int errlen);
+int vc_flux_bound_impl(void* handle, const char* name, const void** w, const void** bias, int32_t* rows, int32_t* cols, int64_t* ldw, char* err,
+                       int errlen);
 int vc_flux_set_lora_scale_impl(void* handle, float scale, char* err, int errlen);
 int vc_flux_set_tap_impl(void* handle, const char* name, void* dst, char* err, int errlen);
 int vc_flux_tap_shape_impl(void* handle, const char* name, int64_t* rows, int32_t* cols, char* err, int errlen);

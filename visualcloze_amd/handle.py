@@ -121,7 +121,7 @@ class FluxHandle(_Handle):
     _destroy = "vc_flux_destroy"
     MAX_BATCH = 4      # samples per launch sequence, as engine.FluxEngine
 
-    def __init__(self, params, weights, dev: torch.device):
+    def __init__(self, params, weights, dev: torch.device, _load=None):
         self.params, self.dev, self.W = params, dev, weights
         D = params.hidden_size
         cfg = hip.FluxConfig(params.in_channels, params.out_channels, params.vec_in_dim, params.context_in_dim, D, params.num_heads,
@@ -131,18 +131,11 @@ class FluxHandle(_Handle):
         with torch.cuda.device(dev):
             hip._check(hip.lib().vc_flux_create(C.byref(cfg), C.byref(self.h)), "vc_flux_create")
         L = hip.lib()
-        for name, off in weights.mod_off.items():          # the stacking order is part of the ABI
-            if L.vc_flux_mod_offset(self.h, name.encode()) != off:
-                raise hip.VclozeHipError(f"modulation row offset of {name} differs between model.prepare and libvcloze_hip.so")
-        if L.vc_flux_mod_offset(self.h, None) != weights.n_mod:
-            raise hip.VclozeHipError("stacked modulation size differs between model.prepare and libvcloze_hip.so")
-        for name, w in weights.w.items():
-            if name.endswith(".linear1.qkv") or name.endswith(".linear1.mlp"):
-                continue                                    # row ranges of linear1, which is bound whole
-            b = weights.b.get(name)
-            rows, cols = (1, w.numel()) if w.dim() == 1 else tuple(w.shape)
-            self._bind(name, w, b, rows, cols)
-        self._bind("modulation", weights.mod_w, weights.mod_b, *weights.mod_w.shape)
+        self._opts: Dict[str, int] = {}
+        if _load is not None:                               # from_state_dict: the library prepares and binds the set itself
+            weights = self.W = self._load(*_load)
+        else:
+            self._bind_prepared(weights)
         hip._check(L.vc_flux_bind_weight(self.h, b"timestep_freqs", weights.temb_freqs.data_ptr(), None, 1, 128, 128),
                    "vc_flux_bind_weight(timestep_freqs)")      # torch's own f32 table: bit-equal to the Python-ordered plan
         # ONE split-K scratch for every geometry of this handle (its launches are ordered on one stream), instead of 100 MB carved
@@ -151,7 +144,6 @@ class FluxHandle(_Handle):
         nf = self._sk_ws.numel() // 4
         hip._check(L.vc_flux_bind_weight(self.h, b"splitk_ws", self._sk_ws.data_ptr(), None, 1, nf, nf), "vc_flux_bind_weight(splitk_ws)")
         self._ws: Dict[tuple, torch.Tensor] = {}
-        self._opts: Dict[str, int] = {}
         self._lora: Dict[str, tuple] = {}
         self._taps: Dict[str, torch.Tensor] = {}
         self.lora_mode = 0
@@ -175,7 +167,121 @@ class FluxHandle(_Handle):
         self._host = _HostCopies()
         # the storage order of the bound qkv rows (head-permuted or natural) and the logit bound are PROPERTIES OF THE
         # WEIGHTS, not knobs: a handle built directly must un-permute exactly as model.handle()'s does
-        self.set_options()
+        if _load is None:
+            self.set_options()
+        else:           # vc_flux_load_finish has set what describes the weights; the rest are the defaults
+            self.set_options(fuse_knorm=True, logit_bound=self.W.logit_bound)
+
+    def _bind_prepared(self, weights) -> None:
+        L = hip.lib()
+        for name, off in weights.mod_off.items():          # the stacking order is part of the ABI
+            if L.vc_flux_mod_offset(self.h, name.encode()) != off:
+                raise hip.VclozeHipError(f"modulation row offset of {name} differs between model.prepare and libvcloze_hip.so")
+        if L.vc_flux_mod_offset(self.h, None) != weights.n_mod:
+            raise hip.VclozeHipError("stacked modulation size differs between model.prepare and libvcloze_hip.so")
+        for name, w in weights.w.items():
+            if name.endswith(".linear1.qkv") or name.endswith(".linear1.mlp"):
+                continue                                    # row ranges of linear1, which is bound whole
+            b = weights.b.get(name)
+            rows, cols = (1, w.numel()) if w.dim() == 1 else tuple(w.shape)
+            self._bind(name, w, b, rows, cols)
+        self._bind("modulation", weights.mod_w, weights.mod_b, *weights.mod_w.shape)
+
+    # ------------------------------------------------------------------ a checkpoint as stored (vc_flux_load_*)
+    @classmethod
+    def from_state_dict(cls, params, tensors, lora_scale: float = 1.0, dev=None) -> "FluxHandle":
+        """A handle over a checkpoint AS STORED: `tensors` maps the state_dict() keys of FluxLoraWrapper (`load_keys()` lists them
+        with their shapes) to tensors on the device - base weights, biases and QK-norm scales bf16 or f32, LoRA factors bf16; pairs
+        may be missing.  The library merges (vc_lora_merge_qkv, one launch per Linear, `lora_scale` applied in f32), stacks the
+        modulation Linears, permutes the qkv rows, casts the scales and binds the result (vc_flux_load_finish) into an arena this
+        object allocates and keeps; `W` holds torch views of what is bound (vc_flux_bound).  No torch arithmetic touches a weight.
+        `reload(lora_scale)` merges again into the same arena."""
+        first = next(iter(tensors.values()))
+        dev = torch.device(dev) if dev is not None else first.device
+        return cls(params, None, dev, _load=(tensors, float(lora_scale)))
+
+    def load_keys(self) -> list:
+        """vc_flux_load_key: [(key, shape), ...] in state_dict order; the LoRA rank is reported as -1"""
+        out, buf, shape, nd = [], C.create_string_buffer(160), (C.c_int64 * 2)(), C.c_int32(0)
+        while hip.lib().vc_flux_load_key(self.h, len(out), buf, 160, shape, C.byref(nd)) == 0:
+            out.append((buf.value.decode(), tuple(shape[:nd.value])))
+        return out
+
+    def bound(self, name: str):
+        """vc_flux_bound: (w, bias) bound under a vc_flux_bind_weight name as (pointer, rows, cols, row stride) and the bias pointer"""
+        w, b, rows, cols, ld = C.c_void_p(), C.c_void_p(), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        hip._check(hip.lib().vc_flux_bound(self.h, name.encode(), C.byref(w), C.byref(b), C.byref(rows), C.byref(cols), C.byref(ld)),
+                   f"vc_flux_bound({name})")
+        return w.value, b.value, rows.value, cols.value, ld.value
+
+    def _view(self, ptr, rows, cols):
+        """the [rows, cols] bf16 tensor at device address `ptr` of the arena"""
+        off = ptr - self._arena.data_ptr()
+        return self._arena[off:off + 2 * rows * cols].view(torch.bfloat16).view(rows, cols)
+
+    def _load(self, tensors, lora_scale):
+        from .engine import PreparedWeights
+        L = hip.lib()
+        self._loaded = {}
+        for key, t in tensors.items():
+            t = t.detach()
+            if not t.is_cuda or t.device != self.dev or t.dtype not in (torch.bfloat16, torch.float32):
+                raise hip.VclozeHipError(f"from_state_dict: {key} must be a bf16 / f32 tensor on {self.dev}, got {t.dtype} on {t.device}")
+            t = t.contiguous()
+            shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+            hip._check(L.vc_flux_load_tensor(self.h, key.encode(), t.data_ptr(), int(t.dtype == torch.float32), shape, t.dim()),
+                       f"vc_flux_load_tensor({key})")
+            self._loaded[key] = t
+        n = L.vc_flux_load_bytes(self.h)
+        self._arena = torch.empty(n + 256, dtype=torch.uint8, device=self.dev)
+        self._finish(lora_scale)
+        w, b = {}, {}
+        D, H = self.params.hidden_size, self.params.num_heads
+        mods = {}
+        for key, shape in self.load_keys():
+            if key.endswith(".scale"):
+                w[key] = self._view(*self.bound(key)[:1], 1, 128).reshape(128)
+            elif key.endswith(".weight") and ".lora_" not in key:
+                name = key[:-len(".weight")]
+                off = L.vc_flux_mod_offset(self.h, name.encode())
+                if off >= 0:
+                    mods[name] = off
+                    continue
+                wp, bp, rows, cols, _ = self.bound(name)
+                w[name] = self._view(wp, rows, cols)
+                b[name] = None if not bp else self._view(bp, 1, rows).reshape(rows)
+                if name.endswith(".linear1"):
+                    w[name + ".qkv"], w[name + ".mlp"] = w[name][:3 * D], w[name][3 * D:]
+                    b[name + ".qkv"], b[name + ".mlp"] = (None, None) if b[name] is None else (b[name][:3 * D], b[name][3 * D:])
+        wp, bp, rows, cols, _ = self.bound("modulation")
+        half = 128
+        freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half).to(self.dev)
+        # the per-block logit bounds as model.Flux.prepare holds them (read by engine-side tools; the C plan computes its own)
+        amax = {k: float(t.float().abs().max()) for k, t in w.items() if k.endswith(("query_norm.scale", "key_norm.scale"))}
+        c_log = 1.02 * 11.313708498984761 * 1.4426950408889634
+        bounds = {}
+        for pf in sorted({k.split(".img_attn.")[0].split(".txt_attn.")[0].split(".norm.")[0] for k in amax}):
+            qm = max(v for k, v in amax.items() if k.startswith(pf + ".") and k.endswith("query_norm.scale"))
+            km = max(v for k, v in amax.items() if k.startswith(pf + ".") and k.endswith("key_norm.scale"))
+            bnd = c_log * qm * km
+            bounds[pf] = float(torch.tensor(bnd, dtype=torch.float32)) if bnd == bnd else 1e30
+        bound = max(bounds.values()) if bounds else 0.0
+        # what vc_flux_load_finish set is remembered as set, so that set_options never overrides the library's values with these
+        self._opts.update(qkv_heads=H, fuse_knorm=1, logit_bound_milli=int(math.ceil(bound * 1000)) if 0 < bound < 2e6 else 0)
+        return PreparedWeights(w=w, b=b, mod_w=self._view(wp, rows, cols), mod_b=self._view(bp, 1, rows).reshape(rows), mod_off=mods,
+                               n_mod=rows, temb_freqs=freqs, ref=None, qkv_heads=H, logit_bound=bound, logit_bounds=bounds)
+
+    def _finish(self, lora_scale: float) -> None:
+        base, nbytes = self._aligned(self._arena)
+        with torch.cuda.device(self.dev):
+            hip._check(hip.lib().vc_flux_load_finish(self.h, float(lora_scale), base, nbytes, hip.cur_stream()), "vc_flux_load_finish")
+        self.lora_scale = float(lora_scale)
+
+    def reload(self, lora_scale: float) -> None:
+        """vc_flux_load_finish once more with another scale: the same arena (the views of `W` see the new values), the handle
+        un-prepared"""
+        self._finish(lora_scale)
+        self.geom = None
 
     def _bind(self, name, w, b, rows, cols):
         hip._bf16(w, name)

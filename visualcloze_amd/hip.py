@@ -242,11 +242,18 @@ SYMBOLS = {
     "vc_randn": (C.c_int, [_vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp]),
     "vc_randn_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, C.c_uint64, C.c_uint64, _vp]),
     "vc_lora_merge": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vc_lora_merge_qkv": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
+                                    _vp]),
     "vc_flux_create": (C.c_int, [C.POINTER(FluxConfig), C.POINTER(_vp)]),
     "vc_flux_destroy": (C.c_int, [_vp]),
     "vc_flux_bind_weight": (C.c_int, [_vp, C.c_char_p, _vp, _vp, _i32, _i32, _i64]),
     "vc_flux_bind_lora": (C.c_int, [_vp, C.c_char_p, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32]),
     "vc_flux_set_lora_scale": (C.c_int, [_vp, C.c_float]),
+    "vc_flux_load_key": (C.c_int, [_vp, _i32, C.c_char_p, _i32, C.POINTER(_i64), C.POINTER(_i32)]),
+    "vc_flux_load_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i32, C.POINTER(_i64), _i32]),
+    "vc_flux_load_bytes": (_i64, [_vp]),
+    "vc_flux_load_finish": (C.c_int, [_vp, C.c_float, _vp, _i64, _vp]),
+    "vc_flux_bound": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
     "vc_flux_set_tap": (C.c_int, [_vp, C.c_char_p, _vp]),
     "vc_flux_tap_shape": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64), C.POINTER(_i32)]),
     "vc_flux_mod_offset": (_i64, [_vp, C.c_char_p]),
@@ -507,12 +514,14 @@ def linear(a, w, bias=None, out=None, epi=EPI_BIAS, res=None, gate=None, tile_cf
     return out
 
 
-def lora_merge(weight, lora_a, lora_b, scale, out=None, bias=None, lora_b_bias=None, stream=None):
+def lora_merge(weight, lora_a, lora_b, scale, out=None, bias=None, lora_b_bias=None, stream=None, qkv_heads=0):
     """(W', b') = (bf16(W + scale * B @ A), bf16(b + scale * b_B)): LinearLora (models/modules/lora.py:92-98) folded into one
     weight by vc_lora_merge.  `weight` [out, in] and `bias` [out]: bf16 or f32; `lora_a` [r, in], `lora_b` [out, r],
     `lora_b_bias` [out]: bf16 (f32 factors are not bf16 values - the matrix cores would round them - and are refused); both
     factors None = rank 0, a conversion of `weight` / `bias`.  `out`: a [out, in] bf16 view with any row stride (rows of a
-    stacked matrix), `weight` itself (bf16: merged in place) or None (a new tensor).  Returns (out, bias_out or None)."""
+    stacked matrix), `weight` itself (bf16: merged in place) or None (a new tensor).  Returns (out, bias_out or None).
+    `qkv_heads` H > 0 (vc_lora_merge_qkv): the rows [0, 3 * 128 * H) of the result and of the bias are stored head-permuted, i.e.
+    `merged[:3 * 128 * H][qkv_head_permutation(H)]`; `out` must then not be `weight`."""
     if weight.dim() != 2 or not weight.is_cuda or weight.dtype not in (torch.bfloat16, torch.float32) or weight.stride(1) != 1:
         raise VclozeHipError(f"lora_merge weight: need a 2-D CUDA bf16 / f32 tensor with contiguous last dim, got {weight.dtype} "
                              f"{tuple(weight.shape)} on {weight.device}")
@@ -549,10 +558,14 @@ def lora_merge(weight, lora_a, lora_b, scale, out=None, bias=None, lora_b_bias=N
         if not t.is_cuda or t.dtype not in ok or tuple(t.shape) != (O,) or not t.is_contiguous():
             raise VclozeHipError(f"lora_merge {n}: need a contiguous CUDA [{O}] tensor of {ok}, got {t.dtype} {tuple(t.shape)}")
         bias_out = torch.empty(O, dtype=torch.bfloat16, device=weight.device) if bias_out is None else bias_out
-    _check(lib().vc_lora_merge(weight.data_ptr(), int(weight.dtype == torch.float32), weight.stride(0),
-                               _p(lora_a), lora_a.stride(0) if R else 0, _p(lora_b), lora_b.stride(0) if R else 0, float(scale),
-                               out.data_ptr(), out.stride(0), _p(bias), int(bias is not None and bias.dtype == torch.float32),
-                               _p(lora_b_bias), _p(bias_out), O, I, R, stream if stream is not None else cur_stream()), "vc_lora_merge")
+    args = (weight.data_ptr(), int(weight.dtype == torch.float32), weight.stride(0),
+            _p(lora_a), lora_a.stride(0) if R else 0, _p(lora_b), lora_b.stride(0) if R else 0, float(scale),
+            out.data_ptr(), out.stride(0), _p(bias), int(bias is not None and bias.dtype == torch.float32),
+            _p(lora_b_bias), _p(bias_out), O, I, R)
+    if qkv_heads:
+        _check(lib().vc_lora_merge_qkv(*args, int(qkv_heads), stream if stream is not None else cur_stream()), "vc_lora_merge_qkv")
+    else:
+        _check(lib().vc_lora_merge(*args, stream if stream is not None else cur_stream()), "vc_lora_merge")
     return out, bias_out
 
 

@@ -289,6 +289,10 @@ class Flux(nn.Module):
         # number of DESIGN.md was taken on) or "hip" (vc_lora_merge, csrc/lora_merge.hip: one launch per Linear, no f32 copy, no
         # vendor GEMM; the same arithmetic up to the order of the f32 sums)
         self.lora_merge = "torch"
+        # True (opt-in): the C handle prepares the weights ITSELF from this module's state_dict (handle.FluxHandle.from_state_dict:
+        # vc_flux_load_*, csrc/flux_load.hip) - merged mode only, no torch arithmetic on a weight, no Python-ordered twin: engine()
+        # and lora_mode "ref" with ref_plan "python" raise.  False: prepare() as it always was.
+        self.load_in_library = False
 
     # ------------------------------------------------------------------ weights -> engine
     def _linears(self):
@@ -516,7 +520,34 @@ class Flux(nn.Module):
         self._handle = None
         self._fingerprint = None
 
+    def _library_handle(self):
+        """load_in_library: the handle over this module's own state_dict, rebuilt when a parameter or the scale changed"""
+        if not self.use_handle or self.lora_mode != "merged":
+            raise hip.VclozeHipError("load_in_library prepares merged weights behind the C handle: it needs use_handle True and lora_mode "
+                                     f"'merged' (got use_handle={self.use_handle}, lora_mode={self.lora_mode!r})")
+        fp = self._weights_fingerprint()
+        if self._handle is None or self._fingerprint != fp or not getattr(self._handle, "_loaded", None):
+            hip.require_gpu()
+            scales = {m.scale for _, m in self._linears() if m.rank}
+            if len(scales) > 1:
+                raise hip.VclozeHipError(f"load_in_library merges with ONE lora scale, the model holds {sorted(scales)}")
+            from .handle import FluxHandle
+            self._engine = None
+            self._handle = FluxHandle.from_state_dict(self.params, self.state_dict(), scales.pop() if scales else 1.0,
+                                                      next(self.parameters()).device)
+            self._handle.stream = torch.cuda.Stream(device=self._handle.dev)      # capture needs a non-default stream
+            self._fingerprint = fp
+        return self._handle
+
+    def plan(self):
+        """whoever holds the device and the capture stream of this model's launches (`.dev`, `.stream`): the engine, or with
+        load_in_library the C handle alone"""
+        return self._library_handle() if self.load_in_library else self.engine()
+
     def engine(self) -> FluxEngine:
+        if self.load_in_library:
+            raise hip.VclozeHipError("load_in_library: the weights are prepared inside libvcloze_hip.so and there is no Python-ordered "
+                                     "twin of them (engine()); set load_in_library = False for the parity paths")
         if self._engine is None or self._fingerprint != self._weights_fingerprint():
             self.prepare()
         return self._engine
@@ -526,6 +557,8 @@ class Flux(nn.Module):
         Python-ordered plan (use_handle False, or the un-merged LoRA mode unless ref_plan is "handle").  Test / A-B knobs set on
         `engine()` apply to both."""
         self._check_ref_plan()
+        if self.load_in_library:
+            return self._library_handle()
         eng = self.engine()
         if not self.use_handle or (eng.W.ref is not None and self.ref_plan != "handle"):
             return None
@@ -568,7 +601,7 @@ class Flux(nn.Module):
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
-        eng = self.engine()
+        eng = self.plan()
         B, N, _ = img.shape
         T = txt.shape[1]
         dev = eng.dev
@@ -601,6 +634,8 @@ class Flux(nn.Module):
 
     def max_batch(self) -> int:
         """samples per launch sequence: the engine's (one in the Python-ordered un-merged mode), the handle's where it runs that mode"""
+        if self.load_in_library:
+            return self._library_handle().MAX_BATCH
         eng, h = self.engine(), self.handle()
         return h.MAX_BATCH if h is not None and eng.W.ref is not None else eng.MAX_BATCH
 
@@ -618,7 +653,7 @@ class Flux(nn.Module):
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
-        eng = self.engine()
+        eng = self.plan()
         B, N, _ = img.shape
         T, D, dev = txt.shape[1], self.hidden_size, eng.dev
         bf = lambda t: t.to(dev, torch.bfloat16).contiguous()  # noqa: E731

@@ -422,7 +422,7 @@ def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max
 def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None):
     """vc_flux_sample_dopri5 per chunk of samples (true CFG: chunks of whole pairs): ONE step size per chunk, so a sample's result
     depends on the samples it shares a chunk with."""
-    eng = flux.engine()
+    eng = flux.plan()
     dev = eng.dev
     B, N, C = x.shape
     cond = kw.get("cond")
@@ -555,7 +555,7 @@ def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
 def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=None, sampler=None, cfg_scale=None):
     """cfg_scale: None = the drift is Flux.forward; a number = Flux.forward_with_cfg with it (C handle only).  Samples then advance
     in chunks of whole pairs (j, j + B/2), conditional samples first, and go back in the caller's order."""
-    eng = flux.engine()
+    eng = flux.plan()
     dev = eng.dev
     B, N, C = x.shape
     cond = kw.get("cond")
