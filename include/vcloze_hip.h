@@ -342,6 +342,31 @@ int vc_residual_sub(const void* a, int64_t a_bstride, const void* b, int64_t b_b
                     int64_t n, void* stream);
 int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride, int32_t B,
                     int64_t n, void* stream);
+/* ---- the numerics monitor's reduction: per sample of a strided tensor, how many elements are NaN / +-inf and how large the rest
+ * is.  The reference has nothing like it.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect by SYMBOL (look up
+ * vc_tensor_stats); vc_monitor_struct_sizes reports sizeof(VcStat).
+ * x: B samples of rows x cols elements, bf16 or F32 (x_is_f32); element (b, r, c) lies b * bstride + r * ld + c elements behind x - the
+ * image rows, the text rows or all rows of a strided joint stream.  Per sample b:
+ *   nonfinite  the number of NaN / +-inf elements (exact)           count    the number of elements examined, rows * cols (exact)
+ *   max_abs    max |x| over the FINITE elements (exact; 0 without)  sum_sq   sum x^2 over the finite elements, in f32, in a fixed order
+ * The order of sum_sq: a row is cut into UNITS of E consecutive elements (E = 8 for bf16, 4 for F32; the last unit of a row is shorter
+ * where cols % E != 0); the sample's units, numbered row by row, are dealt round-robin to the nblk * 256 threads of its
+ * nblk = min(ceil(units / 256), VC_MONITOR_MAX_BLOCKS) blocks (thread t of block k: units k * 256 + t, + nblk * 256, ...).  A thread
+ * adds its elements in ascending order, s = s + x * x, the product rounded to f32 on its own (no fused multiply-add); the block's 256
+ * sums go through a tree (l[t] += l[t + o], o = 128, 64, .., 1) and the sample's nblk block sums through the same tree (thread t holds
+ * block t's, 0 for t >= nblk).  A two-pass block reduction without atomics, as vc_dopri5_error_ratio and vc_residual_change: repeated
+ * runs give the same bits.  A unit is ONE 16-byte load where cols, ld, bstride are multiples of E and x is 16-byte aligned, E
+ * element loads otherwise: the choice is made on the host and gives the same bits.
+ * out: the VcStat of sample b goes to out[row * out_stride + b], row = *row_ptr - a device-side counter, read when the kernel runs,
+ * so ONE captured launch serves every evaluation of a trajectory - or 0 with row_ptr NULL; a row outside [0, capacity) writes
+ * NOTHING.  scratch: B * 4 * VC_MONITOR_MAX_BLOCKS F32 of device memory.  VC_ERR_ARG before the device is touched: a null x / out /
+ * scratch; B, rows, cols or capacity <= 0; B > 65535; bstride < 0; ld < cols; out_stride < B; an out that is not 16-byte aligned; an x
+ * or a scratch that is not aligned to its elements (2 bytes for bf16, 4 for F32); rows * cols >= 2^32 or more than 2^31 - 1 units. */
+typedef struct VcStat { float max_abs; float sum_sq; uint32_t nonfinite; uint32_t count; } VcStat;   /* 16 bytes */
+#define VC_MONITOR_MAX_BLOCKS 256
+void vc_monitor_struct_sizes(int32_t out[1]);
+int vc_tensor_stats(const void* x, int32_t x_is_f32, int64_t bstride, int64_t ld, int32_t B, int64_t rows, int32_t cols, VcStat* out,
+                    int64_t out_stride, const int32_t* row_ptr, int32_t capacity, float* scratch, void* stream);
 /* ---- true classifier-free guidance: the combine of Flux.forward_with_cfg (models/model.py:126-145), which runs forward on a batch
  * whose first half is the conditional and whose second half the unconditional samples and returns
  * cat([uncond_v + cfg_scale * (cond_v - uncond_v), uncond_v]).  Added without a change of VC_ABI_VERSION: detect by SYMBOL (look up
@@ -753,6 +778,49 @@ int vc_flux_set_step_cache(void* handle, float threshold, int32_t max_consecutiv
  * vc_flux_forward and vc_flux_profile ignore the setting (forward_with_cfg = vc_flux_forward + vc_cfg_combine).  No new workspace. */
 int vc_flux_set_cfg(void* handle, int32_t on, float cfg_scale);
 int vc_flux_step_cache_stats(void* handle, int32_t* computed, int32_t* reused, float* metrics, int32_t capacity);
+/* ---- the numerics monitor of the captured step: OPT-IN, off by default.  A sample call returns VC_OK for a latent full of NaN; with
+ * the monitor on, every evaluation leaves vc_tensor_stats of chosen tensors in a log, and vc_flux_monitor_report names the first
+ * (evaluation, site, sample) that held a NaN / +-inf.  Added WITHOUT a change of VC_ABI_VERSION: detect by SYMBOL
+ * (look up vc_flux_set_monitor).  The return codes of the sample calls do NOT change: a caller who wants an error asks the report.
+ * The log is sized for the B prepared when the monitor takes effect: after a prepare with another B, forward / sample_begin* are
+ * VC_ERR_STATE until vc_flux_set_monitor is called again (a call outside a trajectory, with new or the same arguments, also forgets
+ * what was logged).  vc_flux_monitor_report is NOT refused then: it reads the rows with the B they were logged with, so the report of a
+ * finished trajectory can still be asked after the next batch has been prepared.
+ * level 0  off.  The plan is launch for launch, node for node, what it is without these entry points.
+ * level 1  two sites per evaluation: "v", the model's output [B, N, out_channels] before the solver's update (with true CFG on: before
+ *          the combine, every sample's own velocity), and "x", the ODE state behind the solver's update - read as F32 where the state
+ *          is F32.  (vc_flux_forward has no state: its "x" stays zeroed.)
+ * level 2  those, then every tap site under its tap name, in tap order: "img_in", "txt_in", "double.{i}.img", "double.{i}.txt" for
+ *          every i, "single.{i}" for every i.  Each is read in place in the workspace directly behind the block: no copy, and no tap
+ *          needs to be set.  vc_flux_monitor_sites lists the names of the level set, index 0, 1, .. until VC_ERR_ARG (host only).
+ * log, scratch: the caller's device buffers, as tap destinations are (the workspace's size and carve-up do not change); log is
+ * [capacity_evals][n_sites][B] VcStat, sites in the order of vc_flux_monitor_sites, 16-byte aligned.  vc_flux_monitor_bytes gives both
+ * sizes for the PREPARED B (host only; VC_ERR_STATE before vc_flux_prepare or with the monitor off); prepare with another B and they
+ * are to be asked again.  A null log / scratch, a misaligned log, capacity_evals <= 0 or a level outside 0..2 is VC_ERR_ARG.
+ * Every site is one vc_tensor_stats launch (two kernels) of the captured step, indexed by the device-side evaluation counter: the
+ * setting is part of the key a captured step is kept under, exactly as the tap set is, takes effect at the next vc_flux_forward /
+ * vc_flux_sample_begin*, and a change between vc_flux_sample_begin* and vc_flux_sample_end is VC_ERR_STATE.  vc_flux_sample_begin*
+ * zeroes the whole log (one kernel launch outside the captured step) and refuses a trajectory of more EVALUATIONS (steps *
+ * vc_solver_evals) than capacity_evals with VC_ERR_ARG; evaluation e of the trajectory - a stage of midpoint / rk4 included - logs
+ * into row e.  vc_flux_forward zeroes the log and logs into row 0.  An evaluation that the step cache reuses runs block 0 only and
+ * leaves the rows of the blocks it skipped zeroed (count == 0); its "img_in", "txt_in", "double.0.*", "v" and "x" are logged.
+ * vc_flux_sample_dopri5 with the monitor on is VC_ERR_ARG: its device-side counter is the STAGE of an attempt, not an evaluation
+ * index.  vc_flux_profile issues its evaluations without the monitor's launches.
+ * report: a reduction over the rows logged so far on the device plus ONE small read-back (synchronises `stream`): the entry with
+ * nonfinite != 0 that was WRITTEN first - in evaluation order, within an evaluation in the order its sites are written (the tap sites
+ * in tap order, then "v", then "x": what lies upstream comes first, so the site named is where the trajectory went bad), then in
+ * sample order - as the evaluation, the site's index in vc_flux_monitor_sites and the sample, or -1, -1, -1 when there is none;
+ * *evals_logged = the evaluations issued since the log was zeroed (0, and -1s, before anything was logged).  Any output may be NULL.
+ * VC_ERR_STATE with the monitor off.
+ * vc_flux_step_nodes: host only - the number of graph nodes of the captured step of the trajectory begun last, nodes[0] the step (with
+ * the step cache on: head, tail-compute, tail-reuse in nodes[0..2]; else nodes[1] = nodes[2] = 0).  What "node for node" is held to:
+ * every monitor site adds two kernel nodes, level 0 adds none.  VC_ERR_STATE without a captured step (stream NULL captures none). */
+int vc_flux_step_nodes(void* handle, int32_t nodes[3]);
+int vc_flux_set_monitor(void* handle, int32_t level, VcStat* log, int32_t capacity_evals, float* scratch);
+int vc_flux_monitor_sites(void* handle, int32_t index, char* name, int32_t namelen);
+int vc_flux_monitor_bytes(void* handle, int32_t capacity_evals, int64_t* log_bytes, int64_t* scratch_bytes);
+int vc_flux_monitor_report(void* handle, int32_t* first_bad_eval, int32_t* first_bad_site, int32_t* first_bad_sample, int32_t* evals_logged,
+                           void* stream);
 
 /* ---- the plan's own stopwatch (ABI 10): HIP-event times of the launches of whole evaluations, class by class ----
  * What bench.py's `roofline` leg reports.  With a sample in flight (vc_flux_sample_begin), `evaluations` more evaluations of

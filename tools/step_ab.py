@@ -4,9 +4,10 @@ of record) gets its own C handle over the same weight tensors, and rounds of `--
 builds.  Reports the median and the minimum ms / step per build and, with --attn, the in-situ attention time of each.
 
     python tools/step_ab.py main xcdtail [--workload 384-grid-2x3] [--rounds 5] [--steps 29] [--attn] [--opt name:key=val]
+    python tools/step_ab.py main main=l1 main=l2 --monitor l1:1 --monitor l2:2      # the on-cost of the numerics monitor
 
 --opt sets engine options per build, e.g. `--opt b:attn_variant=8` (applied to the model's engine before the handle of
-build `b` is created)."""
+build `b` is created).  --monitor sets the level of the handle's numerics monitor (vc_flux_set_monitor) per build."""
 import argparse
 import ctypes as C
 import json
@@ -28,7 +29,8 @@ def load(name):
     l = C.CDLL(path)
     for sym, (res, args) in hip.SYMBOLS.items():
         # an older library in the A/B: entry points added without a change of VC_ABI_VERSION are detected by symbol
-        if sym in ("vc_flux_profile", "vc_cfg_combine", "vc_flux_set_cfg") and not hasattr(l, sym):
+        if (sym in ("vc_flux_profile", "vc_cfg_combine", "vc_flux_set_cfg", "vc_monitor_struct_sizes", "vc_tensor_stats")
+                or sym.startswith("vc_flux_set_monitor") or sym.startswith("vc_flux_monitor_")) and not hasattr(l, sym):
             continue
         fn = getattr(l, sym)
         fn.restype, fn.argtypes = res, args
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--steps", type=int, default=29)
     ap.add_argument("--attn", action="store_true", help="also time the attention launches in situ (Python-ordered plan)")
     ap.add_argument("--opt", action="append", default=[])
+    ap.add_argument("--monitor", action="append", default=[], help="alias:level - the numerics monitor of that build's handle")
     ap.add_argument("--per-gpu-batch", type=int, default=1)
     a = ap.parse_args()
     hip.require_gpu()
@@ -66,6 +69,7 @@ def main():
     base_opts = dict(attn_variant=eng.attn_variant, tile_cfg=eng.tile_cfg, fuse_qnorm=eng.fuse_qnorm, fuse_vt=eng.fuse_vt,
                      fuse_knorm=eng.fuse_knorm, bounded_softmax=eng.bounded_softmax, mlp_first=eng.mlp_first,
                      splitk=eng.splitk)
+    levels = {m.split(":")[0]: int(m.split(":")[1]) for m in a.monitor}
     jobs, libs = {}, {}
     for libname, alias in builds:
         libs[alias] = load(libname)
@@ -77,6 +81,10 @@ def main():
         with torch.cuda.stream(eng.stream):
             for _ in range(3):
                 job.step()
+            if levels.get(alias):          # takes effect at the next sample_begin: every timed round starts with one
+                job.state()
+                job.h.set_monitor(levels[alias], job.S)
+                job.restart_sample()
         torch.cuda.synchronize()
         jobs[alias] = (job, model._handle, {**base_opts, **opts.get(alias, {})})
     times = {alias: [] for _, alias in builds}
@@ -117,6 +125,14 @@ def main():
     for _, alias in builds:
         out[alias]["vs_first_pct"] = round((base / out[alias]["median_ms"] - 1) * 100, 2)
         print(alias, json.dumps(out[alias]), flush=True)
+    # every handle is destroyed by the library that created it: left to FluxHandle.__del__ at interpreter exit, all of them would go
+    # through whichever library `hip._lib` names last, whose handle struct need not have the layout of another build's
+    torch.cuda.synchronize()
+    model._handle = None
+    for _, alias in builds:
+        h = jobs[alias][1]
+        libs[alias].vc_flux_destroy(h.h)
+        h.h = C.c_void_p()
 
 
 if __name__ == "__main__":

@@ -136,6 +136,11 @@ int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_b
                     int64_t n, void* stream) {
   return vc_residual_op_launch(1, a, a_bstride, b, b_bstride, out, out_bstride, B, n, S(stream), ERRBUF);
 }
+void vc_monitor_struct_sizes(int32_t out[1]) { out[0] = (int32_t)sizeof(VcStat); }
+int vc_tensor_stats(const void* x, int32_t x_is_f32, int64_t bstride, int64_t ld, int32_t B, int64_t rows, int32_t cols, VcStat* out,
+                    int64_t out_stride, const int32_t* row_ptr, int32_t capacity, float* scratch, void* stream) {
+  return vc_tensor_stats_launch(x, x_is_f32, bstride, ld, B, rows, cols, out, out_stride, row_ptr, capacity, scratch, S(stream), ERRBUF);
+}
 
 int vc_sdedit_mix(const void* noise, const void* latent, double strength, void* out, int64_t n, void* stream) {
   return vc_sdedit_mix_launch(noise, latent, strength, out, n, S(stream), ERRBUF);
@@ -299,6 +304,20 @@ int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_
 int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                          void* trajectory, void* stream) {
   return vc_flux_sample_ode(handle, VC_SOLVER_EULER, x, cond, t_grid, n_points, state_is_bf16, trajectory, stream);
+}
+int vc_flux_step_nodes(void* handle, int32_t nodes[3]) { return vc_flux_step_nodes_impl(handle, nodes, ERRBUF); }
+int vc_flux_set_monitor(void* handle, int32_t level, VcStat* log, int32_t capacity_evals, float* scratch) {
+  return vc_flux_set_monitor_impl(handle, level, log, capacity_evals, scratch, ERRBUF);
+}
+int vc_flux_monitor_sites(void* handle, int32_t index, char* name, int32_t namelen) {
+  return vc_flux_monitor_sites_impl(handle, index, name, namelen, ERRBUF);
+}
+int vc_flux_monitor_bytes(void* handle, int32_t capacity_evals, int64_t* log_bytes, int64_t* scratch_bytes) {
+  return vc_flux_monitor_bytes_impl(handle, capacity_evals, log_bytes, scratch_bytes, ERRBUF);
+}
+int vc_flux_monitor_report(void* handle, int32_t* first_bad_eval, int32_t* first_bad_site, int32_t* first_bad_sample, int32_t* evals_logged,
+                           void* stream) {
+  return vc_flux_monitor_report_impl(handle, first_bad_eval, first_bad_site, first_bad_sample, evals_logged, S(stream), ERRBUF);
 }
 
 /* ---- autoencoder handle (vae_engine.hip) ---- */

@@ -54,14 +54,19 @@ struct Carver {
   }
 };
 
-// capture what `issue` launches on `s` into an instantiated graph
-template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue) {
+// capture what `issue` launches on `s` into an instantiated graph; *nodes (where given): the number of nodes of that graph
+template <class F> int capture(hipStream_t s, hipGraphExec_t& out, Err e, F issue, int* nodes = nullptr) {
   HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
   const int rc = issue();
   hipGraph_t g = nullptr;
   hipError_t he = hipStreamEndCapture(s, &g);
   if (rc != VC_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
   HIP(he, "hipStreamEndCapture");
+  if (nodes) {
+    size_t n = 0;
+    if (hipGraphGetNodes(g, nullptr, &n) != hipSuccess) n = 0;
+    *nodes = (int)n;
+  }
   he = hipGraphInstantiate(&out, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   HIP(he, "hipGraphInstantiate");

@@ -27,6 +27,7 @@
 #include "vcloze_internal.h"
 #include "engine_core.h"
 #include "flux_keys.h"
+#include "monitor_sites.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -109,9 +110,15 @@ struct Flux : Buffers {
   std::unordered_map<int, Loaded> loaded;
   float lora_scale = 1.0f;
   bool scale_stale = false;            // the scale changed after vc_flux_prepare ran txt_in / vector_in / guidance_in with the old one
-  // per-block taps (vc_flux_set_tap): the caller's buffer of tap i, or null - img_in, txt_in, then (img, txt) of every double
-  // block, then every single block
+  // per-block taps (vc_flux_set_tap): the caller's buffer of tap i, or null - in the order of monitor_sites.h (vcmon::tap_*)
   std::vector<void*> taps;
+  // the numerics monitor (vc_flux_set_monitor): the caller's setting, read where a step is issued or captured.  mon_evals: evaluations
+  // logged since the log was zeroed; mon_paused: vc_flux_profile issues its evaluations without the monitor's launches
+  int mon_level = 0, mon_cap = 0, mon_evals = 0, mon_B = 0;   // mon_B: the prepared B the caller sized the log for (0: set before a prepare)
+  VcStat* mon_log = nullptr;
+  float* mon_scratch = nullptr;
+  bool mon_paused = false;
+  int mon_sites() const { return vcmon::site_count(mon_level, cfg.depth, cfg.depth_single_blocks); }
   bool in_flight = false;              // between vc_flux_sample_begin* and vc_flux_sample_end
   // resolved at prepare time
   bool resolved = false;
@@ -129,7 +136,7 @@ struct Flux : Buffers {
   char* base = nullptr;
   // a captured step: ONE graph (g[0]), or with the step cache on three - head, tail-compute, tail-reuse (an entry of `graphs` is a
   // whole step, so a cached trajectory never evicts a graph of its own).  step: the one of the sample in flight
-  struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; } step;
+  struct Step { hipGraphExec_t g[3] = {nullptr, nullptr, nullptr}; int nodes[3] = {0, 0, 0}; } step;      // nodes: of each graph (vc_flux_step_nodes)
   struct DropStep {
     void operator()(const Step& st) const { for (auto ge : st.g) DropExec()(ge); }
   };
@@ -137,10 +144,12 @@ struct Flux : Buffers {
     char* base; int B, T, N, S, ragged, gapped, variant, state_f32, method, cache; Options opt; hipStream_t s;   // variant: resolved
     int cfg; uint32_t cfg_bits;          // true CFG on, and the bits of its scale: a kernel argument of the captured combine
     std::vector<void*> taps;             // the tap set: every tap is a copy node of the captured step
+    int mon_level, mon_cap; void* mon_log; void* mon_scratch;      // the monitor: every site is a node of the captured step
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
              variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s &&
-             cfg == o.cfg && cfg_bits == o.cfg_bits && taps == o.taps;
+             cfg == o.cfg && cfg_bits == o.cfg_bits && taps == o.taps && mon_level == o.mon_level && mon_cap == o.mon_cap &&
+             mon_log == o.mon_log && mon_scratch == o.mon_scratch;
     }
   } key{};
   // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
@@ -653,16 +662,36 @@ int d2d(void* dst, const void* src, int64_t bytes, hipStream_t s, Err e) {
   return VC_OK;
 }
 
-// vc_flux_set_tap: tap `idx` <- `bytes` of a residual stream, one copy node on the evaluation's own stream
-int tap(Flux& f, size_t idx, const void* src, int64_t bytes, hipStream_t s, Err e) {
-  if (idx >= f.taps.size() || !f.taps[idx]) return VC_OK;
-  TRY(prof_open(f, s, VC_LAUNCH_TAP, 0, 0, 0, 0, 2.0 * bytes, e));         // every tap in ONE launch class
-  TRY(d2d(f.taps[idx], src, bytes, s, e));
-  return prof_close(f, s, e);
+// vc_flux_set_monitor: site `site` of the evaluation `*step_ptr` (row 0 without a counter) <- vc_tensor_stats of the B samples of
+// rows x cols contiguous elements at x, one launch (two kernels) on the evaluation's own stream
+int monitor(Flux& f, int site, const void* x, bool x_f32, int64_t rows, int cols, const int32_t* step_ptr, hipStream_t s, Err e) {
+  if (!f.mon_level || f.mon_paused) return VC_OK;
+  const int ns = f.mon_sites();
+  return vc_tensor_stats_launch(x, x_f32, rows * cols, cols, f.B, rows, cols, f.mon_log + vcmon::log_index(0, site, 0, f.mon_cap, ns, f.B),
+                                vcmon::log_row_stride(ns, f.B), step_ptr, f.mon_cap, f.mon_scratch, s, e.buf, e.len);
 }
-int tap_double(Flux& f, size_t i, hipStream_t s, Err e) {
-  TRY(tap(f, 2 + 2 * i, f.XI, (int64_t)f.B * f.N * f.D * 2, s, e));
-  return tap(f, 3 + 2 * i, f.XT, (int64_t)f.B * f.T * f.D * 2, s, e);
+// the log was sized for the B prepared when the monitor was set: another B would run past its rows
+int monitor_fits(Flux& f, const char* what, Err e) {
+  if (f.mon_level && f.mon_B && f.mon_B != f.B)
+    FAIL(VC_ERR_STATE, "%s: the monitor's log was sized for B = %d, the prepared B is %d: ask vc_flux_monitor_bytes and call vc_flux_set_monitor again",
+         what, f.mon_B, f.B);
+  if (f.mon_level) f.mon_B = f.B;
+  return VC_OK;
+}
+// a tap site: the residual stream `src` ([B * rows, D] bf16) directly behind its block.  vc_flux_set_tap: tap `idx` <- the stream, one
+// copy node on the evaluation's own stream; monitor level 2: its statistics, read in place
+int tap(Flux& f, int idx, const bf16_t* src, int rows, const int32_t* step_ptr, hipStream_t s, Err e) {
+  if ((size_t)idx < f.taps.size() && f.taps[idx]) {
+    const int64_t bytes = (int64_t)f.B * rows * f.D * 2;
+    TRY(prof_open(f, s, VC_LAUNCH_TAP, 0, 0, 0, 0, 2.0 * bytes, e));       // every tap in ONE launch class
+    TRY(d2d(f.taps[idx], src, bytes, s, e));
+    TRY(prof_close(f, s, e));
+  }
+  return f.mon_level >= 2 ? monitor(f, vcmon::site_of_tap(idx), src, false, rows, f.D, step_ptr, s, e) : VC_OK;
+}
+int tap_double(Flux& f, int i, const int32_t* step_ptr, hipStream_t s, Err e) {
+  TRY(tap(f, vcmon::tap_double(i, false), f.XI, f.N, step_ptr, s, e));
+  return tap(f, vcmon::tap_double(i, true), f.XT, f.T, step_ptr, s, e);
 }
 
 // Flux.forward on `img_rows` (x || cond in XIN when NULL) -> `out` (V when NULL); with `euler` the solver's update behind it
@@ -687,26 +716,26 @@ int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, E
                               (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
 }
 
-int eval_inputs(Flux& f, bool concat, const void* img_rows, hipStream_t s, Err e) {
+int eval_inputs(Flux& f, bool concat, const void* img_rows, const int32_t* step_ptr, hipStream_t s, Err e) {
   const int B = f.B, T = f.T, N = f.N, D = f.D;
   const int in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
   if (concat) TRY(vc_concat_cols_launch(next_input(f), out_ch, f.COND, in_ch - out_ch, f.XIN, (int64_t)B * N, s, e.buf, e.len));
   TRY(d2d(f.XT, f.TXT0, (int64_t)B * T * D * 2, s, e));
   TRY(lin(f, f.img_in, img_rows ? img_rows : f.XIN, in_ch, f.XI, D, B * N, VC_EPI_BIAS, s, e));
-  TRY(tap(f, 0, f.XI, (int64_t)B * N * D * 2, s, e));
-  return tap(f, 1, f.XT, (int64_t)B * T * D * 2, s, e);
+  TRY(tap(f, vcmon::tap_img_in(), f.XI, N, step_ptr, s, e));
+  return tap(f, vcmon::tap_txt_in(), f.XT, T, step_ptr, s, e);
 }
 int eval_blocks(Flux& f, const Ctx& c, size_t first, Err e) {
   const int B = f.B, T = f.T, N = f.N, L = f.L, D = f.D;
   hipStream_t s = c.s;
-  for (size_t i = first; i < f.dbl.size(); ++i) { TRY(double_block(f, c, f.dbl[i], e)); TRY(tap_double(f, i, s, e)); }
+  for (size_t i = first; i < f.dbl.size(); ++i) { TRY(double_block(f, c, f.dbl[i], e)); TRY(tap_double(f, (int)i, c.step_ptr, s, e)); }
   for (int b = 0; b < B; ++b) {   // cat((txt, img), 1) per sample (model.py:116)
     TRY(d2d(f.X + (int64_t)b * L * D, f.XT + (int64_t)b * T * D, (int64_t)T * D * 2, s, e));
     TRY(d2d(f.X + ((int64_t)b * L + T) * D, f.XI + (int64_t)b * N * D, (int64_t)N * D * 2, s, e));
   }
   for (size_t i = 0; i < f.sgl.size(); ++i) {
     TRY(single_block(f, c, f.sgl[i], e));
-    TRY(tap(f, 2 + 2 * f.dbl.size() + i, f.X, (int64_t)B * L * D * 2, s, e));
+    TRY(tap(f, vcmon::tap_single(f.cfg.depth, (int)i), f.X, L, c.step_ptr, s, e));
   }
   return VC_OK;
 }
@@ -720,19 +749,21 @@ int eval_output(Flux& f, const Ctx& c, void* out, bool euler, Err e) {
   VcGemmProblem p = prob(f.XH + (int64_t)T * D, D, f.final_lin, out ? out : f.V, out_ch, B * N);
   p.a_rpb = N; p.a_bstride = (int64_t)L * D;
   TRY(gemm(f, &p, 1, VC_EPI_BIAS, nullptr, 0, s, e));
+  TRY(monitor(f, vcmon::SITE_V, out ? out : f.V, false, N, out_ch, step_ptr, s, e));       // the model's output, before any combine
   if (euler) {
     if (f.cfg_active) {     // V is sample-major: its first half is the conditional samples' velocity, combined in place
       const int64_t half = (int64_t)(B / 2) * N * out_ch;
       TRY(vc_cfg_combine_launch(f.V, f.V + half, f.V, half, f.cfg_s, s, e.buf, e.len));
     }
     TRY(ode_update(f, f.V, step_ptr, s, e));
+    TRY(monitor(f, vcmon::SITE_X, ode_state(f), f.state_f32, N, out_ch, step_ptr, s, e));
     TRY(vc_step_advance_launch((int32_t*)step_ptr, s, e.buf, e.len));
   }
   return VC_OK;
 }
 int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows, void* out, bool euler, hipStream_t s, Err e) {
   Ctx c{step_ptr, s, (int64_t)f.B * f.n_mod};
-  TRY(eval_inputs(f, concat, img_rows, s, e));
+  TRY(eval_inputs(f, concat, img_rows, step_ptr, s, e));
   TRY(eval_blocks(f, c, 0, e));
   return eval_output(f, c, out, euler, e);
 }
@@ -743,10 +774,10 @@ int evaluate(Flux& f, const int32_t* step_ptr, bool concat, const void* img_rows
 int cache_head(Flux& f, hipStream_t s, Err e) {
   const int64_t nd = (int64_t)f.N * f.D;
   Ctx c{f.STEP, s, (int64_t)f.B * f.n_mod};
-  TRY(eval_inputs(f, true, nullptr, s, e));
+  TRY(eval_inputs(f, true, nullptr, f.STEP, s, e));
   TRY(d2d(f.X, f.XI, f.B * nd * 2, s, e));                                   // h0
   TRY(double_block(f, c, f.dbl[0], e));                                      // XI = h1
-  TRY(tap_double(f, 0, s, e));
+  TRY(tap_double(f, 0, f.STEP, s, e));
   TRY(vc_residual_change_launch(f.X, f.XI, f.SC_P, f.SC_RS, nullptr, f.SC_METRIC, f.SC_PART, f.B, nd, s, e.buf, e.len));
   HIP(hipMemcpyAsync(f.sc_host, f.SC_METRIC, sizeof(float), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
   return VC_OK;
@@ -836,7 +867,7 @@ void drop_graph(Flux& f) {
 // evaluation (modulation rows, dt, the stage of a midpoint / rk4 step) is indexed on the device by STEP
 int step_graph(Flux& f, hipStream_t s, Err e) {
   Flux::Key k{f.base, f.B, f.T, f.N, f.S, f.ragged, f.gapped, attention_variant(f), f.state_f32, f.method, f.sc_active, f.opt, s,
-               f.cfg_active, 0, {}};
+               f.cfg_active, 0, {}, f.mon_level, f.mon_cap, f.mon_log, f.mon_scratch};
   if (f.cfg_active) memcpy(&k.cfg_bits, &f.cfg_s, 4);
   k.taps = f.taps;
   if (const Flux::Step* hit = f.graphs.find(k)) {
@@ -849,16 +880,16 @@ int step_graph(Flux& f, hipStream_t s, Err e) {
   if (!f.sc_active) {
     // warm-up outside capture (kernel attributes are set on first launch): one evaluation into V, the state is untouched
     TRY(evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e));
-    rc = capture(s, st.g[0], e, [&] { return evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e); });
+    rc = capture(s, st.g[0], e, [&] { return evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e); }, &st.nodes[0]);
   } else {
     // the same warm-up through the three pieces (P, R and the scratch it writes are rewritten by the trajectory's first evaluation,
     // which always computes, before anything reads them)
     TRY(cache_head(f, s, e));
     TRY(cache_tail_compute(f, false, s, e));
     TRY(cache_tail_reuse(f, false, s, e));
-    rc = capture(s, st.g[0], e, [&] { return cache_head(f, s, e); });
-    if (rc == VC_OK) rc = capture(s, st.g[1], e, [&] { return cache_tail_compute(f, true, s, e); });
-    if (rc == VC_OK) rc = capture(s, st.g[2], e, [&] { return cache_tail_reuse(f, true, s, e); });
+    rc = capture(s, st.g[0], e, [&] { return cache_head(f, s, e); }, &st.nodes[0]);
+    if (rc == VC_OK) rc = capture(s, st.g[1], e, [&] { return cache_tail_compute(f, true, s, e); }, &st.nodes[1]);
+    if (rc == VC_OK) rc = capture(s, st.g[2], e, [&] { return cache_tail_reuse(f, true, s, e); }, &st.nodes[2]);
   }
   if (rc != VC_OK) {
     Flux::DropStep()(st);          // the graphs of a half-captured step
@@ -893,7 +924,7 @@ int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int e
   f->D = cfg->hidden_size; f->H = cfg->num_heads; f->mlp = cfg->mlp_hidden;
   layout_modulation(*f);
   f->keys = vckeys::build(*cfg);
-  f->taps.assign(2 + 2 * (size_t)cfg->depth + (size_t)cfg->depth_single_blocks, nullptr);
+  f->taps.assign((size_t)vcmon::tap_count(cfg->depth, cfg->depth_single_blocks), nullptr);
   // without a ROCm device the handle still answers its host-only calls (vc_flux_mod_offset, vc_flux_load_key / _tensor / _bytes,
   // vc_flux_bound); whatever touches the device then fails with the runtime's own error
   int dev = 0;
@@ -1134,17 +1165,17 @@ static int tap_index(Flux& f, const char* what, const char* name, size_t& idx, E
   if (!name) FAIL(VC_ERR_ARG, "%s: null name", what);
   int i = -1, n = 0;
   char st[4] = "";
-  if (!strcmp(name, "img_in")) { idx = 0; return VC_OK; }
-  if (!strcmp(name, "txt_in")) { idx = 1; return VC_OK; }
+  if (!strcmp(name, "img_in")) { idx = (size_t)vcmon::tap_img_in(); return VC_OK; }
+  if (!strcmp(name, "txt_in")) { idx = (size_t)vcmon::tap_txt_in(); return VC_OK; }
   if (sscanf(name, "double.%d.%3[a-z]%n", &i, st, &n) == 2 && !name[n] && i >= 0 && (!strcmp(st, "img") || !strcmp(st, "txt"))) {
     if (i >= f.cfg.depth) FAIL(VC_ERR_ARG, "%s: name = '%s', the model has %d double blocks", what, name, f.cfg.depth);
-    idx = 2 + 2 * (size_t)i + (st[0] == 't');
+    idx = (size_t)vcmon::tap_double(i, st[0] == 't');
     return VC_OK;
   }
   n = 0;
   if (sscanf(name, "single.%d%n", &i, &n) == 1 && !name[n] && i >= 0) {
     if (i >= f.cfg.depth_single_blocks) FAIL(VC_ERR_ARG, "%s: name = '%s', the model has %d single blocks", what, name, f.cfg.depth_single_blocks);
-    idx = 2 + 2 * (size_t)f.cfg.depth + (size_t)i;
+    idx = (size_t)vcmon::tap_single(f.cfg.depth, i);
     return VC_OK;
   }
   FAIL(VC_ERR_ARG, "%s: unknown tap name = '%s' (img_in, txt_in, double.{i}.img, double.{i}.txt, single.{i})", what, name);
@@ -1160,13 +1191,86 @@ int vc_flux_set_tap_impl(void* handle, const char* name, void* dst, char* err, i
   return VC_OK;
 }
 
+int vc_flux_set_monitor_impl(void* handle, int32_t level, VcStat* log, int32_t capacity_evals, float* scratch, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (level < 0 || level > 2) FAIL(VC_ERR_ARG, "flux_set_monitor: level = %d (0: off, 1: v and x, 2: those and every tap site)", level);
+  if (level == 0) { log = nullptr; scratch = nullptr; capacity_evals = 0; }
+  else {
+    if (!log || !scratch) FAIL(VC_ERR_ARG, "flux_set_monitor: null log / scratch (vc_flux_monitor_bytes gives their sizes)");
+    if ((uintptr_t)log & 15) FAIL(VC_ERR_ARG, "flux_set_monitor: log must be 16-byte aligned (a VcStat is one 16-byte store)");
+    if ((uintptr_t)scratch & 3) FAIL(VC_ERR_ARG, "flux_set_monitor: scratch must be 4-byte aligned");
+    if (capacity_evals <= 0) FAIL(VC_ERR_ARG, "flux_set_monitor: capacity_evals = %d must be positive", capacity_evals);
+  }
+  const bool same = level == f.mon_level && log == f.mon_log && scratch == f.mon_scratch && capacity_evals == f.mon_cap;
+  if (f.in_flight) {                          // the captured step of the trajectory keeps its nodes and their row capacity
+    if (!same) FAIL(VC_ERR_STATE, "flux_set_monitor: the monitor cannot change between vc_flux_sample_begin and vc_flux_sample_end");
+    return VC_OK;
+  }
+  f.mon_evals = 0;                            // a (new) statement about the log: nothing of it is reported until something is logged
+  f.mon_B = level && f.prepared ? f.B : 0;
+  f.mon_level = level; f.mon_log = log; f.mon_scratch = scratch; f.mon_cap = capacity_evals;
+  return VC_OK;
+}
+
+int vc_flux_monitor_sites_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!name || namelen <= 0) FAIL(VC_ERR_ARG, "flux_monitor_sites: null / empty name buffer");
+  if (!vcmon::site_name(f.mon_level, f.cfg.depth, f.cfg.depth_single_blocks, index, name, namelen))
+    FAIL(VC_ERR_ARG, "flux_monitor_sites: index = %d, level %d has %d sites", index, f.mon_level, f.mon_sites());
+  return VC_OK;
+}
+
+int vc_flux_monitor_bytes_impl(void* handle, int32_t capacity_evals, int64_t* log_bytes, int64_t* scratch_bytes, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (capacity_evals <= 0) FAIL(VC_ERR_ARG, "flux_monitor_bytes: capacity_evals = %d must be positive", capacity_evals);
+  if (!f.mon_level) FAIL(VC_ERR_STATE, "flux_monitor_bytes: the monitor is off (the sites of a level size the log: vc_flux_set_monitor first)");
+  if (!f.prepared) FAIL(VC_ERR_STATE, "flux_monitor_bytes: call vc_flux_prepare first (the log holds the samples of the prepared geometry)");
+  if (log_bytes) *log_bytes = vcmon::log_bytes(capacity_evals, f.mon_sites(), f.B);
+  if (scratch_bytes) *scratch_bytes = vcmon::scratch_bytes(f.B);
+  return VC_OK;
+}
+
+int vc_flux_monitor_report_impl(void* handle, int32_t* first_bad_eval, int32_t* first_bad_site, int32_t* first_bad_sample, int32_t* evals_logged,
+                                hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!f.mon_level) FAIL(VC_ERR_STATE, "flux_monitor_report: the monitor is off");
+  // the rows were written for mon_B samples - the B prepared when they were logged, whatever has been prepared since (evaluations
+  // are only ever logged behind monitor_fits, which sets it)
+  const int B = f.mon_B, ns = f.mon_sites();
+  const int evals = B > 0 ? std::min(f.mon_evals, f.mon_cap) : 0;
+  int32_t first = -1;
+  if (evals > 0) {      // the scratch is free between two launches of the stream; its first word takes the answer
+    TRY(vc_monitor_first_bad_launch(f.mon_log, (int64_t)evals * ns * B, ns, B, (int32_t*)f.mon_scratch, s, e.buf, e.len));
+    HIP(hipMemcpyAsync(&first, f.mon_scratch, sizeof(first), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
+    HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
+  }
+  int32_t ev = -1, site = -1, b = -1;
+  if (first >= 0) {      // the rank of the entry that was written first -> its site
+    vcmon::log_split(first, ns, B, &ev, &site, &b);
+    site = vcmon::site_at_rank(site, ns);
+  }
+  if (first_bad_eval) *first_bad_eval = ev;
+  if (first_bad_site) *first_bad_site = site;
+  if (first_bad_sample) *first_bad_sample = b;
+  if (evals_logged) *evals_logged = evals;
+  return VC_OK;
+}
+
+int vc_flux_step_nodes_impl(void* handle, int32_t nodes[3], char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!nodes) FAIL(VC_ERR_ARG, "flux_step_nodes: null nodes");
+  if (!f.step.g[0]) FAIL(VC_ERR_STATE, "flux_step_nodes: no captured step (vc_flux_sample_begin* on a stream captures one)");
+  for (int i = 0; i < 3; ++i) nodes[i] = f.step.nodes[i];
+  return VC_OK;
+}
+
 int vc_flux_tap_shape_impl(void* handle, const char* name, int64_t* rows, int32_t* cols, char* err, int errlen) {
   HANDLE(Flux, f, "flux");
   size_t idx = 0;
   TRY(tap_index(f, "flux_tap_shape", name, idx, e));
   if (!rows || !cols) FAIL(VC_ERR_ARG, "flux_tap_shape: null rows / cols");
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_tap_shape: call vc_flux_prepare first (the rows are those of the prepared geometry)");
-  const size_t first_single = 2 + 2 * (size_t)f.cfg.depth;
+  const size_t first_single = (size_t)vcmon::tap_single(f.cfg.depth, 0);
   *rows = (int64_t)f.B * (idx >= first_single ? f.L : idx % 2 ? f.T : f.N);
   *cols = f.D;
   return VC_OK;
@@ -1331,6 +1435,7 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_forward: call vc_flux_prepare first");
   TRY(fresh_scale(f, "flux_forward", e));
   if (!img || !timesteps || !out) FAIL(VC_ERR_ARG, "flux_forward: null argument");
+  TRY(monitor_fits(f, "flux_forward", e));
   TRY(stage_begin(f, f.B * sizeof(float) + 256, e));
   float* ts = stage_take<float>(f, f.B);
   for (int b = 0; b < f.B; ++b) ts[b] = timesteps[b];
@@ -1339,6 +1444,10 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
   TRY(time_precompute(f, 1, timesteps_is_bf16, s, e));
   f.steps_total = f.steps_done = 0;   // MOD now holds this evaluation's rows, not a trajectory's
   f.in_flight = false;
+  if (f.mon_level) {      // row 0 of a zeroed log
+    TRY(vc_zero_fill_launch(f.mon_log, vcmon::log_bytes(f.mon_cap, f.mon_sites(), f.B), s, e.buf, e.len));
+    f.mon_evals = 1;
+  }
   return evaluate(f, nullptr, false, img, out, false, s, e);
 }
 
@@ -1378,6 +1487,9 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
     if (cached) FAIL(VC_ERR_ARG, "flux_sample: true CFG does not work with the step cache: turn one off (vc_flux_set_cfg(handle, 0, 0) / vc_flux_set_step_cache(handle, 0, 0))");
     if (!(f.cfg_scale - f.cfg_scale == 0.0f)) FAIL(VC_ERR_ARG, "flux_sample: the cfg_scale set by vc_flux_set_cfg is not finite");
   }
+  TRY(monitor_fits(f, "flux_sample", e));
+  if (f.mon_level && (int64_t)S * E > f.mon_cap)
+    FAIL(VC_ERR_ARG, "flux_sample: %d steps of %d evaluation(s), the monitor's log holds capacity_evals = %d (vc_flux_set_monitor)", S, E, f.mon_cap);
   if (cached && !f.sc_host) HIP(hipHostMalloc((void**)&f.sc_host, 256, hipHostMallocDefault), "hipHostMalloc");
   const int SE = S * E;
   TRY(stage_begin(f, ((size_t)SE * B + S) * sizeof(float) + 512, e));
@@ -1411,6 +1523,9 @@ int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const
   f.sc_have = false; f.sc_run = f.sc_computed = f.sc_reused = 0;
   f.sc_metrics.clear();
   if (s) TRY(step_graph(f, s, e));
+  // the monitor's log starts zeroed (behind the warm-up evaluation of a new capture, which logs): a kernel, not a memset node
+  if (f.mon_level) TRY(vc_zero_fill_launch(f.mon_log, vcmon::log_bytes(f.mon_cap, f.mon_sites(), B), s, e.buf, e.len));
+  f.mon_evals = 0;
   // no P yet: the first metric is read against zeros (and reported as NaN), never against an earlier trajectory's residual
   if (cached) HIP(hipMemsetAsync(f.SC_P, 0, (size_t)n * f.D * 2, s), "hipMemsetAsync");
   f.steps_total = S; f.steps_done = 0;
@@ -1443,6 +1558,7 @@ int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, h
   const int64_t state_bytes = ode_state_bytes(f);
   for (int i = 0; i < n_steps; ++i) {
     for (int j = 0; j < f.evals; ++j) {      // a step = `evals` replays; the stage is the device-side counter modulo evals
+      ++f.mon_evals;
       if (f.sc_active) { TRY(cached_step(f, s, e)); continue; }
       if (s) HIP(hipGraphLaunch(f.step.g[0], s), "hipGraphLaunch");
       else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
@@ -1568,6 +1684,9 @@ int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const fl
   if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample_dopri5: call vc_flux_prepare first");
   TRY(fresh_scale(f, "flux_sample_dopri5", e));
   if (!x || !cond || !t_grid) FAIL(VC_ERR_ARG, "flux_sample_dopri5: null argument");
+  if (f.mon_level)
+    FAIL(VC_ERR_ARG, "flux_sample_dopri5: the monitor is on (level %d): the adaptive solve's device-side counter is the stage of an attempt, not "
+                     "an evaluation index; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
   if (!f.opt.adaptive || !f.AD_K)
     FAIL(VC_ERR_STATE, "flux_sample_dopri5: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
                        "(the workspace holds no buffers of the adaptive solve)");
@@ -1655,13 +1774,14 @@ int vc_flux_profile_impl(void* handle, int32_t evaluations, VcFluxLaunchClass* o
   HANDLE(Flux, f, "flux");
   if (!f.prepared || f.steps_total == 0) FAIL(VC_ERR_STATE, "flux_profile: call vc_flux_sample_begin first");
   if (!out || !count || capacity <= 0 || evaluations <= 0) FAIL(VC_ERR_ARG, "flux_profile: bad argument");
-  TRY(evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e));       // warm: caches and clocks as inside a trajectory
+  f.mon_paused = true;                                                 // the trajectory's log keeps its rows
+  int rc = evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e);   // warm: caches and clocks as inside a trajectory
   f.prof_recs.clear();
   f.prof_used = 0;
   f.prof_on = true;
-  int rc = VC_OK;
   for (int i = 0; i < evaluations && rc == VC_OK; ++i) rc = evaluate(f, f.STEP, true, nullptr, nullptr, false, s, e);
   f.prof_on = false;
+  f.mon_paused = false;
   if (rc != VC_OK) return rc;
   HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
   int n = 0;

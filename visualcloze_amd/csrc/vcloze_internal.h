@@ -73,6 +73,10 @@ int vc_residual_change_launch(const void* h0, const void* h1, const void* p, voi
                               int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride,
                           int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
+// monitor.hip: the numerics monitor's reduction (vc_tensor_stats) and the scan of a log for the entry with nonfinite != 0 that was written first
+int vc_tensor_stats_launch(const void* x, int x_is_f32, int64_t bstride, int64_t ld, int B, int64_t rows, int cols, VcStat* out, int64_t out_stride,
+                           const int32_t* row_ptr, int capacity, float* scratch, hipStream_t s, char* err, int errlen);
+int vc_monitor_first_bad_launch(const VcStat* log, int64_t n, int n_sites, int B, int32_t* out, hipStream_t s, char* err, int errlen);
 int vc_pack_latent_launch(const void* in, void* out, int C, int h, int w, int64_t ld, int col0, hipStream_t s, char* err, int errlen);
 int vc_pack_mask_launch(const void* in, void* out, int H, int W, int64_t ld, int col0, hipStream_t s, char* err, int errlen);
 int vc_unpack_latent_launch(const void* in, int64_t ld, int col0, void* out, int C, int h, int w, hipStream_t s, char* err, int errlen);
@@ -177,6 +181,12 @@ int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const fl
                                float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
 int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                             int32_t* evaluations, char* err, int errlen);
+int vc_flux_step_nodes_impl(void* handle, int32_t nodes[3], char* err, int errlen);
+int vc_flux_set_monitor_impl(void* handle, int32_t level, VcStat* log, int32_t capacity_evals, float* scratch, char* err, int errlen);
+int vc_flux_monitor_sites_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen);
+int vc_flux_monitor_bytes_impl(void* handle, int32_t capacity_evals, int64_t* log_bytes, int64_t* scratch_bytes, char* err, int errlen);
+int vc_flux_monitor_report_impl(void* handle, int32_t* first_bad_eval, int32_t* first_bad_site, int32_t* first_bad_sample, int32_t* evals_logged,
+                                hipStream_t s, char* err, int errlen);
 
 // vae_engine.hip: the autoencoder handle
 int vc_vae_create_impl(const VcVaeConfig* cfg, void** handle, char* err, int errlen);

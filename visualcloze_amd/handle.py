@@ -163,6 +163,8 @@ class FluxHandle(_Handle):
                 self.set_lora_scale(sc.pop())
         self._step_cache = (0.0, 0)       # vc_flux_set_step_cache: off
         self._cfg = None                  # vc_flux_set_cfg: off
+        self._monitor = None              # vc_flux_set_monitor: off
+        self._monitor_bufs: Dict[tuple, tuple] = {}
         self.geom: Optional[Tuple[int, int, int, int]] = None
         self._host = _HostCopies()
         # the storage order of the bound qkv rows (head-permuted or natural) and the logit bound are PROPERTIES OF THE
@@ -532,6 +534,69 @@ class FluxHandle(_Handle):
         hip._check(L.vc_flux_dopri5_log(self.h, t, dt, r, a, cap, C.byref(n), C.byref(ev)), "vc_flux_dopri5_log")
         att = [(t[i], dt[i], float(r[i]), bool(a[i])) for i in range(n.value)]
         return {"attempts": att, "evaluations": ev.value, "rejected": sum(1 for x in att if not x[3])}
+
+    # ------------------------------------------------------------------ the numerics monitor (vc_flux_set_monitor)
+    def monitor_sites(self) -> list:
+        """vc_flux_monitor_sites: the site names of the level set, in log order"""
+        out, buf = [], C.create_string_buffer(64)
+        while hip.lib().vc_flux_monitor_sites(self.h, len(out), buf, 64) == 0:
+            out.append(buf.value.decode())
+        return out
+
+    def set_monitor(self, level: int, capacity: int = 0) -> None:
+        """vc_flux_set_monitor: level 0 = off; 1 = the statistics of "v" and "x" per evaluation; 2 = those and every tap site.  The
+        log of `capacity` evaluations and the scratch are allocated here for the PREPARED batch (call `prepare` first) and kept per
+        (level, capacity, B): their addresses are part of the key a captured step is kept under, so a second trajectory of the same
+        shape replays the step the first one captured.  Takes effect at the next forward / sample_begin."""
+        L = hip.lib()
+        if not level:
+            hip._check(L.vc_flux_set_monitor(self.h, 0, None, 0, None), "vc_flux_set_monitor")
+            self._monitor = None
+            return
+        if self.geom is None:
+            raise hip.VclozeHipError("set_monitor: call prepare first (the log holds the samples of the prepared geometry)")
+        B = self.geom[0]
+        n_sites = 2 + (len(self.tap_names()) if int(level) >= 2 else 0)
+        key = (int(level), int(capacity), B)
+        if key not in self._monitor_bufs:
+            if len(self._monitor_bufs) > 8:
+                self._monitor_bufs.clear()
+            self._monitor_bufs[key] = (torch.zeros(max(int(capacity), 0) * n_sites * B * C.sizeof(hip.Stat) + 16, dtype=torch.uint8, device=self.dev),
+                                       torch.empty(B * 4 * hip.MONITOR_MAX_BLOCKS, dtype=torch.float32, device=self.dev))
+        log, scratch = self._monitor_bufs[key]
+        hip._check(L.vc_flux_set_monitor(self.h, int(level), log.data_ptr(), int(capacity), scratch.data_ptr()), "vc_flux_set_monitor")
+        lb, sb = C.c_int64(0), C.c_int64(0)
+        hip._check(L.vc_flux_monitor_bytes(self.h, int(capacity), C.byref(lb), C.byref(sb)), "vc_flux_monitor_bytes")
+        if lb.value > log.numel() or sb.value > scratch.numel() * 4:
+            L.vc_flux_set_monitor(self.h, 0, None, 0, None)
+            raise hip.VclozeHipError(f"set_monitor: the library asks for {lb.value} + {sb.value} bytes, {log.numel()} + {scratch.numel() * 4} allocated")
+        self._monitor = (int(level), int(capacity), B, log, scratch, self.monitor_sites())
+
+    def step_nodes(self) -> tuple:
+        """vc_flux_step_nodes: the graph nodes of the captured step of the trajectory begun last (step; with the step cache on head,
+        tail-compute, tail-reuse)"""
+        n = (C.c_int32 * 3)()
+        hip._check(hip.lib().vc_flux_step_nodes(self.h, n), "vc_flux_step_nodes")
+        return tuple(n)
+
+    def monitor_report(self, stream=None):
+        """vc_flux_monitor_report: (evaluation, site name, sample) of the first logged entry with a NaN / inf - in evaluation, then
+        site, then sample order - or None; synchronises the stream"""
+        ev, site, b, n = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(0)
+        hip._check(hip.lib().vc_flux_monitor_report(self.h, C.byref(ev), C.byref(site), C.byref(b), C.byref(n),
+                                                    stream if stream is not None else hip.cur_stream()), "vc_flux_monitor_report")
+        self._monitor_evals = n.value
+        return None if ev.value < 0 else (ev.value, self._monitor[5][site.value], b.value)
+
+    def monitor_log(self, stream=None) -> dict:
+        """the log of the evaluations issued since the last forward / sample_begin: {site name: {"max_abs", "sum_sq", "nonfinite",
+        "count": numpy arrays [evaluations, B]}}; synchronises the stream"""
+        if getattr(self, "_monitor", None) is None:
+            raise hip.VclozeHipError("monitor_log: the monitor is off (set_monitor)")
+        self.monitor_report(stream)
+        _, cap, B, log, _, names = self._monitor
+        rec = hip.stats_to_numpy(log[:cap * len(names) * B * C.sizeof(hip.Stat)]).reshape(cap, len(names), B)[:self._monitor_evals]
+        return {name: {f: rec[:, i, :][f].copy() for f in hip.STAT_DTYPE.names} for i, name in enumerate(names)}
 
 
 class VaeHandle(_Handle):

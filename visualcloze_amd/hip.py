@@ -11,6 +11,7 @@ import os
 import subprocess
 from typing import Optional
 
+import numpy as np
 import torch  # noqa: F401  (must be imported first so the process shares torch's HIP runtime)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -184,6 +185,13 @@ class FluxLaunchClass(C.Structure):          # VcFluxLaunchClass (vc_flux_profil
 
 LAUNCH_GEMM, LAUNCH_ATTENTION, LAUNCH_LN_MODULATE, LAUNCH_PASS, LAUNCH_TAP = 1, 2, 3, 4, 5
 
+
+class Stat(C.Structure):                     # VcStat (vc_tensor_stats, vc_flux_set_monitor)
+    _fields_ = [("max_abs", C.c_float), ("sum_sq", C.c_float), ("nonfinite", C.c_uint32), ("count", C.c_uint32)]
+
+
+MONITOR_MAX_BLOCKS = 256                     # VC_MONITOR_MAX_BLOCKS
+
 SYMBOLS = {
     "vc_abi_version": (C.c_int, []),
     "vc_last_error": (C.c_char_p, []),
@@ -217,6 +225,8 @@ SYMBOLS = {
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_cfg_combine": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _vp]),
+    "vc_monitor_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_tensor_stats": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp]),
     "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_double, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
@@ -274,6 +284,11 @@ SYMBOLS = {
     "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
     "vc_flux_profile": (C.c_int, [_vp, _i32, C.POINTER(FluxLaunchClass), _i32, C.POINTER(_i32), _vp]),
+    "vc_flux_step_nodes": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vc_flux_set_monitor": (C.c_int, [_vp, _i32, _vp, _i32, _vp]),
+    "vc_flux_monitor_sites": (C.c_int, [_vp, _i32, C.c_char_p, _i32]),
+    "vc_flux_monitor_bytes": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "vc_flux_monitor_report": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "vc_vae_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "vc_vae_create": (C.c_int, [C.POINTER(VaeConfig), C.POINTER(_vp)]),
     "vc_vae_destroy": (C.c_int, [_vp]),
@@ -370,6 +385,9 @@ def lib() -> C.CDLL:
         l.vc_text_struct_sizes(vsize)
         if vsize[0] != C.sizeof(TextConfig):
             raise VclozeHipError(f"libvcloze_hip.so sizeof(VcTextConfig) {vsize[0]} differs from the ctypes mirror - rebuild")
+        l.vc_monitor_struct_sizes(vsize)
+        if vsize[0] != C.sizeof(Stat):
+            raise VclozeHipError(f"libvcloze_hip.so sizeof(VcStat) {vsize[0]} differs from the ctypes mirror - rebuild")
         gsize = (C.c_int32 * 3)()
         l.vc_grid_struct_sizes(gsize)
         if list(gsize) != [C.sizeof(GridConfig), C.sizeof(GridJob), C.sizeof(GridSdedit)]:
@@ -858,6 +876,31 @@ def residual_change(h0, h1, p, r=None, stream=None):
                                     scratch.data_ptr(), B, h0.numel() // B, stream if stream is not None else cur_stream()),
            "vc_residual_change")
     return r, sums, metric
+
+
+STAT_DTYPE = np.dtype([("max_abs", np.float32), ("sum_sq", np.float32), ("nonfinite", np.uint32), ("count", np.uint32)])   # VcStat
+
+
+def stats_to_numpy(log: torch.Tensor) -> np.ndarray:
+    """a device tensor of VcStat records (uint8, 16 bytes each) -> a structured numpy array (fields of STAT_DTYPE)"""
+    return log.detach().cpu().contiguous().view(torch.uint8).numpy().view(STAT_DTYPE)
+
+
+def tensor_stats(x, out=None, row_ptr=None, capacity: int = 1, stream=None) -> torch.Tensor:
+    """vc_tensor_stats on x [B, rows, cols], bf16 or f32, unit stride in the last dimension (any row / sample strides: views of a
+    strided stream are fine): per sample (max |x| and sum x^2 over the finite elements, the number of non-finite elements, the number
+    of elements).  out: a uint8 tensor of capacity * B records of 16 bytes (`stats_to_numpy` reads it); the records go to row
+    *row_ptr (an int32 device tensor), or to row 0.  Returns out."""
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() != 3 or x.stride(2) != 1:
+        raise VclozeHipError("vc_tensor_stats: a [B, rows, cols] bf16 / f32 tensor with unit column stride expected")
+    B, R, Cc = x.shape
+    if out is None:
+        out = torch.zeros(capacity * B * 16, dtype=torch.uint8, device=x.device)
+    scratch = torch.empty(B * 4 * MONITOR_MAX_BLOCKS, dtype=torch.float32, device=x.device)
+    _check(lib().vc_tensor_stats(x.data_ptr(), int(x.dtype == torch.float32), x.stride(0), x.stride(1), B, R, Cc, out.data_ptr(), B,
+                                 _p(row_ptr), int(capacity), scratch.data_ptr(), stream if stream is not None else cur_stream()),
+           "vc_tensor_stats")
+    return out
 
 
 def _residual_op(fn, what, a, b, out, stream):

@@ -274,6 +274,15 @@ class Flux(nn.Module):
         # (engine.FluxEngine) over the op-level ABI - bit-identical results, kept for the parity mode and per-block taps.
         self.use_handle = True
         self.last_step_cache_stats = None      # of the last trajectory sampled with a transport.StepCache: one dict per chunk
+        # the numerics monitor of the C handle (vc_flux_set_monitor): 0 = off, 1 = per evaluation the statistics of the model's output
+        # "v" and of the state "x", 2 = those and every residual stream.  Handle-only: with the Python-ordered plan a non-zero value
+        # raises ValueError.  After a fused solve or a forward last_monitor_log holds one `FluxHandle.monitor_log()` dict per chunk
+        # of samples, last_monitor_report the first bad (chunk, evaluation, site, sample of the chunk) or None; with monitor_strict
+        # both raise FloatingPointError on one.  0 leaves the handle's monitor alone (a caller may have set it on `handle()` itself).
+        self.monitor = 0
+        self.monitor_strict = False
+        self.last_monitor_log = None
+        self.last_monitor_report = None
         # "merged": W + s*B@A folded once (the product mode).  "ref": LinearLora.forward executed as the
         # reference does - base GEMM, two skinny GEMMs, three bf16 roundings (models/modules/lora.py:92-98) - so that
         # the merge's one-rounding deviation is a choice, not a necessity; slower (+8 % FLOPs, unfused epilogues).
@@ -612,6 +621,8 @@ class Flux(nn.Module):
         timesteps = per_sample(timesteps, B)
         lay = MaskLayout(txt_mask, img_mask, B, T, N)
         h = self.handle()
+        level = self.monitor_level(h)
+        logs, bad = [], None
         mb = self.max_batch()
         for b0 in range(0, B, mb):                     # samples of a chunk run as ONE stacked launch sequence
             bs = min(mb, B - b0)
@@ -620,7 +631,18 @@ class Flux(nn.Module):
                 h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
                           lay.img_rows(img_ids, sl), lay.txt_rows(txt_ids, sl), 1, lay.kv_len(sl), lay.kv_gap(sl))
                 o = torch.empty(bs, N, self.out_channels, dtype=torch.bfloat16, device=dev)
-                h.forward(bf(lay.img_rows(img, sl)), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
+                if level:
+                    h.set_monitor(level, 1)
+                try:
+                    h.forward(bf(lay.img_rows(img, sl)), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
+                    if level:
+                        first = h.monitor_report()
+                        if first is not None and bad is None:
+                            bad = (len(logs),) + first
+                        logs.append(h.monitor_log())
+                finally:
+                    if level:
+                        h.set_monitor(0)                # the log was sized for this chunk
                 out[sl].copy_(lay.img_rows_back(o, sl))
                 continue
             ws = eng.workspace(T, N, 1, bs)
@@ -630,7 +652,21 @@ class Flux(nn.Module):
             ws.XIN.copy_(bf(lay.img_rows(img, sl)).reshape(bs * N, -1))
             eng.eval_once(ws, None, euler=False, concat=False)
             out[sl].copy_(lay.img_rows_back(ws.V.reshape(bs, N, -1), sl))
+        if level:
+            self.last_monitor_log, self.last_monitor_report = logs, bad
+            if bad is not None and self.monitor_strict:
+                raise FloatingPointError("the numerics monitor found a NaN / inf: chunk %d, evaluation %d, site '%s', sample %d of the chunk "
+                                         "(Flux.last_monitor_log holds the statistics)" % bad)
         return out
+
+    def monitor_level(self, h) -> int:
+        """`monitor`, checked: 0, 1 or 2, and never silently ignored - only the C handle `h` implements it"""
+        if self.monitor not in (0, 1, 2):
+            raise ValueError(f"monitor must be 0, 1 or 2, got {self.monitor!r}")
+        if self.monitor and h is None:
+            raise ValueError("monitor needs the C handle: not available with the Python-ordered plan (use_handle False, or "
+                             "lora_mode='ref' unless ref_plan='handle')")
+        return int(self.monitor)
 
     def max_batch(self) -> int:
         """samples per launch sequence: the engine's (one in the Python-ordered un-merged mode), the handle's where it runs that mode"""

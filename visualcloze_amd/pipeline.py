@@ -86,6 +86,9 @@ def _grid_handle(model, ae, t5, clip, rng, what: str, **unsupported):
     for name, v in unsupported.items():
         if v is not None:
             raise ValueError(f"{what}(use_grid_handle=True) draws every noise tensor itself: {name} must be None")
+    if getattr(model, "monitor", 0):
+        raise ValueError(f"{what}(use_grid_handle=True) drives its own trajectory, which the numerics monitor does not log: set "
+                         "model.monitor = 0 or use_grid_handle=False")
     if not (getattr(model, "use_handle", False) and model.handle() is not None and getattr(ae, "use_handle", False)
             and t5._handle_serves() and clip._handle_serves()):
         raise ValueError(f"{what}(use_grid_handle=True) needs the C handles of all four modules: model.use_handle, ae.use_handle, "
@@ -189,7 +192,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
                   t5_ids: torch.Tensor, clip_ids: torch.Tensor, seed: int, cfg: float = 30.0, steps: int = 30,
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
                   solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
-                  step_cache=None, use_grid_handle: bool = False, adaptive: Optional[dict] = None) -> List[torch.Tensor]:
+                  step_cache=None, use_grid_handle: bool = False, adaptive: Optional[dict] = None,
+                  monitor: Optional[int] = None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -207,7 +211,22 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     use_handle switches of all four modules on (ValueError otherwise); `rng.offset` advances as it does here.
     `adaptive`: None (the default), or dict(rtol=, atol=) - denoise with the error-controlled Dormand-Prince 5(4) solve instead of
     `solver` (`denoise_grid`); `model.last_adaptive_log` tells what it did.  Refused together with use_grid_handle=True: the grid
-    handle runs the fixed-grid solvers only."""
+    handle runs the fixed-grid solvers only.
+    `monitor`: None (the default: `model.monitor` as it stands), or 0 | 1 | 2 - the numerics monitor of the Flux handle for this call
+    (`Flux.monitor`): `model.last_monitor_log` / `model.last_monitor_report` tell what the solve's evaluations held, and with
+    `model.monitor_strict` a NaN / inf raises FloatingPointError.  Refused together with use_grid_handle=True and with `adaptive`."""
+    if monitor is not None:
+        if monitor and (use_grid_handle or adaptive is not None):
+            raise ValueError("generate_grid(monitor=...) works with the fixed-grid solvers of the Flux handle, not with use_grid_handle=True "
+                             "(the grid handle drives its own trajectory) or adaptive=")
+        before = model.monitor
+        model.monitor = monitor
+        try:
+            return generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
+                                 encode_noise=encode_noise, decode_rows=decode_rows, solver=solver, time_shifting_factor=time_shifting_factor,
+                                 rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle, adaptive=adaptive)
+        finally:
+            model.monitor = before
     if adaptive is not None and use_grid_handle:
         raise ValueError("generate_grid(adaptive=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid solvers only")
     if use_grid_handle:

@@ -446,6 +446,8 @@ def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_at
     st = eng.stream
     st.wait_stream(torch.cuda.current_stream())
     h = flux.handle()
+    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_dopri5 refuses it: its counter is a stage, not an evaluation)
+        raise ValueError("monitor: the adaptive solve has no evaluation index to log under; set Flux.monitor = 0 or use a fixed-grid solver")
     h.set_step_cache(None)
     h.set_cfg(cfg_scale)
     h.set_adaptive(True)
@@ -590,6 +592,8 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
         h.set_cfg(cfg_scale)
     elif cfg_scale is not None:
         raise hip.VclozeHipError("true CFG in the fused loop needs the C handle")
+    level = flux.monitor_level(h)                  # ValueError with the Python-ordered plan: never silently ignored
+    mon_logs, mon_bad = [], None
     mb = flux.max_batch()
     if cfg_scale is None:
         chunks = [slice(b0, min(b0 + mb, B)) for b0 in range(0, B, mb)]
@@ -605,7 +609,18 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
                           lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), S * E, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
                 xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()   # updated in place: never the caller's
                 tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
-                h.sample_ode(method, xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+                if level:
+                    h.set_monitor(level, S * E)
+                try:
+                    h.sample_ode(method, xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+                    if level:
+                        bad = h.monitor_report(s)
+                        if bad is not None and mon_bad is None:
+                            mon_bad = (len(mon_logs),) + bad
+                        mon_logs.append(h.monitor_log(s))
+                finally:
+                    if level:
+                        h.set_monitor(0)           # the log was sized for this chunk
                 if step_cache is not None:
                     stats.append(h.step_cache_stats(S))
                 if return_trajectory:
@@ -632,6 +647,11 @@ def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=
         if cfg_scale is not None:
             h.set_cfg(None)                        # a later trajectory driven on this handle directly is a plain one again
     torch.cuda.current_stream().wait_stream(st)
+    if level:
+        flux.last_monitor_log, flux.last_monitor_report = mon_logs, mon_bad
+        if mon_bad is not None and flux.monitor_strict:
+            raise FloatingPointError("the numerics monitor found a NaN / inf: chunk %d, evaluation %d, site '%s', sample %d of the chunk "
+                                     "(Flux.last_monitor_log holds the statistics)" % mon_bad)
     if step_cache is not None:
         flux.last_step_cache_stats = stats         # one dict per chunk of <= MAX_BATCH samples, in order
         if sampler is not None:
