@@ -9,6 +9,7 @@ The modules below are PARAMETER HOLDERS: every FLOP of `forward` runs in libvclo
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -237,6 +238,56 @@ def per_sample(v: Optional[Tensor], B: int) -> Optional[Tensor]:
     if v.numel() != B:
         raise ValueError(f"expected 1 or {B} per-sample values, got {v.numel()}")
     return v
+
+
+class ChunkPlan:
+    """How one call's batch becomes chunks of handle calls - written down once, for Flux.forward, Flux.block_taps and the fused
+    solves of transport.py.  Built per call from the caller's tensors: checks them, broadcasts the guidance, lays the masks out
+    (`lay`) and cuts the B samples into `chunks` of at most `max_batch`: slices, or with `pairs` (true CFG) `transport.cfg_chunks`'
+    index lists.  `channels`: (of the state x, of cond) where x || cond feeds img_in.  Plain arguments only: no GPU needed."""
+
+    def __init__(self, B: int, N: int, txt, y, guidance, img_ids, txt_ids, txt_mask, img_mask, params: FluxParams,
+                 dev: torch.device, max_batch: int, pairs: bool = False, channels=None):
+        if channels is not None and sum(channels) != params.in_channels:
+            raise hip.VclozeHipError(f"x ({channels[0]}) || cond ({channels[1]}) does not match in_channels {params.in_channels}")
+        if params.guidance_embed and guidance is None:
+            raise ValueError("Didn't get guidance strength for guidance distilled model.")
+        self.B, self.N, self.T, self.dev = B, N, txt.shape[1], dev
+        self.txt, self.y, self.img_ids, self.txt_ids = txt, y, img_ids, txt_ids
+        self.gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
+        self.guidance = per_sample(guidance, B)
+        self.lay = MaskLayout(txt_mask, img_mask, B, self.T, N)
+        self.img_back, self.txt_back = self.lay.img_rows_back, self.lay.txt_rows_back      # (kernel-order rows, sl) -> the caller's order
+        if pairs:
+            from .transport import cfg_chunks
+            self.chunks = cfg_chunks(B, max_batch)
+        else:                                          # samples of a chunk run as ONE stacked launch sequence
+            self.chunks = [slice(b0, min(b0 + max_batch, B)) for b0 in range(0, B, max_batch)]
+
+    def size(self, sl) -> int:
+        return len(range(self.B)[sl]) if isinstance(sl, slice) else len(sl)
+
+    def _inputs(self, sl) -> tuple:
+        # the ids and the guidance stay views of the caller's storage (`MaskLayout._take`): handle._HostCopies keys on that memory
+        bf = lambda t: t.to(self.dev, torch.bfloat16).contiguous()  # noqa: E731
+        return (bf(self.lay.txt_rows(self.txt, sl)), bf(self.y[sl]), None if self.guidance is None else self.guidance[sl], self.gbf16,
+                self.lay.img_rows(self.img_ids, sl), self.lay.txt_rows(self.txt_ids, sl))
+
+    def prepare_args(self, sl, max_evals: int) -> tuple:
+        """the positional arguments of `FluxHandle.prepare` for a chunk: h.prepare(*plan.prepare_args(sl, n), stream=s)"""
+        return self._inputs(sl) + (max_evals, self.lay.kv_len(sl), self.lay.kv_gap(sl))
+
+    def twin_prepare_args(self, sl, timesteps):
+        """(args behind the workspace, kwargs) of the Python-ordered twin's `FluxEngine.prepare_sample`: the same tensors"""
+        return self._inputs(sl) + (timesteps, self.lay.kv_len(sl)), dict(kv_gap=self.lay.kv_gap(sl))
+
+    def img_rows(self, x: Tensor, sl, dtype, copy: bool = False) -> Tensor:
+        """kernel-order rows of a chunk of a [B, N, ...] image-stream tensor, contiguous on the device; `copy`: never x's memory"""
+        return self.lay.img_rows(x, sl).to(self.dev, dtype, copy=copy).contiguous()
+
+    def joint_back(self, o: Tensor, sl) -> Tensor:
+        """a chunk of the joint stream [bs, T + N, ...] (text rows, then image rows: the SingleStream taps) in the caller's order"""
+        return torch.cat((self.txt_back(o[:, :self.T], sl), self.img_back(o[:, self.T:], sl)), dim=1)
 
 
 class Flux(nn.Module):
@@ -604,60 +655,75 @@ class Flux(nn.Module):
         hip.cfg_combine(out[:h], out[h:], cfg_scale, out=out[:h])
         return out.to(img.dtype) if img.dtype.is_floating_point else out
 
+    def chunk_plan(self, B: int, N: int, kw: dict, pairs: bool = False, channels=None) -> ChunkPlan:
+        """the `ChunkPlan` of one call on this model, with forward's arguments in `kw`"""
+        return ChunkPlan(B, N, kw["txt"], kw["y"], kw.get("guidance"), kw["img_ids"], kw["txt_ids"], kw.get("txt_mask"), kw.get("img_mask"),
+                         self.params, self.plan().dev, self.max_batch(), pairs, channels)
+
+    def _forward_plan(self, img, timesteps, **kw):
+        """(the ChunkPlan of one forward, its per-sample timesteps)"""
+        if img.ndim != 3 or kw["txt"].ndim != 3:
+            raise ValueError("Input img and txt tensors must have 3 dimensions.")
+        B, N, _ = img.shape
+        return self.chunk_plan(B, N, kw), per_sample(timesteps, B)
+
     def _forward_bf16(self, img, img_ids, txt, txt_ids, timesteps, y, txt_mask=None, img_mask=None, guidance=None) -> Tensor:
         """Flux.forward as the kernels leave it: bf16 [B, N, out_channels] on the engine's device"""
-        if img.ndim != 3 or txt.ndim != 3:
-            raise ValueError("Input img and txt tensors must have 3 dimensions.")
-        if self.params.guidance_embed and guidance is None:
-            raise ValueError("Didn't get guidance strength for guidance distilled model.")
-        eng = self.plan()
-        B, N, _ = img.shape
-        T = txt.shape[1]
-        dev = eng.dev
-        out = torch.empty(B, N, self.out_channels, dtype=torch.bfloat16, device=dev)
-        bf = lambda t: t.to(dev, torch.bfloat16).contiguous()  # noqa: E731
-        gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
-        guidance = per_sample(guidance, B)
-        timesteps = per_sample(timesteps, B)
-        lay = MaskLayout(txt_mask, img_mask, B, T, N)
+        plan, timesteps = self._forward_plan(img, timesteps, img_ids=img_ids, txt=txt, txt_ids=txt_ids, y=y, txt_mask=txt_mask,
+                                             img_mask=img_mask, guidance=guidance)
+        out = torch.empty(plan.B, plan.N, self.out_channels, dtype=torch.bfloat16, device=plan.dev)
         h = self.handle()
-        level = self.monitor_level(h)
-        logs, bad = [], None
-        mb = self.max_batch()
-        for b0 in range(0, B, mb):                     # samples of a chunk run as ONE stacked launch sequence
-            bs = min(mb, B - b0)
-            sl = slice(b0, b0 + bs)
-            if h is not None:                           # one C call per chunk: vc_flux_prepare + vc_flux_forward
-                h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                          lay.img_rows(img_ids, sl), lay.txt_rows(txt_ids, sl), 1, lay.kv_len(sl), lay.kv_gap(sl))
-                o = torch.empty(bs, N, self.out_channels, dtype=torch.bfloat16, device=dev)
-                if level:
-                    h.set_monitor(level, 1)
-                try:
-                    h.forward(bf(lay.img_rows(img, sl)), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
-                    if level:
-                        first = h.monitor_report()
-                        if first is not None and bad is None:
-                            bad = (len(logs),) + first
-                        logs.append(h.monitor_log())
-                finally:
-                    if level:
-                        h.set_monitor(0)                # the log was sized for this chunk
-                out[sl].copy_(lay.img_rows_back(o, sl))
-                continue
-            ws = eng.workspace(T, N, 1, bs)
-            eng.prepare_sample(ws, bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                               lay.img_rows(img_ids, sl), lay.txt_rows(txt_ids, sl), timesteps[sl].float().reshape(1, bs),
-                               lay.kv_len(sl), timesteps_is_bf16=timesteps.dtype == torch.bfloat16, kv_gap=lay.kv_gap(sl))
-            ws.XIN.copy_(bf(lay.img_rows(img, sl)).reshape(bs * N, -1))
-            eng.eval_once(ws, None, euler=False, concat=False)
-            out[sl].copy_(lay.img_rows_back(ws.V.reshape(bs, N, -1), sl))
-        if level:
-            self.last_monitor_log, self.last_monitor_report = logs, bad
-            if bad is not None and self.monitor_strict:
-                raise FloatingPointError("the numerics monitor found a NaN / inf: chunk %d, evaluation %d, site '%s', sample %d of the chunk "
-                                         "(Flux.last_monitor_log holds the statistics)" % bad)
+        with self.monitored(h) as monitored:
+            if h is None:
+                return self._forward_twin(plan, img, timesteps, out)
+            for sl in plan.chunks:                      # one C call per chunk: vc_flux_prepare + vc_flux_forward
+                h.prepare(*plan.prepare_args(sl, 1))
+                o = torch.empty(plan.size(sl), plan.N, self.out_channels, dtype=torch.bfloat16, device=plan.dev)
+                with monitored(1):
+                    h.forward(plan.img_rows(img, sl, torch.bfloat16), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
+                out[sl].copy_(plan.img_back(o, sl))
         return out
+
+    def _forward_twin(self, plan: ChunkPlan, img, timesteps, out) -> Tensor:
+        """`_forward_bf16` with the Python-ordered plan (engine.FluxEngine): the same launches, ordered from here"""
+        eng = self.engine()
+        for sl in plan.chunks:
+            bs = plan.size(sl)
+            ws = eng.workspace(plan.T, plan.N, 1, bs)
+            args, kwargs = plan.twin_prepare_args(sl, timesteps[sl].float().reshape(1, bs))
+            eng.prepare_sample(ws, *args, timesteps_is_bf16=timesteps.dtype == torch.bfloat16, **kwargs)
+            ws.XIN.copy_(plan.img_rows(img, sl, torch.bfloat16).reshape(bs * plan.N, -1))
+            eng.eval_once(ws, None, euler=False, concat=False)
+            out[sl].copy_(plan.img_back(ws.V.reshape(bs, plan.N, -1), sl))
+        return out
+
+    @contextmanager
+    def monitored(self, h):
+        """The numerics monitor around one call on the handle `h`, at the checked `monitor_level(h)`: yields chunk(capacity, stream),
+        the bracket of one chunk's run.  A call that ends well leaves last_monitor_log / last_monitor_report."""
+        level, logs, bad = self.monitor_level(h), [], []
+
+        @contextmanager
+        def chunk(capacity: int, stream=None):
+            if level:
+                h.set_monitor(level, capacity)
+            try:
+                yield
+                if level:
+                    first = h.monitor_report(stream)
+                    if first is not None and not bad:
+                        bad.append((len(logs),) + first)
+                    logs.append(h.monitor_log(stream))
+            finally:
+                if level:
+                    h.set_monitor(0)                    # the log was sized for this chunk
+
+        yield chunk
+        if level:
+            self.last_monitor_log, self.last_monitor_report = logs, bad[0] if bad else None
+            if bad and self.monitor_strict:
+                raise FloatingPointError("the numerics monitor found a NaN / inf: chunk %d, evaluation %d, site '%s', sample %d of the chunk "
+                                         "(Flux.last_monitor_log holds the statistics)" % bad[0])
 
     def monitor_level(self, h) -> int:
         """`monitor`, checked: 0, 1 or 2, and never silently ignored - only the C handle `h` implements it"""
@@ -685,43 +751,31 @@ class Flux(nn.Module):
         h = self.handle()
         if h is None:
             raise hip.VclozeHipError("block_taps needs the C handle (use_handle True; with lora_mode 'ref': ref_plan 'handle')")
-        if img.ndim != 3 or txt.ndim != 3:
-            raise ValueError("Input img and txt tensors must have 3 dimensions.")
-        if self.params.guidance_embed and guidance is None:
-            raise ValueError("Didn't get guidance strength for guidance distilled model.")
-        eng = self.plan()
-        B, N, _ = img.shape
-        T, D, dev = txt.shape[1], self.hidden_size, eng.dev
-        bf = lambda t: t.to(dev, torch.bfloat16).contiguous()  # noqa: E731
-        gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
-        guidance, timesteps = per_sample(guidance, B), per_sample(timesteps, B)
-        lay = MaskLayout(txt_mask, img_mask, B, T, N)
+        plan, timesteps = self._forward_plan(img, timesteps, img_ids=img_ids, txt=txt, txt_ids=txt_ids, y=y, txt_mask=txt_mask,
+                                             img_mask=img_mask, guidance=guidance)
+        T, N, D, dev = plan.T, plan.N, self.hidden_size, plan.dev
         names = h.tap_names()
         parts = {n: [] for n in names + ["out"]}
-        mb = self.max_batch()
-        for b0 in range(0, B, mb):
-            bs = min(mb, B - b0)
-            sl = slice(b0, b0 + bs)
-            h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                      lay.img_rows(img_ids, sl), lay.txt_rows(txt_ids, sl), 1, lay.kv_len(sl), lay.kv_gap(sl))
+        for sl in plan.chunks:
+            bs = plan.size(sl)
+            h.prepare(*plan.prepare_args(sl, 1))
             bufs = {n: torch.empty(*h.tap_shape(n), dtype=torch.bfloat16, device=dev) for n in names}
             try:
                 for n, t in bufs.items():
                     h.set_tap(n, t)
                 o = torch.empty(bs, N, self.out_channels, dtype=torch.bfloat16, device=dev)
-                h.forward(bf(lay.img_rows(img, sl)), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
+                h.forward(plan.img_rows(img, sl, torch.bfloat16), timesteps[sl], timesteps.dtype == torch.bfloat16, o)
             finally:
                 for n in names:
                     h.set_tap(n, None)
-            parts["out"].append(lay.img_rows_back(o, sl))
+            parts["out"].append(plan.img_back(o, sl))
             for n, t in bufs.items():
                 if n.startswith("single."):
-                    j = t.reshape(bs, T + N, D)
-                    parts[n].append(torch.cat((lay.txt_rows_back(j[:, :T], sl), lay.img_rows_back(j[:, T:], sl)), dim=1))
+                    parts[n].append(plan.joint_back(t.reshape(bs, T + N, D), sl))
                 elif n == "txt_in" or n.endswith(".txt"):
-                    parts[n].append(lay.txt_rows_back(t.reshape(bs, T, D), sl))
+                    parts[n].append(plan.txt_back(t.reshape(bs, T, D), sl))
                 else:
-                    parts[n].append(lay.img_rows_back(t.reshape(bs, N, D), sl))
+                    parts[n].append(plan.img_back(t.reshape(bs, N, D), sl))
         return {n: torch.cat(v, dim=0) for n, v in parts.items()}
 
 

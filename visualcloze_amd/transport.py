@@ -25,6 +25,7 @@ csrc/elementwise.hip (ode_update).
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from typing import Callable, Optional
 
 import torch
@@ -295,6 +296,16 @@ class StepCache:
         return hash((self.threshold, self.max_consecutive))
 
 
+def _classify(model: Callable, model_kwargs: dict):
+    """-> (owner, kind, kw, cfg_scale): kind "forward" / "forward_with_cfg" = that bound method of a visualcloze_amd.Flux (owner), else
+    "foreign"; kw a copy of model_kwargs, for forward_with_cfg without its "cfg_scale" (which is None otherwise)"""
+    from .model import Flux
+    owner, name, kw = getattr(model, "__self__", None), getattr(model, "__name__", ""), dict(model_kwargs)
+    if not isinstance(owner, Flux) or name not in ("forward", "forward_with_cfg"):
+        return owner, "foreign", kw, None
+    return owner, name, kw, float(kw.pop("cfg_scale", 1.0)) if name == "forward_with_cfg" else None
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
@@ -319,19 +330,16 @@ class Sampler:
 
         def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
-            from .model import Flux
-            owner = getattr(model, "__self__", None)
-            if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward_with_cfg":
+            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
+            if kind == "forward_with_cfg":
                 if step_cache is not None:
                     raise ValueError("step_cache works with Flux.forward only, not with forward_with_cfg (true CFG)")
-                kw = dict(model_kwargs)
-                cfg_scale = float(kw.pop("cfg_scale", 1.0))
                 if _cfg_fusable(owner, x, sampling_method, kw):
                     return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, None, self, cfg_scale=cfg_scale)
                 # stepped eagerly (unequal image masks within a pair, no C handle, an f16 / f64 state): the same bf16 velocity
                 fwd = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k).to(torch.bfloat16)  # noqa: E731
                 return _sample_foreign(fwd, x, kw, t, return_trajectory, sampling_method)
-            if isinstance(owner, Flux) and getattr(model, "__name__", "") == "forward":
+            if kind == "forward":
                 if step_cache is not None:      # never silently ignored: only the C handle's loop implements it
                     if owner.handle() is None:
                         raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' (unless ref_plan='handle') "
@@ -339,14 +347,14 @@ class Sampler:
                     if not _fusable(owner, x, sampling_method):
                         raise ValueError(f"step_cache: a {x.dtype} state is stepped eagerly, where no cache exists")
                 if _fusable(owner, x, sampling_method):
-                    return _sample_fused(owner, x, dict(model_kwargs), t, return_trajectory, sampling_method, step_cache, self)
+                    return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, step_cache, self)
                 # stepped eagerly; the velocity of this model is a bf16 tensor as the reference's is under autocast
                 # (visualcloze.py:363) whatever dtype Flux.forward hands back to its caller: dt * f stays a bf16 product
                 fwd = model
                 model = lambda xin, **k: fwd(xin, **k).to(torch.bfloat16)  # noqa: E731
             elif step_cache is not None:
                 raise ValueError("step_cache: only the fused loop of a visualcloze_amd.Flux implements it, not a foreign callable")
-            return _sample_foreign(model, x, dict(model_kwargs), t, return_trajectory, sampling_method)
+            return _sample_foreign(model, x, kw, t, return_trajectory, sampling_method)
 
         return _sample
 
@@ -366,11 +374,8 @@ class Sampler:
 
         def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
-            from .model import Flux
-            owner, name = getattr(model, "__self__", None), getattr(model, "__name__", "")
-            kw = dict(model_kwargs)
-            is_flux = isinstance(owner, Flux) and name in ("forward", "forward_with_cfg")
-            cfg_scale = float(kw.pop("cfg_scale", 1.0)) if is_flux and name == "forward_with_cfg" else None
+            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
+            is_flux = kind != "foreign"
             fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
             if fused and cfg_scale is not None:
                 fused = _cfg_fusable(owner, x, "euler", kw)
@@ -418,66 +423,71 @@ def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max
     return (out if return_trajectory else out[-1:]), _log_dict(log, len(calls))
 
 
-@torch.no_grad()
-def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None):
-    """vc_flux_sample_dopri5 per chunk of samples (true CFG: chunks of whole pairs): ONE step size per chunk, so a sample's result
-    depends on the samples it shares a chunk with."""
-    eng = flux.plan()
-    dev = eng.dev
+@contextmanager
+def _on_capture_stream(st):
+    """run on the plan's capture stream `st`: behind torch's current stream, which waits for it afterwards - on failure too"""
+    st.wait_stream(torch.cuda.current_stream())
+    try:
+        with torch.cuda.stream(st):
+            yield st.cuda_stream
+    finally:
+        torch.cuda.current_stream().wait_stream(st)
+
+
+def _solve_begin(flux, x, kw, S, return_trajectory, pairs=False):
+    """-> (ChunkPlan, cond, out [B, N, C], traj [S, B, N, C] or None) of a fused solve of the state x"""
     B, N, C = x.shape
     cond = kw.get("cond")
     if cond is None:
         raise hip.VclozeHipError("fused sampler expects model_kwargs['cond'] (x || cond feeds img_in)")
-    if C + cond.shape[-1] != flux.in_channels:
-        raise hip.VclozeHipError(f"x ({C}) || cond ({cond.shape[-1]}) does not match in_channels {flux.in_channels}")
-    txt, y, guidance = kw["txt"], kw["y"], kw.get("guidance")
-    if flux.params.guidance_embed and guidance is None:
-        raise ValueError("Didn't get guidance strength for guidance distilled model.")
-    T, S = txt.shape[1], len(t) - 1
-    t32 = t.to(torch.float32)
-    bf = lambda a: a.to(dev, torch.bfloat16).contiguous()  # noqa: E731
-    sdt = x.dtype
-    out = torch.empty(B, N, C, dtype=sdt, device=dev)
-    traj = torch.empty(S, B, N, C, dtype=sdt, device=dev) if return_trajectory else None
-    gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
-    from .model import MaskLayout, per_sample
-    guidance = per_sample(guidance, B)
-    lay = MaskLayout(kw.get("txt_mask"), kw.get("img_mask"), B, T, N)
-    st = eng.stream
-    st.wait_stream(torch.cuda.current_stream())
+    plan = flux.chunk_plan(B, N, kw, pairs, channels=(C, cond.shape[-1]))
+    out = torch.empty(B, N, C, dtype=x.dtype, device=plan.dev)
+    return plan, cond, out, torch.empty(S, B, N, C, dtype=x.dtype, device=plan.dev) if return_trajectory else None
+
+
+def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False):
+    """What the fused solves through the C handle share.  Per trajectory: the options, taken back on failure too.  Per chunk of samples
+    (true CFG: whole pairs (j, j + B/2), conditional samples first): vc_flux_prepare for `max_evals` evaluations, a copy of the state's
+    rows in kernel order for run(xs, cond rows, trajectory buffer [S, bs, N, C] or None, stream) to advance in place, and the way back."""
+    plan, cond, out, traj = _solve_begin(flux, x, kw, S, return_trajectory, pairs=cfg_scale is not None)
+    with _on_capture_stream(flux.plan().stream) as s:
+        try:
+            h.set_step_cache(step_cache)           # None: off, whatever an earlier trajectory on this handle ran with
+            h.set_cfg(cfg_scale)
+            if adaptive:
+                h.set_adaptive(True)
+            for sl in plan.chunks:
+                h.prepare(*plan.prepare_args(sl, max_evals), stream=s)
+                xs = plan.img_rows(x, sl, x.dtype, copy=True)       # stepped in ITS dtype, in place: never the caller's
+                tj = torch.empty(S, plan.size(sl), *x.shape[1:], dtype=x.dtype, device=plan.dev) if return_trajectory else None
+                run(xs, plan.img_rows(cond, sl, torch.bfloat16), tj, s)
+                if return_trajectory:
+                    traj[:, sl] = torch.stack([plan.img_back(tj[i], sl) for i in range(S)])
+                out[sl] = plan.img_back(xs, sl)
+        finally:
+            if adaptive:
+                h.set_adaptive(False)              # a later fixed-grid trajectory sizes its workspace as it always did
+            if cfg_scale is not None:
+                h.set_cfg(None)                    # a later trajectory driven on this handle directly is a plain one again
+    return out[None] if traj is None else torch.cat((x.to(out.device)[None], traj), dim=0)
+
+
+@torch.no_grad()
+def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None):
+    """vc_flux_sample_dopri5 per chunk of samples: ONE step size per chunk, so a sample's result depends on its chunk's other samples"""
     h = flux.handle()
     if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_dopri5 refuses it: its counter is a stage, not an evaluation)
         raise ValueError("monitor: the adaptive solve has no evaluation index to log under; set Flux.monitor = 0 or use a fixed-grid solver")
-    h.set_step_cache(None)
-    h.set_cfg(cfg_scale)
-    h.set_adaptive(True)
-    mb = flux.max_batch()
-    chunks = [slice(b0, min(b0 + mb, B)) for b0 in range(0, B, mb)] if cfg_scale is None else cfg_chunks(B, mb)
+    t32 = t.to(torch.float32)
     logs = []
-    try:
-        with torch.cuda.stream(st):
-            s = st.cuda_stream
-            for sl in chunks:
-                bs = len(range(B)[sl]) if isinstance(sl, slice) else len(sl)
-                h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                          lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), 7, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
-                xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()
-                tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
-                try:
-                    h.sample_dopri5(xs, bf(lay.img_rows(cond, sl)), t32, sdt == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
-                finally:
-                    logs.append(h.dopri5_log())
-                if return_trajectory:
-                    traj[:, sl] = torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)])
-                out[sl] = lay.img_rows_back(xs, sl)
-    finally:
-        h.set_adaptive(False)                      # a later fixed-grid trajectory sizes its workspace as it always did
-        if cfg_scale is not None:
-            h.set_cfg(None)
-        torch.cuda.current_stream().wait_stream(st)
-    if return_trajectory:
-        return torch.cat((x.to(dev)[None], traj), dim=0), logs
-    return out[None], logs
+
+    def run(xs, cond, tj, s):
+        try:
+            h.sample_dopri5(xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
+        finally:
+            logs.append(h.dopri5_log())
+
+    return _solve_on_handle(flux, h, x, kw, len(t) - 1, return_trajectory, 7, run, cfg_scale=cfg_scale, adaptive=True), logs
 
 
 def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
@@ -555,107 +565,59 @@ def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
 
 @torch.no_grad()
 def _sample_fused(flux, x, kw, t, return_trajectory, method="euler", step_cache=None, sampler=None, cfg_scale=None):
-    """cfg_scale: None = the drift is Flux.forward; a number = Flux.forward_with_cfg with it (C handle only).  Samples then advance
-    in chunks of whole pairs (j, j + B/2), conditional samples first, and go back in the caller's order."""
-    eng = flux.plan()
-    dev = eng.dev
-    B, N, C = x.shape
-    cond = kw.get("cond")
-    if cond is None:
-        raise hip.VclozeHipError("fused sampler expects model_kwargs['cond'] (x || cond feeds img_in)")
-    if C + cond.shape[-1] != flux.in_channels:
-        raise hip.VclozeHipError(f"x ({C}) || cond ({cond.shape[-1]}) does not match in_channels {flux.in_channels}")
-    txt, y, guidance = kw["txt"], kw["y"], kw.get("guidance")
-    if flux.params.guidance_embed and guidance is None:
-        raise ValueError("Didn't get guidance strength for guidance distilled model.")
-    T = txt.shape[1]
-    S = len(t) - 1
-    E = hip.solver_evals(method)                   # model evaluations per step: the workspace's tables hold S * E of them
-    t32 = t.to(torch.float32)
-    eval_t = model_times(t32, x)                   # Flux sees 1 - t (transport.py:384), t in the state's dtype
-    dts = (t32[1:] - t32[:-1]).contiguous()        # torchdiffeq fixed grid: dt = t1 - t0
-    bf = lambda a: a.to(dev, torch.bfloat16).contiguous()  # noqa: E731
-    sdt = x.dtype                                  # bf16, or f32 (handle path only): the state is stepped in ITS dtype
-    out = torch.empty(B, N, C, dtype=sdt, device=dev)
-    traj = torch.empty(S, B, N, C, dtype=sdt, device=dev) if return_trajectory else None
-    gbf16 = guidance is not None and guidance.dtype == torch.bfloat16
-    from .model import MaskLayout, per_sample
-    guidance = per_sample(guidance, B)
-    lay = MaskLayout(kw.get("txt_mask"), kw.get("img_mask"), B, T, N)
-    st = eng.stream
-    st.wait_stream(torch.cuda.current_stream())
-    # the C handle runs the whole trajectory of a chunk in ONE call (vc_flux_sample_ode); the un-merged LoRA mode uses the
-    # Python-ordered plan (bf16 states, Euler only: _fusable) unless ref_plan is "handle"
+    """The whole trajectory of a chunk in ONE call on the C handle (vc_flux_sample_ode); without the handle the Python-ordered plan
+    (`_sample_twin`).  cfg_scale: None = the drift is Flux.forward; a number = Flux.forward_with_cfg with it (C handle only)."""
     h = flux.handle()
-    if h is not None:
-        h.set_step_cache(step_cache)               # None: off, whatever an earlier trajectory on this handle ran with
-        h.set_cfg(cfg_scale)
-    elif cfg_scale is not None:
-        raise hip.VclozeHipError("true CFG in the fused loop needs the C handle")
-    level = flux.monitor_level(h)                  # ValueError with the Python-ordered plan: never silently ignored
-    mon_logs, mon_bad = [], None
-    mb = flux.max_batch()
-    if cfg_scale is None:
-        chunks = [slice(b0, min(b0 + mb, B)) for b0 in range(0, B, mb)]
-    else:
-        chunks = cfg_chunks(B, mb)
-    stats = []
-    with torch.cuda.stream(st):
-        s = st.cuda_stream
-        for sl in chunks:                            # a chunk of samples advances together, one graph replay per step
-            bs = len(range(B)[sl]) if isinstance(sl, slice) else len(sl)
-            if h is not None:
-                h.prepare(bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                          lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), S * E, lay.kv_len(sl), lay.kv_gap(sl), stream=s)
-                xs = lay.img_rows(x, sl).to(dev, sdt, copy=True).contiguous()   # updated in place: never the caller's
-                tj = torch.empty(S, bs, N, C, dtype=sdt, device=dev) if return_trajectory else None
-                if level:
-                    h.set_monitor(level, S * E)
-                try:
-                    h.sample_ode(method, xs, bf(lay.img_rows(cond, sl)), t32, x.dtype == torch.bfloat16, s, trajectory=tj)
-                    if level:
-                        bad = h.monitor_report(s)
-                        if bad is not None and mon_bad is None:
-                            mon_bad = (len(mon_logs),) + bad
-                        mon_logs.append(h.monitor_log(s))
-                finally:
-                    if level:
-                        h.set_monitor(0)           # the log was sized for this chunk
-                if step_cache is not None:
-                    stats.append(h.step_cache_stats(S))
-                if return_trajectory:
-                    traj[:, sl] = torch.stack([lay.img_rows_back(tj[i], sl) for i in range(S)])
-                out[sl] = lay.img_rows_back(xs, sl)
-                continue
-            ws = eng.workspace(T, N, S, bs)
-            eng.prepare_sample(ws, bf(lay.txt_rows(txt, sl)), bf(y[sl]), None if guidance is None else guidance[sl], gbf16,
-                               lay.img_rows(kw["img_ids"], sl), lay.txt_rows(kw["txt_ids"], sl), eval_t, lay.kv_len(sl), s=s,
-                               kv_gap=lay.kv_gap(sl))
-            ws.DTS.copy_(dts, non_blocking=True)
-            ws.STEP.zero_()
-            ws.XS.copy_(bf(lay.img_rows(x, sl)).reshape(bs * N, C))     # the state stays in kernel row order for all steps
-            ws.COND.copy_(bf(lay.img_rows(cond, sl)).reshape(bs * N, -1))
-            graph = eng.step_graph(ws, s)
-            states = []
-            for _ in range(S):
-                graph.launch(s)          # one Flux evaluation + Euler update + step counter increment
-                if return_trajectory:
-                    states.append(lay.img_rows_back(ws.XS.reshape(bs, N, C), sl).clone())
-            if return_trajectory:
-                traj[:, sl] = torch.stack(states)                 # [S, bs, N, C]
-            out[sl].copy_(lay.img_rows_back(ws.XS.reshape(bs, N, C), sl))
+    if h is None:
         if cfg_scale is not None:
-            h.set_cfg(None)                        # a later trajectory driven on this handle directly is a plain one again
-    torch.cuda.current_stream().wait_stream(st)
-    if level:
-        flux.last_monitor_log, flux.last_monitor_report = mon_logs, mon_bad
-        if mon_bad is not None and flux.monitor_strict:
-            raise FloatingPointError("the numerics monitor found a NaN / inf: chunk %d, evaluation %d, site '%s', sample %d of the chunk "
-                                     "(Flux.last_monitor_log holds the statistics)" % mon_bad)
+            raise hip.VclozeHipError("true CFG in the fused loop needs the C handle")
+        flux.monitor_level(h)                      # ValueError with the Python-ordered plan: never silently ignored
+        return _sample_twin(flux, x, kw, t, return_trajectory)
+    S = len(t) - 1
+    n = S * hip.solver_evals(method)               # model evaluations: the workspace's tables hold all of them
+    t32 = t.to(torch.float32)
+    stats = []
+    with flux.monitored(h) as monitored:
+        def run(xs, cond, tj, s):
+            with monitored(n, s):
+                h.sample_ode(method, xs, cond, t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+            if step_cache is not None:
+                stats.append(h.step_cache_stats(S))
+
+        out = _solve_on_handle(flux, h, x, kw, S, return_trajectory, n, run, step_cache, cfg_scale)
     if step_cache is not None:
         flux.last_step_cache_stats = stats         # one dict per chunk of <= MAX_BATCH samples, in order
         if sampler is not None:
             sampler.last_step_cache_stats = stats
-    if return_trajectory:
-        return torch.cat((x.to(dev)[None], traj), dim=0)
-    return out[None]
+    return out
+
+
+def _sample_twin(flux, x, kw, t, return_trajectory):
+    """`_sample_fused` with the Python-ordered plan (engine.FluxEngine; bf16 states, Euler only: `_fusable`): a graph replay per step"""
+    eng = flux.engine()
+    S = len(t) - 1
+    t32 = t.to(torch.float32)
+    eval_t = model_times(t32, x)                   # Flux sees 1 - t (transport.py:384), t in the state's dtype
+    dts = (t32[1:] - t32[:-1]).contiguous()        # torchdiffeq fixed grid: dt = t1 - t0
+    plan, cond, out, traj = _solve_begin(flux, x, kw, S, return_trajectory)
+    N, C = x.shape[1:]
+    with _on_capture_stream(eng.stream) as s:
+        for sl in plan.chunks:                     # a chunk of samples advances together
+            bs = plan.size(sl)
+            ws = eng.workspace(plan.T, N, S, bs)
+            args, kwargs = plan.twin_prepare_args(sl, eval_t)
+            eng.prepare_sample(ws, *args, s=s, **kwargs)
+            ws.DTS.copy_(dts, non_blocking=True)
+            ws.STEP.zero_()
+            ws.XS.copy_(plan.img_rows(x, sl, torch.bfloat16).reshape(bs * N, C))     # the state stays in kernel row order for all steps
+            ws.COND.copy_(plan.img_rows(cond, sl, torch.bfloat16).reshape(bs * N, -1))
+            graph = eng.step_graph(ws, s)
+            states = []
+            for _ in range(S):
+                graph.launch(s)                    # one Flux evaluation + Euler update + step counter increment
+                if return_trajectory:
+                    states.append(plan.img_back(ws.XS.reshape(bs, N, C), sl).clone())
+            if return_trajectory:
+                traj[:, sl] = torch.stack(states)  # [S, bs, N, C]
+            out[sl].copy_(plan.img_back(ws.XS.reshape(bs, N, C), sl))
+    return out[None] if traj is None else torch.cat((x.to(out.device)[None], traj), dim=0)
