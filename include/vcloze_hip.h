@@ -324,6 +324,61 @@ int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const 
                           float* out, float* scratch, int64_t n, void* stream);
 int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
                      int64_t n, void* stream);
+/* ---- the stochastic (SDE) sampler: what the reference's Sampler.sample_sde runs between model evaluations (transport.py:300-359,
+ * the step rules of the class sde, integrators.py:27-49, and the score / diffusion forms of ICPlan in transport/path.py).  Added
+ * WITHOUT a change of VC_ABI_VERSION: detect these entry points (vc_sde_plan, vc_sde_stage, vc_flux_sample_sde) by SYMBOL - look up
+ * vc_sde_stage.  VC_SOLVER_* has no code for it and vc_solver_evals / vc_flux_sample_ode keep refusing anything but the
+ * fixed-grid methods.
+ * The reference adapted only sample_ode to Flux's reversed time (transport.py:384); its sample_sde cannot drive Flux.forward as
+ * written.  What is taken from it is the mathematics, applied to the velocity v(x, t) = -model(x || cond, timesteps = 1 - t).
+ * Time runs as in sample_ode (t = 0 noise, t = 1 data; Linear path: alpha = t, sigma = 1 - t).  With w(t) the diffusion coefficient:
+ *   score       s = (t v - x) / (1 - t)
+ *   sde drift   D(x, t) = v + w s = A(t) v - Bc(t) x,   A = 1 + w t / (1 - t),  Bc = w / (1 - t)
+ *   w(t)        "constant" norm | "SBDM" norm (1 - t) / t | "sigma" norm (1 - t) | "linear" norm (1 - t)
+ *               "decreasing" 0.25 (norm cos(pi t) + 1)^2 | "inccreasing-decreasing" norm sin^2(pi t)   (the reference's spelling;
+ *               "increasing-decreasing" is accepted as an alias)
+ *   "Euler"     Euler-Maruyama: x' = x + dt D(x, t) + g z,  g = sqrt(2 w(t) dt),  z ~ N(0, 1)
+ *   "Heun"      xh = x + g z;  K1 = D(xh, t);  xp = xh + dt K1;  K2 = D(xp, t + dt);  x' = xh + (0.5 dt) (K1 + K2)
+ *   last step   at t1 = the last grid point: "Mean" x + lss D(x, t1) | "Euler" x + lss v | "Tweedie" x + (1 - t1) v | none: x
+ * Every update is y + h (A v - Bc y) + g z with scalar coefficients.  The HOST RULE (plan) computes them in double from the F32
+ * grid - t = t_grid[i], dt = f32(t_grid[i + 1] - t_grid[i]), t + dt the double sum - and rounds each ONCE to F32.
+ * plan: host only, needs no device.  method "Euler" | "Heun"; form as above; last_step "Mean" | "Euler" | "Tweedie", or NULL / "" for
+ *        none.  Evaluations: Euler (n_points - 1) + (last step ? 1 : 0), Heun 2 (n_points - 1) + (last step ? 1 : 0); draws:
+ *        n_points - 1.  rows receives *n_evals rows of VC_SDE_ROW F32 (mode, h, A, Bc, g), one per evaluation, and for Heun ONE more
+ *        row behind them, the injection of draw 0 in front of the first evaluation; times receives the model's time 1 - f32(t) of
+ *        every evaluation.  rows / times may be NULL (the counts alone); capacity: the rows `rows` holds, the values `times` holds.
+ *        VC_ERR_ARG with a message: an unknown method / form / last step, n_points < 2, a grid that does not increase strictly, a
+ *        capacity that is too small, and ANY NON-FINITE COEFFICIENT - the message names the time and the form.  That covers "SBDM"
+ *        at t = 0 and any row at t = 1, hence "Heun" without a last step on a grid that ends at 1: a refusal, never a NaN latent.
+ *        "constant" is implemented (in the reference it raises a TypeError, a bug).
+ * stage: one elementwise pass over n elements.  Row e = eval (>= 0), or *eval_ptr - the device-side evaluation counter, so one
+ *        captured launch serves every evaluation; a row outside [0, n_rows), an unknown mode, or a mode whose buffers are NULL
+ *        writes nothing.  y, xhat, k1: F32 [n]; v: the model's bf16 output (the velocity is -v); y_in: bf16 [n], the NEXT evaluation's
+ *        input.  With D = A (-v) - Bc (.):
+ *          VC_SDE_EM      y <- (y + h D(y)) + g z_d,  d = e;                       y_in <- bf16(y)
+ *          VC_SDE_HEUN1   k1 <- D(xhat);  y <- xhat + h k1  (= xp);                y_in <- bf16(y)
+ *          VC_SDE_HEUN2   y <- xhat + h (k1 + D(y))  (= x');  xhat <- y + g z_d,  d = (e + 1) / 2  (the NEXT step's noise);
+ *                         y_in <- bf16(xhat)
+ *          VC_SDE_LAST    y <- y + h D(y);                                         y_in <- bf16(y)
+ *          VC_SDE_INJECT  xhat <- y + g z_0;  (v unused, may be NULL)              y_in <- bf16(xhat)
+ *        g == 0 adds NO noise term (not even a signed zero).  F32 arithmetic, left to right, one operation after the other, no fused
+ *        multiply-add: a torch F32 expression of the same shape gives the same bits (transport.sde_integrate is that expression).
+ *        NOISE: z_d[i] is the VC_RNG_F32 value of the stream of `seed` at position offset + d * n + i, bit for bit what a
+ *        vc_randn call gives there - generated in the kernel, no noise tensor exists.  seed = rng[0], offset = rng[1]: TWO UINT64
+ *        IN DEVICE MEMORY, read when the kernel runs, so a captured launch serves every seed and every replay draws fresh,
+ *        reproducible noise.  The caller keeps offset + (draws) * n inside the 64-bit stream.  Buffers must not overlap.  16-byte
+ *        accesses where every base is 16-byte aligned (8 elements per work item, the n % 8 tail element-wise); anything else
+ *        runs element-wise with the same results.  Grid capped, grid-stride loop. */
+#define VC_SDE_EM 0
+#define VC_SDE_HEUN1 1
+#define VC_SDE_HEUN2 2
+#define VC_SDE_LAST 3
+#define VC_SDE_INJECT 4
+#define VC_SDE_ROW 5   /* F32 values per table row: mode, h, A, Bc, g */
+int vc_sde_plan(const char* method, const char* form, double norm, const char* last_step, double last_step_size, const float* t_grid,
+                int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws);
+int vc_sde_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
+                 const uint64_t* rng, const int32_t* eval_ptr, int64_t n, void* stream);
 /* ---- the three elementwise passes of the first-block step cache (vc_flux_set_step_cache below; the rule is this library's own,
  * DESIGN.md section 4).  Added without a change of VC_ABI_VERSION, like the solver entry points: detect by SYMBOL (look up
  * vc_flux_set_step_cache).  bf16 storage, f32 math, 16-byte accesses: n, every sample stride a multiple of 8, bases 16-byte aligned
@@ -427,7 +482,8 @@ int vc_unpack_latent(const void* tokens, int64_t ld, int32_t col0, void* latent,
 /* out[i] = element offset + i of the stream of `seed`, i < n.  Any n >= 1, any offset, any base aligned to the element size (2 / 4
  * / 4 bytes); stores are 16 bytes wide wherever the base and the phase offset & 3 allow, the element-wise head and tail give the
  * same values.  seed and offset are by-value kernel arguments: the call is legal under stream capture, and A REPLAYED GRAPH
- * REPEATS ITS NOISE - a caller who wants fresh noise per replay draws outside the graph.  Arguments are checked before the device
+ * REPEATS ITS NOISE - a caller who wants fresh noise per replay draws outside the graph (vc_sde_stage, which reads seed and offset
+ * from device memory, is the exception built for the sampling loop).  Arguments are checked before the device
  * is touched (VC_ERR_ARG: null pointer, n <= 0, unknown dtype, offset + n wrapping, misaligned base). */
 int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream);
 /* The sampler's start state x(t0) in one launch, no intermediate tensor: latent element (c, y, x) of a [C, h, w] draw takes stream
@@ -749,6 +805,32 @@ int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* 
                           float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream);
 int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                        int32_t* evaluations);
+/* ---- the stochastic sampler around the same captured evaluation (vc_sde_plan / vc_sde_stage above have the mathematics).  OPT-IN:
+ * set vc_flux_set_option(handle, "sde", 1) BEFORE vc_flux_workspace_bytes / vc_flux_prepare - it adds the F32 state, xhat, K1, the
+ * coefficient table and the seed / offset words to the workspace - and prepare with max_steps >= the plan's evaluations.  With the
+ * option off nothing changes: the same workspace bytes, graphs, nodes and bits.  Detect by SYMBOL (look up vc_sde_stage).
+ * method, form, norm, last_step, last_step_size, t_grid, n_points: as for vc_sde_plan, which is run first - its refusals are this
+ * call's, before anything touches the device.  x [B, N, out_channels]: in = x(t_grid[0]), out = the sample; bf16 (state_is_bf16) or
+ * F32.  The state is stepped in F32 whatever the caller's dtype: a bf16 state is widened on entry and rounded ONCE per output.
+ *   step    the captured step is the existing evaluation with vc_sde_stage on the device-side counter as its last node, kept per
+ *           (geometry, method); for "Euler" it has exactly the nodes of the VC_SOLVER_EULER step (vc_flux_step_nodes).  The
+ *           time embeddings, modulation rows and coefficient rows of all evaluations are built up front.
+ *   noise   draw d (= solver step) of the call takes stream positions offset + d * n + i of the stream of `seed`, n = B * N *
+ *           out_channels, i the flat index in THIS call's [B, N, out_channels] state; n_points - 1 draws.  seed and offset go to the
+ *           device words the stage reads: one captured step serves every seed and every replay.  offset + (n_points - 1) * n
+ *           leaving the 64-bit stream is VC_ERR_ARG.
+ *   trajectory  NULL, or [n_points][B][N][out_channels] in the state's dtype: row i < n_points - 1 receives x' after loop step i,
+ *           the last row the last step's result (the sample; without a last step it repeats row n_points - 2) - n_points rows, as
+ *           the reference's list has num_steps entries.
+ * True CFG (vc_flux_set_cfg: the combine comes before the update; both halves are stepped, each with its own noise positions),
+ * taps and the un-merged LoRA mode work unchanged.  Refused: the option off (VC_ERR_STATE); the step cache on, the monitor on
+ * (its log is indexed by the evaluations of a fixed-grid trajectory; turn it off with level 0), more evaluations than max_steps,
+ * an odd B with true CFG (all VC_ERR_ARG) - each found before the device is touched; the handle stays usable.
+ * Image quality under any diffusion form is UNMEASURED (only random-init weights exist here), and no throughput claim is made:
+ * the update costs one elementwise pass like Euler's, and this was not timed on a GPU. */
+int vc_flux_sample_sde(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
+                       double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
+                       void* trajectory, void* stream);
 
 /* ---- first-block step cache of the Euler loop: OPT-IN, off by default.  IT CHANGES RESULTS: a reused evaluation is an
  * approximation, not the model.  Its effect on image quality is unmeasured (only random-init weights were available) and no default

@@ -120,6 +120,14 @@ int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const floa
                      int64_t n, void* stream) {
   return vc_dopri5_interp_launch(y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF);
 }
+int vc_sde_plan(const char* method, const char* form, double norm, const char* last_step, double last_step_size, const float* t_grid,
+                int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws) {
+  return vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, rows, times, capacity, n_evals, n_draws, ERRBUF);
+}
+int vc_sde_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
+                 const uint64_t* rng, const int32_t* eval_ptr, int64_t n, void* stream) {
+  return vc_sde_stage_launch(eval, table, n_rows, y, v, y_in, xhat, k1, rng, eval_ptr, n, S(stream), ERRBUF);
+}
 int vc_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, void* stream) {
   return vc_cfg_combine_launch(cond, uncond, out, n, cfg_scale, S(stream), ERRBUF);
 }
@@ -300,6 +308,12 @@ int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* 
 int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                        int32_t* evaluations) {
   return vc_flux_dopri5_log_impl(handle, t, dt, ratio, accepted, capacity, attempts, evaluations, ERRBUF);
+}
+int vc_flux_sample_sde(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
+                       double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
+                       void* trajectory, void* stream) {
+  return vc_flux_sample_sde_impl(handle, method, x, cond, t_grid, n_points, form, norm, last_step, last_step_size, seed, offset, state_is_bf16,
+                                 trajectory, S(stream), ERRBUF);
 }
 int vc_flux_sample_euler(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                          void* trajectory, void* stream) {

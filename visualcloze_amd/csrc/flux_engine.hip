@@ -20,6 +20,9 @@
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
 //   AD_K [7][B*N*out] / AD_Y0 / AD_Y1 (f32)  only with option adaptive 1, behind the step cache's: k1..k7, the state and the step's
 //                           end state of the adaptive solve (vc_flux_sample_dopri5, dopri5.hip), its dt, norms and reduction scratch
+//   SD_Y / SD_XHAT / SD_K1 (f32) / SD_TAB / SD_RNG  only with option sde 1, behind the adaptive solve's: the state, x-hat and K1 of the
+//                           stochastic sampler (vc_flux_sample_sde, rng.hip), its coefficient table ([S + 1][VC_SDE_ROW] f32) and the
+//                           seed / offset words its update reads
 //   LY / LY2 / LH / LSCALE  only in the un-merged LoRA mode (option lora_mode 1), behind everything else: base_out, base_out + lora
 //                           and lora_A(x) of the Linear being run, and the lora scale as a bf16 vector (the gate operand of the
 //                           gated-residual epilogue that adds the lora branch; refilled by vc_flux_set_lora_scale)
@@ -64,6 +67,8 @@ struct Buffers {   // the workspace carve-up
   float *SC_PART = nullptr, *SC_METRIC = nullptr;
   bf16_t* AD_K = nullptr;                                          // adaptive solve (carved only while option adaptive is on)
   float *AD_Y0 = nullptr, *AD_Y1 = nullptr, *AD_DT = nullptr, *AD_OUT = nullptr, *AD_PART = nullptr;
+  float *SD_Y = nullptr, *SD_XHAT = nullptr, *SD_K1 = nullptr, *SD_TAB = nullptr;   // stochastic sampler (carved only while option sde is on)
+  uint64_t* SD_RNG = nullptr;
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
   void* SK_WS = nullptr;               // f32 partial tiles of split-K GEMM remainders (VcGemmArgs.splitk_ws)
@@ -75,6 +80,7 @@ struct Options {
   int attn_variant = -1, tile_cfg = 0, fuse_qnorm = 2, fuse_vt = 1, qkv_heads = 0, fuse_knorm = 0, logit_bound_milli = 0, mlp_first = 0, splitk = 1;
   int lora_mode = 0;
   int adaptive = 0;
+  int sde = 0;
 };
 enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
 #define OPT(name, clamp) {#name, &Options::name, clamp}
@@ -85,6 +91,7 @@ constexpr struct { const char* name; int Options::*member; Clamp clamp; } OPTION
     OPT(mlp_first, BOOL),        OPT(splitk, BOOL),              // split-K remainders (VcGemmArgs.splitk_ws) where the launcher's model takes them
     OPT(lora_mode, BOOL),                                        // 1: every Linear runs un-merged (lora_linear below)
     OPT(adaptive, BOOL),                                         // 1: the workspace holds the adaptive solve's buffers (vc_flux_sample_dopri5)
+    OPT(sde, BOOL),                                              // 1: ... the stochastic sampler's (vc_flux_sample_sde)
 };
 #undef OPT
 inline bool operator==(const Options& a, const Options& b) {
@@ -229,6 +236,11 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
     const int64_t n = (int64_t)B * N * out_ch;
     f.AD_K = c.take<bf16_t>(7 * n); f.AD_Y0 = c.take<float>(n); f.AD_Y1 = c.take<float>(n);
     f.AD_DT = c.take<float>(1); f.AD_OUT = c.take<float>(4); f.AD_PART = c.take<float>(VC_DOPRI5_MAX_BLOCKS);
+  }
+  if (g.opt.sde) {         // likewise
+    const int64_t n = (int64_t)B * N * out_ch;
+    f.SD_Y = c.take<float>(n); f.SD_XHAT = c.take<float>(n); f.SD_K1 = c.take<float>(n);
+    f.SD_TAB = c.take<float>(((int64_t)S + 1) * VC_SDE_ROW); f.SD_RNG = c.take<uint64_t>(2);
   }
   if (g.opt.lora_mode) {   // likewise: the widest Linear over the block rows, the modulation Linears over the (evaluation, sample) rows
     const int64_t wide = std::max<int64_t>({3 * D, mlp, D, out_ch}), rows = std::max<int64_t>(B * L, (int64_t)S * B);
@@ -701,6 +713,7 @@ int tap_double(Flux& f, int i, const int32_t* step_ptr, hipStream_t s, Err e) {
 // where the sample in flight keeps its ODE state (in the caller's dtype), and the bf16 rows the next evaluation reads: the state
 // itself for a bf16 Euler step, XS as the bf16 shadow of an f32 Euler state, else YIN - the stage input of a midpoint / rk4 step
 constexpr int SOLVER_DOPRI5 = 100;     // Flux::method of the adaptive solve: no VC_SOLVER_* code (vc_solver_evals keeps refusing it)
+constexpr int SOLVER_SDE_EULER = 101, SOLVER_SDE_HEUN = 102;     // ... of the stochastic sampler: likewise (one captured step per method)
 void* ode_state(Flux& f) { return f.state_f32 ? (void*)f.XS32 : (void*)f.XS; }
 int64_t ode_state_bytes(const Flux& f) { return (int64_t)f.B * f.N * f.cfg.out_channels * (f.state_f32 ? 4 : 2); }
 bf16_t* next_input(Flux& f) { return f.method == VC_SOLVER_EULER ? f.XS : f.YIN; }
@@ -710,6 +723,9 @@ int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, E
   if (f.method == SOLVER_DOPRI5)      // the stage of the adaptive solve is the device-side counter itself
     return vc_dopri5_stage_launch(-1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
                                   e.buf, e.len);
+  if (f.method == SOLVER_SDE_EULER || f.method == SOLVER_SDE_HEUN)      // the table row of the update is the device-side counter itself
+    return vc_sde_stage_launch(-1, f.SD_TAB, f.S + 1, f.SD_Y, v, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, step_ptr,
+                               (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
   void* y = ode_state(f);
   bf16_t* y_in = next_input(f);
   return vc_ode_update_launch("ode_update", f.method, -1, y, !f.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
@@ -1296,7 +1312,7 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
       case ZERO_OR_H: if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H); break;
       case ANY: break;
     }
-    if ((o.member == &Options::lora_mode || o.member == &Options::adaptive) && value != f.opt.*o.member) {
+    if ((o.member == &Options::lora_mode || o.member == &Options::adaptive || o.member == &Options::sde) && value != f.opt.*o.member) {
       if (f.in_flight)
         FAIL(VC_ERR_STATE, "flux_set_option: %s cannot change between vc_flux_sample_begin and vc_flux_sample_end", o.name);
       f.prepared = false;    // the workspace carve-up differs: vc_flux_workspace_bytes + vc_flux_prepare again
@@ -1739,6 +1755,83 @@ int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, i
   if (attempts) *attempts = (int32_t)f.ad_log.size();
   if (evaluations) *evaluations = f.ad_evals;
   return VC_OK;
+}
+
+// ---------------------------------------------------------------- the stochastic sampler (vcloze_hip.h: vc_flux_sample_sde)
+int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
+                            double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
+                            void* trajectory, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  // ---- every check before the device is touched
+  if (!f.prepared) FAIL(VC_ERR_STATE, "flux_sample_sde: call vc_flux_prepare first");
+  TRY(fresh_scale(f, "flux_sample_sde", e));
+  if (!x || !cond || !t_grid) FAIL(VC_ERR_ARG, "flux_sample_sde: null argument");
+  if (!f.opt.sde || !f.SD_Y)
+    FAIL(VC_ERR_STATE, "flux_sample_sde: set vc_flux_set_option(handle, \"sde\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
+                       "(the workspace holds no buffers of the stochastic sampler)");
+  if (f.mon_level)
+    FAIL(VC_ERR_ARG, "flux_sample_sde: the monitor is on (level %d): its log is indexed by the evaluations of a fixed-grid trajectory; turn it "
+                     "off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
+  if (f.sc_on())
+    FAIL(VC_ERR_ARG, "flux_sample_sde: the step cache works with VC_SOLVER_EULER only: turn it off with vc_flux_set_step_cache(handle, 0, 0)");
+  int32_t n_evals = 0, n_draws = 0;
+  TRY(vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, nullptr, nullptr, 0, &n_evals, &n_draws, err, errlen));
+  if (n_evals > f.S)
+    FAIL(VC_ERR_ARG, "flux_sample_sde: %d evaluations (%d points, method %s), the prepared workspace holds 1..%d evaluations", n_evals, n_points,
+         method, f.S);
+  if (f.cfg_on) {
+    if (f.B % 2) FAIL(VC_ERR_ARG, "flux_sample_sde: true CFG pairs the first half of the batch with the second: B = %d is odd", f.B);
+    if (!(f.cfg_scale - f.cfg_scale == 0.0f)) FAIL(VC_ERR_ARG, "flux_sample_sde: the cfg_scale set by vc_flux_set_cfg is not finite");
+  }
+  const int B = f.B;
+  const int64_t n = (int64_t)B * f.N * f.cfg.out_channels;
+  if ((unsigned __int128)offset + (unsigned __int128)n_draws * (unsigned __int128)n > ((unsigned __int128)1 << 64))
+    FAIL(VC_ERR_ARG, "flux_sample_sde: offset + draws * n leaves the 64-bit stream position (offset=%llu, %d draws of %lld elements)",
+         (unsigned long long)offset, n_draws, (long long)n);
+  const bool heun = !strcmp(method, "Heun");
+  const int n_rows = n_evals + (heun ? 1 : 0), E = heun ? 2 : 1, out_bf16 = state_is_bf16 != 0;
+  const int64_t out_bytes = n * (out_bf16 ? 2 : 4);
+  // ---- the tables of the whole trajectory: model times, coefficient rows, the stream's seed and offset
+  TRY(stage_begin(f, ((size_t)n_evals * B + (size_t)n_rows * VC_SDE_ROW + n_evals) * sizeof(float) + 2 * sizeof(uint64_t) + 4 * 256, e));
+  float* ts = stage_take<float>(f, (size_t)n_evals * B);
+  float* rows = stage_take<float>(f, (size_t)n_rows * VC_SDE_ROW);
+  float* times = stage_take<float>(f, n_evals);
+  uint64_t* words = stage_take<uint64_t>(f, 2);
+  TRY(vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, rows, times, n_rows, nullptr, nullptr, err, errlen));
+  for (int j = 0; j < n_evals; ++j)
+    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = times[j];
+  words[0] = seed; words[1] = offset;
+  f.in_flight = false;
+  f.steps_total = f.steps_done = 0;             // an earlier trajectory's tables are overwritten: steps / end refuse from here on
+  TRY(stage_send(f, f.TS, ts, (size_t)n_evals * B * sizeof(float), s, e));
+  TRY(stage_send(f, f.SD_TAB, rows, (size_t)n_rows * VC_SDE_ROW * sizeof(float), s, e));
+  TRY(stage_send(f, f.SD_RNG, words, 2 * sizeof(uint64_t), s, e));
+  TRY(stage_end(f, s, e));
+  TRY(time_precompute(f, n_evals, 0, s, e));
+  f.state_f32 = true;
+  f.method = heun ? SOLVER_SDE_HEUN : SOLVER_SDE_EULER; f.evals = 1;
+  f.sc_active = false;
+  f.cfg_active = f.cfg_on; f.cfg_s = f.cfg_on ? f.cfg_scale : 1.0f;
+  auto run = [&]() -> int {
+    TRY(vc_dopri5_load_launch(x, state_is_bf16, f.SD_Y, f.YIN, n, s, e.buf, e.len));      // the F32 state and its bf16 shadow
+    TRY(d2d(f.COND, cond, (int64_t)B * f.N * (f.cfg.in_channels - f.cfg.out_channels) * 2, s, e));
+    HIP(hipMemsetAsync(f.STEP, 0, sizeof(int32_t), s), "hipMemsetAsync");
+    if (s) TRY(step_graph(f, s, e));
+    // Heun: draw 0 goes in ahead of the first evaluation (the row behind the evaluations' rows)
+    if (heun) TRY(vc_sde_stage_launch(n_evals, f.SD_TAB, f.S + 1, f.SD_Y, nullptr, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, nullptr, n, s, e.buf, e.len));
+    for (int j = 0; j < n_evals; ++j) {
+      if (s) HIP(hipGraphLaunch(f.step.g[0], s), "hipGraphLaunch");
+      else TRY(evaluate(f, f.STEP, true, nullptr, nullptr, true, s, e));
+      // x' after every loop step; the last step's result (or, without one, x' again) as the final row
+      const bool step_done = j < (n_points - 1) * E && (j + 1) % E == 0;
+      if (trajectory && step_done) TRY(vc_sde_store_launch(f.SD_Y, (char*)trajectory + (int64_t)(j / E) * out_bytes, out_bf16, n, s, e.buf, e.len));
+    }
+    if (trajectory) TRY(vc_sde_store_launch(f.SD_Y, (char*)trajectory + (int64_t)(n_points - 1) * out_bytes, out_bf16, n, s, e.buf, e.len));
+    return vc_sde_store_launch(f.SD_Y, x, out_bf16, n, s, e.buf, e.len);
+  };
+  const int rc = run();
+  f.method = VC_SOLVER_EULER;
+  return rc;
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {

@@ -6,6 +6,8 @@
 // (about 100 integer and 20 float operations per block of 4 outputs): the draws of a grid are ~0.2 M values, nothing here is
 // tuned beyond 16-byte stores and a capped grid.  seed / offset are kernel arguments by value: legal under stream capture, and
 // a replayed graph repeats its noise.
+//   sde_stage      the stochastic sampler's update: the same normals drawn in place, seed / offset read from DEVICE memory and the draw
+//                  index taken from the device-side evaluation counter - a replayed graph draws fresh, reproducible noise
 //
 // Precision: ln, sqrt and sin/cos are the PRECISE device functions (logf, sqrtf, sincospif on the exact argument 2*u2, a few f32
 // ulps each), not the bare v_log_f32 / v_sin_f32 approximations, whose error near u1 = 1 (ln u1 -> 0) and absolute error of the
@@ -124,6 +126,133 @@ __global__ __launch_bounds__(256) void randn_tokens_kernel(bf16_t* __restrict__ 
 
 int grid_for(long total) { return (int)((total + 255) / 256 < RNG_MAX_BLOCKS ? (total + 255) / 256 : RNG_MAX_BLOCKS); }
 
+// ---- the stochastic sampler's update (vcloze_hip.h: vc_sde_stage): one row (mode, h, A, Bc, g) of the table per evaluation, the
+// noise drawn in place from the stream above.  Here - and not beside the other solver updates - because the normals must be the
+// VC_RNG_F32 values bit for bit: the same device functions, compiled once.
+// the 8 normals at stream positions p .. p + 7, p & 3 == J: two whole blocks, or the tails and heads of three
+template <int J>
+VC_DEV void normals8(uint64_t p, uint32_t k0, uint32_t k1, float (&z)[8]) {
+  uint32_t a[4], b[4], c[4] = {0, 0, 0, 0};
+  block_words<VC_RNG_F32>(p >> 2, k0, k1, a);
+  block_words<VC_RNG_F32>((p >> 2) + 1, k0, k1, b);
+  if (J != 0) block_words<VC_RNG_F32>((p >> 2) + 2, k0, k1, c);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int q = J + e;
+    z[e] = __builtin_bit_cast(float, q < 4 ? a[q & 3] : q < 8 ? b[q & 3] : c[q & 3]);
+  }
+}
+VC_DEV float normal_at(uint64_t p, uint32_t k0, uint32_t k1) {
+  uint32_t v[4];
+  block_words<VC_RNG_F32>(p >> 2, k0, k1, v);
+  return __builtin_bit_cast(float, pick(v, (uint32_t)p & 3u));
+}
+
+struct SdeRow { int mode; float h, A, Bc, g; };
+struct SdeIo { float y, xhat, k1, y_in; };     // in: what the mode reads (else 0); out: what it stores
+// one element of one row, f32, one operation after the other: the torch expression of transport.sde_integrate gives the same bits.
+// vel = -v, the velocity; z is read only where g != 0 (g == 0: no noise is added, not even a signed zero)
+VC_DEV SdeIo sde_element(const SdeRow& r, const SdeIo& in, float vel, float z) {
+#pragma clang fp contract(off)
+  SdeIo o = in;
+  if (r.mode == VC_SDE_EM || r.mode == VC_SDE_LAST) {
+    float yn = in.y + r.h * (r.A * vel - r.Bc * in.y);
+    if (r.mode == VC_SDE_EM && r.g != 0.0f) yn = yn + r.g * z;
+    o.y = yn; o.y_in = yn;
+  } else if (r.mode == VC_SDE_HEUN1) {
+    const float K1 = r.A * vel - r.Bc * in.xhat;
+    const float xp = in.xhat + r.h * K1;
+    o.k1 = K1; o.y = xp; o.y_in = xp;
+  } else if (r.mode == VC_SDE_HEUN2) {
+    const float K2 = r.A * vel - r.Bc * in.y;
+    const float xn = in.xhat + r.h * (in.k1 + K2);
+    const float xh = r.g != 0.0f ? xn + r.g * z : xn;
+    o.y = xn; o.xhat = xh; o.y_in = xh;
+  } else {                                          // VC_SDE_INJECT
+    const float xh = r.g != 0.0f ? in.y + r.g * z : in.y;
+    o.xhat = xh; o.y_in = xh;
+  }
+  return o;
+}
+
+// work items: `nvec` chunks of 8 elements (16-byte accesses: the host found every base 16-byte aligned), then the n - 8 nvec single
+// elements of the tail.  Everything the row decides (what is read, what is stored, whether noise is drawn) is uniform over the grid.
+__global__ __launch_bounds__(256) void sde_stage_kernel(int eval_arg, const float* __restrict__ table, int n_rows, float* __restrict__ y,
+                                                        const bf16_t* __restrict__ v, bf16_t* __restrict__ y_in, float* __restrict__ xhat,
+                                                        float* __restrict__ k1, const uint64_t* __restrict__ rng,
+                                                        const int* __restrict__ eval_ptr, long n, long nvec) {
+  const int ev = eval_arg >= 0 ? eval_arg : *eval_ptr;
+  if (ev < 0 || ev >= n_rows) return;                // a counter outside the table: nothing is read or written
+  const float* row = table + (long)ev * VC_SDE_ROW;
+  const SdeRow r{(int)row[0], row[1], row[2], row[3], row[4]};
+  if (r.mode < VC_SDE_EM || r.mode > VC_SDE_INJECT) return;
+  const bool heun = r.mode == VC_SDE_HEUN1 || r.mode == VC_SDE_HEUN2;
+  if ((r.mode != VC_SDE_INJECT && !v) || ((heun || r.mode == VC_SDE_INJECT) && !xhat) || (heun && !k1)) return;   // a row the call has no buffers for
+  const bool rd_y = r.mode != VC_SDE_HEUN1, rd_xh = heun, rd_k1 = r.mode == VC_SDE_HEUN2, rd_v = r.mode != VC_SDE_INJECT;
+  const bool wr_y = r.mode != VC_SDE_INJECT, wr_xh = r.mode == VC_SDE_HEUN2 || r.mode == VC_SDE_INJECT, wr_k1 = r.mode == VC_SDE_HEUN1;
+  const bool noisy = r.g != 0.0f && (r.mode == VC_SDE_EM || r.mode == VC_SDE_HEUN2 || r.mode == VC_SDE_INJECT);
+  // draw d of the trajectory: the step an Euler-Maruyama row belongs to, the NEXT step behind a Heun row (its noise is injected ahead
+  // of that step's first evaluation), draw 0 for the injection in front of the first step
+  const uint64_t d = r.mode == VC_SDE_EM ? (uint64_t)ev : r.mode == VC_SDE_HEUN2 ? (uint64_t)(ev + 1) >> 1 : 0;
+  const uint32_t k0 = (uint32_t)rng[0], kk1 = (uint32_t)(rng[0] >> 32);
+  const uint64_t p0 = rng[1] + d * (uint64_t)n;
+  const long total = nvec + (n - nvec * 8);
+  for (long wi = blockIdx.x * 256L + threadIdx.x; wi < total; wi += gridDim.x * 256L) {
+    if (wi < nvec) {
+      const long i = wi * 8;
+      float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (noisy) {
+        const uint64_t p = p0 + (uint64_t)i;
+        switch ((uint32_t)p & 3u) {
+          case 0: normals8<0>(p, k0, kk1, z); break;
+          case 1: normals8<1>(p, k0, kk1, z); break;
+          case 2: normals8<2>(p, k0, kk1, z); break;
+          default: normals8<3>(p, k0, kk1, z); break;
+        }
+      }
+      f32x4 yv[2] = {}, xv[2] = {}, kv[2] = {};
+      u32x4 vv = {0, 0, 0, 0};
+      if (rd_y) { yv[0] = *(const f32x4*)(y + i); yv[1] = *(const f32x4*)(y + i + 4); }
+      if (rd_xh) { xv[0] = *(const f32x4*)(xhat + i); xv[1] = *(const f32x4*)(xhat + i + 4); }
+      if (rd_k1) { kv[0] = *(const f32x4*)(k1 + i); kv[1] = *(const f32x4*)(k1 + i + 4); }
+      if (rd_v) vv = *(const u32x4*)(v + i);
+      f32x4 yo[2], xo[2], ko[2];
+      float in8[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float vel = -((e & 1) ? hi_bf(vv[e >> 1]) : lo_bf(vv[e >> 1]));       // the drift's sign: exact
+        const SdeIo o = sde_element(r, SdeIo{yv[e >> 2][e & 3], xv[e >> 2][e & 3], kv[e >> 2][e & 3], 0.0f}, vel, z[e]);
+        yo[e >> 2][e & 3] = o.y; xo[e >> 2][e & 3] = o.xhat; ko[e >> 2][e & 3] = o.k1; in8[e] = o.y_in;
+      }
+      if (wr_y) { *(f32x4*)(y + i) = yo[0]; *(f32x4*)(y + i + 4) = yo[1]; }
+      if (wr_xh) { *(f32x4*)(xhat + i) = xo[0]; *(f32x4*)(xhat + i + 4) = xo[1]; }
+      if (wr_k1) { *(f32x4*)(k1 + i) = ko[0]; *(f32x4*)(k1 + i + 4) = ko[1]; }
+      u32x4 w;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w[e] = pack2bf(in8[2 * e], in8[2 * e + 1]);
+      *(u32x4*)(y_in + i) = w;
+    } else {
+      const long i = nvec * 8 + (wi - nvec);
+      const float z = noisy ? normal_at(p0 + (uint64_t)i, k0, kk1) : 0.0f;
+      const float vel = rd_v ? -bf2f(v[i]) : 0.0f;
+      const SdeIo o = sde_element(r, SdeIo{rd_y ? y[i] : 0.0f, rd_xh ? xhat[i] : 0.0f, rd_k1 ? k1[i] : 0.0f, 0.0f}, vel, z);
+      if (wr_y) y[i] = o.y;
+      if (wr_xh) xhat[i] = o.xhat;
+      if (wr_k1) k1[i] = o.k1;
+      y_in[i] = f2bf(o.y_in);
+    }
+  }
+}
+
+// the F32 state -> the caller's buffer (a trajectory row, the result): bf16 rounded once, or F32 as it is
+template <bool BF16>
+__global__ __launch_bounds__(256) void sde_store_kernel(const float* __restrict__ y, void* __restrict__ out, long n) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+    if (BF16) ((bf16_t*)out)[i] = f2bf(y[i]);
+    else ((float*)out)[i] = y[i];
+  }
+}
+
 }  // namespace
 
 #define RNG_LAUNCHED(name)                                                                                          \
@@ -170,4 +299,29 @@ int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int co
   hipLaunchKernelGGL(randn_tokens_kernel, dim3(grid_for((long)(h / 2) * (w / 2) * (C / 2))), dim3(256), 0, s, (bf16_t*)tokens, C, h, w, (long)ld,
                      col0, seed, offset);
   RNG_LAUNCHED("randn_tokens")
+}
+
+int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
+                        const uint64_t* rng, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (!table || !y || !y_in || !rng || n <= 0 || n_rows <= 0 || eval >= n_rows || (eval < 0 && !eval_ptr)) {
+    snprintf(err, errlen, "sde_stage: bad args (table, y, y_in, rng required; n, n_rows >= 1; eval in [0, n_rows), or < 0 with the evaluation "
+                          "counter; eval=%d n_rows=%d n=%lld)", eval, n_rows, (long long)n);
+    return VC_ERR_ARG;
+  }
+  if (((uintptr_t)table | (uintptr_t)y | (uintptr_t)xhat | (uintptr_t)k1) & 3 || ((uintptr_t)v | (uintptr_t)y_in) & 1 || (uintptr_t)rng & 7) {
+    snprintf(err, errlen, "sde_stage: every buffer must be aligned to its elements (F32: 4 bytes, bf16: 2, rng: 8)");
+    return VC_ERR_ARG;
+  }
+  const bool vec = !(((uintptr_t)y | (uintptr_t)v | (uintptr_t)y_in | (uintptr_t)xhat | (uintptr_t)k1) & 15);   // (NULL counts as aligned)
+  const long nvec = vec ? (long)(n / 8) : 0;
+  hipLaunchKernelGGL(sde_stage_kernel, dim3(grid_for(nvec + (n - nvec * 8))), dim3(256), 0, s, eval, table, n_rows, y, (const bf16_t*)v,
+                     (bf16_t*)y_in, xhat, k1, rng, (const int*)eval_ptr, (long)n, nvec);
+  RNG_LAUNCHED("sde_stage")
+}
+
+int vc_sde_store_launch(const float* y, void* out, int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (!y || !out || n <= 0) { snprintf(err, errlen, "sde_store: bad args"); return VC_ERR_ARG; }
+  if (out_is_bf16) hipLaunchKernelGGL(sde_store_kernel<true>, dim3(grid_for((long)n)), dim3(256), 0, s, y, out, (long)n);
+  else hipLaunchKernelGGL(sde_store_kernel<false>, dim3(grid_for((long)n)), dim3(256), 0, s, y, out, (long)n);
+  RNG_LAUNCHED("sde_store")
 }

@@ -67,6 +67,12 @@ int vc_dopri5_error_ratio_launch(int mode, const float* y0, const float* y1, con
 int vc_dopri5_interp_launch(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int out_is_bf16,
                             int64_t n, hipStream_t s, char* err, int errlen);
 int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
+// rng.hip / sde_plan.hip: the stochastic sampler's update, the store of its F32 state in the caller's dtype, and its host rule
+int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
+                        const uint64_t* rng, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_sde_store_launch(const float* y, void* out, int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_sde_plan_impl(const char* method, const char* form, double norm, const char* last_step, double last_step_size, const float* t_grid,
+                     int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws, char* err, int errlen);
 int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen);
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
@@ -181,6 +187,9 @@ int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const fl
                                float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
 int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                             int32_t* evaluations, char* err, int errlen);
+int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
+                            double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
+                            void* trajectory, hipStream_t s, char* err, int errlen);
 int vc_flux_step_nodes_impl(void* handle, int32_t nodes[3], char* err, int errlen);
 int vc_flux_set_monitor_impl(void* handle, int32_t level, VcStat* log, int32_t capacity_evals, float* scratch, char* err, int errlen);
 int vc_flux_monitor_sites_impl(void* handle, int32_t index, char* name, int32_t namelen, char* err, int errlen);

@@ -148,6 +148,7 @@ class FluxHandle(_Handle):
         self._taps: Dict[str, torch.Tensor] = {}
         self.lora_mode = 0
         self.adaptive = 0
+        self.sde = 0
         if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
             scales = []
             for name, R in weights.ref.items():
@@ -356,6 +357,14 @@ class FluxHandle(_Handle):
             self.adaptive = int(bool(on))
             self.geom = None
 
+    def set_sde(self, on: bool) -> None:
+        """vc_flux_set_option("sde"): 1 = the workspace holds the buffers of the stochastic sampler (`sample_sde`).  A switch needs a
+        new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
+        hip._check(hip.lib().vc_flux_set_option(self.h, b"sde", int(bool(on))), "vc_flux_set_option(sde)")
+        if int(bool(on)) != self.sde:
+            self.sde = int(bool(on))
+            self.geom = None
+
     def set_lora_scale(self, scale: float) -> None:
         """vc_flux_set_lora_scale: the scale of every pair; a bf16 value, anything else is refused, and so is a change while a
         trajectory is in flight.  Call `prepare` again after a change (forward / sample_* refuse a prepared state of the old scale);
@@ -414,7 +423,7 @@ class FluxHandle(_Handle):
         return {"computed": c.value, "reused": r.value, "metrics": [float(m[i]) for i in range(n)]}
 
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
-        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ())
+        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ()) + (("sde",) if self.sde else ())
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:
@@ -523,6 +532,17 @@ class FluxHandle(_Handle):
         args = self._sample_args("vc_flux_sample_dopri5", 0, x, cond, t_grid, state_is_bf16, trajectory)
         hip._check(hip.lib().vc_flux_sample_dopri5(args[0], *args[2:], float(rtol), float(atol), int(max_attempts), hip._p(trajectory), stream),
                    "vc_flux_sample_dopri5")
+
+    def sample_sde(self, method: str, x, cond, t_grid, state_is_bf16: bool, stream, form: str = "SBDM", norm: float = 1.0,
+                   last_step="Mean", last_step_size: float = 0.04, seed: int = 0, offset: int = 0, trajectory=None) -> None:
+        """vc_flux_sample_sde (after `set_sde(True)` and a prepare with max_steps >= the plan's evaluations): x [B,N,C] in place,
+        x(t_grid[0]) -> the sample, by the stochastic sampler `method` ("Euler" | "Heun"); trajectory: optional [len(t_grid), B, N, C]
+        buffer: x' after every loop step, the last step's result as the final row.  Draw d takes the positions offset + d * x.numel()
+        + i of the stream of `seed`.  The state is stepped in f32 whatever its dtype."""
+        args = self._sample_args("vc_flux_sample_sde", 0, x, cond, t_grid, state_is_bf16, trajectory)
+        hip._check(hip.lib().vc_flux_sample_sde(self.h, hip._cstr(method), args[2], args[3], args[4], args[5], hip._cstr(form), float(norm),
+                                                hip._cstr(last_step), float(last_step_size), hip._u64(seed, "seed"), hip._u64(offset, "offset"),
+                                                args[6], hip._p(trajectory), stream), "vc_flux_sample_sde")
 
     def dopri5_log(self) -> dict:
         """vc_flux_dopri5_log of the last `sample_dopri5`: {"attempts": [(t, dt, ratio, accepted), ...], "evaluations", "rejected"}"""

@@ -21,6 +21,7 @@ CSRC = os.path.join(_HERE, "csrc")
 ABI_VERSION = 11               # VC_ABI_VERSION of include/vcloze_hip.h
 SOLVER_EULER, SOLVER_MIDPOINT, SOLVER_RK4 = 0, 1, 2     # VC_SOLVER_*: the fixed-grid methods of the fused sampling loop
 SOLVERS = {"euler": SOLVER_EULER, "midpoint": SOLVER_MIDPOINT, "rk4": SOLVER_RK4}
+SDE_EM, SDE_HEUN1, SDE_HEUN2, SDE_LAST, SDE_INJECT, SDE_ROW = 0, 1, 2, 3, 4, 5     # VC_SDE_*: the row modes of vc_sde_stage, values per row
 GEMM_MAX_PROBLEMS = 4          # VC_GEMM_MAX_PROBLEMS: grouped problems per vc_gemm launch
 EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_SILU, EPI_QKV = 0, 1, 2, 3, 4
 GEMM_NO_SPLIT = 64             # VC_GEMM_NO_SPLIT: tile_cfg value that keeps an auto-tiled vc_gemm one launch
@@ -221,6 +222,9 @@ SYMBOLS = {
     "vc_dopri5_stage": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_dopri5_error_ratio": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp]),
     "vc_dopri5_interp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _i32, _i64, _vp]),
+    "vc_sde_plan": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_char_p, C.c_double, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float),
+                              C.POINTER(C.c_float), _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_sde_stage": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_residual_change": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
@@ -280,6 +284,8 @@ SYMBOLS = {
     "vc_flux_sample_dopri5": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp]),
     "vc_flux_dopri5_log": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(_i32), _i32,
                                      C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_flux_sample_sde": (C.c_int, [_vp, C.c_char_p, _vp, _vp, C.POINTER(C.c_float), _i32, C.c_char_p, C.c_double, C.c_char_p, C.c_double,
+                                     C.c_uint64, C.c_uint64, _i32, _vp, _vp]),
     "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
     "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
@@ -855,6 +861,53 @@ def dopri5_interp(y0, y1, k, dt, theta: float, out=None, dtype=torch.float32, st
 
 
 RESIDUAL_CHANGE_MAX_BLOCKS = 256     # VC_RESIDUAL_CHANGE_MAX_BLOCKS
+
+
+def _cstr(v):
+    return None if v is None else str(v).encode()
+
+
+def sde_plan(method: str, form: str, norm: float, last_step, last_step_size: float, t_grid) -> dict:
+    """vc_sde_plan (host only): the coefficient rows and model times of a stochastic trajectory over the f32 grid `t_grid` ->
+    {"rows": f32 [n_rows, 5] (mode, h, A, Bc, g; for "Heun" one injection row behind the evaluations'), "times": f32 [evals] (1 - t),
+    "evals", "draws"}.  A refusal (unknown names, a grid that does not increase, a non-finite coefficient) raises VclozeHipError."""
+    t = np.ascontiguousarray(t_grid.detach().cpu().numpy() if torch.is_tensor(t_grid) else t_grid, dtype=np.float32).reshape(-1)
+    tp = t.ctypes.data_as(C.POINTER(C.c_float)) if t.size else None
+    args = (_cstr(method), _cstr(form), float(norm), _cstr(last_step), float(last_step_size), tp, int(t.size))
+    ne, nd = C.c_int32(0), C.c_int32(0)
+    _check(lib().vc_sde_plan(*args, None, None, 0, C.byref(ne), C.byref(nd)), "vc_sde_plan")
+    cap = ne.value + 1
+    rows, times = np.zeros((cap, SDE_ROW), np.float32), np.zeros(cap, np.float32)
+    _check(lib().vc_sde_plan(*args, rows.ctypes.data_as(C.POINTER(C.c_float)), times.ctypes.data_as(C.POINTER(C.c_float)), cap,
+                             C.byref(ne), C.byref(nd)), "vc_sde_plan")
+    n_rows = ne.value + (1 if method == "Heun" else 0)
+    return {"rows": rows[:n_rows], "times": times[:ne.value], "evals": ne.value, "draws": nd.value}
+
+
+def rng_words(seed, offset, device=None) -> torch.Tensor:
+    """the (seed, offset) word pair vc_sde_stage reads from device memory: two uint64, held in an int64 tensor [2]"""
+    w = np.array([_u64(seed, "seed"), _u64(offset, "offset")], dtype=np.uint64).view(np.int64)
+    return torch.from_numpy(w.copy()).to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+
+
+def sde_stage(eval_index: int, table, y, v, y_in, rng, xhat=None, k1=None, eval_ptr=None, stream=None) -> None:
+    """vc_sde_stage: one update of the stochastic sampler on n = y.numel() elements.  table: f32 [n_rows, 5] (device); row =
+    eval_index, or with eval_index < 0 the device-side counter eval_ptr (int32 [1]).  y, xhat, k1: f32 [n]; v: the model's bf16 output
+    (None for an injection row); y_in: bf16 [n]; rng: `rng_words(seed, offset)`.  Draw d of the row takes stream positions
+    offset + d * n + i."""
+    n = y.numel()
+    for name, t, dt in (("table", table, torch.float32), ("y", y, torch.float32), ("xhat", xhat, torch.float32), ("k1", k1, torch.float32),
+                        ("v", v, torch.bfloat16), ("y_in", y_in, torch.bfloat16), ("rng", rng, torch.int64), ("eval_ptr", eval_ptr, torch.int32)):
+        if t is None:
+            continue
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise VclozeHipError(f"vc_sde_stage: {name} must be a contiguous CUDA {dt} tensor, got {t.dtype} on {t.device}")
+        if name in ("xhat", "k1", "v", "y_in") and t.numel() != n:
+            raise VclozeHipError(f"vc_sde_stage: {name} must hold n = {n} values, got {t.numel()}")
+    if table.dim() != 2 or table.shape[1] != SDE_ROW or rng.numel() != 2:
+        raise VclozeHipError("vc_sde_stage: table must be [n_rows, 5] and rng hold the two words (seed, offset)")
+    _check(lib().vc_sde_stage(int(eval_index), table.data_ptr(), table.shape[0], y.data_ptr(), _p(v), y_in.data_ptr(), _p(xhat), _p(k1),
+                              rng.data_ptr(), _p(eval_ptr), n, stream if stream is not None else cur_stream()), "vc_sde_stage")
 
 
 def residual_change(h0, h1, p, r=None, stream=None):

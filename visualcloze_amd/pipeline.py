@@ -113,15 +113,26 @@ def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
 def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[torch.Tensor],
                  mask_rows: List[torch.Tensor], txt: torch.Tensor, vec: torch.Tensor, cfg: float = 30.0,
                  steps: int = 30, solver: str = "euler", time_shifting_factor=1, step_cache=None,
-                 adaptive: Optional[dict] = None) -> List[torch.Tensor]:
+                 adaptive: Optional[dict] = None, sde: Optional[dict] = None, rng=None) -> List[torch.Tensor]:
     """One grid: per-row noise [1,16,h,w], VAE latents of the grid rows (already shifted/scaled), per-row PIXEL
     fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w].
     `adaptive`: None, or dict(rtol=, atol=[, max_attempts=]) - the error-controlled Dormand-Prince 5(4) solve
-    (`Sampler.sample_ode_adaptive`) instead of `solver`; `steps` then only places the end time's grid."""
+    (`Sampler.sample_ode_adaptive`) instead of `solver`; `steps` then only places the end time's grid.
+    `sde`: None, or dict(sampling_method=, diffusion_form=, diffusion_norm=, last_step=, last_step_size=, sample_eps=) - any subset -
+    the stochastic sampler (`Sampler.sample_sde`, num_steps = `steps`) instead of `solver`; its noise comes from `rng`, which must be a
+    `NoiseStream` (its offset advances by the draws).  Image quality under any diffusion form is unmeasured."""
     dev = noise_rows[0].device
     img, img_ids, img_mask = packing.prepare_grid([noise_rows])                       # visualcloze.py:403
     cond = packing.pack_cond(cond_latent_rows, mask_rows)                              # :381-389
     sampler = Sampler(create_transport("Linear", "velocity", do_shift=True))
+    if sde is not None:
+        if adaptive is not None or step_cache is not None:
+            raise ValueError("sde: the stochastic sampler works neither with adaptive= nor with the step cache")
+        if not isinstance(rng, NoiseStream):
+            raise ValueError("sde: the stochastic sampler draws from the library's stream: pass rng=NoiseStream(seed)")
+        fn = sampler.sample_sde(num_steps=steps, rng=rng, **sde)
+        samples = fn(img, model.forward, **_kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]
+        return packing.unpack_rows(samples, [tuple(r.shape[-2:]) for r in noise_rows])
     if adaptive is not None:
         if step_cache is not None:
             raise ValueError("adaptive: the step cache works with the fixed-grid Euler loop only")
@@ -193,7 +204,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
                   solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
                   step_cache=None, use_grid_handle: bool = False, adaptive: Optional[dict] = None,
-                  monitor: Optional[int] = None) -> List[torch.Tensor]:
+                  monitor: Optional[int] = None, sde: Optional[dict] = None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -214,17 +225,25 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     handle runs the fixed-grid solvers only.
     `monitor`: None (the default: `model.monitor` as it stands), or 0 | 1 | 2 - the numerics monitor of the Flux handle for this call
     (`Flux.monitor`): `model.last_monitor_log` / `model.last_monitor_report` tell what the solve's evaluations held, and with
-    `model.monitor_strict` a NaN / inf raises FloatingPointError.  Refused together with use_grid_handle=True and with `adaptive`."""
+    `model.monitor_strict` a NaN / inf raises FloatingPointError.  Refused together with use_grid_handle=True, `adaptive` and `sde`.
+    `sde`: None (the default), or a dict of `Sampler.sample_sde` settings - denoise with the stochastic sampler instead of `solver`
+    (`denoise_grid`); needs `rng` to be a `NoiseStream`, from which the sampler's draws follow the start noise.  Refused together with
+    use_grid_handle=True: the grid handle runs the fixed-grid solvers only."""
+    if sde is not None:
+        if use_grid_handle:
+            raise ValueError("generate_grid(sde=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid solvers only")
+        if not isinstance(rng, NoiseStream):
+            raise ValueError("generate_grid(sde=...) draws from the library's stream: pass rng=NoiseStream(seed)")
     if monitor is not None:
-        if monitor and (use_grid_handle or adaptive is not None):
+        if monitor and (use_grid_handle or adaptive is not None or sde is not None):
             raise ValueError("generate_grid(monitor=...) works with the fixed-grid solvers of the Flux handle, not with use_grid_handle=True "
-                             "(the grid handle drives its own trajectory) or adaptive=")
+                             "(the grid handle drives its own trajectory), adaptive= or sde=")
         before = model.monitor
         model.monitor = monitor
         try:
             return generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                                  encode_noise=encode_noise, decode_rows=decode_rows, solver=solver, time_shifting_factor=time_shifting_factor,
-                                 rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle, adaptive=adaptive)
+                                 rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle, adaptive=adaptive, sde=sde)
         finally:
             model.monitor = before
     if adaptive is not None and use_grid_handle:
@@ -249,7 +268,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     txt = t5(t5_ids)                                                                   # prepare_modified -> HFEmbedder
     vec, _ = clip(clip_ids)
     rows = denoise_grid(model, noise, lat, row_masks, txt, vec, cfg=cfg, steps=steps, solver=solver,
-                        time_shifting_factor=time_shifting_factor, step_cache=step_cache, adaptive=adaptive)
+                        time_shifting_factor=time_shifting_factor, step_cache=step_cache, adaptive=adaptive, sde=sde, rng=rng)
     out = []
     for i in (range(len(rows)) if decode_rows is None else decode_rows):
         img = ae.decode(rows[i])[0]                                                    # :430

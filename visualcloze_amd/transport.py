@@ -17,6 +17,12 @@ behind them) runs the same fused loop with the cross-sample combine as one more 
 own - `sample_ode(sampling_method="dopri5")` keeps raising: adaptive Dormand-Prince 5(4), fused through vc_flux_sample_dopri5 for a
 `visualcloze_amd.Flux` with the C handle, `dopri5_integrate` (the same rule in plain torch) for any other callable.
 
+`Sampler.sample_sde` is the reference's stochastic sampler (transport.py:300-359: Euler-Maruyama / stochastic Heun, the six diffusion
+forms, the four last steps) on the velocity v(x, t) = -model(x || cond, timesteps = 1 - t) - the adaptation the reference made for
+sample_ode only.  `sde_plan` turns a setting into one coefficient row per evaluation (bit for bit vc_sde_plan's table), `sde_integrate`
+is the literal torch restatement of the loop, and the fused path is vc_flux_sample_sde: the captured evaluation with vc_sde_stage
+behind it, the noise drawn inside that kernel from the library's counter-based stream.
+
 The step rules (`STEP_RULES`) are torchdiffeq 0.2.x's fixed-grid solvers as recalled - unpinned against real
 torchdiffeq, which was not available to check against (as the Euler rule, tests/golden/make_golden.py).  They
 are written ONCE, as the literal torch expressions: a correction is a one-line change here and in
@@ -64,8 +70,13 @@ class Transport:
         self.path_type, self.prediction, self.do_shift = path_type, prediction, do_shift
         self.train_eps = self.sample_eps = 0  # velocity & Linear is stable everywhere (transport/__init__.py:46-48)
 
-    def check_interval(self, reverse: bool = False):
-        t0, t1 = 0, 1  # transport.py:70-96 for Linear + velocity, sde=False
+    def check_interval(self, reverse: bool = False, *, sde: bool = False, diffusion_form: str = "SBDM", last_step_size: float = 0.0,
+                       sample_eps=None):
+        t0, t1 = 0, 1  # transport.py:70-96 for Linear + velocity
+        if sde:        # ... eval=True: t0 = eps for SBDM, t1 = 1 - last_step_size with a last step, else 1 - eps
+            eps = self.sample_eps if sample_eps is None else sample_eps
+            t0 = eps if diffusion_form == "SBDM" else 0
+            t1 = 1 - eps if last_step_size == 0 else 1 - last_step_size
         if reverse:
             t0, t1 = 1 - t0, 1 - t1
         return t0, t1
@@ -264,6 +275,154 @@ def dopri5_integrate(f, y0: torch.Tensor, t, rtol: float = 1e-3, atol: float = 1
     return torch.stack(outs)
 
 
+# ---- the stochastic (SDE) sampler (vc_sde_plan / vc_sde_stage / vc_flux_sample_sde).  Time runs as in sample_ode: t = 0 noise, t = 1
+# data; Linear path alpha = t, sigma = 1 - t.  With v the velocity and w(t) the diffusion coefficient:
+#   score s = (t v - x) / (1 - t);   sde drift D(x, t) = v + w s = A v - Bc x,  A = 1 + w t / (1 - t),  Bc = w / (1 - t)
+# so every update is one row of y + h (A v - Bc y) + g z.  The coefficients are computed in double, operation by operation as in
+# csrc/sde_plan.hip, and rounded once to f32.
+SDE_FORMS = ("constant", "SBDM", "sigma", "linear", "decreasing", "inccreasing-decreasing")     # (the reference's spelling of the last)
+SDE_METHODS = ("Euler", "Heun")
+SDE_LAST_STEPS = ("Mean", "Euler", "Tweedie")
+
+
+def _div(a: float, b: float) -> float:
+    """a / b as IEEE double division gives it (inf / NaN for b == 0, where Python raises)"""
+    if b != 0.0:
+        return a / b
+    return math.nan if a == 0.0 or a != a else math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def _sqrt(a: float) -> float:
+    return math.sqrt(a) if a >= 0.0 else math.nan
+
+
+def sde_diffusion(form: str, norm: float, t: float) -> float:
+    """w(t) of transport/path.py's ICPlan.compute_diffusion for the Linear path, in double"""
+    if form == "constant":
+        return norm
+    if form == "SBDM":
+        return _div(norm * (1.0 - t), t)
+    if form in ("sigma", "linear"):
+        return norm * (1.0 - t)
+    if form == "decreasing":
+        u = norm * math.cos(math.pi * t) + 1.0
+        return 0.25 * (u * u)
+    s = math.sin(math.pi * t)
+    return norm * (s * s)
+
+
+def sde_plan(method: str, form: str, norm: float, last_step, last_step_size: float, t) -> dict:
+    """The host rule of the stochastic sampler, bit for bit vc_sde_plan (hip.sde_plan): the f32 time grid `t` (n points) ->
+    {"rows": f32 [n_rows, 5] = (mode, h, A, Bc, g) per evaluation - for "Heun" one more row behind them, the injection of draw 0 -,
+    "rows64": the same coefficients before their rounding to f32 (what an f64 state is stepped with), "times": f32 [evals] = the model
+    times 1 - t, "evals": Euler (n - 1) + (last step ? 1 : 0), Heun 2 (n - 1) + (last step ? 1 : 0), "draws": n - 1}.
+    NotImplementedError for an unknown method / form / last step; ValueError for a grid that does not increase strictly and for ANY
+    non-finite coefficient (SBDM at t = 0 - it needs a sample_eps; any row at t = 1, hence Heun without a last step)."""
+    import numpy as np
+    if method not in SDE_METHODS:
+        raise NotImplementedError(f"sde_plan: unknown method {method!r} {SDE_METHODS}")
+    if form == "increasing-decreasing":
+        form = "inccreasing-decreasing"
+    if form not in SDE_FORMS:
+        raise NotImplementedError(f"sde_plan: unknown diffusion form {form!r} {SDE_FORMS}")
+    if last_step is not None and last_step != "" and last_step not in SDE_LAST_STEPS:
+        raise NotImplementedError(f"sde_plan: unknown last step {last_step!r} ({SDE_LAST_STEPS}, or None)")
+    last_step = last_step or None
+    t32 = np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float32).reshape(-1)
+    n = int(t32.size)
+    if n < 2 or not bool(np.all(t32[1:] > t32[:-1])):
+        raise ValueError("sde_plan: t must hold at least two strictly increasing times")
+    norm, lss, S = float(norm), float(last_step_size), n - 1
+    tt = [float(v) for v in t32]
+    dts = [float(np.float32(t32[i + 1] - t32[i])) for i in range(S)]
+    rows64, times = [], []
+
+    def A(w, tv):
+        return 1.0 + _div(w * tv, 1.0 - tv)
+
+    def Bc(w, tv):
+        return _div(w, 1.0 - tv)
+
+    def noise(i):
+        return _sqrt(2.0 * sde_diffusion(form, norm, tt[i]) * dts[i])
+
+    with np.errstate(all="ignore"):
+        def put(mode, h, a, b, g, tv, timed=True):
+            row = (mode, h, a, b, g)
+            for name, c in zip(("h", "A", "Bc", "g"), row[1:]):
+                if not math.isfinite(float(np.float32(c))):
+                    raise ValueError(f"sde_plan: the coefficient {name} = {c!r} at t = {tv!r} is not finite with diffusion form {form!r} "
+                                     "(SBDM needs t > 0 - a sample_eps; every form needs t < 1 - a last step, or an end time below 1)")
+            rows64.append(tuple(float(c) for c in row))
+            if timed:
+                times.append(np.float32(1.0) - np.float32(tv))
+
+        for i in range(S):
+            tv, dt = tt[i], dts[i]
+            w = sde_diffusion(form, norm, tv)
+            if method == "Euler":
+                put(hip.SDE_EM, dt, A(w, tv), Bc(w, tv), noise(i), tv)
+            else:
+                put(hip.SDE_HEUN1, dt, A(w, tv), Bc(w, tv), 0.0, tv)
+                t2 = tv + dt
+                w2 = sde_diffusion(form, norm, t2)
+                put(hip.SDE_HEUN2, 0.5 * dt, A(w2, t2), Bc(w2, t2), noise(i + 1) if i + 1 < S else 0.0, t2)
+        if last_step is not None:
+            t1 = tt[S]
+            w = sde_diffusion(form, norm, t1)
+            if last_step == "Mean":
+                put(hip.SDE_LAST, lss, A(w, t1), Bc(w, t1), 0.0, t1)
+            else:
+                put(hip.SDE_LAST, lss if last_step == "Euler" else 1.0 - t1, 1.0, 0.0, 0.0, t1)
+        evals = len(rows64)
+        if method == "Heun":
+            put(hip.SDE_INJECT, 0.0, 0.0, 0.0, noise(0), tt[0], timed=False)
+        rows = np.array(rows64, dtype=np.float64).astype(np.float32)
+    return {"rows": rows, "rows64": rows64, "times": np.array(times, dtype=np.float32), "evals": evals, "draws": S, "method": method}
+
+
+def sde_integrate(f, x: torch.Tensor, plan: dict, noise: Callable) -> torch.Tensor:
+    """The stochastic sampler as literal torch expressions - what vc_sde_stage computes, operation by operation (an f32 state gives
+    the kernel's bits) - for any callable and any float dtype: -> [n_points, ...], x' after every loop step and the last step's result
+    as the final row (without a last step it repeats the state).  f(tau, y) is the MODEL's output for the state y at the model time
+    tau = 1 - t (a Python float); the velocity is -f.  noise(d, shape) supplies draw d (d = solver step index).  An f64 state is
+    stepped with the double coefficients (plan["rows64"]), anything else with the f32 rows; g == 0 adds no noise term."""
+    n_evals = plan["evals"]
+    rows = plan["rows64"] if x.dtype == torch.float64 else [tuple(float(c) for c in r) for r in plan["rows"]]
+
+    def z(d):
+        return noise(d, x.shape).to(device=x.device, dtype=x.dtype)
+
+    y, xhat, k1, outs = x, None, None, []
+    y_in = y
+    if len(rows) > n_evals:                        # Heun: draw 0 goes in ahead of the first evaluation
+        g = rows[n_evals][4]
+        xhat = y + g * z(0) if g != 0.0 else y
+        y_in = xhat
+    for e in range(n_evals):
+        mode, h, A, Bc, g = rows[e]
+        mode = int(mode)
+        vel = (-f(float(plan["times"][e]), y_in)).to(x.dtype)
+        if mode in (hip.SDE_EM, hip.SDE_LAST):
+            y = y + h * (A * vel - Bc * y)
+            if mode == hip.SDE_EM and g != 0.0:
+                y = y + g * z(e)
+            y_in = y
+            outs.append(y)
+        elif mode == hip.SDE_HEUN1:
+            k1 = A * vel - Bc * xhat
+            y = xhat + h * k1
+            y_in = y
+        else:                                      # SDE_HEUN2: the step's end, and the NEXT step's noise
+            y = xhat + h * (k1 + (A * vel - Bc * y))
+            xhat = y + g * z((e + 1) // 2) if g != 0.0 else y
+            y_in = xhat
+            outs.append(y)
+    if len(outs) == plan["draws"]:                 # no last step
+        outs.append(y)
+    return torch.stack(outs)
+
+
 class StepCache:
     """Opt-in first-block step cache of the fused Euler loop (vc_flux_set_step_cache).  IT CHANGES RESULTS: an
     evaluation whose first-block residual moved by less than `threshold` (relative L1 against the last computed evaluation's) is
@@ -392,6 +551,103 @@ class Sampler:
         return _sample
 
 
+    def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
+                   num_steps=250, sample_eps=None, rng=None, return_trajectory: bool = False):
+        """The reference's stochastic sampler (transport.py:300-359; names, defaults and call shape are its own): returns
+        `_sample(init, model, **model_kwargs)` -> [1, B, N, C], or [num_steps, B, N, C] with return_trajectory (x' after every loop
+        step, then the last step's result), in the caller's dtype; `[-1]` is the sample, as with the reference's list.
+        sampling_method "Euler" (Euler-Maruyama) | "Heun"; diffusion_form: one of SDE_FORMS; last_step "Mean" | "Euler" | "Tweedie" |
+        None.  The mathematics is applied to the velocity -model(x || cond, timesteps = 1 - t), the adaptation the reference made for
+        sample_ode only.  Interval as `Transport.check_interval(sde=True)`: t0 = eps for SBDM else 0, t1 = 1 - last_step_size with a
+        last step else 1 - eps, eps = `sample_eps` if given else the transport's 0; the grid is linspace(t0, t1, num_steps).  The
+        reference's default (SBDM, eps 0) is infinite at t = 0: here it raises a ValueError naming sample_eps, as does every setting
+        with a non-finite coefficient (Heun without a last step) - never a NaN latent.
+        Fused (vc_flux_sample_sde) for the bound forward / forward_with_cfg of a visualcloze_amd.Flux that has the C handle and a bf16 /
+        f32 state, per chunk of samples; eager (`sde_integrate`) otherwise.  The state is stepped in f32 (f64 for an f64 caller) and
+        rounded once per output.
+        rng: a `pipeline.NoiseStream` - draw d of a chunk takes the stream positions offset + d * n + i, n the chunk's elements and i
+        the flat index in the chunk's [B, N, C] state IN THE HANDLE'S ROW ORDER (image rows valid-first per sample: for all-ones image
+        masks the caller's order); its offset advances by draws * elements, chunk after chunk.  rng=None: a seed is drawn from
+        torch's default generator, so torch.manual_seed reproduces.  The eager path of a CUDA state draws the same stream for the
+        whole batch in the caller's order; a foreign callable on the CPU draws with torch.randn.
+        Image quality under any diffusion_form is unmeasured (only random-init weights exist here)."""
+        if last_step is None:
+            last_step_size = 0.0
+        t0, t1 = self.transport.check_interval(sde=True, diffusion_form=diffusion_form, last_step_size=last_step_size, sample_eps=sample_eps)
+        assert t0 < t1, "SDE sampler has to be in forward time"
+        t = torch.linspace(t0, t1, num_steps)
+        plan = sde_plan(sampling_method, diffusion_form, diffusion_norm, last_step, last_step_size, t)     # every refusal, up front
+        setting = (sampling_method, diffusion_form, float(diffusion_norm), last_step, float(last_step_size))
+
+        def _sample(init: torch.Tensor, model: Callable, **model_kwargs) -> torch.Tensor:
+            x = init
+            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
+            is_flux = kind != "foreign"
+            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
+            if fused and cfg_scale is not None:
+                fused = _cfg_fusable(owner, x, "euler", kw)
+            total = plan["draws"] * x.numel()
+            if rng is not None:
+                if not x.is_cuda:
+                    raise ValueError("sample_sde: a NoiseStream draws on the device; a CPU state draws with torch.randn (rng=None)")
+                seed, offset = int(rng.seed), int(rng.offset)
+                if offset + total > 1 << 64:
+                    raise ValueError(f"sample_sde: {total} elements at offset {offset} leave the 64-bit stream")
+            else:
+                seed, offset = int(torch.randint(0, (1 << 63) - 1, (1,)).item()), 0
+            if fused:
+                out = _sample_sde_fused(owner, x, kw, t, plan, setting, seed, offset, return_trajectory, cfg_scale)
+            else:
+                if cfg_scale is not None:
+                    model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
+                out = _sample_sde_foreign(model, x, kw, plan, seed, offset, return_trajectory, bf16_out=is_flux)
+            if rng is not None:
+                rng.offset = offset + total
+            return out
+
+        return _sample
+
+
+def _sample_sde_foreign(model, x, kw, plan, seed, offset, return_trajectory, bf16_out=False):
+    """Any callable: transport.sde_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
+    cond = kw.pop("cond", None)
+
+    def f(tau, y):
+        ym = y.to(x.dtype)
+        xin = torch.cat((ym, cond), dim=-1) if cond is not None else ym
+        v = model(xin, timesteps=torch.ones(y.size(0), device=y.device) * tau, **kw)
+        assert v.shape == y.shape, "Output shape from SDE solver must match input shape"
+        return v.to(torch.bfloat16) if bf16_out else v
+
+    def noise(d, shape):
+        if not x.is_cuda:
+            return torch.randn(shape, dtype=torch.float32)
+        return hip.randn(tuple(shape), seed, offset + d * x.numel(), dtype=torch.float32, device=x.device)
+
+    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
+    with torch.no_grad():
+        out = sde_integrate(f, y0, plan, noise).to(x.dtype)
+    return out if return_trajectory else out[-1:]
+
+
+@torch.no_grad()
+def _sample_sde_fused(flux, x, kw, t, plan, setting, seed, offset, return_trajectory, cfg_scale=None):
+    """vc_flux_sample_sde per chunk of samples; a chunk's draws follow the last chunk's in the stream"""
+    h = flux.handle()
+    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_sde refuses it)
+        raise ValueError("monitor: the stochastic sampler is not logged; set Flux.monitor = 0 or use a fixed-grid solver")
+    method, form, norm, last_step, lss = setting
+    t32 = t.to(torch.float32)
+    pos = [offset]
+
+    def run(xs, cond, tj, s):
+        h.sample_sde(method, xs, cond, t32, x.dtype == torch.bfloat16, s, form=form, norm=norm, last_step=last_step, last_step_size=lss,
+                     seed=seed, offset=pos[0], trajectory=tj)
+        pos[0] += plan["draws"] * xs.numel()
+
+    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, plan["evals"], run, cfg_scale=cfg_scale, sde=True)
+
+
 def _adaptive_drift(model, x, kw, bf16_out: bool):
     """f(t, y) = -model(y in the caller's dtype || cond, timesteps = 1 - f32(t)) for a Python-float t (vcloze_hip.h)"""
     cond = kw.pop("cond", None)
@@ -445,10 +701,11 @@ def _solve_begin(flux, x, kw, S, return_trajectory, pairs=False):
     return plan, cond, out, torch.empty(S, B, N, C, dtype=x.dtype, device=plan.dev) if return_trajectory else None
 
 
-def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False):
+def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False, sde=False):
     """What the fused solves through the C handle share.  Per trajectory: the options, taken back on failure too.  Per chunk of samples
     (true CFG: whole pairs (j, j + B/2), conditional samples first): vc_flux_prepare for `max_evals` evaluations, a copy of the state's
-    rows in kernel order for run(xs, cond rows, trajectory buffer [S, bs, N, C] or None, stream) to advance in place, and the way back."""
+    rows in kernel order for run(xs, cond rows, trajectory buffer [S, bs, N, C] or None, stream) to advance in place, and the way back.
+    sde: the stochastic sampler's option, and its trajectory as it stands (S rows that end with the sample; no start state in front)."""
     plan, cond, out, traj = _solve_begin(flux, x, kw, S, return_trajectory, pairs=cfg_scale is not None)
     with _on_capture_stream(flux.plan().stream) as s:
         try:
@@ -456,6 +713,8 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
             h.set_cfg(cfg_scale)
             if adaptive:
                 h.set_adaptive(True)
+            if sde:
+                h.set_sde(True)
             for sl in plan.chunks:
                 h.prepare(*plan.prepare_args(sl, max_evals), stream=s)
                 xs = plan.img_rows(x, sl, x.dtype, copy=True)       # stepped in ITS dtype, in place: never the caller's
@@ -467,8 +726,12 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
         finally:
             if adaptive:
                 h.set_adaptive(False)              # a later fixed-grid trajectory sizes its workspace as it always did
+            if sde:
+                h.set_sde(False)
             if cfg_scale is not None:
                 h.set_cfg(None)                    # a later trajectory driven on this handle directly is a plain one again
+    if sde and traj is not None:
+        return traj
     return out[None] if traj is None else torch.cat((x.to(out.device)[None], traj), dim=0)
 
 
