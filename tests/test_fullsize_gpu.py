@@ -153,7 +153,7 @@ def test_full_width_one_plus_one_blocks_vs_oracle(small_model, geom):
 def test_full_width_non_unit_norm_scales_both_sides_of_the_logit_bound(qmax, kmax, single_max, bounded):
     """Which attention instantiation runs is a property of the WEIGHTS, block by block: the bounded-logit kernels (no running max;
     attn64s_kernel<true>, the stream form, with the queries finished by the qkv GEMM's epilogue) while
-    16.65 * max|query_norm.scale| * max|key_norm.scale| of the BLOCK is <= 100 (model.prepare / flux_engine.hip resolve(); every
+    16.65 * max|query_norm.scale| * max|key_norm.scale| of the BLOCK is <= 100 (model.prepare / flux_weights.hip resolve(); every
     other full-size test and the bench use unit scales and therefore always take it), the running-max template beyond - a real
     checkpoint may sit on either side, or on both: "mixed" gives the double block scales up to 1.5 and the single block scales up
     to 3, so ONE evaluation runs both templates (the C handle and the Python-ordered plan must pick the same ones: bit-equal).

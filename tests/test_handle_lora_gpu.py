@@ -422,6 +422,25 @@ def test_euler_trajectory_equals_the_twins_bitwise(ref_model):
     assert not torch.equal(a[0], a[-1])
 
 
+def test_unmerged_euler_step_keeps_its_captured_nodes(ref_model, merged_model):
+    """The captured Euler step in lora_mode 1 at B 2, T 16, N 24 (depth 2 + 2): 121 nodes in ONE graph, against 39 of the merged plan -
+    the count recorded on the engine while it was one file, before resolve() / lora_of / mods (flux_weights.hip) and lora_linear /
+    gemm() (flux_engine.hip) were put into separate units.  Every Linear with a pair is three GEMMs and, where its epilogue is not a plain
+    bias, a pass behind them: a change of this number is a change of the captured graph."""
+    from tests.procedural import tiny_inputs
+    inp = tiny_inputs(B=2)
+    x = inp["x"].to(DEV, torch.bfloat16)
+    assert (x.shape[0], inp["txt"].shape[1], x.shape[1]) == (2, 16, 24)
+    nodes = {}
+    for name, m in (("unmerged", _plan(ref_model, "handle")), ("merged", merged_model)):
+        _fn("euler", 5, return_trajectory=False)(x, m.forward, _kw(inp))
+        torch.cuda.synchronize()
+        h = m.handle()
+        assert h is not None and h.lora_mode == (name == "unmerged")
+        nodes[name] = h.step_nodes()
+    assert nodes == {"unmerged": (121, 0, 0), "merged": (39, 0, 0)}
+
+
 def test_f32_state_rk4_and_true_cfg(ref_model):
     """a 2-step rk4 trajectory on an f32 state, and a true-CFG pair (B = 2, another text-mask length per half): fused through the
     handle against `_sample_foreign` over the same handle's forward - bit for bit, the bound tests/test_solvers_gpu.py and

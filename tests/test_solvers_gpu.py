@@ -298,6 +298,76 @@ def test_methods_alternate_on_one_handle_without_leakage(model):
     assert torch.equal(_fn("midpoint")(x2, m.forward, _kw(inp2)), a) and torch.equal(_fn("rk4")(x2, m.forward, _kw(inp2)), b)
 
 
+def test_every_sampler_in_turn_on_one_handle_equals_a_fresh_handle(model):
+    """One handle, one stream, one workspace (options adaptive and sde on, max_steps 16): Euler, Dormand-Prince, rk4, SDE-Heun, Euler
+    with true CFG, a REFUSED sample_sde, a REFUSED sample_dopri5, midpoint, Euler.  A trajectory latches its solver once where it
+    begins (csrc/flux_sample.hip begin_trajectory): every successful result, and the captured step's node counts after every
+    fixed-grid run, are those of a handle over the same weights that ran nothing else; the last Euler is the first."""
+    from tests.procedural import tiny_inputs
+    from visualcloze_amd import hip
+    from visualcloze_amd.transport import solver_time_grid
+    m, _ = model
+    inp = tiny_inputs(B=2)
+    kw = _kw(inp)
+    x0 = inp["x"].to(DEV, torch.bfloat16)
+    assert (x0.shape[0], kw["txt"].shape[1], x0.shape[1]) == (2, 16, 24)
+    t = solver_time_grid(5, 24, 0, 1, True, None)                         # 4 steps: 16 evaluations of rk4
+    t_sde = torch.linspace(0, 0.75, 4)                                    # Heun: 7 evaluations
+    st = m.engine().stream
+    st.wait_stream(torch.cuda.current_stream())
+    kept = []
+
+    def new_handle(s):
+        m._handle = None                                                   # m.handle() builds another one over the same prepared weights
+        h = m.handle()
+        kept.append(h)
+        h.set_adaptive(True)
+        h.set_sde(True)
+        h.prepare(kw["txt"], kw["y"], kw["guidance"], False, kw["img_ids"], kw["txt_ids"], 16, stream=s)
+        return h
+
+    def run(h, mode, s):
+        x = x0.clone()
+        if mode == "dopri5":
+            h.sample_dopri5(x, kw["cond"], t, True, s, rtol=1e-2, atol=1e-3, max_attempts=200)
+        elif mode == "sde_heun":
+            h.sample_sde("Heun", x, kw["cond"], t_sde, True, s, form="sigma", norm=0.7, last_step="Mean", last_step_size=0.25, seed=3)
+        elif mode == "cfg":
+            h.set_cfg(2.5)
+            h.sample_ode("euler", x, kw["cond"], t, True, s)
+            h.set_cfg(None)
+        else:
+            h.sample_ode(mode, x, kw["cond"], t, True, s)
+        return x, (None if mode in ("dopri5", "sde_heun") else h.step_nodes())
+
+    try:
+        with torch.cuda.stream(st):
+            s = st.cuda_stream
+            one = new_handle(s)
+            got = {}
+            for i, mode in enumerate(("euler", "dopri5", "rk4", "sde_heun", "cfg", "refused_sde", "refused_dopri5", "midpoint", "euler")):
+                if mode == "refused_sde":
+                    with pytest.raises(hip.VclozeHipError, match=r"\(-1\).*evaluations"):   # 19 evaluations, 16 prepared
+                        one.sample_sde("Heun", x0.clone(), kw["cond"], torch.linspace(0, 0.75, 10), True, s, form="sigma", norm=0.7,
+                                       last_step="Mean", last_step_size=0.25, seed=3)
+                elif mode == "refused_dopri5":
+                    with pytest.raises(hip.VclozeHipError, match=r"\(-1\).*increase strictly"):
+                        one.sample_dopri5(x0.clone(), kw["cond"], torch.tensor([0.0, 0.5, 0.5, 1.0]), True, s)
+                else:
+                    got[i, mode] = run(one, mode, s)
+            want = {mode: run(new_handle(s), mode, s) for mode in ("euler", "dopri5", "rk4", "sde_heun", "cfg", "midpoint")}
+        torch.cuda.synchronize()
+    finally:
+        m._handle = None                                                   # the module's model builds its own handle again
+    for (i, mode), (x, nodes) in got.items():
+        assert torch.isfinite(x.float()).all() and not torch.equal(x, x0), mode
+        assert torch.equal(x, want[mode][0]), (i, mode)
+        assert nodes == want[mode][1], (i, mode, nodes, want[mode][1])
+    assert torch.equal(got[8, "euler"][0], got[0, "euler"][0])
+    finals = [want[mode][0] for mode in ("euler", "dopri5", "rk4", "sde_heun", "cfg", "midpoint")]
+    assert all(not torch.equal(a, b) for i, a in enumerate(finals) for b in finals[i + 1:])       # six different samplers
+
+
 def test_pipeline_passes_the_solver_through(model):
     """generate_grid(..., solver=) reaches Sampler.sample_ode through denoise_grid: rk4 runs end to end and is not Euler."""
     from tests.procedural import tiny_inputs

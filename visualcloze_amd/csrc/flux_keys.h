@@ -1,5 +1,5 @@
 // The state_dict() keys a VcFluxConfig implies (FluxLoraWrapper, models/model.py:154-175: Flux with a LoRA pair on every Linear),
-// their shapes, and what vc_flux_load_* needs to know about each.  Host code only, nothing from HIP: flux_engine.hip uses it for
+// their shapes, and what vc_flux_load_* needs to know about each.  Host code only, nothing from HIP: flux_weights.hip uses it for
 // vc_flux_load_key / vc_flux_load_tensor / vc_flux_load_bytes / vc_flux_load_finish, tests/c_abi/flux_keys_check.cpp runs it alone.
 #pragma once
 #include <stdint.h>

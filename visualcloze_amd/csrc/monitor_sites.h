@@ -1,6 +1,6 @@
 // The sites of the Flux handle's numerics monitor (vc_flux_set_monitor) and the arithmetic of its log: which residual stream is tap /
 // site number what, how many bytes a log takes and where the VcStat of (evaluation, site, sample) lies.  Host code only, nothing from
-// HIP: flux_engine.hip uses it for the taps (vc_flux_set_tap) and the monitor alike - ONE enumeration -, tests/c_abi/monitor_check.cpp
+// HIP: flux_engine.hip (through flux_rules.h) uses it for the taps (vc_flux_set_tap) and the monitor alike - ONE enumeration -, tests/c_abi/monitor_check.cpp
 // runs it alone under the sanitizers.
 #pragma once
 #include <stdint.h>

@@ -150,7 +150,8 @@ int vc_time_grid_impl(int32_t n_points, int32_t n_tokens, double t0, double t1, 
 int64_t vc_grid_tokens_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, char* err, int errlen);
 int vc_grid_img_ids_impl(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, float* out, char* err, int errlen);
 
-// flux_engine.hip: the handle API
+// the Flux handle API: flux_weights.hip (create, bind_*, bound, mod_offset, set_lora_scale, load_*), flux_sample.hip (sample_*,
+// dopri5_log, set_step_cache, set_cfg, step_cache_stats), flux_engine.hip (the rest)
 const VcFluxConfig* vc_flux_config_impl(void* handle);
 int vc_flux_create_impl(const VcFluxConfig* cfg, void** handle, char* err, int errlen);
 int vc_flux_destroy_impl(void* handle, char* err, int errlen);

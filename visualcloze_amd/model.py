@@ -544,10 +544,10 @@ class Flux(nn.Module):
         # worth (1 + 2^-9)^6 = 1.012 on the product; the kernel only compares the bound with its <= 100 cutoff)
         # The bound is kept per BLOCK (a double block: both streams share one attention): each launch gets its own, so outlier
         # scales in a few blocks of a checkpoint cost the running-max template there and nowhere else; `logit_bound` = the
-        # largest of them, the cap handed to the C handle (which computes the per-block values itself: flux_engine.hip resolve()).
+        # largest of them, the cap handed to the C handle (which computes the per-block values itself: flux_weights.hip resolve()).
         amax = {n: float(t.float().abs().max()) for n, t in w.items() if n.endswith(("query_norm.scale", "key_norm.scale"))}
         blocks = sorted({n.split(".img_attn.")[0].split(".txt_attn.")[0].split(".norm.")[0] for n in amax})
-        c_log = 1.02 * 11.313708498984761 * 1.4426950408889634          # 1.02 sqrt(128) log2(e), the constant of flux_engine.hip
+        c_log = 1.02 * 11.313708498984761 * 1.4426950408889634          # 1.02 sqrt(128) log2(e), the constant of csrc/flux_rules.h
         logit_bounds = {}
         for pf in blocks:
             qm = max(v for n, v in amax.items() if n.startswith(pf + ".") and n.endswith("query_norm.scale"))
