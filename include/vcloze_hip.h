@@ -453,11 +453,12 @@ int vc_unpack_latent(const void* tokens, int64_t ld, int32_t col0, void* latent,
 
 /* ---- noise source: a counter-based Gaussian stream of this library's own (csrc/rng.hip) ----
  * The reference draws its noise with torch.randn(generator=...) (visualcloze.py:217,394-399) and torch.randn_like (autoencoder.py:272);
- * torch's device stream depends on the grid torch picks from the device's properties and cannot be restated by a host without
- * torch.  This stream can: every element depends on (seed, position) ONLY - not on the launch geometry, not on how a draw is
- * split into calls, not on the memory layout it is written in.  It is NOT torch's stream: a seed here does not reproduce the
- * images torch's generator gives for the same seed.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect these entry
- * points by SYMBOL - look up vc_randn.
+ * torch's device stream depends on the grid torch picks from the device's properties and on how a run is split into draws.
+ * This stream does not: every element depends on (seed, position) ONLY - not on the launch geometry, not on how a draw is
+ * split into calls, not on the memory layout it is written in.  It is the DEFAULT stream of the C entry points and differs from
+ * torch's: a seed here does not reproduce the images torch's generator gives for the same seed.  torch's stream is the opt-in
+ * second source below (vc_randn_torch, THE TORCH STREAM; vc_grid_set_noise).  Added WITHOUT a change of VC_ABI_VERSION (tests pin
+ * 11): detect these entry points by SYMBOL - look up vc_randn.
  *
  * THE STREAM (the contract).  Element at stream position p = offset + i, offset a uint64, offset + n does not wrap:
  *   block    b = p >> 2
@@ -491,6 +492,58 @@ int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset
  * ld / col0 / alignment rules (even C, h, w; ld and col0 multiples of 8; 16-byte aligned token base).  Bit-identical to a
  * VC_RNG_BF16 draw of C*h*w elements into [C, h, w] followed by vc_pack_latent. */
 int vc_randn_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t offset, void* stream);
+
+/* ---- noise source, opt-in: torch's device generator stream (csrc/rng_torch.hip) ----
+ * What G = torch.Generator(device).manual_seed(seed); torch.randn(n, device=device, generator=G) stores, restated: a seed then gives
+ * the images the reference (visualcloze.py:217,394-399) and this package's default path give for it.  The stream is a pure
+ * function of six quantities: the seed, the generator's Philox offset, the element count and three integers of the device - torch's
+ * block size 256, the multiprocessor count and the threads per multiprocessor.  The library reads the last two from the current
+ * device (pass 0) or takes them from the caller, who then needs no GPU to know the geometry (vc_torch_randn_policy) and gets one
+ * machine's noise on another.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect by symbol: look up vc_randn_torch.
+ * Parity is with the torch build this library is tested against (2.10 / ROCm 7; ATen/native/hip/DistributionTemplates.h,
+ * rocrand_philox4x32_10.h, rocrand_normal.h): another torch may lay its stream out differently, THE CONTRACT BELOW is what this
+ * library guarantees.  torch splits a tensor it cannot index in 32 bits into several draws: parity holds for n < 2^31.
+ *
+ * THE TORCH STREAM (the contract).  A draw of n elements, 1 <= n <= 2^48, at seed s and offset o; o is a multiple of 4 and counts
+ * Philox outputs per thread, as torch.Generator.get_offset() reports it.  The grid:
+ *   cap = sm_count * (threads_per_sm / 256)   (integer division; 1 <= cap < 2^31)
+ *   G   = min(ceil(n / 256), cap)             T = 256 G
+ * Element i belongs to thread i mod T, lane (i div T) mod 4, round i div (4 T).  Its Philox4x32-10 block (the rounds, multipliers
+ * and known answers of THE STREAM above) has
+ *   counter  (lo32(c), hi32(c), lo32(thread), hi32(thread)),  c = o / 4 + round
+ *   key      (lo32(s), hi32(s))
+ * which is where rocrand_init(seed, subsequence = thread, offset = o) and one rocrand_normal4 per round put them.  With x0..x3 the
+ * block's words, in f32:
+ *   u = 2^-32 + f32(x0) * 2^-32 in (0, 1],   v = k + f32(x1) * k in (0, 2 pi],  k = f32(2^-32) * f32(2 pi)
+ *   r = sqrt(-2 ln u),  z0 = r sin(v),  z1 = r cos(v);  z2, z3 the same from x2, x3       (SINE FIRST; cuRAND's order differs)
+ * Element i is z[lane], stored as z + 0 (torch's z * std + mean: a negative zero becomes +0).  The operations, as the kernel torch
+ * ships performs them: u and v are ONE fma each; ln u = t + fma(m, L2, fma(m, L1, -t)) with m = log2 u from the hardware (v_log_f32),
+ * t = m * L1, L1 = 0x1.62e42ep-1, L2 = 0x1.efa39ep-25 (ln 2 in two words; the two parts ADDED, not fused); -2 * ln u; a correctly
+ * rounded sqrt; sin / cos the hardware's fast ones on v / (2 pi) (rocrand's __sincosf: v_sin_f32 / v_cos_f32); one product each.
+ * Nothing else is contracted.  VC_RNG_U32 words are exact for any restatement; the normals are bit-equal to torch's on the device
+ * (tests/test_torch_noise_gpu.py: 0 differing elements, f32 and bf16, at every tested size and seed), a host restatement agrees
+ * to the hardware approximations' error only.
+ * After the draw the offset stands at o + ((n - 1) div (4 T) + 1) * 4.  Draws of more than 256 * cap elements depend on the
+ * device's two integers (MI355X: 256 and 2048, cap 2048, 524288 elements); the start state of a 1024 x 3456 grid, 221184
+ * elements, does not.  VC_RNG_BF16 is the f32 normal rounded to nearest-even, torch.randn(f32).to(bf16) - the only bf16 form promised
+ * (torch.randn(dtype=bfloat16) is not restated). */
+/* Host only: torch's grid G and the advance of the offset for a draw of n elements.  sm_count / threads_per_sm: the two device
+ * integers, each 0 = the current device's - only then is a device needed, VC_ERR_HIP without one.  VC_ERR_ARG: null result
+ * pointer, n outside 1 .. 2^48, sm_count < 0, threads_per_sm in 1 .. 255, a cap outside 1 .. 2^31 - 1. */
+int vc_torch_randn_policy(int64_t n, int32_t sm_count, int32_t threads_per_sm, int32_t* grid, uint64_t* offset_advance);
+/* out[i] = element i of the draw (seed, philox_offset, n) of THE TORCH STREAM, dtype VC_RNG_BF16 / VC_RNG_F32 / VC_RNG_U32 (the raw
+ * word x[lane], before the transform).  A function of the contract only: the launch geometry does not show.  Any base aligned to
+ * the element size; 16-byte stores where the base is 16-byte aligned.  seed and philox_offset are by-value kernel arguments, as in
+ * vc_randn: legal under stream capture, and a replayed graph repeats its noise.  The CALLER advances its offset (vc_torch_randn_policy).
+ * Arguments are checked before the device is touched (VC_ERR_ARG: null pointer, n <= 0 or > 2^48, unknown dtype, philox_offset not a
+ * multiple of 4, philox_offset + advance wrapping, misaligned base, sm_count < 0, an explicit threads_per_sm < 256). */
+int vc_randn_torch(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t philox_offset, int32_t sm_count, int32_t threads_per_sm,
+                   void* stream);
+/* The start state in one launch: element (c, y, x) of a [C, h, w] draw is element i = (c*h + y)*w + x of the draw of n = C*h*w,
+ * written as bf16 into the packed-token layout under vc_randn_tokens' rules.  Bit-identical to a VC_RNG_BF16 vc_randn_torch of
+ * C*h*w elements into [C, h, w] followed by vc_pack_latent. */
+int vc_randn_torch_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t philox_offset,
+                          int32_t sm_count, int32_t threads_per_sm, void* stream);
 
 /* ---- VAE decoder glue (reference twin models/modules/autoencoder.py): activations are NHWC bf16
  * [H*W, C], C % 8 == 0; the 3x3 convolutions and 1x1 projections themselves are vc_gemm over these buffers. ----
@@ -1161,6 +1214,17 @@ void vc_grid_struct_sizes(int32_t out[3]);
 /* host-only */
 int vc_grid_create(const VcGridConfig* cfg, void** handle);
 int vc_grid_destroy(void* handle);
+/* The noise source of the handle's jobs.  VC_NOISE_OWN (the default): seed / noise_offset / noise_offset_out of VcGridJob,
+ * VcGridSdedit, VcGridPhotos and VcGridSdeditU8 are the library's own stream, as their comments say.  VC_NOISE_TORCH: they are the
+ * torch generator's seed and Philox offset (a multiple of 4), and every draw of vc_grid_generate, vc_grid_sdedit,
+ * vc_grid_generate_photos and vc_grid_sdedit_u8 is the draw of THE TORCH STREAM (vc_randn_torch VC_RNG_BF16, vc_randn_torch_tokens)
+ * in the same order, the offset advancing per draw as torch's does: the parity twin is pipeline.generate_grid / upsample_images with
+ * rng = TorchNoiseStream(seed).  sm_count / threads_per_sm as in vc_randn_torch (0 = the device's, read when a job runs).  No struct
+ * changes; added WITHOUT a change of VC_ABI_VERSION: look up vc_randn_torch.  Host-only.  VC_ERR_ARG: null handle, unknown source,
+ * sm_count < 0, threads_per_sm in 1 .. 255. */
+#define VC_NOISE_OWN 0
+#define VC_NOISE_TORCH 1
+int vc_grid_set_noise(void* handle, int32_t source, int32_t sm_count, int32_t threads_per_sm);
 /* The bytes vc_grid_generate (vc_grid_sdedit) needs for this job: the sub-handles' own *_workspace_bytes (the autoencoder at the
  * job's largest row, both halves; T5 and CLIP at the ids' lengths; Flux at B = 1 - the sdedit job: min(count, VC_GRID_SDEDIT_CHUNK) -
  * and max_evals) plus the intermediates (cond, the state, the prompt embeddings, staged pixels).  Host-only; the job is checked as

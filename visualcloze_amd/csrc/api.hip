@@ -232,6 +232,17 @@ int vc_randn(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t offset
 int vc_randn_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t offset, void* stream) {
   return vc_randn_tokens_launch(tokens, C, h, w, ld, col0, seed, offset, S(stream), ERRBUF);
 }
+int vc_torch_randn_policy(int64_t n, int32_t sm_count, int32_t threads_per_sm, int32_t* grid, uint64_t* offset_advance) {
+  return vc_torch_randn_policy_impl(n, sm_count, threads_per_sm, grid, offset_advance, ERRBUF);
+}
+int vc_randn_torch(void* out, int32_t dtype, int64_t n, uint64_t seed, uint64_t philox_offset, int32_t sm_count, int32_t threads_per_sm,
+                   void* stream) {
+  return vc_randn_torch_launch(out, dtype, n, seed, philox_offset, sm_count, threads_per_sm, S(stream), ERRBUF);
+}
+int vc_randn_torch_tokens(void* tokens, int32_t C, int32_t h, int32_t w, int64_t ld, int32_t col0, uint64_t seed, uint64_t philox_offset,
+                          int32_t sm_count, int32_t threads_per_sm, void* stream) {
+  return vc_randn_torch_tokens_launch(tokens, C, h, w, ld, col0, seed, philox_offset, sm_count, threads_per_sm, S(stream), ERRBUF);
+}
 
 /* ---- handle API (flux_engine.hip) ---- */
 int vc_flux_create(const VcFluxConfig* cfg, void** handle) { return vc_flux_create_impl(cfg, handle, ERRBUF); }
@@ -393,6 +404,9 @@ void vc_grid_struct_sizes(int32_t out[3]) {
 }
 int vc_grid_create(const VcGridConfig* cfg, void** handle) { return vc_grid_create_impl(cfg, handle, ERRBUF); }
 int vc_grid_destroy(void* handle) { return vc_grid_destroy_impl(handle, ERRBUF); }
+int vc_grid_set_noise(void* handle, int32_t source, int32_t sm_count, int32_t threads_per_sm) {
+  return vc_grid_set_noise_impl(handle, source, sm_count, threads_per_sm, ERRBUF);
+}
 int vc_grid_workspace_bytes(void* handle, const VcGridJob* job, int64_t* bytes) { return vc_grid_workspace_bytes_impl(handle, job, bytes, ERRBUF); }
 int vc_grid_sdedit_workspace_bytes(void* handle, const VcGridSdedit* job, int64_t* bytes) {
   return vc_grid_sdedit_workspace_bytes_impl(handle, job, bytes, ERRBUF);

@@ -2,7 +2,8 @@
 // VisualClozeModel.process_images (visualcloze.py:363-434) and of `upsampling` (:184-240) as ONE call each.  Host code only: it
 // COMPOSES the library's own entry points - vc_randn / vc_randn_tokens, the autoencoder, text-encoder and Flux handles, vc_pack_mask,
 // vc_sdedit_mix, vc_time_grid, vc_grid_img_ids, vc_pixels_out - in the order visualcloze_amd/pipeline.py composes them
-// (generate_grid with rng = NoiseStream(seed), upsample_images): the parity twin, same kernels, same operands, same bits.  The four
+// (generate_grid with rng = NoiseStream(seed), upsample_images): the parity twin, same kernels, same operands, same bits.  With
+// vc_grid_set_noise(VC_NOISE_TORCH) the draws are vc_randn_torch / vc_randn_torch_tokens instead (twin: rng = TorchNoiseStream(seed)).  The four
 // sub-handles are BORROWED; their plan caches keep the captured graphs, this file captures nothing itself.
 //
 // Workspace (caller's device memory), carved in this order; tok = image tokens of the job, C = Flux out_channels (= 4 z), CW =
@@ -28,6 +29,7 @@ namespace {
 struct Grid {
   void *flux = nullptr, *vae = nullptr, *t5 = nullptr, *clip = nullptr;
   int z = 0, C = 0, CW = 0, ctx = 0, vec = 0;
+  int noise = VC_NOISE_OWN, sm_count = 0, threads_per_sm = 0;      // vc_grid_set_noise
 };
 
 // what both kinds of job come down to
@@ -41,8 +43,17 @@ struct Geo {
   int64_t N = 0;                       // image tokens per sample
   int T = 0, clipL = 0, evals = 0, max_evals = 0, pix_f32 = 0, out_form = 0, n_points = 0, method = 0;
   int Hmax = 0, Wmax = 0;              // the item with the most pixels
-  uint64_t draws = 0;                  // stream positions the job consumes
+  uint64_t draws = 0;                  // stream positions the job consumes (VC_NOISE_TORCH: what the generator's offset advances by)
+  int sm = 0, tpsm = 0;                // VC_NOISE_TORCH: the grid cap's factors, the device's where the handle holds 0
 };
+
+// the stretch of the noise stream a draw of n elements takes: n positions of the library's own, torch's advance of the offset
+int draw_span(const Grid& g, const Geo& q, int64_t n, uint64_t* span, Err e) {
+  *span = (uint64_t)n;
+  if (g.noise != VC_NOISE_TORCH) return VC_OK;
+  int32_t grid = 0;
+  return vc_torch_randn_policy_impl(n, q.sm, q.tpsm, &grid, span, e.buf, e.len);
+}
 
 struct Bufs {
   char *vae = nullptr, *t5 = nullptr, *clip = nullptr, *flux = nullptr, *pin = nullptr;
@@ -78,6 +89,11 @@ int check_common(const Grid& g, Geo& q, const void* const* pixels, const int32_t
   if (!q.max_evals) q.max_evals = q.evals;
   q.total = 0;
   q.draws = 0;
+  if (g.noise == VC_NOISE_TORCH) {
+    if (offset & 3) FAIL(VC_ERR_ARG, "%s: noise_offset = %llu is not a multiple of 4 (VC_NOISE_TORCH: torch.Generator.get_offset())", what, (unsigned long long)offset);
+    q.sm = g.sm_count; q.tpsm = g.threads_per_sm;
+    TRY(vc_torch_caps_resolve(what, &q.sm, &q.tpsm, e.buf, e.len));
+  }
   int64_t best = 0;
   for (int i = 0; i < q.items; ++i) {
     const int H = q.H[i], W = q.W[i];
@@ -88,7 +104,9 @@ int check_common(const Grid& g, Geo& q, const void* const* pixels, const int32_t
     q.tok[i] = (int64_t)(H / 16) * (W / 16);
     q.total += q.tok[i];
     // generate: encode draw + start noise; sdedit: encode(image), encode(blank), start noise - z * h * w = C/4 * 4 tok elements each
-    q.draws += (uint64_t)(q.sdedit ? 3 : 2) * (uint64_t)g.C * (uint64_t)q.tok[i];
+    uint64_t span = 0;
+    TRY(draw_span(g, q, (int64_t)g.C * q.tok[i], &span, e));
+    q.draws += (uint64_t)(q.sdedit ? 3 : 2) * span;
     if ((int64_t)H * W > best) { best = (int64_t)H * W; q.Hmax = H; q.Wmax = W; }
   }
   if (q.total > 0x7fffffff / 4) FAIL(VC_ERR_ARG, "%s: %lld image tokens are too many", what, (long long)q.total);
@@ -205,8 +223,11 @@ int encode_prompt(const Grid& g, const Geo& q, const Bufs& b, const int32_t* t5_
 int encode_item(const Grid& g, const Geo& q, const Bufs& b, int H, int W, const void* pixels, bool staged, bf16_t* tokens, int64_t ld,
                 uint64_t seed, uint64_t& pos, hipStream_t s, Err e) {
   const int64_t n = (int64_t)g.z * (H / 8) * (W / 8);
-  TRY(vc_randn_launch(b.enoise, VC_RNG_BF16, n, seed, pos, s, e.buf, e.len));
-  pos += (uint64_t)n;
+  uint64_t span = 0;
+  TRY(draw_span(g, q, n, &span, e));
+  if (g.noise == VC_NOISE_TORCH) TRY(vc_randn_torch_launch(b.enoise, VC_RNG_BF16, n, seed, pos, q.sm, q.tpsm, s, e.buf, e.len));
+  else TRY(vc_randn_launch(b.enoise, VC_RNG_BF16, n, seed, pos, s, e.buf, e.len));
+  pos += span;
   const void* src = pixels;
   if (staged) {
     HIP(hipMemcpyAsync(b.pin, pixels, (size_t)3 * H * W * (q.pix_f32 ? 4 : 2), hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(pixels)");
@@ -214,6 +235,16 @@ int encode_item(const Grid& g, const Geo& q, const Bufs& b, int H, int W, const 
   }
   TRY(vc_vae_prepare_impl(g.vae, H, W, VC_VAE_ENCODER | VC_VAE_DECODER, b.vae, b.vae_b, s, e.buf, e.len));
   return vc_vae_encode_impl(g.vae, src, staged ? q.pix_f32 : 0, b.enoise, tokens, VC_VAE_TOKENS, ld, 0, s, e.buf, e.len);
+}
+
+// the start noise of one item, [z, H/8, W/8], straight into token rows
+int start_noise(const Grid& g, const Geo& q, bf16_t* tokens, int H, int W, uint64_t seed, uint64_t& pos, hipStream_t s, Err e) {
+  uint64_t span = 0;
+  TRY(draw_span(g, q, (int64_t)g.z * (H / 8) * (W / 8), &span, e));
+  if (g.noise == VC_NOISE_TORCH) TRY(vc_randn_torch_tokens_launch(tokens, g.z, H / 8, W / 8, g.C, 0, seed, pos, q.sm, q.tpsm, s, e.buf, e.len));
+  else TRY(vc_randn_tokens_launch(tokens, g.z, H / 8, W / 8, g.C, 0, seed, pos, s, e.buf, e.len));
+  pos += span;
+  return VC_OK;
 }
 
 // AutoEncoder.decode from the sampler's token rows, then the pixel epilogue into the caller's buffer
@@ -272,6 +303,16 @@ int vc_grid_destroy_impl(void* handle, char* err, int errlen) {
   return VC_OK;
 }
 
+int vc_grid_set_noise_impl(void* handle, int source, int sm_count, int threads_per_sm, char* err, int errlen) {
+  HANDLE(Grid, g, "grid");
+  if (source != VC_NOISE_OWN && source != VC_NOISE_TORCH) FAIL(VC_ERR_ARG, "grid_set_noise: unknown source %d (VC_NOISE_OWN, VC_NOISE_TORCH)", source);
+  if (sm_count < 0 || (threads_per_sm != 0 && threads_per_sm < 256))
+    FAIL(VC_ERR_ARG, "grid_set_noise: sm_count = %d, threads_per_sm = %d: 0 (the current device's) or a positive count / at least 256 expected", sm_count,
+         threads_per_sm);
+  g.noise = source; g.sm_count = sm_count; g.threads_per_sm = threads_per_sm;
+  return VC_OK;
+}
+
 int vc_grid_workspace_bytes_impl(void* handle, const VcGridJob* job, int64_t* bytes, char* err, int errlen) {
   HANDLE(Grid, g, "grid");
   if (!bytes) FAIL(VC_ERR_ARG, "grid_workspace_bytes: null result pointer");
@@ -312,8 +353,7 @@ int vc_grid_generate_impl(void* handle, const VcGridJob* job, void* workspace, i
   }
   row0 = 0;
   for (int i = 0; i < q.items; ++i) {          // :394-399 the start noise, row by row
-    TRY(vc_randn_tokens_launch(b.x + row0 * g.C, g.z, q.H[i] / 8, q.W[i] / 8, g.C, 0, job->seed, pos, s, err, errlen));
-    pos += (uint64_t)g.z * (q.H[i] / 8) * (q.W[i] / 8);
+    TRY(start_noise(g, q, b.x + row0 * g.C, q.H[i], q.W[i], job->seed, pos, s, e));
     row0 += q.tok[i];
   }
   TRY(encode_prompt(g, q, b, job->t5_ids, job->clip_ids, s, e));
@@ -353,8 +393,7 @@ int vc_grid_sdedit_impl(void* handle, const VcGridSdedit* job, void* workspace, 
     TRY(encode_item(g, q, b, H, W, job->pixels[k], true, b.lat + k * n * g.C, g.C, job->seed, pos, s, e));
     TRY(encode_item(g, q, b, H, W, b.zero, false, cond, g.CW, job->seed, pos, s, e));
     TRY(vc_pack_mask_launch(b.ones, cond, H, W, g.CW, g.C, s, err, errlen));
-    TRY(vc_randn_tokens_launch(b.noise + k * n * g.C, g.z, lh, lw, g.C, 0, job->seed, pos, s, err, errlen));
-    pos += (uint64_t)g.z * lh * lw;
+    TRY(start_noise(g, q, b.noise + k * n * g.C, H, W, job->seed, pos, s, e));
   }
   TRY(vc_sdedit_mix_launch(b.noise, b.lat, job->strength, b.x, (int64_t)K * n * g.C, s, err, errlen));     // :221, all targets at once
   TRY(encode_prompt(g, q, b, job->t5_ids, job->clip_ids, s, e));

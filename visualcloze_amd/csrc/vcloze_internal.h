@@ -129,6 +129,14 @@ int vc_scale_cast_launch(const VcScaleVectors& v, int n, void* out, int64_t out_
 int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen);
 int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
                            int errlen);
+// rng_torch.hip: torch's device generator stream.  vc_torch_caps_resolve checks (sm_count, threads_per_sm) and replaces each 0 by the
+// current device's value (VC_ERR_HIP without a device)
+int vc_torch_caps_resolve(const char* who, int* sm_count, int* threads_per_sm, char* err, int errlen);
+int vc_torch_randn_policy_impl(int64_t n, int sm_count, int threads_per_sm, int32_t* grid, uint64_t* offset_advance, char* err, int errlen);
+int vc_randn_torch_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, int sm_count, int threads_per_sm, hipStream_t s,
+                          char* err, int errlen);
+int vc_randn_torch_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, int sm_count,
+                                 int threads_per_sm, hipStream_t s, char* err, int errlen);
 int vc_pixels_out_launch(const void* img, int img_is_f32, int H, int W, int x0, int w, void* out, int out_form, hipStream_t s, char* err,
                          int errlen);
 // resample.hip, pixels_in.hip: the photo front end's kernels
@@ -228,6 +236,7 @@ const VcTextConfig* vc_text_config_impl(void* handle);
 // grid_engine.hip: the grid handle
 int vc_grid_create_impl(const VcGridConfig* cfg, void** handle, char* err, int errlen);
 int vc_grid_destroy_impl(void* handle, char* err, int errlen);
+int vc_grid_set_noise_impl(void* handle, int source, int sm_count, int threads_per_sm, char* err, int errlen);
 int vc_grid_workspace_bytes_impl(void* handle, const VcGridJob* job, int64_t* bytes, char* err, int errlen);
 int vc_grid_sdedit_workspace_bytes_impl(void* handle, const VcGridSdedit* job, int64_t* bytes, char* err, int errlen);
 int vc_grid_generate_impl(void* handle, const VcGridJob* job, void* workspace, int64_t workspace_bytes, void* const* out_rows, hipStream_t s,

@@ -862,6 +862,13 @@ class GridHandle(_Handle):
         self._ws: Optional[torch.Tensor] = None
         self._side = None
 
+    def set_noise(self, source="own", sm_count: int = 0, threads_per_sm: int = 0) -> None:
+        """vc_grid_set_noise: "own" (the default) - `seed` / `noise_offset` of every job are the library's stream (`pipeline.NoiseStream`);
+        "torch" - they are a torch generator's seed and Philox offset, every draw is torch's (`pipeline.TorchNoiseStream`).
+        sm_count / threads_per_sm: another device's properties, 0 = this device's."""
+        src = {"own": hip.NOISE_OWN, "torch": hip.NOISE_TORCH}.get(source, source)
+        hip._check(hip.lib().vc_grid_set_noise(self.h, int(src), int(sm_count), int(threads_per_sm)), "vc_grid_set_noise")
+
     def _workspace(self, need: int) -> Tuple[int, int]:
         if self._ws is None or self._aligned(self._ws)[1] < need:
             self._ws = None

@@ -255,6 +255,9 @@ SYMBOLS = {
     "vc_gaussian_sample": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp]),
     "vc_randn": (C.c_int, [_vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp]),
     "vc_randn_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, C.c_uint64, C.c_uint64, _vp]),
+    "vc_torch_randn_policy": (C.c_int, [_i64, _i32, _i32, C.POINTER(_i32), C.POINTER(C.c_uint64)]),
+    "vc_randn_torch": (C.c_int, [_vp, _i32, _i64, C.c_uint64, C.c_uint64, _i32, _i32, _vp]),
+    "vc_randn_torch_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, C.c_uint64, C.c_uint64, _i32, _i32, _vp]),
     "vc_lora_merge": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vc_lora_merge_qkv": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, C.c_float, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
                                     _vp]),
@@ -321,6 +324,7 @@ SYMBOLS = {
     "vc_grid_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "vc_grid_create": (C.c_int, [C.POINTER(GridConfig), C.POINTER(_vp)]),
     "vc_grid_destroy": (C.c_int, [_vp]),
+    "vc_grid_set_noise": (C.c_int, [_vp, _i32, _i32, _i32]),
     "vc_grid_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridJob), C.POINTER(_i64)]),
     "vc_grid_sdedit_workspace_bytes": (C.c_int, [_vp, C.POINTER(GridSdedit), C.POINTER(_i64)]),
     "vc_grid_generate": (C.c_int, [_vp, C.POINTER(GridJob), _vp, _i64, C.POINTER(_vp), _vp]),
@@ -1186,7 +1190,7 @@ def upsampling_size(target_size):
     return a.value, b.value
 
 
-# ---- noise source (csrc/rng.hip): the library's own counter-based Gaussian stream, NOT torch's ----
+# ---- noise source (csrc/rng.hip): the library's own counter-based Gaussian stream (torch's is `randn_torch` below) ----
 RNG_BF16, RNG_F32, RNG_U32 = 0, 1, 2                        # VC_RNG_*
 RNG_MAX_BLOCKS = 2048                                       # workgroups of 256 threads per launch; a grid-stride loop takes the rest
 _RNG_DTYPES = {torch.bfloat16: RNG_BF16, torch.float32: RNG_F32, torch.int32: RNG_U32}
@@ -1231,6 +1235,52 @@ def randn_tokens(C_, h, w, seed, offset=0, tokens=None, col0=0, device=None, str
         raise VclozeHipError(f"randn_tokens: the tensor is on {tokens.device}, the current stream on cuda:{torch.cuda.current_device()}")
     _check(lib().vc_randn_tokens(tokens.data_ptr(), C_, h, w, tokens.stride(0), col0, _u64(seed, "seed"), _u64(offset, "offset"),
                                  stream if stream is not None else cur_stream()), "vc_randn_tokens")
+    return tokens
+
+
+# ---- noise source, opt-in (csrc/rng_torch.hip): torch's device generator stream, bit for bit ----
+NOISE_OWN, NOISE_TORCH = 0, 1                               # VC_NOISE_*
+
+
+def torch_randn_policy(n, sm_count=0, threads_per_sm=0):
+    """vc_torch_randn_policy (host-only): (G, advance) - the blocks of 256 threads torch.randn launches for n elements on a device of
+    `sm_count` multiprocessors and `threads_per_sm` threads each, and what the generator's Philox offset advances by.  0 = the
+    current device's value (only then is a device needed)."""
+    g, adv = C.c_int32(0), C.c_uint64(0)
+    _check(lib().vc_torch_randn_policy(int(n), int(sm_count), int(threads_per_sm), C.byref(g), C.byref(adv)), "vc_torch_randn_policy")
+    return g.value, adv.value
+
+
+def randn_torch(shape, seed, offset=0, dtype=torch.bfloat16, device=None, sm_count=0, threads_per_sm=0, out=None, stream=None):
+    """vc_randn_torch: what torch.randn(shape, device=device, generator=G) gives for a generator of `seed` standing at Philox offset
+    `offset` (a multiple of 4, `G.get_offset()`), bit for bit (include/vcloze_hip.h, THE TORCH STREAM).  dtype: torch.float32,
+    torch.bfloat16 (= the f32 draw .to(bfloat16)), or torch.int32 = the raw Philox words.  The caller advances its offset
+    (`torch_randn_policy`).  sm_count / threads_per_sm: another device's properties instead of the current one's."""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device if device is not None else "cuda")
+    elif shape is not None and tuple(out.shape) != tuple(shape):
+        raise VclozeHipError(f"randn_torch: out has shape {tuple(out.shape)}, not {tuple(shape)}")
+    if out.dtype not in _RNG_DTYPES or not out.is_cuda or not out.is_contiguous():
+        raise VclozeHipError(f"randn_torch: a contiguous CUDA bf16 / f32 / int32 tensor expected, got {out.dtype} on {out.device}")
+    if out.device.index != torch.cuda.current_device():          # the grid cap is the CURRENT device's
+        raise VclozeHipError(f"randn_torch: the tensor is on {out.device}, the current device is cuda:{torch.cuda.current_device()}")
+    _check(lib().vc_randn_torch(out.data_ptr(), _RNG_DTYPES[out.dtype], out.numel(), _u64(seed, "seed"), _u64(offset, "offset"),
+                                int(sm_count), int(threads_per_sm), stream if stream is not None else cur_stream()), "vc_randn_torch")
+    return out
+
+
+def randn_torch_tokens(C_, h, w, seed, offset=0, tokens=None, col0=0, device=None, sm_count=0, threads_per_sm=0, stream=None):
+    """vc_randn_torch_tokens: the [C_, h, w] draw of `randn_torch` written as bf16 into tokens[:, col0:col0+4C_] in pack_latent's
+    layout, in one launch; `tokens` as in `randn_tokens`.  Returns tokens."""
+    if tokens is None:
+        tokens = torch.empty((h // 2) * (w // 2), col0 + 4 * C_, dtype=torch.bfloat16, device=device if device is not None else "cuda")
+    _bf16(tokens, "tokens")
+    if tokens.dim() != 2 or tokens.stride(1) != 1 or tokens.shape[0] != (h // 2) * (w // 2) or tokens.shape[1] < col0 + 4 * C_:
+        raise VclozeHipError(f"randn_torch_tokens: [(h/2)(w/2), >= col0 + 4C] token rows with contiguous last dim expected, got {tuple(tokens.shape)}")
+    if tokens.device.index != torch.cuda.current_device():
+        raise VclozeHipError(f"randn_torch_tokens: the tensor is on {tokens.device}, the current device is cuda:{torch.cuda.current_device()}")
+    _check(lib().vc_randn_torch_tokens(tokens.data_ptr(), C_, h, w, tokens.stride(0), col0, _u64(seed, "seed"), _u64(offset, "offset"),
+                                       int(sm_count), int(threads_per_sm), stream if stream is not None else cur_stream()), "vc_randn_torch_tokens")
     return tokens
 
 

@@ -27,9 +27,10 @@ class NoiseStream:
     """The counterpart of `torch.Generator` over the library's own noise source (`hip.randn`, vc_randn of include/vcloze_hip.h:
     Philox4x32-10 + Box-Muller, every element a function of (seed, stream position) only).  `randn` draws at the current
     `offset` and advances it by the number of elements drawn, so a sequence of draws is one contiguous stretch of the stream: a
-    caller without torch reproduces every tensor from (seed, offset) with vc_randn / vc_randn_tokens.  It is NOT torch's stream:
-    the images of a seed here are not the images `torch.Generator.manual_seed` gives for the same seed.  Pass one as `rng` to
-    `generate_grid`, `upsample_image(s)` or `generate_and_upsample`; the default noise stays torch's."""
+    caller without torch reproduces every tensor from (seed, offset) with vc_randn / vc_randn_tokens.  Its values differ from
+    torch's: the images of a seed here are not the images `torch.Generator.manual_seed` gives for the same seed -
+    `TorchNoiseStream` below is the stream that gives those.  Pass one as `rng` to `generate_grid`, `upsample_image(s)` or
+    `generate_and_upsample`; the default noise stays torch's."""
 
     def __init__(self, seed: int, offset: int = 0, device=None):
         self.seed = int(seed)
@@ -57,6 +58,53 @@ class NoiseStream:
         out = hip.randn(tuple(shape), self.seed, self._offset, dtype=dtype, device=device if device is not None else self.device)
         self._offset += n
         return out
+
+
+class TorchNoiseStream(NoiseStream):
+    """`NoiseStream`'s interface over torch's device generator stream, restated by the library (`hip.randn_torch`, vc_randn_torch of
+    include/vcloze_hip.h, THE TORCH STREAM): the k-th `randn(shape, dtype)` is bit for bit the k-th
+    `torch.randn(shape, device=dev, generator=G).to(dtype)` of `G = torch.Generator(dev).manual_seed(seed)`, and `offset` is
+    `G.get_offset()` after every draw (the Philox offset, a multiple of 4 - not an element count).  Accepted wherever `rng` takes a
+    `NoiseStream` - `use_grid_handle=True` included - except by the stochastic sampler, whose in-kernel draws are the library's own
+    stream.  With it a seed gives the images the default path (`seed=`) and the reference give, now also from the C entry points.
+    `sm_count` / `threads_per_sm`: another device's properties (draws above 256 * sm_count * (threads_per_sm / 256) elements depend
+    on them); 0 = the current device's.  Parity is with the torch build this package is tested against."""
+
+    def __init__(self, seed: int, device=None, sm_count: int = 0, threads_per_sm: int = 0, offset: int = 0):
+        self.sm_count, self.threads_per_sm = int(sm_count), int(threads_per_sm)
+        super().__init__(seed, offset, device)
+
+    @property
+    def offset(self) -> int:
+        """the generator's Philox offset before the next draw (readable and settable; a multiple of 4)"""
+        return self._offset
+
+    @offset.setter
+    def offset(self, value: int) -> None:
+        value = int(value)
+        if not 0 <= value < 1 << 64 or value % 4:
+            raise ValueError(f"TorchNoiseStream.offset = {value}: an unsigned 64-bit multiple of 4 expected (torch.Generator.get_offset())")
+        self._offset = value
+
+    def randn(self, shape, dtype=torch.bfloat16, device=None) -> torch.Tensor:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        if n < 1:
+            raise ValueError(f"TorchNoiseStream.randn: {n} elements")
+        advance = hip.torch_randn_policy(n, self.sm_count, self.threads_per_sm)[1]
+        if self._offset + advance >= 1 << 64:
+            raise ValueError(f"TorchNoiseStream.randn: {n} elements at offset {self._offset} leave the 64-bit Philox offset")
+        out = hip.randn_torch(tuple(shape), self.seed, self._offset, dtype=dtype, device=device if device is not None else self.device,
+                              sm_count=self.sm_count, threads_per_sm=self.threads_per_sm)
+        self._offset += advance
+        return out
+
+
+def _no_torch_stream(rng, what: str) -> None:
+    if isinstance(rng, TorchNoiseStream):
+        raise ValueError(f"{what}: the stochastic sampler draws its noise inside the step from the library's own stream (vc_sde_stage), "
+                         "which a TorchNoiseStream does not restate: pass rng=NoiseStream(seed)")
 
 
 def _draw(rng, shape, dev) -> torch.Tensor:
@@ -99,6 +147,10 @@ def _grid_handle(model, ae, t5, clip, rng, what: str, **unsupported):
     if c is None or c[0] != key:
         c = (key, GridHandle(model, ae, t5, clip))
         _GRID_HANDLES[model] = c
+    if isinstance(rng, TorchNoiseStream):
+        c[1].set_noise("torch", rng.sm_count, rng.threads_per_sm)
+    else:
+        c[1].set_noise("own")
     return c[1]
 
 
@@ -130,6 +182,7 @@ def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[t
             raise ValueError("sde: the stochastic sampler works neither with adaptive= nor with the step cache")
         if not isinstance(rng, NoiseStream):
             raise ValueError("sde: the stochastic sampler draws from the library's stream: pass rng=NoiseStream(seed)")
+        _no_torch_stream(rng, "sde")
         fn = sampler.sample_sde(num_steps=steps, rng=rng, **sde)
         samples = fn(img, model.forward, **_kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]
         return packing.unpack_rows(samples, [tuple(r.shape[-2:]) for r in noise_rows])
@@ -214,7 +267,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     `rng`: the generator to draw from instead of a fresh one seeded with `seed` (the upsampling stage keeps drawing from
     the SAME generator, :450-458), or a `NoiseStream`: every draw then comes from the library's own stream in the reference's
     order of draws - the DiagonalGaussian draw of each row's encode (:377; unless `encode_noise` gives it), then one start-noise
-    tensor per row (:395-399) - each a contiguous stretch of the stream.  Returns the decoded rows `decode_rows` (default: all) as
+    tensor per row (:395-399) - each a contiguous stretch of the stream.  A `TorchNoiseStream` is taken the same way and draws
+    torch's own stream: with `encode_noise` given, `rng=TorchNoiseStream(seed)` is bit for bit what `seed` alone gives.  Returns the decoded rows `decode_rows` (default: all) as
     [3, H, W_row] tensors in [0, 1] (:430-432).  `step_cache`: a `transport.StepCache` or None (off, the default) - the opt-in first-block step cache of
     the Euler loop; it changes results; the stats of the last cached trajectory are `model.last_step_cache_stats`.
     `use_grid_handle`: opt-in, off by default - the whole function as ONE call of the library's grid handle (vc_grid_generate,
@@ -234,6 +288,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
             raise ValueError("generate_grid(sde=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid solvers only")
         if not isinstance(rng, NoiseStream):
             raise ValueError("generate_grid(sde=...) draws from the library's stream: pass rng=NoiseStream(seed)")
+        _no_torch_stream(rng, "generate_grid(sde=...)")
     if monitor is not None:
         if monitor and (use_grid_handle or adaptive is not None or sde is not None):
             raise ValueError("generate_grid(monitor=...) works with the fixed-grid solvers of the Flux handle, not with use_grid_handle=True "

@@ -588,6 +588,9 @@ class Sampler:
                 fused = _cfg_fusable(owner, x, "euler", kw)
             total = plan["draws"] * x.numel()
             if rng is not None:
+                if hasattr(rng, "threads_per_sm"):            # a pipeline.TorchNoiseStream: its offset counts Philox outputs, not elements
+                    raise ValueError("sample_sde: the stochastic sampler draws inside the step from the library's own stream (vc_sde_stage), "
+                                     "which a TorchNoiseStream does not restate: pass rng=NoiseStream(seed)")
                 if not x.is_cuda:
                     raise ValueError("sample_sde: a NoiseStream draws on the device; a CPU state draws with torch.randn (rng=None)")
                 seed, offset = int(rng.seed), int(rng.offset)
