@@ -324,6 +324,46 @@ int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const 
                           float* out, float* scratch, int64_t n, void* stream);
 int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
                      int64_t n, void* stream);
+/* ---- embedded Runge-Kutta pairs, tableau-driven: the three kernels above with the method as an argument, and the cheaper pairs an
+ * error-controlled odeint offers beside Dormand-Prince.  Added WITHOUT a change of VC_ABI_VERSION: detect these entry points
+ * (vc_rk_evals, vc_rk_stage, vc_rk_error_ratio, vc_rk_interp, vc_flux_sample_rk, vc_flux_rk_log) by SYMBOL - look up vc_rk_stage.
+ * VC_SOLVER_* has no code for them and vc_solver_evals / vc_flux_sample_ode keep refusing anything but the fixed-grid methods.
+ * The contract is the Dormand-Prince group's: f(t, y) = -model(bf16(y) || cond, 1 - f32(t)), every k bf16, the state F32, every
+ * coefficient a double rounded once to f32, every sum left to right over the non-zero coefficients, one f32 operation after the
+ * other, no fused multiply-add (transport.rk_step / rk_error_ratio / rk_hermite are the same expressions in torch: the same bits).
+ * A method of S stages evaluates k1..kS per step; kS = f(t1, y1) is the next step's k1 (first same as last), so an attempt costs
+ * S - 1 model evaluations:
+ *   VC_RK_DOPRI5         S = 7, order 5: exactly the tableau of vc_dopri5_stage.  Taken by vc_rk_stage and vc_rk_error_ratio ONLY,
+ *                        where it returns the bits of vc_dopri5_stage / vc_dopri5_error_ratio: it holds the generic code to the
+ *                        pinned one.  vc_rk_interp and vc_flux_sample_rk refuse it (VC_ERR_ARG): use the vc_dopri5 entry points.
+ *   VC_RK_BOSH3          Bogacki-Shampine 3(2), S = 4, order 3 (SciPy's RK23.C / .A / .B / .E):
+ *                        c 0, 1/2, 3/4, 1;  a2 1/2;  a3 0, 3/4;  a4 = b 2/9, 1/3, 4/9;  e 5/72, -1/12, -1/9, 1/8
+ *   VC_RK_ADAPTIVE_HEUN  Heun-Euler 2(1), S = 3, order 2:
+ *                        c 0, 1, 1;  a2 1;  a3 = b 1/2, 1/2;  e 1/2, -1/2, 0
+ * The tableaus are pinned to SciPy (bosh3) and to the closed form (adaptive_heun) in single steps; the controller around them is
+ * torchdiffeq's as recalled, unpinned against real torchdiffeq.
+ * evals: *start = 2 (k1 and the probe of the first step size), *per_attempt = S - 1, *order; any may be NULL.  Works without a GPU.
+ * stage: as vc_dopri5_stage with k [S][n] (a [7][n] buffer serves every method): stage s <= S - 3 forms y0 + dt * (a row s + 2),
+ *        s = S - 2 forms y1 = y0 + dt * (b . k), s = S - 1 only stores kS; stage 7 (v NULL) forms the probe state y0 + dt * k1;
+ *        stage < 0: *eval_ptr (a counter outside 0..S-1 and 7 reads and writes nothing).
+ * error_ratio: as vc_dopri5_error_ratio - the same four modes, the same fixed summation order - with the method's e row in mode 0.
+ * interp: VC_RK_BOSH3 / VC_RK_ADAPTIVE_HEUN: the Hermite cubic through (y0, f0 = k1, y1, f1 = kS),
+ *          y(x) = (1-x) y0 + x y1 + x (x-1) ((1-2x)(y1-y0) + (x-1) dt f0 + x dt f1),  evaluated in f32 as
+ *          c0 = 1 - x; c1 = x - 1; c2 = 1 - 2 x; w = x c1; h0 = c1 dt; h1 = x dt;  y = (c0 y0 + x y1) + w ((c2 (y1 - y0) + h0 f0) + h1 f1)
+ *        theta = 0 and theta = 1 return y0 and y1 themselves.  For bosh3 this IS SciPy's RK23 dense output (its P rows are this cubic
+ *        expanded).
+ * stage and interp move 16 bytes per access where n % 8 == 0 and the bases are 16-byte aligned; anything else runs element-wise
+ * with the same results. */
+#define VC_RK_DOPRI5 0
+#define VC_RK_BOSH3 1
+#define VC_RK_ADAPTIVE_HEUN 2
+int vc_rk_evals(int32_t method, int32_t* start, int32_t* per_attempt, int32_t* order);
+int vc_rk_stage(int32_t method, int32_t stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
+                float* y_stage, void* y_in, int64_t n, void* stream);
+int vc_rk_error_ratio(int32_t method, int32_t mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol,
+                      float atol, float* out, float* scratch, int64_t n, void* stream);
+int vc_rk_interp(int32_t method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                 int32_t out_is_bf16, int64_t n, void* stream);
 /* ---- the stochastic (SDE) sampler: what the reference's Sampler.sample_sde runs between model evaluations (transport.py:300-359,
  * the step rules of the class sde, integrators.py:27-49, and the score / diffusion forms of ICPlan in transport/path.py).  Added
  * WITHOUT a change of VC_ABI_VERSION: detect these entry points (vc_sde_plan, vc_sde_stage, vc_flux_sample_sde) by SYMBOL - look up
@@ -858,6 +898,22 @@ int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* 
                           float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream);
 int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                        int32_t* evaluations);
+/* ---- the same adaptive solve with a cheaper embedded pair: method VC_RK_BOSH3 (3 evaluations per attempt) or VC_RK_ADAPTIVE_HEUN
+ * (2), against Dormand-Prince's 6.  OPT-IN through the SAME option "adaptive": it reuses that option's buffers (the first S planes of
+ * k [7]), so the workspace bytes are those of vc_flux_sample_dopri5; prepare with max_steps >= S (4 / 3).  Everything said for
+ * vc_flux_sample_dopri5 holds - the F32 state, host-side double time, ONE step size per call, one stream synchronisation per attempt
+ * (three more for the first step), unclamped steps, its refusals and errors - with these differences:
+ *   first step / decision   the same rules with the exponent 1 / order (order 3 / 2) where Dormand-Prince has 1/5; safety 0.9, growth
+ *           capped at 10, shrink at 0.2, an accepted step never shrinks.  torchdiffeq's as recalled, unpinned against real torchdiffeq.
+ *   probe   the evaluation at t0 + h0 runs as the last stage (c_S = 1), whose node stores k alone.
+ *   outputs from vc_rk_interp, the Hermite cubic of the accepted step that covers them.
+ *   VC_RK_DOPRI5 is VC_ERR_ARG: there is one route to Dormand-Prince, vc_flux_sample_dopri5.
+ * The captured step is kept per (geometry, method).  log: of the last adaptive solve on the handle, of either entry point;
+ * *evaluations = 2 + (S - 1) per attempt. */
+int vc_flux_sample_rk(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                      float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream);
+int vc_flux_rk_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                   int32_t* evaluations);
 /* ---- the stochastic sampler around the same captured evaluation (vc_sde_plan / vc_sde_stage above have the mathematics).  OPT-IN:
  * set vc_flux_set_option(handle, "sde", 1) BEFORE vc_flux_workspace_bytes / vc_flux_prepare - it adds the F32 state, xhat, K1, the
  * coefficient table and the seed / offset words to the workspace - and prepare with max_steps >= the plan's evaluations.  With the

@@ -1,6 +1,7 @@
 // C ABI of libvcloze_hip.so (declared in include/vcloze_hip.h): argument checks, per-thread error string,
 // stream / hipGraph / event helpers.  No torch types cross this boundary.
 #include "vcloze_internal.h"
+#include "flux_rules.h"
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -119,6 +120,29 @@ int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const 
 int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
                      int64_t n, void* stream) {
   return vc_dopri5_interp_launch(y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF);
+}
+int vc_rk_evals(int32_t method, int32_t* start, int32_t* per_attempt, int32_t* order) {
+  const int S = vc_rk_stages_of(method);
+  if (!S) {
+    snprintf(g_err, sizeof(g_err), "rk_evals: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", method);
+    return VC_ERR_ARG;
+  }
+  if (start) *start = 2;
+  if (per_attempt) *per_attempt = vcrules::rk_evals_per_attempt(method);
+  if (order) *order = vcrules::rk_order(method);
+  return VC_OK;
+}
+int vc_rk_stage(int32_t method, int32_t stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
+                float* y_stage, void* y_in, int64_t n, void* stream) {
+  return vc_rk_stage_launch(method, stage, y0, k, v, dt_ptr, eval_ptr, y_stage, y_in, n, S(stream), ERRBUF);
+}
+int vc_rk_error_ratio(int32_t method, int32_t mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol,
+                      float atol, float* out, float* scratch, int64_t n, void* stream) {
+  return vc_rk_error_ratio_launch(method, mode, y0, y1, k, dt_ptr, rtol, atol, out, scratch, n, S(stream), ERRBUF);
+}
+int vc_rk_interp(int32_t method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                 int32_t out_is_bf16, int64_t n, void* stream) {
+  return vc_rk_interp_launch(method, y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF);
 }
 int vc_sde_plan(const char* method, const char* form, double norm, const char* last_step, double last_step_size, const float* t_grid,
                 int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws) {
@@ -318,6 +342,14 @@ int vc_flux_sample_dopri5(void* handle, void* x, const void* cond, const float* 
 }
 int vc_flux_dopri5_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                        int32_t* evaluations) {
+  return vc_flux_dopri5_log_impl(handle, t, dt, ratio, accepted, capacity, attempts, evaluations, ERRBUF);
+}
+int vc_flux_sample_rk(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                      float rtol, float atol, int32_t max_attempts, void* trajectory, void* stream) {
+  return vc_flux_sample_rk_impl(handle, method, x, cond, t_grid, n_points, state_is_bf16, rtol, atol, max_attempts, trajectory, S(stream), ERRBUF);
+}
+int vc_flux_rk_log(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
+                   int32_t* evaluations) {      // one log serves both adaptive entry points: the last solve's
   return vc_flux_dopri5_log_impl(handle, t, dt, ratio, accepted, capacity, attempts, evaluations, ERRBUF);
 }
 int vc_flux_sample_sde(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,

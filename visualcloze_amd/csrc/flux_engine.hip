@@ -501,6 +501,9 @@ int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, c
   if (f.traj.method == SOLVER_DOPRI5)      // the stage of the adaptive solve is the device-side counter itself
     return vc_dopri5_stage_launch(-1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
                                   e.buf, e.len);
+  if (f.traj.method == SOLVER_RK)          // likewise, with the pair's tableau
+    return vc_rk_stage_launch(f.traj.rk, -1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
+                              e.buf, e.len);
   if (f.traj.method == SOLVER_SDE_EULER || f.traj.method == SOLVER_SDE_HEUN)      // the table row of the update is the device-side counter itself
     return vc_sde_stage_launch(-1, f.SD_TAB, f.S + 1, f.SD_Y, v, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, step_ptr,
                                (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
@@ -572,6 +575,7 @@ int step_graph(Flux& f, hipStream_t s, char* err, int errlen) {
                f.cfg_active, 0, {}, f.mon_level, f.mon_cap, f.mon_log, f.mon_scratch};
   if (f.cfg_active) memcpy(&k.cfg_bits, &f.cfg_s, 4);
   k.taps = f.taps;
+  k.rk = f.traj.method == SOLVER_RK ? f.traj.rk : 0;
   if (const Flux::Step* hit = f.graphs.find(k)) {
     f.step = *hit; f.key = k;
     return VC_OK;

@@ -83,9 +83,11 @@ inline bool operator==(const Options& a, const Options& b) {
 // the solver's update read it and nothing else
 constexpr int SOLVER_DOPRI5 = 100;     // the adaptive solve: no VC_SOLVER_* code (vc_solver_evals keeps refusing it)
 constexpr int SOLVER_SDE_EULER = 101, SOLVER_SDE_HEUN = 102;     // the stochastic sampler: likewise (one captured step per method)
+constexpr int SOLVER_RK = 103;         // the embedded pairs of vc_flux_sample_rk: ONE code, the pair is Trajectory::rk (VC_RK_*)
 struct Trajectory {
   int method = VC_SOLVER_EULER;        // VC_SOLVER_*, or one of the codes above
   int evals = 1;                       // replays of the captured evaluation per step
+  int rk = 0;                          // SOLVER_RK: the VC_RK_* pair whose stage node the step ends with (0 otherwise)
   bool state_f32 = false;              // the state is stepped in f32 (XS32; XS is its bf16 shadow)
   bool cached = false;                 // the step cache steers it: a step is head + one of two tails
 };
@@ -143,11 +145,12 @@ struct Flux : Buffers {
     int cfg; uint32_t cfg_bits;          // true CFG on, and the bits of its scale: a kernel argument of the captured combine
     std::vector<void*> taps;             // the tap set: every tap is a copy node of the captured step
     int mon_level, mon_cap; void* mon_log; void* mon_scratch;      // the monitor: every site is a node of the captured step
+    int rk;                              // SOLVER_RK: the pair (a kernel argument of the captured stage node), 0 otherwise
     bool operator==(const Key& o) const {
       return base == o.base && B == o.B && T == o.T && N == o.N && S == o.S && ragged == o.ragged && gapped == o.gapped &&
              variant == o.variant && state_f32 == o.state_f32 && method == o.method && cache == o.cache && opt == o.opt && s == o.s &&
              cfg == o.cfg && cfg_bits == o.cfg_bits && taps == o.taps && mon_level == o.mon_level && mon_cap == o.mon_cap &&
-             mon_log == o.mon_log && mon_scratch == o.mon_scratch;
+             mon_log == o.mon_log && mon_scratch == o.mon_scratch && rk == o.rk;
     }
   } key{};
   // captured steps, most recently used first (a two-stage pipeline alternates between two geometries)
@@ -169,7 +172,7 @@ struct Flux : Buffers {
   // trajectory from its sample_begin on (cfg_active, cfg_s)
   bool cfg_on = false, cfg_active = false;
   float cfg_scale = 1.0f, cfg_s = 1.0f;
-  // the adaptive solve (vc_flux_sample_dopri5): the pinned words its norms are read from, and the log of the last run
+  // the adaptive solves (vc_flux_sample_dopri5, vc_flux_sample_rk): the pinned words its norms are read from, and the log of the last run
   float* ad_host = nullptr;
   struct Attempt { double t, dt; float ratio; int accepted; };
   std::vector<Attempt> ad_log;

@@ -67,6 +67,16 @@ int vc_dopri5_error_ratio_launch(int mode, const float* y0, const float* y1, con
 int vc_dopri5_interp_launch(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int out_is_bf16,
                             int64_t n, hipStream_t s, char* err, int errlen);
 int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
+// rk_embedded.hip: the same three kernels with the tableau as an argument (VC_RK_*)
+__host__ __device__ inline int vc_rk_stages_of(int method) {   // evaluations k1..kS of a step, the last one first-same-as-last; 0 = not a VC_RK_*
+  return method == VC_RK_DOPRI5 ? 7 : method == VC_RK_BOSH3 ? 4 : method == VC_RK_ADAPTIVE_HEUN ? 3 : 0;
+}
+int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
+                       float* y_stage, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
+                             float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_rk_interp_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                        int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen);
 // rng.hip / sde_plan.hip: the stochastic sampler's update, the store of its F32 state in the caller's dtype, and its host rule
 int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
                         const uint64_t* rng, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
@@ -196,6 +206,8 @@ int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const fl
                                float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
 int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
                             int32_t* evaluations, char* err, int errlen);
+int vc_flux_sample_rk_impl(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                           float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
 int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
                             double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
                             void* trajectory, hipStream_t s, char* err, int errlen);

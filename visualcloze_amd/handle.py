@@ -533,6 +533,15 @@ class FluxHandle(_Handle):
         hip._check(hip.lib().vc_flux_sample_dopri5(args[0], *args[2:], float(rtol), float(atol), int(max_attempts), hip._p(trajectory), stream),
                    "vc_flux_sample_dopri5")
 
+    def sample_rk(self, method, x, cond, t_grid, state_is_bf16: bool, stream, rtol: float = 1e-3, atol: float = 1e-6,
+                  max_attempts: int = 1000, trajectory=None) -> None:
+        """vc_flux_sample_rk (after `set_adaptive(True)` and a prepare with max_steps >= the method's stages): `sample_dopri5` with the
+        embedded pair `method` - "bosh3" | "adaptive_heun" (hip.RK_METHODS) or a VC_RK_* code; 3 / 2 evaluations per attempt.
+        `dopri5_log()` tells what the solve did (one log serves both)."""
+        args = self._sample_args("vc_flux_sample_rk", 0, x, cond, t_grid, state_is_bf16, trajectory)
+        hip._check(hip.lib().vc_flux_sample_rk(args[0], hip._rk_code(method), *args[2:], float(rtol), float(atol), int(max_attempts),
+                                               hip._p(trajectory), stream), "vc_flux_sample_rk")
+
     def sample_sde(self, method: str, x, cond, t_grid, state_is_bf16: bool, stream, form: str = "SBDM", norm: float = 1.0,
                    last_step="Mean", last_step_size: float = 0.04, seed: int = 0, offset: int = 0, trajectory=None) -> None:
         """vc_flux_sample_sde (after `set_sde(True)` and a prepare with max_steps >= the plan's evaluations): x [B,N,C] in place,
@@ -554,6 +563,10 @@ class FluxHandle(_Handle):
         hip._check(L.vc_flux_dopri5_log(self.h, t, dt, r, a, cap, C.byref(n), C.byref(ev)), "vc_flux_dopri5_log")
         att = [(t[i], dt[i], float(r[i]), bool(a[i])) for i in range(n.value)]
         return {"attempts": att, "evaluations": ev.value, "rejected": sum(1 for x in att if not x[3])}
+
+    def rk_log(self) -> dict:
+        """vc_flux_rk_log: `dopri5_log()` under the embedded pairs' name - the log of the last adaptive solve on the handle"""
+        return self.dopri5_log()
 
     # ------------------------------------------------------------------ the numerics monitor (vc_flux_set_monitor)
     def monitor_sites(self) -> list:

@@ -222,6 +222,10 @@ SYMBOLS = {
     "vc_dopri5_stage": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_dopri5_error_ratio": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp]),
     "vc_dopri5_interp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _i32, _i64, _vp]),
+    "vc_rk_evals": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_rk_stage": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "vc_rk_error_ratio": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp]),
+    "vc_rk_interp": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.c_float, _vp, _i32, _i64, _vp]),
     "vc_sde_plan": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_char_p, C.c_double, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float),
                               C.POINTER(C.c_float), _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_sde_stage": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -287,6 +291,9 @@ SYMBOLS = {
     "vc_flux_sample_dopri5": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp]),
     "vc_flux_dopri5_log": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(_i32), _i32,
                                      C.POINTER(_i32), C.POINTER(_i32)]),
+    "vc_flux_sample_rk": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, C.c_float, C.c_float, _i32, _vp, _vp]),
+    "vc_flux_rk_log": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(_i32), _i32,
+                                 C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_flux_sample_sde": (C.c_int, [_vp, C.c_char_p, _vp, _vp, C.POINTER(C.c_float), _i32, C.c_char_p, C.c_double, C.c_char_p, C.c_double,
                                      C.c_uint64, C.c_uint64, _i32, _vp, _vp]),
     "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
@@ -861,6 +868,77 @@ def dopri5_interp(y0, y1, k, dt, theta: float, out=None, dtype=torch.float32, st
         raise VclozeHipError("vc_dopri5_interp: y1 and a contiguous f32 / bf16 out of n values expected")
     _check(lib().vc_dopri5_interp(y0.data_ptr(), y1.data_ptr(), k.data_ptr(), dt.data_ptr(), float(theta), out.data_ptr(),
                                   int(out.dtype == torch.bfloat16), n, stream if stream is not None else cur_stream()), "vc_dopri5_interp")
+    return out
+
+
+# ---- embedded Runge-Kutta pairs (vc_rk_*): the three ops above with the method as an argument
+RK_METHODS = {"dopri5": 0, "bosh3": 1, "adaptive_heun": 2}      # VC_RK_*
+
+
+def _rk_code(method) -> int:
+    if isinstance(method, str):
+        if method not in RK_METHODS:
+            raise VclozeHipError(f"unknown embedded pair {method!r}: one of {sorted(RK_METHODS)} expected")
+        return RK_METHODS[method]
+    return int(method)
+
+
+def rk_evals(method) -> dict:
+    """vc_rk_evals: {"start", "per_attempt", "order", "stages"} of a method name or VC_RK_* code (no GPU needed)"""
+    st, per, order = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().vc_rk_evals(_rk_code(method), C.byref(st), C.byref(per), C.byref(order)), f"vc_rk_evals({method!r})")
+    return {"start": st.value, "per_attempt": per.value, "order": order.value, "stages": per.value + 1}
+
+
+def _rk_k(what, k, n, stages):
+    _bf16(k, "k")
+    if not k.is_contiguous() or k.numel() < stages * n or k.numel() % n:
+        raise VclozeHipError(f"{what}: k must be a contiguous bf16 [S, n] tensor of at least the method's {stages} planes")
+
+
+def rk_stage(method, stage: int, y0, k, v, dt, eval_ptr=None, y_stage=None, y_in=None, stream=None):
+    """vc_rk_stage: dopri5_stage with the tableau of `method` (a name of RK_METHODS or a VC_RK_* code).  k: bf16 [S, n] or more planes;
+    stage S - 2 forms y1, stage S - 1 only stores kS, stage 7 (v None) the probe state; stage < 0: eval_ptr[0] on the device."""
+    code, n = _rk_code(method), y0.numel()
+    _dopri5_f32("vc_rk_stage", y0=y0, dt=dt, y_stage=y_stage)
+    _rk_k("vc_rk_stage", k, n, rk_evals(code)["stages"])
+    for name, t in (("v", v), ("y_in", y_in)):
+        if t is not None:
+            _bf16(t, name)
+            if not t.is_contiguous() or t.numel() != n:
+                raise VclozeHipError(f"vc_rk_stage: {name} must be contiguous and hold n values")
+    if y_stage is not None and y_stage.numel() != n:
+        raise VclozeHipError("vc_rk_stage: y_stage must hold n values")
+    _check(lib().vc_rk_stage(code, int(stage), y0.data_ptr(), k.data_ptr(), _p(v), dt.data_ptr(), _p(eval_ptr), _p(y_stage), _p(y_in), n,
+                             stream if stream is not None else cur_stream()), "vc_rk_stage")
+
+
+def rk_error_ratio(method, y0, y1, k, dt, rtol: float, atol: float, mode: int = 0, out=None, stream=None):
+    """vc_rk_error_ratio: dopri5_error_ratio with the e row of `method` in mode 0 (modes 1, 2, 3: the initial-step norms)"""
+    code, n = _rk_code(method), y0.numel()
+    _dopri5_f32("vc_rk_error_ratio", y0=y0, y1=y1, dt=dt, out=out)
+    if k is not None:
+        _rk_k("vc_rk_error_ratio", k, n, rk_evals(code)["stages"])
+    if y1 is not None and y1.numel() != n:
+        raise VclozeHipError("vc_rk_error_ratio: y1 must hold n values")
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=y0.device)
+    scratch = torch.empty(DOPRI5_MAX_BLOCKS, dtype=torch.float32, device=y0.device)
+    _check(lib().vc_rk_error_ratio(code, int(mode), y0.data_ptr(), _p(y1), _p(k), _p(dt), float(rtol), float(atol), out.data_ptr(),
+                                   scratch.data_ptr(), n, stream if stream is not None else cur_stream()), "vc_rk_error_ratio")
+    return out
+
+
+def rk_interp(method, y0, y1, k, dt, theta: float, out=None, dtype=torch.float32, stream=None):
+    """vc_rk_interp: the Hermite dense output of the step (y0, y1, k, dt) of "bosh3" / "adaptive_heun" at theta in [0, 1] -> out (f32 or
+    bf16, n values)"""
+    code, n = _rk_code(method), y0.numel()
+    _dopri5_f32("vc_rk_interp", y0=y0, y1=y1, dt=dt)
+    _rk_k("vc_rk_interp", k, n, rk_evals(code)["stages"])
+    out = out if out is not None else torch.empty(y0.shape, dtype=dtype, device=y0.device)
+    if out.dtype not in (torch.float32, torch.bfloat16) or not (out.is_cuda and out.is_contiguous()) or out.numel() != n or y1.numel() != n:
+        raise VclozeHipError("vc_rk_interp: y1 and a contiguous f32 / bf16 out of n values expected")
+    _check(lib().vc_rk_interp(code, y0.data_ptr(), y1.data_ptr(), k.data_ptr(), dt.data_ptr(), float(theta), out.data_ptr(),
+                              int(out.dtype == torch.bfloat16), n, stream if stream is not None else cur_stream()), "vc_rk_interp")
     return out
 
 

@@ -168,8 +168,8 @@ def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[t
                  adaptive: Optional[dict] = None, sde: Optional[dict] = None, rng=None) -> List[torch.Tensor]:
     """One grid: per-row noise [1,16,h,w], VAE latents of the grid rows (already shifted/scaled), per-row PIXEL
     fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w].
-    `adaptive`: None, or dict(rtol=, atol=[, max_attempts=]) - the error-controlled Dormand-Prince 5(4) solve
-    (`Sampler.sample_ode_adaptive`) instead of `solver`; `steps` then only places the end time's grid.
+    `adaptive`: None, or dict(rtol=, atol=[, max_attempts=][, method=]) - the error-controlled solve (`Sampler.sample_ode_adaptive`:
+    Dormand-Prince 5(4), or with method="bosh3" / "adaptive_heun" a cheaper embedded pair) instead of `solver`; `steps` then only places the end time's grid.
     `sde`: None, or dict(sampling_method=, diffusion_form=, diffusion_norm=, last_step=, last_step_size=, sample_eps=) - any subset -
     the stochastic sampler (`Sampler.sample_sde`, num_steps = `steps`) instead of `solver`; its noise comes from `rng`, which must be a
     `NoiseStream` (its offset advances by the draws).  Image quality under any diffusion form is unmeasured."""
@@ -274,7 +274,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     `use_grid_handle`: opt-in, off by default - the whole function as ONE call of the library's grid handle (vc_grid_generate,
     `handle.GridHandle`: the same composition kept in csrc/grid_engine.hip, the same bits).  Valid only with a `NoiseStream` and the
     use_handle switches of all four modules on (ValueError otherwise); `rng.offset` advances as it does here.
-    `adaptive`: None (the default), or dict(rtol=, atol=) - denoise with the error-controlled Dormand-Prince 5(4) solve instead of
+    `adaptive`: None (the default), or dict(rtol=, atol=[, method="dopri5" | "bosh3" | "adaptive_heun"]) - denoise with the
+    error-controlled solve (Dormand-Prince 5(4) unless `method` names a cheaper embedded pair) instead of
     `solver` (`denoise_grid`); `model.last_adaptive_log` tells what it did.  Refused together with use_grid_handle=True: the grid
     handle runs the fixed-grid solvers only.
     `monitor`: None (the default: `model.monitor` as it stands), or 0 | 1 | 2 - the numerics monitor of the Flux handle for this call

@@ -16,6 +16,8 @@ behind them) runs the same fused loop with the cross-sample combine as one more 
 `Sampler.sample_ode_adaptive` is the error-controlled solve the reference's `sample_ode` defaults to ("dopri5"), under a name of its
 own - `sample_ode(sampling_method="dopri5")` keeps raising: adaptive Dormand-Prince 5(4), fused through vc_flux_sample_dopri5 for a
 `visualcloze_amd.Flux` with the C handle, `dopri5_integrate` (the same rule in plain torch) for any other callable.
+`method="bosh3"` / `"adaptive_heun"` run the cheaper embedded pairs (3 / 2 evaluations per attempt against 6) through the same loop:
+vc_flux_sample_rk fused, `rk_integrate` in plain torch.
 
 `Sampler.sample_sde` is the reference's stochastic sampler (transport.py:300-359: Euler-Maruyama / stochastic Heun, the six diffusion
 forms, the four last steps) on the velocity v(x, t) = -model(x || cond, timesteps = 1 - t) - the adaptation the reference made for
@@ -32,6 +34,7 @@ from __future__ import annotations
 
 import math
 from contextlib import contextmanager
+from functools import partial
 from typing import Callable, Optional
 
 import torch
@@ -271,6 +274,183 @@ def dopri5_integrate(f, y0: torch.Tensor, t, rtol: float = 1e-3, atol: float = 1
                 outs.append(dopri5_interp(y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
                 nxt += 1
             y0, k1, tc = y1, ks[6], t1
+        dt = dt_next
+    return torch.stack(outs)
+
+
+# ---- embedded Runge-Kutta pairs, tableau-driven (vc_rk_* / vc_flux_sample_rk, csrc/rk_embedded.hip): the same rules in plain torch,
+# bit-equal to the fused loop for an f32 state.  A method of S stages evaluates k1..kS per step; kS = f(t1, y1) is the next step's k1
+# (first same as last), so an attempt costs S - 1 evaluations.  c: the S stage times; a: the rows a2 .. a(S-1); b: forms y1 (= row aS);
+# e: the S weights of the error estimate.  bosh3 is SciPy's RK23.C / .A / .B / .E and adaptive_heun the closed form
+# (tests/test_rk_embedded_cpu.py pins both, in single steps); the controller is torchdiffeq's as recalled - unpinned against real
+# torchdiffeq - with the exponent 1 / order where Dormand-Prince has 1/5.  "dopri5" is here for the stage and error kernels only
+# (vc_rk_stage / vc_rk_error_ratio return vc_dopri5_*'s bits with it): its solve is dopri5_integrate.
+RK_TABLEAUS = {
+    "dopri5": dict(code=0, order=5, c=DOPRI5_C + (1.0,), a=DOPRI5_A, b=DOPRI5_B, e=DOPRI5_E),
+    "bosh3": dict(code=1, order=3, c=(0.0, 1 / 2, 3 / 4, 1.0), a=((1 / 2,), (0.0, 3 / 4)), b=(2 / 9, 1 / 3, 4 / 9),
+                  e=(5 / 72, -1 / 12, -1 / 9, 1 / 8)),
+    "adaptive_heun": dict(code=2, order=2, c=(0.0, 1.0, 1.0), a=((1.0,),), b=(1 / 2, 1 / 2), e=(1 / 2, -1 / 2, 0.0)),
+}
+ADAPTIVE_METHODS = ("dopri5", "bosh3", "adaptive_heun")       # Sampler.sample_ode_adaptive(method=)
+
+
+def _rk_tableau(method: str, solve: bool = False) -> dict:
+    if method not in RK_TABLEAUS or (solve and method == "dopri5"):
+        raise ValueError(f"method {method!r}: one of {[m for m in RK_TABLEAUS if not (solve and m == 'dopri5')]} expected"
+                         + (" (Dormand-Prince has one route: dopri5_integrate)" if method == "dopri5" else ""))
+    return RK_TABLEAUS[method]
+
+
+def _rk_norm(num: torch.Tensor, den: torch.Tensor) -> float:
+    """sqrt(mean(q^2)) of q = num / den over all n elements, summed in q's dtype in the fixed order of csrc/rk_embedded.hip (and dopri5.hip): the
+    elements are dealt round-robin to nblk * 256 threads (nblk = min(ceil(n / 256), 256)), a thread adds its squares in ascending
+    order, a block's 256 sums go down one binary tree, the block sums down the same tree.  For an f32 q this gives the kernel's bits;
+    the callers form num and den on the CPU too."""
+    q = num.reshape(-1) / den.reshape(-1)
+    n = q.numel()
+    nblk = min((n + 255) // 256, 256)
+    T = nblk * 256
+    rounds = -(-n // T)
+    q2 = torch.zeros(rounds * T, dtype=q.dtype)
+    q2[:n] = q * q
+    q2 = q2.view(rounds, T)
+    s = q2[0]
+    for r in range(1, rounds):
+        s = s + q2[r]
+
+    def tree(v):
+        o = 128
+        while o >= 1:
+            v = v[..., :o] + v[..., o:2 * o]
+            o //= 2
+        return v[..., 0]
+
+    part = torch.zeros(256, dtype=q.dtype)
+    part[:nblk] = tree(s.view(nblk, 256))
+    mean = float(tree(part) / torch.tensor(float(n), dtype=torch.float64).to(q.dtype))
+    # the square root in double, rounded once more for an f32 q: the correctly rounded f32 root (53 >= 2 * 24 + 2 bits), which
+    # torch's vectorised CPU sqrt is not
+    return math.sqrt(mean) if q.dtype == torch.float64 else _f32(math.sqrt(mean))
+
+
+def rk_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor, method: str):
+    """One step of the pair from (t, y0) with k1 = f(t, y0): -> (y1, [k1..kS]); kS = f(t + dt, y1) is the next step's k1.  Every k is
+    converted to the state's dtype, every sum is taken left to right over the non-zero coefficients."""
+    tab = _rk_tableau(method)
+    h = _scalar(dt, y0)
+    ks = [k1.to(y0.dtype)]
+    for i, row in enumerate(tab["a"]):
+        ks.append(f(t + tab["c"][i + 1] * dt, y0 + h * _dopri5_combine(row, ks)).to(y0.dtype))
+    y1 = y0 + h * _dopri5_combine(tab["b"], ks)
+    ks.append(f(t + dt, y1).to(y0.dtype))
+    return y1, ks
+
+
+def rk_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float, method: str) -> float:
+    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements, in the kernel's summation order"""
+    y0, y1, ks = y0.detach().cpu(), y1.detach().cpu(), [k.detach().cpu() for k in ks]
+    err = _scalar(dt, y0) * _dopri5_combine(_rk_tableau(method)["e"], ks)
+    tol = _scalar(atol, y0) + _scalar(rtol, y0) * torch.maximum(y0.abs(), y1.abs())
+    return _rk_norm(err, tol)
+
+
+def rk_hermite(y0, y1, ks, dt: float, theta: float):
+    """The dense output of bosh3 / adaptive_heun at theta in [0, 1]: the cubic through (y0, f0 = k1, y1, f1 = kS),
+    y = (1-x) y0 + x y1 + x (x-1) ((1-2x)(y1-y0) + (x-1) dt f0 + x dt f1), as the ONE sequence of operations csrc/rk_embedded.hip
+    states; theta = 0 and theta = 1 return y0 and y1 themselves.  For an f32 state every scalar is formed in f32."""
+    x = _scalar(theta, y0)
+    if x == 0.0:
+        return y0.clone()
+    if x == 1.0:
+        return y1.clone()
+    f0, f1 = ks[0], ks[-1]
+    if y0.dtype == torch.float32:
+        xt, h, one = (torch.tensor(v, dtype=torch.float64).to(torch.float32) for v in (x, dt, 1.0))
+        c1 = xt - one
+        c0, c1, c2, w, h0, h1 = (float(v) for v in (one - xt, c1, one - 2 * xt, xt * c1, c1 * h, xt * h))
+    else:
+        c0, c1, c2 = 1.0 - x, x - 1.0, 1.0 - 2.0 * x
+        w, h0, h1 = x * c1, c1 * dt, x * dt
+    d = y1 - y0
+    inner = (c2 * d + h0 * f0) + h1 * f1
+    return (c0 * y0 + x * y1) + w * inner
+
+
+def rk_controller(dt: float, ratio: float, order: int):
+    """-> (accepted, dt_next): dopri5_controller with the exponent 1 / order (at order 5 the same bits).  A NaN ratio raises."""
+    if ratio != ratio:
+        raise Dopri5Error(f"rk: the error ratio of a step of dt = {dt:.3g} is NaN")
+    if ratio == 0.0:
+        return True, dt * 10.0
+    return ratio <= 1.0, dt * min(10.0, max(0.9 / math.pow(ratio, 1.0 / order), 1.0 if ratio < 1.0 else 0.2))
+
+
+def _rk_first_dt(order: int, h0: float, d1: float, d2: float) -> float:
+    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else math.pow(0.01 / max(d1, d2), 1.0 / order)
+    return min(100.0 * h0, h1)
+
+
+def rk_initial_step(f, t0: float, y0, f0, rtol: float, atol: float, order: int) -> float:
+    """dopri5_initial_step with the exponent 1 / order and the norms in the kernel's summation order (one more evaluation)"""
+    f0 = f0.to(y0.dtype)
+    c0, cf0 = y0.detach().cpu(), f0.detach().cpu()
+    scale = _scalar(atol, y0) + _scalar(rtol, y0) * c0.abs()
+    d0, d1 = _rk_norm(c0, scale), _rk_norm(cf0, scale)
+    if d0 != d0 or d1 != d1:
+        raise Dopri5Error("rk: the state or the drift at the first time is not finite")
+    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
+    f1 = f(t0 + h0, y0 + _scalar(h0, y0) * f0).to(y0.dtype)
+    d2 = _rk_norm(f1.detach().cpu() - cf0, scale) / h0
+    if d2 != d2:
+        raise Dopri5Error("rk: the drift at the first time + h0 is not finite")
+    return _rk_first_dt(order, h0, d1, d2)
+
+
+def rk_integrate(f, y0: torch.Tensor, t, method: str, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
+                 log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
+    """dopri5_integrate for the pair `method` ("bosh3" | "adaptive_heun"): the same loop, arguments, log and errors (Dopri5Error), the
+    outputs read off the Hermite cubic of the accepted step that covers them.  For an f32 state every bit - states, ratios, step
+    sizes - is the fused loop's (vc_flux_sample_rk)."""
+    tab = _rk_tableau(method, solve=True)
+    order = tab["order"]
+    ts = [float(v) for v in (t.tolist() if torch.is_tensor(t) else t)]
+    if len(ts) < 2 or any(b <= a for a, b in zip(ts, ts[1:])):
+        raise ValueError("rk_integrate: t must hold at least two strictly increasing times")
+    if y0.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"rk_integrate: an f32 or f64 state expected, got {y0.dtype}")
+    log = log if log is not None else []
+    tc = ts[0]
+    k1 = f(tc, y0).to(y0.dtype)
+    forced = None if forced_dts is None else list(forced_dts)
+    dt = None if forced is not None else rk_initial_step(f, tc, y0, k1, rtol, atol, order)
+    outs, nxt, attempts = [y0], 1, 0
+    while nxt < len(ts):
+        if forced is not None:
+            if attempts >= len(forced):
+                raise Dopri5Error(f"rk: the {len(forced)} forced attempts end at t = {tc!r}, before t[{nxt}] = {ts[nxt]!r}")
+            item = forced[attempts]
+            dt, accept_as = (float(item[0]), bool(item[1])) if isinstance(item, (tuple, list)) else (float(item), None)
+        if attempts >= max_attempts:
+            raise Dopri5Error(f"rk: more than max_attempts = {max_attempts} attempts (t = {tc!r}, dt = {dt:.3g})")
+        if tc + dt == tc:
+            raise Dopri5Error(f"rk: the step size underflowed (t = {tc!r}, dt = {dt:.3g})")
+        attempts += 1
+        y1, ks = rk_step(f, tc, dt, y0, k1, method)
+        ratio = rk_error_ratio(y0, y1, ks, dt, rtol, atol, method)
+        if on_attempt is not None:
+            on_attempt(tc, dt, y0, y1, ks)
+        if forced is not None and accept_as is not None:
+            accepted, dt_next = accept_as, None
+            log.append((tc, dt, ratio, accepted))
+        else:
+            log.append((tc, dt, ratio, ratio <= 1.0))
+            accepted, dt_next = rk_controller(dt, ratio, order)
+        if accepted:
+            t1 = tc + dt
+            while nxt < len(ts) and ts[nxt] <= t1:
+                outs.append(rk_hermite(y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
+                nxt += 1
+            y0, k1, tc = y1, ks[-1], t1
         dt = dt_next
     return torch.stack(outs)
 
@@ -518,14 +698,19 @@ class Sampler:
         return _sample
 
     def sample_ode_adaptive(self, *, num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, do_shift=True, time_shifting_factor=None,
-                            strength=None, return_trajectory: bool = False, max_attempts: int = 1000):
+                            strength=None, return_trajectory: bool = False, max_attempts: int = 1000, method: str = "dopri5"):
         """The error-controlled solve the reference's sample_ode defaults to (sampling_method="dopri5", atol, rtol), under a name of
         its own: sample_ode("dopri5") keeps raising.  Adaptive Dormand-Prince 5(4) (`dopri5_integrate`); `num_steps` only places the
         OUTPUT times - the solver chooses its own steps and reads the outputs off its dense output.  Fused (vc_flux_sample_dopri5:
         replays of one captured evaluation, one 4-byte host read per attempt) for the bound forward / forward_with_cfg of a
         visualcloze_amd.Flux that has the C handle and a bf16 or f32 state, eager otherwise.  The state is stepped in f32 (f64 for an
         f64 caller) and rounded once per output.  `sampler.last_adaptive_log` holds, per chunk of samples,
-        {"attempts": [(t, dt, ratio, accepted)], "evaluations", "rejected"} of the last run."""
+        {"attempts": [(t, dt, ratio, accepted)], "evaluations", "rejected"} of the last run.
+        `method`: "dopri5" (the default: the path above, untouched), or one of the cheaper embedded pairs "bosh3" (Bogacki-Shampine
+        3(2)) / "adaptive_heun" (2(1)) - `rk_integrate`, fused through vc_flux_sample_rk under the same conditions, eager otherwise;
+        evaluations per attempt: 6 / 3 / 2.  Their controller is torchdiffeq's as recalled, unpinned against real torchdiffeq."""
+        if method not in ADAPTIVE_METHODS:
+            raise ValueError(f"sample_ode_adaptive: method {method!r}: one of {list(ADAPTIVE_METHODS)} expected")
         t0, t1 = self.transport.check_interval(reverse=reverse)
         if strength is not None:
             t0 = (t1 - t0) * strength + t0
@@ -539,11 +724,12 @@ class Sampler:
             if fused and cfg_scale is not None:
                 fused = _cfg_fusable(owner, x, "euler", kw)
             if fused:
-                out, logs = _sample_adaptive_fused(owner, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale)
+                out, logs = _sample_adaptive_fused(owner, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale, method=method)
             else:
                 if cfg_scale is not None:
                     model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
-                out, log = _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=is_flux)
+                out, log = _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=is_flux,
+                                                    method=method)
                 logs = [log]
             self.last_adaptive_log = logs
             return out
@@ -670,15 +856,17 @@ def _log_dict(attempts, evaluations):
 
 
 def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=False, forced_dts=None,
-                             on_attempt=None):
-    """Any callable: transport.dopri5_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
+                             on_attempt=None, method="dopri5"):
+    """Any callable: transport.dopri5_integrate (method "dopri5") or rk_integrate on the whole batch, the state in f32 (f64 for an f64
+    caller), rounded once per output"""
     calls = []
     drift = _adaptive_drift(model, x, kw, bf16_out)
     f = lambda tt, y: (calls.append(tt), drift(tt, y))[1]  # noqa: E731
     y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
     log = []
-    out = dopri5_integrate(f, y0, t.to(torch.float32), rtol, atol, max_attempts, forced_dts=forced_dts, log=log,
-                           on_attempt=on_attempt).to(x.dtype)
+    solve = dopri5_integrate if method == "dopri5" else partial(rk_integrate, method=method)
+    out = solve(f, y0, t.to(torch.float32), rtol=rtol, atol=atol, max_attempts=max_attempts, forced_dts=forced_dts, log=log,
+                on_attempt=on_attempt).to(x.dtype)
     return (out if return_trajectory else out[-1:]), _log_dict(log, len(calls))
 
 
@@ -739,8 +927,9 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
 
 
 @torch.no_grad()
-def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None):
-    """vc_flux_sample_dopri5 per chunk of samples: ONE step size per chunk, so a sample's result depends on its chunk's other samples"""
+def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None, method="dopri5"):
+    """vc_flux_sample_dopri5 (method "dopri5") or vc_flux_sample_rk per chunk of samples: ONE step size per chunk, so a sample's result
+    depends on its chunk's other samples"""
     h = flux.handle()
     if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_dopri5 refuses it: its counter is a stage, not an evaluation)
         raise ValueError("monitor: the adaptive solve has no evaluation index to log under; set Flux.monitor = 0 or use a fixed-grid solver")
@@ -749,11 +938,15 @@ def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_at
 
     def run(xs, cond, tj, s):
         try:
-            h.sample_dopri5(xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
+            if method == "dopri5":
+                h.sample_dopri5(xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
+            else:
+                h.sample_rk(method, xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
         finally:
-            logs.append(h.dopri5_log())
+            logs.append(h.dopri5_log())            # one log serves both entry points: the last adaptive solve's
 
-    return _solve_on_handle(flux, h, x, kw, len(t) - 1, return_trajectory, 7, run, cfg_scale=cfg_scale, adaptive=True), logs
+    stages = len(RK_TABLEAUS[method]["c"])         # the modulation rows of one attempt
+    return _solve_on_handle(flux, h, x, kw, len(t) - 1, return_trajectory, stages, run, cfg_scale=cfg_scale, adaptive=True), logs
 
 
 def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
