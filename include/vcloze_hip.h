@@ -462,6 +462,56 @@ typedef struct VcStat { float max_abs; float sum_sq; uint32_t nonfinite; uint32_
 void vc_monitor_struct_sizes(int32_t out[1]);
 int vc_tensor_stats(const void* x, int32_t x_is_f32, int64_t bstride, int64_t ld, int32_t B, int64_t rows, int32_t cols, VcStat* out,
                     int64_t out_stride, const int32_t* row_ptr, int32_t capacity, float* scratch, void* stream);
+/* ---- the flow-matching loss of ONE model evaluation, forward only: Transport.training_losses (transport.py:132-176) on
+ * Transport.sample (transport.py:98-130) for the Linear path (alpha = t, sigma = 1 - t) and velocity prediction - the objective a
+ * VisualCloze LoRA is trained on, as a validation loss.  No backward pass exists.  Added WITHOUT a change of VC_ABI_VERSION (tests
+ * pin 11): detect by SYMBOL (look up vc_fm_plan).  Every argument is checked before the device is touched.
+ * vc_fm_plan: the path sample.  x1: B samples of rows x cols elements, bf16 or F32 (x1_is_f32); element (b, r, c) lies
+ *   b * x1_bstride + r * x1_ld + c elements behind x1.  t: DEVICE F32 [B].  x0: a dense [B, rows, cols] tensor of x1's dtype, or
+ *   NULL: element i (the flat index (b * rows + r) * cols + c) is then drawn IN the kernel - the VC_RNG_F32 value of THE STREAM of
+ *   `seed` at position offset + i, rounded to bf16 for a bf16 x1 (the VC_RNG_BF16 value): what a vc_randn call of x1's dtype gives
+ *   there, with no draw launch and no stored x0 (seed and offset are unused with a tensor).  In F32, one operation after the other,
+ *   no fused multiply-add, with x1 and x0 converted to F32:
+ *       xt[(b * rows + r) * xt_ld + c] = bf16( t[b] * x1 + (1 - t[b]) * x0 )      rounded ONCE; columns >= cols of xt are not touched
+ *       ut[(b * rows + r) * cols + c]  = x1 - x0                                   F32, dense
+ *   - the torch F32 expression of the same shape gives the same bits.  xt is the model-input row (xt_ld = in_channels): the cond
+ *   columns beside x_t are the caller's, the concat costs no pass.  16-byte accesses where cols, x1_ld, x1_bstride, xt_ld are
+ *   multiples of 8 (4 for the strides of an F32 x1) and x1, x0, xt, ut are 16-byte aligned; anything else runs element-wise: the
+ *   choice is made on the host and gives the same bits.  Grid capped, grid-stride loop.  Buffers must not overlap.
+ *   VC_ERR_ARG: a null x1 / t / xt / ut; B, rows or cols <= 0; x1_bstride < 0; x1_ld or xt_ld < cols; a buffer that is not aligned to
+ *   its elements; B * rows * cols beyond a 64-bit byte offset; with x0 NULL, offset + B * rows * cols - 1 past 2^64 - 1.
+ * vc_fm_loss: the masked squared error.  out: the model's bf16 output, element (b, r, c) at (b * rows + r) * out_ld + c; ut: as
+ *   vc_fm_plan left it.  valid_rows: per sample the number of VALID rows, a prefix of its rows (the handle's valid-first row
+ *   order) - int32 [B] in device memory (valid_on_host 0; clamped to [0, rows] by the kernel; 0 gives NaN), or on the host
+ *   (valid_on_host != 0; at most VC_FM_MAX_HOST_COUNTS samples, the counts travel as kernel arguments), or NULL = every row.
+ *       loss[b] = ( sum over r < valid_rows[b], c < cols of ((-out) - ut)^2 ) / F32(valid_rows[b] * cols)            F32 [B], device
+ *   The order of the sum is vc_tensor_stats' above, with units of 8 elements: a row is cut into units of 8 consecutive elements
+ *   (the last one shorter where cols % 8 != 0); the units of the sample's valid rows, numbered row by row, are dealt round-robin to
+ *   the nblk * 256 threads of nblk = min(ceil(rows * ceil(cols / 8) / 256), VC_FM_LOSS_MAX_BLOCKS) blocks - nblk from ALL rows, the
+ *   same for every sample - thread t of block k taking units k * 256 + t, + nblk * 256, ...  A thread adds its elements in ascending
+ *   order, d = (-out) - ut, s = s + d * d, the product rounded on its own; the block's 256 sums go through a tree (l[t] += l[t + o],
+ *   o = 128, 64, .., 1), the nblk block sums through the same tree (thread t holds block t's, 0 for t >= nblk); one F32 division.
+ *   No atomics: repeated runs give the same bits.  An inf in `out` gives inf.  A unit is one 16-byte load of out and two of ut where
+ *   cols and out_ld are multiples of 8 and out, ut are 16-byte aligned, element loads otherwise, with the same bits.
+ *   scratch: B * VC_FM_LOSS_MAX_BLOCKS F32 of device memory.  VC_ERR_ARG: a null out / ut / loss / scratch; B, rows or cols <= 0;
+ *   B > 65535; out_ld < cols; a buffer that is not aligned to its elements; more than 2^31 - 1 units per sample; with host counts
+ *   B > VC_FM_MAX_HOST_COUNTS or a count outside [1, rows] - a sample without a valid row has no loss.
+ * vc_fm_times: HOST only.  The training times Transport.sample draws (transport.py:107-129), from the caller's n base draws: F32
+ *   uniforms in [0, 1) for snr_type "uniform" and "uniform_<t0>_<t1>", F32 standard normals for "lognorm"; anything else - and a
+ *   "uniform_..." that is not two finite plain decimal numbers - is VC_ERR_ARG, as the reference raises.  check_interval
+ *   (transport.py:70-96) gives (0, 1) for Linear + velocity.  In torch's F32 operations, nothing contracted:
+ *       uniform   t = u * F32(t1 - t0) + F32(t0)                  (t1 - t0 in double)
+ *       lognorm   t = (1 / (1 + e)) * 1 + 0,  e = F32(exp(-u)) with the exponential taken in double: the correctly rounded F32
+ *                 exponential (torch's own vectorised F32 exp is within an ulp of it)
+ *   then, with do_shift, step 3 of vc_time_grid below with n_tokens = x1.shape[1] (time_shift of transport.py:123-127).  out: HOST
+ *   F32 [n], bit for bit transport.fm_times.  VC_ERR_ARG also: a null pointer, n <= 0, n_tokens < 1. */
+#define VC_FM_LOSS_MAX_BLOCKS 256
+#define VC_FM_MAX_HOST_COUNTS 64
+int vc_fm_plan(const void* x1, int32_t x1_is_f32, int64_t x1_bstride, int64_t x1_ld, const float* t, const void* x0, uint64_t seed,
+               uint64_t offset, void* xt, int64_t xt_ld, float* ut, int32_t B, int64_t rows, int32_t cols, void* stream);
+int vc_fm_loss(const void* out, int64_t out_ld, const float* ut, const int32_t* valid_rows, int32_t valid_on_host, float* loss,
+               float* scratch, int32_t B, int64_t rows, int32_t cols, void* stream);
+int vc_fm_times(const char* snr_type, const float* base, int32_t n, int32_t n_tokens, int32_t do_shift, float* out);
 /* ---- true classifier-free guidance: the combine of Flux.forward_with_cfg (models/model.py:126-145), which runs forward on a batch
  * whose first half is the conditional and whose second half the unconditional samples and returns
  * cat([uncond_v + cfg_scale * (cond_v - uncond_v), uncond_v]).  Added without a change of VC_ABI_VERSION: detect by SYMBOL (look up
@@ -841,6 +891,26 @@ typedef struct VcFluxInputs {   /* everything of model_kwargs that does not chan
 int vc_flux_prepare(void* handle, const VcFluxInputs* in, void* workspace, int64_t workspace_bytes, void* stream);
 /* ONE evaluation: out [B, N, out_channels] = Flux(img [B, N, in_channels]; timesteps HOST [B]) */
 int vc_flux_forward(void* handle, const void* img, const float* timesteps, int32_t timesteps_is_bf16, void* out, void* stream);
+/* ONE evaluation as the flow-matching loss: Transport.training_losses (transport.py:132-176) on the prepared samples, forward only.
+ * Detect by SYMBOL (look up vc_flux_eval_loss).  OPT-IN: vc_flux_set_option(handle, "eval_loss", 1) BEFORE vc_flux_workspace_bytes /
+ * vc_flux_prepare (max_steps >= 1) - it adds u_t (B * N * out_channels F32), the B times and the B * VC_FM_LOSS_MAX_BLOCKS partial
+ * sums behind everything else; with it off the workspace, the captured steps and every output bit are what they were.  A switch
+ * un-prepares the handle; VC_ERR_STATE without the option, before vc_flux_prepare, between vc_flux_sample_begin* and
+ * vc_flux_sample_end, and with true CFG on (vc_flux_set_cfg: the reference never trains through forward_with_cfg).
+ * x1 [B, N, out_channels] dense, bf16 or F32 (x1_is_f32), rows in the handle's order (image rows valid-first per sample, as img of
+ * vc_flux_forward); cond [B, N, in_channels - out_channels] bf16, required (vc_flux_create takes in_channels > out_channels only: a model whose img_in
+ * reads x_t alone runs vc_fm_plan / vc_fm_loss around its own evaluation); t HOST F32 [B],
+ * finite; x0 a tensor of x1's dtype, or NULL for the draw of vc_fm_plan at (seed, offset); loss DEVICE F32 [B].  One call issues
+ *   vc_fm_plan(x1, t', x0 | seed, offset) -> the model-input rows and u_t;   the cond columns beside x_t (one strided copy);
+ *   vc_flux_forward's evaluation of those rows at timesteps = 1 - t' -> the velocity buffer;   vc_fm_loss over each sample's
+ *   valid image rows, kv_len[b] - T (all N without kv_len) -> loss
+ * with t' = t rounded to bf16 for a bf16 x1 (transport.py:129: t.to(x1[0])) and 1 - t' rounded likewise (a bf16 timesteps tensor,
+ * timesteps_is_bf16 of vc_flux_forward); for an F32 x1 both stay F32.  It reuses the forward's buffers for the model input and
+ * output.  The numerics monitor, if on, logs this evaluation into row 0 like vc_flux_forward.  Not captured: the launches are
+ * issued on `stream`.  VC_ERR_ARG: a null x1 / cond / t / loss, a non-finite t, a sample without
+ * a valid image row, B > VC_FM_MAX_HOST_COUNTS, a stream position past 2^64 - 1. */
+int vc_flux_eval_loss(void* handle, const void* x1, int32_t x1_is_f32, const void* cond, const float* t, const void* x0, uint64_t seed,
+                      uint64_t offset, float* loss, void* stream);
 /* The loop.  x [B, N, out_channels]: in = x(t_grid[0]), out = x(t_grid[n_points-1]); cond [B, N, in - out channels] bf16;
  * t_grid HOST f32 [n_points] (n_points - 1 <= max_steps evaluations); state_is_bf16 != 0: x, x_out and trajectory are bf16 -
  * the pipeline's state dtype, visualcloze.py:399 - and the model sees 1 - bf16(t_i) (torchdiffeq hands the drift

@@ -169,6 +169,17 @@ int vc_residual_add(const void* a, int64_t a_bstride, const void* b, int64_t b_b
   return vc_residual_op_launch(1, a, a_bstride, b, b_bstride, out, out_bstride, B, n, S(stream), ERRBUF);
 }
 void vc_monitor_struct_sizes(int32_t out[1]) { out[0] = (int32_t)sizeof(VcStat); }
+int vc_fm_plan(const void* x1, int32_t x1_is_f32, int64_t x1_bstride, int64_t x1_ld, const float* t, const void* x0, uint64_t seed, uint64_t offset,
+               void* xt, int64_t xt_ld, float* ut, int32_t B, int64_t rows, int32_t cols, void* stream) {
+  return vc_fm_plan_launch(x1, x1_is_f32, x1_bstride, x1_ld, t, x0, seed, offset, xt, xt_ld, ut, B, rows, cols, S(stream), ERRBUF);
+}
+int vc_fm_loss(const void* out, int64_t out_ld, const float* ut, const int32_t* valid_rows, int32_t valid_on_host, float* loss, float* scratch,
+               int32_t B, int64_t rows, int32_t cols, void* stream) {
+  return vc_fm_loss_launch(out, out_ld, ut, valid_rows, valid_on_host, loss, scratch, B, rows, cols, S(stream), ERRBUF);
+}
+int vc_fm_times(const char* snr_type, const float* base, int32_t n, int32_t n_tokens, int32_t do_shift, float* out) {
+  return vc_fm_times_impl(snr_type, base, n, n_tokens, do_shift, out, ERRBUF);
+}
 int vc_tensor_stats(const void* x, int32_t x_is_f32, int64_t bstride, int64_t ld, int32_t B, int64_t rows, int32_t cols, VcStat* out,
                     int64_t out_stride, const int32_t* row_ptr, int32_t capacity, float* scratch, void* stream) {
   return vc_tensor_stats_launch(x, x_is_f32, bstride, ld, B, rows, cols, out, out_stride, row_ptr, capacity, scratch, S(stream), ERRBUF);
@@ -306,6 +317,10 @@ int vc_flux_prepare(void* handle, const VcFluxInputs* in, void* workspace, int64
 }
 int vc_flux_forward(void* handle, const void* img, const float* timesteps, int32_t timesteps_is_bf16, void* out, void* stream) {
   return vc_flux_forward_impl(handle, img, timesteps, timesteps_is_bf16, out, S(stream), ERRBUF);
+}
+int vc_flux_eval_loss(void* handle, const void* x1, int32_t x1_is_f32, const void* cond, const float* t, const void* x0, uint64_t seed,
+                      uint64_t offset, float* loss, void* stream) {
+  return vc_flux_eval_loss_impl(handle, x1, x1_is_f32, cond, t, x0, seed, offset, loss, S(stream), ERRBUF);
 }
 int vc_flux_sample_begin(void* handle, const void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                          void* stream) {

@@ -24,6 +24,8 @@
 //   SD_Y / SD_XHAT / SD_K1 (f32) / SD_TAB / SD_RNG  only with option sde 1, behind the adaptive solve's: the state, x-hat and K1 of the
 //                           stochastic sampler (vc_flux_sample_sde, rng.hip), its coefficient table ([S + 1][VC_SDE_ROW] f32) and the
 //                           seed / offset words its update reads
+//   FM_U (f32) / FM_T / FM_PART  only with option eval_loss 1, behind the stochastic sampler's: u_t = x1 - x0 of vc_flux_eval_loss
+//                           (fm_loss.hip), its B times and the partial sums of its reduction
 //   LY / LY2 / LH / LSCALE  only in the un-merged LoRA mode (option lora_mode 1), behind everything else: base_out, base_out + lora
 //                           and lora_A(x) of the Linear being run, and the lora scale as a bf16 vector (the gate operand of the
 //                           gated-residual epilogue that adds the lora branch; refilled by vc_flux_set_lora_scale)
@@ -76,6 +78,10 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
     const int64_t n = (int64_t)B * N * out_ch;
     f.SD_Y = c.take<float>(n); f.SD_XHAT = c.take<float>(n); f.SD_K1 = c.take<float>(n);
     f.SD_TAB = c.take<float>(((int64_t)S + 1) * VC_SDE_ROW); f.SD_RNG = c.take<uint64_t>(2);
+  }
+  if (g.opt.eval_loss) {   // likewise
+    f.FM_U = c.take<float>((int64_t)B * N * out_ch); f.FM_T = c.take<float>(B);
+    f.FM_PART = c.take<float>((int64_t)B * VC_FM_LOSS_MAX_BLOCKS);
   }
   if (g.opt.lora_mode) {   // likewise: the widest Linear over the block rows, the modulation Linears over the (evaluation, sample) rows
     const int64_t wide = std::max<int64_t>({3 * D, mlp, D, out_ch}), rows = std::max<int64_t>(B * L, (int64_t)S * B);
@@ -742,7 +748,8 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
       case ZERO_OR_H: if (value != 0 && value != f.H) FAIL(VC_ERR_ARG, "flux_set_option: qkv_heads must be 0 or num_heads = %d", f.H); break;
       case ANY: break;
     }
-    if ((o.member == &Options::lora_mode || o.member == &Options::adaptive || o.member == &Options::sde) && value != f.opt.*o.member) {
+    if ((o.member == &Options::lora_mode || o.member == &Options::adaptive || o.member == &Options::sde ||
+         o.member == &Options::eval_loss) && value != f.opt.*o.member) {
       if (f.in_flight)
         FAIL(VC_ERR_STATE, "flux_set_option: %s cannot change between vc_flux_sample_begin and vc_flux_sample_end", o.name);
       f.prepared = false;    // the workspace carve-up differs: vc_flux_workspace_bytes + vc_flux_prepare again
@@ -797,6 +804,9 @@ int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, 
     }
   }
   if (f.gapped) f.ragged = true;
+  f.n_img.assign((size_t)B, N);
+  for (int b = 0; b < B; ++b)
+    if (in->kv_len) f.n_img[b] = std::min(std::max(in->kv_len[b] - T, 0), N);
   // host tables -> pinned staging -> HBM
   const size_t n_rope = (size_t)B * L * 128;
   TRY(stage_begin(f, (n_rope + 128 + 4 * B + 64) * sizeof(float) + 8 * 256, e.buf, e.len));
@@ -865,6 +875,59 @@ int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, 
     f.mon_evals = 1;
   }
   return forward_rows(f, img, out, s, e);
+}
+
+// ONE evaluation as the flow-matching loss sees it (vcloze_hip.h): the path sample x_t -> XIN beside the cond columns, u_t -> FM_U,
+// vc_flux_forward's evaluation of XIN at timesteps 1 - t -> V, the masked squared error of (V, FM_U) -> loss
+int vc_flux_eval_loss_impl(void* handle, const void* x1, int32_t x1_is_f32, const void* cond, const float* t, const void* x0, uint64_t seed,
+                           uint64_t offset, float* loss, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (!f.prepared) FAIL(VC_ERR_STATE, "flux_eval_loss: call vc_flux_prepare first");
+  if (!f.opt.eval_loss || !f.FM_U)
+    FAIL(VC_ERR_STATE, "flux_eval_loss: set vc_flux_set_option(handle, \"eval_loss\", 1) before vc_flux_workspace_bytes / vc_flux_prepare");
+  if (f.cfg_on) FAIL(VC_ERR_STATE, "flux_eval_loss: true CFG is on (vc_flux_set_cfg): the loss is that of Flux.forward, never of forward_with_cfg");
+  if (f.in_flight) FAIL(VC_ERR_STATE, "flux_eval_loss: a trajectory is in flight (vc_flux_sample_end first)");
+  TRY(fresh_scale(f, "flux_eval_loss", e.buf, e.len));
+  if (!x1 || !t || !loss) FAIL(VC_ERR_ARG, "flux_eval_loss: null x1 / t / loss");
+  const int B = f.B, N = f.N, in_ch = f.cfg.in_channels, out_ch = f.cfg.out_channels;
+  if (!cond) FAIL(VC_ERR_ARG, "flux_eval_loss: img_in takes %d channels, x1 has %d: cond [B, N, %d] is required", in_ch, out_ch, in_ch - out_ch);
+  if ((uintptr_t)loss & 3) FAIL(VC_ERR_ARG, "flux_eval_loss: loss must be 4-byte aligned");
+  for (int b = 0; b < B; ++b) {
+    if (!(t[b] - t[b] == 0.0f)) FAIL(VC_ERR_ARG, "flux_eval_loss: t[%d] is not finite", b);
+    if (f.n_img[b] <= 0) FAIL(VC_ERR_ARG, "flux_eval_loss: sample %d has no valid image row (kv_len <= T): it has no loss", b);
+  }
+  if (!x0 && (uint64_t)B * N * out_ch - 1 > UINT64_MAX - offset) FAIL(VC_ERR_ARG, "flux_eval_loss: offset + B * N * out_channels wraps the 64-bit stream position");
+  TRY(monitor_fits(f, "flux_eval_loss", e.buf, e.len));
+  // the times: t as the plan takes it - rounded to bf16 for a bf16 x1 (transport.py:129: t.to(x1[0])) - and the model's 1 - t in that dtype
+  TRY(stage_begin(f, 2 * (B * sizeof(float) + 256), e.buf, e.len));
+  float* tp = stage_take<float>(f, B);
+  float* ts = stage_take<float>(f, B);
+  auto as_x1 = [&](float v) {   // a value of a tensor of x1's dtype: bf16 rounds to nearest even, as torch's .to(bfloat16)
+    if (x1_is_f32) return v;
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+    memcpy(&v, &u, 4);
+    return v;
+  };
+  for (int b = 0; b < B; ++b) {
+    tp[b] = as_x1(t[b]);
+    ts[b] = as_x1(1.0f - tp[b]);      // timesteps = 1 - t, a tensor of t's dtype
+  }
+  TRY(stage_send(f, f.FM_T, tp, B * sizeof(float), s, e.buf, e.len));
+  TRY(stage_send(f, f.TS, ts, B * sizeof(float), s, e.buf, e.len));
+  TRY(stage_end(f, s, e.buf, e.len));
+  TRY(vc_fm_plan_launch(x1, x1_is_f32, (int64_t)N * out_ch, out_ch, f.FM_T, x0, seed, offset, f.XIN, in_ch, f.FM_U, B, N, out_ch, s, e.buf, e.len));
+  HIP(hipMemcpy2DAsync(f.XIN + out_ch, (size_t)in_ch * 2, cond, (size_t)(in_ch - out_ch) * 2, (size_t)(in_ch - out_ch) * 2, (size_t)B * N,
+                       hipMemcpyDeviceToDevice, s), "hipMemcpy2DAsync");
+  TRY(time_precompute(f, 1, !x1_is_f32, s, e.buf, e.len));
+  f.steps_total = f.steps_done = 0;   // MOD now holds this evaluation's rows, not a trajectory's
+  if (f.mon_level) {      // row 0 of a zeroed log, as vc_flux_forward
+    TRY(vc_zero_fill_launch(f.mon_log, vcmon::log_bytes(f.mon_cap, f.mon_sites(), f.B), s, e.buf, e.len));
+    f.mon_evals = 1;
+  }
+  TRY(forward_rows(f, f.XIN, f.V, s, e));
+  return vc_fm_loss_launch(f.V, out_ch, f.FM_U, f.n_img.data(), 1, loss, f.FM_PART, B, N, out_ch, s, e.buf, e.len);
 }
 
 // HIP-event times of the launches of the product's plan, class by class (vcloze_hip.h): `evaluations` evaluations of the sample in

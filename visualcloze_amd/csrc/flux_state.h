@@ -48,6 +48,7 @@ struct Buffers {   // the workspace carve-up
   float *AD_Y0 = nullptr, *AD_Y1 = nullptr, *AD_DT = nullptr, *AD_OUT = nullptr, *AD_PART = nullptr;
   float *SD_Y = nullptr, *SD_XHAT = nullptr, *SD_K1 = nullptr, *SD_TAB = nullptr;   // stochastic sampler (carved only while option sde is on)
   uint64_t* SD_RNG = nullptr;
+  float *FM_U = nullptr, *FM_T = nullptr, *FM_PART = nullptr;      // vc_flux_eval_loss (carved only while option eval_loss is on): u_t, t, the sum's partials
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
   void* SK_WS = nullptr;               // f32 partial tiles of split-K GEMM remainders (VcGemmArgs.splitk_ws)
@@ -60,6 +61,7 @@ struct Options {
   int lora_mode = 0;
   int adaptive = 0;
   int sde = 0;
+  int eval_loss = 0;
 };
 enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
 #define OPT(name, clamp) {#name, &Options::name, clamp}
@@ -72,6 +74,7 @@ inline constexpr OptionRule OPTIONS[] = {      // (inline: ONE table for the thr
     OPT(lora_mode, BOOL),                                        // 1: every Linear runs un-merged (flux_engine.hip: lora_linear)
     OPT(adaptive, BOOL),                                         // 1: the workspace holds the adaptive solve's buffers (vc_flux_sample_dopri5)
     OPT(sde, BOOL),                                              // 1: ... the stochastic sampler's (vc_flux_sample_sde)
+    OPT(eval_loss, BOOL),                                        // 1: ... the flow-matching loss's (vc_flux_eval_loss)
 };
 #undef OPT
 inline bool operator==(const Options& a, const Options& b) {
@@ -133,6 +136,7 @@ struct Flux : Buffers {
   bool ws_sized = false;     // vc_flux_workspace_bytes / vc_flux_prepare have answered with the current carve-up
   int B = 0, T = 0, N = 0, L = 0, Lp = 0, S = 0;
   bool ragged = false, gapped = false;
+  std::vector<int32_t> n_img;          // per prepared sample: the valid image rows, kv_len - T clamped to [0, N] (vc_flux_eval_loss)
   char* base = nullptr;
   // a captured step: ONE graph (g[0]), or with the step cache on three - head, tail-compute, tail-reuse (an entry of `graphs` is a
   // whole step, so a cached trajectory never evicts a graph of its own).  step: the one of the sample in flight

@@ -4,6 +4,7 @@
 // written out, where torch's own kernel fuses.
 #include "vcloze_internal.h"
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -12,6 +13,38 @@
 
 namespace {
 bool finite_d(double v) { return v - v == 0.0; }
+// time_shift(mu, 1.0, t) of transport/utils.py in torch's f32 operations, mu = get_lin_function(y1=0.5, y2=1.15)(n_tokens) in Python
+// floats: E = f32(exp(mu)); the endpoints 0 and 1 go through inf arithmetic as the reference's do
+float shift_exp(int32_t n_tokens) {
+#pragma clang fp contract(off)
+  const double m = (1.15 - 0.5) / (4096.0 - 256.0);
+  const double b = 0.5 - m * 256.0;
+  const double mx = m * (double)n_tokens;
+  const double mu = mx + b;
+  return (float)exp(mu);
+}
+float shift_f32(float E, float t) {
+#pragma clang fp contract(off)
+  const float u = 1.0f - t;                // t = 1 - t
+  const float q = 1.0f / u;                // 1 / t: reciprocal (times 1)
+  const float r = q - 1.0f;                // (1 / t - 1) ** 1.0
+  const float den = E + r;
+  const float rec = 1.0f / den;            // number / Tensor = reciprocal * number
+  const float v = rec * E;
+  return 1.0f - v;
+}
+// "<number>" up to `end`: digits, sign, point and exponent only (what Python's float() and strtod read alike), finite
+bool plain_number(const char* p, const char* end, double* v) {
+  if (p == end || end - p > 63) return false;
+  char buf[64];
+  for (const char* c = p; c < end; ++c)
+    if (!((*c >= '0' && *c <= '9') || *c == '+' || *c == '-' || *c == '.' || *c == 'e' || *c == 'E')) return false;
+  memcpy(buf, p, (size_t)(end - p));
+  buf[end - p] = 0;
+  char* stop = nullptr;
+  *v = strtod(buf, &stop);
+  return stop == buf + (end - p) && finite_d(*v);
+}
 }  // namespace
 
 int vc_time_grid_impl(int32_t n_points, int32_t n_tokens, double t0, double t1, int32_t do_shift, double time_shifting_factor, float* out,
@@ -42,20 +75,50 @@ int vc_time_grid_impl(int32_t n_points, int32_t n_tokens, double t0, double t1, 
     }
   }
   if (do_shift) {                              // time_shift(mu, 1.0, t) with mu = get_lin_function(y1=0.5, y2=1.15)(n_tokens), Python floats
-    const double m = (1.15 - 0.5) / (4096.0 - 256.0);
-    const double b = 0.5 - m * 256.0;
-    const double mx = m * (double)n_tokens;
-    const double mu = mx + b;
-    const float E = (float)exp(mu);
-    for (int i = 0; i < n_points; ++i) {
-      const float u = 1.0f - out[i];           // t = 1 - t
-      const float q = 1.0f / u;                // 1 / t: reciprocal (times 1)
-      const float r = q - 1.0f;                // (1 / t - 1) ** 1.0
-      const float den = E + r;
-      const float rec = 1.0f / den;            // number / Tensor = reciprocal * number
-      const float v = rec * E;
-      out[i] = 1.0f - v;
+    const float E = shift_exp(n_tokens);
+    for (int i = 0; i < n_points; ++i) out[i] = shift_f32(E, out[i]);
+  }
+  return VC_OK;
+}
+
+// Transport.sample's training times (transport.py:107-129) for Linear + velocity - check_interval gives (0, 1) - from the caller's
+// base draws, in torch's f32 operations: "uniform" t = u * f32(t1 - t0) + f32(t0) with (t0, t1) = (0, 1) or "uniform_<t0>_<t1>";
+// "lognorm" t = 1 / (1 + exp(-u)) * 1 + 0, the exponential taken in double and rounded once to f32 (the correctly rounded f32
+// exponential; torch's vectorised one is within an ulp of it); then time_shift with do_shift
+int vc_fm_times_impl(const char* snr_type, const float* base, int32_t n, int32_t n_tokens, int32_t do_shift, float* out, char* err, int errlen) {
+#pragma clang fp contract(off)
+  if (!snr_type || !base || !out) { snprintf(err, errlen, "fm_times: null snr_type / base / out"); return VC_ERR_ARG; }
+  if (n <= 0) { snprintf(err, errlen, "fm_times: n = %d must be positive", n); return VC_ERR_ARG; }
+  if (n_tokens < 1) { snprintf(err, errlen, "fm_times: n_tokens = %d must be positive", n_tokens); return VC_ERR_ARG; }
+  double t0 = 0.0, t1 = 1.0;
+  bool lognorm = false;
+  if (!strcmp(snr_type, "lognorm")) lognorm = true;
+  else if (!strncmp(snr_type, "uniform_", 8)) {
+    const char* a = snr_type + 8;
+    const char* mid = strchr(a, '_');
+    if (!mid || strchr(mid + 1, '_') || !plain_number(a, mid, &t0) || !plain_number(mid + 1, mid + 1 + strlen(mid + 1), &t1)) {
+      snprintf(err, errlen, "fm_times: snr_type '%.64s' is not 'uniform_<t0>_<t1>' with two finite numbers", snr_type);
+      return VC_ERR_ARG;
     }
+  } else if (strcmp(snr_type, "uniform")) {
+    snprintf(err, errlen, "fm_times: Not implemented snr_type '%.64s' ('uniform', 'uniform_<t0>_<t1>', 'lognorm')", snr_type);
+    return VC_ERR_ARG;
+  }
+  const float scale = (float)(t1 - t0), shift = (float)t0;
+  for (int i = 0; i < n; ++i) {
+    float v = base[i];
+    if (lognorm) {
+      const float neg = -v;
+      const float ex = (float)exp((double)neg);
+      const float den = 1.0f + ex;
+      v = 1.0f / den;
+    }
+    const float m = v * scale;
+    out[i] = m + shift;
+  }
+  if (do_shift) {
+    const float E = shift_exp(n_tokens);
+    for (int i = 0; i < n; ++i) out[i] = shift_f32(E, out[i]);
   }
   return VC_OK;
 }

@@ -89,6 +89,12 @@ int vc_residual_change_launch(const void* h0, const void* h1, const void* p, voi
                               int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride,
                           int32_t B, int64_t n, hipStream_t s, char* err, int errlen);
+// fm_loss.hip: the flow-matching loss's two passes (vc_fm_plan, vc_fm_loss); grid_rules.hip: its training times
+int vc_fm_plan_launch(const void* x1, int x1_is_f32, int64_t x1_bstride, int64_t x1_ld, const float* t, const void* x0, uint64_t seed,
+                      uint64_t offset, void* xt, int64_t xt_ld, float* ut, int B, int64_t rows, int cols, hipStream_t s, char* err, int errlen);
+int vc_fm_loss_launch(const void* out, int64_t out_ld, const float* ut, const int32_t* valid_rows, int valid_on_host, float* loss, float* scratch,
+                      int B, int64_t rows, int cols, hipStream_t s, char* err, int errlen);
+int vc_fm_times_impl(const char* snr_type, const float* base, int32_t n, int32_t n_tokens, int32_t do_shift, float* out, char* err, int errlen);
 // monitor.hip: the numerics monitor's reduction (vc_tensor_stats) and the scan of a log for the entry with nonfinite != 0 that was written first
 int vc_tensor_stats_launch(const void* x, int x_is_f32, int64_t bstride, int64_t ld, int B, int64_t rows, int cols, VcStat* out, int64_t out_stride,
                            const int32_t* row_ptr, int capacity, float* scratch, hipStream_t s, char* err, int errlen);
@@ -193,6 +199,8 @@ int64_t vc_flux_workspace_bytes_impl(void* handle, int32_t B, int32_t T, int32_t
 int vc_flux_prepare_impl(void* handle, const VcFluxInputs* in, void* workspace, int64_t workspace_bytes, hipStream_t s, char* err, int errlen);
 int vc_flux_forward_impl(void* handle, const void* img, const float* timesteps, int32_t timesteps_is_bf16, void* out, hipStream_t s,
                          char* err, int errlen);
+int vc_flux_eval_loss_impl(void* handle, const void* x1, int32_t x1_is_f32, const void* cond, const float* t, const void* x0, uint64_t seed,
+                           uint64_t offset, float* loss, hipStream_t s, char* err, int errlen);
 int vc_flux_sample_begin_impl(void* handle, int32_t method, const void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                               hipStream_t s, char* err, int errlen);
 int vc_flux_sample_steps_impl(void* handle, int32_t n_steps, void* trajectory, hipStream_t s, char* err, int errlen);

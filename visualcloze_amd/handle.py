@@ -149,6 +149,7 @@ class FluxHandle(_Handle):
         self.lora_mode = 0
         self.adaptive = 0
         self.sde = 0
+        self.eval_loss_on = 0
         if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
             scales = []
             for name, R in weights.ref.items():
@@ -365,6 +366,14 @@ class FluxHandle(_Handle):
             self.sde = int(bool(on))
             self.geom = None
 
+    def set_eval_loss(self, on: bool) -> None:
+        """vc_flux_set_option("eval_loss"): 1 = the workspace holds u_t of the flow-matching loss (`eval_loss`).  A switch needs a new
+        prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
+        hip._check(hip.lib().vc_flux_set_option(self.h, b"eval_loss", int(bool(on))), "vc_flux_set_option(eval_loss)")
+        if int(bool(on)) != self.eval_loss_on:
+            self.eval_loss_on = int(bool(on))
+            self.geom = None
+
     def set_lora_scale(self, scale: float) -> None:
         """vc_flux_set_lora_scale: the scale of every pair; a bf16 value, anything else is refused, and so is a change while a
         trajectory is in flight.  Call `prepare` again after a change (forward / sample_* refuse a prepared state of the old scale);
@@ -423,7 +432,8 @@ class FluxHandle(_Handle):
         return {"computed": c.value, "reused": r.value, "metrics": [float(m[i]) for i in range(n)]}
 
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
-        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ()) + (("sde",) if self.sde else ())
+        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ()) + (("sde",) if self.sde else ()) + \
+            (("eval_loss",) if self.eval_loss_on else ())
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:
@@ -473,6 +483,34 @@ class FluxHandle(_Handle):
             raise hip.VclozeHipError(f"vc_flux_forward: {t.size} timesteps for a batch of {self.geom[0]}")
         hip._check(hip.lib().vc_flux_forward(self.h, img.data_ptr(), _fp(t), int(bool(timesteps_is_bf16)), out.data_ptr(),
                                              stream if stream is not None else hip.cur_stream()), "vc_flux_forward")
+
+    def eval_loss(self, x1, cond, t, x0=None, seed: int = 0, offset: int = 0, loss=None, stream=None) -> torch.Tensor:
+        """vc_flux_eval_loss (after `set_eval_loss(True)` and a prepare): the flow-matching loss of the prepared samples, f32 [B] on the
+        device.  x1 [B, N, out] bf16 / f32 contiguous, rows in the handle's order; cond [B, N, in - out] bf16; t: B
+        values (host); x0: a contiguous tensor of x1's shape and dtype, or None = drawn in the kernel at (seed, offset + flat index)."""
+        if self.geom is None:
+            raise hip.VclozeHipError("vc_flux_eval_loss: call prepare first")
+        B, _, N, _ = self.geom
+        p = self.params
+        if x1.dtype not in (torch.bfloat16, torch.float32) or tuple(x1.shape) != (B, N, p.out_channels) or not x1.is_contiguous():
+            raise hip.VclozeHipError(f"vc_flux_eval_loss: a contiguous bf16 / f32 x1 of shape {(B, N, p.out_channels)} expected, got "
+                                     f"{x1.dtype} {tuple(x1.shape)}")
+        if cond is None:
+            raise hip.VclozeHipError(f"vc_flux_eval_loss: cond {(B, N, p.in_channels - p.out_channels)} is required (x1 || cond feeds img_in)")
+        hip._bf16(cond, "cond")
+        if tuple(cond.shape) != (B, N, p.in_channels - p.out_channels) or not cond.is_contiguous():
+            raise hip.VclozeHipError(f"vc_flux_eval_loss: a contiguous cond of shape {(B, N, p.in_channels - p.out_channels)} expected")
+        if x0 is not None and (x0.dtype != x1.dtype or x0.shape != x1.shape or not x0.is_contiguous()):
+            raise hip.VclozeHipError("vc_flux_eval_loss: x0 must be a contiguous tensor of x1's shape and dtype")
+        tt = _f32(t).reshape(-1)
+        if tt.size != B:
+            raise hip.VclozeHipError(f"vc_flux_eval_loss: {tt.size} times for a batch of {B}")
+        if loss is None:
+            loss = torch.empty(B, dtype=torch.float32, device=self.dev)
+        hip._check(hip.lib().vc_flux_eval_loss(self.h, x1.data_ptr(), int(x1.dtype == torch.float32), hip._p(cond), _fp(tt), hip._p(x0),
+                                               hip._u64(seed, "seed"), hip._u64(offset, "offset"), loss.data_ptr(),
+                                               stream if stream is not None else hip.cur_stream()), "vc_flux_eval_loss")
+        return loss
 
     @staticmethod
     def _method(method) -> int:

@@ -235,6 +235,9 @@ SYMBOLS = {
     "vc_cfg_combine": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _vp]),
     "vc_monitor_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "vc_tensor_stats": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "vc_fm_plan": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _i64, _vp, _i32, _i64, _i32, _vp]),
+    "vc_fm_loss": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp]),
+    "vc_fm_times": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), _i32, _i32, _i32, C.POINTER(C.c_float)]),
     "vc_sdedit_mix": (C.c_int, [_vp, _vp, C.c_double, _vp, _i64, _vp]),
     "vc_pack_latent": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vc_pack_mask": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
@@ -282,6 +285,7 @@ SYMBOLS = {
     "vc_flux_workspace_bytes": (_i64, [_vp, _i32, _i32, _i32, _i32]),
     "vc_flux_prepare": (C.c_int, [_vp, C.POINTER(FluxInputs), _vp, _i64, _vp]),
     "vc_flux_forward": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), _i32, _vp, _vp]),
+    "vc_flux_eval_loss": (C.c_int, [_vp, _vp, _i32, _vp, C.POINTER(C.c_float), _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     "vc_flux_sample_euler": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
     "vc_flux_sample_begin": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp]),
     "vc_flux_sample_steps": (C.c_int, [_vp, _i32, _vp, _vp]),
@@ -1038,6 +1042,67 @@ def tensor_stats(x, out=None, row_ptr=None, capacity: int = 1, stream=None) -> t
     return out
 
 
+FM_LOSS_MAX_BLOCKS = 256             # VC_FM_LOSS_MAX_BLOCKS
+FM_MAX_HOST_COUNTS = 64              # VC_FM_MAX_HOST_COUNTS
+
+
+def fm_plan(x1, t, xt, x0=None, seed=0, offset=0, ut=None, stream=None):
+    """vc_fm_plan: the path sample of the flow-matching loss.  x1 [B, rows, cols] bf16 / f32 with unit column stride (any row / sample
+    strides); t [B] f32 on the device; xt: a bf16 [B, rows, ld] tensor (or [B * rows, ld]) with ld >= cols whose first `cols` columns
+    receive bf16(t x1 + (1 - t) x0) - the other columns are left alone; x0: a contiguous [B, rows, cols] tensor of x1's dtype, or None:
+    drawn in the kernel at (seed, offset + flat index), what `randn(x1.shape, seed, offset, x1.dtype)` holds.  Returns ut = x1 - x0, f32
+    [B, rows, cols]."""
+    if x1.dtype not in (torch.bfloat16, torch.float32) or x1.dim() != 3 or x1.stride(2) != 1:
+        raise VclozeHipError("vc_fm_plan: a [B, rows, cols] bf16 / f32 x1 with unit column stride expected")
+    B, R, Cc = x1.shape
+    _bf16(xt, "xt")
+    if xt.dim() not in (2, 3) or xt.stride(-1) != 1 or xt.numel() == 0 or xt.shape[-1] < Cc or xt.numel() // xt.shape[-1] != B * R or \
+            (xt.dim() == 3 and xt.stride(0) != R * xt.stride(1)):
+        raise VclozeHipError(f"vc_fm_plan: xt must hold {B * R} evenly strided rows of at least {Cc} columns, got {tuple(xt.shape)}")
+    if t.dtype != torch.float32 or not t.is_cuda or t.numel() != B or not t.is_contiguous():
+        raise VclozeHipError(f"vc_fm_plan: t must be a contiguous f32 device tensor of {B} values")
+    if x0 is not None and (x0.dtype != x1.dtype or tuple(x0.shape) != (B, R, Cc) or not x0.is_contiguous()):
+        raise VclozeHipError(f"vc_fm_plan: x0 must be a contiguous {x1.dtype} tensor of shape {(B, R, Cc)}")
+    if ut is None:
+        ut = torch.empty(B, R, Cc, dtype=torch.float32, device=x1.device)
+    elif ut.dtype != torch.float32 or ut.numel() != B * R * Cc or not ut.is_contiguous():
+        raise VclozeHipError("vc_fm_plan: ut must be a contiguous f32 tensor of x1's element count")
+    _check(lib().vc_fm_plan(x1.data_ptr(), int(x1.dtype == torch.float32), x1.stride(0), x1.stride(1), t.data_ptr(), _p(x0), _u64(seed, "seed"),
+                            _u64(offset, "offset"), xt.data_ptr(), xt.stride(-2), ut.data_ptr(), B, R, Cc,
+                            stream if stream is not None else cur_stream()), "vc_fm_plan")
+    return ut
+
+
+def fm_loss(out, ut, valid_rows=None, loss=None, stream=None):
+    """vc_fm_loss: loss[b] = sum over the first valid_rows[b] rows of ((-out) - ut)^2 / (valid_rows[b] * cols), f32 [B], in the fixed
+    summation order of include/vcloze_hip.h (`transport.fm_loss_terms(ordered=True)` restates it).  out: the model's bf16 output [B, rows,
+    cols'] with unit column stride, rows stride(1) apart, samples rows * stride(1) apart (cols' >= cols: a column window is fine); ut f32
+    [B, rows, cols] contiguous; valid_rows: None (every row), an int32 device tensor [B], or a sequence of B ints (at most
+    FM_MAX_HOST_COUNTS, each in [1, rows])."""
+    _bf16(out, "out")
+    if ut.dtype != torch.float32 or ut.dim() != 3 or not ut.is_contiguous():
+        raise VclozeHipError("vc_fm_loss: ut must be a contiguous f32 [B, rows, cols] tensor")
+    B, R, Cc = ut.shape
+    if out.dim() != 3 or tuple(out.shape) != (B, R, Cc) or out.stride(2) != 1 or (B > 1 and out.stride(0) != R * out.stride(1)):
+        raise VclozeHipError(f"vc_fm_loss: out must be a bf16 view of shape {(B, R, Cc)} with evenly strided rows")
+    host, vp, keep = 0, None, None
+    if torch.is_tensor(valid_rows):
+        if valid_rows.dtype != torch.int32 or not valid_rows.is_cuda or valid_rows.numel() != B or not valid_rows.is_contiguous():
+            raise VclozeHipError(f"vc_fm_loss: device counts must be a contiguous int32 tensor of {B} values")
+        vp = valid_rows.data_ptr()
+    elif valid_rows is not None:
+        keep = (C.c_int32 * len(valid_rows))(*[int(v) for v in valid_rows])
+        if len(valid_rows) != B:
+            raise VclozeHipError(f"vc_fm_loss: {len(valid_rows)} counts for {B} samples")
+        host, vp = 1, C.cast(keep, C.c_void_p)
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=ut.device)
+    scratch = torch.empty(B * FM_LOSS_MAX_BLOCKS, dtype=torch.float32, device=ut.device)
+    _check(lib().vc_fm_loss(out.data_ptr(), out.stride(1), ut.data_ptr(), vp, host, loss.data_ptr(), scratch.data_ptr(), B, R, Cc,
+                            stream if stream is not None else cur_stream()), "vc_fm_loss")
+    return loss
+
+
 def _residual_op(fn, what, a, b, out, stream):
     """a, b, out: [B, n...] bf16, each sample's n elements contiguous, samples stride(0) apart (views of row ranges are fine)"""
     _bf16(a, "a"); _bf16(b, "b")
@@ -1130,6 +1195,17 @@ def time_grid(n_points: int, n_tokens: int, t0: float = 0.0, t1: float = 1.0, do
     out = torch.empty(max(int(n_points), 0), dtype=torch.float32)
     _check(lib().vc_time_grid(int(n_points), int(n_tokens), float(t0), float(t1), int(bool(do_shift)), float(time_shifting_factor or 0.0),
                               C.cast(out.data_ptr(), C.POINTER(C.c_float)) if out.numel() else None), "vc_time_grid")
+    return out
+
+
+def fm_times(base, snr_type: str, n_tokens: int, do_shift: bool = True) -> torch.Tensor:
+    """vc_fm_times: the training times of Transport.sample for the f32 base draws `base` (uniforms, or standard normals for "lognorm"),
+    bit for bit `transport.fm_times(base.float(), snr_type, n_tokens, do_shift)`.  A CPU f32 tensor; an unknown or malformed snr_type
+    raises VclozeHipError."""
+    b = torch.as_tensor(base).detach().to("cpu", torch.float32).contiguous().reshape(-1)
+    out = torch.empty(b.numel(), dtype=torch.float32)
+    fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float)) if t.numel() else None  # noqa: E731
+    _check(lib().vc_fm_times(_cstr(snr_type), fp(b), b.numel(), int(n_tokens), int(bool(do_shift)), fp(out)), "vc_fm_times")
     return out
 
 

@@ -25,6 +25,12 @@ sample_ode only.  `sde_plan` turns a setting into one coefficient row per evalua
 is the literal torch restatement of the loop, and the fused path is vc_flux_sample_sde: the captured evaluation with vc_sde_stage
 behind it, the noise drawn inside that kernel from the library's counter-based stream.
 
+`Transport.sample` / `Transport.training_losses` are the reference's training objective (transport.py:98-176: the masked flow-matching
+loss of ONE model evaluation at a drawn time and noise) as an EVALUATION: forward only, under torch.no_grad(), nothing here can be
+back-propagated.  `fm_times` is the rule that maps base draws to training times (bit for bit vc_fm_times for f32 draws), `fm_loss_terms`
+the loss in literal torch for any callable, and the fused path is vc_flux_eval_loss: vc_fm_plan in front of the handle's single
+evaluation and vc_fm_loss behind it, one call per chunk of samples.
+
 The step rules (`STEP_RULES`) are torchdiffeq 0.2.x's fixed-grid solvers as recalled - unpinned against real
 torchdiffeq, which was not available to check against (as the Euler rule, tests/golden/make_golden.py).  They
 are written ONCE, as the literal torch expressions: a correction is a one-line change here and in
@@ -33,6 +39,7 @@ csrc/elementwise.hip (ode_update).
 from __future__ import annotations
 
 import math
+import re
 from contextlib import contextmanager
 from functools import partial
 from typing import Callable, Optional
@@ -68,10 +75,227 @@ def solver_time_grid(num_steps: int, n_tokens: int, t0: float, t1: float, do_shi
     return t
 
 
+_SNR_UNIFORM = re.compile(r"^uniform_([0-9eE+\-.]+)_([0-9eE+\-.]+)$")
+
+
+def parse_snr_type(snr_type: str):
+    """-> ("uniform" | "lognorm", t0, t1) of Transport.sample's `snr_type` (transport.py:112-121): "uniform", "uniform_<t0>_<t1>" (two
+    finite plain decimal numbers) or "lognorm"; (t0, t1) = (0, 1) - check_interval for Linear + velocity - unless the string gives
+    them.  Anything else raises: NotImplementedError for an unknown type, as the reference, ValueError for a malformed interval
+    (where the reference's unpacking or float() fails).  vc_fm_times refuses the same strings."""
+    if not isinstance(snr_type, str):
+        raise NotImplementedError("Not implemented snr_type %s" % (snr_type,))
+    if snr_type == "lognorm":
+        return "lognorm", 0.0, 1.0
+    if snr_type == "uniform":
+        return "uniform", 0.0, 1.0
+    if snr_type.startswith("uniform_"):
+        m = _SNR_UNIFORM.match(snr_type)
+        try:
+            t0, t1 = (float(m.group(1)), float(m.group(2))) if m else (math.nan, math.nan)
+        except ValueError:
+            t0 = t1 = math.nan
+        if not (math.isfinite(t0) and math.isfinite(t1)):
+            raise ValueError(f"snr_type {snr_type!r} is not 'uniform_<t0>_<t1>' with two finite numbers")
+        return "uniform", t0, t1
+    raise NotImplementedError("Not implemented snr_type %s" % snr_type)
+
+
+def _exp_f32(x: torch.Tensor) -> torch.Tensor:
+    """exp of an f32 tensor, each value taken in double (libm, as vc_fm_times) and rounded once to f32: the correctly rounded f32
+    exponential, which torch's vectorised CPU exp is not (it is within an ulp of it)"""
+    def one(v: float) -> float:
+        try:
+            return math.exp(v)
+        except OverflowError:
+            return math.inf
+    return torch.tensor([one(float(v)) for v in x.reshape(-1).tolist()], dtype=torch.float64).to(torch.float32).reshape(x.shape)
+
+
+def fm_times(base: torch.Tensor, snr_type: str, n_tokens: int, do_shift: bool) -> torch.Tensor:
+    """Transport.sample's training times (transport.py:112-127) from its base draws - torch.rand for "uniform" / "uniform_<t0>_<t1>",
+    torch.normal(0, 1) for "lognorm" - as the reference's own torch expressions, in the draws' dtype:
+        uniform   t = base * (t1 - t0) + t0          lognorm   t = 1 / (1 + exp(-base)) * (t1 - t0) + t0
+    then time_shift(mu(n_tokens), 1.0, t) with do_shift.  f64 draws give the reference's f64 bits; f32 draws give vc_fm_times' bits
+    (hip.fm_times), which are the reference's f32 operations except that the exponential of "lognorm" is the correctly rounded one
+    (`_exp_f32`).  Any other dtype is computed in f32."""
+    kind, t0, t1 = parse_snr_type(snr_type)
+    if base.dtype not in (torch.float32, torch.float64):
+        base = base.to(torch.float32)
+    if kind == "uniform":
+        t = base * (t1 - t0) + t0
+    else:
+        e = torch.exp(-base) if base.dtype == torch.float64 else _exp_f32(-base.cpu()).to(base.device)
+        t = 1 / (1 + e) * (t1 - t0) + t0
+    if do_shift:
+        t = time_shift(get_lin_function(y1=0.5, y2=1.15)(n_tokens), 1.0, t)
+    return t
+
+
+def fm_path(t: torch.Tensor, x0: torch.Tensor, x1: torch.Tensor):
+    """ICPlan.plan of the reference for the Linear path (alpha = t, sigma = 1 - t): -> (x_t, u_t) = (t x1 + (1 - t) x0, x1 - x0) with t
+    [B] broadcast over the samples.  f64 tensors: the reference's f64 expressions, bit for bit.  f32 / bf16 tensors: vc_fm_plan's
+    arithmetic - every operand converted to f32, t * x1 and (1 - t) * x0 rounded on their own, x_t rounded ONCE to bf16 and handed
+    back in x1's dtype, u_t in f32."""
+    tb = t.view(t.size(0), *([1] * (x1.dim() - 1)))
+    if x1.dtype == torch.float64:
+        return tb * x1 + (1 - tb) * x0, 1 * x1 + -1 * x0
+    tf, a, z = tb.to(torch.float32), x1.to(torch.float32), x0.to(torch.float32)
+    return (tf * a + (1 - tf) * z).to(torch.bfloat16).to(x1.dtype), a - z
+
+
+def _fm_ordered_sum(sq: torch.Tensor, rows_total: int) -> torch.Tensor:
+    """sum of the f32 squares `sq` [valid rows, cols] of ONE sample in vc_fm_loss's order (include/vcloze_hip.h): units of 8 elements
+    along a row, dealt round-robin to nblk * 256 threads with nblk = min(ceil(rows_total * ceil(cols / 8) / 256), 256), a thread's
+    elements added in ascending order, the block's 256 sums and then the nblk block sums down one binary tree"""
+    sq = sq.detach().to("cpu", torch.float32)
+    R, cols = sq.shape
+    upr = (cols + 7) // 8
+    nblk = min((rows_total * upr + 255) // 256, hip.FM_LOSS_MAX_BLOCKS)
+    T = nblk * 256
+    units = torch.zeros(R, upr * 8, dtype=torch.float32)       # (x + 0 = x for the squares: zero padding does not show)
+    units[:, :cols] = sq
+    units = units.view(R * upr, 8)
+    rounds = max(-(-(R * upr) // T), 1)
+    pad = torch.zeros(rounds * T, 8, dtype=torch.float32)
+    pad[:R * upr] = units
+    pad = pad.view(rounds, T, 8)
+    s = torch.zeros(T, dtype=torch.float32)
+    for r in range(rounds):
+        for e in range(8):
+            s = s + pad[r, :, e]
+
+    def tree(v):
+        o = 128
+        while o >= 1:
+            v = v[..., :o] + v[..., o:2 * o]
+            o //= 2
+        return v[..., 0]
+
+    part = torch.zeros(256, dtype=torch.float32)
+    part[:nblk] = tree(s.view(nblk, 256))
+    return tree(part)
+
+
+def fm_loss_reduce(out: torch.Tensor, ut: torch.Tensor, img_mask: Optional[torch.Tensor] = None, ordered: bool = False) -> torch.Tensor:
+    """The reduction of Transport.training_losses (transport.py:149-171) for a tensor x1: model_output = -out; with an image mask
+    sum(((model_output - ut) * mask)^2) / (mask.sum * D) per sample, else the mean over all non-batch dimensions.  f64 `ut`: the
+    reference's expressions in f64.  Otherwise f32, d = (-out) - ut, in torch's own summation order - or with `ordered` in the fixed
+    order of vc_fm_loss over each sample's valid rows (taken in row order: the handle's valid-first order), divided by
+    f32(valid rows * D): the kernel's bits.  -> [B]"""
+    B = ut.shape[0]
+    if ut.dtype == torch.float64:
+        model_output = -out.to(torch.float64)
+        if img_mask is not None:
+            D = model_output.shape[-1]
+            mask_loss = (model_output - ut) * img_mask.unsqueeze(-1)
+            return (mask_loss ** 2).sum(dim=list(range(1, ut.dim()))) / (img_mask.sum(dim=1) * D)
+        return torch.mean((model_output - ut) ** 2, dim=list(range(1, ut.dim())))
+    d = (0 - out.to(torch.float32)) - ut.to(torch.float32)
+    sq = d * d
+    if not ordered:
+        if img_mask is not None:
+            m = img_mask.to(sq.device, torch.float32)
+            return (sq * m.unsqueeze(-1)).sum(dim=list(range(1, ut.dim()))) / (m.sum(dim=1) * sq.shape[-1])
+        return torch.mean(sq, dim=list(range(1, ut.dim())))
+    sq = sq.reshape(B, -1, sq.shape[-1]).cpu()
+    rows, cols = sq.shape[1:]
+    res = []
+    for b in range(B):
+        keep = torch.ones(rows, dtype=torch.bool) if img_mask is None else img_mask[b].reshape(-1).cpu() != 0
+        n = int(keep.sum())
+        total = _fm_ordered_sum(sq[b][keep], rows)
+        res.append(total / torch.tensor(float(n * cols), dtype=torch.float64).to(torch.float32))
+    return torch.stack(res).to(ut.device)
+
+
+@torch.no_grad()
+def fm_loss_terms(model: Callable, x1: torch.Tensor, t: torch.Tensor, x0: torch.Tensor, model_kwargs: Optional[dict] = None,
+                  cond: Optional[torch.Tensor] = None, ordered: bool = False) -> dict:
+    """Transport.training_losses (transport.py:132-176) for given t [B] and x0, in literal torch, for any callable and any float dtype:
+    -> {"loss", "task_loss" [B], "t"}.  EVALUATION only: it runs under torch.no_grad() and nothing here can be back-propagated.
+    x_t, u_t = `fm_path`; out = model(x_t || cond, timesteps = 1 - t, **model_kwargs); the reduction = `fm_loss_reduce` with
+    model_kwargs["img_mask"] where it is given.  f64 in: the reference's f64 computation.  f32 / bf16 in: the arithmetic of
+    vc_fm_plan / vc_fm_loss (t in x1's dtype, x_t rounded once to bf16, u_t and the loss in f32); with `ordered` the sum follows the
+    kernel's stated order, so a test can ask for its bits."""
+    model_kwargs = {} if model_kwargs is None else model_kwargs
+    t = t.to(x1[0])
+    x0 = x0.to(x1)
+    xt, ut = fm_path(t, x0, x1)
+    xin = torch.cat((xt, cond.to(xt)), dim=-1) if cond is not None else xt
+    out = model(xin, timesteps=1 - t, **model_kwargs)
+    assert out.shape == ut.shape, f"the model returned {tuple(out.shape)} for a target of {tuple(ut.shape)}"
+    loss = fm_loss_reduce(out.detach(), ut, model_kwargs.get("img_mask"), ordered).detach()
+    return {"loss": loss, "task_loss": loss.clone(), "t": t}
+
+
 class Transport:
-    def __init__(self, path_type: str, prediction: str, do_shift: bool):
-        self.path_type, self.prediction, self.do_shift = path_type, prediction, do_shift
+    def __init__(self, path_type: str, prediction: str, do_shift: bool, snr_type: str = "uniform"):
+        self.path_type, self.prediction, self.do_shift, self.snr_type = path_type, prediction, do_shift, snr_type
         self.train_eps = self.sample_eps = 0  # velocity & Linear is stable everywhere (transport/__init__.py:46-48)
+
+    def sample(self, x1, snr_type=None):
+        """transport.py:98-130: draw x0 and t for the data x1 [B, N, C] -> (t, x0, x1), with torch.randn_like, then torch.rand
+        ("uniform...") or torch.normal ("lognorm") exactly as the reference draws them, so the same torch.manual_seed gives the
+        reference's t and x0 on the CPU.  t = `fm_times` of the base draw with n_tokens = x1.shape[1], converted to x1's dtype and device."""
+        if isinstance(x1, (list, tuple)):
+            raise NotImplementedError("Transport.sample: a list of tensors (the reference's variable-size branch) is not implemented; pass "
+                                      "one [B, N, C] tensor")
+        kind, _, _ = parse_snr_type(self.snr_type if snr_type is None else snr_type)
+        x0 = torch.randn_like(x1)
+        if kind == "uniform":
+            base = torch.rand((len(x1),))
+        else:
+            base = torch.normal(mean=0.0, std=1.0, size=(len(x1),))
+        t = fm_times(base, self.snr_type if snr_type is None else snr_type, x1.shape[1], self.do_shift)
+        return t.to(x1[0]), x0, x1
+
+    @torch.no_grad()
+    def training_losses(self, model, x1, model_kwargs=None, extra_kwargs=None, *, t=None, x0=None, rng=None):
+        """transport.py:132-176 as an EVALUATION: the flow-matching loss of one model evaluation at a drawn (or given) time t [B] and
+        noise x0 -> {"loss", "task_loss": [B], "t": [B]} - masked by model_kwargs["img_mask"] where given, the mean over all
+        non-batch elements otherwise; extra_kwargs["cond"] is concatenated behind x_t.  It runs under torch.no_grad(): `loss` carries
+        no graph and NOTHING HERE CAN BE BACK-PROPAGATED - it is the validation loss, not a training step.
+        t / x0 None: drawn as `sample` draws them (torch.manual_seed reproduces).  rng: a `pipeline.NoiseStream` - x0 comes from the
+        library's stream at rng.offset, which advances by x1.numel(); a `TorchNoiseStream` draws x0 = rng.randn(x1.shape) first.
+        Fused (vc_flux_eval_loss, one call per chunk of samples through `ChunkPlan`) for the bound `forward` of a visualcloze_amd.Flux that
+        has the C handle and a bf16 / f32 x1; a NoiseStream's x0 is then drawn inside the kernel, element i of a chunk - the flat index
+        in its [bs, N, C] rows IN THE HANDLE'S ROW ORDER (image rows valid-first per sample) - at offset + i, chunk after chunk.  Eager
+        (`fm_loss_terms`) for everything else.  A list of tensors raises NotImplementedError."""
+        if isinstance(x1, (list, tuple)):
+            raise NotImplementedError("training_losses: a list of tensors (the reference's variable-size branch) is not implemented; pass "
+                                      "one [B, N, C] tensor")
+        model_kwargs = {} if model_kwargs is None else model_kwargs
+        cond = (extra_kwargs or {}).get("cond")
+        if rng is not None and x0 is not None:
+            raise ValueError("training_losses: pass x0 or rng, not both")
+        owner, kind, kw, _ = _classify(model, model_kwargs)
+        fused = kind == "forward" and owner.handle() is not None and x1.dtype in (torch.bfloat16, torch.float32) and x1.dim() == 3
+        if t is None and x0 is None and rng is None:
+            t, x0, _ = self.sample(x1)
+        elif t is None:
+            kind_, _, _ = parse_snr_type(self.snr_type)
+            base = torch.rand((len(x1),)) if kind_ == "uniform" else torch.normal(mean=0.0, std=1.0, size=(len(x1),))
+            t = fm_times(base, self.snr_type, x1.shape[1], self.do_shift)
+        t = torch.as_tensor(t).reshape(-1).to(x1[0])
+        if t.numel() != len(x1):
+            raise ValueError(f"training_losses: {t.numel()} times for a batch of {len(x1)}")
+        in_kernel = None
+        if rng is not None:
+            if hasattr(rng, "threads_per_sm") or not fused:      # a TorchNoiseStream, or the eager path: the tensor first
+                x0 = rng.randn(tuple(x1.shape), dtype=x1.dtype, device=x1.device if x1.is_cuda else None)
+            else:
+                if rng.offset + x1.numel() > 1 << 64:
+                    raise ValueError(f"training_losses: {x1.numel()} elements at offset {rng.offset} leave the 64-bit stream")
+                in_kernel = (int(rng.seed), int(rng.offset))
+        elif x0 is None:
+            x0 = torch.randn_like(x1)
+        if fused:
+            loss = _losses_fused(owner, x1, kw, cond, t, x0, in_kernel)
+            if in_kernel is not None:
+                rng.offset = in_kernel[1] + x1.numel()
+            return {"loss": loss, "task_loss": loss.clone(), "t": t}
+        return fm_loss_terms(model, x1, t, x0, model_kwargs, cond)
 
     def check_interval(self, reverse: bool = False, *, sde: bool = False, diffusion_form: str = "SBDM", last_step_size: float = 0.0,
                        sample_eps=None):
@@ -89,7 +313,39 @@ def create_transport(path_type="Linear", prediction="velocity", loss_weight=None
                      snr_type="uniform", loss_type="mse", do_shift=True) -> Transport:
     if path_type != "Linear" or prediction != "velocity":
         raise NotImplementedError("the MI355X denoising path implements Linear path + velocity prediction only")
-    return Transport(path_type, prediction, do_shift)
+    return Transport(path_type, prediction, do_shift, snr_type)
+
+
+@torch.no_grad()
+def _losses_fused(flux, x1, kw, cond, t, x0, in_kernel):
+    """vc_flux_eval_loss per chunk of samples -> loss f32 [B] on the model's device.  in_kernel: (seed, offset) of the in-kernel draw
+    (x0 None), a chunk's draw behind the last chunk's in the stream"""
+    h = flux.handle()
+    B, N, C = x1.shape
+    kw = dict(kw)
+    if kw.get("img_mask") is not None and kw.get("txt_mask") is None:      # the loss's mask alone: every text row is valid
+        kw["txt_mask"] = torch.ones(kw["txt"].shape[:2], dtype=torch.bool)
+    plan = flux.chunk_plan(B, N, kw, channels=(C, 0 if cond is None else cond.shape[-1]))
+    loss = torch.empty(B, dtype=torch.float32, device=plan.dev)
+    pos = None if in_kernel is None else in_kernel[1]
+    tf = t.detach().to("cpu", torch.float32)
+    with flux.monitored(h) as monitored:
+        try:
+            h.set_cfg(None)
+            h.set_eval_loss(True)
+            for sl in plan.chunks:
+                h.prepare(*plan.prepare_args(sl, 1))
+                xs = plan.img_rows(x1, sl, x1.dtype)
+                with monitored(1):
+                    out = h.eval_loss(xs, None if cond is None else plan.img_rows(cond, sl, torch.bfloat16), tf[sl],
+                                      x0=None if x0 is None else plan.img_rows(x0, sl, x1.dtype),
+                                      seed=0 if in_kernel is None else in_kernel[0], offset=pos or 0)
+                if pos is not None:
+                    pos += xs.numel()
+                loss[sl] = out
+        finally:
+            h.set_eval_loss(False)             # a later forward or trajectory sizes its workspace as it always did
+    return loss
 
 
 def _step_euler(f, t0, t1, dt, y0):
