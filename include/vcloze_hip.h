@@ -1278,6 +1278,77 @@ int vc_grid_img_ids(int32_t rows, const int32_t* lat_h, const int32_t* lat_w, fl
 int vc_pixels_out(const void* img, int32_t img_is_f32, int32_t H, int32_t W, int32_t x0, int32_t w, void* out, int32_t out_form,
                   void* stream);
 
+/* IMAGE COMPARE: how far two renderings of equal geometry C x H x W lie apart - error sums, PSNR and the mean SSIM of Wang, Bovik,
+ * Sheikh, Simoncelli 2004 - computed on the device, deterministically, on what vc_pixels_out writes.  The reference has nothing like
+ * it; the rule below is this library's own.  Added WITHOUT a change of VC_ABI_VERSION (tests pin 11): detect by SYMBOL (look up
+ * vc_image_compare); vc_image_struct_sizes reports sizeof(VcImageMetrics).
+ * form names the storage of BOTH images and the data range L:
+ *   VC_IMG_U8_HWC   8-bit [H, W, C], element (c, y, x) at (y * W + x) * C + c, value v = F32(byte) (exact), L = 255
+ *   VC_IMG_F32_CHW  F32 [C, H, W], element (c, y, x) at (c * H + y) * W + x, value as stored, meant to lie in [0, 1], L = 1
+ * ERROR SUMS over all n = C * H * W elements: d = a - b (F32, exact for bytes), sse = sum d * d, max_abs = max |d|, n_diff = the
+ *   number of elements with a != b.  8-bit form: sse_u64, max_abs, n_diff are exact integers (255^2 * n passes 2^32 at 66052
+ *   elements, so the sum is carried in 64 bits) and sse_f32 = F32(sse_u64).  F32 form: sse_u64 = 0 and sse_f32 is a fixed-order F32
+ *   sum (below); a NaN difference counts in n_diff, makes sse_f32 NaN and is skipped by max_abs.
+ * PSNR: vc_image_psnr - a HOST function on a copied-back VcImageMetrics - stores, in double, 10 * log10(L^2 * n / sse) with sse =
+ *   sse_u64 (8-bit form) or sse_f32 (F32 form); sse == 0 gives +inf; a NULL argument is VC_ERR_ARG.  The device never computes it.
+ * MEAN SSIM: the window is the 11 x 11 Gaussian with sigma = 1.5, applied separably; the eleven one-dimensional weights are
+ *   exp(-(k - 5)^2 / 4.5), k = 0 .. 10, normalised in double to sum 1 and rounded to F32 ONCE - VC_SSIM_WEIGHTS below.  Only VALID
+ *   positions count: window (c, y, x), 0 <= y < H - 10, 0 <= x < W - 10, covers rows y .. y + 10 and columns x .. x + 10 of channel c;
+ *   no padding; n_windows = C * (H - 10) * (W - 10).  All arithmetic is F32, one operation after the other, every operation rounded
+ *   on its own (no fused multiply-add), in this order:
+ *     five planes  p in { a, b, F32(a * a), F32(b * b), F32(a * b) }
+ *     horizontal   h_p(r, x) = sum over k = 0 .. 10, ascending, of w[k] * p(r, x + k):  s = w[0] * p(r, x);  s = s + w[k] * p(r, x + k)
+ *     vertical     m_p(y, x) = sum over j = 0 .. 10, ascending, of w[j] * h_p(y + j, x), the same way
+ *                  -> mu_a, mu_b, e_aa, e_bb, e_ab
+ *     ma2 = mu_a * mu_a;  mb2 = mu_b * mu_b;  mab = mu_a * mu_b;   va = e_aa - ma2;  vb = e_bb - mb2;  cab = e_ab - mab
+ *     n1 = (mab + mab) + C1;  n2 = (cab + cab) + C2;  d1 = (ma2 + mb2) + C1;  d2 = (va + vb) + C2
+ *     ssim = (n1 * n2) / (d1 * d2)                      the division correctly rounded
+ *   C1 = F32((0.01 * L)^2), C2 = F32((0.03 * L)^2), the squares taken in double.  Every step is symmetric in (a, b) - products and
+ *   sums of two values commute - so swapping the operands gives the same bits; and with a == b numerator and denominator are formed
+ *   by the same operations on equal values (mab == ma2 == mb2, cab == va == vb bit for bit), so every window gives exactly 1.0f.
+ *   ssim_mean = F32(S / n_windows) with S the sum below, the division in double.
+ * TILES AND THE ORDER OF THE SUMS (VC_IMG_TILE = 32; nothing else about the launch enters the result): channel c is cut into tiles of
+ *   32 x 32 WINDOWS, tile (c, ty, tx) holding windows y in [32 ty, 32 ty + 32), x in [32 tx, 32 tx + 32) inside the valid range;
+ *   TY = ceil((H - 10) / 32), TX = ceil((W - 10) / 32); its index is p = (c * TY + ty) * TX + tx.  One workgroup of 256 threads per
+ *   tile.  Thread t owns column x = t % 32 and rows y = t / 32 + 8 i, i = 0 .. 3, of the tile: it adds the ssim of its valid windows
+ *   in ascending i, starting from 0.  The ERROR SUMS of a tile run over its share of PIXELS: the tile's halo is the 42 x 42 pixels
+ *   its windows cover; the tile owns halo rows r < 32, or ALL its halo rows inside the image if ty = TY - 1, and likewise columns -
+ *   every pixel of the channel belongs to exactly one tile.  Thread t visits halo positions q = t + 256 i, i = 0 .. 6 (row q / 42,
+ *   column q % 42) in ascending i and takes the owned ones: s = s + d * d (F32 form), exact integers (8-bit form).  The 256 thread
+ *   values of a tile go through a tree, l[t] = l[t] (op) l[t + o], o = 128, 64, .., 1 (op: F32 add, integer add, max), and make the
+ *   tile's record.  A second launch of ONE workgroup folds the P = C * TY * TX records: thread t adds records t, t + 256, .. in
+ *   ascending order, then the same tree - the ssim sums and the F32 sse in DOUBLE (rounded to F32 once, at the end), the integers in
+ *   64 bits.  No atomics: repeated runs give the same bits.  Rows are fetched with 16-byte loads where W % 16 == 0 and both bases
+ *   are 16-byte aligned (and C == 3 for the 8-bit form), element-wise otherwise; the choice is made on the host and the values that
+ *   reach the arithmetic are the same, so are the bits.
+ * vc_image_compare_scratch_bytes: HOST only; bytes = P * VC_IMG_RECORD_BYTES.  vc_image_compare: a, b, out_dev, scratch are DEVICE
+ *   pointers, nothing is allocated, nothing is read back: two launches on `stream`, legal under stream capture.  a and b may be the
+ *   same buffer.  VC_ERR_ARG with a message, before the device is touched: a null pointer; an unknown form; C outside 1 .. 65535;
+ *   H or W outside 11 .. 65535 (a window needs 11 rows and 11 columns); an F32 image not aligned to 4 bytes; out_dev or scratch not
+ *   aligned to 16 bytes; scratch_bytes smaller than vc_image_compare_scratch_bytes answers. */
+#define VC_IMG_U8_HWC 0
+#define VC_IMG_F32_CHW 1
+#define VC_IMG_TILE 32
+#define VC_IMG_RECORD_BYTES 32
+#define VC_SSIM_WEIGHTS { 0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005543f, 0.266011715f, \
+                          0.213005543f, 0.109360687f, 0.0360007733f, 0.00759875821f, 0.00102838012f }
+typedef struct VcImageMetrics {
+  uint64_t n;                                /* C * H * W */
+  uint64_t n_windows;                        /* C * (H - 10) * (W - 10) */
+  uint64_t sse_u64;                          /* 8-bit form: exact; F32 form: 0 */
+  uint64_t n_diff;
+  float sse_f32;                             /* F32 form: the fixed-order sum; 8-bit form: F32(sse_u64) */
+  float max_abs;
+  float ssim_mean;
+  int32_t form;
+} VcImageMetrics;                            /* 48 bytes */
+/* sizeof(VcImageMetrics) as this library was compiled */
+void vc_image_struct_sizes(int32_t out[1]);
+int vc_image_compare_scratch_bytes(int32_t C, int32_t H, int32_t W, int64_t* bytes);
+int vc_image_compare(const void* a, const void* b, int32_t form, int32_t C, int32_t H, int32_t W, VcImageMetrics* out_dev, void* scratch,
+                     int64_t scratch_bytes, void* stream);
+int vc_image_psnr(const VcImageMetrics* m, double* psnr_db);
+
 /* THE HANDLE: VisualClozeModel.process_images' tensor path (visualcloze.py:363-434) and `upsampling`'s (:184-240) as ONE call each,
  * composed of the entry points above in the order visualcloze_amd/pipeline.py composes them (generate_grid with
  * rng = NoiseStream(seed); upsample_images): the same kernels on the same operands, so the same bits.  The handle BORROWS its four

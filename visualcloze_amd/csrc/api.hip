@@ -446,6 +446,15 @@ int vc_pixels_out(const void* img, int32_t img_is_f32, int32_t H, int32_t W, int
                   void* stream) {
   return vc_pixels_out_launch(img, img_is_f32, H, W, x0, w, out, out_form, S(stream), ERRBUF);
 }
+void vc_image_struct_sizes(int32_t out[1]) { out[0] = (int32_t)sizeof(VcImageMetrics); }
+int vc_image_compare_scratch_bytes(int32_t C, int32_t H, int32_t W, int64_t* bytes) {
+  return vc_image_compare_scratch_bytes_impl(C, H, W, bytes, ERRBUF);
+}
+int vc_image_compare(const void* a, const void* b, int32_t form, int32_t C, int32_t H, int32_t W, VcImageMetrics* out_dev, void* scratch,
+                     int64_t scratch_bytes, void* stream) {
+  return vc_image_compare_launch(a, b, form, C, H, W, out_dev, scratch, scratch_bytes, S(stream), ERRBUF);
+}
+int vc_image_psnr(const VcImageMetrics* m, double* psnr_db) { return vc_image_psnr_impl(m, psnr_db, ERRBUF); }
 void vc_grid_struct_sizes(int32_t out[3]) {
   out[0] = (int32_t)sizeof(VcGridConfig); out[1] = (int32_t)sizeof(VcGridJob); out[2] = (int32_t)sizeof(VcGridSdedit);
 }

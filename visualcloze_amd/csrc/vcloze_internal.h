@@ -155,6 +155,11 @@ int vc_randn_torch_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, 
                                  int threads_per_sm, hipStream_t s, char* err, int errlen);
 int vc_pixels_out_launch(const void* img, int img_is_f32, int H, int W, int x0, int w, void* out, int out_form, hipStream_t s, char* err,
                          int errlen);
+// image_metrics.hip: vc_image_compare
+int vc_image_compare_scratch_bytes_impl(int C, int H, int W, int64_t* bytes, char* err, int errlen);
+int vc_image_compare_launch(const void* a, const void* b, int form, int C, int H, int W, VcImageMetrics* out_dev, void* scratch, int64_t scratch_bytes,
+                            hipStream_t s, char* err, int errlen);
+int vc_image_psnr_impl(const VcImageMetrics* m, double* psnr_db, char* err, int errlen);
 // resample.hip, pixels_in.hip: the photo front end's kernels
 int vc_resample_kmax_impl(int in, int out, int filter, char* err, int errlen);
 int vc_resample_coeffs_impl(int in, int out, int filter, int32_t* xmin, int32_t* len, int32_t* ki, int kmax, char* err, int errlen);

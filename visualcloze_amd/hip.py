@@ -193,6 +193,15 @@ class Stat(C.Structure):                     # VcStat (vc_tensor_stats, vc_flux_
 
 MONITOR_MAX_BLOCKS = 256                     # VC_MONITOR_MAX_BLOCKS
 
+
+class ImageMetrics(C.Structure):             # VcImageMetrics (vc_image_compare)
+    _fields_ = [("n", C.c_uint64), ("n_windows", C.c_uint64), ("sse_u64", C.c_uint64), ("n_diff", C.c_uint64), ("sse_f32", C.c_float),
+                ("max_abs", C.c_float), ("ssim_mean", C.c_float), ("form", C.c_int32)]
+
+
+IMG_U8_HWC, IMG_F32_CHW = 0, 1               # VC_IMG_*: the storage of both operands of vc_image_compare
+IMG_TILE, IMG_RECORD_BYTES = 32, 32          # VC_IMG_TILE / VC_IMG_RECORD_BYTES
+
 SYMBOLS = {
     "vc_abi_version": (C.c_int, []),
     "vc_last_error": (C.c_char_p, []),
@@ -332,6 +341,10 @@ SYMBOLS = {
     "vc_grid_tokens": (_i64, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_grid_img_ids": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float)]),
     "vc_pixels_out": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "vc_image_struct_sizes": (None, [C.POINTER(C.c_int32)]),
+    "vc_image_compare_scratch_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "vc_image_compare": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "vc_image_psnr": (C.c_int, [C.POINTER(ImageMetrics), C.POINTER(C.c_double)]),
     "vc_grid_struct_sizes": (None, [C.POINTER(C.c_int32)]),
     "vc_grid_create": (C.c_int, [C.POINTER(GridConfig), C.POINTER(_vp)]),
     "vc_grid_destroy": (C.c_int, [_vp]),
@@ -409,6 +422,9 @@ def lib() -> C.CDLL:
         l.vc_monitor_struct_sizes(vsize)
         if vsize[0] != C.sizeof(Stat):
             raise VclozeHipError(f"libvcloze_hip.so sizeof(VcStat) {vsize[0]} differs from the ctypes mirror - rebuild")
+        l.vc_image_struct_sizes(vsize)
+        if vsize[0] != C.sizeof(ImageMetrics):
+            raise VclozeHipError(f"libvcloze_hip.so sizeof(VcImageMetrics) {vsize[0]} differs from the ctypes mirror - rebuild")
         gsize = (C.c_int32 * 3)()
         l.vc_grid_struct_sizes(gsize)
         if list(gsize) != [C.sizeof(GridConfig), C.sizeof(GridJob), C.sizeof(GridSdedit)]:
@@ -1243,6 +1259,80 @@ def pixels_out(img, x0: int = 0, w: Optional[int] = None, uint8: bool = False, o
     _check(lib().vc_pixels_out(img.data_ptr(), int(img.dtype == torch.float32), H, W, int(x0), int(w), out.data_ptr(),
                                PIXELS_U8 if uint8 else PIXELS_F32, stream if stream is not None else cur_stream()), "vc_pixels_out")
     return out
+
+
+# ---- image comparison (csrc/image_metrics.hip) ----
+def image_compare_scratch_bytes(Cn: int, H: int, W: int) -> int:
+    """vc_image_compare_scratch_bytes (host-only): the device scratch one comparison of two [Cn, H, W] images needs"""
+    n = C.c_int64()
+    _check(lib().vc_image_compare_scratch_bytes(int(Cn), int(H), int(W), C.byref(n)), "vc_image_compare_scratch_bytes")
+    return n.value
+
+
+def image_form(a, b):
+    """(form, C, H, W) of two images vc_image_compare takes: both uint8 [H, W, C] (what pixels_out(uint8=True) writes) or both f32
+    [C, H, W] in [0, 1], contiguous, of one shape, on one CUDA device.  ValueError otherwise."""
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"image_compare: {name} must be a torch tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise ValueError(f"image_compare: {name} must live on a CUDA device, got {t.device}")
+        if t.dim() != 3:
+            raise ValueError(f"image_compare: {name} must have 3 dimensions ([H, W, C] uint8 or [C, H, W] float32), got shape {tuple(t.shape)}")
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"image_compare: {name} must be uint8 or float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"image_compare: {name} must be contiguous")
+    if a.dtype != b.dtype:
+        raise ValueError(f"image_compare: a is {a.dtype} and b is {b.dtype}: both images must have one form")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"image_compare: shapes differ: {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"image_compare: devices differ: {a.device} and {b.device}")
+    if a.dtype == torch.uint8:
+        H, W, Cn = (int(d) for d in a.shape)
+        form = IMG_U8_HWC
+    else:
+        Cn, H, W = (int(d) for d in a.shape)
+        form = IMG_F32_CHW
+    if H < 11 or W < 11:
+        raise ValueError(f"image_compare: a {H}x{W} image is smaller than the 11 x 11 SSIM window")
+    return form, Cn, H, W
+
+
+def image_compare_raw(a, b, out=None, scratch=None, stream=None) -> torch.Tensor:
+    """vc_image_compare: the VcImageMetrics of (a, b) as 48 bytes of device memory (uint8 [48]); nothing is read back, so the call
+    may be captured.  `out` (uint8 [48]) and `scratch` (uint8, image_compare_scratch_bytes of it) may be the caller's."""
+    form, Cn, H, W = image_form(a, b)
+    need = image_compare_scratch_bytes(Cn, H, W)
+    if out is None:
+        out = torch.empty(C.sizeof(ImageMetrics), dtype=torch.uint8, device=a.device)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=a.device)
+    for name, t, nbytes in (("out", out, C.sizeof(ImageMetrics)), ("scratch", scratch, need)):
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < nbytes or not t.is_contiguous() or t.device != a.device or t.data_ptr() % 16:
+            raise ValueError(f"image_compare: {name} must be a contiguous 16-byte aligned uint8 tensor of at least {nbytes} bytes on {a.device}")
+    _check(lib().vc_image_compare(a.data_ptr(), b.data_ptr(), form, Cn, H, W, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                  stream if stream is not None else cur_stream()), "vc_image_compare")
+    return out
+
+
+def image_metrics_of(raw: torch.Tensor) -> dict:
+    """the dict of a copied-back VcImageMetrics: psnr_db is vc_image_psnr's double, mse = sse / n"""
+    m = ImageMetrics.from_buffer_copy(bytes(raw.cpu().numpy().tobytes()[:C.sizeof(ImageMetrics)]))
+    sse = float(m.sse_u64) if m.form == IMG_U8_HWC else float(m.sse_f32)
+    psnr = C.c_double()
+    _check(lib().vc_image_psnr(C.byref(m), C.byref(psnr)), "vc_image_psnr")
+    return {"psnr_db": psnr.value, "ssim": float(m.ssim_mean), "mse": sse / float(m.n),
+            "max_abs": float(m.max_abs), "n_diff": int(m.n_diff), "sse": int(m.sse_u64) if m.form == IMG_U8_HWC else float(m.sse_f32),
+            "n": int(m.n), "n_windows": int(m.n_windows), "form": int(m.form)}
+
+
+def image_compare(a, b, stream=None) -> dict:
+    """How far two renderings lie apart (include/vcloze_hip.h: IMAGE COMPARE): {"psnr_db", "ssim", "mse", "max_abs", "n_diff", ...} of two
+    uint8 [H, W, C] or two f32 [C, H, W] images of one shape on one device.  The form is inferred from the dtype.  Synchronises: the
+    48-byte result is copied back."""
+    return image_metrics_of(image_compare_raw(a, b, stream=stream))
 
 
 # ---- the photo front end: resampling (csrc/resample.hip), pixels in (csrc/pixels_in.hip), the size rules (csrc/grid_rules.hip) ----

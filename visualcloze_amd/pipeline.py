@@ -340,6 +340,20 @@ def to_uint8_image(img01: torch.Tensor):
     return Image.fromarray(a)
 
 
+def compare_images(a, b):
+    """How far two renderings lie apart: `hip.image_compare` (vc_image_compare: error sums, PSNR, mean SSIM, computed on the device,
+    the same bits on every run) on what `generate_grid` / `upsample_images` return on either path - two f32 [3, H, W] tensors in
+    [0, 1], or two uint8 [H, W, 3] tensors (the 8-bit form of vc_pixels_out) - or two lists of them of one length, image by image.
+    Returns {"psnr_db", "ssim", "mse", "max_abs", "n_diff"} (a list of them for lists).  A distance between two renderings made with
+    the SAME weights, seed and prompt: it ranks sampler settings against each other and says nothing about absolute image quality."""
+    if isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
+        if not (isinstance(a, (list, tuple)) and isinstance(b, (list, tuple))) or len(a) != len(b):
+            raise ValueError("compare_images: two lists of one length (or two tensors) expected")
+        return [compare_images(x, y) for x, y in zip(a, b)]
+    m = hip.image_compare(a, b)
+    return {k: m[k] for k in ("psnr_db", "ssim", "mse", "max_abs", "n_diff")}
+
+
 def upsampling_size(target_size):
     """The size rule of `upsampling` (visualcloze.py:165-179): default 1024x1024, at most 1024^2 pixels at the requested
     aspect ratio, both sides rounded down to multiples of 16.  (w, h) in, (w, h) out."""
