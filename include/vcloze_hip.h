@@ -419,6 +419,42 @@ int vc_sde_plan(const char* method, const char* form, double norm, const char* l
                 int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws);
 int vc_sde_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
                  const uint64_t* rng, const int32_t* eval_ptr, int64_t n, void* stream);
+/* ---- the Adams-Bashforth multistep solver: a fixed-grid, VARIABLE-STEP rule of order 1..4 that costs exactly ONE model evaluation
+ * per step - it reuses the velocities of the steps before.  The reference's sample_ode advertises torchdiffeq's Adams methods and
+ * ships none that run; the rule below is the textbook one, stated in full.  Added WITHOUT a change of VC_ABI_VERSION: detect these
+ * entry points (vc_ms_plan, vc_ms_stage, vc_flux_sample_multistep, vc_flux_plan_count) by SYMBOL - look up vc_ms_plan.  VC_SOLVER_*
+ * has no code for it and vc_solver_evals / vc_flux_sample_ode keep refusing anything but the fixed-grid methods.
+ * Time runs as in sample_ode (t = 0 noise, t = 1 data); the drift is f(t, y) = -model(bf16(y) || cond, 1 - f32(t)).
+ * For step i (0-based) from t_i to t_{i+1} the order used is k_i = min(order, i + 1) - the usual low-order start, no extra
+ * evaluations -, the nodes are tau_j = t_{i-j}, j = 0 .. k_i - 1, and
+ *   c_{i,j} = INT_{t_i}^{t_{i+1}} PROD_{m != j} (tau - tau_m) / (tau_j - tau_m) dtau
+ * computed on the HOST in double from the F32 grid values, widened, and rounded ONCE to F32; unused coefficients are exactly 0.0f.
+ * Each coefficient contains the step length: SUM_j c_{i,j} = t_{i+1} - t_i.  The update is
+ *   y <- y + (((c_{i,0} f_i) + c_{i,1} f_{i-1}) + c_{i,2} f_{i-2}) + c_{i,3} f_{i-3}
+ * in F32, left to right, one operation after the other, no fused multiply-add - that is, as a compiler reads the line:
+ * z = c0 f_i;  z = z + c1 f_{i-1};  z = z + c2 f_{i-2};  y = y + z;  y = y + c3 f_{i-3}.  A torch F32 expression of the same shape
+ * gives the same bits (transport.multistep_integrate is that expression).  A coefficient c_{i,j}, j >= 1, that is exactly zero adds
+ * NO term and its velocity is NOT READ (the c_{i,0} term is always there: f_i is what the model has just written).
+ * Order 1 is Euler's rule with F32 roundings - not bit-equal to vc_euler_step_f32, which multiplies by bf16(dt).  Orders 3 and 4
+ * have small stability regions; nothing here recommends an order.
+ * plan:  host only, needs no device.  rows receives n_points - 1 rows of VC_MS_ROW F32 (c_{i,0..3}), times the model's time
+ *        1 - f32(t_i) of every evaluation; both may be NULL (the count alone); capacity: the rows `rows` holds, the values `times`
+ *        holds; *n_evals = n_points - 1.  VC_ERR_ARG with a message: an order outside 1..4, n_points < 2, a grid that does not increase
+ *        strictly, a capacity that is too small, ANY NON-FINITE COEFFICIENT.
+ * stage: one elementwise pass over n elements.  Row e = eval (>= 0), or *eval_ptr - the device-side evaluation counter, so one
+ *        captured launch serves every step and every order; a row outside [0, n_rows) writes nothing.  y: F32 [n]; v: the model's
+ *        bf16 output v_e (f_e = -v_e); hist: bf16 [VC_MS_HIST][n], a RING of past outputs as the model wrote them - v_{e-j} lives in
+ *        slot (e - j) mod VC_MS_HIST; y_in: bf16 [n] <- bf16(y), the NEXT evaluation's input.  After the sum, v_e is stored into slot
+ *        e mod VC_MS_HIST: the element it overwrites, v_{e-3}, is the one the same work item has just read.  During the start the
+ *        slots hold whatever the buffer held: they are not read, and 0 * NaN never reaches the state.  Buffers must not overlap.
+ *        16-byte accesses where n % 8 == 0 (the ring's planes start n elements apart) and every base is 16-byte aligned, 8
+ *        elements per work item; anything else runs element-wise with the same results.  Grid capped, grid-stride loop; no LDS,
+ *        no atomics. */
+#define VC_MS_ROW 4    /* F32 values per table row: c_{i,0} .. c_{i,3}; also the highest order */
+#define VC_MS_HIST 3   /* planes of the ring of past model outputs */
+int vc_ms_plan(int32_t order, const float* t_grid, int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals);
+int vc_ms_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* hist, void* y_in, const int32_t* eval_ptr,
+                int64_t n, void* stream);
 /* ---- the three elementwise passes of the first-block step cache (vc_flux_set_step_cache below; the rule is this library's own,
  * DESIGN.md section 4).  Added without a change of VC_ABI_VERSION, like the solver entry points: detect by SYMBOL (look up
  * vc_flux_set_step_cache).  bf16 storage, f32 math, 16-byte accesses: n, every sample stride a multiple of 8, bases 16-byte aligned
@@ -1010,6 +1046,33 @@ int vc_flux_rk_log(void* handle, double* t, double* dt, float* ratio, int32_t* a
 int vc_flux_sample_sde(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
                        double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
                        void* trajectory, void* stream);
+/* ---- the Adams-Bashforth multistep solve around the same captured evaluation (vc_ms_plan / vc_ms_stage above have the rule).
+ * OPT-IN: set vc_flux_set_option(handle, "multistep", 1) BEFORE vc_flux_workspace_bytes / vc_flux_prepare - it adds the F32 state,
+ * the ring of VC_MS_HIST past outputs and the coefficient table to the workspace - and prepare with max_steps >= n_points - 1.  With
+ * the option off nothing changes: the same workspace bytes, graphs, nodes and bits.  Detect by SYMBOL (look up vc_ms_plan).
+ * order, t_grid, n_points: as for vc_ms_plan, which is run first - its refusals are this call's, before anything touches the device.
+ * x [B, N, out_channels]: in = x(t_grid[0]), out = x(t_grid[n_points - 1]); bf16 (state_is_bf16) or F32.  The state is stepped in F32
+ * whatever the caller's dtype: a bf16 state is widened on entry and rounded ONCE per output.  One evaluation per step.
+ *   step    the captured step is the existing evaluation with vc_ms_stage on the device-side counter as its last node, kept per
+ *           geometry; it has exactly the nodes of the VC_SOLVER_EULER step (vc_flux_step_nodes).  ONE captured step serves every
+ *           order: the order lives in the uploaded table, not in the graph (vc_flux_plan_count tells the captured steps the handle
+ *           holds).  The time embeddings, modulation rows and coefficient rows of all evaluations are built up front.
+ *   ring    the first evaluation of a call writes slot 0, the second slot 1, the third slot 2, each BEFORE any row reads it (row i
+ *           reads i, at most 3, slots back); nothing of an earlier call or of the workspace's earlier contents is read.
+ *   trajectory  NULL, or [n_points][B][N][out_channels] in the state's dtype: row 0 receives x(t_grid[0]) as the solver holds it
+ *           (the caller's values), row i the state after step i - 1 - n_points rows.
+ * True CFG (vc_flux_set_cfg: the combine comes before the update, the ring holds the combined velocity; both halves are stepped),
+ * taps and the un-merged LoRA mode work unchanged.  Refused: the option off (VC_ERR_STATE); the step cache on, the monitor on
+ * (turn it off with level 0), more evaluations than max_steps, an odd B with true CFG (all VC_ERR_ARG) - each found before the
+ * device is touched; the handle stays usable.
+ * Image quality at any order is UNMEASURED (only random-init weights exist here), and no throughput claim is made beyond "one
+ * evaluation per step": the update is one elementwise pass like Euler's. */
+int vc_flux_sample_multistep(void* handle, int32_t order, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                             int32_t state_is_bf16, void* trajectory, void* stream);
+/* the captured steps the handle holds (most recently used first), or -1 for a null handle.  Host only.  The list holds at most 4: at
+ * 4 a new capture evicts the least recently used step and the count STAYS 4 - a caller who reads it to tell whether a call
+ * captured must start below 4. */
+int vc_flux_plan_count(void* handle);
 
 /* ---- first-block step cache of the Euler loop: OPT-IN, off by default.  IT CHANGES RESULTS: a reused evaluation is an
  * approximation, not the model.  Its effect on image quality is unmeasured (only random-init weights were available) and no default

@@ -148,6 +148,13 @@ int vc_sde_plan(const char* method, const char* form, double norm, const char* l
                 int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws) {
   return vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, rows, times, capacity, n_evals, n_draws, ERRBUF);
 }
+int vc_ms_plan(int32_t order, const float* t_grid, int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals) {
+  return vc_ms_plan_impl(order, t_grid, n_points, rows, times, capacity, n_evals, ERRBUF);
+}
+int vc_ms_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* hist, void* y_in, const int32_t* eval_ptr,
+                int64_t n, void* stream) {
+  return vc_ms_stage_launch(eval, table, n_rows, y, v, hist, y_in, eval_ptr, n, S(stream), ERRBUF);
+}
 int vc_sde_stage(int32_t eval, const float* table, int32_t n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
                  const uint64_t* rng, const int32_t* eval_ptr, int64_t n, void* stream) {
   return vc_sde_stage_launch(eval, table, n_rows, y, v, y_in, xhat, k1, rng, eval_ptr, n, S(stream), ERRBUF);
@@ -367,6 +374,11 @@ int vc_flux_rk_log(void* handle, double* t, double* dt, float* ratio, int32_t* a
                    int32_t* evaluations) {      // one log serves both adaptive entry points: the last solve's
   return vc_flux_dopri5_log_impl(handle, t, dt, ratio, accepted, capacity, attempts, evaluations, ERRBUF);
 }
+int vc_flux_sample_multistep(void* handle, int32_t order, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                             int32_t state_is_bf16, void* trajectory, void* stream) {
+  return vc_flux_sample_multistep_impl(handle, order, x, cond, t_grid, n_points, state_is_bf16, trajectory, S(stream), ERRBUF);
+}
+int vc_flux_plan_count(void* handle) { return vc_flux_plan_count_impl(handle); }
 int vc_flux_sample_sde(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
                        double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
                        void* trajectory, void* stream) {

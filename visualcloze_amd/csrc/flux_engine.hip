@@ -26,6 +26,9 @@
 //                           seed / offset words its update reads
 //   FM_U (f32) / FM_T / FM_PART  only with option eval_loss 1, behind the stochastic sampler's: u_t = x1 - x0 of vc_flux_eval_loss
 //                           (fm_loss.hip), its B times and the partial sums of its reduction
+//   MS_Y (f32) / MS_HIST / MS_TAB  only with option multistep 1, behind the loss's: the state of the Adams-Bashforth solve
+//                           (vc_flux_sample_multistep, multistep.hip), its ring of VC_MS_HIST past model outputs ([3][B*N*out] bf16) and
+//                           its coefficient table ([S][VC_MS_ROW] f32)
 //   LY / LY2 / LH / LSCALE  only in the un-merged LoRA mode (option lora_mode 1), behind everything else: base_out, base_out + lora
 //                           and lora_A(x) of the Linear being run, and the lora scale as a bf16 vector (the gate operand of the
 //                           gated-residual epilogue that adds the lora branch; refilled by vc_flux_set_lora_scale)
@@ -82,6 +85,10 @@ int64_t carve(Buffers& f, const Flux& g, char* base, int B, int T, int N, int S)
   if (g.opt.eval_loss) {   // likewise
     f.FM_U = c.take<float>((int64_t)B * N * out_ch); f.FM_T = c.take<float>(B);
     f.FM_PART = c.take<float>((int64_t)B * VC_FM_LOSS_MAX_BLOCKS);
+  }
+  if (g.opt.multistep) {   // likewise
+    const int64_t n = (int64_t)B * N * out_ch;
+    f.MS_Y = c.take<float>(n); f.MS_HIST = c.take<bf16_t>(VC_MS_HIST * n); f.MS_TAB = c.take<float>((int64_t)S * VC_MS_ROW);
   }
   if (g.opt.lora_mode) {   // likewise: the widest Linear over the block rows, the modulation Linears over the (evaluation, sample) rows
     const int64_t wide = std::max<int64_t>({3 * D, mlp, D, out_ch}), rows = std::max<int64_t>(B * L, (int64_t)S * B);
@@ -513,6 +520,9 @@ int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, c
   if (f.traj.method == SOLVER_SDE_EULER || f.traj.method == SOLVER_SDE_HEUN)      // the table row of the update is the device-side counter itself
     return vc_sde_stage_launch(-1, f.SD_TAB, f.S + 1, f.SD_Y, v, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, step_ptr,
                                (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
+  if (f.traj.method == SOLVER_MULTISTEP)   // likewise: the row holds the order
+    return vc_ms_stage_launch(-1, f.MS_TAB, f.S, f.MS_Y, v, f.MS_HIST, f.YIN, step_ptr, (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf,
+                              e.len);
   void* y = ode_state(f);
   bf16_t* y_in = next_input(f);
   return vc_ode_update_launch("ode_update", f.traj.method, -1, y, !f.traj.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
@@ -725,6 +735,8 @@ int vc_flux_step_nodes_impl(void* handle, int32_t nodes[3], char* err, int errle
   return VC_OK;
 }
 
+int vc_flux_plan_count_impl(void* handle) { return handle ? (int)((Flux*)handle)->graphs.size() : -1; }
+
 int vc_flux_tap_shape_impl(void* handle, const char* name, int64_t* rows, int32_t* cols, char* err, int errlen) {
   HANDLE(Flux, f, "flux");
   size_t idx = 0;
@@ -749,7 +761,7 @@ int vc_flux_set_option_impl(void* handle, const char* name, int32_t value, char*
       case ANY: break;
     }
     if ((o.member == &Options::lora_mode || o.member == &Options::adaptive || o.member == &Options::sde ||
-         o.member == &Options::eval_loss) && value != f.opt.*o.member) {
+         o.member == &Options::eval_loss || o.member == &Options::multistep) && value != f.opt.*o.member) {
       if (f.in_flight)
         FAIL(VC_ERR_STATE, "flux_set_option: %s cannot change between vc_flux_sample_begin and vc_flux_sample_end", o.name);
       f.prepared = false;    // the workspace carve-up differs: vc_flux_workspace_bytes + vc_flux_prepare again

@@ -1,7 +1,7 @@
 // What a solver does with a Flux handle (flux_state.h): ONE trajectory core - the refusals every sampler shares, begin_trajectory and
 // replay - and on top of it the fixed-grid loop (vc_flux_sample_begin / _steps / _end), the adaptive Dormand-Prince solve
-// (vc_flux_sample_dopri5), its tableau-driven twin for the low-order embedded pairs (vc_flux_sample_rk) and the stochastic sampler
-// (vc_flux_sample_sde).  An entry point keeps what is its own: its tables, its own
+// (vc_flux_sample_dopri5), its tableau-driven twin for the low-order embedded pairs (vc_flux_sample_rk), the stochastic sampler
+// (vc_flux_sample_sde) and the Adams-Bashforth multistep solve (vc_flux_sample_multistep).  An entry point keeps what is its own: its tables, its own
 // refusals and its loop.  Host code only; the arithmetic of the tables is flux_rules.h.
 #include "flux_state.h"
 
@@ -58,7 +58,7 @@ int begin_trajectory(Flux& f, int method, const void* x, int x_is_bf16, const vo
   f.traj.cached = f.sc_on();
   f.cfg_active = f.cfg_on; f.cfg_s = f.cfg_on ? f.cfg_scale : 1.0f;
   if (!fixed) {                                 // the f32 state of the solver and its bf16 shadow
-    TRY(vc_dopri5_load_launch(x, x_is_bf16, method == SOLVER_DOPRI5 || method == SOLVER_RK ? f.AD_Y0 : f.SD_Y, f.YIN, n, s, e.buf, e.len));
+    TRY(vc_dopri5_load_launch(x, x_is_bf16, method == SOLVER_DOPRI5 || method == SOLVER_RK ? f.AD_Y0 : method == SOLVER_MULTISTEP ? f.MS_Y : f.SD_Y, f.YIN, n, s, e.buf, e.len));
   } else {
     TRY(d2d(ode_state(f), x, ode_state_bytes(f), s, e.buf, e.len));
     // the first evaluation reads bf16(y0)
@@ -472,6 +472,48 @@ int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const voi
   }
   if (trajectory) TRY(vc_sde_store_launch(f.SD_Y, (char*)trajectory + (int64_t)(n_points - 1) * out_bytes, out_bf16, n, s, e.buf, e.len));
   return vc_sde_store_launch(f.SD_Y, x, out_bf16, n, s, e.buf, e.len);
+}
+
+// ---------------------------------------------------------------- the multistep solve (vcloze_hip.h: vc_flux_sample_multistep)
+int vc_flux_sample_multistep_impl(void* handle, int32_t order, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                                  int32_t state_is_bf16, void* trajectory, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  // ---- every check before the device is touched
+  TRY(refuse_unready(f, "flux_sample_multistep", x, cond, t_grid, e));
+  if (!f.opt.multistep || !f.MS_Y)
+    FAIL(VC_ERR_STATE, "flux_sample_multistep: set vc_flux_set_option(handle, \"multistep\", 1) before vc_flux_workspace_bytes / "
+                       "vc_flux_prepare (the workspace holds no buffers of the multistep solve)");
+  if (f.mon_level)
+    FAIL(VC_ERR_ARG, "flux_sample_multistep: the monitor is on (level %d): its log is indexed by the evaluations of a fixed-grid trajectory; "
+                     "turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
+  TRY(refuse_cache(f, "flux_sample_multistep", NO_SOLVER_CODE, e));
+  int32_t n_evals = 0;
+  TRY(vc_ms_plan_impl(order, t_grid, n_points, nullptr, nullptr, 0, &n_evals, err, errlen));
+  if (n_evals > f.S)
+    FAIL(VC_ERR_ARG, "flux_sample_multistep: %d evaluations (%d points), the prepared workspace holds 1..%d evaluations", n_evals, n_points, f.S);
+  TRY(refuse_cfg(f, "flux_sample_multistep", e));
+  const int B = f.B, out_bf16 = state_is_bf16 != 0;
+  const int64_t n = (int64_t)B * f.N * f.cfg.out_channels, out_bytes = n * (out_bf16 ? 2 : 4);
+  // ---- the tables of the whole trajectory: model times and coefficient rows
+  TRY(stage_begin(f, ((size_t)n_evals * B + (size_t)n_evals * VC_MS_ROW + n_evals) * sizeof(float) + 3 * 256, e.buf, e.len));
+  float* ts = stage_take<float>(f, (size_t)n_evals * B);
+  float* rows = stage_take<float>(f, (size_t)n_evals * VC_MS_ROW);
+  float* times = stage_take<float>(f, n_evals);
+  TRY(vc_ms_plan_impl(order, t_grid, n_points, rows, times, n_evals, nullptr, err, errlen));
+  for (int j = 0; j < n_evals; ++j)
+    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = times[j];
+  end_trajectory(f);
+  TRY(stage_send(f, f.TS, ts, (size_t)n_evals * B * sizeof(float), s, e.buf, e.len));
+  TRY(stage_send(f, f.MS_TAB, rows, (size_t)n_evals * VC_MS_ROW * sizeof(float), s, e.buf, e.len));
+  TRY(stage_end(f, s, e.buf, e.len));
+  TRY(time_precompute(f, n_evals, 0, s, e.buf, e.len));
+  TRY(begin_trajectory(f, SOLVER_MULTISTEP, x, state_is_bf16, cond, s, e));
+  if (trajectory) TRY(vc_sde_store_launch(f.MS_Y, trajectory, out_bf16, n, s, e.buf, e.len));
+  for (int j = 0; j < n_evals; ++j) {
+    TRY(replay(f, s, e));
+    if (trajectory) TRY(vc_sde_store_launch(f.MS_Y, (char*)trajectory + (int64_t)(j + 1) * out_bytes, out_bf16, n, s, e.buf, e.len));
+  }
+  return vc_sde_store_launch(f.MS_Y, x, out_bf16, n, s, e.buf, e.len);
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {

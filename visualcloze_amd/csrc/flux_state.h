@@ -1,7 +1,7 @@
 // The Flux handle (include/vcloze_hip.h: vc_flux_*): its state, and the few functions its three units call across each other -
 //   flux_weights.hip  what is bound: the weight and LoRA tables, their resolution per block, a checkpoint as stored (vc_flux_load_*)
 //   flux_engine.hip   what is launched: the workspace, the plan of an evaluation and of a step, its capture, prepare / forward / profile
-//   flux_sample.hip   what a solver does: one trajectory core and the fixed-grid, adaptive and stochastic samplers on top of it
+//   flux_sample.hip   what a solver does: one trajectory core and the fixed-grid, adaptive, stochastic and multistep samplers on top of it
 // Host code only.  The types live in a NAMED namespace: all three units must see the same Flux.
 #pragma once
 #include "common.h"
@@ -48,6 +48,8 @@ struct Buffers {   // the workspace carve-up
   float *AD_Y0 = nullptr, *AD_Y1 = nullptr, *AD_DT = nullptr, *AD_OUT = nullptr, *AD_PART = nullptr;
   float *SD_Y = nullptr, *SD_XHAT = nullptr, *SD_K1 = nullptr, *SD_TAB = nullptr;   // stochastic sampler (carved only while option sde is on)
   uint64_t* SD_RNG = nullptr;
+  float *MS_Y = nullptr, *MS_TAB = nullptr;                        // multistep solve (carved only while option multistep is on)
+  bf16_t* MS_HIST = nullptr;
   float *FM_U = nullptr, *FM_T = nullptr, *FM_PART = nullptr;      // vc_flux_eval_loss (carved only while option eval_loss is on): u_t, t, the sum's partials
   void* ATT_SCRATCH = nullptr;
   int64_t att_scratch_bytes = 0;
@@ -62,6 +64,7 @@ struct Options {
   int adaptive = 0;
   int sde = 0;
   int eval_loss = 0;
+  int multistep = 0;
 };
 enum Clamp { ANY, BOOL, AT_LEAST_0, ZERO_TO_2, ZERO_OR_H };
 #define OPT(name, clamp) {#name, &Options::name, clamp}
@@ -75,6 +78,7 @@ inline constexpr OptionRule OPTIONS[] = {      // (inline: ONE table for the thr
     OPT(adaptive, BOOL),                                         // 1: the workspace holds the adaptive solve's buffers (vc_flux_sample_dopri5)
     OPT(sde, BOOL),                                              // 1: ... the stochastic sampler's (vc_flux_sample_sde)
     OPT(eval_loss, BOOL),                                        // 1: ... the flow-matching loss's (vc_flux_eval_loss)
+    OPT(multistep, BOOL),                                        // 1: ... the multistep solve's (vc_flux_sample_multistep)
 };
 #undef OPT
 inline bool operator==(const Options& a, const Options& b) {
@@ -87,6 +91,7 @@ inline bool operator==(const Options& a, const Options& b) {
 constexpr int SOLVER_DOPRI5 = 100;     // the adaptive solve: no VC_SOLVER_* code (vc_solver_evals keeps refusing it)
 constexpr int SOLVER_SDE_EULER = 101, SOLVER_SDE_HEUN = 102;     // the stochastic sampler: likewise (one captured step per method)
 constexpr int SOLVER_RK = 103;         // the embedded pairs of vc_flux_sample_rk: ONE code, the pair is Trajectory::rk (VC_RK_*)
+constexpr int SOLVER_MULTISTEP = 104;  // the Adams-Bashforth solve: ONE code and one captured step, the order lives in the table
 struct Trajectory {
   int method = VC_SOLVER_EULER;        // VC_SOLVER_*, or one of the codes above
   int evals = 1;                       // replays of the captured evaluation per step

@@ -83,6 +83,11 @@ int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, cons
 int vc_sde_store_launch(const float* y, void* out, int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_sde_plan_impl(const char* method, const char* form, double norm, const char* last_step, double last_step_size, const float* t_grid,
                      int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals, int32_t* n_draws, char* err, int errlen);
+// multistep.hip: the Adams-Bashforth multistep solver's host rule and its update
+int vc_ms_plan_impl(int32_t order, const float* t_grid, int32_t n_points, float* rows, float* times, int32_t capacity, int32_t* n_evals,
+                    char* err, int errlen);
+int vc_ms_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* hist, void* y_in, const int32_t* eval_ptr,
+                       int64_t n, hipStream_t s, char* err, int errlen);
 int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen);
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
@@ -221,6 +226,9 @@ int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, i
                             int32_t* evaluations, char* err, int errlen);
 int vc_flux_sample_rk_impl(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
                            float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen);
+int vc_flux_sample_multistep_impl(void* handle, int32_t order, void* x, const void* cond, const float* t_grid, int32_t n_points,
+                                  int32_t state_is_bf16, void* trajectory, hipStream_t s, char* err, int errlen);
+int vc_flux_plan_count_impl(void* handle);
 int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const void* cond, const float* t_grid, int32_t n_points, const char* form,
                             double norm, const char* last_step, double last_step_size, uint64_t seed, uint64_t offset, int32_t state_is_bf16,
                             void* trajectory, hipStream_t s, char* err, int errlen);

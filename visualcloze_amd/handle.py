@@ -150,6 +150,7 @@ class FluxHandle(_Handle):
         self.adaptive = 0
         self.sde = 0
         self.eval_loss_on = 0
+        self.multistep = 0
         if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
             scales = []
             for name, R in weights.ref.items():
@@ -374,6 +375,18 @@ class FluxHandle(_Handle):
             self.eval_loss_on = int(bool(on))
             self.geom = None
 
+    def set_multistep(self, on: bool) -> None:
+        """vc_flux_set_option("multistep"): 1 = the workspace holds the buffers of the Adams-Bashforth solve (`sample_multistep`).  A
+        switch needs a new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
+        hip._check(hip.lib().vc_flux_set_option(self.h, b"multistep", int(bool(on))), "vc_flux_set_option(multistep)")
+        if int(bool(on)) != self.multistep:
+            self.multistep = int(bool(on))
+            self.geom = None
+
+    def plan_count(self) -> int:
+        """vc_flux_plan_count: the captured steps the handle holds"""
+        return hip.lib().vc_flux_plan_count(self.h)
+
     def set_lora_scale(self, scale: float) -> None:
         """vc_flux_set_lora_scale: the scale of every pair; a bf16 value, anything else is refused, and so is a change while a
         trajectory is in flight.  Call `prepare` again after a change (forward / sample_* refuse a prepared state of the old scale);
@@ -433,7 +446,7 @@ class FluxHandle(_Handle):
 
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
         key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ()) + (("sde",) if self.sde else ()) + \
-            (("eval_loss",) if self.eval_loss_on else ())
+            (("eval_loss",) if self.eval_loss_on else ()) + (("multistep",) if self.multistep else ())
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:
@@ -590,6 +603,15 @@ class FluxHandle(_Handle):
         hip._check(hip.lib().vc_flux_sample_sde(self.h, hip._cstr(method), args[2], args[3], args[4], args[5], hip._cstr(form), float(norm),
                                                 hip._cstr(last_step), float(last_step_size), hip._u64(seed, "seed"), hip._u64(offset, "offset"),
                                                 args[6], hip._p(trajectory), stream), "vc_flux_sample_sde")
+
+    def sample_multistep(self, order: int, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
+        """vc_flux_sample_multistep (after `set_multistep(True)` and a prepare with max_steps >= len(t_grid) - 1): x [B,N,C] in place,
+        x(t_grid[0]) -> x(t_grid[-1]) by the Adams-Bashforth rule of `order` (1..4), one evaluation per step; trajectory: optional
+        [len(t_grid), B, N, C] buffer: the start state, then the state after every step.  The state is stepped in f32 whatever its
+        dtype."""
+        args = self._sample_args("vc_flux_sample_multistep", 0, x, cond, t_grid, state_is_bf16, trajectory)
+        hip._check(hip.lib().vc_flux_sample_multistep(self.h, int(order), args[2], args[3], args[4], args[5], args[6], hip._p(trajectory),
+                                                      stream), "vc_flux_sample_multistep")
 
     def dopri5_log(self) -> dict:
         """vc_flux_dopri5_log of the last `sample_dopri5`: {"attempts": [(t, dt, ratio, accepted), ...], "evaluations", "rejected"}"""

@@ -22,6 +22,7 @@ ABI_VERSION = 11               # VC_ABI_VERSION of include/vcloze_hip.h
 SOLVER_EULER, SOLVER_MIDPOINT, SOLVER_RK4 = 0, 1, 2     # VC_SOLVER_*: the fixed-grid methods of the fused sampling loop
 SOLVERS = {"euler": SOLVER_EULER, "midpoint": SOLVER_MIDPOINT, "rk4": SOLVER_RK4}
 SDE_EM, SDE_HEUN1, SDE_HEUN2, SDE_LAST, SDE_INJECT, SDE_ROW = 0, 1, 2, 3, 4, 5     # VC_SDE_*: the row modes of vc_sde_stage, values per row
+MS_ROW, MS_HIST = 4, 3         # VC_MS_ROW / VC_MS_HIST: coefficients per row (= the highest order) and ring planes of vc_ms_stage
 GEMM_MAX_PROBLEMS = 4          # VC_GEMM_MAX_PROBLEMS: grouped problems per vc_gemm launch
 EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_SILU, EPI_QKV = 0, 1, 2, 3, 4
 GEMM_NO_SPLIT = 64             # VC_GEMM_NO_SPLIT: tile_cfg value that keeps an auto-tiled vc_gemm one launch
@@ -238,6 +239,8 @@ SYMBOLS = {
     "vc_sde_plan": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_char_p, C.c_double, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float),
                               C.POINTER(C.c_float), _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_sde_stage": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "vc_ms_plan": (C.c_int, [_i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
+    "vc_ms_stage": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "vc_residual_change": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "vc_residual_sub": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
     "vc_residual_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp]),
@@ -309,6 +312,8 @@ SYMBOLS = {
                                  C.POINTER(_i32), C.POINTER(_i32)]),
     "vc_flux_sample_sde": (C.c_int, [_vp, C.c_char_p, _vp, _vp, C.POINTER(C.c_float), _i32, C.c_char_p, C.c_double, C.c_char_p, C.c_double,
                                      C.c_uint64, C.c_uint64, _i32, _vp, _vp]),
+    "vc_flux_sample_multistep": (C.c_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_float), _i32, _i32, _vp, _vp]),
+    "vc_flux_plan_count": (C.c_int, [_vp]),
     "vc_flux_set_step_cache": (C.c_int, [_vp, C.c_float, _i32]),
     "vc_flux_set_cfg": (C.c_int, [_vp, _i32, C.c_float]),
     "vc_flux_step_cache_stats": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_float), _i32]),
@@ -984,6 +989,42 @@ def sde_plan(method: str, form: str, norm: float, last_step, last_step_size: flo
                              C.byref(ne), C.byref(nd)), "vc_sde_plan")
     n_rows = ne.value + (1 if method == "Heun" else 0)
     return {"rows": rows[:n_rows], "times": times[:ne.value], "evals": ne.value, "draws": nd.value}
+
+
+def ms_plan(order: int, t_grid) -> dict:
+    """vc_ms_plan (host only): the coefficient rows and model times of an Adams-Bashforth trajectory of `order` (1..4) over the f32
+    grid `t_grid` -> {"rows": f32 [n - 1, 4], "times": f32 [n - 1] (1 - t), "evals": n - 1}.  A refusal (the order, fewer than two
+    points, a grid that does not increase, a non-finite coefficient) raises VclozeHipError."""
+    t = np.ascontiguousarray(t_grid.detach().cpu().numpy() if torch.is_tensor(t_grid) else t_grid, dtype=np.float32).reshape(-1)
+    tp = t.ctypes.data_as(C.POINTER(C.c_float)) if t.size else None
+    ne = C.c_int32(0)
+    _check(lib().vc_ms_plan(int(order), tp, int(t.size), None, None, 0, C.byref(ne)), "vc_ms_plan")
+    cap = ne.value
+    rows, times = np.zeros((cap, MS_ROW), np.float32), np.zeros(cap, np.float32)
+    _check(lib().vc_ms_plan(int(order), tp, int(t.size), rows.ctypes.data_as(C.POINTER(C.c_float)),
+                            times.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ne)), "vc_ms_plan")
+    return {"rows": rows, "times": times, "evals": ne.value}
+
+
+def ms_stage(eval_index: int, table, y, v, hist, y_in, eval_ptr=None, stream=None) -> None:
+    """vc_ms_stage: one Adams-Bashforth update on n = y.numel() elements.  table: f32 [n_rows, 4] (device); row = eval_index, or with
+    eval_index < 0 the device-side counter eval_ptr (int32 [1]).  y: f32 [n]; v: the model's bf16 output [n]; hist: bf16 [3, n], the
+    ring of past outputs (v_{e-j} in slot (e - j) % 3; v is stored into slot e % 3); y_in: bf16 [n] <- bf16(y)."""
+    n = y.numel()
+    for name, t, dt in (("table", table, torch.float32), ("y", y, torch.float32), ("v", v, torch.bfloat16), ("hist", hist, torch.bfloat16),
+                        ("y_in", y_in, torch.bfloat16), ("eval_ptr", eval_ptr, torch.int32)):
+        if t is None:
+            if name == "eval_ptr":
+                continue
+            raise VclozeHipError(f"vc_ms_stage: {name} is required")
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise VclozeHipError(f"vc_ms_stage: {name} must be a contiguous CUDA {dt} tensor, got {t.dtype} on {t.device}")
+        if name in ("v", "y_in") and t.numel() != n:
+            raise VclozeHipError(f"vc_ms_stage: {name} must hold n = {n} values, got {t.numel()}")
+    if table.dim() != 2 or table.shape[1] != MS_ROW or hist.numel() != MS_HIST * n:
+        raise VclozeHipError(f"vc_ms_stage: table must be [n_rows, {MS_ROW}] and hist hold {MS_HIST} planes of n = {n} values")
+    _check(lib().vc_ms_stage(int(eval_index), table.data_ptr(), table.shape[0], y.data_ptr(), v.data_ptr(), hist.data_ptr(), y_in.data_ptr(),
+                             _p(eval_ptr), n, stream if stream is not None else cur_stream()), "vc_ms_stage")
 
 
 def rng_words(seed, offset, device=None) -> torch.Tensor:

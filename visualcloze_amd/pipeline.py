@@ -165,18 +165,27 @@ def _kwargs(inp_ids, inp_mask, txt, vec, cond, cfg, dev):
 def denoise_grid(model, noise_rows: List[torch.Tensor], cond_latent_rows: List[torch.Tensor],
                  mask_rows: List[torch.Tensor], txt: torch.Tensor, vec: torch.Tensor, cfg: float = 30.0,
                  steps: int = 30, solver: str = "euler", time_shifting_factor=1, step_cache=None,
-                 adaptive: Optional[dict] = None, sde: Optional[dict] = None, rng=None) -> List[torch.Tensor]:
+                 adaptive: Optional[dict] = None, sde: Optional[dict] = None, rng=None,
+                 multistep: Optional[dict] = None) -> List[torch.Tensor]:
     """One grid: per-row noise [1,16,h,w], VAE latents of the grid rows (already shifted/scaled), per-row PIXEL
     fill masks [1,1,8h,8w]; txt [1,T,4096], vec [1,768].  Returns the denoised row latents [1,16,h,w].
     `adaptive`: None, or dict(rtol=, atol=[, max_attempts=][, method=]) - the error-controlled solve (`Sampler.sample_ode_adaptive`:
     Dormand-Prince 5(4), or with method="bosh3" / "adaptive_heun" a cheaper embedded pair) instead of `solver`; `steps` then only places the end time's grid.
     `sde`: None, or dict(sampling_method=, diffusion_form=, diffusion_norm=, last_step=, last_step_size=, sample_eps=) - any subset -
     the stochastic sampler (`Sampler.sample_sde`, num_steps = `steps`) instead of `solver`; its noise comes from `rng`, which must be a
-    `NoiseStream` (its offset advances by the draws).  Image quality under any diffusion form is unmeasured."""
+    `NoiseStream` (its offset advances by the draws).  Image quality under any diffusion form is unmeasured.
+    `multistep`: None, or dict(order=) - the Adams-Bashforth multistep solve (`Sampler.sample_ode_multistep`, num_steps = `steps`, one
+    evaluation per step) instead of `solver`.  Image quality at any order is unmeasured."""
     dev = noise_rows[0].device
     img, img_ids, img_mask = packing.prepare_grid([noise_rows])                       # visualcloze.py:403
     cond = packing.pack_cond(cond_latent_rows, mask_rows)                              # :381-389
     sampler = Sampler(create_transport("Linear", "velocity", do_shift=True))
+    if multistep is not None:
+        if adaptive is not None or sde is not None or step_cache is not None:
+            raise ValueError("multistep: the multistep solve works neither with adaptive=, nor with sde=, nor with the step cache")
+        fn = sampler.sample_ode_multistep(num_steps=steps, do_shift=True, time_shifting_factor=time_shifting_factor, **multistep)
+        samples = fn(img, model.forward, _kwargs(img_ids, img_mask, txt, vec, cond, cfg, dev))[-1][:1]
+        return packing.unpack_rows(samples, [tuple(r.shape[-2:]) for r in noise_rows])
     if sde is not None:
         if adaptive is not None or step_cache is not None:
             raise ValueError("sde: the stochastic sampler works neither with adaptive= nor with the step cache")
@@ -257,7 +266,7 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
                   encode_noise: Optional[List[torch.Tensor]] = None, decode_rows: Optional[Sequence[int]] = None,
                   solver: str = "euler", time_shifting_factor=1, rng: Union[torch.Generator, NoiseStream, None] = None,
                   step_cache=None, use_grid_handle: bool = False, adaptive: Optional[dict] = None,
-                  monitor: Optional[int] = None, sde: Optional[dict] = None) -> List[torch.Tensor]:
+                  monitor: Optional[int] = None, sde: Optional[dict] = None, multistep: Optional[dict] = None) -> List[torch.Tensor]:
     """One grid, pixels in, pixels out (visualcloze.py:363-434).
 
     row_images[i]: [3, H, W_row] in [-1, 1] (the images of grid row i side by side); row_masks[i]: [1, 1, H, W_row]
@@ -283,7 +292,23 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     `model.monitor_strict` a NaN / inf raises FloatingPointError.  Refused together with use_grid_handle=True, `adaptive` and `sde`.
     `sde`: None (the default), or a dict of `Sampler.sample_sde` settings - denoise with the stochastic sampler instead of `solver`
     (`denoise_grid`); needs `rng` to be a `NoiseStream`, from which the sampler's draws follow the start noise.  Refused together with
-    use_grid_handle=True: the grid handle runs the fixed-grid solvers only."""
+    use_grid_handle=True: the grid handle runs the fixed-grid solvers only.
+    `multistep`: None (the default), or dict(order=) - denoise with the Adams-Bashforth multistep solve of that order (1..4, one
+    evaluation per step) instead of `solver` (`denoise_grid`, `Sampler.sample_ode_multistep`).  Refused together with
+    use_grid_handle=True, `adaptive`, `sde`, `step_cache` and a `monitor` level above 0."""
+    if multistep is not None:
+        if use_grid_handle:
+            raise ValueError("generate_grid(multistep=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid "
+                             "solvers only")
+        if adaptive is not None:
+            raise ValueError("generate_grid(multistep=...) does not work with adaptive=: one solver per call")
+        if sde is not None:
+            raise ValueError("generate_grid(multistep=...) does not work with sde=: one solver per call")
+        if step_cache is not None:
+            raise ValueError("generate_grid(multistep=...) does not work with step_cache=: the step cache works with the fixed-grid Euler "
+                             "loop only")
+        if monitor:
+            raise ValueError("generate_grid(multistep=...) does not work with monitor=: the multistep solve is not logged")
     if sde is not None:
         if use_grid_handle:
             raise ValueError("generate_grid(sde=...) does not work with use_grid_handle=True: the grid handle runs the fixed-grid solvers only")
@@ -299,7 +324,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
         try:
             return generate_grid(model, ae, t5, clip, row_images, row_masks, t5_ids, clip_ids, seed, cfg=cfg, steps=steps,
                                  encode_noise=encode_noise, decode_rows=decode_rows, solver=solver, time_shifting_factor=time_shifting_factor,
-                                 rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle, adaptive=adaptive, sde=sde)
+                                 rng=rng, step_cache=step_cache, use_grid_handle=use_grid_handle, adaptive=adaptive, sde=sde,
+                                 multistep=multistep)
         finally:
             model.monitor = before
     if adaptive is not None and use_grid_handle:
@@ -324,7 +350,8 @@ def generate_grid(model, ae, t5, clip, row_images: List[torch.Tensor], row_masks
     txt = t5(t5_ids)                                                                   # prepare_modified -> HFEmbedder
     vec, _ = clip(clip_ids)
     rows = denoise_grid(model, noise, lat, row_masks, txt, vec, cfg=cfg, steps=steps, solver=solver,
-                        time_shifting_factor=time_shifting_factor, step_cache=step_cache, adaptive=adaptive, sde=sde, rng=rng)
+                        time_shifting_factor=time_shifting_factor, step_cache=step_cache, adaptive=adaptive, sde=sde, rng=rng,
+                        multistep=multistep)
     out = []
     for i in (range(len(rows)) if decode_rows is None else decode_rows):
         img = ae.decode(rows[i])[0]                                                    # :430

@@ -859,6 +859,89 @@ def sde_integrate(f, x: torch.Tensor, plan: dict, noise: Callable) -> torch.Tens
     return torch.stack(outs)
 
 
+MS_MAX_ORDER = 4
+
+
+def ms_plan(order: int, t, rounded: bool = True) -> dict:
+    """The host rule of the Adams-Bashforth multistep solve, bit for bit vc_ms_plan (hip.ms_plan): the f32 time grid `t` (n points) and
+    the order (1..4) -> {"rows": [n - 1, 4] = c_{i,0..3} per step, "times": f32 [n - 1] = the model times 1 - t_i, "evals": n - 1}.
+    Step i uses k = min(order, i + 1) nodes tau_j = t_{i-j}; c_{i,j} = the integral over [t_i, t_{i+1}] of the Lagrange polynomial of
+    node j, computed in double from the widened f32 grid values - in u = (tau - t_i) / h the numerator is multiplied out factor by
+    factor, integrated term by term, divided by the running product of the node differences and scaled by h - and rounded ONCE to f32;
+    unused entries are exactly 0.  rounded=False: "rows" holds the double coefficients (what an f64 state is stepped with).
+    ValueError for an order outside 1..4, fewer than two points, a grid that does not increase strictly and any non-finite
+    coefficient."""
+    import numpy as np
+    if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= MS_MAX_ORDER:
+        raise ValueError(f"ms_plan: order = {order!r} outside 1..{MS_MAX_ORDER}")
+    t32 = np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float32).reshape(-1)
+    n = int(t32.size)
+    if n < 2:
+        raise ValueError(f"ms_plan: n_points = {n}, at least 2 expected")
+    if not bool(np.all(t32[1:] > t32[:-1])):
+        raise ValueError("ms_plan: t must increase strictly")
+    tt = [float(v) for v in t32]
+    rows64 = []
+    for i in range(n - 1):
+        k = min(order, i + 1)
+        ti = tt[i]
+        h = tt[i + 1] - ti
+        b = [(tt[i - m] - ti) / h for m in range(k)]
+        row = [0.0] * MS_MAX_ORDER
+        for j in range(k):
+            p, den = [1.0], 1.0
+            for m in range(k):
+                if m == j:
+                    continue
+                deg = len(p) - 1
+                q = [-(b[m] * p[0])] + [p[d - 1] - b[m] * p[d] for d in range(1, deg + 1)] + [p[deg]]
+                p = q
+                den = den * (b[j] - b[m])
+            integral = 0.0
+            for d, pd in enumerate(p):
+                integral = integral + pd / float(d + 1)
+            c = h * _div(integral, den)
+            with np.errstate(all="ignore"):
+                finite = math.isfinite(float(np.float32(c)))
+            if not finite:
+                raise ValueError(f"ms_plan: the coefficient c[{i}][{j}] = {c!r} of the step from t = {ti!r} to {tt[i + 1]!r} is not finite "
+                                 f"(order {order})")
+            row[j] = c
+        rows64.append(row)
+    rows = np.array(rows64, dtype=np.float64).reshape(n - 1, MS_MAX_ORDER)
+    return {"rows": rows.astype(np.float32) if rounded else rows, "times": np.float32(1.0) - t32[:-1], "evals": n - 1, "order": order}
+
+
+def multistep_integrate(f, y0: torch.Tensor, t, order: int) -> torch.Tensor:
+    """The Adams-Bashforth multistep solve as literal torch expressions - what vc_ms_stage computes, operation by operation (an f32
+    state gives the kernel's bits) - for any callable and an f32 or f64 state: -> [n_points, ...], y0 and the state after every step.
+    f(t_i, y) is the DRIFT for the state y at the grid time t_i (a Python float, the widened f32 value); ONE call per step, its result
+    is kept as returned (a bf16 velocity stays bf16) and widened where a later step uses it.  Step i:
+        y <- y + (((c0 f_i) + c1 f_{i-1}) + c2 f_{i-2}) + c3 f_{i-3}
+    left to right; a coefficient c_j, j >= 1, that is exactly zero adds no term.  An f64 state is stepped with the double coefficients
+    (ms_plan(rounded=False)), an f32 state with the f32 rows."""
+    if y0.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"multistep_integrate: an f32 or f64 state expected, got {y0.dtype}")
+    plan = ms_plan(order, t, rounded=y0.dtype != torch.float64)
+    t32 = t.detach().cpu().to(torch.float32).reshape(-1) if torch.is_tensor(t) else torch.tensor(t, dtype=torch.float32).reshape(-1)
+    y, past, outs = y0, [], [y0]
+    for i in range(plan["evals"]):
+        c0, c1, c2, c3 = (float(c) for c in plan["rows"][i])
+        past.insert(0, f(float(t32[i]), y))
+        del past[MS_MAX_ORDER:]
+        fs = [past[j].to(y0.dtype) if j < len(past) else None for j in range(MS_MAX_ORDER)]
+        z = c0 * fs[0]
+        if c1 != 0.0:
+            z = z + c1 * fs[1]
+        if c2 != 0.0:
+            z = z + c2 * fs[2]
+        y = y + z
+        if c3 != 0.0:
+            y = y + c3 * fs[3]
+        outs.append(y)
+    return torch.stack(outs)
+
+
 class StepCache:
     """Opt-in first-block step cache of the fused Euler loop (vc_flux_set_step_cache).  IT CHANGES RESULTS: an
     evaluation whose first-block residual moved by less than `threshold` (relative L1 against the last computed evaluation's) is
@@ -993,6 +1076,39 @@ class Sampler:
         return _sample
 
 
+    def sample_ode_multistep(self, *, order: int = 2, num_steps=50, reverse=False, do_shift=True, time_shifting_factor=None, strength=None,
+                             return_trajectory: bool = False):
+        """A fixed-grid, variable-step Adams-Bashforth solve of `order` 1..4 on sample_ode's own (time-shifted) grid, under a name of
+        its own: sample_ode("adams") keeps raising.  ONE model evaluation per step - the velocities of the last steps are reused; the
+        first steps run at the orders 1, 2, ... (no extra evaluations).  Returns `_sample(x, model, model_kwargs)` -> [1, B, N, C], or
+        [num_steps, B, N, C] with return_trajectory (the start state, then the state after every step), in the caller's dtype.
+        Fused (vc_flux_sample_multistep: replays of one captured evaluation, whatever the order) for the bound forward /
+        forward_with_cfg of a visualcloze_amd.Flux that has the C handle and a bf16 or f32 state, eager (`multistep_integrate`)
+        otherwise.  The state is stepped in f32 (f64 for an f64 caller) and rounded once per output.
+        Order 1 is Euler's rule with f32 roundings (not bit-equal to sample_ode("euler"), whose step multiplies by bf16(dt)); orders
+        3 and 4 have small stability regions and no order is recommended; image quality at any order is unmeasured."""
+        if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= MS_MAX_ORDER:
+            raise ValueError(f"sample_ode_multistep: order = {order!r} outside 1..{MS_MAX_ORDER}")
+        t0, t1 = self.transport.check_interval(reverse=reverse)
+        if strength is not None:
+            t0 = (t1 - t0) * strength + t0
+        assert t0 < t1, "ODE sampler has to be in forward time"
+
+        def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
+            t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
+            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
+            is_flux = kind != "foreign"
+            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
+            if fused and cfg_scale is not None:
+                fused = _cfg_fusable(owner, x, "euler", kw)
+            if fused:
+                return _sample_multistep_fused(owner, x, kw, t, order, return_trajectory, cfg_scale)
+            if cfg_scale is not None:
+                model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
+            return _sample_multistep_foreign(model, x, kw, t, order, return_trajectory, bf16_out=is_flux)
+
+        return _sample
+
     def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
                    num_steps=250, sample_eps=None, rng=None, return_trajectory: bool = False):
         """The reference's stochastic sampler (transport.py:300-359; names, defaults and call shape are its own): returns
@@ -1051,6 +1167,29 @@ class Sampler:
             return out
 
         return _sample
+
+
+def _sample_multistep_foreign(model, x, kw, t, order, return_trajectory, bf16_out=False):
+    """Any callable: transport.multistep_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
+    drift = _adaptive_drift(model, x, kw, bf16_out)
+    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
+    with torch.no_grad():
+        out = multistep_integrate(drift, y0, t.to(torch.float32), order).to(x.dtype)
+    return out if return_trajectory else out[-1:]
+
+
+@torch.no_grad()
+def _sample_multistep_fused(flux, x, kw, t, order, return_trajectory, cfg_scale=None):
+    """vc_flux_sample_multistep per chunk of samples"""
+    h = flux.handle()
+    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_multistep refuses it)
+        raise ValueError("monitor: the multistep solve is not logged; set Flux.monitor = 0 or use a fixed-grid solver")
+    t32 = t.to(torch.float32)
+
+    def run(xs, cond, tj, s):
+        h.sample_multistep(order, xs, cond, t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+
+    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, len(t) - 1, run, cfg_scale=cfg_scale, multistep=True)
 
 
 def _sample_sde_foreign(model, x, kw, plan, seed, offset, return_trajectory, bf16_out=False):
@@ -1148,11 +1287,13 @@ def _solve_begin(flux, x, kw, S, return_trajectory, pairs=False):
     return plan, cond, out, torch.empty(S, B, N, C, dtype=x.dtype, device=plan.dev) if return_trajectory else None
 
 
-def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False, sde=False):
+def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False, sde=False,
+                     multistep=False):
     """What the fused solves through the C handle share.  Per trajectory: the options, taken back on failure too.  Per chunk of samples
     (true CFG: whole pairs (j, j + B/2), conditional samples first): vc_flux_prepare for `max_evals` evaluations, a copy of the state's
     rows in kernel order for run(xs, cond rows, trajectory buffer [S, bs, N, C] or None, stream) to advance in place, and the way back.
-    sde: the stochastic sampler's option, and its trajectory as it stands (S rows that end with the sample; no start state in front)."""
+    sde: the stochastic sampler's option, and its trajectory as it stands (S rows that end with the sample; no start state in front).
+    multistep: the multistep solve's option, and its trajectory as it stands (S rows that begin with the start state)."""
     plan, cond, out, traj = _solve_begin(flux, x, kw, S, return_trajectory, pairs=cfg_scale is not None)
     with _on_capture_stream(flux.plan().stream) as s:
         try:
@@ -1162,6 +1303,8 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
                 h.set_adaptive(True)
             if sde:
                 h.set_sde(True)
+            if multistep:
+                h.set_multistep(True)
             for sl in plan.chunks:
                 h.prepare(*plan.prepare_args(sl, max_evals), stream=s)
                 xs = plan.img_rows(x, sl, x.dtype, copy=True)       # stepped in ITS dtype, in place: never the caller's
@@ -1175,9 +1318,11 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
                 h.set_adaptive(False)              # a later fixed-grid trajectory sizes its workspace as it always did
             if sde:
                 h.set_sde(False)
+            if multistep:
+                h.set_multistep(False)
             if cfg_scale is not None:
                 h.set_cfg(None)                    # a later trajectory driven on this handle directly is a plain one again
-    if sde and traj is not None:
+    if (sde or multistep) and traj is not None:
         return traj
     return out[None] if traj is None else torch.cat((x.to(out.device)[None], traj), dim=0)
 
