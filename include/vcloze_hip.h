@@ -299,7 +299,7 @@ int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, 
  * vc_flux_sample_dopri5, vc_flux_dopri5_log) by SYMBOL - look up vc_dopri5_stage.  VC_SOLVER_* has no code for it and
  * vc_solver_evals / vc_flux_sample_ode keep refusing anything but the fixed-grid methods.
  * With f(t, y) = -model(bf16(y) || cond, 1 - f32(t)): every k is stored in bf16 (the model's output dtype), the state y is F32.  The
- * tableau is SciPy's RK45.C / .A / .B / .E and torchdiffeq's DPS_C_MID (written out in csrc/dopri5.hip), each coefficient a double
+ * tableau is SciPy's RK45.C / .A / .B / .E and torchdiffeq's DPS_C_MID (written out in csrc/rk_embedded.hip), each coefficient a double
  * rounded once to f32; every sum runs left to right over the non-zero coefficients, one f32 operation after the other, no fused
  * multiply-add, so a torch f32 expression of the same shape gives the same bits (transport.dopri5_integrate is that expression).
  * The controller is torchdiffeq's as recalled, unpinned against real torchdiffeq (the package was not available to check against); it is

@@ -47,28 +47,31 @@ static void fixed_grid(const std::vector<float>& grid) {
     }
 }
 
+// the adaptive solve's rules at Dormand-Prince: VC_RK_DOPRI5, order 5
 static void dopri5() {
+  const int order = vcrules::rk_order(VC_RK_DOPRI5);
+  CHECK(order == 5 && vcrules::rk_stages(VC_RK_DOPRI5) == 7);
   // (d0, d1, r = rms(f(t0 + h0) - f0)): the ordinary case, d0 < 1e-5, max(d1, d2) <= 1e-15
   const double cases[3][3] = {{0.5, 0.25, ldexp(1.0, -10)}, {ldexp(1.0, -20), 0.25, ldexp(1.0, -12)}, {0.5, ldexp(1.0, -60), 0.0}};
   for (const auto& c : cases) {
-    const double h0 = vcrules::dopri5_h0(c[0], c[1]);
-    printf("initial %a %a %a %a %a\n", c[0], c[1], c[2], h0, vcrules::dopri5_first_dt(h0, c[1], c[2] / h0));
+    const double h0 = vcrules::rk_h0(c[0], c[1]);
+    printf("initial %a %a %a %a %a\n", c[0], c[1], c[2], h0, vcrules::rk_first_dt(order, h0, c[1], c[2] / h0));
   }
   const double ratios[6] = {0.0, 0.5, 1.0, 1.0 + ldexp(1.0, -23), 7.0, 1e-12};
   for (double r : ratios) {
     bool accept = false;
     double factor = 0;
-    CHECK(vcrules::dopri5_controller(r, &accept, &factor));
+    CHECK(vcrules::rk_controller(order, r, &accept, &factor));
     printf("controller %a %d %a\n", r, (int)accept, factor);
   }
   bool accept = true;
   double factor = 0;
-  CHECK(!vcrules::dopri5_controller(std::numeric_limits<double>::quiet_NaN(), &accept, &factor) && !accept);
+  CHECK(!vcrules::rk_controller(order, std::numeric_limits<double>::quiet_NaN(), &accept, &factor) && !accept);
   printf("controller nan refused\n");
   const double steps[3][2] = {{0.0, 0.0}, {0.0, 1e-6}, {0.3721, 0.0713}};
   for (const auto& st : steps) {
     Exact<float> tm(7);
-    vcrules::dopri5_row_times(st[0], st[1], tm.p);
+    vcrules::rk_row_times(VC_RK_DOPRI5, st[0], st[1], tm.p);
     printf("rows %a %a", st[0], st[1]);
     for (int j = 0; j < 7; ++j) printf(" %a", (double)tm.p[j]);
     printf("\n");

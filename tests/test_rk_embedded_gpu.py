@@ -2,9 +2,10 @@
 
   * vc_rk_stage and vc_rk_interp against the torch f32 expressions of transport.py (rk_step, rk_hermite), bit for bit, at sizes that
     take the 16-byte body, the scalar tail, more than 256 blocks x 256 threads and a base 2 bytes off alignment;
-  * VC_RK_DOPRI5 against vc_dopri5_stage / vc_dopri5_error_ratio, bit for bit: the generic code is held to the pinned one;
-  * vc_rk_error_ratio against fp64 inside the budget of its f32 arithmetic, reproducible, moved by its last element - and bit-equal
-    to transport.rk_error_ratio, which restates the kernel's summation order;
+  * VC_RK_DOPRI5 against vc_dopri5_stage / vc_dopri5_error_ratio, bit for bit: the vc_dopri5_* entries are the same kernels under
+    their own names (what pins Dormand-Prince itself are the stage and norm tests, which run every method);
+  * vc_rk_error_ratio, Dormand-Prince included, against fp64 inside the budget of its f32 arithmetic, reproducible, moved by its
+    last element - and bit-equal to transport.rk_error_ratio, which restates the kernel's summation order;
   * the fused solve against transport.rk_integrate through Flux.forward: every output bit and an identical log;
   * the refusals, the workspace bytes, and Dormand-Prince and Euler on the same handle before and after.
 The controller is torchdiffeq's as recalled, unpinned against real torchdiffeq (tests/test_rk_embedded_cpu.py pins the tableaus and
@@ -127,7 +128,7 @@ def test_stage_equals_the_torch_expressions_bitwise(method, n, off):
             hip.rk_stage(3, 0, y0, k, vs[0], dt_dev, None, y_stage, None)
 
 
-# ---------------------------------------------------------------------------------------------- 2. the generic code against the pinned one
+# ---------------------------------------------------------------------------------------------- 2. the vc_dopri5_* entries are aliases
 @pytest.mark.parametrize("off", [0, 1])
 @pytest.mark.parametrize("n", SIZES)
 def test_dopri5_method_returns_the_bits_of_the_dopri5_kernels(n, off):
@@ -184,7 +185,7 @@ def _ratio64(method, y0, y1, ks, dt32, rtol, atol):
 
 @pytest.mark.parametrize("off", [0, 1])
 @pytest.mark.parametrize("n", SIZES)
-@pytest.mark.parametrize("method", PAIRS)
+@pytest.mark.parametrize("method", METHODS)
 def test_error_ratio_within_its_f32_budget_reproducible_and_the_twins_bits(method, n, off):
     from tests.budget import assert_within_budget
     from visualcloze_amd import hip

@@ -1,7 +1,7 @@
 """CPU: the rk_* host rules of csrc/flux_rules.h against transport.rk_controller / rk_initial_step and the tableaus' stage times, bit
 for bit.  tests/c_abi/rk_rules_check.cpp (its own main) takes the cases from here, runs the rules at the buffer sizes the engine passes
-under AddressSanitizer and UBSan - a stand-alone host program, run directly - compares the order-5 rules with their dopri5_* twins
-itself and prints hex floats."""
+under AddressSanitizer and UBSan - a stand-alone host program, run directly - and prints hex floats.  Dormand-Prince is method 0 of
+the same rules; tests/test_flux_rules_cpu.py holds them at order 5 to transport.dopri5_*."""
 import os
 import shutil
 import subprocess

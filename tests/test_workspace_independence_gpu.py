@@ -665,8 +665,8 @@ def _live_results(m, J):
 @pytest.mark.parametrize("kind", ["b2", "gap"])
 def test_live_rows_depend_on_live_inputs_only(inputs, kind):
     """NaN in a masked row is not part of the property (the reference's own masked softmax turns 0 * NaN into NaN); large finite
-    values are.  The adaptive solvers' error norm and the step cache's metric sum over every row, masked ones included (dopri5.hip,
-    rk_embedded.hip, step_cache.hip take no mask), so those two are not asserted here."""
+    values are.  The adaptive solvers' error norm and the step cache's metric sum over every row, masked ones included
+    (rk_embedded.hip, step_cache.hip take no mask), so those two are not asserted here."""
     inp = flux_inputs(kind)
     I = inputs[kind]
     m = _model()

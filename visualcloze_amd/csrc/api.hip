@@ -109,17 +109,18 @@ int vc_ode_stage(int32_t method, int32_t stage, void* y, int32_t state_is_bf16, 
                  const float* dts, const int32_t* eval_ptr, int64_t n, void* stream) {
   return vc_ode_stage_launch(method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, S(stream), ERRBUF);
 }
+// vc_dopri5_*: the rk launchers at VC_RK_DOPRI5, under their own names in the messages
 int vc_dopri5_stage(int32_t stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr, float* y_stage,
                     void* y_in, int64_t n, void* stream) {
-  return vc_dopri5_stage_launch(stage, y0, k, v, dt_ptr, eval_ptr, y_stage, y_in, n, S(stream), ERRBUF);
+  return vc_rk_stage_launch(VC_RK_DOPRI5, stage, y0, k, v, dt_ptr, eval_ptr, y_stage, y_in, n, S(stream), ERRBUF, "dopri5_stage");
 }
 int vc_dopri5_error_ratio(int32_t mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
                           float* out, float* scratch, int64_t n, void* stream) {
-  return vc_dopri5_error_ratio_launch(mode, y0, y1, k, dt_ptr, rtol, atol, out, scratch, n, S(stream), ERRBUF);
+  return vc_rk_error_ratio_launch(VC_RK_DOPRI5, mode, y0, y1, k, dt_ptr, rtol, atol, out, scratch, n, S(stream), ERRBUF, "dopri5_error_ratio");
 }
 int vc_dopri5_interp(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int32_t out_is_bf16,
                      int64_t n, void* stream) {
-  return vc_dopri5_interp_launch(y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF);
+  return vc_rk_dense_launch(VC_RK_DOPRI5, y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, S(stream), ERRBUF, "dopri5_interp");
 }
 int vc_rk_evals(int32_t method, int32_t* start, int32_t* per_attempt, int32_t* order) {
   const int S = vc_rk_stages_of(method);

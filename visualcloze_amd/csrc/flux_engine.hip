@@ -19,8 +19,9 @@
 //                           in place (cfg_combine_kernel, elementwise.hip); no buffer of its own
 //   SC_P / SC_R / SC_RS [B*N, D]  only with the step cache on (vc_flux_set_step_cache), behind everything else: P and R of the last
 //                           computed evaluation, and a scratch that holds r = h1 - h0 until the decision and h1 after it
-//   AD_K [7][B*N*out] / AD_Y0 / AD_Y1 (f32)  only with option adaptive 1, behind the step cache's: k1..k7, the state and the step's
-//                           end state of the adaptive solve (vc_flux_sample_dopri5, dopri5.hip), its dt, norms and reduction scratch
+//   AD_K [7][B*N*out] / AD_Y0 / AD_Y1 (f32)  only with option adaptive 1, behind the step cache's: k1..kS (S <= 7: the pair's stages),
+//                           the state and the step's end state of the adaptive solve (vc_flux_sample_dopri5 / vc_flux_sample_rk,
+//                           rk_embedded.hip), its dt, norms and reduction scratch
 //   SD_Y / SD_XHAT / SD_K1 (f32) / SD_TAB / SD_RNG  only with option sde 1, behind the adaptive solve's: the state, x-hat and K1 of the
 //                           stochastic sampler (vc_flux_sample_sde, rng.hip), its coefficient table ([S + 1][VC_SDE_ROW] f32) and the
 //                           seed / offset words its update reads
@@ -511,10 +512,7 @@ int monitor_fits(Flux& f, const char* what, char* err, int errlen) {
 // where it IS the state (the kernel's pointers are __restrict__)
 int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, char* err, int errlen) {
   Err e{err, errlen};
-  if (f.traj.method == SOLVER_DOPRI5)      // the stage of the adaptive solve is the device-side counter itself
-    return vc_dopri5_stage_launch(-1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
-                                  e.buf, e.len);
-  if (f.traj.method == SOLVER_RK)          // likewise, with the pair's tableau
+  if (f.traj.method == SOLVER_RK)          // the stage of the adaptive solve is the device-side counter itself, the tableau the pair's
     return vc_rk_stage_launch(f.traj.rk, -1, f.AD_Y0, f.AD_K, v, f.AD_DT, step_ptr, f.AD_Y1, f.YIN, (int64_t)f.B * f.N * f.cfg.out_channels, s,
                               e.buf, e.len);
   if (f.traj.method == SOLVER_SDE_EULER || f.traj.method == SOLVER_SDE_HEUN)      // the table row of the update is the device-side counter itself

@@ -99,50 +99,30 @@ inline void model_times(int method, int E, const float* t_grid, int S, int B, bo
   }
 }
 
-// ---- the adaptive solve (transport.dopri5_initial_step / dopri5_controller are the same rules in Python)
-// the times of the seven modulation rows of a step t -> t + dt (row = the stage of the evaluation): k1's own (its evaluation is the
-// last step's seventh), then c2..c6 and t + dt again for k7; the model sees 1 - f32(t)
-inline void dopri5_row_times(double t, double dt, float out[7]) {
-  static const double C[7] = {0.0, 1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0, 1.0};
-  for (int j = 0; j < 7; ++j) out[j] = 1.0f - (float)(t + C[j] * dt);
-}
-// Hairer's starting step size, split at its two host reads: h0 from d0 = rms(y0 / scale) and d1 = rms(f0 / scale); the first dt
-// from h0, d1 and d2 = rms((f(t0 + h0) - f0) / scale) / h0
-inline double dopri5_h0(double d0, double d1) { return (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1; }
-inline double dopri5_first_dt(double h0, double d1, double d2) {
-  const double dmax = d1 > d2 ? d1 : d2;
-  const double h1 = dmax <= 1e-15 ? std::max(1e-6, h0 * 1e-3) : pow(0.01 / dmax, 1.0 / 5.0);
-  return std::min(100.0 * h0, h1);
-}
-// the controller behind an attempt of error ratio `ratio`: accepted iff ratio <= 1, and the factor the next dt takes; false (the
-// attempt stands as not accepted) for a NaN ratio, which ends the solve
-inline bool dopri5_controller(double ratio, bool* accept, double* factor) {
-  *accept = ratio <= 1.0;
-  *factor = 10.0;
-  if (ratio != ratio) return false;
-  if (ratio != 0.0) *factor = std::min(10.0, std::max(0.9 / pow(ratio, 1.0 / 5.0), ratio < 1.0 ? 1.0 : 0.2));
-  return true;
-}
-
-// ---- the embedded pairs of vc_flux_sample_rk (transport.rk_initial_step / rk_controller are the same rules in Python): the rules
-// above with the method's tableau and order as parameters.  The controller is torchdiffeq's as recalled, unpinned against real
-// torchdiffeq; at order 5 every rule returns the bits of its dopri5_* twin
+// ---- the adaptive solve of an embedded pair (vc_flux_sample_dopri5, vc_flux_sample_rk; transport.rk_initial_step / rk_controller are
+// the same rules in Python, dopri5_initial_step / dopri5_controller those at order 5): the pair's tableau and order are parameters.
+// The controller is torchdiffeq's as recalled, unpinned against real torchdiffeq
 // evaluations k1..kS of a step (kS = f(t1, y1) is the next step's k1), model evaluations per attempt (2 more start a solve: k1 and
 // the probe of the first step size) and the order the step-size rules take; 0 for an unknown method
 inline int rk_stages(int method) { return method == VC_RK_DOPRI5 ? 7 : method == VC_RK_BOSH3 ? 4 : method == VC_RK_ADAPTIVE_HEUN ? 3 : 0; }
 inline int rk_evals_per_attempt(int method) { return rk_stages(method) ? rk_stages(method) - 1 : 0; }
 inline int rk_order(int method) { return method == VC_RK_DOPRI5 ? 5 : method == VC_RK_BOSH3 ? 3 : method == VC_RK_ADAPTIVE_HEUN ? 2 : 0; }
-// the times of the rk_stages(method) modulation rows of a step t -> t + dt (row = the stage of the evaluation); the model sees 1 - f32(t)
+// the times of the rk_stages(method) modulation rows of a step t -> t + dt (row = the stage of the evaluation): k1's own (its
+// evaluation is the last step's last), then c2.. and t + dt again for kS; the model sees 1 - f32(t)
 inline void rk_row_times(int method, double t, double dt, float* out) {
   static const double C[3][7] = {{0.0, 1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0, 1.0}, {0.0, 1.0 / 2.0, 3.0 / 4.0, 1.0}, {0.0, 1.0, 1.0}};
   for (int j = 0; j < rk_stages(method); ++j) out[j] = 1.0f - (float)(t + C[method][j] * dt);
 }
+// Hairer's starting step size, split at its two host reads: h0 from d0 = rms(y0 / scale) and d1 = rms(f0 / scale); the first dt
+// from h0, d1 and d2 = rms((f(t0 + h0) - f0) / scale) / h0
 inline double rk_h0(double d0, double d1) { return (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1; }
 inline double rk_first_dt(int order, double h0, double d1, double d2) {
   const double dmax = d1 > d2 ? d1 : d2;
   const double h1 = dmax <= 1e-15 ? std::max(1e-6, h0 * 1e-3) : pow(0.01 / dmax, 1.0 / order);
   return std::min(100.0 * h0, h1);
 }
+// the controller behind an attempt of error ratio `ratio`: accepted iff ratio <= 1, and the factor the next dt takes; false (the
+// attempt stands as not accepted) for a NaN ratio, which ends the solve
 inline bool rk_controller(int order, double ratio, bool* accept, double* factor) {
   *accept = ratio <= 1.0;
   *factor = 10.0;

@@ -1,8 +1,8 @@
 // What a solver does with a Flux handle (flux_state.h): ONE trajectory core - the refusals every sampler shares, begin_trajectory and
-// replay - and on top of it the fixed-grid loop (vc_flux_sample_begin / _steps / _end), the adaptive Dormand-Prince solve
-// (vc_flux_sample_dopri5), its tableau-driven twin for the low-order embedded pairs (vc_flux_sample_rk), the stochastic sampler
-// (vc_flux_sample_sde) and the Adams-Bashforth multistep solve (vc_flux_sample_multistep).  An entry point keeps what is its own: its tables, its own
-// refusals and its loop.  Host code only; the arithmetic of the tables is flux_rules.h.
+// replay - and on top of it the fixed-grid loop (vc_flux_sample_begin / _steps / _end), the adaptive solve of an embedded pair (ONE
+// loop behind vc_flux_sample_dopri5 and vc_flux_sample_rk, the pair a parameter), the stochastic sampler (vc_flux_sample_sde) and the
+// Adams-Bashforth multistep solve (vc_flux_sample_multistep).  An entry point keeps what is its own: its tables, its own refusals and
+// its loop.  Host code only; the arithmetic of the tables is flux_rules.h.
 #include "flux_state.h"
 
 namespace vcflux {
@@ -51,14 +51,14 @@ void end_trajectory(Flux& f) {
 // else the warm-up evaluation of a new capture reads - the modulation rows, its tables - on `s` before
 int begin_trajectory(Flux& f, int method, const void* x, int x_is_bf16, const void* cond, hipStream_t s, Err e, int rk = 0) {
   const int64_t rows = (int64_t)f.B * f.N, n = rows * f.cfg.out_channels;
-  const bool fixed = method < SOLVER_DOPRI5;
+  const bool fixed = vc_evals_of(method) != 0;
   f.traj.method = method; f.traj.evals = fixed ? vc_evals_of(method) : 1;
   f.traj.rk = method == SOLVER_RK ? rk : 0;
   f.traj.state_f32 = !fixed || !x_is_bf16;
   f.traj.cached = f.sc_on();
   f.cfg_active = f.cfg_on; f.cfg_s = f.cfg_on ? f.cfg_scale : 1.0f;
   if (!fixed) {                                 // the f32 state of the solver and its bf16 shadow
-    TRY(vc_dopri5_load_launch(x, x_is_bf16, method == SOLVER_DOPRI5 || method == SOLVER_RK ? f.AD_Y0 : method == SOLVER_MULTISTEP ? f.MS_Y : f.SD_Y, f.YIN, n, s, e.buf, e.len));
+    TRY(vc_dopri5_load_launch(x, x_is_bf16, method == SOLVER_RK ? f.AD_Y0 : method == SOLVER_MULTISTEP ? f.MS_Y : f.SD_Y, f.YIN, n, s, e.buf, e.len));
   } else {
     TRY(d2d(ode_state(f), x, ode_state_bytes(f), s, e.buf, e.len));
     // the first evaluation reads bf16(y0)
@@ -164,79 +164,83 @@ int vc_flux_sample_end_impl(void* handle, void* x_out, hipStream_t s, char* err,
   return d2d(x_out, ode_state(f), ode_state_bytes(f), s, e.buf, e.len);
 }
 
-// ---------------------------------------------------------------- the adaptive solve (vcloze_hip.h: vc_flux_sample_dopri5)
-// the seven modulation rows of a step t -> t + dt (row = the device-side counter = the stage of the evaluation:
-// vcrules::dopri5_row_times), and dt itself
-static int dopri5_rows(Flux& f, double t, double dt, hipStream_t s, Err e) {
-  const int B = f.B;
-  TRY(stage_begin(f, (size_t)7 * B * sizeof(float) + 1024, e.buf, e.len));
-  float* ts = stage_take<float>(f, (size_t)7 * B);
+// ---------------------------------------------------------------- the adaptive solve (vcloze_hip.h: vc_flux_sample_dopri5, vc_flux_sample_rk)
+// ONE loop for every embedded pair: the rows, the stage node, the norm and the dense output take the pair (VC_RK_*), the step-size
+// rules its order.  `what` is the entry point's message prefix.  The buffers are the first S of AD_K's seven planes, AD_Y0 / AD_Y1.
+// the S modulation rows of a step t -> t + dt (row = the device-side counter = the stage of the evaluation: vcrules::rk_row_times),
+// and dt itself
+static int rk_rows(Flux& f, int method, double t, double dt, hipStream_t s, Err e) {
+  const int B = f.B, S = vcrules::rk_stages(method);
+  TRY(stage_begin(f, (size_t)S * B * sizeof(float) + 1024, e.buf, e.len));
+  float* ts = stage_take<float>(f, (size_t)S * B);
   float* hdt = stage_take<float>(f, 1);
   float tm[7];
-  vcrules::dopri5_row_times(t, dt, tm);
-  for (int j = 0; j < 7; ++j)
+  vcrules::rk_row_times(method, t, dt, tm);
+  for (int j = 0; j < S; ++j)
     for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = tm[j];
   *hdt = (float)dt;
-  TRY(stage_send(f, f.TS, ts, (size_t)7 * B * sizeof(float), s, e.buf, e.len));
+  TRY(stage_send(f, f.TS, ts, (size_t)S * B * sizeof(float), s, e.buf, e.len));
   TRY(stage_send(f, f.AD_DT, hdt, sizeof(float), s, e.buf, e.len));
   TRY(stage_end(f, s, e.buf, e.len));
-  return time_precompute(f, 7, 0, s, e.buf, e.len);
+  return time_precompute(f, S, 0, s, e.buf, e.len);
 }
 // `count` replays of the captured evaluation (+ its stage node) with the counter starting at `first`
-static int dopri5_evals(Flux& f, int first, int count, hipStream_t s, Err e) {
+static int rk_evals(Flux& f, int first, int count, hipStream_t s, Err e) {
   HIP(hipMemsetD32Async((hipDeviceptr_t)f.STEP, first, 1, s), "hipMemsetD32Async");
   for (int j = 0; j < count; ++j) TRY(replay(f, s, e));
   f.ad_evals += count;
   return VC_OK;
 }
 // the first `count` words of AD_OUT -> the host: the ONE synchronisation of an attempt
-static int dopri5_read(Flux& f, int count, hipStream_t s, Err e) {
+static int rk_read(Flux& f, int count, hipStream_t s, Err e) {
   HIP(hipMemcpyAsync(f.ad_host, f.AD_OUT, count * sizeof(float), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(D2H)");
   HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
   return VC_OK;
 }
 
-static int dopri5_run(Flux& f, void* x, const float* t_grid, int n_points, int out_bf16, float rtol, float atol, int max_attempts,
-                      void* trajectory, hipStream_t s, Err e) {
+static int rk_run(Flux& f, const char* what, int method, void* x, const float* t_grid, int n_points, int out_bf16, float rtol, float atol,
+                  int max_attempts, void* trajectory, hipStream_t s, Err e) {
   const int64_t n = (int64_t)f.B * f.N * f.cfg.out_channels, out_bytes = n * (out_bf16 ? 2 : 4);
+  const int S = vcrules::rk_stages(method), order = vcrules::rk_order(method);
   const volatile float* host = f.ad_host;
   double t = t_grid[0];
   // k1 = f(t0, y0): the counter at 0 stores it (the caller set the rows of t0 with dt = 0: the state the stage node forms is y0)
-  TRY(dopri5_evals(f, 0, 1, s, e));
+  TRY(rk_evals(f, 0, 1, s, e));
   // the initial step size
-  TRY(vc_dopri5_error_ratio_launch(1, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-  TRY(vc_dopri5_error_ratio_launch(2, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT + 1, f.AD_PART, n, s, e.buf, e.len));
-  TRY(dopri5_read(f, 2, s, e));
+  TRY(vc_rk_error_ratio_launch(method, 1, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+  TRY(vc_rk_error_ratio_launch(method, 2, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT + 1, f.AD_PART, n, s, e.buf, e.len));
+  TRY(rk_read(f, 2, s, e));
   const double d0 = host[0], d1 = host[1];
-  if (d0 != d0 || d1 != d1) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the state or the model's output at t_grid[0] is not finite");
-  const double h0 = vcrules::dopri5_h0(d0, d1);
-  TRY(dopri5_rows(f, t, h0, s, e));                       // (row 1 stands at t0 + c2 h0; the probe wants t0 + h0: row 5)
-  TRY(vc_dopri5_stage_launch(7, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, nullptr, f.YIN, n, s, e.buf, e.len));
-  TRY(dopri5_evals(f, 5, 1, s, e));                       // its k lands in k6 (and the state it forms is not used)
+  if (d0 != d0 || d1 != d1) FAIL(VC_ERR_STATE, "%s: the state or the model's output at t_grid[0] is not finite", what);
+  const double h0 = vcrules::rk_h0(d0, d1);
+  TRY(rk_rows(f, method, t, h0, s, e));
+  TRY(vc_rk_stage_launch(method, 7, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, nullptr, f.YIN, n, s, e.buf, e.len));
+  // the probe runs as the LAST stage: its row stands at t0 + h0 (c_S = 1) and its node stores k alone, into k_S
+  TRY(rk_evals(f, S - 1, 1, s, e));
   // d2 reads the probe from k2: the slots are free until the first attempt
-  TRY(d2d(f.AD_K + n, f.AD_K + 5 * n, n * 2, s, e.buf, e.len));
-  TRY(vc_dopri5_error_ratio_launch(3, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-  TRY(dopri5_read(f, 1, s, e));
+  if (S - 1 != 1) TRY(d2d(f.AD_K + n, f.AD_K + (int64_t)(S - 1) * n, n * 2, s, e.buf, e.len));
+  TRY(vc_rk_error_ratio_launch(method, 3, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+  TRY(rk_read(f, 1, s, e));
   const double d2 = (double)host[0] / h0;
-  if (d2 != d2) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the model's output at t_grid[0] + h0 is not finite");
-  double dt = vcrules::dopri5_first_dt(h0, d1, d2);
+  if (d2 != d2) FAIL(VC_ERR_STATE, "%s: the model's output at t_grid[0] + h0 is not finite", what);
+  double dt = vcrules::rk_first_dt(order, h0, d1, d2);
   int next_out = 1;
   while (next_out < n_points) {
     if ((int)f.ad_log.size() >= max_attempts)
-      FAIL(VC_ERR_STATE, "flux_sample_dopri5: more than max_attempts = %d attempts (t = %.9g of [%.9g, %.9g], dt = %.3g)", max_attempts, t,
+      FAIL(VC_ERR_STATE, "%s: more than max_attempts = %d attempts (t = %.9g of [%.9g, %.9g], dt = %.3g)", what, max_attempts, t,
            (double)t_grid[0], (double)t_grid[n_points - 1], dt);
-    if (t + dt == t) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the step size underflowed (t = %.17g, dt = %.3g)", t, dt);
-    TRY(dopri5_rows(f, t, dt, s, e));
-    TRY(vc_dopri5_stage_launch(0, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, f.AD_Y1, f.YIN, n, s, e.buf, e.len));   // k1 is in place
-    TRY(dopri5_evals(f, 1, 6, s, e));
-    TRY(vc_dopri5_error_ratio_launch(0, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-    TRY(dopri5_read(f, 1, s, e));
+    if (t + dt == t) FAIL(VC_ERR_STATE, "%s: the step size underflowed (t = %.17g, dt = %.3g)", what, t, dt);
+    TRY(rk_rows(f, method, t, dt, s, e));
+    TRY(vc_rk_stage_launch(method, 0, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, f.AD_Y1, f.YIN, n, s, e.buf, e.len));   // k1 is in place
+    TRY(rk_evals(f, 1, S - 1, s, e));
+    TRY(vc_rk_error_ratio_launch(method, 0, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
+    TRY(rk_read(f, 1, s, e));
     const float ratio32 = host[0];
     bool accept;
     double factor;
-    const bool ok = vcrules::dopri5_controller(ratio32, &accept, &factor);
+    const bool ok = vcrules::rk_controller(order, ratio32, &accept, &factor);
     f.ad_log.push_back(Flux::Attempt{t, dt, ratio32, accept});
-    if (!ok) FAIL(VC_ERR_STATE, "flux_sample_dopri5: the error ratio of the step at t = %.9g, dt = %.3g is NaN", t, dt);
+    if (!ok) FAIL(VC_ERR_STATE, "%s: the error ratio of the step at t = %.9g, dt = %.3g is NaN", what, t, dt);
     if (accept) {
       const double t1 = t + dt;
       for (; next_out < n_points && (double)t_grid[next_out] <= t1; ++next_out) {
@@ -245,11 +249,11 @@ static int dopri5_run(Flux& f, void* x, const float* t_grid, int n_points, int o
         double theta = ((double)t_grid[next_out] - t) / dt;
         theta = theta < 0.0 ? 0.0 : theta > 1.0 ? 1.0 : theta;
         void* dst = trajectory ? (void*)((char*)trajectory + (int64_t)(next_out - 1) * out_bytes) : x;
-        TRY(vc_dopri5_interp_launch(f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, (float)theta, dst, out_bf16, n, s, e.buf, e.len));
+        TRY(vc_rk_dense_launch(method, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, (float)theta, dst, out_bf16, n, s, e.buf, e.len));
         if (trajectory && last) TRY(d2d(x, dst, out_bytes, s, e.buf, e.len));
       }
       TRY(d2d(f.AD_Y0, f.AD_Y1, n * 4, s, e.buf, e.len));
-      TRY(d2d(f.AD_K, f.AD_K + 6 * n, n * 2, s, e.buf, e.len));        // first same as last
+      TRY(d2d(f.AD_K, f.AD_K + (int64_t)(S - 1) * n, n * 2, s, e.buf, e.len));        // first same as last
       t = t1;
     }
     dt *= factor;
@@ -257,33 +261,53 @@ static int dopri5_run(Flux& f, void* x, const float* t_grid, int n_points, int o
   return VC_OK;
 }
 
-int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
-                               float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen) {
-  HANDLE(Flux, f, "flux");
-  TRY(refuse_unready(f, "flux_sample_dopri5", x, cond, t_grid, e));
+// the refusals of both entry points behind their own first lines, in their order, then the solve
+static int rk_solve(Flux& f, const char* what, int method, void* x, const void* cond, const float* t_grid, int n_points, int state_is_bf16,
+                    float rtol, float atol, int max_attempts, void* trajectory, hipStream_t s, Err e) {
+  const int S = vcrules::rk_stages(method);
+  TRY(refuse_unready(f, what, x, cond, t_grid, e));
   if (f.mon_level)
-    FAIL(VC_ERR_ARG, "flux_sample_dopri5: the monitor is on (level %d): the adaptive solve's device-side counter is the stage of an attempt, not "
-                     "an evaluation index; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
+    FAIL(VC_ERR_ARG, "%s: the monitor is on (level %d): the adaptive solve's device-side counter is the stage of an attempt, not "
+                     "an evaluation index; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", what, f.mon_level);
   if (!f.opt.adaptive || !f.AD_K)
-    FAIL(VC_ERR_STATE, "flux_sample_dopri5: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
-                       "(the workspace holds no buffers of the adaptive solve)");
-  if (f.S < 7) FAIL(VC_ERR_ARG, "flux_sample_dopri5: the workspace was prepared with max_steps = %d, the adaptive solve needs 7", f.S);
-  if (n_points < 2) FAIL(VC_ERR_ARG, "flux_sample_dopri5: n_points = %d, at least 2 expected", n_points);
+    FAIL(VC_ERR_STATE, "%s: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
+                       "(the workspace holds no buffers of the adaptive solve)", what);
+  if (f.S < S) {                                // (each entry point's own wording)
+    if (method == VC_RK_DOPRI5) FAIL(VC_ERR_ARG, "%s: the workspace was prepared with max_steps = %d, the adaptive solve needs 7", what, f.S);
+    FAIL(VC_ERR_ARG, "%s: the workspace was prepared with max_steps = %d, method %d needs %d", what, f.S, method, S);
+  }
+  if (n_points < 2) FAIL(VC_ERR_ARG, "%s: n_points = %d, at least 2 expected", what, n_points);
   for (int i = 1; i < n_points; ++i)
-    if (!(t_grid[i] > t_grid[i - 1])) FAIL(VC_ERR_ARG, "flux_sample_dopri5: t_grid must increase strictly (index %d)", i);
+    if (!(t_grid[i] > t_grid[i - 1])) FAIL(VC_ERR_ARG, "%s: t_grid must increase strictly (index %d)", what, i);
   if (!(rtol >= 0.0f) || !(atol >= 0.0f) || !(rtol + atol > 0.0f) || !(rtol + atol - (rtol + atol) == 0.0f))
-    FAIL(VC_ERR_ARG, "flux_sample_dopri5: rtol = %g and atol = %g must be finite, non-negative and not both zero", rtol, atol);
-  if (max_attempts < 1) FAIL(VC_ERR_ARG, "flux_sample_dopri5: max_attempts = %d must be positive", max_attempts);
-  TRY(refuse_cache(f, "flux_sample_dopri5", NO_SOLVER_CODE, e));
-  TRY(refuse_cfg(f, "flux_sample_dopri5", e));
+    FAIL(VC_ERR_ARG, "%s: rtol = %g and atol = %g must be finite, non-negative and not both zero", what, rtol, atol);
+  if (max_attempts < 1) FAIL(VC_ERR_ARG, "%s: max_attempts = %d must be positive", what, max_attempts);
+  TRY(refuse_cache(f, what, NO_SOLVER_CODE, e));
+  TRY(refuse_cfg(f, what, e));
   if (!f.ad_host) HIP(hipHostMalloc((void**)&f.ad_host, 256, hipHostMallocDefault), "hipHostMalloc");
   end_trajectory(f);
   f.ad_log.clear();
   f.ad_evals = 0;
   // the warm-up evaluation of a new capture indexes the modulation rows by the counter and reads dt: both defined first
-  TRY(dopri5_rows(f, (double)t_grid[0], 0.0, s, e));
-  TRY(begin_trajectory(f, SOLVER_DOPRI5, x, state_is_bf16, cond, s, e));
-  return dopri5_run(f, x, t_grid, n_points, state_is_bf16 != 0, rtol, atol, max_attempts, trajectory, s, e);
+  TRY(rk_rows(f, method, (double)t_grid[0], 0.0, s, e));
+  TRY(begin_trajectory(f, SOLVER_RK, x, state_is_bf16, cond, s, e, method));
+  return rk_run(f, what, method, x, t_grid, n_points, state_is_bf16 != 0, rtol, atol, max_attempts, trajectory, s, e);
+}
+
+int vc_flux_sample_dopri5_impl(void* handle, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                               float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  return rk_solve(f, "flux_sample_dopri5", VC_RK_DOPRI5, x, cond, t_grid, n_points, state_is_bf16, rtol, atol, max_attempts, trajectory, s, e);
+}
+
+// the public route to Dormand-Prince 5(4) is vc_flux_sample_dopri5 alone
+int vc_flux_sample_rk_impl(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
+                           float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen) {
+  HANDLE(Flux, f, "flux");
+  if (method == VC_RK_DOPRI5)
+    FAIL(VC_ERR_ARG, "flux_sample_rk: VC_RK_DOPRI5 is not solved here: there is one route to Dormand-Prince 5(4), vc_flux_sample_dopri5");
+  if (!vcrules::rk_stages(method)) FAIL(VC_ERR_ARG, "flux_sample_rk: unknown method %d (VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", method);
+  return rk_solve(f, "flux_sample_rk", method, x, cond, t_grid, n_points, state_is_bf16, rtol, atol, max_attempts, trajectory, s, e);
 }
 
 int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, int32_t* accepted, int32_t capacity, int32_t* attempts,
@@ -300,121 +324,6 @@ int vc_flux_dopri5_log_impl(void* handle, double* t, double* dt, float* ratio, i
   if (attempts) *attempts = (int32_t)f.ad_log.size();
   if (evaluations) *evaluations = f.ad_evals;
   return VC_OK;
-}
-
-// ---------------------------------------------------------------- the embedded pairs (vcloze_hip.h: vc_flux_sample_rk)
-// dopri5_run's loop with the pair as a parameter: the rows, the stage node and the norm take the method, the step-size rules its
-// order, and the dense output is the Hermite cubic.  The buffers are the adaptive solve's (the first S of AD_K's seven planes)
-static int rk_rows(Flux& f, int method, double t, double dt, hipStream_t s, Err e) {
-  const int B = f.B, S = vcrules::rk_stages(method);
-  TRY(stage_begin(f, (size_t)S * B * sizeof(float) + 1024, e.buf, e.len));
-  float* ts = stage_take<float>(f, (size_t)S * B);
-  float* hdt = stage_take<float>(f, 1);
-  float tm[7];
-  vcrules::rk_row_times(method, t, dt, tm);
-  for (int j = 0; j < S; ++j)
-    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = tm[j];
-  *hdt = (float)dt;
-  TRY(stage_send(f, f.TS, ts, (size_t)S * B * sizeof(float), s, e.buf, e.len));
-  TRY(stage_send(f, f.AD_DT, hdt, sizeof(float), s, e.buf, e.len));
-  TRY(stage_end(f, s, e.buf, e.len));
-  return time_precompute(f, S, 0, s, e.buf, e.len);
-}
-
-static int rk_run(Flux& f, int method, void* x, const float* t_grid, int n_points, int out_bf16, float rtol, float atol, int max_attempts,
-                  void* trajectory, hipStream_t s, Err e) {
-  const int64_t n = (int64_t)f.B * f.N * f.cfg.out_channels, out_bytes = n * (out_bf16 ? 2 : 4);
-  const int S = vcrules::rk_stages(method), order = vcrules::rk_order(method);
-  const volatile float* host = f.ad_host;
-  double t = t_grid[0];
-  // k1 = f(t0, y0): the counter at 0 stores it (the caller set the rows of t0 with dt = 0: the state the stage node forms is y0)
-  TRY(dopri5_evals(f, 0, 1, s, e));
-  // the initial step size
-  TRY(vc_rk_error_ratio_launch(method, 1, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-  TRY(vc_rk_error_ratio_launch(method, 2, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT + 1, f.AD_PART, n, s, e.buf, e.len));
-  TRY(dopri5_read(f, 2, s, e));
-  const double d0 = host[0], d1 = host[1];
-  if (d0 != d0 || d1 != d1) FAIL(VC_ERR_STATE, "flux_sample_rk: the state or the model's output at t_grid[0] is not finite");
-  const double h0 = vcrules::rk_h0(d0, d1);
-  TRY(rk_rows(f, method, t, h0, s, e));
-  TRY(vc_rk_stage_launch(method, 7, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, nullptr, f.YIN, n, s, e.buf, e.len));
-  // the probe runs as the LAST stage: its row stands at t0 + h0 (c_S = 1) and its node stores k alone, into k_S
-  TRY(dopri5_evals(f, S - 1, 1, s, e));
-  // d2 reads the probe from k2: the slots are free until the first attempt
-  if (S - 1 != 1) TRY(d2d(f.AD_K + n, f.AD_K + (int64_t)(S - 1) * n, n * 2, s, e.buf, e.len));
-  TRY(vc_rk_error_ratio_launch(method, 3, f.AD_Y0, nullptr, f.AD_K, nullptr, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-  TRY(dopri5_read(f, 1, s, e));
-  const double d2 = (double)host[0] / h0;
-  if (d2 != d2) FAIL(VC_ERR_STATE, "flux_sample_rk: the model's output at t_grid[0] + h0 is not finite");
-  double dt = vcrules::rk_first_dt(order, h0, d1, d2);
-  int next_out = 1;
-  while (next_out < n_points) {
-    if ((int)f.ad_log.size() >= max_attempts)
-      FAIL(VC_ERR_STATE, "flux_sample_rk: more than max_attempts = %d attempts (t = %.9g of [%.9g, %.9g], dt = %.3g)", max_attempts, t,
-           (double)t_grid[0], (double)t_grid[n_points - 1], dt);
-    if (t + dt == t) FAIL(VC_ERR_STATE, "flux_sample_rk: the step size underflowed (t = %.17g, dt = %.3g)", t, dt);
-    TRY(rk_rows(f, method, t, dt, s, e));
-    TRY(vc_rk_stage_launch(method, 0, f.AD_Y0, f.AD_K, nullptr, f.AD_DT, nullptr, f.AD_Y1, f.YIN, n, s, e.buf, e.len));   // k1 is in place
-    TRY(dopri5_evals(f, 1, S - 1, s, e));
-    TRY(vc_rk_error_ratio_launch(method, 0, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, rtol, atol, f.AD_OUT, f.AD_PART, n, s, e.buf, e.len));
-    TRY(dopri5_read(f, 1, s, e));
-    const float ratio32 = host[0];
-    bool accept;
-    double factor;
-    const bool ok = vcrules::rk_controller(order, ratio32, &accept, &factor);
-    f.ad_log.push_back(Flux::Attempt{t, dt, ratio32, accept});
-    if (!ok) FAIL(VC_ERR_STATE, "flux_sample_rk: the error ratio of the step at t = %.9g, dt = %.3g is NaN", t, dt);
-    if (accept) {
-      const double t1 = t + dt;
-      for (; next_out < n_points && (double)t_grid[next_out] <= t1; ++next_out) {
-        const bool last = next_out == n_points - 1;
-        if (!trajectory && !last) continue;
-        double theta = ((double)t_grid[next_out] - t) / dt;
-        theta = theta < 0.0 ? 0.0 : theta > 1.0 ? 1.0 : theta;
-        void* dst = trajectory ? (void*)((char*)trajectory + (int64_t)(next_out - 1) * out_bytes) : x;
-        TRY(vc_rk_interp_launch(method, f.AD_Y0, f.AD_Y1, f.AD_K, f.AD_DT, (float)theta, dst, out_bf16, n, s, e.buf, e.len));
-        if (trajectory && last) TRY(d2d(x, dst, out_bytes, s, e.buf, e.len));
-      }
-      TRY(d2d(f.AD_Y0, f.AD_Y1, n * 4, s, e.buf, e.len));
-      TRY(d2d(f.AD_K, f.AD_K + (int64_t)(S - 1) * n, n * 2, s, e.buf, e.len));        // first same as last
-      t = t1;
-    }
-    dt *= factor;
-  }
-  return VC_OK;
-}
-
-int vc_flux_sample_rk_impl(void* handle, int32_t method, void* x, const void* cond, const float* t_grid, int32_t n_points, int32_t state_is_bf16,
-                           float rtol, float atol, int32_t max_attempts, void* trajectory, hipStream_t s, char* err, int errlen) {
-  HANDLE(Flux, f, "flux");
-  if (method == VC_RK_DOPRI5)
-    FAIL(VC_ERR_ARG, "flux_sample_rk: VC_RK_DOPRI5 is not solved here: there is one route to Dormand-Prince 5(4), vc_flux_sample_dopri5");
-  const int S = vcrules::rk_stages(method);
-  if (!S) FAIL(VC_ERR_ARG, "flux_sample_rk: unknown method %d (VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", method);
-  TRY(refuse_unready(f, "flux_sample_rk", x, cond, t_grid, e));
-  if (f.mon_level)
-    FAIL(VC_ERR_ARG, "flux_sample_rk: the monitor is on (level %d): the adaptive solve's device-side counter is the stage of an attempt, not "
-                     "an evaluation index; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
-  if (!f.opt.adaptive || !f.AD_K)
-    FAIL(VC_ERR_STATE, "flux_sample_rk: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
-                       "(the workspace holds no buffers of the adaptive solve)");
-  if (f.S < S) FAIL(VC_ERR_ARG, "flux_sample_rk: the workspace was prepared with max_steps = %d, method %d needs %d", f.S, method, S);
-  if (n_points < 2) FAIL(VC_ERR_ARG, "flux_sample_rk: n_points = %d, at least 2 expected", n_points);
-  for (int i = 1; i < n_points; ++i)
-    if (!(t_grid[i] > t_grid[i - 1])) FAIL(VC_ERR_ARG, "flux_sample_rk: t_grid must increase strictly (index %d)", i);
-  if (!(rtol >= 0.0f) || !(atol >= 0.0f) || !(rtol + atol > 0.0f) || !(rtol + atol - (rtol + atol) == 0.0f))
-    FAIL(VC_ERR_ARG, "flux_sample_rk: rtol = %g and atol = %g must be finite, non-negative and not both zero", rtol, atol);
-  if (max_attempts < 1) FAIL(VC_ERR_ARG, "flux_sample_rk: max_attempts = %d must be positive", max_attempts);
-  TRY(refuse_cache(f, "flux_sample_rk", NO_SOLVER_CODE, e));
-  TRY(refuse_cfg(f, "flux_sample_rk", e));
-  if (!f.ad_host) HIP(hipHostMalloc((void**)&f.ad_host, 256, hipHostMallocDefault), "hipHostMalloc");
-  end_trajectory(f);
-  f.ad_log.clear();
-  f.ad_evals = 0;
-  // the warm-up evaluation of a new capture indexes the modulation rows by the counter and reads dt: both defined first
-  TRY(rk_rows(f, method, (double)t_grid[0], 0.0, s, e));
-  TRY(begin_trajectory(f, SOLVER_RK, x, state_is_bf16, cond, s, e, method));
-  return rk_run(f, method, x, t_grid, n_points, state_is_bf16 != 0, rtol, atol, max_attempts, trajectory, s, e);
 }
 
 // ---------------------------------------------------------------- the stochastic sampler (vcloze_hip.h: vc_flux_sample_sde)

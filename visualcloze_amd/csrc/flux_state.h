@@ -88,9 +88,9 @@ inline bool operator==(const Options& a, const Options& b) {
 
 // what a trajectory runs with, latched ONCE where it begins (flux_sample.hip: begin_trajectory): the step's plan, its capture key and
 // the solver's update read it and nothing else
-constexpr int SOLVER_DOPRI5 = 100;     // the adaptive solve: no VC_SOLVER_* code (vc_solver_evals keeps refusing it)
-constexpr int SOLVER_SDE_EULER = 101, SOLVER_SDE_HEUN = 102;     // the stochastic sampler: likewise (one captured step per method)
-constexpr int SOLVER_RK = 103;         // the embedded pairs of vc_flux_sample_rk: ONE code, the pair is Trajectory::rk (VC_RK_*)
+// codes of the solvers that have no VC_SOLVER_* code (vc_solver_evals keeps refusing them)
+constexpr int SOLVER_SDE_EULER = 101, SOLVER_SDE_HEUN = 102;     // the stochastic sampler (one captured step per method)
+constexpr int SOLVER_RK = 103;         // the adaptive solve (vc_flux_sample_dopri5, vc_flux_sample_rk): ONE code, the pair is Trajectory::rk (VC_RK_*)
 constexpr int SOLVER_MULTISTEP = 104;  // the Adams-Bashforth solve: ONE code and one captured step, the order lives in the table
 struct Trajectory {
   int method = VC_SOLVER_EULER;        // VC_SOLVER_*, or one of the codes above

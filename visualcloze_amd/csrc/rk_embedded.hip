@@ -1,13 +1,26 @@
-// Embedded Runge-Kutta pairs, tableau-driven: the twin of dopri5.hip with the method as an argument ("the
-// adaptive solve").  The contract is dopri5.hip's: f(t, y) = -model(bf16(y) || cond, 1 - f32(t)); every k is stored in bf16 (the
+// The adaptive solve's kernels: embedded Runge-Kutta pairs, tableau-driven, the ONE implementation behind vc_rk_* and vc_dopri5_*
+// ("the adaptive solve").  f(t, y) = -model(bf16(y) || cond, 1 - f32(t)); every k is stored in bf16 (the
 // model's output dtype), the state y is f32; every sum is taken left to right over the NON-ZERO coefficients, one f32 operation after
 // the other with floating-point contraction off; every coefficient is a double rounded ONCE to f32.  A torch f32 expression of the
-// same shape (transport.rk_step / rk_error_ratio / rk_hermite) gives the same bits.
+// same shape (transport.rk_step / rk_error_ratio / rk_hermite / dopri5_interp) gives the same bits.
 //   rk_stage        k[stage] = -v and the next stage's input state (or y1 behind the last-but-one evaluation)
 //   rk_error_ratio  the mixed-tolerance RMS norm of the embedded error estimate, and the three norms of the initial step size
-//   rk_interp       the dense output of bosh3 / adaptive_heun: the Hermite cubic through (y0, f0, y1, f1)
+//   rk_dense        the dense output of the pair: the quartic through (y0, f0, y_mid, y1, f1) for Dormand-Prince, the Hermite cubic
+//                   through (y0, f0, y1, f1) for bosh3 / adaptive_heun
+//   dopri5_load     the caller's state -> the f32 state and its bf16 shadow (every solver with an f32 state of its own starts here)
+// vc_dopri5_stage / _error_ratio / _interp are these launchers at VC_RK_DOPRI5 under their own names (api.hip).
 // The methods (a method of S stages evaluates k1..kS per step; kS = f(t1, y1) is the next step's k1: first same as last):
-//   VC_RK_DOPRI5 = 0         the rows of dopri5.hip, S = 7.  Stage and error kernels only: it holds the generic code to the pinned one
+//   VC_RK_DOPRI5 = 0         Dormand & Prince 1980 5(4) (SciPy's RK45.C / .A / .B / .E), S = 7, order 5
+//     c    0, 1/5, 3/10, 4/5, 8/9, 1, 1
+//     a2   1/5
+//     a3   3/40, 9/40
+//     a4   44/45, -56/15, 32/9
+//     a5   19372/6561, -25360/2187, 64448/6561, -212/729
+//     a6   9017/3168, -355/33, 46732/5247, 49/176, -5103/18656
+//     b    35/384, 0, 500/1113, 125/192, -2187/6784, 11/84                       (5th order: y1; also the row a7)
+//     e    -71/57600, 0, 71/16695, -71/1920, 17253/339200, -22/525, 1/40         (b - b^, the 4th-order companion)
+//     DPS_C_MID  6025192743/30085553152/2, 0, 51252292925/65400821598/2, -2691868925/45128329728/2,
+//                187940372067/1594534317056/2, -1776094331/19743644256/2, 11237099/235043384/2        (y at t0 + dt/2: torchdiffeq's)
 //   VC_RK_BOSH3 = 1          Bogacki-Shampine 3(2) (SciPy's RK23.C / .A / .B / .E), S = 4, order 3
 //     c 0, 1/2, 3/4, 1;  a2 1/2;  a3 0, 3/4;  a4 = b 2/9, 1/3, 4/9;  e 5/72, -1/12, -1/9, 1/8
 //   VC_RK_ADAPTIVE_HEUN = 2  Heun-Euler 2(1), S = 3, order 2
@@ -16,12 +29,15 @@
 //   c0 = 1 - x; c1 = x - 1; c2 = 1 - 2 x; w = x c1; h0 = c1 dt; h1 = x dt
 //   y(x) = (c0 y0 + x y1) + w ((c2 d + h0 f0) + h1 f1)                          theta = 0 / 1: the bits of y0 / y1
 // For bosh3 this is SciPy's RK23 dense output (its P rows are this cubic expanded).  The controller around these kernels
-// (flux_sample.hip, transport.rk_integrate) is torchdiffeq's as recalled, unpinned against real torchdiffeq.
+// (flux_sample.hip, transport.rk_integrate / dopri5_integrate) is torchdiffeq's AS RECALLED - the package was not available to check
+// against: "unpinned against real torchdiffeq" - and pinned to SciPy's RK45 / RK23 in the tableaus and in single steps
+// (tests/test_dopri5_cpu.py, tests/test_rk_embedded_cpu.py).
 // Memory: elementwise passes over n elements with 2..7 k planes.  The W = 8 kernels move 16 bytes per access - eight bf16 of a k
 // plane, four f32 of the state - wherever the address allows it (plane j starts at element j n: 16-byte aligned for every j only
 // where n % 8 == 0, which every [B, N, 64] state is); the last n % 8 elements, and every element where a base is not 16-byte
-// aligned (the launcher picks W = 1), run one by one through the SAME per-element expression.  The norm keeps dopri5.hip's deal of
-// single elements to threads: its summation order is what makes it bit-equal to vc_dopri5_error_ratio.
+// aligned (the launcher picks W = 1), run one by one through the SAME per-element expression.  The norm deals single elements to
+// threads: its summation order is part of its result (transport._rk_norm restates it).  The quartic and the load run one element
+// per thread.
 #include "common.h"
 #include "vcloze_internal.h"
 
@@ -31,7 +47,7 @@ namespace {
 
 constexpr int RK_THREADS = 256;                        // = VC_DOPRI5_MAX_BLOCKS: pass 2 reduces one partial per thread
 static_assert(RK_THREADS == VC_DOPRI5_MAX_BLOCKS, "pass 2 holds one block partial per thread");
-constexpr int RK_PROBE = 7;                            // the probe stage of every method (dopri5.hip's stage 7)
+constexpr int RK_PROBE = 7;                            // the probe stage of every method
 constexpr int RK_E = 6;                                // the row of e
 
 // [method]: rows 0..S-3 feed the evaluations behind stages 0..S-3 (a2..), row S-2 is b (forms y1), row 6 is e
@@ -59,6 +75,11 @@ __constant__ float RK_ROWS[3][7][7] = {
      {0, 0, 0, 0, 0, 0, 0},
      {(float)(1.0 / 2.0), (float)(-1.0 / 2.0), 0, 0, 0, 0, 0}},
 };
+// DPS_C_MID: the weights of y at t0 + dt / 2, which the quartic dense output of Dormand-Prince goes through
+__constant__ float DP_MID[7] = {
+    (float)(6025192743.0 / 30085553152.0 / 2.0), 0, (float)(51252292925.0 / 65400821598.0 / 2.0),
+    (float)(-2691868925.0 / 45128329728.0 / 2.0), (float)(187940372067.0 / 1594534317056.0 / 2.0),
+    (float)(-1776094331.0 / 19743644256.0 / 2.0), (float)(11237099.0 / 235043384.0 / 2.0)};
 
 // ---- W consecutive elements at p: one 16-byte access (two for f32) where W = 8 and the address allows it, else one by one
 template <int W> VC_DEV void ld_bf(const bf16_t* __restrict__ p, float (&out)[W]) {
@@ -112,7 +133,7 @@ template <int W> VC_DEV void st_f(float* __restrict__ p, const float (&v)[W]) {
   for (int e = 0; e < W; ++e) p[e] = v[e];
 }
 
-// sum over the non-zero coefficients of `row`, left to right: ((c_a k_a + c_b k_b) + c_c k_c) + ...  (dopri5.hip: dp_combine)
+// sum over the non-zero coefficients of `row`, left to right: ((c_a k_a + c_b k_b) + c_c k_c) + ...
 template <int W> VC_DEV void rk_combine(const float* __restrict__ row, const bf16_t* __restrict__ k, long n, long i, float (&acc)[W]) {
   bool first = true;
 #pragma unroll
@@ -171,7 +192,7 @@ __global__ __launch_bounds__(RK_THREADS) void rk_stage_kernel(int method, int st
     for (long t = i; t < n; ++t) rk_stage_elems<1>(method, stage, S, y0, k, v, dt_ptr, y_stage, y_in, n, t);
 }
 
-// the block's 256 partial sums -> thread 0, always the same tree (dopri5.hip: dp_block_sum)
+// the block's 256 partial sums -> thread 0, always the same tree
 VC_DEV float rk_block_sum(float (&l)[RK_THREADS], float s) {
   const int t = threadIdx.x;
   l[t] = s;
@@ -186,8 +207,11 @@ VC_DEV float rk_block_sum(float (&l)[RK_THREADS], float s) {
   return r;
 }
 
-// pass 1, the deal and the modes of dopri5_norm_kernel: the n elements go to the nblk * 256 threads round-robin, a thread adds its q^2
-// in ascending order.  mode 0 takes the method's e row; modes 1..3 read y0, k1 and k2 - k1 (k2 holds the probe evaluation)
+// pass 1: the n elements are dealt to the nblk * 256 threads round-robin, a thread adds its q^2 in ascending order.
+//   mode 0  q = dt * (e row) / (atol + rtol * max(|y0|, |y1|))        the error ratio of a step
+//   mode 1  q = y0 / (atol + rtol * |y0|)                              d0 of the initial step size
+//   mode 2  q = k1 / (atol + rtol * |y0|)                              d1
+//   mode 3  q = (k2 - k1) / (atol + rtol * |y0|)                       d2 * h0 (k2 holds the probe evaluation)
 __global__ __launch_bounds__(RK_THREADS) void rk_norm_kernel(int method, int mode, const float* __restrict__ y0, const float* __restrict__ y1,
                                                              const bf16_t* __restrict__ k, const float* __restrict__ dt_ptr, float rtol,
                                                              float atol, float* __restrict__ partial, long n) {
@@ -262,6 +286,50 @@ __global__ __launch_bounds__(RK_THREADS) void rk_hermite_kernel(int last, const 
     for (long t = i; t < n; ++t) rk_hermite_elems<1, BF16>(y0, y1, k, kl, dt, x, out, t);
 }
 
+// Dormand-Prince's dense output - torchdiffeq's _interp_fit / _interp_evaluate, operation by operation; theta = 0 and theta = 1 hand
+// back y0 and y1 themselves
+template <bool BF16>
+__global__ __launch_bounds__(RK_THREADS) void dopri5_interp_kernel(const float* __restrict__ y0, const float* __restrict__ y1,
+                                                                   const bf16_t* __restrict__ k, const float* __restrict__ dt_ptr, float x,
+                                                                   void* __restrict__ out, long n) {
+  const long i = (long)blockIdx.x * RK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float a0 = y0[i], a1 = y1[i];
+  float r;
+  if (x == 0.0f) r = a0;
+  else if (x == 1.0f) r = a1;
+  else {
+    const float dt = *dt_ptr;
+    const float f0 = bf2f(k[i]), f1 = bf2f(k[6 * n + i]);
+    float mid[1];
+    rk_combine<1>(DP_MID, k, n, i, mid);
+    const float ym = a0 + dt * mid[0];
+    const float two_dt = 2.0f * dt;
+    const float ca = (two_dt * (f1 - f0) - 8.0f * (a1 + a0)) + 16.0f * ym;
+    const float cb = ((dt * (5.0f * f0 - 3.0f * f1) + 18.0f * a0) + 14.0f * a1) - 32.0f * ym;
+    const float cc = ((dt * (f1 - 4.0f * f0) - 11.0f * a0) - 5.0f * a1) + 16.0f * ym;
+    const float cd = dt * f0;
+    float xp = x;
+    r = a0 + xp * cd;
+    xp = xp * x; r = r + xp * cc;
+    xp = xp * x; r = r + xp * cb;
+    xp = xp * x; r = r + xp * ca;
+  }
+  if constexpr (BF16) ((bf16_t*)out)[i] = f2bf(r);
+  else ((float*)out)[i] = r;
+}
+
+// the caller's state -> the f32 state and its bf16 shadow (what img_in reads)
+template <bool BF16>
+__global__ __launch_bounds__(RK_THREADS) void dopri5_load_kernel(const void* __restrict__ x, float* __restrict__ y0, bf16_t* __restrict__ y_in,
+                                                                 long n) {
+  const long i = (long)blockIdx.x * RK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float v = BF16 ? bf2f(((const bf16_t*)x)[i]) : ((const float*)x)[i];
+  y0[i] = v;
+  y_in[i] = f2bf(v);
+}
+
 // a grid of ceil(n / 256) blocks must fit the x dimension
 inline bool rk_n_ok(int64_t n) { return n > 0 && n <= (int64_t)0x7fffffff * RK_THREADS; }
 inline unsigned rk_blocks(int64_t n, int W) { return (unsigned)(((n + W - 1) / W + RK_THREADS - 1) / RK_THREADS); }
@@ -273,21 +341,26 @@ inline bool rk_aligned16(std::initializer_list<const void*> ps) {
 
 }  // namespace
 
-#define VC_CHECK_LAUNCH(name)                                                                     \
+// `what`: the entry point's name in its messages
+#define VC_CHECK_LAUNCH(what)                                                                     \
   do {                                                                                            \
     hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } \
+    if (e_ != hipSuccess) { snprintf(err, errlen, "%s launch: %s", what, hipGetErrorString(e_)); return VC_ERR_HIP; } \
     return VC_OK;                                                                                 \
   } while (0)
 
+// `alias` (all three launchers): the vc_dopri5_* entry point the call serves - its name stands in the messages, which then name no method
 int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
-                       float* y_stage, void* y_in, int64_t n, hipStream_t s, char* err, int errlen) {
+                       float* y_stage, void* y_in, int64_t n, hipStream_t s, char* err, int errlen, const char* alias) {
+  const char* what = alias ? alias : "rk_stage";
   const int S = vc_rk_stages_of(method);
-  if (!S) { snprintf(err, errlen, "rk_stage: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", method); return VC_ERR_ARG; }
+  if (!S) { snprintf(err, errlen, "%s: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", what, method); return VC_ERR_ARG; }
   if (!y0 || !k || !dt_ptr || !rk_n_ok(n) || (stage >= S && stage != RK_PROBE) || (stage < 0 && !eval_ptr) || (stage == S - 1 && !v) ||
       (stage == RK_PROBE && v) || (stage != S - 1 && !y_stage && !y_in)) {
-    snprintf(err, errlen, "rk_stage: bad args (method %d: stage 0..%d, or < 0 with the evaluation counter; stage 7, the probe state, takes no v)",
-             method, S - 1);
+    char of[32] = "";
+    if (!alias) snprintf(of, sizeof(of), "method %d: ", method);
+    snprintf(err, errlen, "%s: bad args (%sstage 0..%d, or < 0 with the evaluation counter; stage 7, the probe state, takes no v)", what, of,
+             S - 1);
     return VC_ERR_ARG;
   }
   if (rk_aligned16({y0, k, v, y_stage, y_in}))
@@ -296,21 +369,22 @@ int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const vo
   else
     hipLaunchKernelGGL(rk_stage_kernel<1>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, method, stage, y0, (bf16_t*)k, (const bf16_t*)v, dt_ptr,
                        (const int*)eval_ptr, y_stage, (bf16_t*)y_in, (long)n);
-  VC_CHECK_LAUNCH("rk_stage");
+  VC_CHECK_LAUNCH(what);
 }
 
 int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
-                             float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen) {
+                             float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen, const char* alias) {
+  const char* what = alias ? alias : "rk_error_ratio";
   if (!vc_rk_stages_of(method)) {
-    snprintf(err, errlen, "rk_error_ratio: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", method);
+    snprintf(err, errlen, "%s: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", what, method);
     return VC_ERR_ARG;
   }
   if (mode < 0 || mode > 3 || !y0 || !out || !scratch || !rk_n_ok(n) || (mode == 0 && (!y1 || !dt_ptr)) || (mode != 1 && !k)) {
-    snprintf(err, errlen, "rk_error_ratio: bad args (mode 0..3; mode 0 needs y1, k and dt, modes 2 and 3 need k)");
+    snprintf(err, errlen, "%s: bad args (mode 0..3; mode 0 needs y1, k and dt, modes 2 and 3 need k)", what);
     return VC_ERR_ARG;
   }
   if (!(rtol >= 0.0f) || !(atol >= 0.0f) || !(rtol + atol > 0.0f) || !(rtol + atol - (rtol + atol) == 0.0f)) {
-    snprintf(err, errlen, "rk_error_ratio: rtol = %g and atol = %g must be finite, non-negative and not both zero", rtol, atol);
+    snprintf(err, errlen, "%s: rtol = %g and atol = %g must be finite, non-negative and not both zero", what, rtol, atol);
     return VC_ERR_ARG;
   }
   const int64_t want = (n + RK_THREADS - 1) / RK_THREADS;
@@ -318,19 +392,25 @@ int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float*
   hipLaunchKernelGGL(rk_norm_kernel, dim3(nblk), dim3(RK_THREADS), 0, s, method, mode, y0, y1, (const bf16_t*)k, dt_ptr, rtol, atol, scratch,
                      (long)n);
   hipLaunchKernelGGL(rk_norm_finish_kernel, dim3(1), dim3(RK_THREADS), 0, s, (const float*)scratch, out, nblk, (long)n);
-  VC_CHECK_LAUNCH("rk_error_ratio");
+  VC_CHECK_LAUNCH(what);
 }
 
-int vc_rk_interp_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
-                        int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen) {
-  if (method != VC_RK_BOSH3 && method != VC_RK_ADAPTIVE_HEUN) {
-    snprintf(err, errlen, "rk_interp: method %d has no Hermite dense output (VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN; Dormand-Prince: vc_dopri5_interp)",
-             method);
-    return VC_ERR_ARG;
+// the dense output of the pair: the quartic for Dormand-Prince, the Hermite cubic for the others
+int vc_rk_dense_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                       int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen, const char* alias) {
+  const char* what = alias ? alias : "rk_interp";
+  const int S = vc_rk_stages_of(method);
+  if (!S) { snprintf(err, errlen, "%s: unknown method %d (VC_RK_DOPRI5, VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN)", what, method); return VC_ERR_ARG; }
+  if (!y0 || !y1 || !k || !dt_ptr || !out || !rk_n_ok(n)) { snprintf(err, errlen, "%s: bad args", what); return VC_ERR_ARG; }
+  if (!(theta >= 0.0f && theta <= 1.0f)) { snprintf(err, errlen, "%s: theta = %g outside [0, 1]", what, theta); return VC_ERR_ARG; }
+  if (method == VC_RK_DOPRI5) {
+    if (out_is_bf16) hipLaunchKernelGGL(dopri5_interp_kernel<true>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, y0, y1, (const bf16_t*)k, dt_ptr,
+                                        theta, out, (long)n);
+    else hipLaunchKernelGGL(dopri5_interp_kernel<false>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, y0, y1, (const bf16_t*)k, dt_ptr, theta,
+                            out, (long)n);
+    VC_CHECK_LAUNCH(what);
   }
-  if (!y0 || !y1 || !k || !dt_ptr || !out || !rk_n_ok(n)) { snprintf(err, errlen, "rk_interp: bad args"); return VC_ERR_ARG; }
-  if (!(theta >= 0.0f && theta <= 1.0f)) { snprintf(err, errlen, "rk_interp: theta = %g outside [0, 1]", theta); return VC_ERR_ARG; }
-  const int last = vc_rk_stages_of(method) - 1;
+  const int last = S - 1;
   const bool vec = rk_aligned16({y0, y1, k, out});
 #define RK_HERMITE(W, BF)                                                                                                              \
   hipLaunchKernelGGL((rk_hermite_kernel<W, BF>), dim3(rk_blocks(n, W)), dim3(RK_THREADS), 0, s, last, y0, y1, (const bf16_t*)k, dt_ptr, \
@@ -340,5 +420,23 @@ int vc_rk_interp_launch(int method, const float* y0, const float* y1, const void
   else if (out_is_bf16) RK_HERMITE(1, true);
   else RK_HERMITE(1, false);
 #undef RK_HERMITE
-  VC_CHECK_LAUNCH("rk_interp");
+  VC_CHECK_LAUNCH(what);
+}
+
+// vc_rk_interp: the Hermite pairs alone - the public route to Dormand-Prince's dense output is vc_dopri5_interp
+int vc_rk_interp_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                        int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (method != VC_RK_BOSH3 && method != VC_RK_ADAPTIVE_HEUN) {
+    snprintf(err, errlen, "rk_interp: method %d has no Hermite dense output (VC_RK_BOSH3, VC_RK_ADAPTIVE_HEUN; Dormand-Prince: vc_dopri5_interp)",
+             method);
+    return VC_ERR_ARG;
+  }
+  return vc_rk_dense_launch(method, y0, y1, k, dt_ptr, theta, out, out_is_bf16, n, s, err, errlen);
+}
+
+int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen) {
+  if (!x || !y0 || !y_in || !rk_n_ok(n)) { snprintf(err, errlen, "dopri5_load: bad args"); return VC_ERR_ARG; }
+  if (x_is_bf16) hipLaunchKernelGGL(dopri5_load_kernel<true>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, x, y0, (bf16_t*)y_in, (long)n);
+  else hipLaunchKernelGGL(dopri5_load_kernel<false>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, x, y0, (bf16_t*)y_in, (long)n);
+  VC_CHECK_LAUNCH("dopri5_load");
 }

@@ -59,24 +59,22 @@ int vc_ode_update_launch(const char* what, int method, int stage, void* y, int s
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen);
-// dopri5.hip: the adaptive solve's kernels (vc_dopri5_load_launch: the caller's state -> the f32 state and its bf16 shadow)
-int vc_dopri5_stage_launch(int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr, float* y_stage,
-                           void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
-int vc_dopri5_error_ratio_launch(int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
-                                 float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen);
-int vc_dopri5_interp_launch(const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out, int out_is_bf16,
-                            int64_t n, hipStream_t s, char* err, int errlen);
-int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
-// rk_embedded.hip: the same three kernels with the tableau as an argument (VC_RK_*)
+// rk_embedded.hip: the adaptive solve's kernels with the pair (VC_RK_*) as an argument.  `alias`: the vc_dopri5_* entry point a call
+// serves (its name stands in the messages); vc_rk_dense_launch: the pair's dense output, the quartic of Dormand-Prince or the Hermite
+// cubic; vc_rk_interp_launch: the public vc_rk_interp, which refuses VC_RK_DOPRI5; vc_dopri5_load_launch: the caller's state -> the
+// f32 state and its bf16 shadow
 __host__ __device__ inline int vc_rk_stages_of(int method) {   // evaluations k1..kS of a step, the last one first-same-as-last; 0 = not a VC_RK_*
   return method == VC_RK_DOPRI5 ? 7 : method == VC_RK_BOSH3 ? 4 : method == VC_RK_ADAPTIVE_HEUN ? 3 : 0;
 }
 int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
-                       float* y_stage, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
+                       float* y_stage, void* y_in, int64_t n, hipStream_t s, char* err, int errlen, const char* alias = nullptr);
 int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
-                             float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen);
+                             float* out, float* scratch, int64_t n, hipStream_t s, char* err, int errlen, const char* alias = nullptr);
+int vc_rk_dense_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
+                       int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen, const char* alias = nullptr);
 int vc_rk_interp_launch(int method, const float* y0, const float* y1, const void* k, const float* dt_ptr, float theta, void* out,
                         int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen);
+int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, int64_t n, hipStream_t s, char* err, int errlen);
 // rng.hip / sde_plan.hip: the stochastic sampler's update, the store of its F32 state in the caller's dtype, and its host rule
 int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
                         const uint64_t* rng, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen);

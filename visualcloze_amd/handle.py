@@ -575,23 +575,26 @@ class FluxHandle(_Handle):
     def sample_euler(self, x, cond, t_grid, state_is_bf16: bool, stream, trajectory=None) -> None:
         self.sample_ode("euler", x, cond, t_grid, state_is_bf16, stream, trajectory)
 
+    def _sample_adaptive(self, name, method, x, cond, t_grid, state_is_bf16, stream, rtol, atol, max_attempts, trajectory) -> None:
+        """the adaptive entry point `name`; method: the VC_RK_* argument of vc_flux_sample_rk, None for vc_flux_sample_dopri5, which takes none"""
+        args = self._sample_args(name, 0, x, cond, t_grid, state_is_bf16, trajectory)
+        pair = () if method is None else (hip._rk_code(method),)
+        hip._check(getattr(hip.lib(), name)(args[0], *pair, *args[2:], float(rtol), float(atol), int(max_attempts), hip._p(trajectory), stream),
+                   name)
+
     def sample_dopri5(self, x, cond, t_grid, state_is_bf16: bool, stream, rtol: float = 1e-3, atol: float = 1e-6,
                       max_attempts: int = 1000, trajectory=None) -> None:
         """vc_flux_sample_dopri5 (after `set_adaptive(True)` and a prepare with max_steps >= 7): x [B,N,C] in place, x(t_grid[0]) ->
         x(t_grid[-1]) by the adaptive Dormand-Prince 5(4) solve; trajectory: optional [len(t_grid) - 1, B, N, C] buffer receiving
         x(t_grid[1:]) (dense output).  The state is stepped in f32 whatever its dtype.  `dopri5_log()` tells what the solve did."""
-        args = self._sample_args("vc_flux_sample_dopri5", 0, x, cond, t_grid, state_is_bf16, trajectory)
-        hip._check(hip.lib().vc_flux_sample_dopri5(args[0], *args[2:], float(rtol), float(atol), int(max_attempts), hip._p(trajectory), stream),
-                   "vc_flux_sample_dopri5")
+        self._sample_adaptive("vc_flux_sample_dopri5", None, x, cond, t_grid, state_is_bf16, stream, rtol, atol, max_attempts, trajectory)
 
     def sample_rk(self, method, x, cond, t_grid, state_is_bf16: bool, stream, rtol: float = 1e-3, atol: float = 1e-6,
                   max_attempts: int = 1000, trajectory=None) -> None:
         """vc_flux_sample_rk (after `set_adaptive(True)` and a prepare with max_steps >= the method's stages): `sample_dopri5` with the
         embedded pair `method` - "bosh3" | "adaptive_heun" (hip.RK_METHODS) or a VC_RK_* code; 3 / 2 evaluations per attempt.
         `dopri5_log()` tells what the solve did (one log serves both)."""
-        args = self._sample_args("vc_flux_sample_rk", 0, x, cond, t_grid, state_is_bf16, trajectory)
-        hip._check(hip.lib().vc_flux_sample_rk(args[0], hip._rk_code(method), *args[2:], float(rtol), float(atol), int(max_attempts),
-                                               hip._p(trajectory), stream), "vc_flux_sample_rk")
+        self._sample_adaptive("vc_flux_sample_rk", method, x, cond, t_grid, state_is_bf16, stream, rtol, atol, max_attempts, trajectory)
 
     def sample_sde(self, method: str, x, cond, t_grid, state_is_bf16: bool, stream, form: str = "SBDM", norm: float = 1.0,
                    last_step="Mean", last_step_size: float = 0.04, seed: int = 0, offset: int = 0, trajectory=None) -> None:

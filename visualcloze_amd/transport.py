@@ -371,9 +371,13 @@ def _step_rk4(f, t0, t1, dt, y0):          # the 3/8 rule
 STEP_RULES = {"euler": _step_euler, "midpoint": _step_midpoint, "rk4": _step_rk4}
 
 
-# ---- the adaptive Dormand-Prince 5(4) solve (vc_flux_sample_dopri5): the same rule in plain torch, for any callable.  The tableau is
-# SciPy's RK45.C / .A / .B / .E (tests/test_dopri5_cpu.py pins it, and single steps, against SciPy) plus torchdiffeq's DPS_C_MID; the
-# controller is torchdiffeq's as recalled - unpinned against real torchdiffeq, which was not available to check against.
+# ---- the adaptive solve of an embedded Runge-Kutta pair (vc_flux_sample_dopri5 / vc_flux_sample_rk, csrc/rk_embedded.hip): the same
+# rules in plain torch, for any callable - ONE step, error ratio, controller, initial-step search and loop (the _rk_* functions), each
+# taking the pair's record; the public dopri5_* and rk_* names below are those at a record.  A method of S stages evaluates k1..kS
+# per step; kS = f(t1, y1) is the next step's k1 (first same as last), so an attempt costs S - 1 evaluations.  The Dormand-Prince
+# tableau is SciPy's RK45.C / .A / .B / .E plus torchdiffeq's DPS_C_MID, bosh3 SciPy's RK23.C / .A / .B / .E and adaptive_heun the
+# closed form (tests/test_dopri5_cpu.py and tests/test_rk_embedded_cpu.py pin them, and single steps); the controller is
+# torchdiffeq's as recalled - unpinned against real torchdiffeq, which was not available to check against.
 DOPRI5_C = (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0)
 DOPRI5_A = ((1 / 5,),
             (3 / 40, 9 / 40),
@@ -391,7 +395,7 @@ class Dopri5Error(RuntimeError):
 
 
 def _dopri5_combine(row, ks):
-    """sum of row[j] * ks[j] over the non-zero coefficients, left to right (csrc/dopri5.hip: dp_combine - the same bits in f32)"""
+    """sum of row[j] * ks[j] over the non-zero coefficients, left to right (csrc/rk_embedded.hip: rk_combine - the same bits in f32)"""
     acc = None
     for c, k in zip(row, ks):
         if c == 0.0:
@@ -410,155 +414,12 @@ def _scalar(v: float, y: torch.Tensor) -> float:
     return _f32(v) if y.dtype == torch.float32 else float(v)
 
 
-def dopri5_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor):
-    """One Dormand-Prince step from (t, y0) with k1 = f(t, y0): -> (y1, [k1..k7]); k7 = f(t + dt, y1) is the next step's k1.
-    Every k is converted to the state's dtype, every sum is taken left to right."""
-    h = _scalar(dt, y0)
-    ks = [k1.to(y0.dtype)]
-    for i, row in enumerate(DOPRI5_A):
-        ks.append(f(t + DOPRI5_C[i + 1] * dt, y0 + h * _dopri5_combine(row, ks)).to(y0.dtype))
-    y1 = y0 + h * _dopri5_combine(DOPRI5_B, ks)
-    ks.append(f(t + dt, y1).to(y0.dtype))
-    return y1, ks
-
-
-def dopri5_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float) -> float:
-    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements"""
-    err = _scalar(dt, y0) * _dopri5_combine(DOPRI5_E, ks)
-    tol = _scalar(atol, y0) + _scalar(rtol, y0) * torch.maximum(y0.abs(), y1.abs())
-    q = err / tol
-    return float((q * q).mean().sqrt())
-
-
-def dopri5_interp(y0, y1, ks, dt: float, theta: float):
-    """The dense output at theta in [0, 1]: the quartic through (y0, f0, y_mid, y1, f1) as torchdiffeq fits and evaluates it; theta = 0
-    and theta = 1 return y0 and y1 themselves.  For an f32 state the scalars are f32, as in csrc/dopri5.hip."""
-    x = _scalar(theta, y0)
-    if x == 0.0:
-        return y0.clone()
-    if x == 1.0:
-        return y1.clone()
-    f32 = y0.dtype == torch.float32
-    h = _scalar(dt, y0)
-    f0, f1 = ks[0], ks[6]
-    y_mid = y0 + h * _dopri5_combine(DOPRI5_C_MID, ks)
-    a = (2 * h * (f1 - f0) - 8 * (y1 + y0)) + 16 * y_mid
-    b = ((h * (5 * f0 - 3 * f1) + 18 * y0) + 14 * y1) - 32 * y_mid
-    c = ((h * (f1 - 4 * f0) - 11 * y0) - 5 * y1) + 16 * y_mid
-    d = h * f0
-    xp = x
-    out = y0 + xp * d
-    for coeff in (c, b, a):
-        xp = _f32(xp * x) if f32 else xp * x          # (the product of two f32 values in double, rounded once: the f32 product)
-        out = out + xp * coeff
-    return out
-
-
-def dopri5_controller(dt: float, ratio: float):
-    """-> (accepted, dt_next): accept iff ratio <= 1; dt_next = 10 dt for ratio 0, else dt * min(10, max(0.9 / ratio^(1/5), 1 if
-    ratio < 1 else 0.2)).  A NaN ratio raises Dopri5Error."""
-    if ratio != ratio:
-        raise Dopri5Error(f"dopri5: the error ratio of a step of dt = {dt:.3g} is NaN")
-    if ratio == 0.0:
-        return True, dt * 10.0
-    return ratio <= 1.0, dt * min(10.0, max(0.9 / math.pow(ratio, 1.0 / 5.0), 1.0 if ratio < 1.0 else 0.2))
-
-
 def _rms(a) -> float:
     return float((a * a).mean().sqrt())
 
 
-def dopri5_initial_step(f, t0: float, y0, f0, rtol: float, atol: float) -> float:
-    """Hairer's starting step size for order 4 (one more evaluation)"""
-    scale = _scalar(atol, y0) + _scalar(rtol, y0) * y0.abs()
-    f0 = f0.to(y0.dtype)
-    d0, d1 = _rms(y0 / scale), _rms(f0 / scale)
-    if d0 != d0 or d1 != d1:
-        raise Dopri5Error("dopri5: the state or the drift at the first time is not finite")
-    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
-    f1 = f(t0 + h0, y0 + _scalar(h0, y0) * f0).to(y0.dtype)
-    d2 = _rms((f1 - f0) / scale) / h0
-    if d2 != d2:
-        raise Dopri5Error("dopri5: the drift at the first time + h0 is not finite")
-    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else math.pow(0.01 / max(d1, d2), 1.0 / 5.0)
-    return min(100.0 * h0, h1)
-
-
-def dopri5_integrate(f, y0: torch.Tensor, t, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
-                     log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
-    """The adaptive Dormand-Prince 5(4) solve of y' = f(t, y) from y(t[0]) = y0: -> [len(t), ...] = y at every t (t[0]: y0 itself;
-    the others by dense output inside the accepted step that covers them - steps are not clamped to the output times, so f may be
-    evaluated past t[-1]).  t: increasing Python floats (or a 1-d tensor); f takes a Python float and the state and returns the drift.
-    The state keeps its dtype (f32 or f64); one step size serves the whole tensor.  `forced_dts`: replay a given attempt sequence -
-    a list of dt, or of (dt, accepted) pairs, one per attempt: no initial-step search, no controller.  `log` (a list) receives
-    (t, dt, ratio, accepted) per attempt; `on_attempt(t, dt, y0, y1, ks)` sees every attempt's tensors.  Raises Dopri5Error on a NaN ratio, an underflowed step or more than max_attempts attempts."""
-    ts = [float(v) for v in (t.tolist() if torch.is_tensor(t) else t)]
-    if len(ts) < 2 or any(b <= a for a, b in zip(ts, ts[1:])):
-        raise ValueError("dopri5_integrate: t must hold at least two strictly increasing times")
-    if y0.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"dopri5_integrate: an f32 or f64 state expected, got {y0.dtype}")
-    log = log if log is not None else []
-    tc = ts[0]
-    k1 = f(tc, y0).to(y0.dtype)
-    forced = None if forced_dts is None else list(forced_dts)
-    dt = None if forced is not None else dopri5_initial_step(f, tc, y0, k1, rtol, atol)
-    outs, nxt, attempts = [y0], 1, 0
-    while nxt < len(ts):
-        if forced is not None:
-            if attempts >= len(forced):
-                raise Dopri5Error(f"dopri5: the {len(forced)} forced attempts end at t = {tc!r}, before t[{nxt}] = {ts[nxt]!r}")
-            item = forced[attempts]
-            dt, accept_as = (float(item[0]), bool(item[1])) if isinstance(item, (tuple, list)) else (float(item), None)
-        if attempts >= max_attempts:
-            raise Dopri5Error(f"dopri5: more than max_attempts = {max_attempts} attempts (t = {tc!r}, dt = {dt:.3g})")
-        if tc + dt == tc:
-            raise Dopri5Error(f"dopri5: the step size underflowed (t = {tc!r}, dt = {dt:.3g})")
-        attempts += 1
-        y1, ks = dopri5_step(f, tc, dt, y0, k1)
-        ratio = dopri5_error_ratio(y0, y1, ks, dt, rtol, atol)
-        if on_attempt is not None:
-            on_attempt(tc, dt, y0, y1, ks)
-        if forced is not None and accept_as is not None:
-            accepted, dt_next = accept_as, None
-            log.append((tc, dt, ratio, accepted))
-        else:
-            log.append((tc, dt, ratio, ratio <= 1.0))
-            accepted, dt_next = dopri5_controller(dt, ratio)
-        if accepted:
-            t1 = tc + dt
-            while nxt < len(ts) and ts[nxt] <= t1:
-                outs.append(dopri5_interp(y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
-                nxt += 1
-            y0, k1, tc = y1, ks[6], t1
-        dt = dt_next
-    return torch.stack(outs)
-
-
-# ---- embedded Runge-Kutta pairs, tableau-driven (vc_rk_* / vc_flux_sample_rk, csrc/rk_embedded.hip): the same rules in plain torch,
-# bit-equal to the fused loop for an f32 state.  A method of S stages evaluates k1..kS per step; kS = f(t1, y1) is the next step's k1
-# (first same as last), so an attempt costs S - 1 evaluations.  c: the S stage times; a: the rows a2 .. a(S-1); b: forms y1 (= row aS);
-# e: the S weights of the error estimate.  bosh3 is SciPy's RK23.C / .A / .B / .E and adaptive_heun the closed form
-# (tests/test_rk_embedded_cpu.py pins both, in single steps); the controller is torchdiffeq's as recalled - unpinned against real
-# torchdiffeq - with the exponent 1 / order where Dormand-Prince has 1/5.  "dopri5" is here for the stage and error kernels only
-# (vc_rk_stage / vc_rk_error_ratio return vc_dopri5_*'s bits with it): its solve is dopri5_integrate.
-RK_TABLEAUS = {
-    "dopri5": dict(code=0, order=5, c=DOPRI5_C + (1.0,), a=DOPRI5_A, b=DOPRI5_B, e=DOPRI5_E),
-    "bosh3": dict(code=1, order=3, c=(0.0, 1 / 2, 3 / 4, 1.0), a=((1 / 2,), (0.0, 3 / 4)), b=(2 / 9, 1 / 3, 4 / 9),
-                  e=(5 / 72, -1 / 12, -1 / 9, 1 / 8)),
-    "adaptive_heun": dict(code=2, order=2, c=(0.0, 1.0, 1.0), a=((1.0,),), b=(1 / 2, 1 / 2), e=(1 / 2, -1 / 2, 0.0)),
-}
-ADAPTIVE_METHODS = ("dopri5", "bosh3", "adaptive_heun")       # Sampler.sample_ode_adaptive(method=)
-
-
-def _rk_tableau(method: str, solve: bool = False) -> dict:
-    if method not in RK_TABLEAUS or (solve and method == "dopri5"):
-        raise ValueError(f"method {method!r}: one of {[m for m in RK_TABLEAUS if not (solve and m == 'dopri5')]} expected"
-                         + (" (Dormand-Prince has one route: dopri5_integrate)" if method == "dopri5" else ""))
-    return RK_TABLEAUS[method]
-
-
 def _rk_norm(num: torch.Tensor, den: torch.Tensor) -> float:
-    """sqrt(mean(q^2)) of q = num / den over all n elements, summed in q's dtype in the fixed order of csrc/rk_embedded.hip (and dopri5.hip): the
+    """sqrt(mean(q^2)) of q = num / den over all n elements, summed in q's dtype in the fixed order of csrc/rk_embedded.hip: the
     elements are dealt round-robin to nblk * 256 threads (nblk = min(ceil(n / 256), 256)), a thread adds its squares in ascending
     order, a block's 256 sums go down one binary tree, the block sums down the same tree.  For an f32 q this gives the kernel's bits;
     the callers form num and den on the CPU too."""
@@ -589,25 +450,28 @@ def _rk_norm(num: torch.Tensor, den: torch.Tensor) -> float:
     return math.sqrt(mean) if q.dtype == torch.float64 else _f32(math.sqrt(mean))
 
 
-def rk_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor, method: str):
-    """One step of the pair from (t, y0) with k1 = f(t, y0): -> (y1, [k1..kS]); kS = f(t + dt, y1) is the next step's k1.  Every k is
-    converted to the state's dtype, every sum is taken left to right over the non-zero coefficients."""
-    tab = _rk_tableau(method)
+def dopri5_interp(y0, y1, ks, dt: float, theta: float):
+    """The dense output at theta in [0, 1]: the quartic through (y0, f0, y_mid, y1, f1) as torchdiffeq fits and evaluates it; theta = 0
+    and theta = 1 return y0 and y1 themselves.  For an f32 state the scalars are f32, as in csrc/rk_embedded.hip."""
+    x = _scalar(theta, y0)
+    if x == 0.0:
+        return y0.clone()
+    if x == 1.0:
+        return y1.clone()
+    f32 = y0.dtype == torch.float32
     h = _scalar(dt, y0)
-    ks = [k1.to(y0.dtype)]
-    for i, row in enumerate(tab["a"]):
-        ks.append(f(t + tab["c"][i + 1] * dt, y0 + h * _dopri5_combine(row, ks)).to(y0.dtype))
-    y1 = y0 + h * _dopri5_combine(tab["b"], ks)
-    ks.append(f(t + dt, y1).to(y0.dtype))
-    return y1, ks
-
-
-def rk_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float, method: str) -> float:
-    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements, in the kernel's summation order"""
-    y0, y1, ks = y0.detach().cpu(), y1.detach().cpu(), [k.detach().cpu() for k in ks]
-    err = _scalar(dt, y0) * _dopri5_combine(_rk_tableau(method)["e"], ks)
-    tol = _scalar(atol, y0) + _scalar(rtol, y0) * torch.maximum(y0.abs(), y1.abs())
-    return _rk_norm(err, tol)
+    f0, f1 = ks[0], ks[6]
+    y_mid = y0 + h * _dopri5_combine(DOPRI5_C_MID, ks)
+    a = (2 * h * (f1 - f0) - 8 * (y1 + y0)) + 16 * y_mid
+    b = ((h * (5 * f0 - 3 * f1) + 18 * y0) + 14 * y1) - 32 * y_mid
+    c = ((h * (f1 - 4 * f0) - 11 * y0) - 5 * y1) + 16 * y_mid
+    d = h * f0
+    xp = x
+    out = y0 + xp * d
+    for coeff in (c, b, a):
+        xp = _f32(xp * x) if f32 else xp * x          # (the product of two f32 values in double, rounded once: the f32 product)
+        out = out + xp * coeff
+    return out
 
 
 def rk_hermite(y0, y1, ks, dt: float, theta: float):
@@ -632,67 +496,104 @@ def rk_hermite(y0, y1, ks, dt: float, theta: float):
     return (c0 * y0 + x * y1) + w * inner
 
 
-def rk_controller(dt: float, ratio: float, order: int):
-    """-> (accepted, dt_next): dopri5_controller with the exponent 1 / order (at order 5 the same bits).  A NaN ratio raises."""
+# A pair's record.  c: the S stage times; a: the rows a2 .. a(S-1); b: forms y1 (= row aS); e: the S weights of the error estimate;
+# interp: its dense output.  `name` (the prefix of its messages), `local` and `norm` say how the RMS norms are taken, and there are
+# two ways, which differ in the last bits: _KERNEL_NORM, on CPU copies in the summation order of the kernel (vc_rk_error_ratio) - what
+# every rk_* function does, Dormand-Prince included; and _TORCH_NORM, torch's mean() on the tensor's own device - what the dopri5_*
+# functions do (_DOPRI5).  The fused Dormand-Prince solve is held to the latter on forced attempts (tests/test_dopri5_gpu.py).
+_KERNEL_NORM = dict(name="rk", local=lambda v: v.detach().cpu(), norm=_rk_norm)
+_TORCH_NORM = dict(name="dopri5", local=lambda v: v, norm=lambda num, den: _rms(num / den))
+RK_TABLEAUS = {
+    "dopri5": dict(code=0, order=5, c=DOPRI5_C + (1.0,), a=DOPRI5_A, b=DOPRI5_B, e=DOPRI5_E, interp=dopri5_interp, **_KERNEL_NORM),
+    "bosh3": dict(code=1, order=3, c=(0.0, 1 / 2, 3 / 4, 1.0), a=((1 / 2,), (0.0, 3 / 4)), b=(2 / 9, 1 / 3, 4 / 9),
+                  e=(5 / 72, -1 / 12, -1 / 9, 1 / 8), interp=rk_hermite, **_KERNEL_NORM),
+    "adaptive_heun": dict(code=2, order=2, c=(0.0, 1.0, 1.0), a=((1.0,),), b=(1 / 2, 1 / 2), e=(1 / 2, -1 / 2, 0.0), interp=rk_hermite,
+                          **_KERNEL_NORM),
+}
+_DOPRI5 = dict(RK_TABLEAUS["dopri5"], **_TORCH_NORM)
+ADAPTIVE_METHODS = ("dopri5", "bosh3", "adaptive_heun")       # Sampler.sample_ode_adaptive(method=)
+
+
+def _rk_tableau(method: str, solve: bool = False) -> dict:
+    """the record behind the rk_* functions; solve: of rk_integrate, which leaves Dormand-Prince to dopri5_integrate"""
+    if method not in RK_TABLEAUS or (solve and method == "dopri5"):
+        raise ValueError(f"method {method!r}: one of {[m for m in RK_TABLEAUS if not (solve and m == 'dopri5')]} expected"
+                         + (" (Dormand-Prince has one route: dopri5_integrate)" if method == "dopri5" else ""))
+    return RK_TABLEAUS[method]
+
+
+def _rk_step(tab, f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor):
+    h = _scalar(dt, y0)
+    ks = [k1.to(y0.dtype)]
+    for i, row in enumerate(tab["a"]):
+        ks.append(f(t + tab["c"][i + 1] * dt, y0 + h * _dopri5_combine(row, ks)).to(y0.dtype))
+    y1 = y0 + h * _dopri5_combine(tab["b"], ks)
+    ks.append(f(t + dt, y1).to(y0.dtype))
+    return y1, ks
+
+
+def _rk_error_ratio(tab, y0, y1, ks, dt: float, rtol: float, atol: float) -> float:
+    local = tab["local"]
+    y0, y1, ks = local(y0), local(y1), [local(k) for k in ks]
+    err = _scalar(dt, y0) * _dopri5_combine(tab["e"], ks)
+    tol = _scalar(atol, y0) + _scalar(rtol, y0) * torch.maximum(y0.abs(), y1.abs())
+    return tab["norm"](err, tol)
+
+
+def _rk_controller(tab, dt: float, ratio: float):
     if ratio != ratio:
-        raise Dopri5Error(f"rk: the error ratio of a step of dt = {dt:.3g} is NaN")
+        raise Dopri5Error(f"{tab['name']}: the error ratio of a step of dt = {dt:.3g} is NaN")
     if ratio == 0.0:
         return True, dt * 10.0
-    return ratio <= 1.0, dt * min(10.0, max(0.9 / math.pow(ratio, 1.0 / order), 1.0 if ratio < 1.0 else 0.2))
+    return ratio <= 1.0, dt * min(10.0, max(0.9 / math.pow(ratio, 1.0 / tab["order"]), 1.0 if ratio < 1.0 else 0.2))
 
 
-def _rk_first_dt(order: int, h0: float, d1: float, d2: float) -> float:
-    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else math.pow(0.01 / max(d1, d2), 1.0 / order)
+def _rk_initial_step(tab, f, t0: float, y0, f0, rtol: float, atol: float) -> float:
+    """Hairer's starting step size with the exponent 1 / order (one more evaluation)"""
+    name, local, norm = tab["name"], tab["local"], tab["norm"]
+    f0 = f0.to(y0.dtype)
+    c0, cf0 = local(y0), local(f0)
+    scale = _scalar(atol, y0) + _scalar(rtol, y0) * c0.abs()
+    d0, d1 = norm(c0, scale), norm(cf0, scale)
+    if d0 != d0 or d1 != d1:
+        raise Dopri5Error(f"{name}: the state or the drift at the first time is not finite")
+    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
+    f1 = f(t0 + h0, y0 + _scalar(h0, y0) * f0).to(y0.dtype)
+    d2 = norm(local(f1) - cf0, scale) / h0
+    if d2 != d2:
+        raise Dopri5Error(f"{name}: the drift at the first time + h0 is not finite")
+    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else math.pow(0.01 / max(d1, d2), 1.0 / tab["order"])
     return min(100.0 * h0, h1)
 
 
-def rk_initial_step(f, t0: float, y0, f0, rtol: float, atol: float, order: int) -> float:
-    """dopri5_initial_step with the exponent 1 / order and the norms in the kernel's summation order (one more evaluation)"""
-    f0 = f0.to(y0.dtype)
-    c0, cf0 = y0.detach().cpu(), f0.detach().cpu()
-    scale = _scalar(atol, y0) + _scalar(rtol, y0) * c0.abs()
-    d0, d1 = _rk_norm(c0, scale), _rk_norm(cf0, scale)
-    if d0 != d0 or d1 != d1:
-        raise Dopri5Error("rk: the state or the drift at the first time is not finite")
-    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
-    f1 = f(t0 + h0, y0 + _scalar(h0, y0) * f0).to(y0.dtype)
-    d2 = _rk_norm(f1.detach().cpu() - cf0, scale) / h0
-    if d2 != d2:
-        raise Dopri5Error("rk: the drift at the first time + h0 is not finite")
-    return _rk_first_dt(order, h0, d1, d2)
-
-
-def rk_integrate(f, y0: torch.Tensor, t, method: str, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
-                 log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
-    """dopri5_integrate for the pair `method` ("bosh3" | "adaptive_heun"): the same loop, arguments, log and errors (Dopri5Error), the
-    outputs read off the Hermite cubic of the accepted step that covers them.  For an f32 state every bit - states, ratios, step
-    sizes - is the fused loop's (vc_flux_sample_rk)."""
-    tab = _rk_tableau(method, solve=True)
-    order = tab["order"]
+def _rk_integrate(tab, f, y0, t, rtol, atol, max_attempts, forced_dts, log, on_attempt) -> torch.Tensor:
+    """the loop of dopri5_integrate and rk_integrate"""
+    name = tab["name"]
+    who = name + "_integrate"
     ts = [float(v) for v in (t.tolist() if torch.is_tensor(t) else t)]
     if len(ts) < 2 or any(b <= a for a, b in zip(ts, ts[1:])):
-        raise ValueError("rk_integrate: t must hold at least two strictly increasing times")
+        raise ValueError(f"{who}: t must hold at least two strictly increasing times")
     if y0.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"rk_integrate: an f32 or f64 state expected, got {y0.dtype}")
+        raise TypeError(f"{who}: an f32 or f64 state expected, got {y0.dtype}")
     log = log if log is not None else []
     tc = ts[0]
     k1 = f(tc, y0).to(y0.dtype)
     forced = None if forced_dts is None else list(forced_dts)
-    dt = None if forced is not None else rk_initial_step(f, tc, y0, k1, rtol, atol, order)
+    dt = None if forced is not None else _rk_initial_step(tab, f, tc, y0, k1, rtol, atol)
     outs, nxt, attempts = [y0], 1, 0
     while nxt < len(ts):
         if forced is not None:
             if attempts >= len(forced):
-                raise Dopri5Error(f"rk: the {len(forced)} forced attempts end at t = {tc!r}, before t[{nxt}] = {ts[nxt]!r}")
+                raise Dopri5Error(f"{name}: the {len(forced)} forced attempts end at t = {tc!r}, before t[{nxt}] = {ts[nxt]!r}")
             item = forced[attempts]
             dt, accept_as = (float(item[0]), bool(item[1])) if isinstance(item, (tuple, list)) else (float(item), None)
         if attempts >= max_attempts:
-            raise Dopri5Error(f"rk: more than max_attempts = {max_attempts} attempts (t = {tc!r}, dt = {dt:.3g})")
+            raise Dopri5Error(f"{name}: more than max_attempts = {max_attempts} attempts (t = {tc!r}, dt = {dt:.3g})")
         if tc + dt == tc:
-            raise Dopri5Error(f"rk: the step size underflowed (t = {tc!r}, dt = {dt:.3g})")
+            raise Dopri5Error(f"{name}: the step size underflowed (t = {tc!r}, dt = {dt:.3g})")
         attempts += 1
-        y1, ks = rk_step(f, tc, dt, y0, k1, method)
-        ratio = rk_error_ratio(y0, y1, ks, dt, rtol, atol, method)
+        y1, ks = _rk_step(tab, f, tc, dt, y0, k1)
+        ratio = _rk_error_ratio(tab, y0, y1, ks, dt, rtol, atol)
         if on_attempt is not None:
             on_attempt(tc, dt, y0, y1, ks)
         if forced is not None and accept_as is not None:
@@ -700,15 +601,77 @@ def rk_integrate(f, y0: torch.Tensor, t, method: str, rtol: float = 1e-3, atol: 
             log.append((tc, dt, ratio, accepted))
         else:
             log.append((tc, dt, ratio, ratio <= 1.0))
-            accepted, dt_next = rk_controller(dt, ratio, order)
+            accepted, dt_next = _rk_controller(tab, dt, ratio)
         if accepted:
             t1 = tc + dt
             while nxt < len(ts) and ts[nxt] <= t1:
-                outs.append(rk_hermite(y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
+                outs.append(tab["interp"](y0, y1, ks, dt, min(1.0, max(0.0, (ts[nxt] - tc) / dt))))
                 nxt += 1
             y0, k1, tc = y1, ks[-1], t1
         dt = dt_next
     return torch.stack(outs)
+
+
+def dopri5_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor):
+    """One Dormand-Prince step from (t, y0) with k1 = f(t, y0): -> (y1, [k1..k7]); k7 = f(t + dt, y1) is the next step's k1.
+    Every k is converted to the state's dtype, every sum is taken left to right."""
+    return _rk_step(_DOPRI5, f, t, dt, y0, k1)
+
+
+def dopri5_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float) -> float:
+    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements"""
+    return _rk_error_ratio(_DOPRI5, y0, y1, ks, dt, rtol, atol)
+
+
+def dopri5_controller(dt: float, ratio: float):
+    """-> (accepted, dt_next): accept iff ratio <= 1; dt_next = 10 dt for ratio 0, else dt * min(10, max(0.9 / ratio^(1/5), 1 if
+    ratio < 1 else 0.2)).  A NaN ratio raises Dopri5Error."""
+    return _rk_controller(_DOPRI5, dt, ratio)
+
+
+def dopri5_initial_step(f, t0: float, y0, f0, rtol: float, atol: float) -> float:
+    """Hairer's starting step size for order 4 (one more evaluation)"""
+    return _rk_initial_step(_DOPRI5, f, t0, y0, f0, rtol, atol)
+
+
+def dopri5_integrate(f, y0: torch.Tensor, t, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
+                     log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
+    """The adaptive Dormand-Prince 5(4) solve of y' = f(t, y) from y(t[0]) = y0: -> [len(t), ...] = y at every t (t[0]: y0 itself;
+    the others by dense output inside the accepted step that covers them - steps are not clamped to the output times, so f may be
+    evaluated past t[-1]).  t: increasing Python floats (or a 1-d tensor); f takes a Python float and the state and returns the drift.
+    The state keeps its dtype (f32 or f64); one step size serves the whole tensor.  `forced_dts`: replay a given attempt sequence -
+    a list of dt, or of (dt, accepted) pairs, one per attempt: no initial-step search, no controller.  `log` (a list) receives
+    (t, dt, ratio, accepted) per attempt; `on_attempt(t, dt, y0, y1, ks)` sees every attempt's tensors.  Raises Dopri5Error on a NaN ratio, an underflowed step or more than max_attempts attempts."""
+    return _rk_integrate(_DOPRI5, f, y0, t, rtol, atol, max_attempts, forced_dts, log, on_attempt)
+
+
+def rk_step(f, t: float, dt: float, y0: torch.Tensor, k1: torch.Tensor, method: str):
+    """One step of the pair from (t, y0) with k1 = f(t, y0): -> (y1, [k1..kS]); kS = f(t + dt, y1) is the next step's k1.  Every k is
+    converted to the state's dtype, every sum is taken left to right over the non-zero coefficients."""
+    return _rk_step(_rk_tableau(method), f, t, dt, y0, k1)
+
+
+def rk_error_ratio(y0, y1, ks, dt: float, rtol: float, atol: float, method: str) -> float:
+    """sqrt(mean(((dt * sum e_i k_i) / (atol + rtol * max(|y0|, |y1|)))^2)) over ALL elements, in the kernel's summation order"""
+    return _rk_error_ratio(_rk_tableau(method), y0, y1, ks, dt, rtol, atol)
+
+
+def rk_controller(dt: float, ratio: float, order: int):
+    """-> (accepted, dt_next): dopri5_controller with the exponent 1 / order (at order 5 the same bits).  A NaN ratio raises."""
+    return _rk_controller(dict(_KERNEL_NORM, order=order), dt, ratio)
+
+
+def rk_initial_step(f, t0: float, y0, f0, rtol: float, atol: float, order: int) -> float:
+    """dopri5_initial_step with the exponent 1 / order and the norms in the kernel's summation order (one more evaluation)"""
+    return _rk_initial_step(dict(_KERNEL_NORM, order=order), f, t0, y0, f0, rtol, atol)
+
+
+def rk_integrate(f, y0: torch.Tensor, t, method: str, rtol: float = 1e-3, atol: float = 1e-6, max_attempts: int = 1000, forced_dts=None,
+                 log: Optional[list] = None, on_attempt: Optional[Callable] = None) -> torch.Tensor:
+    """dopri5_integrate for the pair `method` ("bosh3" | "adaptive_heun"): the same loop, arguments, log and errors (Dopri5Error), the
+    outputs read off the Hermite cubic of the accepted step that covers them.  For an f32 state every bit - states, ratios, step
+    sizes - is the fused loop's (vc_flux_sample_rk)."""
+    return _rk_integrate(_rk_tableau(method, solve=True), f, y0, t, rtol, atol, max_attempts, forced_dts, log, on_attempt)
 
 
 # ---- the stochastic (SDE) sampler (vc_sde_plan / vc_sde_stage / vc_flux_sample_sde).  Time runs as in sample_ode: t = 0 noise, t = 1
@@ -1259,9 +1222,8 @@ def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max
     f = lambda tt, y: (calls.append(tt), drift(tt, y))[1]  # noqa: E731
     y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
     log = []
-    solve = dopri5_integrate if method == "dopri5" else partial(rk_integrate, method=method)
-    out = solve(f, y0, t.to(torch.float32), rtol=rtol, atol=atol, max_attempts=max_attempts, forced_dts=forced_dts, log=log,
-                on_attempt=on_attempt).to(x.dtype)
+    tab = _DOPRI5 if method == "dopri5" else _rk_tableau(method, solve=True)
+    out = _rk_integrate(tab, f, y0, t.to(torch.float32), rtol, atol, max_attempts, forced_dts, log, on_attempt).to(x.dtype)
     return (out if return_trajectory else out[-1:]), _log_dict(log, len(calls))
 
 
@@ -1338,11 +1300,9 @@ def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_at
     logs = []
 
     def run(xs, cond, tj, s):
-        try:
-            if method == "dopri5":
-                h.sample_dopri5(xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
-            else:
-                h.sample_rk(method, xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
+        try:                                       # (the C ABI keeps one route to Dormand-Prince: its own entry point)
+            solve = h.sample_dopri5 if method == "dopri5" else partial(h.sample_rk, method)
+            solve(xs, cond, t32, x.dtype == torch.bfloat16, s, rtol, atol, max_attempts, trajectory=tj)
         finally:
             logs.append(h.dopri5_log())            # one log serves both entry points: the last adaptive solve's
 
