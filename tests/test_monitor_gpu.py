@@ -157,6 +157,44 @@ def test_two_runs_and_both_load_paths_give_the_same_bits(cases):
     assert torch.equal(_stats(x.contiguous()), _stats(y))
 
 
+def _ordered_sum_sq(x: torch.Tensor) -> torch.Tensor:
+    """sum_sq [B] of a [B, rows, cols] tensor in the order the header states, through the host mirror: the f32 squares of each row
+    cut into units of E, a non-finite element's square replaced by zero (it is skipped; x + 0 = x for these non-negative terms)"""
+    from visualcloze_amd.reduction import ordered_sum
+    B, rows, cols = x.shape
+    E = 4 if x.dtype == torch.float32 else 8
+    upr = (cols + E - 1) // E
+    v = x.detach().cpu().to(torch.float32)
+    sq = torch.where(torch.isfinite(v), v * v, torch.zeros(()))
+    terms = torch.zeros(B, rows, upr * E, dtype=torch.float32)
+    terms[:, :, :cols] = sq
+    return torch.stack([ordered_sum(terms[b].reshape(rows * upr, E), max_blocks=256) for b in range(B)])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_sum_sq_has_the_bits_of_the_stated_order(dtype):
+    """vc_tensor_stats.sum_sq against reduction.ordered_sum, f32 bit for bit, B = 3 with different data per sample: a partial single
+    block, a second block that is nearly empty, a second round of the capped grid (one 16-byte unit per row), short units on the
+    element path (6 columns of rows 11 apart), and non-finite elements, which the sum skips."""
+    E = 4 if dtype == torch.float32 else 8
+    inf, nan = float("inf"), float("nan")
+    planted = _values((3, 1, 257 * E), dtype, 34)
+    planted[0, 0, 0], planted[0, 0, 5], planted[1, 0, 256 * E], planted[2, 0, 257 * E - 1], planted[2, 0, 300] = nan, inf, -inf, nan, inf
+    cases = [("9 units", _values((3, 1, 9 * E), dtype, 31).to(DEV)),
+             ("257 units", _values((3, 1, 257 * E), dtype, 32).to(DEV)),
+             ("256 * 256 + 8 units", _values((3, 256 * 256 + 8, E), dtype, 33).to(DEV)),
+             ("cols 6 of ld 11", _values((3, 300, 11), dtype, 35).to(DEV)[:, :, :6]),
+             ("257 units, non-finite planted", planted.to(DEV))]
+    from visualcloze_amd import hip
+    for name, x in cases:
+        rec = hip.stats_to_numpy(_stats(x))
+        got, want = torch.from_numpy(rec["sum_sq"].astype(np.float32)), _ordered_sum_sq(x)
+        worst = _check(rec, x, name)
+        print(f"tensor_stats {name} {dtype}: sum_sq {got.tolist()} mirror {want.tolist()}, {worst:.3f} of the fp64 budget")
+        assert torch.equal(got, want), (name, got, want)
+    assert int(hip.stats_to_numpy(_stats(cases[-1][1]))["nonfinite"].sum()) == 5
+
+
 def test_row_ptr_writes_its_row_and_nothing_else(cases):
     from visualcloze_amd import hip
     name, x = cases[1]

@@ -194,6 +194,34 @@ def test_kernels_against_torch(B, n):
     assert torch.equal(joint[:, 64:], (a.float() + b.float()).to(torch.bfloat16)) and torch.equal(joint[:, :64], before[:, :64])
 
 
+@pytest.mark.parametrize("n", [8, 257 * 8, (256 * 256 + 3) * 8], ids=["1 chunk", "257 chunks", "256 * 256 + 3 chunks"])
+def test_sums_have_the_bits_of_the_stated_order(n):
+    """Both sums of vc_residual_change against reduction.ordered_sum, f32 bit for bit: one chunk, a second block that is nearly
+    empty, a second round of the capped grid.  B = 3: pass 2 runs its tree three times over the same LDS.  The addends of a 16-byte
+    chunk, in order: |f32(r) - f32(P)| (and |f32(P)|) of its eight elements, r = bf16(h1 - h0).  The fp64 budget of
+    test_kernels_against_torch stands beside the bit comparison."""
+    from visualcloze_amd import hip
+    from visualcloze_amd.reduction import ordered_sum
+    B = 3
+    g = torch.Generator().manual_seed(77 + n % 997)
+    h0, h1, p = [(torch.randn(B, n, generator=g) * 3).to(DEV, torch.bfloat16) for _ in range(3)]
+    p[2] *= 0.01
+    r, sums, metric = hip.residual_change(h0, h1, p)
+    torch.cuda.synchronize()
+    want_r = (h1.float() - h0.float()).to(torch.bfloat16)
+    assert torch.equal(r, want_r)
+    rf, pf = want_r.float().cpu(), p.float().cpu()
+    t0, t1 = (rf - pf).abs().reshape(B, n // 8, 8), pf.abs().reshape(B, n // 8, 8)
+    want = torch.stack([torch.stack([ordered_sum(t[b], max_blocks=hip.RESIDUAL_CHANGE_MAX_BLOCKS) for t in (t0, t1)]) for b in range(B)])
+    s64 = torch.stack([t0.double().sum((1, 2)), t1.double().sum((1, 2))], 1)
+    tol = 1.01 * n * 2.0 ** -24
+    rel = ((sums.double().cpu() - s64).abs() / s64).max().item()
+    print(f"\nresidual_change B={B} n={n}: sums {sums.tolist()} mirror {want.tolist()}, rel err against fp64 {rel:.2e} (tolerance {tol:.2e})")
+    assert rel <= tol
+    assert torch.equal(sums.cpu(), want)
+    assert metric.item() == (sums[:, 0] / sums[:, 1]).max().item()          # the max of the f32 ratios, exactly
+
+
 def test_kernel_argument_errors():
     from visualcloze_amd import hip
     a = torch.zeros(2, 12, dtype=torch.bfloat16, device=DEV)

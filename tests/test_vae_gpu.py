@@ -96,6 +96,23 @@ def test_groupnorm_swish(hip, HW, C, swish):
     assert torch.equal(y, y2)                                            # deterministic reduction
 
 
+def test_groupnorm_repeats_its_bits_past_256_partial_blocks(hip):
+    """HW / 128 = 288 partial blocks: the finalize kernel's threads add more than one partial each before the tree (block_reduce.h).
+    C = 64 is the smallest channel count 32 groups take.  Two runs into poisoned outputs: the same statistics and the same y."""
+    HW, C = 384 * 96, 64
+    x = bf(ptensor((HW, C), 21, q=5) + 0.25)
+    g, b = bf(ptensor((C,), 4, q=8, kmax=64, offset=1.0)), bf(ptensor((C,), 5, q=8, kmax=32))
+    assert (HW + 127) // 128 > 256
+    runs = []
+    for fill in (0.0, float("nan")):
+        y = torch.full_like(x, fill)
+        sc = torch.full((hip.groupnorm_scratch_floats(HW),), fill, dtype=torch.float32, device=DEV)
+        hip.groupnorm(x, g, b, y, sc, swish=True)
+        torch.cuda.synchronize()
+        runs.append((y, sc[:64].clone()))
+    assert torch.isfinite(runs[0][1]).all() and torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][0], runs[1][0])
+
+
 @pytest.mark.parametrize("R,Cc", [(16, 16), (40, 24), (7, 2304), (3, 6912)])
 def test_softmax_rows(hip, R, Cc):
     x = bf(ptensor((R, Cc), 9, q=3))

@@ -1659,9 +1659,8 @@ int vc_attention64_launch(const VcAttention& A, const AttnPlan& pl, uint64_t* de
   a.inmerge = pl.inmerge;
   a.flags = pl.full_rounds >= 0 ? (uint32_t*)((char*)A.scratch + pl.flags_offset) : nullptr;
   static VcOncePerDevice done;
-  hipError_t e;
   if (done.need()) {
-    e = hipFuncSetAttribute((const void*)attn64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
+    hipError_t e = hipFuncSetAttribute((const void*)attn64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn64s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn64s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
@@ -1672,8 +1671,5 @@ int vc_attention64_launch(const VcAttention& A, const AttnPlan& pl, uint64_t* de
   void (*kern)(const Attn64Args) = stream ? (pl.bounded ? attn64s_kernel<true> : attn64s_kernel<false>) : pl.bounded ? attn64_kernel<true> : attn64_kernel<false>;
   hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), pl.lds, s, a);
   if (pl.merge_grid) hipLaunchKernelGGL(attn64_merge_kernel, dim3(pl.merge_grid), dim3(256), 0, s, a, pl.grid);
-  e = hipGetLastError();
-  if (e == hipSuccess) return VC_OK;
-  snprintf(err, errlen, "attention64 launch: %s", hipGetErrorString(e));
-  return VC_ERR_HIP;
+  return vc_launch_status("attention64 launch", err, errlen);
 }

@@ -212,22 +212,15 @@ __global__ void cfg_combine_kernel(const bf16_t* c, const bf16_t* u, bf16_t* out
 
 }  // namespace
 
-#define VC_CHECK_LAUNCH(name)                                                                     \
-  do {                                                                                            \
-    hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } \
-    return VC_OK;                                                                                 \
-  } while (0)
-
 int vc_temb_launch(const float* t, const float* freqs, void* out, int n, int half, int round_t, hipStream_t s, char* err, int errlen) {
   if (!t || !freqs || !out || n <= 0 || half <= 0) { snprintf(err, errlen, "timestep_embedding: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(temb_kernel, dim3((n * half + 255) / 256), dim3(256), 0, s, t, freqs, (bf16_t*)out, n, half, round_t);
-  VC_CHECK_LAUNCH("timestep_embedding");
+  return vc_launch_status("timestep_embedding launch", err, errlen);
 }
 int vc_silu_launch(const void* x, void* y, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!x || !y || n <= 0) { snprintf(err, errlen, "silu: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (long)n);
-  VC_CHECK_LAUNCH("silu");
+  return vc_launch_status("silu launch", err, errlen);
 }
 int vc_act2d_launch(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t cols, int32_t act, hipStream_t s,
                     char* err, int errlen) {
@@ -235,7 +228,7 @@ int vc_act2d_launch(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t ro
   const long n = (long)rows * cols;
   hipLaunchKernelGGL(act2d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x, (long)ldx, (bf16_t*)y,
                      (long)ldy, rows, cols, act);
-  VC_CHECK_LAUNCH("act2d");
+  return vc_launch_status("act2d launch", err, errlen);
 }
 int vc_gate_residual_launch(const void* y, int64_t ldy, const void* res, int64_t ldres, const void* gate, void* out, int64_t ldo,
                             int32_t rows, int32_t cols, const int32_t* step_ptr, int64_t gate_step_stride, hipStream_t s,
@@ -245,21 +238,21 @@ int vc_gate_residual_launch(const void* y, int64_t ldy, const void* res, int64_t
   hipLaunchKernelGGL(gate_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)y, (long)ldy,
                      (const bf16_t*)res, (long)ldres, (const bf16_t*)gate, (bf16_t*)out, (long)ldo, rows, cols, step_ptr,
                      (long)gate_step_stride);
-  VC_CHECK_LAUNCH("gate_residual");
+  return vc_launch_status("gate_residual launch", err, errlen);
 }
 int vc_add3_launch(const void* a, const void* b, const void* c, void* y, int64_t n, int64_t bn, int64_t cn, hipStream_t s, char* err, int errlen) {
   if (!a || !b || !y || n <= 0 || bn <= 0 || (c && cn <= 0)) { snprintf(err, errlen, "add3: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(add3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)c, (bf16_t*)y, (long)n, (long)bn, (long)(c ? cn : 1));
-  VC_CHECK_LAUNCH("add3");
+  return vc_launch_status("add3 launch", err, errlen);
 }
 int vc_concat_cols_launch(const void* x, int cx, const void* cond, int cc, void* out, int64_t rows, hipStream_t s, char* err, int errlen) {
   if (!x || !cond || !out || rows <= 0 || cx <= 0 || cc <= 0 || cx % 8 || cc % 8) { snprintf(err, errlen, "concat_cols: need cx, cc positive multiples of 8"); return VC_ERR_ARG; }
   const long n = rows * ((cx + cc) / 8);
   hipLaunchKernelGGL(concat_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)x, cx / 8, (const u32x4*)cond, cc / 8, (u32x4*)out, (long)rows);
-  VC_CHECK_LAUNCH("concat_cols");
+  return vc_launch_status("concat_cols launch", err, errlen);
 }
-// the one launch behind vc_euler_step, vc_euler_step_f32 and vc_ode_stage, which check their own arguments (`what` names the caller
-// in a launch error).  y_in may be null (the state alone is written), v may be null (y_in = bf16(y) alone, f32 state)
+// the one launch behind vc_euler_step, vc_euler_step_f32 and vc_ode_stage, which check their own arguments (`what`: the caller's
+// prefix of a launch error).  y_in may be null (the state alone is written), v may be null (y_in = bf16(y) alone, f32 state)
 int vc_ode_update_launch(const char* what, int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in,
                          const float* dts, const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
   // 16-byte accesses: every base 16-byte aligned and n a multiple of 8 (k2, k3 start n and 2n elements into k); else element-wise
@@ -273,18 +266,16 @@ int vc_ode_update_launch(const char* what, int method, int stage, void* y, int s
   if (state_is_bf16) { if (vec) VC_ODE_LAUNCH(false, 8); else VC_ODE_LAUNCH(false, 1); }
   else { if (vec) VC_ODE_LAUNCH(true, 8); else VC_ODE_LAUNCH(true, 1); }
 #undef VC_ODE_LAUNCH
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) { snprintf(err, errlen, "%s launch: %s", what, hipGetErrorString(he)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status(what, err, errlen);
 }
 int vc_euler_launch(void* x, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!x || !v || !dts || n <= 0) { snprintf(err, errlen, "euler_step: bad args"); return VC_ERR_ARG; }
-  return vc_ode_update_launch("euler_step", VC_SOLVER_EULER, 0, x, 1, v, nullptr, nullptr, dts, step_ptr, n, s, err, errlen);
+  return vc_ode_update_launch("euler_step launch", VC_SOLVER_EULER, 0, x, 1, v, nullptr, nullptr, dts, step_ptr, n, s, err, errlen);
 }
 int vc_euler_f32_launch(float* x32, void* shadow, const void* v, const float* dts, const int32_t* step_ptr, int64_t n, hipStream_t s,
                         char* err, int errlen) {
   if (!x32 || !shadow || (v && !dts) || n <= 0) { snprintf(err, errlen, "euler_step_f32: bad args"); return VC_ERR_ARG; }
-  return vc_ode_update_launch("euler_step_f32", VC_SOLVER_EULER, 0, x32, 0, v, nullptr, shadow, dts, step_ptr, n, s, err, errlen);
+  return vc_ode_update_launch("euler_step_f32 launch", VC_SOLVER_EULER, 0, x32, 0, v, nullptr, shadow, dts, step_ptr, n, s, err, errlen);
 }
 int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const void* v, void* k, void* y_in, const float* dts,
                         const int32_t* eval_ptr, int64_t n, hipStream_t s, char* err, int errlen) {
@@ -294,7 +285,7 @@ int vc_ode_stage_launch(int method, int stage, void* y, int state_is_bf16, const
     snprintf(err, errlen, "ode_stage: bad args");
     return VC_ERR_ARG;
   }
-  return vc_ode_update_launch("ode_stage", method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, s, err, errlen);
+  return vc_ode_update_launch("ode_stage launch", method, stage, y, state_is_bf16, v, k, y_in, dts, eval_ptr, n, s, err, errlen);
 }
 int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64_t n, float cfg_scale, hipStream_t s, char* err, int errlen) {
   if (!cond || !uncond || !out) { snprintf(err, errlen, "cfg_combine: null pointer"); return VC_ERR_ARG; }
@@ -312,21 +303,21 @@ int vc_cfg_combine_launch(const void* cond, const void* uncond, void* out, int64
   const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
   if (vec) hipLaunchKernelGGL(cfg_combine_kernel<8>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
   else hipLaunchKernelGGL(cfg_combine_kernel<1>, grid, block, 0, s, (const bf16_t*)cond, (const bf16_t*)uncond, (bf16_t*)out, cfg_scale, (long)n);
-  VC_CHECK_LAUNCH("cfg_combine");
+  return vc_launch_status("cfg_combine launch", err, errlen);
 }
 int vc_fill_bf16_launch(void* p, float value, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!p || n <= 0) { snprintf(err, errlen, "fill_bf16: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(fill_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)p, value, (long)n);
-  VC_CHECK_LAUNCH("fill_bf16");
+  return vc_launch_status("fill_bf16 launch", err, errlen);
 }
 int vc_step_advance_launch(int32_t* step_ptr, hipStream_t s, char* err, int errlen) {
   if (!step_ptr) { snprintf(err, errlen, "step_advance: null"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, s, step_ptr);
-  VC_CHECK_LAUNCH("step_advance");
+  return vc_launch_status("step_advance launch", err, errlen);
 }
 int vc_sdedit_mix_launch(const void* noise, const void* latent, double strength, void* out, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!noise || !latent || !out || n <= 0) { snprintf(err, errlen, "sdedit_mix: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(sdedit_mix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)noise, (const bf16_t*)latent,
                      (float)(1.0 - strength), (float)strength, (bf16_t*)out, (long)n);
-  VC_CHECK_LAUNCH("sdedit_mix");
+  return vc_launch_status("sdedit_mix launch", err, errlen);
 }

@@ -523,7 +523,7 @@ int ode_update(Flux& f, const void* v, const int32_t* step_ptr, hipStream_t s, c
                               e.len);
   void* y = ode_state(f);
   bf16_t* y_in = next_input(f);
-  return vc_ode_update_launch("ode_update", f.traj.method, -1, y, !f.traj.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
+  return vc_ode_update_launch("ode_update launch", f.traj.method, -1, y, !f.traj.state_f32, v, f.KS, y_in == y ? nullptr : y_in, f.DTS, step_ptr,
                               (int64_t)f.B * f.N * f.cfg.out_channels, s, e.buf, e.len);
 }
 

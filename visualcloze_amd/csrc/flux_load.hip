@@ -35,7 +35,5 @@ int vc_scale_cast_launch(const VcScaleVectors& v, int n, void* out, int64_t out_
   for (int i = 0; i < n; ++i)
     if (!v.src[i]) { snprintf(err, errlen, "scale_cast: null vector %d", i); return VC_ERR_ARG; }
   hipLaunchKernelGGL(scale_cast_kernel, dim3(n), dim3(128), 0, s, v, (bf16_t*)out, out_stride, amax);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(err, errlen, "scale_cast: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("scale_cast", err, errlen);
 }

@@ -6,22 +6,19 @@
 //             them are the caller's);  u_t = x1 - x0 -> f32.  x0 is a tensor, or drawn in place from THE STREAM (rng_device.h): no
 //             draw launch, no stored x0.  f32 arithmetic, one operation after the other, no fused multiply-add.
 //   fm_loss   loss[b] = sum over the first valid[b] rows and all cols of ((-out) - u_t)^2 / (valid[b] * cols), summed in f32 in the
-//             FIXED ORDER of vc_tensor_stats (monitor.hip): a row is cut into units of 8 consecutive elements (the last unit of a row
-//             is shorter where cols % 8 != 0), the units of the sample's VALID rows, numbered row by row, are dealt round-robin to
-//             the nblk * 256 threads of its nblk = min(ceil(rows * upr / 256), VC_FM_LOSS_MAX_BLOCKS) blocks (nblk from ALL rows:
-//             one grid serves every sample), a thread adds its elements in ascending order, s = s + d * d with the product rounded
-//             on its own; the block's 256 sums go through an LDS tree (l[t] += l[t + o], o = 128 .. 1: neighbouring threads read
-//             neighbouring words, no bank conflict), the sample's nblk block sums through the same tree.  No atomics: repeated
-//             runs give the same bits, and so do the 16-byte and the element-wise path.
+//             FIXED ORDER of block_reduce.h, over the units of vc_tensor_stats (monitor.hip): a row is cut into units of 8
+//             consecutive elements (the last unit of a row is shorter where cols % 8 != 0); the units of the sample's VALID rows,
+//             numbered row by row, are the ones summed, while nblk comes from ALL rows (one grid serves every sample); a thread
+//             adds s = s + d * d with the product rounded on its own.  The 16-byte and the element-wise path give the same bits.
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 #include "rng_device.h"
 
 namespace {
 
 constexpr int FM_THREADS = 256;
 constexpr int FM_PLAN_MAX_BLOCKS = 2048;      // 8 workgroups of 256 per CU of a 256-CU device; the grid-stride loop takes the rest
-static_assert(FM_THREADS == VC_FM_LOSS_MAX_BLOCKS, "pass 2 holds one block partial per thread");
 
 struct FmPair { float xt, ut; };
 // one element, f32, one operation after the other: t * x1.float() + (1 - t) * x0.float() and x1.float() - x0.float() in torch
@@ -115,18 +112,6 @@ VC_DEV long fm_valid(const FmCounts& hc, const int* __restrict__ dev, int b, lon
   return v < 0 ? 0 : v > rows ? rows : v;          // a device count outside [0, rows] reads nothing outside the sample
 }
 
-VC_DEV float fm_tree(float (&l)[FM_THREADS], float s) {
-  const int t = threadIdx.x;
-  l[t] = s;
-  __syncthreads();
-#pragma unroll
-  for (int o = FM_THREADS / 2; o >= 1; o >>= 1) {
-    if (t < o) l[t] += l[t + o];
-    __syncthreads();
-  }
-  return l[0];
-}
-
 VC_DEV void fm_take(float& s, float o, float u) {
 #pragma clang fp contract(off)
   const float d = (0.0f - o) - u;      // (-out) - u_t: the negation is exact
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(FM_THREADS) void fm_loss_kernel(const bf16_t* __res
       for (int i = 0; i < n; ++i) fm_take(s, bf2f(out[oo + i]), ut[uo + i]);
     }
   }
-  s = fm_tree(l, s);
+  s = block_tree(l, s, VcAddOp());
   if (threadIdx.x == 0) partial[(long)b * nblk + blockIdx.x] = s;
 }
 
@@ -172,16 +157,9 @@ __global__ __launch_bounds__(FM_THREADS) void fm_loss_finish_kernel(const float*
                                                                     const int* __restrict__ valid_dev, long rows, int cols, float* __restrict__ loss) {
   __shared__ float l[FM_THREADS];
   const int b = blockIdx.x;
-  const float total = fm_tree(l, (int)threadIdx.x < nblk ? partial[(long)b * nblk + threadIdx.x] : 0.0f);
+  const float total = block_tree(l, (int)threadIdx.x < nblk ? partial[(long)b * nblk + threadIdx.x] : 0.0f, VcAddOp());
   if (threadIdx.x == 0) loss[b] = total / (float)(fm_valid(hc, valid_dev, b, rows) * (long)cols);
 }
-
-#define FM_LAUNCHED(name)                                                                                           \
-  {                                                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                                              \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }  \
-  }                                                                                                                 \
-  return VC_OK;
 
 template <bool F32, bool VEC>
 void fm_plan_issue(bool draw, int grid, hipStream_t s, const void* x1, long x1_bstride, long x1_ld, const float* t, const void* x0, uint64_t seed,
@@ -227,7 +205,7 @@ int vc_fm_plan_launch(const void* x1, int x1_is_f32, int64_t x1_bstride, int64_t
   if (x1_is_f32) { if (vec) fm_plan_issue<true, true>(FM_PLAN_ARGS); else fm_plan_issue<true, false>(FM_PLAN_ARGS); }
   else { if (vec) fm_plan_issue<false, true>(FM_PLAN_ARGS); else fm_plan_issue<false, false>(FM_PLAN_ARGS); }
 #undef FM_PLAN_ARGS
-  FM_LAUNCHED("fm_plan")
+  return vc_launch_status("fm_plan launch", err, errlen);
 }
 
 int vc_fm_loss_launch(const void* out, int64_t out_ld, const float* ut, const int32_t* valid_rows, int valid_on_host, float* loss, float* scratch,
@@ -263,10 +241,9 @@ int vc_fm_loss_launch(const void* out, int64_t out_ld, const float* ut, const in
   }
   const int* dev = valid_rows && !valid_on_host ? valid_rows : nullptr;
   const bool vec = cols % 8 == 0 && out_ld % 8 == 0 && !(((uintptr_t)out | (uintptr_t)ut) & 15);
-  const int64_t want = (units + FM_THREADS - 1) / FM_THREADS;
-  const int nblk = (int)(want < VC_FM_LOSS_MAX_BLOCKS ? want : VC_FM_LOSS_MAX_BLOCKS);
+  const int nblk = vc_reduce_blocks<FM_THREADS, VC_FM_LOSS_MAX_BLOCKS>(units);
   if (vec) hipLaunchKernelGGL(fm_loss_kernel<true>, dim3(nblk, B), dim3(FM_THREADS), 0, s, (const bf16_t*)out, (long)out_ld, ut, hc, dev, (long)rows, cols, (uint32_t)upr, scratch);
   else hipLaunchKernelGGL(fm_loss_kernel<false>, dim3(nblk, B), dim3(FM_THREADS), 0, s, (const bf16_t*)out, (long)out_ld, ut, hc, dev, (long)rows, cols, (uint32_t)upr, scratch);
   hipLaunchKernelGGL(fm_loss_finish_kernel, dim3(B), dim3(FM_THREADS), 0, s, (const float*)scratch, nblk, hc, dev, (long)rows, cols, loss);
-  FM_LAUNCHED("fm_loss")
+  return vc_launch_status("fm_loss launch", err, errlen);
 }

@@ -11,8 +11,10 @@
 // words of one row in every pass (ds_read_b32 / ds_write_b32 bank by word % 32 per 32-lane half): no bank conflict at any stride.
 // Memory-bound and small beside a model evaluation: NOT tuned beyond that (one channel per workgroup re-reads the interleaved
 // 8-bit rows three times, from L2).
+#include <type_traits>
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 #include "image_tiling.h"
 
 namespace {
@@ -93,20 +95,17 @@ VC_DEV float ssim_of(float mu_a, float mu_b, float e_aa, float e_bb, float e_ab,
   return num / den;
 }
 
-template <typename T, typename Op>
-VC_DEV T img_tree(T (&l)[IMG_THREADS], T v, Op op) {
-  const int t = threadIdx.x;
-  l[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = IMG_THREADS / 2; o >= 1; o >>= 1) {
-    if (t < o) l[t] = op(l[t], l[t + o]);
-    __syncthreads();
-  }
-  return l[0];
-}
-struct AddOp { template <typename T> VC_DEV T operator()(T x, T y) const { return x + y; } };
 struct MaxOp { VC_DEV float operator()(float x, float y) const { return y > x ? y : x; } };
+// a tile's sums go down ONE tree (block_reduce.h), field by field; `sse` is the integer sum for 8-bit images, the float one otherwise
+template <bool U8> struct TileAcc { float ssim, mx; uint32_t nd; std::conditional_t<U8, uint32_t, float> sse; };
+struct TileOp {
+  template <typename A> VC_DEV A operator()(A x, A y) const { return A{x.ssim + y.ssim, MaxOp()(x.mx, y.mx), x.nd + y.nd, x.sse + y.sse}; }
+};
+// the finish kernel's 8-byte fields; max_abs keeps a tree of its own
+struct ImgTotals { double ssim, sse_f; uint64_t sse_u, nd; };
+struct TotalsOp {
+  VC_DEV ImgTotals operator()(ImgTotals x, ImgTotals y) const { return ImgTotals{x.ssim + y.ssim, x.sse_f + y.sse_f, x.sse_u + y.sse_u, x.nd + y.nd}; }
+};
 
 // grid (TX, TY, C)
 template <bool U8, bool WIDE>
@@ -115,8 +114,7 @@ __global__ __launch_bounds__(IMG_THREADS) void image_tile_kernel(const void* __r
 #pragma clang fp contract(off)
   __shared__ float ha[HALO][HS], hb[HALO][HS];
   __shared__ float pl[5][HALO][TILE];
-  __shared__ float lf[IMG_THREADS], lg[IMG_THREADS], lm[IMG_THREADS];
-  __shared__ uint32_t lu[IMG_THREADS], ln[IMG_THREADS];
+  __shared__ TileAcc<U8> lt[IMG_THREADS];
   const int t = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y, c = blockIdx.z;
   const int y0 = ty * TILE, x0 = tx * TILE;
   load_halo<U8, WIDE>(a, ha, c, C, H, W, y0, x0);
@@ -186,16 +184,17 @@ __global__ __launch_bounds__(IMG_THREADS) void image_tile_kernel(const void* __r
     }
   }
 
-  const float tile_ssim = img_tree(lf, ssim, AddOp());
-  const float tile_mx = img_tree(lm, mx, MaxOp());
-  const uint32_t tile_nd = img_tree(ln, nd, AddOp());
-  float tile_sse_f = 0.0f;
-  uint32_t tile_sse_u = 0u;
-  if constexpr (U8) tile_sse_u = img_tree(lu, sse_u, AddOp());
-  else tile_sse_f = img_tree(lg, sse_f, AddOp());
+  TileAcc<U8> acc;
+  acc.ssim = ssim; acc.mx = mx; acc.nd = nd;
+  if constexpr (U8) acc.sse = sse_u;
+  else acc.sse = sse_f;
+  acc = block_tree(lt, acc, TileOp());
   if (t == 0) {
     ImgRecord o;
-    o.sse_u = tile_sse_u; o.ssim = tile_ssim; o.sse_f = tile_sse_f; o.max_abs = tile_mx; o.n_diff = tile_nd; o.pad[0] = 0u; o.pad[1] = 0u;
+    o.sse_u = 0; o.sse_f = 0.0f;
+    if constexpr (U8) o.sse_u = acc.sse;
+    else o.sse_f = acc.sse;
+    o.ssim = acc.ssim; o.max_abs = acc.mx; o.n_diff = acc.nd; o.pad[0] = 0u; o.pad[1] = 0u;
     rec[((long)c * gridDim.y + ty) * gridDim.x + tx] = o;
   }
 }
@@ -203,8 +202,7 @@ __global__ __launch_bounds__(IMG_THREADS) void image_tile_kernel(const void* __r
 // one workgroup: thread t folds records t, t + 256, .. in ascending order, then the tree
 __global__ __launch_bounds__(IMG_THREADS) void image_finish_kernel(const ImgRecord* __restrict__ rec, long P, uint64_t n, uint64_t n_windows, int form,
                                                                     VcImageMetrics* __restrict__ out) {
-  __shared__ double ls[IMG_THREADS], lq[IMG_THREADS];
-  __shared__ uint64_t lu[IMG_THREADS], ln[IMG_THREADS];
+  __shared__ ImgTotals lt[IMG_THREADS];
   __shared__ float lm[IMG_THREADS];
   double ssim = 0.0, sse_f = 0.0;
   uint64_t sse_u = 0, nd = 0;
@@ -217,17 +215,14 @@ __global__ __launch_bounds__(IMG_THREADS) void image_finish_kernel(const ImgReco
     nd += r.n_diff;
     mx = r.max_abs > mx ? r.max_abs : mx;
   }
-  ssim = img_tree(ls, ssim, AddOp());
-  sse_f = img_tree(lq, sse_f, AddOp());
-  sse_u = img_tree(lu, sse_u, AddOp());
-  nd = img_tree(ln, nd, AddOp());
-  mx = img_tree(lm, mx, MaxOp());
+  const ImgTotals tot = block_tree(lt, ImgTotals{ssim, sse_f, sse_u, nd}, TotalsOp());
+  mx = block_tree(lm, mx, MaxOp());
   if (threadIdx.x == 0) {
     VcImageMetrics m;
-    m.n = n; m.n_windows = n_windows; m.sse_u64 = sse_u; m.n_diff = nd;
-    m.sse_f32 = form == VC_IMG_U8_HWC ? (float)sse_u : (float)sse_f;
+    m.n = n; m.n_windows = n_windows; m.sse_u64 = tot.sse_u; m.n_diff = tot.nd;
+    m.sse_f32 = form == VC_IMG_U8_HWC ? (float)tot.sse_u : (float)tot.sse_f;
     m.max_abs = mx;
-    m.ssim_mean = (float)(ssim / (double)n_windows);
+    m.ssim_mean = (float)(tot.ssim / (double)n_windows);
     m.form = form;
     *out = m;
   }
@@ -283,9 +278,7 @@ int vc_image_compare_launch(const void* a, const void* b, int form, int C, int H
 #undef VC_IMG_LAUNCH
   const uint64_t n = (uint64_t)C * (uint64_t)H * (uint64_t)W, nw = (uint64_t)C * (uint64_t)(H - TAPS + 1) * (uint64_t)(W - TAPS + 1);
   hipLaunchKernelGGL(image_finish_kernel, dim3(1), block, 0, s, (const ImgRecord*)rec, P, n, nw, form, out_dev);
-  const hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "image_compare launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("image_compare launch", err, errlen);
 }
 
 int vc_image_psnr_impl(const VcImageMetrics* m, double* psnr_db, char* err, int errlen) {

@@ -280,14 +280,13 @@ int vc_lora_merge_qkv_launch(const void* w, int32_t w_is_f32, int64_t ldw, const
     attr_done[slot].mark();
   }
   hipLaunchKernelGGL(fn, dim3(strips, (O + rows - 1) / rows), dim3(LM_THREADS), lds, s, p);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && bias_out) {
+  int rc = vc_launch_status("lora_merge", err, errlen);
+  if (rc == VC_OK && bias_out) {
     hipLaunchKernelGGL(lora_bias_kernel, dim3((O + 255) / 256), dim3(256), 0, s, bias, bias_is_f32, (const bf16_t*)lora_b_bias, scale,
                        (bf16_t*)bias_out, O, p.qd);
-    e = hipGetLastError();
+    rc = vc_launch_status("lora_merge", err, errlen);
   }
-  if (e != hipSuccess) { snprintf(err, errlen, "lora_merge: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
-  return VC_OK;
+  return rc;
 }
 
 int vc_lora_merge_launch(const void* w, int32_t w_is_f32, int64_t ldw, const void* lora_a, int64_t lda, const void* lora_b, int64_t ldb,

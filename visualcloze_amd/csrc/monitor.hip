@@ -2,27 +2,24 @@
 // of non-finite elements, the number of elements, max |x| and sum x^2 over the finite ones.  A read-once streaming pass: HBM-bound,
 // 16-byte loads where the geometry allows, a capped grid.  There is no reference for it - the reference has no such check.
 //
-// The order of the sum (include/vcloze_hip.h states it too).  A row is cut into UNITS of E consecutive elements (E = 8 for bf16, 4 for
-// f32 - 16 bytes; the last unit of a row is shorter where cols % E != 0); the sample's units are numbered row by row and dealt
-// round-robin to the nblk * 256 threads of the sample's nblk = min(ceil(units / 256), VC_MONITOR_MAX_BLOCKS) blocks: thread t of block
-// k takes units k * 256 + t, + nblk * 256, ...  A thread adds its elements in ascending order, s = s + x * x with the product
-// rounded to f32 on its own (no fused multiply-add), a non-finite x skipped; the block's 256 sums go through an LDS tree (l[t] +=
-// l[t + o], o = 128, 64, .., 1); the sample's nblk block sums go through the same tree (thread t holds block t's, 0 for t >= nblk).
-// No atomics: a repeated run gives the same bits, and the 16-byte and the element-wise path - the same units, loaded differently -
-// give the same bits too.  max |x| and the two counts do not depend on any order.
+// The order of the sum (include/vcloze_hip.h states it too) is the two-pass reduction of block_reduce.h.  A row is cut into UNITS of
+// E consecutive elements (E = 8 for bf16, 4 for f32 - 16 bytes; the last unit of a row is shorter where cols % E != 0), numbered row
+// by row.  A thread adds s = s + x * x with the product rounded to f32 on its own (no fused multiply-add), a non-finite x skipped.
+// The 16-byte and the element-wise path - the same units, loaded differently - give the same bits.  max |x| and the two counts do
+// not depend on any order.
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 #include "monitor_sites.h"
 
 namespace {
 
 constexpr int MON_THREADS = 256;                      // = VC_MONITOR_MAX_BLOCKS: pass 2 reduces one partial per thread
-static_assert(MON_THREADS == VC_MONITOR_MAX_BLOCKS, "pass 2 holds one block partial per thread");
 static_assert(sizeof(VcStat) == 16, "a VcStat is one 16-byte store");
 
-struct Acc {
-  float mx = 0.0f, ss = 0.0f;
-  uint32_t bad = 0, cnt = 0;
+struct Acc { float mx, ss; uint32_t bad, cnt; };      // (no initialisers: it lives in LDS too)
+struct AccOp {
+  VC_DEV Acc operator()(Acc x, Acc y) const { return Acc{fmaxf(x.mx, y.mx), x.ss + y.ss, x.bad + y.bad, x.cnt + y.cnt}; }
 };
 VC_DEV void take(Acc& a, float v) {
 #pragma clang fp contract(off)
@@ -33,31 +30,14 @@ VC_DEV void take(Acc& a, float v) {
   a.ss = a.ss + sq;
 }
 
-// the block's 256 accumulators -> thread 0 (every thread returns it), always the same tree
-VC_DEV Acc block_tree(float (&lm)[MON_THREADS], float (&ls)[MON_THREADS], uint32_t (&lb)[MON_THREADS], uint32_t (&lc)[MON_THREADS], Acc a) {
-  const int t = threadIdx.x;
-  lm[t] = a.mx; ls[t] = a.ss; lb[t] = a.bad; lc[t] = a.cnt;
-  __syncthreads();
-#pragma unroll
-  for (int o = MON_THREADS / 2; o >= 1; o >>= 1) {
-    if (t < o) { lm[t] = fmaxf(lm[t], lm[t + o]); ls[t] += ls[t + o]; lb[t] += lb[t + o]; lc[t] += lc[t + o]; }
-    __syncthreads();
-  }
-  Acc r;
-  r.mx = lm[0]; r.ss = ls[0]; r.bad = lb[0]; r.cnt = lc[0];
-  __syncthreads();
-  return r;
-}
-
 // pass 1: grid (nblk, B).  VEC: every unit is one aligned 16-byte load (cols % E == 0, the strides and the base allow it)
 template <bool F32, bool VEC>
 __global__ __launch_bounds__(MON_THREADS) void tensor_stats_kernel(const void* __restrict__ x, long bstride, long ld, int cols, uint32_t upr,
                                                                    uint32_t units, uint32_t* __restrict__ partial) {
   constexpr int E = F32 ? 4 : 8;
-  __shared__ float lm[MON_THREADS], ls[MON_THREADS];
-  __shared__ uint32_t lb[MON_THREADS], lc[MON_THREADS];
+  __shared__ Acc l[MON_THREADS];
   const uint32_t nblk = gridDim.x, b = blockIdx.y;
-  Acc a;
+  Acc a = {0.0f, 0.0f, 0u, 0u};
   for (uint64_t u64 = (uint64_t)blockIdx.x * MON_THREADS + threadIdx.x; u64 < units; u64 += (uint64_t)nblk * MON_THREADS) {
     const uint32_t u = (uint32_t)u64, row = u / upr, c0 = (u - row * upr) * E;
     const long off = (long)b * bstride + (long)row * ld + c0;
@@ -74,7 +54,7 @@ __global__ __launch_bounds__(MON_THREADS) void tensor_stats_kernel(const void* _
       for (int i = 0; i < n; ++i) take(a, F32 ? ((const float*)x)[off + i] : bf2f(((const bf16_t*)x)[off + i]));
     }
   }
-  a = block_tree(lm, ls, lb, lc, a);
+  a = block_tree(l, a, AccOp());
   if (threadIdx.x == 0) {
     uint32_t* p = partial + ((long)b * nblk + blockIdx.x) * 4;
     p[0] = __builtin_bit_cast(uint32_t, a.mx); p[1] = __builtin_bit_cast(uint32_t, a.ss); p[2] = a.bad; p[3] = a.cnt;
@@ -85,15 +65,14 @@ __global__ __launch_bounds__(MON_THREADS) void tensor_stats_kernel(const void* _
 // [0, capacity) writes nothing
 __global__ __launch_bounds__(MON_THREADS) void tensor_stats_finish_kernel(const uint32_t* __restrict__ partial, int nblk, u32x4* __restrict__ out,
                                                                           long out_stride, const int* __restrict__ row_ptr, int capacity) {
-  __shared__ float lm[MON_THREADS], ls[MON_THREADS];
-  __shared__ uint32_t lb[MON_THREADS], lc[MON_THREADS];
+  __shared__ Acc l[MON_THREADS];
   const int b = blockIdx.x;
-  Acc a;
+  Acc a = {0.0f, 0.0f, 0u, 0u};
   if ((int)threadIdx.x < nblk) {
     const uint32_t* p = partial + ((long)b * nblk + threadIdx.x) * 4;
     a.mx = __builtin_bit_cast(float, p[0]); a.ss = __builtin_bit_cast(float, p[1]); a.bad = p[2]; a.cnt = p[3];
   }
-  a = block_tree(lm, ls, lb, lc, a);
+  a = block_tree(l, a, AccOp());
   if (threadIdx.x != 0) return;
   const int row = row_ptr ? *row_ptr : 0;
   if (row < 0 || row >= capacity) return;
@@ -113,14 +92,8 @@ __global__ __launch_bounds__(MON_THREADS) void first_bad_kernel(const u32x4* __r
     const int b = i % B, site = i / B % n_sites, ev = i / B / n_sites;
     first = min(first, (ev * n_sites + vcmon::site_rank(site, n_sites)) * B + b);
   }
-  l[threadIdx.x] = first;
-  __syncthreads();
-#pragma unroll
-  for (int o = MON_THREADS / 2; o >= 1; o >>= 1) {
-    if ((int)threadIdx.x < o) l[threadIdx.x] = min(l[threadIdx.x], l[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = l[0] == 0x7fffffff ? -1 : l[0];
+  first = block_tree(l, first, [](int x, int y) { return min(x, y); });
+  if (threadIdx.x == 0) out[0] = first == 0x7fffffff ? -1 : first;
 }
 
 }  // namespace
@@ -144,23 +117,18 @@ int vc_tensor_stats_launch(const void* x, int x_is_f32, int64_t bstride, int64_t
     return VC_ERR_ARG;
   }
   const bool vec = cols % E == 0 && ld % E == 0 && bstride % E == 0 && ((uintptr_t)x & 15) == 0;
-  const int64_t want = (units + MON_THREADS - 1) / MON_THREADS;
-  const int nblk = (int)(want < VC_MONITOR_MAX_BLOCKS ? want : VC_MONITOR_MAX_BLOCKS);
+  const int nblk = vc_reduce_blocks<MON_THREADS, VC_MONITOR_MAX_BLOCKS>(units);
   auto kernel = x_is_f32 ? (vec ? tensor_stats_kernel<true, true> : tensor_stats_kernel<true, false>)
                          : (vec ? tensor_stats_kernel<false, true> : tensor_stats_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(nblk, B), dim3(MON_THREADS), 0, s, x, (long)bstride, (long)ld, cols, (uint32_t)upr, (uint32_t)units,
                      (uint32_t*)scratch);
   hipLaunchKernelGGL(tensor_stats_finish_kernel, dim3(B), dim3(MON_THREADS), 0, s, (const uint32_t*)scratch, nblk, (u32x4*)out, (long)out_stride,
                      (const int*)row_ptr, capacity);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "tensor_stats launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("tensor_stats launch", err, errlen);
 }
 
 int vc_monitor_first_bad_launch(const VcStat* log, int64_t n, int n_sites, int B, int32_t* out, hipStream_t s, char* err, int errlen) {
   if (!log || !out || n_sites < 2 || B <= 0 || n <= 0 || n > 0x7fffffff || ((uintptr_t)log & 15)) { snprintf(err, errlen, "monitor_first_bad: bad args"); return VC_ERR_ARG; }
   hipLaunchKernelGGL(first_bad_kernel, dim3(1), dim3(MON_THREADS), 0, s, (const u32x4*)log, (int)n, n_sites, B, (int*)out);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "monitor_first_bad launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("monitor_first_bad launch", err, errlen);
 }

@@ -160,7 +160,5 @@ int vc_ms_stage_launch(int eval, const float* table, int n_rows, float* y, const
   const long nvec = vec ? (long)(n / 8) : 0;
   hipLaunchKernelGGL(ms_stage_kernel, dim3(grid_for(nvec + (n - nvec * 8))), dim3(256), 0, s, eval, table, n_rows, y, (const bf16_t*)v,
                      (bf16_t*)hist, (bf16_t*)y_in, (const int*)eval_ptr, (long)n, nvec);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "ms_stage launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("ms_stage launch", err, errlen);
 }

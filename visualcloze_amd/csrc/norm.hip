@@ -214,9 +214,7 @@ int vc_ln_modulate2_launch(const VcLnStream* a, const VcLnStream* b, int64_t mod
     hipLaunchKernelGGL(ln_modulate_kernel<8>, grid, block, 0, s, (const bf16_t*)a->x, (long)a->ldx, (bf16_t*)a->y, (long)a->ldy,
                        (const bf16_t*)a->shift, (const bf16_t*)a->scale, (long)mod_bstride, a->rows, D, a->rows_per_batch,
                        step_ptr, (long)mod_step_stride, second);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(err, errlen, "ln_modulate launch: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("ln_modulate launch", err, errlen);
 }
 
 int vc_ln_modulate_launch(const void* x, int64_t ldx, void* y, int64_t ldy, const void* shift, const void* scale,
@@ -241,16 +239,12 @@ int vc_qknorm_rope_vt_launch(void* qkv, int64_t ld, int64_t bstride, const void*
     hipLaunchKernelGGL(qknorm_rope_rows_kernel<HG>, dim3((L + 15) / 16, (H + HG - 1) / HG, B), dim3(256), 0, s, (bf16_t*)qkv, (long)ld,
                        (long)bstride, (const bf16_t*)q_scale, (const bf16_t*)k_scale, (const bf16_t*)q_scale2, (const bf16_t*)k_scale2,
                        split, rope, (long)rope_bstride, L, H, parts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(err, errlen, "qknorm_rope rows launch: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
-    return VC_OK;
+    return vc_launch_status("qknorm_rope rows launch", err, errlen);
   }
 #endif
   const dim3 grid((L + 63) / 64, H, B), block(256);
   hipLaunchKernelGGL(qknorm_rope_vt_kernel, grid, block, 0, s, (bf16_t*)qkv, (long)ld, (long)bstride,
                      (const bf16_t*)q_scale, (const bf16_t*)k_scale, (const bf16_t*)q_scale2, (const bf16_t*)k_scale2, split,
                      rope, (long)rope_bstride, (bf16_t*)vt, L, Lpad, H, parts);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(err, errlen, "qknorm_rope_vt launch: %s", hipGetErrorString(e)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("qknorm_rope_vt launch", err, errlen);
 }

@@ -84,28 +84,22 @@ __global__ __launch_bounds__(256) void pack_mask_kernel(const bf16_t* __restrict
 
 }  // namespace
 
-#define PK_LAUNCH(name, kern, grid, lds_bytes, ...)                                                 \
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, __VA_ARGS__);                             \
-  {                                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                              \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } \
-  }                                                                                                 \
-  return VC_OK;
-
 int vc_pack_latent_launch(const void* in, void* out, int C, int h, int w, int64_t ld, int col0, hipStream_t s, char* err, int errlen) {
   if (!in || !out || C <= 0 || h <= 0 || w <= 0 || (C & 1) || (h & 1) || (w & 1) || ld % 8 || col0 % 8) {
     snprintf(err, errlen, "pack_latent: need even C, h, w and 16-B aligned ld / col0 (C=%d h=%d w=%d)", C, h, w); return VC_ERR_ARG; }
   if (C > 64) { snprintf(err, errlen, "pack_latent: C=%d > 64 channels", C); return VC_ERR_ARG; }
   if (((uintptr_t)out & 15) || ((uintptr_t)in & 3)) {   // 16-B vector stores on the token side, 4-B words on the map side
     snprintf(err, errlen, "pack_latent: the token rows must be 16-byte aligned and the latent 4-byte aligned"); return VC_ERR_ARG; }
-  PK_LAUNCH("pack_latent", pack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), (size_t)C * 2 * LDW * 4, (const bf16_t*)in, (bf16_t*)out, C, h, w, (long)ld, col0)
+  hipLaunchKernelGGL(pack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), dim3(256), (size_t)C * 2 * LDW * 4, s, (const bf16_t*)in, (bf16_t*)out, C, h, w, (long)ld, col0);
+  return vc_launch_status("pack_latent launch", err, errlen);
 }
 int vc_pack_mask_launch(const void* in, void* out, int H, int W, int64_t ld, int col0, hipStream_t s, char* err, int errlen) {
   if (!in || !out || H <= 0 || W <= 0 || H % 16 || W % 16 || ld % 8 || col0 % 8) {
     snprintf(err, errlen, "pack_mask: H, W must be positive multiples of 16 (H=%d W=%d)", H, W); return VC_ERR_ARG; }
   if (((uintptr_t)in | (uintptr_t)out) & 15) {     // the kernel reads the mask and writes the tokens in 16-B vectors (advisor r04)
     snprintf(err, errlen, "pack_mask: the mask and the token rows must be 16-byte aligned"); return VC_ERR_ARG; }
-  PK_LAUNCH("pack_mask", pack_mask_kernel, dim3((W / 16 + TWM - 1) / TWM, H / 16), 0, (const bf16_t*)in, (bf16_t*)out, H, W, (long)ld, col0)
+  hipLaunchKernelGGL(pack_mask_kernel, dim3((W / 16 + TWM - 1) / TWM, H / 16), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, H, W, (long)ld, col0);
+  return vc_launch_status("pack_mask launch", err, errlen);
 }
 int vc_unpack_latent_launch(const void* in, int64_t ld, int col0, void* out, int C, int h, int w, hipStream_t s, char* err, int errlen) {
   if (!in || !out || C <= 0 || h <= 0 || w <= 0 || (C & 1) || (h & 1) || (w & 1) || ld % 8 || col0 % 8) {
@@ -113,5 +107,6 @@ int vc_unpack_latent_launch(const void* in, int64_t ld, int col0, void* out, int
   if (C > 64) { snprintf(err, errlen, "unpack_latent: C=%d > 64 channels", C); return VC_ERR_ARG; }
   if (((uintptr_t)in & 15) || ((uintptr_t)out & 3)) {   // 16-B vector loads on the token side, 4-B words on the map side
     snprintf(err, errlen, "unpack_latent: the token rows must be 16-byte aligned and the latent 4-byte aligned"); return VC_ERR_ARG; }
-  PK_LAUNCH("unpack_latent", unpack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), (size_t)C * 2 * LDW * 4, (const bf16_t*)in, (long)ld, col0, (bf16_t*)out, C, h, w)
+  hipLaunchKernelGGL(unpack_latent_kernel, dim3((w / 2 + TW - 1) / TW, h / 2), dim3(256), (size_t)C * 2 * LDW * 4, s, (const bf16_t*)in, (long)ld, col0, (bf16_t*)out, C, h, w);
+  return vc_launch_status("unpack_latent launch", err, errlen);
 }

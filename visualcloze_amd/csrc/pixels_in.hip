@@ -65,9 +65,7 @@ int vc_pixels_in_launch(const void* src, int H, int W, int left, int top, void* 
   const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
   if (out_is_f32) hipLaunchKernelGGL((pixels_in_kernel<true>), grid, block, 0, s, (const unsigned char*)src, H, W, left, top, out, h, Wrow, x0, w);
   else hipLaunchKernelGGL((pixels_in_kernel<false>), grid, block, 0, s, (const unsigned char*)src, H, W, left, top, out, h, Wrow, x0, w);
-  const hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "pixels_in launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("pixels_in launch", err, errlen);
 }
 
 int vc_mask_fill_launch(void* mask, int h, int Wrow, int x0, int w, int value, hipStream_t s, char* err, int errlen) {
@@ -81,7 +79,5 @@ int vc_mask_fill_launch(void* mask, int h, int Wrow, int x0, int w, int value, h
   const long threads = (long)h * w;
   hipLaunchKernelGGL(mask_fill_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (bf16_t*)mask, h, Wrow, x0, w,
                      (bf16_t)(value ? 0x3F80 : 0));
-  const hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "mask_fill launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("mask_fill launch", err, errlen);
 }

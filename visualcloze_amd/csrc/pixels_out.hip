@@ -137,7 +137,5 @@ int vc_pixels_out_launch(const void* img, int img_is_f32, int H, int W, int x0, 
     else { if (u8) VC_PX_LAUNCH(pixels_out_kernel, false, true); else VC_PX_LAUNCH(pixels_out_kernel, false, false); }
   }
 #undef VC_PX_LAUNCH
-  const hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "pixels_out launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status("pixels_out launch", err, errlen);
 }

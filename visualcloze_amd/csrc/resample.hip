@@ -266,7 +266,6 @@ int vc_resample_u8_launch(const void* src, int H, int W, void* dst, int h, int w
     hipLaunchKernelGGL((resample_kernel<true>), dim3((unsigned)((total + 255) / 256)), block, 0, s, in, (unsigned char*)dst, H, h, w, t, t + h,
                        t + 2 * (size_t)h, axis_of(H, h, filter).kmax);
   }
-  VC_RS_HIP(hipGetLastError(), "resample_u8 launch");
 #undef VC_RS_HIP
-  return VC_OK;
+  return vc_launch_status("resample_u8 launch", err, errlen);
 }

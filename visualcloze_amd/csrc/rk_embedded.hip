@@ -36,17 +36,17 @@
 // plane, four f32 of the state - wherever the address allows it (plane j starts at element j n: 16-byte aligned for every j only
 // where n % 8 == 0, which every [B, N, 64] state is); the last n % 8 elements, and every element where a base is not 16-byte
 // aligned (the launcher picks W = 1), run one by one through the SAME per-element expression.  The norm deals single elements to
-// threads: its summation order is part of its result (transport._rk_norm restates it).  The quartic and the load run one element
+// threads: its summation order is part of its result (block_reduce.h, transport._rk_norm).  The quartic and the load run one element
 // per thread.
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int RK_THREADS = 256;                        // = VC_DOPRI5_MAX_BLOCKS: pass 2 reduces one partial per thread
-static_assert(RK_THREADS == VC_DOPRI5_MAX_BLOCKS, "pass 2 holds one block partial per thread");
 constexpr int RK_PROBE = 7;                            // the probe stage of every method
 constexpr int RK_E = 6;                                // the row of e
 
@@ -192,21 +192,6 @@ __global__ __launch_bounds__(RK_THREADS) void rk_stage_kernel(int method, int st
     for (long t = i; t < n; ++t) rk_stage_elems<1>(method, stage, S, y0, k, v, dt_ptr, y_stage, y_in, n, t);
 }
 
-// the block's 256 partial sums -> thread 0, always the same tree
-VC_DEV float rk_block_sum(float (&l)[RK_THREADS], float s) {
-  const int t = threadIdx.x;
-  l[t] = s;
-  __syncthreads();
-#pragma unroll
-  for (int o = RK_THREADS / 2; o >= 1; o >>= 1) {
-    if (t < o) l[t] += l[t + o];
-    __syncthreads();
-  }
-  const float r = l[0];
-  __syncthreads();
-  return r;
-}
-
 // pass 1: the n elements are dealt to the nblk * 256 threads round-robin, a thread adds its q^2 in ascending order.
 //   mode 0  q = dt * (e row) / (atol + rtol * max(|y0|, |y1|))        the error ratio of a step
 //   mode 1  q = y0 / (atol + rtol * |y0|)                              d0 of the initial step size
@@ -232,14 +217,14 @@ __global__ __launch_bounds__(RK_THREADS) void rk_norm_kernel(int method, int mod
     const float q = num / (atol + rtol * mag);
     s = s + q * q;
   }
-  s = rk_block_sum(l, s);
+  s = block_tree(l, s, VcAddOp());
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // pass 2: ONE block; the nblk <= 256 partials -> out[0] = sqrt(sum / n)
 __global__ __launch_bounds__(RK_THREADS) void rk_norm_finish_kernel(const float* __restrict__ partial, float* __restrict__ out, int nblk, long n) {
   __shared__ float l[RK_THREADS];
-  const float s = rk_block_sum(l, (int)threadIdx.x < nblk ? partial[threadIdx.x] : 0.0f);
+  const float s = block_tree(l, (int)threadIdx.x < nblk ? partial[threadIdx.x] : 0.0f, VcAddOp());
   if (threadIdx.x == 0) out[0] = sqrtf(s / (float)n);
 }
 
@@ -341,13 +326,12 @@ inline bool rk_aligned16(std::initializer_list<const void*> ps) {
 
 }  // namespace
 
-// `what`: the entry point's name in its messages
-#define VC_CHECK_LAUNCH(what)                                                                     \
-  do {                                                                                            \
-    hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) { snprintf(err, errlen, "%s launch: %s", what, hipGetErrorString(e_)); return VC_ERR_HIP; } \
-    return VC_OK;                                                                                 \
-  } while (0)
+// `what`: the entry point's name, known at run time only (an alias)
+static int rk_launch_status(const char* what, char* err, int errlen) {
+  char prefix[64];
+  snprintf(prefix, sizeof(prefix), "%s launch", what);
+  return vc_launch_status(prefix, err, errlen);
+}
 
 // `alias` (all three launchers): the vc_dopri5_* entry point the call serves - its name stands in the messages, which then name no method
 int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const void* v, const float* dt_ptr, const int32_t* eval_ptr,
@@ -369,7 +353,7 @@ int vc_rk_stage_launch(int method, int stage, const float* y0, void* k, const vo
   else
     hipLaunchKernelGGL(rk_stage_kernel<1>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, method, stage, y0, (bf16_t*)k, (const bf16_t*)v, dt_ptr,
                        (const int*)eval_ptr, y_stage, (bf16_t*)y_in, (long)n);
-  VC_CHECK_LAUNCH(what);
+  return rk_launch_status(what, err, errlen);
 }
 
 int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float* y1, const void* k, const float* dt_ptr, float rtol, float atol,
@@ -387,12 +371,11 @@ int vc_rk_error_ratio_launch(int method, int mode, const float* y0, const float*
     snprintf(err, errlen, "%s: rtol = %g and atol = %g must be finite, non-negative and not both zero", what, rtol, atol);
     return VC_ERR_ARG;
   }
-  const int64_t want = (n + RK_THREADS - 1) / RK_THREADS;
-  const int nblk = (int)(want < VC_DOPRI5_MAX_BLOCKS ? want : VC_DOPRI5_MAX_BLOCKS);
+  const int nblk = vc_reduce_blocks<RK_THREADS, VC_DOPRI5_MAX_BLOCKS>(n);
   hipLaunchKernelGGL(rk_norm_kernel, dim3(nblk), dim3(RK_THREADS), 0, s, method, mode, y0, y1, (const bf16_t*)k, dt_ptr, rtol, atol, scratch,
                      (long)n);
   hipLaunchKernelGGL(rk_norm_finish_kernel, dim3(1), dim3(RK_THREADS), 0, s, (const float*)scratch, out, nblk, (long)n);
-  VC_CHECK_LAUNCH(what);
+  return rk_launch_status(what, err, errlen);
 }
 
 // the dense output of the pair: the quartic for Dormand-Prince, the Hermite cubic for the others
@@ -408,7 +391,7 @@ int vc_rk_dense_launch(int method, const float* y0, const float* y1, const void*
                                         theta, out, (long)n);
     else hipLaunchKernelGGL(dopri5_interp_kernel<false>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, y0, y1, (const bf16_t*)k, dt_ptr, theta,
                             out, (long)n);
-    VC_CHECK_LAUNCH(what);
+    return rk_launch_status(what, err, errlen);
   }
   const int last = S - 1;
   const bool vec = rk_aligned16({y0, y1, k, out});
@@ -420,7 +403,7 @@ int vc_rk_dense_launch(int method, const float* y0, const float* y1, const void*
   else if (out_is_bf16) RK_HERMITE(1, true);
   else RK_HERMITE(1, false);
 #undef RK_HERMITE
-  VC_CHECK_LAUNCH(what);
+  return rk_launch_status(what, err, errlen);
 }
 
 // vc_rk_interp: the Hermite pairs alone - the public route to Dormand-Prince's dense output is vc_dopri5_interp
@@ -438,5 +421,5 @@ int vc_dopri5_load_launch(const void* x, int x_is_bf16, float* y0, void* y_in, i
   if (!x || !y0 || !y_in || !rk_n_ok(n)) { snprintf(err, errlen, "dopri5_load: bad args"); return VC_ERR_ARG; }
   if (x_is_bf16) hipLaunchKernelGGL(dopri5_load_kernel<true>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, x, y0, (bf16_t*)y_in, (long)n);
   else hipLaunchKernelGGL(dopri5_load_kernel<false>, dim3(rk_blocks(n, 1)), dim3(RK_THREADS), 0, s, x, y0, (bf16_t*)y_in, (long)n);
-  VC_CHECK_LAUNCH("dopri5_load");
+  return vc_launch_status("dopri5_load launch", err, errlen);
 }

@@ -200,13 +200,6 @@ __global__ __launch_bounds__(256) void sde_store_kernel(const float* __restrict_
 
 }  // namespace
 
-#define RNG_LAUNCHED(name)                                                                                          \
-  {                                                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                                              \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }  \
-  }                                                                                                                 \
-  return VC_OK;
-
 int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s, char* err, int errlen) {
   if (!out) { snprintf(err, errlen, "randn: null output pointer"); return VC_ERR_ARG; }
   if (n <= 0) { snprintf(err, errlen, "randn: n = %lld, need n >= 1", (long long)n); return VC_ERR_ARG; }
@@ -225,7 +218,7 @@ int vc_randn_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64_t off
   if (dtype == VC_RNG_BF16) hipLaunchKernelGGL(randn_kernel<VC_RNG_BF16>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
   else if (dtype == VC_RNG_F32) hipLaunchKernelGGL(randn_kernel<VC_RNG_F32>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
   else hipLaunchKernelGGL(randn_kernel<VC_RNG_U32>, dim3(grid), dim3(256), 0, s, out, (long)n, seed, offset, head, nvec);
-  RNG_LAUNCHED("randn")
+  return vc_launch_status("randn launch", err, errlen);
 }
 
 int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, hipStream_t s, char* err,
@@ -243,7 +236,7 @@ int vc_randn_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int co
     return VC_ERR_ARG; }
   hipLaunchKernelGGL(randn_tokens_kernel, dim3(grid_for((long)(h / 2) * (w / 2) * (C / 2))), dim3(256), 0, s, (bf16_t*)tokens, C, h, w, (long)ld,
                      col0, seed, offset);
-  RNG_LAUNCHED("randn_tokens")
+  return vc_launch_status("randn_tokens launch", err, errlen);
 }
 
 int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, const void* v, void* y_in, float* xhat, float* k1,
@@ -261,12 +254,12 @@ int vc_sde_stage_launch(int eval, const float* table, int n_rows, float* y, cons
   const long nvec = vec ? (long)(n / 8) : 0;
   hipLaunchKernelGGL(sde_stage_kernel, dim3(grid_for(nvec + (n - nvec * 8))), dim3(256), 0, s, eval, table, n_rows, y, (const bf16_t*)v,
                      (bf16_t*)y_in, xhat, k1, rng, (const int*)eval_ptr, (long)n, nvec);
-  RNG_LAUNCHED("sde_stage")
+  return vc_launch_status("sde_stage launch", err, errlen);
 }
 
 int vc_sde_store_launch(const float* y, void* out, int out_is_bf16, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!y || !out || n <= 0) { snprintf(err, errlen, "sde_store: bad args"); return VC_ERR_ARG; }
   if (out_is_bf16) hipLaunchKernelGGL(sde_store_kernel<true>, dim3(grid_for((long)n)), dim3(256), 0, s, y, out, (long)n);
   else hipLaunchKernelGGL(sde_store_kernel<false>, dim3(grid_for((long)n)), dim3(256), 0, s, y, out, (long)n);
-  RNG_LAUNCHED("sde_store")
+  return vc_launch_status("sde_store launch", err, errlen);
 }

@@ -187,13 +187,6 @@ int check_wrap(const char* who, uint64_t offset, const Policy& p, char* err, int
 }  // namespace
 
 #define RNGT_TRY(x) { int rc_ = (x); if (rc_ != VC_OK) return rc_; }
-#define RNGT_LAUNCHED(name)                                                                                         \
-  {                                                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                                              \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; }  \
-  }                                                                                                                 \
-  return VC_OK;
-
 int vc_torch_caps_resolve(const char* who, int* sm_count, int* threads_per_sm, char* err, int errlen) {
   RNGT_TRY(check_caps(who, *sm_count, *threads_per_sm, err, errlen));
   if (*sm_count && *threads_per_sm) return VC_OK;
@@ -240,7 +233,7 @@ int vc_randn_torch_launch(void* out, int dtype, int64_t n, uint64_t seed, uint64
   if (dtype == VC_RNG_BF16) hipLaunchKernelGGL(randn_torch_kernel<VC_RNG_BF16>, dim3(grid), dim3(256), 0, s, out, (long)n, d, (long)p.rounds, vec);
   else if (dtype == VC_RNG_F32) hipLaunchKernelGGL(randn_torch_kernel<VC_RNG_F32>, dim3(grid), dim3(256), 0, s, out, (long)n, d, (long)p.rounds, vec);
   else hipLaunchKernelGGL(randn_torch_kernel<VC_RNG_U32>, dim3(grid), dim3(256), 0, s, out, (long)n, d, (long)p.rounds, vec);
-  RNGT_LAUNCHED("randn_torch")
+  return vc_launch_status("randn_torch launch", err, errlen);
 }
 
 int vc_randn_torch_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, int col0, uint64_t seed, uint64_t offset, int sm_count,
@@ -263,5 +256,5 @@ int vc_randn_torch_tokens_launch(void* tokens, int C, int h, int w, int64_t ld, 
   const TorchDraw d{(uint32_t)seed, (uint32_t)(seed >> 32), offset >> 2, (long)p.T};
   hipLaunchKernelGGL(randn_torch_tokens_kernel, dim3(grid_for((long)(h / 2) * (w / 2) * (C / 2))), dim3(256), 0, s, (bf16_t*)tokens, C, h, w,
                      (long)ld, col0, d);
-  RNGT_LAUNCHED("randn_torch_tokens")
+  return vc_launch_status("randn_torch_tokens launch", err, errlen);
 }

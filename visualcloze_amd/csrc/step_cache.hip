@@ -2,36 +2,25 @@
 // The rule is this library's own - the reference evaluates every block at every step.
 //   residual_change   r = bf16(f32(h1) - f32(h0)) -> HBM, and per sample (sum |f32(r) - f32(P)|, sum |f32(P)|) in f32
 //   residual_sub/add  out = bf16(f32(a) -/+ f32(b)) on per-sample contiguous rows (R = hE - h1; X_img = h1 + R)
-// All HBM-bound, 16-byte accesses, bf16 storage, f32 math.  The sums are a two-pass block reduction in a FIXED order (per thread:
-// its chunks in ascending order; per block: an LDS tree; per sample: a tree over the block partials) and use no atomics, so a
-// repeated run gives the same bits.
+// All HBM-bound, 16-byte accesses, bf16 storage, f32 math.  The sums are the two-pass reduction of block_reduce.h over 16-byte
+// chunks: a FIXED order, no atomics, so a repeated run gives the same bits.
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 
 namespace {
 
 constexpr int RC_THREADS = 256;                       // = VC_RESIDUAL_CHANGE_MAX_BLOCKS: pass 2 reduces one partial per thread
-static_assert(RC_THREADS == VC_RESIDUAL_CHANGE_MAX_BLOCKS, "pass 2 holds one block partial per thread");
 
-// the block's 256 (s0, s1) pairs -> thread 0, always the same tree
-VC_DEV void block_tree_sum(float (&l0)[RC_THREADS], float (&l1)[RC_THREADS], float& s0, float& s1) {
-  const int t = threadIdx.x;
-  l0[t] = s0; l1[t] = s1;
-  __syncthreads();
-#pragma unroll
-  for (int o = RC_THREADS / 2; o >= 1; o >>= 1) {
-    if (t < o) { l0[t] += l0[t + o]; l1[t] += l1[t + o]; }
-    __syncthreads();
-  }
-  s0 = l0[0]; s1 = l1[0];
-  __syncthreads();
-}
+// (sum |r - P|, sum |P|): one tree carries both
+struct RcPair { float s0, s1; };
+struct RcAdd { VC_DEV RcPair operator()(RcPair x, RcPair y) const { return RcPair{x.s0 + y.s0, x.s1 + y.s1}; } };
 
 // pass 1: grid (nblk, B); sample b's n8 16-byte chunks are dealt to the nblk * 256 threads round-robin
 __global__ __launch_bounds__(RC_THREADS) void residual_change_kernel(const u32x4* __restrict__ h0, const u32x4* __restrict__ h1,
                                                                      const u32x4* __restrict__ p, u32x4* __restrict__ r,
                                                                      float* __restrict__ partial, long n8) {
-  __shared__ float l0[RC_THREADS], l1[RC_THREADS];
+  __shared__ RcPair l[RC_THREADS];
   const int nblk = gridDim.x, b = blockIdx.y;
   const long base = (long)b * n8;
   float s0 = 0.0f, s1 = 0.0f;
@@ -48,10 +37,10 @@ __global__ __launch_bounds__(RC_THREADS) void residual_change_kernel(const u32x4
     }
     r[base + c] = o;
   }
-  block_tree_sum(l0, l1, s0, s1);
+  const RcPair t = block_tree(l, RcPair{s0, s1}, RcAdd());
   if (threadIdx.x == 0) {
-    partial[((long)b * nblk + blockIdx.x) * 2] = s0;
-    partial[((long)b * nblk + blockIdx.x) * 2 + 1] = s1;
+    partial[((long)b * nblk + blockIdx.x) * 2] = t.s0;
+    partial[((long)b * nblk + blockIdx.x) * 2 + 1] = t.s1;
   }
 }
 
@@ -59,18 +48,18 @@ __global__ __launch_bounds__(RC_THREADS) void residual_change_kernel(const u32x4
 // (a NaN ratio - no P: 0 / 0 - stays NaN, so that a host comparing `metric < threshold` never reuses on it)
 __global__ __launch_bounds__(RC_THREADS) void residual_change_finish_kernel(const float* __restrict__ partial, float* __restrict__ sums,
                                                                             float* __restrict__ metric, int B, int nblk) {
-  __shared__ float l0[RC_THREADS], l1[RC_THREADS];
+  __shared__ RcPair l[RC_THREADS];
   float m = 0.0f;
   for (int b = 0; b < B; ++b) {
-    float s0 = 0.0f, s1 = 0.0f;
+    RcPair t = {0.0f, 0.0f};
     if ((int)threadIdx.x < nblk) {
-      s0 = partial[((long)b * nblk + threadIdx.x) * 2];
-      s1 = partial[((long)b * nblk + threadIdx.x) * 2 + 1];
+      t.s0 = partial[((long)b * nblk + threadIdx.x) * 2];
+      t.s1 = partial[((long)b * nblk + threadIdx.x) * 2 + 1];
     }
-    block_tree_sum(l0, l1, s0, s1);
-    const float mb = s0 / s1;
+    t = block_tree(l, t, RcAdd());
+    const float mb = t.s0 / t.s1;
     if (b == 0 || mb > m || mb != mb) m = (m != m) ? m : mb;
-    if (threadIdx.x == 0 && sums) { sums[2 * b] = s0; sums[2 * b + 1] = s1; }
+    if (threadIdx.x == 0 && sums) { sums[2 * b] = t.s0; sums[2 * b + 1] = t.s1; }
   }
   if (threadIdx.x == 0 && metric) *metric = m;
 }
@@ -96,13 +85,6 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-#define VC_CHECK_LAUNCH(name)                                                                     \
-  do {                                                                                            \
-    hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) { snprintf(err, errlen, name " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } \
-    return VC_OK;                                                                                 \
-  } while (0)
-
 int vc_residual_change_launch(const void* h0, const void* h1, const void* p, void* r, float* sums, float* metric, float* scratch,
                               int32_t B, int64_t n, hipStream_t s, char* err, int errlen) {
   if (!h0 || !h1 || !p || !r || !scratch || (!sums && !metric) || B <= 0 || B > 65535 || n <= 0) {
@@ -114,12 +96,11 @@ int vc_residual_change_launch(const void* h0, const void* h1, const void* p, voi
     return VC_ERR_ARG;
   }
   const long n8 = n / 8;
-  const long want = (n8 + RC_THREADS - 1) / RC_THREADS;
-  const int nblk = (int)(want < VC_RESIDUAL_CHANGE_MAX_BLOCKS ? want : VC_RESIDUAL_CHANGE_MAX_BLOCKS);
+  const int nblk = vc_reduce_blocks<RC_THREADS, VC_RESIDUAL_CHANGE_MAX_BLOCKS>(n8);
   hipLaunchKernelGGL(residual_change_kernel, dim3(nblk, B), dim3(RC_THREADS), 0, s, (const u32x4*)h0, (const u32x4*)h1, (const u32x4*)p,
                      (u32x4*)r, scratch, n8);
   hipLaunchKernelGGL(residual_change_finish_kernel, dim3(1), dim3(RC_THREADS), 0, s, (const float*)scratch, sums, metric, (int)B, nblk);
-  VC_CHECK_LAUNCH("residual_change");
+  return vc_launch_status("residual_change launch", err, errlen);
 }
 
 int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void* b, int64_t b_bstride, void* out, int64_t out_bstride,
@@ -139,7 +120,5 @@ int vc_residual_op_launch(int add, const void* a, int64_t a_bstride, const void*
                               (long)(b_bstride / 8), (u32x4*)out, (long)(out_bstride / 8), n8);
   else hipLaunchKernelGGL(residual_op_kernel<false>, grid, block, 0, s, (const u32x4*)a, (long)(a_bstride / 8), (const u32x4*)b,
                           (long)(b_bstride / 8), (u32x4*)out, (long)(out_bstride / 8), n8);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) { snprintf(err, errlen, "%s launch: %s", name, hipGetErrorString(e_)); return VC_ERR_HIP; }
-  return VC_OK;
+  return vc_launch_status(add ? "residual_add launch" : "residual_sub launch", err, errlen);
 }

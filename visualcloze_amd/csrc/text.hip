@@ -184,17 +184,12 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const int32_t* __restric
 
 }  // namespace
 
-#define TXT_LAUNCH_CHECK(what)                                                                   \
-  do { hipError_t e_ = hipGetLastError();                                                        \
-       if (e_ != hipSuccess) { snprintf(err, errlen, what " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } } while (0)
-
 int vc_embedding_launch(const int32_t* ids, const void* table, int64_t ldt, int V, void* out, int L, int D, hipStream_t s, char* err, int errlen) {
   if (!ids || !table || !out) { snprintf(err, errlen, "embedding: null pointer"); return VC_ERR_ARG; }
   if (L <= 0 || D <= 0 || D % 8 || V <= 0 || ldt < D || ldt % 8) { snprintf(err, errlen, "embedding: bad shape L=%d D=%d V=%d", L, D, V); return VC_ERR_ARG; }
   const long total = (long)L * (D >> 3);
   hipLaunchKernelGGL(embedding_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ids, (const bf16_t*)table, (long)ldt, V, (bf16_t*)out, L, D);
-  TXT_LAUNCH_CHECK("embedding");
-  return VC_OK;
+  return vc_launch_status("embedding launch", err, errlen);
 }
 
 int vc_rownorm_launch(const void* x, const void* w, const void* b, void* y, int rows, int D, float eps, int affine_ln, hipStream_t s, char* err, int errlen) {
@@ -202,8 +197,7 @@ int vc_rownorm_launch(const void* x, const void* w, const void* b, void* y, int 
   if (rows <= 0 || D <= 0 || D % 8 || D > 4096) { snprintf(err, errlen, "rmsnorm/layernorm: rows=%d D=%d (D %% 8 == 0, D <= 4096)", rows, D); return VC_ERR_ARG; }
   if (affine_ln) hipLaunchKernelGGL(rownorm_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, rows, D, eps);
   else hipLaunchKernelGGL(rownorm_kernel<0>, dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, rows, D, eps);
-  TXT_LAUNCH_CHECK("rmsnorm/layernorm");
-  return VC_OK;
+  return vc_launch_status("rmsnorm/layernorm launch", err, errlen);
 }
 
 int vc_ewise_launch(const void* a, const void* b, void* y, int64_t n, int op, hipStream_t s, char* err, int errlen) {
@@ -211,8 +205,7 @@ int vc_ewise_launch(const void* a, const void* b, void* y, int64_t n, int op, hi
   if (n <= 0 || n % 8) { snprintf(err, errlen, "elementwise: n=%ld must be a positive multiple of 8", (long)n); return VC_ERR_ARG; }
   const long n8 = n >> 3;
   hipLaunchKernelGGL(ewise_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n8, op);
-  TXT_LAUNCH_CHECK("elementwise");
-  return VC_OK;
+  return vc_launch_status("elementwise launch", err, errlen);
 }
 
 // T5Attention._relative_position_bucket (bidirectional) of relative position r = key - query, in the arithmetic of
@@ -266,8 +259,7 @@ int vc_t5_position_bias_launch(const void* table, int64_t ld, int H, int L, int 
   const long total = (long)H * L * (L >> 3);
   hipLaunchKernelGGL(t5_position_bias_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)table, (long)ld, H, L, half,
                      max_exact, st, (bf16_t*)out);
-  TXT_LAUNCH_CHECK("t5_position_bias");
-  return VC_OK;
+  return vc_launch_status("t5_position_bias launch", err, errlen);
 }
 
 int vc_clip_embed_launch(const int32_t* ids, const void* tok, int64_t ldt, int V, const void* pos, int64_t ldp, void* out, int L, int Lp, int D,
@@ -280,8 +272,7 @@ int vc_clip_embed_launch(const int32_t* ids, const void* tok, int64_t ldt, int V
   const long total = (long)Lp * (D >> 3);
   hipLaunchKernelGGL(clip_embed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ids, (const bf16_t*)tok, (long)ldt, V, (const bf16_t*)pos,
                      (long)ldp, (bf16_t*)out, L, Lp, D);
-  TXT_LAUNCH_CHECK("clip_embed");
-  return VC_OK;
+  return vc_launch_status("clip_embed launch", err, errlen);
 }
 
 int vc_clip_pool_launch(const int32_t* ids, const void* hidden, int64_t ld, int L, int D, int eos, void* pooled, hipStream_t s, char* err, int errlen) {
@@ -291,6 +282,5 @@ int vc_clip_pool_launch(const int32_t* ids, const void* hidden, int64_t ld, int 
     return VC_ERR_ARG;
   }
   hipLaunchKernelGGL(clip_pool_kernel, dim3(((D >> 3) + 255) / 256), dim3(256), 0, s, ids, (const bf16_t*)hidden, (long)ld, L, D, eos, (bf16_t*)pooled);
-  TXT_LAUNCH_CHECK("clip_pool");
-  return VC_OK;
+  return vc_launch_status("clip_pool launch", err, errlen);
 }

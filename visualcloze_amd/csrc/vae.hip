@@ -10,6 +10,7 @@
 //   nchw <-> nhwc layout changes at the two ends (latent in, image out), with the affine `z / scale + shift` (:306-307)
 #include "common.h"
 #include "vcloze_internal.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -80,23 +81,19 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t* __restric
 }
 
 // stats[2g] = mean, stats[2g+1] = rstd.  One 256-thread block per group: thread t adds partials t, t+256, ... in that
-// order, then a fixed-shape tree over the 256 thread sums - deterministic, and parallel enough for the 1152 partial
+// order, then the tree of block_reduce.h over the 256 thread sums - deterministic, and parallel enough for the 1152 partial
 // blocks of a 384x384 map.
+struct GnSums { double s, q; };
+struct GnAdd { VC_DEV GnSums operator()(GnSums x, GnSums y) const { return GnSums{x.s + y.s, x.q + y.q}; } };
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats, int nblk, int G, float inv_n, float eps) {
-  __shared__ double rs[256], rq[256];
+  __shared__ GnSums l[256];
   const int g = blockIdx.x, t = threadIdx.x;
   double s = 0.0, q = 0.0;
   for (int b = t; b < nblk; b += 256) { s += part[(long)b * 2 * G + 2 * g]; q += part[(long)b * 2 * G + 2 * g + 1]; }
-  rs[t] = s; rq[t] = q;
-  __syncthreads();
-#pragma unroll
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) { rs[t] += rs[t + w]; rq[t] += rq[t + w]; }
-    __syncthreads();
-  }
+  const GnSums r = block_tree(l, GnSums{s, q}, GnAdd());
   if (t == 0) {
-    const double mean = rs[0] * inv_n;
-    const double var = rq[0] * inv_n - mean * mean;
+    const double mean = r.s * inv_n;
+    const double var = r.q * inv_n - mean * mean;
     stats[2 * g] = (float)mean;
     stats[2 * g + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
   }
@@ -282,18 +279,13 @@ __global__ void cast_pad_kernel(const void* __restrict__ src, int src_f32, bf16_
 
 }  // namespace
 
-#define VAE_LAUNCH_CHECK(what)                                                                   \
-  do { hipError_t e_ = hipGetLastError();                                                        \
-       if (e_ != hipSuccess) { snprintf(err, errlen, what " launch: %s", hipGetErrorString(e_)); return VC_ERR_HIP; } } while (0)
-
 int vc_im2col3x3_launch(const void* src, void* dst, int H, int W, int C, int up, hipStream_t s, char* err, int errlen) {
   if (!src || !dst) { snprintf(err, errlen, "im2col3x3: null pointer"); return VC_ERR_ARG; }
   if (H <= 0 || W <= 0 || C <= 0 || C % 8 || up < 0 || up > 2 || (up == 1 && ((H | W) & 1))) {
     snprintf(err, errlen, "im2col3x3: bad shape H=%d W=%d C=%d mode=%d (C %% 8 == 0; even H, W when upsampling)", H, W, C, up); return VC_ERR_ARG; }
   const long total = (long)H * W * 9 * (C >> 3);
   hipLaunchKernelGGL(im2col3x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)dst, H, W, C, up);
-  VAE_LAUNCH_CHECK("im2col3x3");
-  return VC_OK;
+  return vc_launch_status("im2col3x3 launch", err, errlen);
 }
 
 int vc_groupnorm_launch(const void* x, const void* gamma, const void* beta, void* y, void* scratch, int64_t scratch_bytes,
@@ -311,8 +303,7 @@ int vc_groupnorm_launch(const void* x, const void* gamma, const void* beta, void
   const long chunks = HW * (C >> 3);
   hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x, stats,
                      (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, (long)HW, C, G, swish);
-  VAE_LAUNCH_CHECK("groupnorm");
-  return VC_OK;
+  return vc_launch_status("groupnorm launch", err, errlen);
 }
 
 int vc_softmax_rows_launch(void* x, int64_t ld, int rows, int cols, float scale, const void* bias, int64_t ldb, int causal_period,
@@ -322,16 +313,14 @@ int vc_softmax_rows_launch(void* x, int64_t ld, int rows, int cols, float scale,
     snprintf(err, errlen, "softmax_rows: bad shape rows=%d cols=%d (cols <= 16384)", rows, cols); return VC_ERR_ARG; }
   auto fn = cols <= 512 ? softmax_rows_kernel<2> : cols <= 2048 ? softmax_rows_kernel<8> : cols <= 8192 ? softmax_rows_kernel<32> : softmax_rows_kernel<64>;
   hipLaunchKernelGGL(fn, dim3(rows), dim3(256), 0, s, (bf16_t*)x, (long)ld, cols, scale, (const bf16_t*)bias, (long)ldb, causal_period);
-  VAE_LAUNCH_CHECK("softmax_rows");
-  return VC_OK;
+  return vc_launch_status("softmax_rows launch", err, errlen);
 }
 
 int vc_transpose_launch(const void* src, int64_t lds_, void* dst, int64_t ldd, int R, int Cc, hipStream_t s, char* err, int errlen) {
   if (!src || !dst) { snprintf(err, errlen, "transpose: null pointer"); return VC_ERR_ARG; }
   if (R <= 0 || Cc <= 0 || lds_ < Cc || ldd < R) { snprintf(err, errlen, "transpose: bad shape R=%d C=%d", R, Cc); return VC_ERR_ARG; }
   hipLaunchKernelGGL(transpose_kernel, dim3((Cc + 31) / 32, (R + 31) / 32), dim3(256), 0, s, (const bf16_t*)src, (long)lds_, (bf16_t*)dst, (long)ldd, R, Cc);
-  VAE_LAUNCH_CHECK("transpose");
-  return VC_OK;
+  return vc_launch_status("transpose launch", err, errlen);
 }
 
 int vc_nchw_to_nhwc_launch(const void* src, int src_f32, void* dst, int C, int Cp, int64_t HW, float div, float add, hipStream_t s, char* err, int errlen) {
@@ -339,8 +328,7 @@ int vc_nchw_to_nhwc_launch(const void* src, int src_f32, void* dst, int C, int C
   if (C <= 0 || Cp < C || HW <= 0 || div == 0.0f) { snprintf(err, errlen, "nchw_to_nhwc: bad shape C=%d Cp=%d HW=%ld (div != 0)", C, Cp, (long)HW); return VC_ERR_ARG; }
   const long total = HW * Cp;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, src_f32, (bf16_t*)dst, C, Cp, (long)HW, div, add);
-  VAE_LAUNCH_CHECK("nchw_to_nhwc");
-  return VC_OK;
+  return vc_launch_status("nchw_to_nhwc launch", err, errlen);
 }
 
 int vc_nhwc_to_nchw_launch(const void* src, void* dst, int dst_f32, int C, int Cp, int64_t HW, hipStream_t s, char* err, int errlen) {
@@ -348,8 +336,7 @@ int vc_nhwc_to_nchw_launch(const void* src, void* dst, int dst_f32, int C, int C
   if (C <= 0 || Cp < C || HW <= 0) { snprintf(err, errlen, "nhwc_to_nchw: bad shape C=%d Cp=%d HW=%ld", C, Cp, (long)HW); return VC_ERR_ARG; }
   const long total = HW * C;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)src, dst, dst_f32, C, Cp, (long)HW);
-  VAE_LAUNCH_CHECK("nhwc_to_nchw");
-  return VC_OK;
+  return vc_launch_status("nhwc_to_nchw launch", err, errlen);
 }
 
 int vc_gaussian_sample_launch(const void* moments, int Cp, const void* noise, void* out, int Z, int64_t HW, float scale, float shift,
@@ -359,8 +346,7 @@ int vc_gaussian_sample_launch(const void* moments, int Cp, const void* noise, vo
   const long total = HW * Z;
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)moments, Cp,
                      (const bf16_t*)noise, (bf16_t*)out, Z, (long)HW, scale, shift);
-  VAE_LAUNCH_CHECK("gaussian_sample");
-  return VC_OK;
+  return vc_launch_status("gaussian_sample launch", err, errlen);
 }
 
 int vc_vae_weight_relayout_launch(const void* w, int w_f32, void* dst, int O, int I, int kk, int Op, int Ip, hipStream_t s, char* err, int errlen) {
@@ -368,22 +354,19 @@ int vc_vae_weight_relayout_launch(const void* w, int w_f32, void* dst, int O, in
   if (O <= 0 || I <= 0 || kk <= 0 || Op < O || Ip < I || Ip % 8) { snprintf(err, errlen, "vae weight relayout: bad shape O=%d I=%d kk=%d Op=%d Ip=%d", O, I, kk, Op, Ip); return VC_ERR_ARG; }
   const long total = (long)Op * kk * (Ip >> 3);
   hipLaunchKernelGGL(conv_weight_relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, w_f32, (bf16_t*)dst, O, I, kk, Op, Ip);
-  VAE_LAUNCH_CHECK("vae weight relayout");
-  return VC_OK;
+  return vc_launch_status("vae weight relayout launch", err, errlen);
 }
 
 int vc_vae_cast_pad_launch(const void* src, int src_f32, void* dst, int n, int n_pad, hipStream_t s, char* err, int errlen) {
   if (!src || !dst) { snprintf(err, errlen, "vae cast: null pointer"); return VC_ERR_ARG; }
   if (n <= 0 || n_pad < n) { snprintf(err, errlen, "vae cast: bad size n=%d n_pad=%d", n, n_pad); return VC_ERR_ARG; }
   hipLaunchKernelGGL(cast_pad_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, src, src_f32, (bf16_t*)dst, n, n_pad);
-  VAE_LAUNCH_CHECK("vae cast");
-  return VC_OK;
+  return vc_launch_status("vae cast launch", err, errlen);
 }
 
 int vc_zero_fill_launch(void* p, int64_t bytes, hipStream_t s, char* err, int errlen) {
   if (!p || bytes <= 0 || bytes % 16 || ((uintptr_t)p & 15)) { snprintf(err, errlen, "zero fill: a 16-byte aligned pointer and a multiple of 16 bytes expected (%ld)", (long)bytes); return VC_ERR_ARG; }
   const long n16 = bytes / 16;
   hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (u32x4*)p, n16);
-  VAE_LAUNCH_CHECK("zero fill");
-  return VC_OK;
+  return vc_launch_status("zero fill launch", err, errlen);
 }

@@ -27,6 +27,13 @@ inline int vc_cu_count() {          // compute units of the CURRENT device
   }
   return n[d];
 }
+// the tail of a launcher: VC_OK, or "<what>: <the runtime's message>" in err and VC_ERR_HIP (`what` is the whole prefix, "silu launch")
+inline int vc_launch_status(const char* what, char* err, int errlen) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return VC_OK;
+  snprintf(err, errlen, "%s: %s", what, hipGetErrorString(e));
+  return VC_ERR_HIP;
+}
 int vc_gemm_launch(VcGemmArgs a, int tile_cfg, hipStream_t s, char* err, int errlen);
 int vc_gemm_plan_impl(VcGemmArgs a, int tile_cfg, int32_t out[8], char* err, int errlen);
 int vc_attention_launch(const VcAttention& a, hipStream_t s, char* err, int errlen);

@@ -47,6 +47,7 @@ from typing import Callable, Optional
 import torch
 
 from . import hip
+from .reduction import ordered_sum
 
 
 def time_shift(mu: float, sigma: float, t: torch.Tensor) -> torch.Tensor:
@@ -146,35 +147,13 @@ def fm_path(t: torch.Tensor, x0: torch.Tensor, x1: torch.Tensor):
 
 def _fm_ordered_sum(sq: torch.Tensor, rows_total: int) -> torch.Tensor:
     """sum of the f32 squares `sq` [valid rows, cols] of ONE sample in vc_fm_loss's order (include/vcloze_hip.h): units of 8 elements
-    along a row, dealt round-robin to nblk * 256 threads with nblk = min(ceil(rows_total * ceil(cols / 8) / 256), 256), a thread's
-    elements added in ascending order, the block's 256 sums and then the nblk block sums down one binary tree"""
+    along a row, the grid sized by all `rows_total` rows, summed by `reduction.ordered_sum`"""
     sq = sq.detach().to("cpu", torch.float32)
     R, cols = sq.shape
     upr = (cols + 7) // 8
-    nblk = min((rows_total * upr + 255) // 256, hip.FM_LOSS_MAX_BLOCKS)
-    T = nblk * 256
     units = torch.zeros(R, upr * 8, dtype=torch.float32)       # (x + 0 = x for the squares: zero padding does not show)
     units[:, :cols] = sq
-    units = units.view(R * upr, 8)
-    rounds = max(-(-(R * upr) // T), 1)
-    pad = torch.zeros(rounds * T, 8, dtype=torch.float32)
-    pad[:R * upr] = units
-    pad = pad.view(rounds, T, 8)
-    s = torch.zeros(T, dtype=torch.float32)
-    for r in range(rounds):
-        for e in range(8):
-            s = s + pad[r, :, e]
-
-    def tree(v):
-        o = 128
-        while o >= 1:
-            v = v[..., :o] + v[..., o:2 * o]
-            o //= 2
-        return v[..., 0]
-
-    part = torch.zeros(256, dtype=torch.float32)
-    part[:nblk] = tree(s.view(nblk, 256))
-    return tree(part)
+    return ordered_sum(units.view(R * upr, 8), rows_total * upr, hip.FM_LOSS_MAX_BLOCKS)
 
 
 def fm_loss_reduce(out: torch.Tensor, ut: torch.Tensor, img_mask: Optional[torch.Tensor] = None, ordered: bool = False) -> torch.Tensor:
@@ -419,32 +398,11 @@ def _rms(a) -> float:
 
 
 def _rk_norm(num: torch.Tensor, den: torch.Tensor) -> float:
-    """sqrt(mean(q^2)) of q = num / den over all n elements, summed in q's dtype in the fixed order of csrc/rk_embedded.hip: the
-    elements are dealt round-robin to nblk * 256 threads (nblk = min(ceil(n / 256), 256)), a thread adds its squares in ascending
-    order, a block's 256 sums go down one binary tree, the block sums down the same tree.  For an f32 q this gives the kernel's bits;
-    the callers form num and den on the CPU too."""
+    """sqrt(mean(q^2)) of q = num / den over all n elements, summed in q's dtype in the fixed order of csrc/rk_embedded.hip: single
+    elements through `reduction.ordered_sum`.  For an f32 q this gives the kernel's bits; the callers form num and den on the CPU too."""
     q = num.reshape(-1) / den.reshape(-1)
     n = q.numel()
-    nblk = min((n + 255) // 256, 256)
-    T = nblk * 256
-    rounds = -(-n // T)
-    q2 = torch.zeros(rounds * T, dtype=q.dtype)
-    q2[:n] = q * q
-    q2 = q2.view(rounds, T)
-    s = q2[0]
-    for r in range(1, rounds):
-        s = s + q2[r]
-
-    def tree(v):
-        o = 128
-        while o >= 1:
-            v = v[..., :o] + v[..., o:2 * o]
-            o //= 2
-        return v[..., 0]
-
-    part = torch.zeros(256, dtype=q.dtype)
-    part[:nblk] = tree(s.view(nblk, 256))
-    mean = float(tree(part) / torch.tensor(float(n), dtype=torch.float64).to(q.dtype))
+    mean = float(ordered_sum((q * q).reshape(n, 1)) / torch.tensor(float(n), dtype=torch.float64).to(q.dtype))
     # the square root in double, rounded once more for an f32 q: the correctly rounded f32 root (53 >= 2 * 24 + 2 bits), which
     # torch's vectorised CPU sqrt is not
     return math.sqrt(mean) if q.dtype == torch.float64 else _f32(math.sqrt(mean))
