@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import text_oracle as TO
+from tests import tokenview as TV
 from tests.procedural import TINY_CLIP, TINY_T5, procedural_text_param, ptensor, tiny_ids
 
 pytestmark = pytest.mark.gpu
@@ -131,6 +132,8 @@ def test_xxl_width_t5_layers_match_oracle(hip):
     o16 = TO.t5_encode(sd, ids, cfg, "bf16")
     noise = rel_l2(o16, o32)
     assert rel_l2(out, o32) <= 3.0 * noise + 2e-3, (rel_l2(out, o32), noise)
+    # ... and token by token: the first / last row of each of the 8 tiles and the interior (tests/tokenview.py)
+    TV.assert_tokens_within_bf16_noise(out, o16, o32, TV.t5_regions(512), "XXL-width T5, 2 layers", TV.TOKEN_M["t5"])
 
 
 def test_clip_l_width_matches_oracle(hip):
@@ -149,3 +152,6 @@ def test_clip_l_width_matches_oracle(hip):
     assert hs.shape == (1, 77, 768) and pooled.shape == (1, 768)
     assert rel_l2(hs[0].float().cpu(), h32) <= 3.0 * noise + 2e-3, (rel_l2(hs[0].float().cpu(), h32), noise)
     assert rel_l2(pooled[0].float().cpu(), p32) <= 3.0 * rel_l2(p16, p32) + 4e-3
+    # ... and token by token: row 0, the EOS row, the last live row (76 of the 128 rows run), the rest, and `pooled` as a row
+    TV.assert_tokens_within_bf16_noise(hs[0].float().cpu(), h16, h32, TV.clip_regions(77, 20), "CLIP-L width, 3 layers", TV.TOKEN_M["clip"],
+                                       pooled=(pooled[0].float().cpu(), p16, p32))
