@@ -305,7 +305,7 @@ def test_option_off_changes_nothing_and_the_refusals(model):
     assert [L.vc_flux_workspace_bytes(h.h, B, T_, N, S) for S in (4, 7, 30)] == before
     fn = _sampler().sample_ode_adaptive(num_steps=4, rtol=1e-2, atol=1e-6, do_shift=True, time_shifting_factor=1)
     a0 = fn(x, m.forward, kw)
-    assert h.adaptive == 0                                                # the sampler leaves the option off behind it
+    assert h.ws_options["adaptive"] == 0                                                # the sampler leaves the option off behind it
     assert [L.vc_flux_workspace_bytes(h.h, B, T_, N, S) for S in (4, 7, 30)] == before
     assert torch.equal(euler(), e0)                                       # the same Euler bits after an adaptive run on the handle
     # the refusals, on the handle directly

@@ -265,7 +265,7 @@ def test_off_means_off():
     terms = T.create_transport().training_losses(m.forward, x, loss_kw, {"cond": kw["cond"]}, t=torch.tensor([0.4]),
                                                  x0=torch.randn(x.shape, generator=torch.Generator().manual_seed(1)).to(DEV, torch.bfloat16))
     assert torch.isfinite(terms["loss"]).all()
-    assert h.eval_loss_on == 0 and sizes(h) == sizes(ho)                                   # the option is off again behind the call
+    assert h.ws_options["eval_loss"] == 0 and sizes(h) == sizes(ho)                                   # the option is off again behind the call
     h.set_eval_loss(True)
     n = B * N * x.shape[2]
     assert all(a - b >= n * 4 for a, b in zip(sizes(h), sizes(ho)))                     # u_t, carved only with the option

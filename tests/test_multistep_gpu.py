@@ -296,7 +296,7 @@ def test_option_off_changes_nothing_and_the_refusals():
     assert sizes() == before
     s0 = _fused(m, x, kw, 3, 5, trajectory=False)
     assert h.step_nodes() == ode_nodes
-    assert h.multistep == 0 and sizes() == before                         # the sampler leaves the option off behind it
+    assert h.ws_options["multistep"] == 0 and sizes() == before                         # the sampler leaves the option off behind it
     assert torch.equal(euler(), e0) and h.step_nodes() == ode_nodes       # the same Euler bits and nodes after a multistep run on the handle
     # the refusals, on the handle directly
     from visualcloze_amd.transport import solver_time_grid

@@ -277,7 +277,7 @@ def test_option_off_changes_nothing_the_node_count_and_the_refusals():
     opts = SETTINGS["euler_mean"]
     s0 = _sampler().sample_sde(rng=NoiseStream(3, device=DEV), **opts)(x, m.forward, **kw)
     assert h.step_nodes() == ode_nodes                                    # the Euler-Maruyama step: the nodes of the ODE Euler step
-    assert h.sde == 0 and sizes() == before                               # the sampler leaves the option off behind it
+    assert h.ws_options["sde"] == 0 and sizes() == before                               # the sampler leaves the option off behind it
     assert torch.equal(euler(), e0) and h.step_nodes() == ode_nodes       # the same Euler bits and nodes after an SDE run on the handle
     # the refusals, on the handle directly
     t = torch.linspace(0, 0.75, 4)

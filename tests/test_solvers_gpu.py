@@ -368,6 +368,64 @@ def test_every_sampler_in_turn_on_one_handle_equals_a_fresh_handle(model):
     assert all(not torch.equal(a, b) for i, a in enumerate(finals) for b in finals[i + 1:])       # six different samplers
 
 
+def test_every_sampler_method_in_turn_on_one_model_leaves_the_handle_as_it_found_it(model):
+    """The same at the Sampler level, where every method sets the handle's options and takes them back: Euler, adaptive bosh3, SDE-Heun,
+    multistep of order 3, rk4 with true CFG, an adaptive solve that FAILS inside the fused loop (max_attempts = 1), Euler.  After every
+    call, the failed one too, the workspace options and true CFG are off; every successful result is bit-equal to the same call on a
+    model whose handle ran nothing else; the last Euler is the first."""
+    from tests.procedural import tiny_inputs
+    from visualcloze_amd import hip
+    from visualcloze_amd.pipeline import NoiseStream
+    from visualcloze_amd.transport import Sampler, create_transport
+    m, _ = model
+    inp = tiny_inputs(B=2)
+    kw = _kw(inp)
+    x = inp["x"].to(DEV, torch.bfloat16)
+    assert (x.shape[0], kw["txt"].shape[1], x.shape[1]) == (2, 16, 24)
+    S = Sampler(create_transport())
+    grid = dict(num_steps=5, do_shift=True, time_shifting_factor=1, return_trajectory=True)
+    calls = {
+        "euler": lambda: S.sample_ode(sampling_method="euler", **grid)(x, m.forward, kw),
+        "bosh3": lambda: S.sample_ode_adaptive(method="bosh3", rtol=1e-2, atol=1e-3, **grid)(x, m.forward, kw),
+        "sde_heun": lambda: S.sample_sde(sampling_method="Heun", diffusion_form="sigma", diffusion_norm=0.7, last_step="Mean", last_step_size=0.25,
+                                         num_steps=4, sample_eps=1e-3, rng=NoiseStream(3), return_trajectory=True)(x, m.forward, **kw),
+        "multistep": lambda: S.sample_ode_multistep(order=3, **grid)(x, m.forward, kw),
+        "cfg_rk4": lambda: S.sample_ode(sampling_method="rk4", **grid)(x, m.forward_with_cfg, dict(kw, cfg_scale=2.5)),
+        "failing": lambda: S.sample_ode_adaptive(method="bosh3", rtol=1e-2, atol=1e-3, max_attempts=1, **grid)(x, m.forward, kw),
+    }
+
+    def all_off():
+        h = m.handle()
+        return {k: h.ws_options[k] for k in ("adaptive", "sde", "multistep")} == dict(adaptive=0, sde=0, multistep=0) and h._cfg is None
+
+    kept = []                                                              # every handle lives until the device is idle
+    try:
+        m._handle = None
+        got = []
+        for name in ("euler", "bosh3", "sde_heun", "multistep", "cfg_rk4", "failing", "euler"):
+            if name == "failing":
+                with pytest.raises(hip.VclozeHipError, match="max_attempts = 1"):
+                    calls[name]()
+            else:
+                got.append((name, calls[name]()))
+            assert all_off(), name
+        want = {}
+        for name in ("euler", "bosh3", "sde_heun", "multistep", "cfg_rk4"):
+            kept.append(m.handle())
+            m._handle = None                                               # m.handle() builds another one over the same prepared weights
+            want[name] = calls[name]()
+        kept.append(m.handle())
+        torch.cuda.synchronize()
+    finally:
+        m._handle = None                                                   # the module's model builds its own handle again
+    for name, out in got:
+        assert torch.isfinite(out.float()).all() and not torch.equal(out[-1], x), name
+        assert torch.equal(out, want[name]), name
+    assert torch.equal(got[-1][1], got[0][1])
+    finals = [want[name][-1] for name in want]
+    assert all(not torch.equal(a, b) for i, a in enumerate(finals) for b in finals[i + 1:])       # five different samplers
+
+
 def test_pipeline_passes_the_solver_through(model):
     """generate_grid(..., solver=) reaches Sampler.sample_ode through denoise_grid: rk4 runs end to end and is not Euler."""
     from tests.procedural import tiny_inputs

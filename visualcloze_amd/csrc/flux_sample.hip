@@ -78,6 +78,54 @@ int replay(Flux& f, hipStream_t s, Err e, int piece = 0) {
   return VC_OK;
 }
 
+// ---------------------------------------------------------------- what the solves with tables of their own share
+// the refusals: the entry point's workspace option is off or the workspace was prepared without it (`ready`: both hold), and the
+// monitor, whose log only a fixed-grid trajectory can index (`why`: the entry point's own sentence)
+int refuse_no_buffers(bool ready, const char* what, const char* option, const char* of_what, Err e) {
+  if (!ready)
+    FAIL(VC_ERR_STATE, "%s: set vc_flux_set_option(handle, \"%s\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
+                       "(the workspace holds no buffers of %s)", what, option, of_what);
+  return VC_OK;
+}
+int refuse_monitor(Flux& f, const char* what, Err e, const char* why = "its log is indexed by the evaluations of a fixed-grid trajectory") {
+  if (f.mon_level)
+    FAIL(VC_ERR_ARG, "%s: the monitor is on (level %d): %s; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", what, f.mon_level, why);
+  return VC_OK;
+}
+
+// a staged TS block from one model time per evaluation: tm[j] for each of the B samples of evaluation j
+void broadcast_times(const Flux& f, const float* tm, int evals, float* ts) {
+  for (int j = 0; j < evals; ++j)
+    for (int b = 0; b < f.B; ++b) ts[(size_t)j * f.B + b] = tm[j];
+}
+
+// the tail of vc_flux_sample_sde and vc_flux_sample_multistep behind their checks and their plan: the staged tables go out - TS,
+// filled here from the plan's `times`, then the solver's own `tabs` (device address, staged copy, bytes) -, the trajectory begins,
+// `ahead()` issues what stands in front of the first evaluation, the n_evals evaluations replay and x receives the f32 state Y.
+// With a trajectory buffer, row_after(j) names the row that receives Y behind evaluation j - j = -1: ahead of the first one,
+// j = n_evals: behind them all once more - or -1 for none.
+template <class Ahead, class RowAfter>
+int run_tables(Flux& f, int solver, const float* Y, const float* times, float* ts, std::initializer_list<std::tuple<void*, const void*, size_t>> tabs,
+               int n_evals, void* x, int state_is_bf16, const void* cond, void* trajectory, Ahead ahead, RowAfter row_after, hipStream_t s, Err e) {
+  const int64_t n = (int64_t)f.B * f.N * f.cfg.out_channels, out_bytes = n * (state_is_bf16 ? 2 : 4);
+  auto store = [&](int row) {
+    return trajectory && row >= 0 ? vc_sde_store_launch(Y, (char*)trajectory + row * out_bytes, state_is_bf16 != 0, n, s, e.buf, e.len) : VC_OK;
+  };
+  broadcast_times(f, times, n_evals, ts);
+  end_trajectory(f);
+  TRY(stage_send(f, f.TS, ts, (size_t)n_evals * f.B * sizeof(float), s, e.buf, e.len));
+  for (auto [dev, staged, bytes] : tabs) TRY(stage_send(f, dev, staged, bytes, s, e.buf, e.len));
+  TRY(stage_end(f, s, e.buf, e.len));
+  TRY(time_precompute(f, n_evals, 0, s, e.buf, e.len));
+  TRY(begin_trajectory(f, solver, x, state_is_bf16, cond, s, e));
+  TRY(ahead());
+  for (int j = -1; j <= n_evals; ++j) {
+    if (j >= 0 && j < n_evals) TRY(replay(f, s, e));
+    TRY(store(row_after(j)));
+  }
+  return vc_sde_store_launch(Y, x, state_is_bf16 != 0, n, s, e.buf, e.len);
+}
+
 }  // namespace
 }  // namespace vcflux
 using namespace vcflux;
@@ -176,8 +224,7 @@ static int rk_rows(Flux& f, int method, double t, double dt, hipStream_t s, Err 
   float* hdt = stage_take<float>(f, 1);
   float tm[7];
   vcrules::rk_row_times(method, t, dt, tm);
-  for (int j = 0; j < S; ++j)
-    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = tm[j];
+  broadcast_times(f, tm, S, ts);
   *hdt = (float)dt;
   TRY(stage_send(f, f.TS, ts, (size_t)S * B * sizeof(float), s, e.buf, e.len));
   TRY(stage_send(f, f.AD_DT, hdt, sizeof(float), s, e.buf, e.len));
@@ -266,12 +313,8 @@ static int rk_solve(Flux& f, const char* what, int method, void* x, const void* 
                     float rtol, float atol, int max_attempts, void* trajectory, hipStream_t s, Err e) {
   const int S = vcrules::rk_stages(method);
   TRY(refuse_unready(f, what, x, cond, t_grid, e));
-  if (f.mon_level)
-    FAIL(VC_ERR_ARG, "%s: the monitor is on (level %d): the adaptive solve's device-side counter is the stage of an attempt, not "
-                     "an evaluation index; turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", what, f.mon_level);
-  if (!f.opt.adaptive || !f.AD_K)
-    FAIL(VC_ERR_STATE, "%s: set vc_flux_set_option(handle, \"adaptive\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
-                       "(the workspace holds no buffers of the adaptive solve)", what);
+  TRY(refuse_monitor(f, what, e, "the adaptive solve's device-side counter is the stage of an attempt, not an evaluation index"));
+  TRY(refuse_no_buffers(f.opt.adaptive && f.AD_K, what, "adaptive", "the adaptive solve", e));
   if (f.S < S) {                                // (each entry point's own wording)
     if (method == VC_RK_DOPRI5) FAIL(VC_ERR_ARG, "%s: the workspace was prepared with max_steps = %d, the adaptive solve needs 7", what, f.S);
     FAIL(VC_ERR_ARG, "%s: the workspace was prepared with max_steps = %d, method %d needs %d", what, f.S, method, S);
@@ -333,12 +376,8 @@ int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const voi
   HANDLE(Flux, f, "flux");
   // ---- every check before the device is touched
   TRY(refuse_unready(f, "flux_sample_sde", x, cond, t_grid, e));
-  if (!f.opt.sde || !f.SD_Y)
-    FAIL(VC_ERR_STATE, "flux_sample_sde: set vc_flux_set_option(handle, \"sde\", 1) before vc_flux_workspace_bytes / vc_flux_prepare "
-                       "(the workspace holds no buffers of the stochastic sampler)");
-  if (f.mon_level)
-    FAIL(VC_ERR_ARG, "flux_sample_sde: the monitor is on (level %d): its log is indexed by the evaluations of a fixed-grid trajectory; turn it "
-                     "off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
+  TRY(refuse_no_buffers(f.opt.sde && f.SD_Y, "flux_sample_sde", "sde", "the stochastic sampler", e));
+  TRY(refuse_monitor(f, "flux_sample_sde", e));
   TRY(refuse_cache(f, "flux_sample_sde", NO_SOLVER_CODE, e));
   int32_t n_evals = 0, n_draws = 0;
   TRY(vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, nullptr, nullptr, 0, &n_evals, &n_draws, err, errlen));
@@ -352,8 +391,7 @@ int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const voi
     FAIL(VC_ERR_ARG, "flux_sample_sde: offset + draws * n leaves the 64-bit stream position (offset=%llu, %d draws of %lld elements)",
          (unsigned long long)offset, n_draws, (long long)n);
   const bool heun = !strcmp(method, "Heun");
-  const int n_rows = n_evals + (heun ? 1 : 0), E = heun ? 2 : 1, out_bf16 = state_is_bf16 != 0;
-  const int64_t out_bytes = n * (out_bf16 ? 2 : 4);
+  const int n_rows = n_evals + (heun ? 1 : 0), E = heun ? 2 : 1;
   // ---- the tables of the whole trajectory: model times, coefficient rows, the stream's seed and offset
   TRY(stage_begin(f, ((size_t)n_evals * B + (size_t)n_rows * VC_SDE_ROW + n_evals) * sizeof(float) + 2 * sizeof(uint64_t) + 4 * 256, e.buf, e.len));
   float* ts = stage_take<float>(f, (size_t)n_evals * B);
@@ -361,26 +399,16 @@ int vc_flux_sample_sde_impl(void* handle, const char* method, void* x, const voi
   float* times = stage_take<float>(f, n_evals);
   uint64_t* words = stage_take<uint64_t>(f, 2);
   TRY(vc_sde_plan_impl(method, form, norm, last_step, last_step_size, t_grid, n_points, rows, times, n_rows, nullptr, nullptr, err, errlen));
-  for (int j = 0; j < n_evals; ++j)
-    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = times[j];
   words[0] = seed; words[1] = offset;
-  end_trajectory(f);
-  TRY(stage_send(f, f.TS, ts, (size_t)n_evals * B * sizeof(float), s, e.buf, e.len));
-  TRY(stage_send(f, f.SD_TAB, rows, (size_t)n_rows * VC_SDE_ROW * sizeof(float), s, e.buf, e.len));
-  TRY(stage_send(f, f.SD_RNG, words, 2 * sizeof(uint64_t), s, e.buf, e.len));
-  TRY(stage_end(f, s, e.buf, e.len));
-  TRY(time_precompute(f, n_evals, 0, s, e.buf, e.len));
-  TRY(begin_trajectory(f, heun ? SOLVER_SDE_HEUN : SOLVER_SDE_EULER, x, state_is_bf16, cond, s, e));
   // Heun: draw 0 goes in ahead of the first evaluation (the row behind the evaluations' rows)
-  if (heun) TRY(vc_sde_stage_launch(n_evals, f.SD_TAB, f.S + 1, f.SD_Y, nullptr, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, nullptr, n, s, e.buf, e.len));
-  for (int j = 0; j < n_evals; ++j) {
-    TRY(replay(f, s, e));
-    // x' after every loop step; the last step's result (or, without one, x' again) as the final row
-    const bool step_done = j < (n_points - 1) * E && (j + 1) % E == 0;
-    if (trajectory && step_done) TRY(vc_sde_store_launch(f.SD_Y, (char*)trajectory + (int64_t)(j / E) * out_bytes, out_bf16, n, s, e.buf, e.len));
-  }
-  if (trajectory) TRY(vc_sde_store_launch(f.SD_Y, (char*)trajectory + (int64_t)(n_points - 1) * out_bytes, out_bf16, n, s, e.buf, e.len));
-  return vc_sde_store_launch(f.SD_Y, x, out_bf16, n, s, e.buf, e.len);
+  auto inject = [&] {
+    return heun ? vc_sde_stage_launch(n_evals, f.SD_TAB, f.S + 1, f.SD_Y, nullptr, f.YIN, f.SD_XHAT, f.SD_K1, f.SD_RNG, nullptr, n, s, e.buf, e.len) : VC_OK;
+  };
+  // x' after every loop step; the last step's result (or, without one, x' again) as the final row
+  auto row_after = [&](int j) { return j == n_evals ? n_points - 1 : j >= 0 && j < (n_points - 1) * E && (j + 1) % E == 0 ? j / E : -1; };
+  return run_tables(f, heun ? SOLVER_SDE_HEUN : SOLVER_SDE_EULER, f.SD_Y, times, ts,
+                    {{f.SD_TAB, rows, (size_t)n_rows * VC_SDE_ROW * sizeof(float)}, {f.SD_RNG, words, 2 * sizeof(uint64_t)}}, n_evals, x,
+                    state_is_bf16, cond, trajectory, inject, row_after, s, e);
 }
 
 // ---------------------------------------------------------------- the multistep solve (vcloze_hip.h: vc_flux_sample_multistep)
@@ -389,40 +417,24 @@ int vc_flux_sample_multistep_impl(void* handle, int32_t order, void* x, const vo
   HANDLE(Flux, f, "flux");
   // ---- every check before the device is touched
   TRY(refuse_unready(f, "flux_sample_multistep", x, cond, t_grid, e));
-  if (!f.opt.multistep || !f.MS_Y)
-    FAIL(VC_ERR_STATE, "flux_sample_multistep: set vc_flux_set_option(handle, \"multistep\", 1) before vc_flux_workspace_bytes / "
-                       "vc_flux_prepare (the workspace holds no buffers of the multistep solve)");
-  if (f.mon_level)
-    FAIL(VC_ERR_ARG, "flux_sample_multistep: the monitor is on (level %d): its log is indexed by the evaluations of a fixed-grid trajectory; "
-                     "turn it off with vc_flux_set_monitor(handle, 0, NULL, 0, NULL)", f.mon_level);
+  TRY(refuse_no_buffers(f.opt.multistep && f.MS_Y, "flux_sample_multistep", "multistep", "the multistep solve", e));
+  TRY(refuse_monitor(f, "flux_sample_multistep", e));
   TRY(refuse_cache(f, "flux_sample_multistep", NO_SOLVER_CODE, e));
   int32_t n_evals = 0;
   TRY(vc_ms_plan_impl(order, t_grid, n_points, nullptr, nullptr, 0, &n_evals, err, errlen));
   if (n_evals > f.S)
     FAIL(VC_ERR_ARG, "flux_sample_multistep: %d evaluations (%d points), the prepared workspace holds 1..%d evaluations", n_evals, n_points, f.S);
   TRY(refuse_cfg(f, "flux_sample_multistep", e));
-  const int B = f.B, out_bf16 = state_is_bf16 != 0;
-  const int64_t n = (int64_t)B * f.N * f.cfg.out_channels, out_bytes = n * (out_bf16 ? 2 : 4);
+  const int B = f.B;
   // ---- the tables of the whole trajectory: model times and coefficient rows
   TRY(stage_begin(f, ((size_t)n_evals * B + (size_t)n_evals * VC_MS_ROW + n_evals) * sizeof(float) + 3 * 256, e.buf, e.len));
   float* ts = stage_take<float>(f, (size_t)n_evals * B);
   float* rows = stage_take<float>(f, (size_t)n_evals * VC_MS_ROW);
   float* times = stage_take<float>(f, n_evals);
   TRY(vc_ms_plan_impl(order, t_grid, n_points, rows, times, n_evals, nullptr, err, errlen));
-  for (int j = 0; j < n_evals; ++j)
-    for (int b = 0; b < B; ++b) ts[(size_t)j * B + b] = times[j];
-  end_trajectory(f);
-  TRY(stage_send(f, f.TS, ts, (size_t)n_evals * B * sizeof(float), s, e.buf, e.len));
-  TRY(stage_send(f, f.MS_TAB, rows, (size_t)n_evals * VC_MS_ROW * sizeof(float), s, e.buf, e.len));
-  TRY(stage_end(f, s, e.buf, e.len));
-  TRY(time_precompute(f, n_evals, 0, s, e.buf, e.len));
-  TRY(begin_trajectory(f, SOLVER_MULTISTEP, x, state_is_bf16, cond, s, e));
-  if (trajectory) TRY(vc_sde_store_launch(f.MS_Y, trajectory, out_bf16, n, s, e.buf, e.len));
-  for (int j = 0; j < n_evals; ++j) {
-    TRY(replay(f, s, e));
-    if (trajectory) TRY(vc_sde_store_launch(f.MS_Y, (char*)trajectory + (int64_t)(j + 1) * out_bytes, out_bf16, n, s, e.buf, e.len));
-  }
-  return vc_sde_store_launch(f.MS_Y, x, out_bf16, n, s, e.buf, e.len);
+  // the start state as row 0, then the state after every step
+  return run_tables(f, SOLVER_MULTISTEP, f.MS_Y, times, ts, {{f.MS_TAB, rows, (size_t)n_evals * VC_MS_ROW * sizeof(float)}}, n_evals, x, state_is_bf16,
+                    cond, trajectory, [] { return VC_OK; }, [&](int j) { return j < n_evals ? j + 1 : -1; }, s, e);
 }
 
 int vc_flux_set_step_cache_impl(void* handle, float threshold, int32_t max_consecutive, char* err, int errlen) {

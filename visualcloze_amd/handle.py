@@ -147,10 +147,7 @@ class FluxHandle(_Handle):
         self._lora: Dict[str, tuple] = {}
         self._taps: Dict[str, torch.Tensor] = {}
         self.lora_mode = 0
-        self.adaptive = 0
-        self.sde = 0
-        self.eval_loss_on = 0
-        self.multistep = 0
+        self.ws_options = dict.fromkeys(self.WS_OPTIONS, 0)     # name -> 0 / 1 as last set (`set_ws_option`)
         if getattr(weights, "ref", None) is not None:       # un-merged weights: every pair next to its base weight
             scales = []
             for name, R in weights.ref.items():
@@ -351,37 +348,33 @@ class FluxHandle(_Handle):
             self._ws.clear()
             self.geom = None
 
-    def set_adaptive(self, on: bool) -> None:
-        """vc_flux_set_option("adaptive"): 1 = the workspace holds the buffers of the adaptive solve (`sample_dopri5`).  A switch needs
-        a new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
-        hip._check(hip.lib().vc_flux_set_option(self.h, b"adaptive", int(bool(on))), "vc_flux_set_option(adaptive)")
-        if int(bool(on)) != self.adaptive:
-            self.adaptive = int(bool(on))
+    # the workspace options: name -> what the workspace holds while the option is 1
+    WS_OPTIONS = {"adaptive": "the buffers of the adaptive solve (`sample_dopri5`, `sample_rk`)",
+                  "sde": "the buffers of the stochastic sampler (`sample_sde`)",
+                  "eval_loss": "u_t of the flow-matching loss (`eval_loss`)",
+                  "multistep": "the buffers of the Adams-Bashforth solve (`sample_multistep`)"}
+
+    def set_ws_option(self, name: str, on: bool) -> None:
+        """vc_flux_set_option(name) for a name of WS_OPTIONS: 1 = the workspace holds what the table says.  A switch needs a new prepare
+        (other workspace size); with it off nothing differs from a handle that never heard of it."""
+        if name not in self.WS_OPTIONS:
+            raise KeyError(f"set_ws_option: {name!r} is no workspace option ({sorted(self.WS_OPTIONS)})")
+        hip._check(hip.lib().vc_flux_set_option(self.h, name.encode(), int(bool(on))), f"vc_flux_set_option({name})")
+        if int(bool(on)) != self.ws_options[name]:
+            self.ws_options[name] = int(bool(on))
             self.geom = None
+
+    def set_adaptive(self, on: bool) -> None:
+        self.set_ws_option("adaptive", on)
 
     def set_sde(self, on: bool) -> None:
-        """vc_flux_set_option("sde"): 1 = the workspace holds the buffers of the stochastic sampler (`sample_sde`).  A switch needs a
-        new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
-        hip._check(hip.lib().vc_flux_set_option(self.h, b"sde", int(bool(on))), "vc_flux_set_option(sde)")
-        if int(bool(on)) != self.sde:
-            self.sde = int(bool(on))
-            self.geom = None
+        self.set_ws_option("sde", on)
 
     def set_eval_loss(self, on: bool) -> None:
-        """vc_flux_set_option("eval_loss"): 1 = the workspace holds u_t of the flow-matching loss (`eval_loss`).  A switch needs a new
-        prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
-        hip._check(hip.lib().vc_flux_set_option(self.h, b"eval_loss", int(bool(on))), "vc_flux_set_option(eval_loss)")
-        if int(bool(on)) != self.eval_loss_on:
-            self.eval_loss_on = int(bool(on))
-            self.geom = None
+        self.set_ws_option("eval_loss", on)
 
     def set_multistep(self, on: bool) -> None:
-        """vc_flux_set_option("multistep"): 1 = the workspace holds the buffers of the Adams-Bashforth solve (`sample_multistep`).  A
-        switch needs a new prepare (other workspace size); with it off nothing differs from a handle that never heard of it."""
-        hip._check(hip.lib().vc_flux_set_option(self.h, b"multistep", int(bool(on))), "vc_flux_set_option(multistep)")
-        if int(bool(on)) != self.multistep:
-            self.multistep = int(bool(on))
-            self.geom = None
+        self.set_ws_option("multistep", on)
 
     def plan_count(self) -> int:
         """vc_flux_plan_count: the captured steps the handle holds"""
@@ -445,8 +438,7 @@ class FluxHandle(_Handle):
         return {"computed": c.value, "reused": r.value, "metrics": [float(m[i]) for i in range(n)]}
 
     def workspace(self, B: int, T: int, N: int, S: int) -> torch.Tensor:
-        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + ((True,) if self.adaptive else ()) + (("sde",) if self.sde else ()) + \
-            (("eval_loss",) if self.eval_loss_on else ()) + (("multistep",) if self.multistep else ())
+        key = (B, T, N, S, self._step_cache[0] > 0 and self._step_cache[1] != 0) + tuple(k for k, on in self.ws_options.items() if on)
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) > 8:

@@ -905,6 +905,44 @@ def _classify(model: Callable, model_kwargs: dict):
     return owner, name, kw, float(kw.pop("cfg_scale", 1.0)) if name == "forward_with_cfg" else None
 
 
+def _route(model: Callable, model_kwargs: dict, x: torch.Tensor, method: str, step_cache: Optional[StepCache] = None):
+    """What a sampler method branches on, once: -> (owner, kw, cfg_scale, fused, eager).  owner, kw (without "cfg_scale") and cfg_scale
+    as `_classify`; fused: the fused loop of `owner` runs (`_fusable` / `_cfg_fusable`); eager: the callable stepped on the host
+    otherwise - the foreign callable itself, and for a visualcloze_amd.Flux its forward (true CFG: forward_with_cfg at cfg_scale) with
+    the velocity rounded to bf16, as the reference's is under autocast (visualcloze.py:363) whatever dtype Flux.forward hands back to
+    its caller.  method: a STEP_RULES name of the fixed grid - "euler" alone may run on the Python-ordered plan - or the family
+    "adaptive" / "sde" / "multistep", which needs the C handle.  step_cache (sample_ode's): never silently ignored - only the C
+    handle's Euler loop over Flux.forward implements it, every other route raises."""
+    owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
+    if kind == "foreign":
+        if step_cache is not None:
+            raise ValueError("step_cache: only the fused loop of a visualcloze_amd.Flux implements it, not a foreign callable")
+        return owner, kw, None, False, model
+    if kind == "forward_with_cfg":
+        if step_cache is not None:
+            raise ValueError("step_cache works with Flux.forward only, not with forward_with_cfg (true CFG)")
+        # eager: unequal image masks within a pair, no C handle, an f16 / f64 state
+        return (owner, kw, cfg_scale, _cfg_fusable(owner, x, method, kw),
+                lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k).to(torch.bfloat16))
+    fused = _fusable(owner, x, method)
+    if step_cache is not None:
+        if owner.handle() is None:
+            raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' (unless ref_plan='handle') "
+                             "or the Python-ordered plan (use_handle False)")
+        if not fused:
+            raise ValueError(f"step_cache: a {x.dtype} state is stepped eagerly, where no cache exists")
+    return owner, kw, None, fused, lambda xin, **k: model(xin, **k).to(torch.bfloat16)
+
+
+def _ode_interval(transport: Transport, reverse: bool, strength: Optional[float]):
+    """-> (t0, t1) of the three ODE methods: check_interval, the start moved by `strength`, forward time"""
+    t0, t1 = transport.check_interval(reverse=reverse)
+    if strength is not None:
+        t0 = (t1 - t0) * strength + t0
+    assert t0 < t1, "ODE sampler has to be in forward time"
+    return t0, t1
+
+
 class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
@@ -922,38 +960,14 @@ class Sampler:
                 raise TypeError(f"step_cache must be a StepCache or None, got {type(step_cache).__name__}")
             if sampling_method != "euler":
                 raise ValueError(f"step_cache works with sampling_method='euler' only, not {sampling_method!r}")
-        t0, t1 = self.transport.check_interval(reverse=reverse)
-        if strength is not None:
-            t0 = (t1 - t0) * strength + t0
-        assert t0 < t1, "ODE sampler has to be in forward time"
+        t0, t1 = _ode_interval(self.transport, reverse, strength)
 
         def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
-            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
-            if kind == "forward_with_cfg":
-                if step_cache is not None:
-                    raise ValueError("step_cache works with Flux.forward only, not with forward_with_cfg (true CFG)")
-                if _cfg_fusable(owner, x, sampling_method, kw):
-                    return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, None, self, cfg_scale=cfg_scale)
-                # stepped eagerly (unequal image masks within a pair, no C handle, an f16 / f64 state): the same bf16 velocity
-                fwd = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k).to(torch.bfloat16)  # noqa: E731
-                return _sample_foreign(fwd, x, kw, t, return_trajectory, sampling_method)
-            if kind == "forward":
-                if step_cache is not None:      # never silently ignored: only the C handle's loop implements it
-                    if owner.handle() is None:
-                        raise ValueError("step_cache needs the C handle: not available with lora_mode='ref' (unless ref_plan='handle') "
-                                         "or the Python-ordered plan (use_handle False)")
-                    if not _fusable(owner, x, sampling_method):
-                        raise ValueError(f"step_cache: a {x.dtype} state is stepped eagerly, where no cache exists")
-                if _fusable(owner, x, sampling_method):
-                    return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, step_cache, self)
-                # stepped eagerly; the velocity of this model is a bf16 tensor as the reference's is under autocast
-                # (visualcloze.py:363) whatever dtype Flux.forward hands back to its caller: dt * f stays a bf16 product
-                fwd = model
-                model = lambda xin, **k: fwd(xin, **k).to(torch.bfloat16)  # noqa: E731
-            elif step_cache is not None:
-                raise ValueError("step_cache: only the fused loop of a visualcloze_amd.Flux implements it, not a foreign callable")
-            return _sample_foreign(model, x, kw, t, return_trajectory, sampling_method)
+            owner, kw, cfg_scale, fused, eager = _route(model, model_kwargs, x, sampling_method, step_cache)
+            if fused:
+                return _sample_fused(owner, x, kw, t, return_trajectory, sampling_method, step_cache, self, cfg_scale=cfg_scale)
+            return _sample_foreign(eager, x, kw, t, return_trajectory, sampling_method)      # (dt * f stays a bf16 product for a Flux)
 
         return _sample
 
@@ -971,31 +985,20 @@ class Sampler:
         evaluations per attempt: 6 / 3 / 2.  Their controller is torchdiffeq's as recalled, unpinned against real torchdiffeq."""
         if method not in ADAPTIVE_METHODS:
             raise ValueError(f"sample_ode_adaptive: method {method!r}: one of {list(ADAPTIVE_METHODS)} expected")
-        t0, t1 = self.transport.check_interval(reverse=reverse)
-        if strength is not None:
-            t0 = (t1 - t0) * strength + t0
-        assert t0 < t1, "ODE sampler has to be in forward time"
+        t0, t1 = _ode_interval(self.transport, reverse, strength)
 
         def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
-            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
-            is_flux = kind != "foreign"
-            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
-            if fused and cfg_scale is not None:
-                fused = _cfg_fusable(owner, x, "euler", kw)
+            owner, kw, cfg_scale, fused, eager = _route(model, model_kwargs, x, "adaptive")
             if fused:
                 out, logs = _sample_adaptive_fused(owner, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale, method=method)
             else:
-                if cfg_scale is not None:
-                    model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
-                out, log = _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=is_flux,
-                                                    method=method)
+                out, log = _sample_adaptive_foreign(eager, x, kw, t, return_trajectory, rtol, atol, max_attempts, method=method)
                 logs = [log]
             self.last_adaptive_log = logs
             return out
 
         return _sample
-
 
     def sample_ode_multistep(self, *, order: int = 2, num_steps=50, reverse=False, do_shift=True, time_shifting_factor=None, strength=None,
                              return_trajectory: bool = False):
@@ -1010,23 +1013,14 @@ class Sampler:
         3 and 4 have small stability regions and no order is recommended; image quality at any order is unmeasured."""
         if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= MS_MAX_ORDER:
             raise ValueError(f"sample_ode_multistep: order = {order!r} outside 1..{MS_MAX_ORDER}")
-        t0, t1 = self.transport.check_interval(reverse=reverse)
-        if strength is not None:
-            t0 = (t1 - t0) * strength + t0
-        assert t0 < t1, "ODE sampler has to be in forward time"
+        t0, t1 = _ode_interval(self.transport, reverse, strength)
 
         def _sample(x: torch.Tensor, model: Callable, model_kwargs: dict) -> torch.Tensor:
             t = solver_time_grid(num_steps, x.shape[1], t0, t1, do_shift, time_shifting_factor)
-            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
-            is_flux = kind != "foreign"
-            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
-            if fused and cfg_scale is not None:
-                fused = _cfg_fusable(owner, x, "euler", kw)
+            owner, kw, cfg_scale, fused, eager = _route(model, model_kwargs, x, "multistep")
             if fused:
                 return _sample_multistep_fused(owner, x, kw, t, order, return_trajectory, cfg_scale)
-            if cfg_scale is not None:
-                model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
-            return _sample_multistep_foreign(model, x, kw, t, order, return_trajectory, bf16_out=is_flux)
+            return _sample_multistep_foreign(eager, x, kw, t, order, return_trajectory)
 
         return _sample
 
@@ -1060,11 +1054,7 @@ class Sampler:
 
         def _sample(init: torch.Tensor, model: Callable, **model_kwargs) -> torch.Tensor:
             x = init
-            owner, kind, kw, cfg_scale = _classify(model, model_kwargs)
-            is_flux = kind != "foreign"
-            fused = is_flux and owner.handle() is not None and x.dtype in (torch.bfloat16, torch.float32)
-            if fused and cfg_scale is not None:
-                fused = _cfg_fusable(owner, x, "euler", kw)
+            owner, kw, cfg_scale, fused, eager = _route(model, model_kwargs, x, "sde")
             total = plan["draws"] * x.numel()
             if rng is not None:
                 if hasattr(rng, "threads_per_sm"):            # a pipeline.TorchNoiseStream: its offset counts Philox outputs, not elements
@@ -1080,9 +1070,7 @@ class Sampler:
             if fused:
                 out = _sample_sde_fused(owner, x, kw, t, plan, setting, seed, offset, return_trajectory, cfg_scale)
             else:
-                if cfg_scale is not None:
-                    model = lambda xin, **k: owner.forward_with_cfg(xin, cfg_scale=cfg_scale, **k)  # noqa: E731
-                out = _sample_sde_foreign(model, x, kw, plan, seed, offset, return_trajectory, bf16_out=is_flux)
+                out = _sample_sde_foreign(eager, x, kw, plan, seed, offset, return_trajectory)
             if rng is not None:
                 rng.offset = offset + total
             return out
@@ -1090,81 +1078,63 @@ class Sampler:
         return _sample
 
 
-def _sample_multistep_foreign(model, x, kw, t, order, return_trajectory, bf16_out=False):
-    """Any callable: transport.multistep_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
-    drift = _adaptive_drift(model, x, kw, bf16_out)
-    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
-    with torch.no_grad():
-        out = multistep_integrate(drift, y0, t.to(torch.float32), order).to(x.dtype)
+def _times_as_state(ti, y):
+    """the fixed grid's `timesteps` (transport.py:193-198,384): ones(B) * t with t a 0-dim tensor rounded to the state's dtype, then 1 - t"""
+    tt = torch.ones(y.size(0), device=y.device) * _solver_t_as_state(ti, y)
+    return torch.ones_like(tt) * (1 - tt)
+
+
+def _times_f32(t, y):
+    """`timesteps` = 1 - f32(t) for a Python-float t, the f32 subtraction (vcloze_hip.h: the adaptive and the multistep solve)"""
+    tm = torch.tensor(1.0) - torch.tensor(t, dtype=torch.float64).to(torch.float32)
+    return torch.ones(y.size(0), device=y.device) * tm.to(y.device)
+
+
+def _times_tau(tau, y):
+    """`timesteps` = the model time tau the stochastic sampler's plan holds (a Python float)"""
+    return torch.ones(y.size(0), device=y.device) * tau
+
+
+def _drift(model, dtype, kw, times, sign=-1, bf16_out=False, solver="ODE"):
+    """f(t, y) = sign * model(y in `dtype` || cond, timesteps = times(t, y), **kw) - THE drift of every eager solve; what differs
+    between them is the dtype the model sees the state in (the caller's; None: the solver's own, as it comes), the sign (the
+    stochastic sampler takes the model's output itself), how the solver's time becomes `timesteps` (`_times_*`) and whether the
+    output is rounded to bf16 (bf16_out: a Flux velocity that `_route` has not rounded)"""
+    cond = kw.pop("cond", None)
+
+    def f(t, y):
+        ym = y if dtype is None else y.to(dtype)
+        xin = torch.cat((ym, cond), dim=-1) if cond is not None else ym
+        v = model(xin, timesteps=times(t, y), **kw)
+        assert v.shape == y.shape, f"Output shape from {solver} solver must match input shape"
+        v = v.to(torch.bfloat16) if bf16_out else v
+        return -v if sign < 0 else v
+    return f
+
+
+def _sample_eager(x, return_trajectory, integrate):
+    """What the eager adaptive, stochastic and multistep solves share: integrate(y0) -> [rows, ...] on the whole batch with the state
+    in f32 (f64 for an f64 caller), rounded once per output; the whole trajectory or its last row"""
+    out = integrate(x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)).to(x.dtype)
     return out if return_trajectory else out[-1:]
 
 
-@torch.no_grad()
-def _sample_multistep_fused(flux, x, kw, t, order, return_trajectory, cfg_scale=None):
-    """vc_flux_sample_multistep per chunk of samples"""
-    h = flux.handle()
-    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_multistep refuses it)
-        raise ValueError("monitor: the multistep solve is not logged; set Flux.monitor = 0 or use a fixed-grid solver")
-    t32 = t.to(torch.float32)
-
-    def run(xs, cond, tj, s):
-        h.sample_multistep(order, xs, cond, t32, x.dtype == torch.bfloat16, s, trajectory=tj)
-
-    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, len(t) - 1, run, cfg_scale=cfg_scale, multistep=True)
+def _sample_multistep_foreign(model, x, kw, t, order, return_trajectory, bf16_out=False):
+    """Any callable: transport.multistep_integrate through `_sample_eager`"""
+    drift = _drift(model, x.dtype, kw, _times_f32, bf16_out=bf16_out)
+    return _sample_eager(x, return_trajectory, torch.no_grad()(lambda y0: multistep_integrate(drift, y0, t.to(torch.float32), order)))
 
 
 def _sample_sde_foreign(model, x, kw, plan, seed, offset, return_trajectory, bf16_out=False):
-    """Any callable: transport.sde_integrate on the whole batch, the state in f32 (f64 for an f64 caller), rounded once per output"""
-    cond = kw.pop("cond", None)
-
-    def f(tau, y):
-        ym = y.to(x.dtype)
-        xin = torch.cat((ym, cond), dim=-1) if cond is not None else ym
-        v = model(xin, timesteps=torch.ones(y.size(0), device=y.device) * tau, **kw)
-        assert v.shape == y.shape, "Output shape from SDE solver must match input shape"
-        return v.to(torch.bfloat16) if bf16_out else v
+    """Any callable: transport.sde_integrate through `_sample_eager`"""
+    f = _drift(model, x.dtype, kw, _times_tau, sign=1, bf16_out=bf16_out, solver="SDE")
 
     def noise(d, shape):
         if not x.is_cuda:
             return torch.randn(shape, dtype=torch.float32)
         return hip.randn(tuple(shape), seed, offset + d * x.numel(), dtype=torch.float32, device=x.device)
 
-    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
-    with torch.no_grad():
-        out = sde_integrate(f, y0, plan, noise).to(x.dtype)
-    return out if return_trajectory else out[-1:]
-
-
-@torch.no_grad()
-def _sample_sde_fused(flux, x, kw, t, plan, setting, seed, offset, return_trajectory, cfg_scale=None):
-    """vc_flux_sample_sde per chunk of samples; a chunk's draws follow the last chunk's in the stream"""
-    h = flux.handle()
-    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_sde refuses it)
-        raise ValueError("monitor: the stochastic sampler is not logged; set Flux.monitor = 0 or use a fixed-grid solver")
-    method, form, norm, last_step, lss = setting
-    t32 = t.to(torch.float32)
-    pos = [offset]
-
-    def run(xs, cond, tj, s):
-        h.sample_sde(method, xs, cond, t32, x.dtype == torch.bfloat16, s, form=form, norm=norm, last_step=last_step, last_step_size=lss,
-                     seed=seed, offset=pos[0], trajectory=tj)
-        pos[0] += plan["draws"] * xs.numel()
-
-    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, plan["evals"], run, cfg_scale=cfg_scale, sde=True)
-
-
-def _adaptive_drift(model, x, kw, bf16_out: bool):
-    """f(t, y) = -model(y in the caller's dtype || cond, timesteps = 1 - f32(t)) for a Python-float t (vcloze_hip.h)"""
-    cond = kw.pop("cond", None)
-
-    def f(t, y):
-        tm = torch.tensor(1.0) - torch.tensor(t, dtype=torch.float64).to(torch.float32)        # the f32 subtraction
-        ym = y.to(x.dtype)
-        xin = torch.cat((ym, cond), dim=-1) if cond is not None else ym
-        v = model(xin, timesteps=torch.ones(y.size(0), device=y.device) * tm.to(y.device), **kw)
-        assert v.shape == y.shape, "Output shape from ODE solver must match input shape"
-        return -(v.to(torch.bfloat16) if bf16_out else v)
-    return f
+    return _sample_eager(x, return_trajectory, torch.no_grad()(lambda y0: sde_integrate(f, y0, plan, noise)))
 
 
 def _log_dict(attempts, evaluations):
@@ -1173,16 +1143,15 @@ def _log_dict(attempts, evaluations):
 
 def _sample_adaptive_foreign(model, x, kw, t, return_trajectory, rtol, atol, max_attempts, bf16_out=False, forced_dts=None,
                              on_attempt=None, method="dopri5"):
-    """Any callable: transport.dopri5_integrate (method "dopri5") or rk_integrate on the whole batch, the state in f32 (f64 for an f64
-    caller), rounded once per output"""
+    """Any callable: transport.dopri5_integrate (method "dopri5") or rk_integrate through `_sample_eager` (not under no_grad, as ever)"""
     calls = []
-    drift = _adaptive_drift(model, x, kw, bf16_out)
+    drift = _drift(model, x.dtype, kw, _times_f32, bf16_out=bf16_out)
     f = lambda tt, y: (calls.append(tt), drift(tt, y))[1]  # noqa: E731
-    y0 = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
     log = []
     tab = _DOPRI5 if method == "dopri5" else _rk_tableau(method, solve=True)
-    out = _rk_integrate(tab, f, y0, t.to(torch.float32), rtol, atol, max_attempts, forced_dts, log, on_attempt).to(x.dtype)
-    return (out if return_trajectory else out[-1:]), _log_dict(log, len(calls))
+    out = _sample_eager(x, return_trajectory,
+                        lambda y0: _rk_integrate(tab, f, y0, t.to(torch.float32), rtol, atol, max_attempts, forced_dts, log, on_attempt))
+    return out, _log_dict(log, len(calls))
 
 
 @contextmanager
@@ -1207,24 +1176,22 @@ def _solve_begin(flux, x, kw, S, return_trajectory, pairs=False):
     return plan, cond, out, torch.empty(S, B, N, C, dtype=x.dtype, device=plan.dev) if return_trajectory else None
 
 
-def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, adaptive=False, sde=False,
-                     multistep=False):
+def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_cache=None, cfg_scale=None, buffers=None,
+                     prepend_start=True):
     """What the fused solves through the C handle share.  Per trajectory: the options, taken back on failure too.  Per chunk of samples
     (true CFG: whole pairs (j, j + B/2), conditional samples first): vc_flux_prepare for `max_evals` evaluations, a copy of the state's
     rows in kernel order for run(xs, cond rows, trajectory buffer [S, bs, N, C] or None, stream) to advance in place, and the way back.
-    sde: the stochastic sampler's option, and its trajectory as it stands (S rows that end with the sample; no start state in front).
-    multistep: the multistep solve's option, and its trajectory as it stands (S rows that begin with the start state)."""
+    buffers: the workspace option the solve needs (a name of `FluxHandle.WS_OPTIONS`, None for the fixed grid).  The trajectory
+    buffer has S rows; prepend_start: the start state goes in front of them (the fixed grid's and the adaptive solve's rows are the
+    states after it) - False: the rows stand as the entry point wrote them (the stochastic sampler's S rows end with the sample, the
+    multistep solve's begin with the start state)."""
     plan, cond, out, traj = _solve_begin(flux, x, kw, S, return_trajectory, pairs=cfg_scale is not None)
     with _on_capture_stream(flux.plan().stream) as s:
         try:
             h.set_step_cache(step_cache)           # None: off, whatever an earlier trajectory on this handle ran with
             h.set_cfg(cfg_scale)
-            if adaptive:
-                h.set_adaptive(True)
-            if sde:
-                h.set_sde(True)
-            if multistep:
-                h.set_multistep(True)
+            if buffers is not None:
+                h.set_ws_option(buffers, True)
             for sl in plan.chunks:
                 h.prepare(*plan.prepare_args(sl, max_evals), stream=s)
                 xs = plan.img_rows(x, sl, x.dtype, copy=True)       # stepped in ITS dtype, in place: never the caller's
@@ -1234,26 +1201,58 @@ def _solve_on_handle(flux, h, x, kw, S, return_trajectory, max_evals, run, step_
                     traj[:, sl] = torch.stack([plan.img_back(tj[i], sl) for i in range(S)])
                 out[sl] = plan.img_back(xs, sl)
         finally:
-            if adaptive:
-                h.set_adaptive(False)              # a later fixed-grid trajectory sizes its workspace as it always did
-            if sde:
-                h.set_sde(False)
-            if multistep:
-                h.set_multistep(False)
+            if buffers is not None:
+                h.set_ws_option(buffers, False)    # a later fixed-grid trajectory sizes its workspace as it always did
             if cfg_scale is not None:
                 h.set_cfg(None)                    # a later trajectory driven on this handle directly is a plain one again
-    if (sde or multistep) and traj is not None:
-        return traj
-    return out[None] if traj is None else torch.cat((x.to(out.device)[None], traj), dim=0)
+    if traj is None:
+        return out[None]
+    return torch.cat((x.to(out.device)[None], traj), dim=0) if prepend_start else traj
+
+
+def _unmonitored_handle(flux, why: str):
+    """the C handle of a solve the monitor cannot log: never silently ignored (the entry points refuse it too)"""
+    h = flux.handle()
+    if flux.monitor_level(h):
+        raise ValueError(f"monitor: {why}; set Flux.monitor = 0 or use a fixed-grid solver")
+    return h
+
+
+@torch.no_grad()
+def _sample_multistep_fused(flux, x, kw, t, order, return_trajectory, cfg_scale=None):
+    """vc_flux_sample_multistep per chunk of samples"""
+    h = _unmonitored_handle(flux, "the multistep solve is not logged")
+    t32 = t.to(torch.float32)
+
+    def run(xs, cond, tj, s):
+        h.sample_multistep(order, xs, cond, t32, x.dtype == torch.bfloat16, s, trajectory=tj)
+
+    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, len(t) - 1, run, cfg_scale=cfg_scale, buffers="multistep",
+                            prepend_start=False)
+
+
+@torch.no_grad()
+def _sample_sde_fused(flux, x, kw, t, plan, setting, seed, offset, return_trajectory, cfg_scale=None):
+    """vc_flux_sample_sde per chunk of samples; a chunk's draws follow the last chunk's in the stream"""
+    h = _unmonitored_handle(flux, "the stochastic sampler is not logged")
+    method, form, norm, last_step, lss = setting
+    t32 = t.to(torch.float32)
+    pos = [offset]
+
+    def run(xs, cond, tj, s):
+        h.sample_sde(method, xs, cond, t32, x.dtype == torch.bfloat16, s, form=form, norm=norm, last_step=last_step, last_step_size=lss,
+                     seed=seed, offset=pos[0], trajectory=tj)
+        pos[0] += plan["draws"] * xs.numel()
+
+    return _solve_on_handle(flux, h, x, kw, len(t), return_trajectory, plan["evals"], run, cfg_scale=cfg_scale, buffers="sde",
+                            prepend_start=False)
 
 
 @torch.no_grad()
 def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_attempts, cfg_scale=None, method="dopri5"):
     """vc_flux_sample_dopri5 (method "dopri5") or vc_flux_sample_rk per chunk of samples: ONE step size per chunk, so a sample's result
     depends on its chunk's other samples"""
-    h = flux.handle()
-    if flux.monitor_level(h):      # never silently ignored (vc_flux_sample_dopri5 refuses it: its counter is a stage, not an evaluation)
-        raise ValueError("monitor: the adaptive solve has no evaluation index to log under; set Flux.monitor = 0 or use a fixed-grid solver")
+    h = _unmonitored_handle(flux, "the adaptive solve has no evaluation index to log under")     # (its counter is a stage of an attempt)
     t32 = t.to(torch.float32)
     logs = []
 
@@ -1265,7 +1264,7 @@ def _sample_adaptive_fused(flux, x, kw, t, return_trajectory, rtol, atol, max_at
             logs.append(h.dopri5_log())            # one log serves both entry points: the last adaptive solve's
 
     stages = len(RK_TABLEAUS[method]["c"])         # the modulation rows of one attempt
-    return _solve_on_handle(flux, h, x, kw, len(t) - 1, return_trajectory, stages, run, cfg_scale=cfg_scale, adaptive=True), logs
+    return _solve_on_handle(flux, h, x, kw, len(t) - 1, return_trajectory, stages, run, cfg_scale=cfg_scale, buffers="adaptive"), logs
 
 
 def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
@@ -1274,7 +1273,8 @@ def _fusable(flux, x: torch.Tensor, method: str = "euler") -> bool:
     parity mode where its plan is ordered from Python, ref_plan="python") is stepped eagerly through Flux.forward with torch's own promotion rules:
     never a silent per-step rounding of the caller's state.  The Python-ordered plan (engine.py: use_handle False, or the
     un-merged LoRA parity mode lora_mode="ref" unless ref_plan="handle") knows the Euler update only: "midpoint" / "rk4" without the C handle are
-    stepped eagerly too, one Flux.forward per stage through `_sample_foreign`."""
+    stepped eagerly too, one Flux.forward per stage through `_sample_foreign` - and so are the solves that are no fixed grid (method:
+    `_route`'s family name "adaptive" / "sde" / "multistep"), through their own eager runners."""
     if method != "euler" and flux.handle() is None:
         return False
     if x.dtype == torch.bfloat16:
@@ -1321,17 +1321,11 @@ def model_times(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 
 
 def _sample_foreign(model, x, kw, t, return_trajectory, method="euler"):
-    """Any other callable: the same grid and step rule (STEP_RULES), one host-driven call per evaluation."""
-    cond = kw.pop("cond", None)
+    """Any other callable: the same grid and step rule (STEP_RULES), one host-driven call per evaluation.  Not through
+    `_sample_eager`, on purpose: this is the reference's own stepping, the state in the CALLER's dtype under torch's promotion rules
+    with 0-dim tensor times, where the other eager solves keep an f32 / f64 state and round once per output."""
     rule = STEP_RULES[method]
-
-    def f(ti, y):            # the drift the reference builds (transport.py:193-198,384), ti a 0-dim f32 tensor
-        tt = torch.ones(y.size(0), device=y.device) * _solver_t_as_state(ti, y)
-        xin = torch.cat((y, cond), dim=-1) if cond is not None else y
-        v = model(xin, timesteps=torch.ones_like(tt) * (1 - tt), **kw)
-        assert v.shape == y.shape, "Output shape from ODE solver must match input shape"
-        return -v
-
+    f = _drift(model, None, kw, _times_as_state)      # the drift the reference builds (transport.py:193-198,384), ti a 0-dim f32 tensor
     t = t.to(x.device)       # as integrators.py:113: t0, t1 and dt are 0-dim tensors on the state's device
     states = [x]
     for i in range(len(t) - 1):
